@@ -59,7 +59,13 @@ def parse_args(argv=None):
     ap.add_argument("--graph", action="store_true", help="--workload infer only: replay the forward as one hipGraph")
     ap.add_argument("--workload", choices=["train", "infer"], default="train",
                     help="train: BASELINE configs[2] (the metric, default); infer: configs[1], eval-mode forward only")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float32, at most 64 MB in "
+                         "all; see dump_outputs), so that two builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -269,6 +275,39 @@ def parity_vs_reference(dev, dtype):
     return out
 
 
+# --dump-outputs: an array of up to DUMP_WHOLE_MAX elements is written whole (the batch-32 prediction has 4.4 M); a larger one -- the
+# ~31 M-entry parameter, gradient and EMA arenas -- as DUMP_SAMPLE of its entries.  The metric's train step writes 43 MB.
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_WHOLE_MAX = 1 << 23
+DUMP_SAMPLE = 1 << 21
+
+
+def host_outputs(tensors):
+    """name -> host float32 array.  A flattened, fixed sample stands in for an array of more than DUMP_WHOLE_MAX elements: the
+    entries a generator seeded with 0 picks, in index order, so that every run of the same configuration keeps the same ones."""
+    import numpy as np
+    out = {}
+    for name, t in tensors.items():
+        a = t.detach().cpu().float().numpy()
+        if a.size > DUMP_WHOLE_MAX:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        out[name] = a
+    return out
+
+
+def dump_outputs(directory, arrays):
+    """Write every array as directory/<name>.npy; refuses (before writing anything) if they come to more than 64 MB."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total / 1e6:.1f} MB, more than {DUMP_LIMIT_BYTES / 1e6:.0f} MB")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    print("bench.py: wrote %s to %s (%.1f MB)" % (", ".join("%s%s" % (n, list(a.shape)) for n, a in arrays.items()), directory,
+                                                  total / 1e6), file=sys.stderr)
+
+
 class Leg:
     """One timed workload: model + step + synthetic batch resident in HBM."""
 
@@ -303,10 +342,24 @@ class Leg:
 
     def _infer(self):
         with self.torch.no_grad():
-            self.model(x=self.x)
+            return self.model(x=self.x)
 
-    def run(self, steps, warmup, barrier):
-        """W untimed steps, then exactly K steps between two barrier+synchronize; returns (seconds, kernel log, regions)."""
+    def outputs_of(self, last):
+        """What the step that returned `last` computed, as the tensors it left behind (--dump-outputs): the prediction and, for a
+        train step, the loss, the gradient, the updated parameters and EMA shadow, and the BatchNorm running statistics."""
+        if self.workload == "infer":
+            return {"prediction": last}
+        st = self.step
+        out = {"loss": last, "prediction": st._out, "grads": st.g_flat, "params": st.p_flat}
+        if st.ema_flat is not None:
+            out["ema_params"] = st.ema_flat
+        out["bn_running_stats"] = self.torch.cat([b.detach().reshape(-1).cpu() for _, b in self.model.named_buffers()
+                                                  if b.dtype == self.torch.float32])
+        return out
+
+    def run(self, steps, warmup, barrier, keep_outputs=False):
+        """W untimed steps, then exactly K steps between two barrier+synchronize; returns (seconds, kernel log, regions).
+        keep_outputs: copy what the K-th step computed to the host (self.outputs) before any further step runs."""
         for _ in range(warmup):
             self.one_step()
         barrier()
@@ -322,9 +375,10 @@ class Leg:
                 eng.wgrad_log = []
         t0 = time.perf_counter()
         for _ in range(steps):
-            self.one_step()
+            last = self.one_step()
         barrier()
         elapsed = time.perf_counter() - t0
+        self.outputs = host_outputs(self.outputs_of(last)) if keep_outputs else None
         self.logged_steps = steps
         if overlapped:
             self.logged_steps = min(steps, 5)
@@ -594,7 +648,10 @@ def main():
         return float(tab[:, 0].max()), [round(float(v), 3) for v in tab[:, 0] / args.steps * 1e3], comm
 
     leg = Leg(dev, rank, args.dtype, args.workload, B, pg=pg, sync_bn=args.sync_bn, graph=args.graph)
-    elapsed, klog, rlog = leg.run(args.steps, args.warmup, barrier)
+    elapsed, klog, rlog = leg.run(args.steps, args.warmup, barrier, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if leg.outputs is not None:
+        dump_outputs(args.dump_outputs, leg.outputs)
+        leg.outputs = None
     loss = float(leg.step.last_loss.item())
     elapsed, per_rank_ms, comm = over_ranks(elapsed, leg.comm(barrier))
     hbm = leg.inc_hbm(rlog) if rank == 0 else None

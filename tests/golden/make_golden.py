@@ -324,6 +324,21 @@ def g_dataset():
     save("gdataset.npz", **out)
 
 
+# ----------------------------------------------------------------------------- checkpoint layout
+def g_checkpoint():
+    """The reference UNet's freshly initialised state_dict (torch's default init, seeded), in its own key order, and the
+    order of its named_parameters: what tests/test_abi.py checks the drop-in module's checkpoint layout against."""
+    dims, seed = [8, 16, 32], 5
+    torch.manual_seed(seed)
+    net = UNet(n_channels=3, n_classes=1, layer_dimensions=dims)
+    sd = net.state_dict()
+    out = {"meta/dims": np.array(dims), "meta/seed": np.array(seed),
+           "meta/state_keys": np.array(list(sd.keys())),
+           "meta/param_names": np.array([k for k, _ in net.named_parameters()])}
+    out.update(pack("state", OrderedDict((k, v.detach().numpy().copy()) for k, v in sd.items())))
+    save("gref_checkpoint.npz", **out)
+
+
 if __name__ == "__main__":
     if "--only-proc" in sys.argv:
         g_proc()
@@ -331,8 +346,12 @@ if __name__ == "__main__":
     if "--only-dataset" in sys.argv:
         g_dataset()
         sys.exit(0)
+    if "--only-checkpoint" in sys.argv:
+        g_checkpoint()
+        sys.exit(0)
     g_proc()
     g_dataset()
+    g_checkpoint()
     g_ops()
     # G-tiny: both inits; 21x27 exercises H and W padding in Up (diff=1 both)
     g_net("gtiny_conditioned.npz", [4, 8, 16], 2, 21, 27, 101, "conditioned")
