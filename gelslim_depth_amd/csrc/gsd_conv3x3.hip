@@ -40,9 +40,9 @@ struct Conv3Params {
   int TH, TW, tiles_y, tiles_x, WR, WC, PS, NPV;
 };
 
-template <int WM, int WN, int NT>
-__global__ __launch_bounds__(256, NT == 4 ? 3 : 2) void conv3x3_dma_kernel(const Conv3Params P) {
-  constexpr int MT = 4;
+template <int WM, int WN>
+__global__ __launch_bounds__(256, 3) void conv3x3_dma_kernel(const Conv3Params P) {
+  constexpr int MT = 4, NT = 4;   // a wave's tile: MT x 16 output channels by NT x 16 pixels
   constexpr int BM = WM * 64;
   constexpr int WS = BM;             // unpadded rows: conflict-free for the ds_read_b128 A fetch (9*WS == 0 mod 64 banks)
   constexpr int WTILE = 36 * WS;     // floats per chunk
@@ -365,18 +365,15 @@ int plane_stride_16mod32(int n) {  // smallest PS >= n with PS % 32 == 16
 }
 
 struct ConvPlan {
-  bool wide;  // true: 64x256 block tile (M<=64), false: 128x128 or 128x256
-  bool big;   // 128x256 block tile (wave tile 64 x 128, 2 blocks per CU): tuning option, measured no faster than 128x128
+  bool wide;  // true: 64x256 block tile (M<=64), false: 128x128 (a 128x256 tile measured no faster)
   int BM, BN, WN, TH, TW, tiles_y, tiles_x, mblocks;
 };
 
 ConvPlan plan_conv3x3(int H, int W, int M) {
-  const int big_min = gsd_env_int("GSD_CONV_BIG", 0);   // tuning: min H*W for 128x256
   ConvPlan p;
   p.wide = M <= 64;
-  p.big = !p.wide && big_min > 0 && H * W >= big_min;
   p.BM = p.wide ? 64 : 128;
-  p.BN = (p.wide || p.big) ? 256 : 128;
+  p.BN = p.wide ? 256 : 128;
   p.WN = p.wide ? 4 : 2;
   choose_tile(H, W, p.BN, &p.TH, &p.TW);
   p.tiles_y = ceil_div(H, p.TH);
@@ -385,14 +382,14 @@ ConvPlan plan_conv3x3(int H, int W, int M) {
   return p;
 }
 
-template <int WM, int WN, int NT>
+template <int WM, int WN>
 int launch(const Conv3Params& P, int grid, size_t lds, hipStream_t st) {
   static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&conv3x3_dma_kernel<WM, WN, NT>)); e != hipSuccess) {
+  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&conv3x3_dma_kernel<WM, WN>)); e != hipSuccess) {
     gsd_set_error("gsd_conv3x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
     return GSD_ERR_HIP;
   }
-  hipLaunchKernelGGL((conv3x3_dma_kernel<WM, WN, NT>), dim3(grid), dim3(256), lds, st, P);
+  hipLaunchKernelGGL((conv3x3_dma_kernel<WM, WN>), dim3(grid), dim3(256), lds, st, P);
   GSD_LAUNCH_CHECK("gsd_conv3x3");
   return GSD_OK;
 }
@@ -416,7 +413,7 @@ extern "C" int gsd_conv3x3_algo(int N, int H, int W, int Cin, int Cout) {
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
   if (Cin < 16) return 0;   // a K loop of 1-3 chunks is all prologue + epilogue, and the Winograd epilogue is the longer one
   const ConvPlan p = plan_conv3x3(H, W, Cout);
-  const int64_t direct = (int64_t)N * p.tiles_y * p.tiles_x * p.mblocks * ceil_div(Cin, 4) * (p.big ? 1152 : 576);
+  const int64_t direct = (int64_t)N * p.tiles_y * p.tiles_x * p.mblocks * ceil_div(Cin, 4) * 576;
   const int64_t wino = gsd_conv3x3_w43_mfma_count(N, H, W, Cin, Cout);
   return wino > 0 && wino * 10 <= direct * 8 ? 1 : 0;
 }
@@ -467,12 +464,9 @@ static int conv3x3_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, 
   GSD_REQUIRE(P.NPV <= 8, GSD_ERR_UNSUPPORTED, "gsd_conv3x3: halo window too large");
   const long grid = (long)N * pl.tiles_y * pl.tiles_x * pl.mblocks;
   GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_conv3x3: grid too large");
-  size_t lds = (size_t)(2 * (36 * pl.BM + 4 * P.PS) + 2 * 4 * P.nchunks + 4 * pl.BM) * sizeof(float);   // 2 tile images + BN coefficients (input side, output side)
-  const int lds_min = gsd_env_int("GSD_CONV_LDS_MIN", 0);   // tuning: cap blocks/CU
-  if ((size_t)lds_min > lds) lds = lds_min;
-  if (pl.wide) return launch<1, 4, 4>(P, (int)grid, lds, (hipStream_t)stream);
-  if (pl.big) return launch<2, 2, 8>(P, (int)grid, lds, (hipStream_t)stream);
-  return launch<2, 2, 4>(P, (int)grid, lds, (hipStream_t)stream);
+  const size_t lds = (size_t)(2 * (36 * pl.BM + 4 * P.PS) + 2 * 4 * P.nchunks + 4 * pl.BM) * sizeof(float);   // 2 tile images + BN coefficients (input side, output side)
+  if (pl.wide) return launch<1, 4>(P, (int)grid, lds, (hipStream_t)stream);
+  return launch<2, 2>(P, (int)grid, lds, (hipStream_t)stream);
 }
 
 extern "C" int gsd_conv3x3(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst,

@@ -70,12 +70,13 @@ struct W2DParams {
 namespace {
 constexpr int W2D_BM = 64;
 constexpr int W2D_WTILE = 96 * W2D_BM;   // floats per weight chunk (24 KiB)
+constexpr int NWP = 2;                    // pixel groups of 16 tiles (128 pixels) per block
 }  // namespace
 
 // ---- epilogue (shared by the conv kernel and the K-slab reducer): a lane holds, per (m-tile, register) = channel, the 2 x 4 outputs
 // of its Winograd tile (get_y); NCHW stores (two destination segments with crop), BatchNorm partial sums, or the fused
 // BatchNorm-backward form.  sBw: the block's [4][64] coefficients of that form in LDS.
-template <int NWP, class GetY>
+template <class GetY>
 __device__ __forceinline__ void w2d_epilogue(const W2DParams& P, const float* sBw, const int n, const int h0, const int w0, const int tr2,
                                              const int tq, const int vmask, const int m0, const int mh, const int ph, const int j,
                                              const int l16, const int pt, GetY get_y) {
@@ -218,9 +219,8 @@ __device__ __forceinline__ void w2d_epilogue(const W2DParams& P, const float* sB
 }
 
 // PLAIN: no source segment carries a deferred BatchNorm or ReLU (every dX launch; the pooled / up-sampled sources of the forward)
-// NWP: pixel groups of 16 tiles (128 pixels) per block.  2: four waves, 64 channels x 256 pixels, two blocks per CU.  4: eight
-// waves, 64 x 512 pixels, one block per CU -- the 24-KiB weight chunk then feeds twice the MFMAs: with a third of the direct
-// form's multiplications the L2 -> LDS fills (30 KiB per 192 MFMAs in the four-wave form) are what the kernel waits for.
+// NWP = 2 pixel groups per block: four waves, 64 channels x 256 pixels, two blocks per CU (measured faster than one eight-wave
+// block of 64 x 512 pixels per CU, profiles/r05_w2d_vs_w43.txt).
 //
 // X4: the halo windows move as ALIGNED 16-byte pieces (global_load_lds_dwordx4) instead of dword gathers: a quarter of the halo's
 // DMA instructions (2 instead of 6 per channel plane of a 10 x 34 window), and the LDS-DMA issue -- 60-180 cycles an instruction --
@@ -241,7 +241,7 @@ __device__ __forceinline__ void w2d_epilogue(const W2DParams& P, const float* sB
 // 20 x 26 levels at small batches) is cut along the input channels; the output transform is linear, so each slab stores its own
 // Y = A2^T M A4 and w2d_slab_reduce_kernel adds the slabs in slab order and runs the epilogue.  A slab that starts inside the
 // second (concat) segment starts its fills there.
-template <bool PLAIN, int NWP, int HM = 0, bool SPLIT = false>
+template <bool PLAIN, int HM = 0, bool SPLIT = false>
 __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DParams P) {
   constexpr bool X4 = HM == 1, U4 = HM == 2, PC = HM != 0;   // PC: the halo lies in LDS as 16-byte pieces
   constexpr int W2D_NONE = -2147483647 - 1, W2D_PAD = -2147483647;   // lane offsets: no position / a padding position (prefilled)
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       __builtin_amdgcn_global_load_lds(d_base + (u / P.NI) * d_cs + f_xl[pp], Xb + (u / P.NI) * PS + 1 + (u % P.NI) * 256, 16, 0, 0);
     if (pp == 1) d_base += 4 * d_cs;
   };
-  constexpr int WPW = 24 / NW;   // 1-KiB weight pieces per wave and chunk (6 or 3)
+  constexpr int WPW = 24 / NW;   // 1-KiB weight pieces per wave and chunk (6)
   const float* const wsrc0 = P.wt + (size_t)mbb * P.nchunks * WTILE + wave8 * (WPW * 256) + lane * 4;
   // the wave's pieces of the 24 are adjacent: they share LDS bases (M0) and differ in the instruction's immediate offset, which
   // moves the global and the LDS address alike
@@ -710,12 +710,11 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       }
     return;
   }
-  w2d_epilogue<NWP>(P, sBw, n, h0, w0, tr2, tq, vmask, m0, mh, ph, j, l16, pt, out_transform);
+  w2d_epilogue(P, sBw, n, h0, w0, tr2, tq, vmask, m0, mh, ph, j, l16, pt, out_transform);
 }
 
 // The second half of a K-slab launch: one block per (pixel tile, m-block) with the conv kernel's thread -> (tile, channel) map adds
 // the slabs IN SLAB ORDER (run-to-run bitwise) and runs the conv kernel's epilogue on the sums.
-template <int NWP>
 __global__ __launch_bounds__(128 * NWP) void w2d_slab_reduce_kernel(const W2DParams P) {
   constexpr int BM = W2D_BM;
   __shared__ float sBw[4 * BM];
@@ -769,7 +768,7 @@ __global__ __launch_bounds__(128 * NWP) void w2d_slab_reduce_kernel(const W2DPar
     y[0][0] = a[0], y[0][1] = a[1], y[0][2] = a[2], y[0][3] = a[3];
     y[1][0] = b[0], y[1][1] = b[1], y[1][2] = b[2], y[1][3] = b[3];
   };
-  w2d_epilogue<NWP>(P, sBw, n, h0, w0, tr2, tq, vmask, m0, mh, ph, j, l16, pt, get_y);
+  w2d_epilogue(P, sBw, n, h0, w0, tr2, tq, vmask, m0, mh, ph, j, l16, pt, get_y);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -778,16 +777,16 @@ __global__ __launch_bounds__(128 * NWP) void w2d_slab_reduce_kernel(const W2DPar
 namespace {
 
 struct W2DPlan {
-  int TH, TW, TWq, tiles_y, tiles_x, mblocks, WR, WC, WCp, PS, nwp;
+  int TH, TW, TWq, tiles_y, tiles_x, mblocks, WR, WC, WCp, PS;
 };
 
 // LDS bank cost of the consumers' halo reads (one ds_read_b128 + one ds_read_b64 per window row; a lane's tile rows are 2 apart):
 // sum over the two pixel halves of the LDS cycles per read pair.
-int w2d_read_cycles(int TWq, int LP, int PS, int nwp) {
+int w2d_read_cycles(int TWq, int LP, int PS) {
   static const int g128[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
                                   {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
   int total = 0;
-  for (int ph = 0; ph < nwp; ++ph) {
+  for (int ph = 0; ph < NWP; ++ph) {
     int addr[64];
     for (int lane = 0; lane < 64; ++lane) {
       const int q = ph * 16 + (lane & 15);
@@ -827,21 +826,19 @@ int w2d_read_cycles(int TWq, int LP, int PS, int nwp) {
   return total;
 }
 
-// TH x TW output tile of 16 nwp two-row Winograd tiles (256 or 512 pixels) whose padded halo window fits the 128 NW DMA positions:
+// TH x TW output tile of 16 NWP two-row Winograd tiles (256 pixels) whose padded halo window fits the 128 NW DMA positions:
 // fewest blocks; among equals 32-wide rows, then the widest.  The LDS row pitch and plane stride are the ones with the fewest
-// bank conflicts.  GSD_W2D_WAVES = 4 | 8 (tuning): the four-wave (two blocks per CU) or the eight-wave block.
+// bank conflicts.
 bool plan_w2d(int N, int H, int W, int M, W2DPlan* best) {
   long best_cost = -1;
   const int force_tw = gsd_env_int("GSD_W2D_TW", 0);   // tuning
-  const int nwp = gsd_env_int("GSD_W2D_WAVES", 4) == 8 ? 4 : 2;   // measured (profiles/r05_w2d_vs_w43.txt): four waves win
-  best->nwp = nwp;
-  const int maxpos = 256 * nwp;
+  const int maxpos = 256 * NWP;
   static const int tws[4] = {32, 64, 16, 8};
   for (int k = 0; k < 4; ++k) {
     const int tw = tws[k];
     if (force_tw && tw != force_tw) continue;
     const int twq = tw / 4;
-    int th = 2 * (16 * nwp / twq);
+    int th = 2 * (16 * NWP / twq);
     const int wcp0 = round_up(tw + 2, 4);
     if ((th + 2) * wcp0 > maxpos) continue;
     const int ty = ceil_div(H, th);
@@ -867,8 +864,8 @@ bool plan_w2d(int N, int H, int W, int M, W2DPlan* best) {
   //  and the payload in separate words two writers of colliding keys could hand a reader a torn pair, and the LDS size would then
   //  be computed from another PS than the kernel's)
   static std::atomic<uint64_t> memo[16];
-  const int th = best->TH, tw = best->TW, key = (th << 16) | (tw << 4) | nwp;
-  std::atomic<uint64_t>& mm = memo[(th * 7 + tw + nwp) & 15];
+  const int th = best->TH, tw = best->TW, key = (th << 16) | (tw << 4);
+  std::atomic<uint64_t>& mm = memo[(th * 7 + tw) & 15];
   {
     const uint64_t v = mm.load(std::memory_order_acquire);
     if (v != 0 && (int)(v >> 40) == key) {
@@ -881,7 +878,7 @@ bool plan_w2d(int N, int H, int W, int M, W2DPlan* best) {
   int bc = -1;
   for (int c = wcp0; c <= wcp0 + 12 && (th + 2) * c <= maxpos; c += 4)
     for (int ps = round_up((th + 2) * c, 4) + 4; ps < round_up((th + 2) * c, 4) + 4 + 36; ps += 4) {
-      const int cyc = w2d_read_cycles(best->TWq, c, ps, nwp);
+      const int cyc = w2d_read_cycles(best->TWq, c, ps);
       if (bc < 0 || cyc < bc) {
         bc = cyc;
         best->WCp = c;
@@ -904,7 +901,7 @@ int w2d_x4_plane_stride(int TWq, int WCp, int WR) {
   }
   int best = -1, ps_best = WR * WCp + 4;
   for (int ps = WR * WCp + 4; ps < WR * WCp + 4 + 68; ps += 4) {
-    const int c = w2d_read_cycles(TWq, WCp, ps, 2);
+    const int c = w2d_read_cycles(TWq, WCp, ps);
     if (best < 0 || c < best) {
       best = c;
       ps_best = ps;
@@ -914,19 +911,19 @@ int w2d_x4_plane_stride(int TWq, int WCp, int WR) {
   return ps_best;
 }
 
-template <bool PLAIN, int NWP, int HM = 0, bool SPLIT = false>
+template <bool PLAIN, int HM = 0, bool SPLIT = false>
 int launch_w2d(const W2DParams& P, int grid, size_t lds, hipStream_t st) {
   static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  const void* fn = reinterpret_cast<const void*>(&conv3x3_w2d_kernel<PLAIN, NWP, HM, SPLIT>);
+  const void* fn = reinterpret_cast<const void*>(&conv3x3_w2d_kernel<PLAIN, HM, SPLIT>);
   if (hipError_t e = gsd_allow_big_lds(big_lds, fn); e != hipSuccess) {
     gsd_set_error("gsd_conv3x3_w2d: hipFuncSetAttribute: %s", hipGetErrorString(e));
     return GSD_ERR_HIP;
   }
   GSD_REQUIRE(lds <= 160 * 1024, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w2d: LDS image %zu B too large", lds);
-  hipLaunchKernelGGL((conv3x3_w2d_kernel<PLAIN, NWP, HM, SPLIT>), dim3(grid), dim3(128 * NWP), lds, st, P);
+  hipLaunchKernelGGL((conv3x3_w2d_kernel<PLAIN, HM, SPLIT>), dim3(grid), dim3(128 * NWP), lds, st, P);
   GSD_LAUNCH_CHECK("gsd_conv3x3_w2d");
   if constexpr (SPLIT) {
-    hipLaunchKernelGGL((w2d_slab_reduce_kernel<NWP>), dim3(grid / P.nslab), dim3(128 * NWP), 0, st, P);
+    hipLaunchKernelGGL(w2d_slab_reduce_kernel, dim3(grid / P.nslab), dim3(128 * NWP), 0, st, P);
     GSD_LAUNCH_CHECK("gsd_conv3x3_w2d (slab sums)");
   }
   return GSD_OK;
@@ -972,14 +969,14 @@ extern "C" int gsd_conv3x3_w2d_partial_rows(int N, int H, int W, int Cout) {
   if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
   W2DPlan p;
   if (!plan_w2d(N, H, W, Cout, &p)) return 0;
-  return N * p.tiles_y * p.tiles_x * p.nwp;
+  return N * p.tiles_y * p.tiles_x * NWP;
 }
 
 // MFMA instructions of one launch (all blocks, padding included)
 extern "C" int64_t gsd_conv3x3_w2d_mfma_count(int N, int H, int W, int Cin, int Cout) {
   W2DPlan p;
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !plan_w2d(N, H, W, Cout, &p)) return 0;
-  return (int64_t)N * p.tiles_y * p.tiles_x * p.mblocks * ceil_div(Cin, 4) * (2 * p.nwp * 48);
+  return (int64_t)N * p.tiles_y * p.tiles_x * p.mblocks * ceil_div(Cin, 4) * (2 * NWP * 48);
 }
 
 // Modelled run time of the launch in microseconds, as gsd_conv3x3_w43_estimate_us: a CU with k = ceil(blocks / 256) blocks runs
@@ -989,7 +986,6 @@ extern "C" double gsd_conv3x3_w2d_estimate_us(int N, int H, int W, int Cin, int 
   W2DPlan p;
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !plan_w2d(N, H, W, Cout, &p)) return 0.0;
   const long blocks = (long)N * p.tiles_y * p.tiles_x * p.mblocks;
-  if (p.nwp != 2) return (double)((blocks + gsd_cu_count() - 1) / gsd_cu_count()) * (4.6 * ceil_div(Cin, 4) + 5.0);   // (the eight-wave block: one per CU, twice the pixels)
   return w2d_time_us(blocks, ceil_div(Cin, 4), 1, false);
 }
 
@@ -997,7 +993,6 @@ extern "C" double gsd_conv3x3_w2d_estimate_us(int N, int H, int W, int Cin, int 
 extern "C" double gsd_conv3x3_w2d_estimate_slabs_us(int N, int H, int W, int Cin, int Cout) {
   W2DPlan p;
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !plan_w2d(N, H, W, Cout, &p)) return 0.0;
-  if (p.nwp != 2) return gsd_conv3x3_w2d_estimate_us(N, H, W, Cin, Cout);
   const long blocks = (long)N * p.tiles_y * p.tiles_x * p.mblocks;
   return w2d_time_us(blocks, ceil_div(Cin, 4), w2d_pick_slabs(blocks, ceil_div(Cin, 4), false), false);
 }
@@ -1006,7 +1001,7 @@ extern "C" double gsd_conv3x3_w2d_estimate_slabs_us(int N, int H, int W, int Cin
 // shrinks S to what fits.
 extern "C" int64_t gsd_conv3x3_w2d_workspace(int N, int H, int W, int Cin, int Cout) {
   W2DPlan p;
-  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 4 != 0 || !plan_w2d(N, H, W, Cout, &p) || p.nwp != 2) return 0;
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 4 != 0 || !plan_w2d(N, H, W, Cout, &p)) return 0;
   const long blocks = (long)N * p.tiles_y * p.tiles_x * p.mblocks;
   const int S = std::max(w2d_pick_slabs(blocks, Cin / 4, false), w2d_pick_slabs(blocks, Cin / 4, true));
   return S > 1 ? (int64_t)blocks * S * (W2D_BM * 256) : 0;
@@ -1072,7 +1067,7 @@ static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   P.TH = pl.TH; P.TW = pl.TW; P.TWq = pl.TWq; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;
   P.WR = pl.WR; P.WC = pl.WC; P.WCp = pl.WCp; P.PS = pl.PS;
   P.NPV = ceil_div(P.WR * P.WCp, 64);
-  GSD_REQUIRE(P.NPV <= 4 * pl.nwp, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w2d: halo window too large");
+  GSD_REQUIRE(P.NPV <= 4 * NWP, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w2d: halo window too large");
   // block order: as many m-blocks per pass as have their weight images (24 KiB per chunk) in 3 MiB of the XCD's 4-MiB L2, over
   // groups of as many pixel tiles as make 64 blocks (what an XCD of the four-wave form holds).  GSD_W2D_MGROUP: 0 all m-blocks of a
   // pixel tile together (the order of the shallow levels), n that many; GSD_W2D_PGROUP the pixel tiles per group.  (tuning / A-B runs)
@@ -1087,7 +1082,7 @@ static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   }
   const long base = (long)N * pl.tiles_y * pl.tiles_x * P.mblocks;
   // K slabs: only with a workspace (the engine lends one in train mode), only in the four-wave form, and never more than fit
-  int S = (ws != nullptr && pl.nwp == 2) ? w2d_pick_slabs(base, P.nchunks, bw_raw != nullptr) : 1;
+  int S = ws != nullptr ? w2d_pick_slabs(base, P.nchunks, bw_raw != nullptr) : 1;
   while (S > 1 && (int64_t)base * S * (W2D_BM * 256) > ws_elems) --S;
   if (S > 1 && P.nchunks / S < 2) S = 1;
   P.nslab = S;
@@ -1101,14 +1096,14 @@ static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   // its pad columns must hold zeros -- the engine's row-pitched d_raw buffer does (GSD_W2D_X4=0: dword gathers, A/B runs)
   P.NP = pl.TW / 4 + 2;
   P.NI = ceil_div(P.WR * P.NP, 64);
-  const bool x4 = plain && nsrc == 1 && pl.nwp == 2 && 4 * P.NI <= 8 && gsd_env_int("GSD_W2D_X4", 1) != 0 &&
+  const bool x4 = plain && nsrc == 1 && 4 * P.NI <= 8 && gsd_env_int("GSD_W2D_X4", 1) != 0 &&
                   ((uintptr_t)src[0].ptr & 15) == 0 && src[0].w_stride % 4 == 0 && src[0].c_stride % 4 == 0 && src[0].n_stride % 4 == 0 &&
                   src[0].off_h == 0 && src[0].off_w == 0 && src[0].w_stride >= round_up(src[0].W, 4);
   // unaligned 16-byte pieces for every other source: each segment vouches for 4 readable floats around its tensor (slack), lane
   // offsets stay 32-bit.  GSD_W2D_U4=0 keeps the dword gathers.  Default 1 since the loop's other vector work was halved (packed
   // transforms, constant image offsets): forward layer set 21.9 -> 21.2 ms, step -0.4 ms, bit-identical (when first built, against
   // the scalar transforms, it measured neutral: 97.7-97.9 ms either way)
-  bool u4 = !x4 && pl.nwp == 2 && 4 * P.NI <= 8 && gsd_env_int("GSD_W2D_U4", 1) != 0;
+  bool u4 = !x4 && 4 * P.NI <= 8 && gsd_env_int("GSD_W2D_U4", 1) != 0;
   for (int i = 0; i < nsrc && u4; ++i) u4 = src[i].slack >= 4;
   if (x4 || u4) {
     P.WCp = 4 * P.NP;
@@ -1120,15 +1115,13 @@ static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
             nsrc, ndst, (int)plain, (int)x4, (int)u4, (int)((uintptr_t)src[0].ptr & 15), src[0].w_stride, (int)(src[0].c_stride % 4),
             (int)(src[0].n_stride % 4), P.NI, pl.TH, pl.TW, S);
   if (S > 1) {
-    if (x4) return launch_w2d<true, 2, 1, true>(P, (int)grid, lds, (hipStream_t)stream);
-    if (u4) return plain ? launch_w2d<true, 2, 2, true>(P, (int)grid, lds, (hipStream_t)stream) : launch_w2d<false, 2, 2, true>(P, (int)grid, lds, (hipStream_t)stream);
-    return plain ? launch_w2d<true, 2, 0, true>(P, (int)grid, lds, (hipStream_t)stream) : launch_w2d<false, 2, 0, true>(P, (int)grid, lds, (hipStream_t)stream);
+    if (x4) return launch_w2d<true, 1, true>(P, (int)grid, lds, (hipStream_t)stream);
+    if (u4) return plain ? launch_w2d<true, 2, true>(P, (int)grid, lds, (hipStream_t)stream) : launch_w2d<false, 2, true>(P, (int)grid, lds, (hipStream_t)stream);
+    return plain ? launch_w2d<true, 0, true>(P, (int)grid, lds, (hipStream_t)stream) : launch_w2d<false, 0, true>(P, (int)grid, lds, (hipStream_t)stream);
   }
-  if (x4) return launch_w2d<true, 2, 1>(P, (int)grid, lds, (hipStream_t)stream);
-  if (u4) return plain ? launch_w2d<true, 2, 2>(P, (int)grid, lds, (hipStream_t)stream) : launch_w2d<false, 2, 2>(P, (int)grid, lds, (hipStream_t)stream);
-  if (pl.nwp == 2)
-    return plain ? launch_w2d<true, 2>(P, (int)grid, lds, (hipStream_t)stream) : launch_w2d<false, 2>(P, (int)grid, lds, (hipStream_t)stream);
-  return plain ? launch_w2d<true, 4>(P, (int)grid, lds, (hipStream_t)stream) : launch_w2d<false, 4>(P, (int)grid, lds, (hipStream_t)stream);
+  if (x4) return launch_w2d<true, 1>(P, (int)grid, lds, (hipStream_t)stream);
+  if (u4) return plain ? launch_w2d<true, 2>(P, (int)grid, lds, (hipStream_t)stream) : launch_w2d<false, 2>(P, (int)grid, lds, (hipStream_t)stream);
+  return plain ? launch_w2d<true>(P, (int)grid, lds, (hipStream_t)stream) : launch_w2d<false>(P, (int)grid, lds, (hipStream_t)stream);
 }
 
 extern "C" int gsd_conv3x3_w2d(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst,

@@ -96,133 +96,13 @@ __device__ __forceinline__ void w43_row(const W43Params& P, int n, int rho, int&
   if (nn >= P.N) nn = 0;
 }
 
-// Loader wave of the producer / consumer form of the kernel below (NL > 0): it issues EVERY LDS-DMA of the block -- the 18
-// one-KiB pieces of the weight chunk and the halo windows of the chunk's four input channels -- one chunk ahead of the four
-// MFMA waves, which then run a loop of ds_read + transform + MFMA only.  Measured with in-kernel stamps (profiles/
-// stamp_conv.py): a wave that issues its share of the fills itself spends ~250 cycles per global_load_lds (plus the
-// segment / padding bookkeeping around it) and the five k-steps that carried them took as long as the other thirteen
-// together; a wave that does nothing else issues them back to back (cdna_hip_programming.md, LDS-DMA loader rings).
-template <bool X4, int NL>
-__device__ __forceinline__ void w43_loader(const W43Params& P, float* smem, int BUF, int n, int h0, int w0, int mb, int lane,
-                                           int lw) {
-  constexpr int WTILE = W43_WTILE;
-  constexpr int NIL = ((X4 ? 2 : 8) + NL - 1) / NL;   // halo instructions per loader wave and channel plane
-  const int PS = P.PS;
-  int xo0[NIL], xo1[NIL], ldo[NIL];
-#pragma unroll
-  for (int k = 0; k < NIL; ++k) {
-    const int idx = lw + NL * k;
-    xo0[k] = xo1[k] = -2;
-    if constexpr (X4) {
-      ldo[k] = idx * P.RPI * P.WCp + 1;            // + 1 float: image column w0-1 then sits 16-byte aligned
-      const int rl = lane / P.NP, pc = lane - rl * P.NP;
-      const int rr = idx * P.RPI + rl;
-      if (idx < P.NI && rl < P.RPI && rr < P.WR) {
-        const int gh = h0 - 1 + rr, gw = w0 - 4 + 4 * pc;
-        int hs = gh - P.src0.oh, ws = gw - P.src0.ow;
-        xo0[k] = ((unsigned)hs < (unsigned)P.src0.H && ws >= 0 && ws < P.src0.W && ws + 4 <= P.src0.ws) ? hs * P.src0.ws + ws : -1;
-        hs = gh - P.src1.oh;
-        ws = gw - P.src1.ow;
-        xo1[k] = ((unsigned)hs < (unsigned)P.src1.H && ws >= 0 && ws < P.src1.W && ws + 4 <= P.src1.ws) ? hs * P.src1.ws + ws : -1;
-      }
-    } else {
-      ldo[k] = idx * 64;
-      const int pos = idx * 64 + lane;
-      const int rr = pos / P.WCp, cc = pos - rr * P.WCp;
-      if (idx < P.NPV && rr < P.WR && cc < P.WC) {
-        const int gh = h0 - 1 + rr, gw = w0 - 1 + cc;
-        int hs = gh - P.src0.oh, ws = gw - P.src0.ow;
-        xo0[k] = ((unsigned)hs < (unsigned)P.src0.H && (unsigned)ws < (unsigned)P.src0.W) ? hs * P.src0.ws + ws : -1;
-        hs = gh - P.src1.oh;
-        ws = gw - P.src1.ow;
-        xo1[k] = ((unsigned)hs < (unsigned)P.src1.H && (unsigned)ws < (unsigned)P.src1.W) ? hs * P.src1.ws + ws : -1;
-      }
-    }
-  }
-  {
-    // padding positions of the first segment: written once, in both images and all four channel planes; a fill of a
-    // first-segment channel then only moves the lanes that have a pixel
-    const float pad0 = P.src0.relu ? __builtin_nanf("") : 0.f;
-#pragma unroll
-    for (int k = 0; k < NIL; ++k)
-      if (xo0[k] == -1) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int ch = 0; ch < 4; ++ch) {
-            float* d = smem + b * BUF + WTILE + ch * PS + ldo[k];
-            if constexpr (X4) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) d[lane * 4 + e] = pad0;
-            } else {
-              d[lane] = pad0;
-            }
-          }
-      }
-  }
-  int d_seg = 0, d_left = P.src0.C;
-  const float* d_base = P.src0.p + (long long)n * P.src0.ns;
-  long long d_cs = P.src0.cs;
-  const float* const zeros = X4 ? &gsd_pad16_w43[0] : &gsd_pad_w43[0];
-  const float* d_sent = X4 ? (P.src0.relu ? &gsd_pad16_w43[4] : &gsd_pad16_w43[0]) : (P.src0.relu ? &gsd_pad_w43[1] : &gsd_pad_w43[0]);
-  const float* const wsrc = P.wt + (size_t)mb * P.nchunks * WTILE + lane * 4;
-
-  auto fill = [&](int chunk, int buf) {
-    float* Wb = smem + buf * BUF;
-    const float* wc = wsrc + (size_t)chunk * WTILE;
-#pragma unroll
-    for (int i = 0; i < 18; ++i)
-      if (i % NL == lw) __builtin_amdgcn_global_load_lds(wc + i * 256, Wb + i * 256, 16, 0, 0);
-    float* Xb = Wb + WTILE;
-#pragma unroll
-    for (int ch = 0; ch < 4; ++ch) {
-      if (d_left == 0 && d_seg == 0) {
-        d_seg = 1;
-        d_left = P.src1.C;
-        d_base = P.src1.p + (long long)n * P.src1.ns;
-        d_cs = P.src1.cs;
-        d_sent = X4 ? (P.src1.relu ? &gsd_pad16_w43[4] : &gsd_pad16_w43[0]) : (P.src1.relu ? &gsd_pad_w43[1] : &gsd_pad_w43[0]);
-      }
-      const bool c_ok = d_left > 0;
-      if (c_ok && d_seg == 0) {
-#pragma unroll
-        for (int k = 0; k < NIL; ++k)
-          if (xo0[k] >= 0) {
-            const float* gp = d_base + xo0[k];
-            __builtin_amdgcn_global_load_lds(gp, Xb + ch * PS + ldo[k], X4 ? 16 : 4, 0, 0);
-          }
-      } else {
-        // second (concat) segment and K padding: every window position is written, padding from the sentinel
-#pragma unroll
-        for (int k = 0; k < NIL; ++k) {
-          const int xo = d_seg == 0 ? xo0[k] : xo1[k];
-          if (xo != -2) {
-            const float* gp = (c_ok && xo >= 0) ? d_base + xo : (c_ok ? d_sent : zeros);
-            __builtin_amdgcn_global_load_lds(gp, Xb + ch * PS + ldo[k], X4 ? 16 : 4, 0, 0);
-          }
-        }
-      }
-      if (c_ok) {
-        d_base += d_cs;
-        --d_left;
-      }
-    }
-  };
-
-  fill(0, 0);
-  for (int chunk = 0; chunk < P.nchunks; ++chunk) {
-    gsd_dma_barrier();   // chunk `chunk` has landed (this wave's vmcnt); the MFMA waves have left the other image
-    if (chunk + 1 < P.nchunks) fill(chunk + 1, (chunk + 1) & 1);
-  }
-}
-
 // Epilogue shared by the convolution kernel (y = A^T M of its accumulators) and the K-slab reducer (y = sum of the slabs' tiles): NCHW
 // stores into two destination segments with crop, BatchNorm partial sums, or the fused BatchNorm-backward form.  The lane owns the
 // four pixels (h_t, w0 + 4 tq ..) of image n_t (fold) / n for the 16 output channels m0 + m * 16 + j * 4 + reg.
-template <int WM, class GetY>
-__device__ __forceinline__ void w43_epilogue(const W43Params& P, int n, int pt, int wave, int wm, int mbb, int m0, int j, int l16,
+template <class GetY>
+__device__ __forceinline__ void w43_epilogue(const W43Params& P, int n, int pt, int wave, int wm, int m0, int j, int l16,
                                              int n_t, int h_t, int w0, int tq, int vmask, const float* sBw, GetY&& get_y) {
-  constexpr int MT = 4, BM = W43_BM, BMB = WM * BM;
+  constexpr int MT = 4, BM = W43_BM;
   // ---- epilogue: y = A^T M, NCHW stores (two destination segments with crop), BatchNorm partial sums ----------------------
   // per destination: element offset of the tile's first pixel inside a plane, and the mask of its pixels that are stored
   int off0 = 0, off1 = 0, sm0 = 0, sm1 = 0;
@@ -315,7 +195,7 @@ __device__ __forceinline__ void w43_epilogue(const W43Params& P, int n, int pt, 
         const int co = m0 + m * 16 + j * 4 + reg;
         float* const px = d0 + (long long)co * P.dst0.cs + off0;
         const int cl = wm * BM + m * 16 + j * 4 + reg;
-        const float bsc = sBw[cl], bsh = sBw[BMB + cl], bmu = sBw[2 * BMB + cl], bis = sBw[3 * BMB + cl];
+        const float bsc = sBw[cl], bsh = sBw[BM + cl], bmu = sBw[2 * BM + cl], bis = sBw[3 * BM + cl];
         const int sm = co < P.Cout ? sm0 : 0;
         float y[4];
         get_y(m, reg, y);
@@ -348,10 +228,6 @@ __device__ __forceinline__ void w43_epilogue(const W43Params& P, int n, int pt, 
   }
 }
 
-// WM = groups of 4 waves per block: 1 -> 64 m x 256 px, two blocks per CU; 2 -> 128 m x 256 px (two 64-channel weight
-// images side by side), 8 waves, one block per CU: the halo DMA -- the expensive part of the data movement -- is then shared
-// by twice the MFMAs (9 instead of 13 DMA instructions per wave and chunk).  Tuning option (GSD_W43_BIG), not the default.
-//
 // X4: the halo windows move as ALIGNED 16-byte pieces (global_load_lds_dwordx4 with a per-lane source address) instead of
 // dword gathers: possible when every source row starts 16-byte aligned (row pitch, plane and image strides multiples of 4
 // floats, pad offset a multiple of 4) -- the engine allocates its activations that way.  A window row is then the NP =
@@ -359,8 +235,6 @@ __device__ __forceinline__ void w43_epilogue(const W43Params& P, int n, int pt, 
 // image column w0-1 lands 16-byte aligned and the consumer reads stay one b128 + one b64 per kernel row.  A quarter of the
 // gather instructions (2 per channel plane instead of 6), each a coalesced run of 16-byte lanes.  Columns >= W inside the
 // pitch come from memory: producers keep the padding value there (NaN under a ReLU'd BatchNorm, else 0).
-//
-// NL > 0: producer / consumer form -- NL extra waves per block issue all the DMA (w43_loader above); WM must be 1.
 //
 // FAST: straight halo fills, no per-slot bookkeeping (which segment, how many channels it has left, which sentinel: a
 // chain of scalar branches per slot in the general form): possible when a chunk of 4 channels never straddles the two
@@ -385,27 +259,27 @@ __device__ __forceinline__ void w43_epilogue(const W43Params& P, int n, int pt, 
 // small per-GPU batches: 152-600 blocks of 128-256 chunks each) is cut along the input channels instead: block (tile, slab k)
 // runs chunks [k nchunks / S, (k+1) nchunks / S) and stores its UN-reduced y = A^T M tile to P.slabs; w43_slab_reduce_kernel adds
 // the S slabs in slab order and runs this kernel's epilogue (crop, statistics, fused BatchNorm-backward) on the sums.
-template <int WM, int X4M, int NL, bool FAST, bool PLAIN, bool SPLIT = false>
+template <int X4M, bool FAST, bool PLAIN, bool SPLIT = false>
 #ifndef W43_ABL   // diagnostic builds: 1 no weight fills, 2 no halo fills, 4 no barrier per chunk, 8 no wait for the fills, 16 / 32 halo fills from hot addresses (results are then garbage)
 #define W43_ABL 0
 #endif
 #ifndef W43_MIN_WAVES   // diagnostic builds: waves per SIMD the register allocation must admit for the 4-wave form
 #define W43_MIN_WAVES 2
 #endif
-__global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN_WAVES : 1)) void conv3x3_w43_kernel(const W43Params P) {
-  static_assert(NL == 0 || WM == 1, "loader waves serve one 64-channel weight image");
+__global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W43Params P) {
   constexpr bool X4 = X4M == 1, U4 = X4M == 2;
-  static_assert(!U4 || (FAST && WM == 1 && NL == 0), "unaligned 16-byte halo pieces: the straight-fill 4-wave form");
-  static_assert(!SPLIT || (FAST && WM == 1 && NL == 0 && !U4), "K slabs: the straight-fill 4-wave form");
-  constexpr int MT = 4, BM = W43_BM, WS = BM, WTILE = W43_WTILE, W4 = W43_W4 * WM, NT = 256 * WM + 64 * NL, NWAVE = 4 * WM;
-  constexpr int NWI = (W4 + NT - 1) / NT;
+  static_assert(!U4 || FAST, "unaligned 16-byte halo pieces: the straight-fill form");
+  static_assert(!SPLIT || (FAST && !U4), "K slabs: the straight-fill form");
+  constexpr int MT = 4, BM = W43_BM, WS = BM, WTILE = W43_WTILE, NT = 256, NWAVE = 4, NWI = W43_NWI;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int PS = P.PS;
-  const int BUF = U4 ? WM * WTILE + P.NI * 256 : WM * WTILE + 4 * PS;   // U4: whole 64-piece instructions
+  const int BUF = U4 ? WTILE + P.NI * 256 : WTILE + 4 * PS;   // U4: whole 64-piece instructions
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave8 >> 2, wave = wave8 & 3;   // wave: pixel group of the wave, wm: its 64-channel group
+  // wave: pixel group of the wave.  wm (0 in a 256-thread block) stays a run-time value: folding it to 0 changes the register
+  // allocation of the kernel, and this form is the one that was measured
+  const int wm = wave8 >> 2, wave = wave8 & 3;
 #ifdef GSD_W43_STAMPS
   unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
@@ -415,13 +289,12 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
   // The m-blocks of one pixel tile read the same halo: hardware deals blocks round-robin over the 8 XCDs, so give every XCD
   // a contiguous range of logical ids (pixel tile major, m-block minor) and its L2 serves the halo once.
   const int lid = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int mbb = lid % P.mblocks;              // P.mblocks counts blocks (WM 64-channel groups each)
+  const int mbb = lid % P.mblocks;
   const int slab = SPLIT ? (lid / P.mblocks) % P.nslab : 0;   // SPLIT: pixel tile major, then slab, m-block minor
   const int pt = SPLIT ? lid / (P.mblocks * P.nslab) : lid / P.mblocks;
   const int c_lo = SPLIT ? (int)((long long)slab * P.nchunks / P.nslab) : 0;            // this block's channel chunks
   const int c_hi = SPLIT ? (int)((long long)(slab + 1) * P.nchunks / P.nslab) : P.nchunks;
-  const int mb = mbb * WM + wm;
-  const int m0 = mb * BM;
+  const int m0 = (mbb + wm) * BM;
   const int tpi = P.tiles_y * P.tiles_x;
   const int n = P.fold ? 0 : pt / tpi;            // fold: the tile rows cover the whole batch, the image is a per-lane value
   const int rt = pt - n * tpi;
@@ -433,7 +306,7 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
   const bool q_ok = q < P.TH * P.TWq;
   const int tr = q_ok ? q / P.TWq : 0;
   const int tq = q_ok ? q - tr * P.TWq : 0;
-  const int baddr = WM * WTILE + j * PS + tr * P.WCp + 4 * tq + (X4 ? 4 : 0);   // halo columns 4*tq .. 4*tq+5 of halo rows tr .. tr+2
+  const int baddr = WTILE + j * PS + tr * P.WCp + 4 * tq + (X4 ? 4 : 0);   // halo columns 4*tq .. 4*tq+5 of halo rows tr .. tr+2
   int vmask = 0;                                            // pixels of the tile that exist in the image
   int n_t, h_t;                                             // this lane's image and row
   w43_row(P, n, h0 + tr, n_t, h_t);
@@ -444,7 +317,7 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
   }
 
   // ---- DMA lane geometry (as gsd_conv3x3.hip, window rows padded to WCp floats) ------------------------------------------
-  constexpr int NPP = 2 / WM;   // dword form: position chunks of 64 per wave (the block's waves cover the 512 window positions
+  constexpr int NPP = 2;   // dword form: position chunks of 64 per wave (the block's waves cover the 512 window positions
                                 // once); X4: DMA units (channel plane, instruction) per wave and chunk
   int xo0[NPP], xo1[NPP];
   int u_ch[NPP], u_lds[NPP];    // X4: the unit's channel of the chunk and its float offset inside the channel plane
@@ -534,14 +407,14 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
   const float* u_base = P.src0.p + (long long)n * P.src0.ns;   // U4: first channel plane of the next chunk to fill
   const float* u_sent = P.src0.relu ? &gsd_pad16_w43[4] : &gsd_pad16_w43[0];
   long long u_cs = P.src0.cs;
-  const float* wsrc0 = P.wt + (size_t)(mbb * WM) * P.nchunks * WTILE;   // the block's WM weight images follow each other
+  const float* wsrc0 = P.wt + (size_t)mbb * P.nchunks * WTILE;   // the block's weight image
   const long long wlane = tid * 4;   // this lane's float offset inside a 1 KiB weight piece group
   long long xl0[NPP];   // first segment's offsets as 64-bit lane values (the address add is then a single instruction)
 #pragma unroll
   for (int pp = 0; pp < NPP; ++pp) xl0[pp] = xo0[pp];
   // SPLIT: a slab that lies wholly in the second (concat) segment starts there -- its padding positions, plane pointer and lane offsets
   const bool s1_start = SPLIT && P.src1.C > 0 && c_lo * 4 > P.src0.C;
-  if constexpr (NL == 0 && !U4)
+  if constexpr (!U4)
   {
     // padding positions of the first segment, once, in all 2 x 4 channel planes (own positions only: the lanes that
     // would otherwise DMA the sentinel there on every fill); visible to the consumers after the first barrier
@@ -553,10 +426,10 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
         for (int b = 0; b < 2; ++b) {
           if constexpr (X4) {   // the unit's own plane: the other planes' pieces belong to other units
 #pragma unroll
-            for (int e = 0; e < 4; ++e) smem[b * BUF + WM * WTILE + u_ch[pp] * PS + u_lds[pp] + lane * 4 + e] = pad0;
+            for (int e = 0; e < 4; ++e) smem[b * BUF + WTILE + u_ch[pp] * PS + u_lds[pp] + lane * 4 + e] = pad0;
           } else {
 #pragma unroll
-            for (int ch = 0; ch < 4; ++ch) smem[b * BUF + WM * WTILE + ch * PS + (wave8 + NWAVE * pp) * 64 + lane] = pad0;
+            for (int ch = 0; ch < 4; ++ch) smem[b * BUF + WTILE + ch * PS + (wave8 + NWAVE * pp) * 64 + lane] = pad0;
           }
         }
       }
@@ -616,10 +489,10 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
       if (p_on[pp] && f_xo[pp] == -1) {
         if constexpr (X4) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) smem[buf * BUF + WM * WTILE + u_ch[pp] * PS + u_lds[pp] + lane * 4 + e] = pad1;
+          for (int e = 0; e < 4; ++e) smem[buf * BUF + WTILE + u_ch[pp] * PS + u_lds[pp] + lane * 4 + e] = pad1;
         } else {
 #pragma unroll
-          for (int ch = 0; ch < 4; ++ch) smem[buf * BUF + WM * WTILE + ch * PS + (wave8 + NWAVE * pp) * 64 + lane] = pad1;
+          for (int ch = 0; ch < 4; ++ch) smem[buf * BUF + WTILE + ch * PS + (wave8 + NWAVE * pp) * 64 + lane] = pad1;
         }
       }
   };
@@ -667,29 +540,22 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
     float* Wb = smem + buf * BUF;
     if constexpr (FAST) {
       if (slot >= NWI && slot < NWI + 4) {
-        fast_halo(slot - NWI, Wb + WM * WTILE);
+        fast_halo(slot - NWI, Wb + WTILE);
         return;
       }
     }
     if (slot < NWI) {
-      const int e = tid + slot * NT;                 // 16-byte piece of the block's WM weight images (LDS: linear in e)
-      if constexpr (WM == 1) {
-        // one image: scalar chunk base + the lane's fixed offset.  The last slot is half full (1152 = 4.5 x 256 pieces):
-        // it goes to waves 2 and 3, because waves 0 and 1 already move two position chunks of every halo plane where
-        // waves 2 and 3 move one -- the barrier waits for the busiest wave.
-        if (slot < NWI - 1) {
-          __builtin_amdgcn_global_load_lds(wsrc0 + (size_t)chunk * WTILE + slot * (NT * 4) + wlane, Wb + (slot * NT + wave8 * 64) * 4, 16, 0, 0);
-        } else if (wave8 >= 2) {
-          __builtin_amdgcn_global_load_lds(wsrc0 + (size_t)chunk * WTILE + (slot * NT - 128) * 4 + wlane, Wb + (slot * NT - 128 + wave8 * 64) * 4, 16, 0, 0);
-        }
-      } else {
-        const int img = e >= W43_W4 ? 1 : 0;
-        const float* wsrc = wsrc0 + ((size_t)img * P.nchunks + chunk) * WTILE + (e - img * W43_W4) * 4;
-        if (e < W4) __builtin_amdgcn_global_load_lds(wsrc, Wb + (slot * NT + wave8 * 64) * 4, 16, 0, 0);
+      // scalar chunk base + the lane's fixed offset.  The last slot is half full (1152 = 4.5 x 256 pieces): it goes to waves
+      // 2 and 3, because waves 0 and 1 already move two position chunks of every halo plane where waves 2 and 3 move one --
+      // the barrier waits for the busiest wave.
+      if (slot < NWI - 1) {
+        __builtin_amdgcn_global_load_lds(wsrc0 + (size_t)chunk * WTILE + slot * (NT * 4) + wlane, Wb + (slot * NT + wave8 * 64) * 4, 16, 0, 0);
+      } else if (wave8 >= 2) {
+        __builtin_amdgcn_global_load_lds(wsrc0 + (size_t)chunk * WTILE + (slot * NT - 128) * 4 + wlane, Wb + (slot * NT - 128 + wave8 * 64) * 4, 16, 0, 0);
       }
     } else if (slot < NWI + 4) {
       const int ch = slot - NWI;
-      float* Xb = Wb + WM * WTILE;
+      float* Xb = Wb + WTILE;
       if (d_left == 0 && d_seg == 0) {
         d_seg = 1;
         d_left = P.src1.C;
@@ -757,21 +623,14 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
     sAff[c] = sc;
     sAff[Kpad + c] = sh;
   }
-  constexpr int BMB = WM * BM;    // output channels of the block
-  float* sBw = sAff + 2 * Kpad;   // [4][BMB]: scale, shift, mean, invstd of the fused BatchNorm-backward epilogue
+  float* sBw = sAff + 2 * Kpad;   // [4][BM]: scale, shift, mean, invstd of the fused BatchNorm-backward epilogue
   if (P.bw_raw != nullptr) {
-    for (int c = tid; c < BMB; c += NT) {
-      const int co = mbb * BMB + c < P.Cout ? mbb * BMB + c : 0;
+    for (int c = tid; c < BM; c += NT) {
+      const int co = mbb * BM + c < P.Cout ? mbb * BM + c : 0;
       sBw[c] = P.bw_scale[co];
-      sBw[BMB + c] = P.bw_shift[co];
-      sBw[2 * BMB + c] = P.bw_mean[co];
-      sBw[3 * BMB + c] = P.bw_invstd[co];
-    }
-  }
-  if constexpr (NL > 0) {
-    if (wave8 >= NWAVE) {   // wave-uniform: the loader waves never reach the MFMA loop or the epilogue
-      w43_loader<X4, NL>(P, smem, BUF, n, h0, w0, mbb, lane, wave8 - NWAVE);
-      return;
+      sBw[BM + c] = P.bw_shift[co];
+      sBw[2 * BM + c] = P.bw_mean[co];
+      sBw[3 * BM + c] = P.bw_invstd[co];
     }
   }
   const float lo0 = P.src0.relu ? 0.f : -__builtin_inff(), lo1 = P.src1.relu ? 0.f : -__builtin_inff();
@@ -800,11 +659,9 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
   };
 
   const int a_lane = wm * WTILE + l16 * 4;
-  if constexpr (NL == 0) {
-    if constexpr (FAST) begin_fill(c_lo, 0);
+  if constexpr (FAST) begin_fill(c_lo, 0);
 #pragma unroll
-    for (int slot = 0; slot < NWI + 4; ++slot) dma_slot(slot, c_lo, 0);
-  }
+  for (int slot = 0; slot < NWI + 4; ++slot) dma_slot(slot, c_lo, 0);
   W43_STAMP(5)   // prologue
   for (int chunk = c_lo; chunk < c_hi; ++chunk) {
     const int cur = (chunk - c_lo) & 1;
@@ -813,7 +670,7 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
       if (u_patch) {   // a block at the left / right image edge: the outside floats of the straddling pieces this lane moved
         const bool seg1 = f_sw >= 0 && chunk >= f_sw;
         const float padv = (seg1 ? P.src1.relu : P.src0.relu) ? __builtin_nanf("") : 0.f;
-        float* Xh = smem + cur * BUF + WM * WTILE;
+        float* Xh = smem + cur * BUF + WTILE;
 #pragma unroll
         for (int k = 0; k < KH; ++k) {
           const int pm = seg1 ? h_pm1[k] : h_pm0[k];
@@ -870,52 +727,44 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
           av[(s + W43_PF) % (W43_PF + 1)] = *reinterpret_cast<const f32x4*>(&Wc[(j * 18 + s + W43_PF) * WS + a_lane]);
 #pragma unroll
         for (int m = 0; m < MT; ++m) acc[m][f] = mfma16(av[cs][m], v[f], acc[m][f]);
-        if constexpr (NL == 0) {
-          if constexpr (FAST && WM == 1) {
-            // weights first, in ONE k-step: a wave's four pieces are adjacent (4 KiB), so they share one LDS base (M0) and differ
-            // in the instruction's immediate offset, which moves the global and the LDS address alike -- a changed M0 between
-            // two LDS-DMA instructions costs the wave ~45 cycles at two blocks per CU (profiles/ubench/dma_m0.hip); then the halo
-            if (more && s < 3) {
-              if (s == 0) {
-                begin_fill(chunk + 1, cur ^ 1);
-                if (!((W43_ABL) & 1)) {
-                float* Wn = smem + (cur ^ 1) * BUF;
-                const float* wg = wsrc0 + (size_t)(chunk + 1) * WTILE + wave8 * 1024 + lane * 4;
-                float* wl = Wn + wave8 * 1024;
-                __builtin_amdgcn_global_load_lds(wg, wl, 16, 0, 0);
-                __builtin_amdgcn_global_load_lds(wg, wl, 16, 1024, 0);
-                __builtin_amdgcn_global_load_lds(wg, wl, 16, 2048, 0);
-                __builtin_amdgcn_global_load_lds(wg, wl, 16, 3072, 0);
-                if (wave8 >= 2) {   // pieces 16, 17 of the 18
-                  const float* wg2 = wsrc0 + (size_t)(chunk + 1) * WTILE + (14 + wave8) * 256 + lane * 4;
-                  float* wl2 = Wn + (14 + wave8) * 256;
-                  __builtin_amdgcn_global_load_lds(wg2, wl2, 16, 0, 0);
-                }
-                }
-              } else if (!((W43_ABL) & 2)) {
-                dma_slot(NWI + 2 * s - 2, chunk + 1, cur ^ 1);
-                dma_slot(NWI + 2 * s - 1, chunk + 1, cur ^ 1);
+        if constexpr (FAST) {
+          // weights first, in ONE k-step: a wave's four pieces are adjacent (4 KiB), so they share one LDS base (M0) and differ
+          // in the instruction's immediate offset, which moves the global and the LDS address alike -- a changed M0 between
+          // two LDS-DMA instructions costs the wave ~45 cycles at two blocks per CU (profiles/ubench/dma_m0.hip); then the halo
+          if (more && s < 3) {
+            if (s == 0) {
+              begin_fill(chunk + 1, cur ^ 1);
+              if (!((W43_ABL) & 1)) {
+              float* Wn = smem + (cur ^ 1) * BUF;
+              const float* wg = wsrc0 + (size_t)(chunk + 1) * WTILE + wave8 * 1024 + lane * 4;
+              float* wl = Wn + wave8 * 1024;
+              __builtin_amdgcn_global_load_lds(wg, wl, 16, 0, 0);
+              __builtin_amdgcn_global_load_lds(wg, wl, 16, 1024, 0);
+              __builtin_amdgcn_global_load_lds(wg, wl, 16, 2048, 0);
+              __builtin_amdgcn_global_load_lds(wg, wl, 16, 3072, 0);
+              if (wave8 >= 2) {   // pieces 16, 17 of the 18
+                const float* wg2 = wsrc0 + (size_t)(chunk + 1) * WTILE + (14 + wave8) * 256 + lane * 4;
+                float* wl2 = Wn + (14 + wave8) * 256;
+                __builtin_amdgcn_global_load_lds(wg2, wl2, 16, 0, 0);
               }
+              }
+            } else if (!((W43_ABL) & 2)) {
+              dma_slot(NWI + 2 * s - 2, chunk + 1, cur ^ 1);
+              dma_slot(NWI + 2 * s - 1, chunk + 1, cur ^ 1);
             }
-          } else if constexpr (FAST) {
-            if (more && s < 5) {
-              if (s == 0) begin_fill(chunk + 1, cur ^ 1);
-              dma_slot(2 * s, chunk + 1, cur ^ 1);
-              dma_slot(2 * s + 1, chunk + 1, cur ^ 1);
-            }
-          } else if (more && s < 5) {
-#ifdef W43_STAMP_DMA
-            W43_STAMP(2)
-#endif
-            dma_slot(2 * s, chunk + 1, cur ^ 1);
-            dma_slot(2 * s + 1, chunk + 1, cur ^ 1);
-#ifdef W43_STAMP_DMA
-            W43_STAMP(6)   // the DMA slots alone
-#endif
           }
+        } else if (more && s < 5) {
+#ifdef W43_STAMP_DMA
+          W43_STAMP(2)
+#endif
+          dma_slot(2 * s, chunk + 1, cur ^ 1);
+          dma_slot(2 * s + 1, chunk + 1, cur ^ 1);
+#ifdef W43_STAMP_DMA
+          W43_STAMP(6)   // the DMA slots alone
+#endif
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (s == ((FAST && WM == 1) ? 2 : 4)) W43_STAMP(2)   // the k-steps that carry the next chunk's DMA issue
+        if (s == (FAST ? 2 : 4)) W43_STAMP(2)   // the k-steps that carry the next chunk's DMA issue
       }
     }
     W43_STAMP(3)     // the other thirteen k-steps (52 MFMAs)
@@ -944,7 +793,7 @@ __global__ __launch_bounds__(256 * WM + 64 * NL, NL > 0 ? 3 : (WM == 1 ? W43_MIN
         *reinterpret_cast<f32x4*>(tile + (m * 16 + j * 4 + reg) * 256) = f32x4{y[0], y[1], y[2], y[3]};
       }
   } else {
-    w43_epilogue<WM>(P, n, pt, wave, wm, mbb, m0, j, l16, n_t, h_t, w0, tq, vmask, sBw, out_transform);
+    w43_epilogue(P, n, pt, wave, wm, m0, j, l16, n_t, h_t, w0, tq, vmask, sBw, out_transform);
   }
 #ifdef GSD_W43_STAMPS
   W43_STAMP(4)   // epilogue
@@ -1008,7 +857,7 @@ __global__ __launch_bounds__(256) void w43_slab_reduce_kernel(const W43Params P)
   auto get_y = [&](int m, int reg, float (&y)[4]) {
     y[0] = ys[m][reg][0], y[1] = ys[m][reg][1], y[2] = ys[m][reg][2], y[3] = ys[m][reg][3];
   };
-  w43_epilogue<1>(P, n, pt, wave, 0, mbb, mbb * W43_BM, j, l16, n_t, h_t, w0, tq, vmask, sBw, get_y);
+  w43_epilogue(P, n, pt, wave, 0, mbb * W43_BM, j, l16, n_t, h_t, w0, tq, vmask, sBw, get_y);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1122,16 +971,16 @@ int halo_read_cycles(int TWq, int LP, int PS, int off) {
 }
 
 // one launcher per kernel instantiation (the address of the kernel keys the per-device launch-attribute cache)
-template <int WM, int X4, int NL, bool FAST, bool PLAIN = false, bool SPLIT = false>
+template <int X4, bool FAST, bool PLAIN = false, bool SPLIT = false>
 int launch_one(const W43Params& P, int grid, size_t lds, hipStream_t st) {
   static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  const void* fn = reinterpret_cast<const void*>(&conv3x3_w43_kernel<WM, X4, NL, FAST, PLAIN, SPLIT>);
+  const void* fn = reinterpret_cast<const void*>(&conv3x3_w43_kernel<X4, FAST, PLAIN, SPLIT>);
   if (hipError_t e = gsd_allow_big_lds(big_lds, fn); e != hipSuccess) {
     gsd_set_error("gsd_conv3x3_w43: hipFuncSetAttribute: %s", hipGetErrorString(e));
     return GSD_ERR_HIP;
   }
   GSD_REQUIRE(lds <= 160 * 1024, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w43: LDS image %zu B too large", lds);
-  hipLaunchKernelGGL((conv3x3_w43_kernel<WM, X4, NL, FAST, PLAIN, SPLIT>), dim3(grid), dim3(256 * WM + 64 * NL), lds, st, P);
+  hipLaunchKernelGGL((conv3x3_w43_kernel<X4, FAST, PLAIN, SPLIT>), dim3(grid), dim3(256), lds, st, P);
   GSD_LAUNCH_CHECK("gsd_conv3x3_w43");
   return GSD_OK;
 }
@@ -1139,22 +988,19 @@ int launch_one(const W43Params& P, int grid, size_t lds, hipStream_t st) {
 // K-slab form: the SPLIT blocks (grid = tile blocks x slabs), then the reducer over the tile blocks
 int launch_split(const W43Params& P, int base_grid, size_t lds, hipStream_t st, bool x4, bool plain) {
   const int grid = base_grid * P.nslab;
-  int e = x4 ? (plain ? launch_one<1, 1, 0, true, true, true>(P, grid, lds, st) : launch_one<1, 1, 0, true, false, true>(P, grid, lds, st))
-             : (plain ? launch_one<1, 0, 0, true, true, true>(P, grid, lds, st) : launch_one<1, 0, 0, true, false, true>(P, grid, lds, st));
+  int e = x4 ? (plain ? launch_one<1, true, true, true>(P, grid, lds, st) : launch_one<1, true, false, true>(P, grid, lds, st))
+             : (plain ? launch_one<0, true, true, true>(P, grid, lds, st) : launch_one<0, true, false, true>(P, grid, lds, st));
   if (e != GSD_OK) return e;
   hipLaunchKernelGGL(w43_slab_reduce_kernel, dim3(base_grid), dim3(256), 0, st, P);
   GSD_LAUNCH_CHECK("gsd_conv3x3_w43 (slab reduce)");
   return GSD_OK;
 }
 
-int launch_w43(const W43Params& P, int grid, size_t lds, hipStream_t st, int wm, bool x4, int nl, bool fast, bool plain, bool u4) {
-  if (u4) return plain ? launch_one<1, 2, 0, true, true>(P, grid, lds, st) : launch_one<1, 2, 0, true, false>(P, grid, lds, st);
-  if (nl == 1) return x4 ? launch_one<1, true, 1, false>(P, grid, lds, st) : launch_one<1, false, 1, false>(P, grid, lds, st);
-  if (nl == 2) return x4 ? launch_one<1, true, 2, false>(P, grid, lds, st) : launch_one<1, false, 2, false>(P, grid, lds, st);
-  if (wm == 2) return x4 ? launch_one<2, true, 0, false>(P, grid, lds, st) : launch_one<2, false, 0, false>(P, grid, lds, st);
-  if (fast && plain) return x4 ? launch_one<1, true, 0, true, true>(P, grid, lds, st) : launch_one<1, false, 0, true, true>(P, grid, lds, st);
-  if (fast) return x4 ? launch_one<1, true, 0, true>(P, grid, lds, st) : launch_one<1, false, 0, true>(P, grid, lds, st);
-  return x4 ? launch_one<1, true, 0, false>(P, grid, lds, st) : launch_one<1, false, 0, false>(P, grid, lds, st);
+int launch_w43(const W43Params& P, int grid, size_t lds, hipStream_t st, bool x4, bool fast, bool plain, bool u4) {
+  if (u4) return plain ? launch_one<2, true, true>(P, grid, lds, st) : launch_one<2, true, false>(P, grid, lds, st);
+  if (fast && plain) return x4 ? launch_one<1, true, true>(P, grid, lds, st) : launch_one<0, true, true>(P, grid, lds, st);
+  if (fast) return x4 ? launch_one<1, true>(P, grid, lds, st) : launch_one<0, true>(P, grid, lds, st);
+  return x4 ? launch_one<1, false>(P, grid, lds, st) : launch_one<0, false>(P, grid, lds, st);
 }
 
 // K slabs of a launch of `base` tile blocks of `nchunks` 4-channel chunks (1: the launch runs as it is).  Two blocks are resident
@@ -1279,16 +1125,11 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   P.Cout = Cout;
   P.Mpad = round_up(Cout, 64);
   P.nchunks = ceil_div(Cin, 4);
-  // measured (profiles/bench_conv_forms.py): two independent 4-wave blocks per CU hide each other's barriers better than one
-  // 8-wave block shares its halo (+6 % for the 8-wave form at Cin <= 512, +1.5 % at Cin = 1024); GSD_W43_BIG=1 selects it
-  const bool big = gsd_env_set("GSD_W43_BIG");
-  // producer / consumer form (default): GSD_W43_NL loader waves per block (0: every wave issues its share of the DMA itself)
-  const int nl = big ? 0 : gsd_env_int("GSD_W43_NL", 0);   // measured: a loader wave cannot keep up without a deeper ring
+  // 4-wave blocks, two per CU: they hide each other's barriers better than one 8-wave block shares its halo (measured +6 %
+  // at Cin <= 512, profiles/bench_conv_forms.py); a loader wave cannot keep up without a deeper ring
   // straight fills (no per-slot bookkeeping): every 4-channel chunk lies inside one source segment
-  const bool fast = gsd_env_int("GSD_W43_FAST", 1) != 0 && Cin % 4 == 0 && (nsrc == 1 || src[0].C % 4 == 0);
-  GSD_REQUIRE(nl >= 0 && nl <= 2, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: GSD_W43_NL must be 0, 1 or 2");
-  const int WM = (pl.mblocks % 2 == 0 && big) ? 2 : 1;
-  P.mblocks = pl.mblocks / WM;
+  const bool fast = Cin % 4 == 0 && (nsrc == 1 || src[0].C % 4 == 0);
+  P.mblocks = pl.mblocks;
   P.N = N; P.H = H; P.W = W;
   P.TH = pl.TH; P.TW = pl.TW; P.TWq = pl.TWq; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;
   P.WR = pl.WR; P.WC = pl.WC; P.WCp = pl.WCp;
@@ -1323,7 +1164,7 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   // worth 9.5 %: it is the halo's memory traffic and latency the kernel waits for, not the instruction count -- unlike the dW
   // kernel, where the same change bought 11 %.  GSD_W43_U4 = 0 off (default), 1 where tiles_x >= 4, 2 always
   const int u4_env = gsd_env_int("GSD_W43_U4", 0);
-  bool u4 = (u4_env == 2 || (u4_env == 1 && pl.tiles_x >= 4)) && fast && WM == 1 && nl == 0;
+  bool u4 = (u4_env == 2 || (u4_env == 1 && pl.tiles_x >= 4)) && fast;
   for (int i = 0; i < nsrc; ++i)
     u4 = u4 && src[i].slack >= 4 && 4 * src[i].c_stride + (int64_t)(pl.fold ? N : 1) * src[i].n_stride < (1LL << 31);
   if (u4) {
@@ -1342,12 +1183,11 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   P.slabs = nullptr;
   const long grid = (long)(pl.fold ? 1 : N) * pl.tiles_y * pl.tiles_x * P.mblocks;
   GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w43: grid too large");
-  GSD_REQUIRE(!pl.fold || nl == 0, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w43: the loader-wave form does not fold rows (GSD_W43_FOLD=0)");
-  const size_t lds = (size_t)(2 * (WM * W43_WTILE + (u4 ? P.NI * 256 : 4 * P.PS)) + 2 * 4 * P.nchunks + 4 * WM * W43_BM) * sizeof(float);
+  const size_t lds = (size_t)(2 * (W43_WTILE + (u4 ? P.NI * 256 : 4 * P.PS)) + 2 * 4 * P.nchunks + 4 * W43_BM) * sizeof(float);
   bool plain = gsd_env_int("GSD_W43_PLAIN", 1) != 0;   // no deferred BatchNorm / ReLU on any source segment
   for (int i = 0; i < nsrc; ++i) plain = plain && src[i].scale == nullptr && src[i].relu == 0;
-  // K slabs (the caller lends scratch): straight-fill 4-wave form only; the slab count shrinks to what the scratch holds
-  if (ws != nullptr && fast && WM == 1 && nl == 0 && !u4) {
+  // K slabs (the caller lends scratch): straight-fill form only; the slab count shrinks to what the scratch holds
+  if (ws != nullptr && fast && !u4) {
     GSD_REQUIRE(((uintptr_t)ws & 15) == 0, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: workspace must be 16-byte aligned");
     int S = w43_pick_slabs(grid, P.nchunks, bw_raw != nullptr);
     while (S > 1 && (int64_t)S * grid * W43_BM * 256 > ws_elems) --S;
@@ -1357,7 +1197,7 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
       return launch_split(P, (int)grid, lds, (hipStream_t)stream, x4, plain);
     }
   }
-  return launch_w43(P, (int)grid, lds, (hipStream_t)stream, WM, x4, nl, fast, plain, u4);
+  return launch_w43(P, (int)grid, lds, (hipStream_t)stream, x4, fast, plain, u4);
 }
 
 extern "C" int gsd_conv3x3_w43(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst,

@@ -17,10 +17,6 @@
 
 #include <cstdlib>
 
-#ifndef GSD_WG_SCHED
-#define GSD_WG_SCHED 2   // 0: sched_barrier fences around the MFMA burst, 1: sched_group_barrier interleave, 2: hipcc's own order (fastest at 2 waves/SIMD)
-#endif
-
 struct WgradParams {
   SrcD a0, a1;  // B operand (activation)
   SrcD dy;      // A operand (gradient, plain)
@@ -132,37 +128,27 @@ __global__ __launch_bounds__(256) void convT_wgrad_kernel(const WgradParams P) {
 
 // -------------------------------------------------------------------------------------------------
 // conv3x3 dW, LDS-DMA form.  Both operand tiles go HBM/L2 -> LDS with global_load_lds_dword (no VGPR
-// staging).  Default (NBUF 1): one LDS image per block and two blocks per CU (<= 256 registers per lane): a
-// block's DMA issue + flight is covered by the other block's MFMAs -- measured 16 % faster than one block per
-// CU with a double-buffered image (NBUF 2), where the 64-80 DMA issues per stage sit on the MFMA critical path.  The
+// staging).  One LDS image per block and two blocks per CU (<= 256 registers per lane): a block's DMA issue +
+// flight is covered by the other block's MFMAs -- measured 16 % faster than one block per CU with a double-buffered
+// image, where the 64-80 DMA issues per stage sit on the MFMA critical path.  The
 // deferred BatchNorm+ReLU of the activation operand is applied after the ds_read, per lane (a lane's
 // input channel is fixed): b = max(fma(raw, scale, shift), lo).  Zero padding / out-of-segment
 // positions are DMA'd from a sentinel: quiet NaN for relu'd segments (max(NaN,0) = 0), 0 otherwise.
 // -------------------------------------------------------------------------------------------------
 __device__ const float gsd_pad[2] = {0.f, __builtin_nanf("")};
 
-// NBUF 1: one LDS image, 4 waves, two blocks per CU.   NBUF 2: two images, 4 waves, one block per CU.
-// NBUF 3: two images, 8 waves in two groups that SWAP ROLES every stage: one group multiplies stage s out of image
-//         s&1 while the other issues the DMA of stage s+1 into the other image and waits for it; the barrier at
-//         the end of the stage swaps them.  Loads never interrupt a multiplying wave, and the alternation is
-//         enforced instead of being left to how two independent blocks happen to drift (NBUF 1).  Each group
-//         accumulates the stages of its parity and writes its own slab.
-template <int WM, int WN, int NBUF>
-__global__ __launch_bounds__(NBUF == 3 ? 512 : 256, NBUF == 2 ? 1 : 2) void wgrad3x3_dma_kernel(const WgradParams P) {
+// KSP: <= 16 input channels: one 64 x 16ci tile, the 4 waves take every 4th k-step (each writes its own slab).
+template <int WM, int WN, bool KSP>
+__global__ __launch_bounds__(256, 2) void wgrad3x3_dma_kernel(const WgradParams P) {
   constexpr int MT = 4, NW = WM * WN;
-  constexpr bool SWAP = NBUF == 3;
-  constexpr bool KSP = NBUF == 4;   // <= 16 input channels: one 64 x 16ci tile, the 4 waves take every 4th k-step
   constexpr int BMw = WM * 64, BNw = KSP ? 16 : WN * 16, DS = 66;
-  static_assert(NW == 4, "4 waves per group");
+  static_assert(NW == 4, "4 waves per block");
   static_assert(!KSP || WM == 1, "k-split form is for M <= 64 tiles");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int XS = P.PS;
-  const int BUF = BMw * DS + BNw * XS;
 
   const int tid = threadIdx.x, lane = tid & 63;
-  const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wave = wave8 & 3;        // role inside the group: MFMA sub-tile and share of the DMA work
-  const int grp = wave8 >> 2;        // 0 / 1 (always 0 unless SWAP)
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6) & 3;   // MFMA sub-tile and share of the DMA work
   const int wm = KSP ? 0 : wave / WN, wn = KSP ? 0 : wave % WN;
   const int j = lane >> 4, l16 = lane & 15;
 
@@ -208,13 +194,13 @@ __global__ __launch_bounds__(NBUF == 3 ? 512 : 256, NBUF == 2 ? 1 : 2) void wgra
     }
   }
 
-  auto issue_dma = [&](int stage, int buf) {
+  auto issue_dma = [&](int stage) {
     const int tpi = P.tiles_y * P.tiles_x;
     const int n = stage / tpi;
     const int rs = stage - n * tpi;
     const int ty = rs / P.tiles_x;
     const int h0 = ty * P.TH, w0 = (rs - ty * P.tiles_x) * P.TW;
-    float* Ab = smem + buf * BUF;
+    float* Ab = smem;
     float* Bb = Ab + BMw * DS;
     const bool pix_ok = a_qin && (h0 + a_r) < P.H && (w0 + a_c) < P.W;
     const float* abase = P.dy.p + (long long)n * P.dy.ns + (long long)(h0 + a_r) * P.dy.W + (w0 + a_c);
@@ -257,7 +243,7 @@ __global__ __launch_bounds__(NBUF == 3 ? 512 : 256, NBUF == 2 ? 1 : 2) void wgra
   const int a_off = (wm * 64 + l16) * DS + j;
   const int b_off = BMw * DS + (wn * 16 + l16) * XS + j;
 
-  auto compute = [&](int cur) {
+  auto compute = [&]() {
     if constexpr (KSP) {
       const float* Ab = smem + a_off;
       const float* Bb = smem + b_off;
@@ -277,8 +263,8 @@ __global__ __launch_bounds__(NBUF == 3 ? 512 : 256, NBUF == 2 ? 1 : 2) void wgra
       }
       return;
     }
-    const float* Ab = smem + cur * BUF + a_off;
-    const float* Bb = smem + cur * BUF + b_off;
+    const float* Ab = smem + a_off;
+    const float* Bb = smem + b_off;
     int r = 0, c = 0;
     float an[MT], bn[9];
 #pragma unroll
@@ -307,58 +293,23 @@ __global__ __launch_bounds__(NBUF == 3 ? 512 : 256, NBUF == 2 ? 1 : 2) void wgra
 #pragma unroll
         for (int t = 0; t < 9; ++t) bn[t] = Bb[((s + 1 < nk) ? xb : 0) + (t / 3) * P.WC + (t % 3)];
       }
-#if GSD_WG_SCHED == 0
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      // hipcc's own instruction order: faster at 2 waves per SIMD than sched_barrier fences or a sched_group_barrier interleave
 #pragma unroll
       for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int t = 0; t < 9; ++t) acc[m][t] = mfma16(a[m], b[t], acc[m][t]);
-#if GSD_WG_SCHED == 0
-      __builtin_amdgcn_sched_barrier(0);
-#elif GSD_WG_SCHED == 1
-      // one MFMA, then a little of everything else: VALU / LDS reads issue in the shadow of the 32-cycle MFMAs
-#pragma unroll
-      for (int g = 0; g < 13; ++g) {
-        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // VALU
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-      }
-#pragma unroll
-      for (int g = 0; g < 23; ++g) {
-        __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      }
-#endif
     }
   };
 
   const int nst = s_end - s_begin;
-  if constexpr (SWAP) {
-    if (grp == 1 && nst > 0) issue_dma(s_begin, 0);
-    gsd_dma_barrier();
-    for (int it = 0; it < nst; ++it) {
-      const int cur = it & 1;
-      if (grp == cur) compute(cur);
-      else if (it + 1 < nst) issue_dma(s_begin + it + 1, cur ^ 1);
-      gsd_dma_barrier();  // the loaders' vmcnt(0) + barrier: image cur^1 is complete, image cur is free; roles swap
-    }
-  } else {
-    if (NBUF == 2 && nst > 0) issue_dma(s_begin, 0);
-    for (int it = 0; it < nst; ++it) {
-      const int cur = NBUF == 2 ? it & 1 : 0;   // NBUF 1 and 4: one image
-      gsd_dma_barrier();  // NBUF 2: this stage's DMA has landed, everyone left the other image; NBUF 1: everyone left the image
-      if (NBUF == 2) {
-        if (it + 1 < nst) issue_dma(s_begin + it + 1, cur ^ 1);
-      } else {
-        issue_dma(s_begin + it, 0);
-        gsd_dma_barrier();  // vmcnt(0) + barrier: the image is complete
-      }
-      compute(cur);
-    }
+  for (int it = 0; it < nst; ++it) {
+    gsd_dma_barrier();  // everyone left the image
+    issue_dma(s_begin + it);
+    gsd_dma_barrier();  // vmcnt(0) + barrier: the image is complete
+    compute();
   }
 
-  const int slab = SWAP ? split * 2 + grp : (KSP ? split * 4 + wave : split);
+  const int slab = KSP ? split * 4 + wave : split;
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -652,8 +603,8 @@ void choose_wgrad_tile(int H, int W, int* TH, int* TW) {
   // Stage = TH x TW pixels, TH*TW <= 64, TW % 4 == 0, halo window <= 256 positions.  First the least MFMA work
   // (stages * pixels per stage); then the WIDEST rows: a DMA instruction that covers one 256-byte row segment is
   // measurably faster than one that covers two 128-byte segments (TH 2 x TW 32 was 13 % slower than 1 x 64 although
-  // its halo traffic is a third lower) -- the cost is per cache line touched, not per byte.
-  const bool halo_first = gsd_env_set("GSD_WGRAD_HALO");
+  // its halo traffic is a third lower) -- the cost is per cache line touched, not per byte; preferring the least halo
+  // traffic instead measured slower.
   long min_work = -1;
   for (int pass = 0; pass < 2; ++pass) {
     long best = -1;
@@ -671,9 +622,7 @@ void choose_wgrad_tile(int H, int W, int* TH, int* TW) {
         continue;
       }
       if (work * 100 > min_work * 103) continue;
-      long cost;
-      if (halo_first) cost = stages * (long)((th + 2) * (tw + 2)) + ((tw < 32 && W >= 32) ? (1L << 40) : 0);
-      else cost = work * 1000 + stages * 10 - tw;
+      const long cost = work * 1000 + stages * 10 - tw;
       if (best < 0 || cost < best) {
         best = cost;
         *TH = th;
@@ -722,8 +671,8 @@ WgradPlan plan_wgrad(int mode, int N, int H, int W, int M, int Ncols) {
   if (splits > 2048) splits = 2048;
   if (splits < 1) splits = 1;
   p.splits = splits;
-  // conv3x3: the role-swap kernel writes two slabs per split (one per wave group)
-  p.slab_elems = (int64_t)splits * (mode == 0 ? (p.ksplit ? 36 : 18) : 1) * M * Ncols;
+  // conv3x3: 9 taps per slab, and the k-split form writes one slab per wave
+  p.slab_elems = (int64_t)splits * (mode == 0 ? (p.ksplit ? 36 : 9) : 1) * M * Ncols;
   return p;
 }
 
@@ -748,15 +697,15 @@ int launch_convT_wgrad(const WgradParams& P, int grid, size_t lds, hipStream_t s
   return GSD_OK;
 }
 
-template <int WM, int WN, int NBUF>
+template <int WM, int WN, bool KSP>
 int launch_dma(const WgradParams& P, int grid, size_t lds, hipStream_t st) {
   static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&wgrad3x3_dma_kernel<WM, WN, NBUF>)); e != hipSuccess) {
+  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&wgrad3x3_dma_kernel<WM, WN, KSP>)); e != hipSuccess) {
     gsd_set_error("gsd_conv3x3_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
     return GSD_ERR_HIP;
   }
   GSD_REQUIRE(lds <= 160 * 1024, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_wgrad: LDS tile %zu B too large", lds);
-  hipLaunchKernelGGL((wgrad3x3_dma_kernel<WM, WN, NBUF>), dim3(grid), dim3(NBUF == 3 ? 512 : 256), lds, st, P);
+  hipLaunchKernelGGL((wgrad3x3_dma_kernel<WM, WN, KSP>), dim3(grid), dim3(256), lds, st, P);
   GSD_LAUNCH_CHECK("gsd_conv3x3_wgrad");
   return GSD_OK;
 }
@@ -855,19 +804,12 @@ extern "C" int gsd_conv3x3_wgrad(const gsd_src* a, int nsrc, const gsd_src* dy, 
   for (int i = 0; i < nsrc; ++i)
     GSD_REQUIRE(a[i].scale == nullptr || a[i].relu != 0, GSD_ERR_UNSUPPORTED,
                 "gsd_conv3x3_wgrad: an affine activation segment must also have relu (zero padding uses a NaN sentinel)");
-  const int wmode = gsd_env_int("GSD_WGRAD_MODE", 1);   // 1 (default, fastest) / 2 / 3: see kernel
-  const int nslabs = pl.ksplit ? 4 * pl.splits : (wmode == 3 ? 2 * pl.splits : pl.splits);
+  const int nslabs = pl.ksplit ? 4 * pl.splits : pl.splits;
   int rc;
   if (pl.ksplit)
-    rc = launch_dma<1, 4, 4>(P, grid, lds, (hipStream_t)stream);
-  else if (wmode == 1)
-    rc = pl.wide ? launch_dma<1, 4, 1>(P, grid, lds, (hipStream_t)stream) : launch_dma<2, 2, 1>(P, grid, lds, (hipStream_t)stream);
-  else if (wmode == 2)
-    rc = pl.wide ? launch_dma<1, 4, 2>(P, grid, 2 * lds, (hipStream_t)stream)
-                 : launch_dma<2, 2, 2>(P, grid, 2 * lds, (hipStream_t)stream);
+    rc = launch_dma<1, 4, true>(P, grid, lds, (hipStream_t)stream);
   else
-    rc = pl.wide ? launch_dma<1, 4, 3>(P, grid, 2 * lds, (hipStream_t)stream)
-                 : launch_dma<2, 2, 3>(P, grid, 2 * lds, (hipStream_t)stream);
+    rc = pl.wide ? launch_dma<1, 4, false>(P, grid, lds, (hipStream_t)stream) : launch_dma<2, 2, false>(P, grid, lds, (hipStream_t)stream);
   if (rc) return rc;
   launch_wgrad_reduce<0>(workspace, dw, nslabs, Cout, Cin, (hipStream_t)stream);
   GSD_LAUNCH_CHECK("gsd_conv3x3_wgrad reduce");

@@ -174,9 +174,8 @@ class UNetEngine:
     # Library switches that change launch plans (tile shapes, partial-row counts, slab counts, the form a launch takes): partials,
     # conv_ws and the weight-gradient workspaces are sized from them, so they are part of the shape key -- a switch flipped
     # between two steps (a test's monkeypatch, a sweep in one process) re-sizes the buffers instead of overrunning them
-    _SIZING_ENV = ("GSD_W2D_WAVES", "GSD_W2D_TW", "GSD_W2D_TW8_PCT", "GSD_W43_TW", "GSD_W43_FOLD", "GSD_CONV_W2D", "GSD_CONV_ALGO",
-                   "GSD_W43_SPLIT", "GSD_WGRAD_ALGO", "GSD_WGRAD_W2D", "GSD_WG2D_KX", "GSD_WG2D_BLOCKS", "GSD_WGRAD_BLOCKS",
-                   "GSD_WG43_TW", "GSD_WG43_SMALL")
+    _SIZING_ENV = ("GSD_W2D_TW", "GSD_W2D_TW8_PCT", "GSD_W43_TW", "GSD_W43_FOLD", "GSD_CONV_W2D", "GSD_CONV_ALGO", "GSD_W43_SPLIT",
+                   "GSD_WGRAD_ALGO", "GSD_WGRAD_W2D", "GSD_WG2D_KX", "GSD_WG2D_BLOCKS", "GSD_WGRAD_BLOCKS", "GSD_WG43_TW")
 
     def _ensure(self, n: int, h: int, w: int, dev: torch.device, train: bool) -> None:
         key = (n, h, w, str(dev), tuple(os.environ.get(k) for k in self._SIZING_ENV))

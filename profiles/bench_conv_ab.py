@@ -1,7 +1,7 @@
 """A/B of tuning variants of the fp32 Winograd conv3x3 kernel on the U-Net's layer shapes, all in ONE process (interleaved
 rounds), each checked against the direct-tap kernel.
 usage (GPU box): PYTHONPATH=. python profiles/bench_conv_ab.py B W0 "NAME:ENV=V,ENV=V;NAME:..." [rounds]
-   e.g. python profiles/bench_conv_ab.py 32 427 "base:GSD_W43_NL=0;lw1:GSD_W43_NL=1;lw2:GSD_W43_NL=2" """
+   e.g. python profiles/bench_conv_ab.py 32 427 "base:GSD_W43_U4=0;u4:GSD_W43_U4=1;u4all:GSD_W43_U4=2" """
 import os
 import sys
 import torch
