@@ -114,6 +114,8 @@ SIGNATURES = {
     "gsd_conv3x3_wgrad_bn_supported": (_I, [_I, _I, _I, _I, _I]),
     "gsd_conv3x3_wgrad_bn_workspace": (_L, [_I, _I, _I, _I, _I]),
     "gsd_conv3x3_wgrad_bn": (_I, [_SRC, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _L, _I, _I, _I, _P]),
+    "gsd_conv3x3_dgrad_bn_supported": (_I, [_I, _I, _I, _I, _I]),
+    "gsd_conv3x3_dgrad_bn": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _P]),
     "gsd_convT2x2_wgrad_workspace": (_L, [_I, _I, _I, _I, _I]),
     "gsd_convT2x2_wgrad": (_I, [_SRC, _SRC, _I, _I, _P, _P, _P, _L, _I, _I, _I, _P]),
     "gsd_bn_reduce_partials": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -121,6 +123,7 @@ SIGNATURES = {
     "gsd_add_counters": (_I, [C.POINTER(C.c_void_p), _I, _L, _P]),
     "gsd_bn_finalize": (_I, [_P, _I, _D, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _GUARD, _P]),
     "gsd_bn_eval_coeffs": (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _P]),
+    "gsd_bn_eval_coeffs_bwd": (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P]),
     "gsd_bn_bwd_partial_rows": (_I, [_I, _I, _I, _I]),
     "gsd_bn_bwd_reduce": (_I, [_I, _P, _P, _P, _P, _P, _SRC, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "gsd_bn_bwd_reduce_partials": (_I, [_P, _I, _I, _P, _P]),

@@ -636,6 +636,27 @@ extern "C" int gsd_bn_eval_coeffs(const float* gamma, const float* beta, const f
   return GSD_OK;
 }
 
+__global__ void bn_eval_coeffs_bwd_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
+                                          int C, float* scale, float* shift, float* mean, float* invstd) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float sc = gamma[c] / sqrtf(rv[c] + eps);   // bn_eval_coeffs_kernel's expressions
+  scale[c] = sc;
+  shift[c] = beta[c] - rm[c] * sc;
+  mean[c] = rm[c];
+  invstd[c] = 1.f / sqrtf(rv[c] + eps);
+}
+extern "C" int gsd_bn_eval_coeffs_bwd(const float* gamma, const float* beta, const float* running_mean,
+                                      const float* running_var, float eps, int C, float* scale, float* shift, float* mean,
+                                      float* invstd, void* stream) {
+  GSD_REQUIRE(gamma && beta && running_mean && running_var && scale && shift && mean && invstd && C > 0, GSD_ERR_BAD_ARG,
+              "gsd_bn_eval_coeffs_bwd: bad argument");
+  hipLaunchKernelGGL(bn_eval_coeffs_bwd_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, gamma, beta,
+                     running_mean, running_var, eps, C, scale, shift, mean, invstd);
+  GSD_LAUNCH_CHECK("gsd_bn_eval_coeffs_bwd");
+  return GSD_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // BatchNorm + ReLU (+ max-pool / 1x1 output conv) backward, pass 1
 // ---------------------------------------------------------------------------------------------

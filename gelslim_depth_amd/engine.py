@@ -27,6 +27,7 @@ from ._lib import lib, check
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
+GSD_ERR_UNSUPPORTED = -2   # include/gsd.h
 
 
 def _r64(c: int) -> int:
@@ -150,7 +151,8 @@ class UNetEngine:
         self._dev = None
         self.sync_fn: Optional[Callable[[torch.Tensor], None]] = None   # SyncBN hook: all-reduce fp64 sums in place
         self.world = 1
-        self._saved_train = False
+        self._saved = False        # the last forward kept what a backward needs (train mode, or eval mode with keep=True)
+        self._saved_eval = False   # ... and ran in eval mode: BatchNorm normalised with the running statistics
         self.block_done_cb: Optional[Callable[[str], None]] = None   # data-parallel hook: a block's grads are final
         self._nbt: list = []   # num_batches_tracked buffers of the current train-mode forward
         self.guard = None          # non-finite guard of the current step (_lib.make_guard), set by TrainStep per step
@@ -218,6 +220,12 @@ class UNetEngine:
             need = max(lib.gsd_weight_layout_size(f.mode_f, u.cout, u.cin) for f in u.forms_f.values())
             if u.wt_f is None or u.wt_f.numel() != need or u.wt_f.device != dev:
                 u.wt_f = torch.empty((need,), **f32)
+            if not u.need_dgrad and train:
+                # the first layer's dX runs only for an input gradient; where gsd_conv3x3_dgrad_bn does not take over (u.fused_dw
+                # off) it is the direct form on the materialised d_raw (_input_dgrad)
+                need = lib.gsd_weight_layout_size(1, u.cout, u.cin)
+                if u.wt_d is None or u.wt_d.numel() != need or u.wt_d.device != dev:
+                    u.wt_d = torch.empty((need,), **f32)
             if u.need_dgrad:
                 need = lib.gsd_weight_layout_size(u.form_d.mode_d, u.cout, u.cin)
                 if u.wt_d is None or u.wt_d.numel() != need or u.wt_d.device != dev:
@@ -297,7 +305,8 @@ class UNetEngine:
     def _act_src(u: _Unit) -> L.gsd_src:
         return L.make_src(u.raw, u.scale, u.shift, relu=True, slack=L.SLACK)
 
-    def _run_unit(self, u: _Unit, srcs: List[L.gsd_src], P: Dict[str, torch.Tensor], train: bool, st: int) -> None:
+    def _run_unit(self, u: _Unit, srcs: List[L.gsd_src], P: Dict[str, torch.Tensor], train: bool, st: int,
+                  keep: bool = False) -> None:
         n = u.raw.shape[0]
         lh, lw = self.hs[u.level], self.ws[u.level]
         u.form_f = u.forms_f[train]
@@ -335,6 +344,11 @@ class UNetEngine:
                                       self.guard, st),
                   "bn_finalize")
             self._nbt.append(P[u.nbtname])   # int64 counter buffers (BatchNorm2d.num_batches_tracked): one add for all, below
+        elif keep:   # a backward follows: also the running statistics as mean / invstd (same scale / shift bits)
+            check(lib.gsd_bn_eval_coeffs_bwd(P[u.gname].data_ptr(), P[u.bname].data_ptr(), P[u.rmname].data_ptr(),
+                                             P[u.rvname].data_ptr(), BN_EPS, u.cout, u.scale.data_ptr(), u.shift.data_ptr(),
+                                             u.mean.data_ptr(), u.invstd.data_ptr(), st),
+                  "bn_eval_coeffs_bwd")
         else:
             check(lib.gsd_bn_eval_coeffs(P[u.gname].data_ptr(), P[u.bname].data_ptr(), P[u.rmname].data_ptr(),
                                          P[u.rvname].data_ptr(), BN_EPS, u.cout, u.scale.data_ptr(), u.shift.data_ptr(), st),
@@ -372,19 +386,24 @@ class UNetEngine:
         return dy // 2, dx // 2
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], train: bool, out: Optional[torch.Tensor] = None
-                ) -> torch.Tensor:
-        """P: name -> tensor for every state_dict entry (reference names). Returns (N, n_classes, H, W)."""
+    def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], train: bool, out: Optional[torch.Tensor] = None,
+                keep: bool = False) -> torch.Tensor:
+        """P: name -> tensor for every state_dict entry (reference names). Returns (N, n_classes, H, W).
+        keep (eval mode): also keep what a backward() needs -- the launches and output bits are those of the plain eval forward
+        (the eval forms, scale / shift from the running statistics; nothing updates the running statistics), the backward
+        buffers are allocated and every unit's mean / invstd hold the running statistics."""
         if x.dtype != torch.float32 or not x.is_cuda:
             raise L.GsdError("UNetEngine.forward needs a float32 tensor on the GPU (no CPU fallback)")
         self._nbt = []
         x = x.contiguous()
         n, c, h, w = x.shape
         assert c == self.n_channels, f"expected {self.n_channels} input channels, got {c}"
-        self._ensure(n, h, w, x.device, train)
+        keep = keep and not train
+        self._ensure(n, h, w, x.device, train or keep)
         st = L.stream_ptr()
         self._x = x
-        self._saved_train = train
+        self._saved = train or keep
+        self._saved_eval = keep
         self.generation += 1       # every forward overwrites the saved activations
         if self.batch_wl:          # every forward-mode weight layout of the pass: the 2-D Winograd images in one launch
             self._layouts([(u.forms_f[train].mode_f, P[u.wname], u.cout, u.cin, u.wt_f) for u in self.units] +
@@ -404,8 +423,8 @@ class UNetEngine:
                 check(lib.gsd_maxpool2(C.byref(s), self.pooled[lvl].data_ptr(), n, prev.cout, self.hs[lvl - 1],
                                        self.ws[lvl - 1], st), "maxpool2")
                 srcs = [L.make_src(self.pooled[lvl], slack=L.SLACK)]
-            self._run_unit(u0, srcs, P, train, st)
-            self._run_unit(u1, [self._act_src(u0)], P, train, st)
+            self._run_unit(u0, srcs, P, train, st, keep)
+            self._run_unit(u1, [self._act_src(u0)], P, train, st, keep)
         if self.L == 0 and region is not None:          # a one-level network (profiles/inc_block.py): the block ends here
             e = torch.cuda.Event(enable_timing=True)
             e.record()
@@ -422,8 +441,9 @@ class UNetEngine:
                                    self.hs[lvl + 1], self.ws[lvl + 1], st), "convT2x2")
             skip = self.enc[lvl][1]
             u0, u1 = self.dec[j]
-            self._run_unit(u0, [self._act_src(skip), L.make_src(up.out, off=self._pad_off(lvl), slack=L.SLACK)], P, train, st)
-            self._run_unit(u1, [self._act_src(u0)], P, train, st)
+            self._run_unit(u0, [self._act_src(skip), L.make_src(up.out, off=self._pad_off(lvl), slack=L.SLACK)], P, train, st,
+                           keep)
+            self._run_unit(u1, [self._act_src(u0)], P, train, st, keep)
             cur = u1
         if self._nbt:
             L.add_counters(self._nbt, 1)        # one libgsd launch for every BatchNorm layer's counter
@@ -464,6 +484,11 @@ class UNetEngine:
                                           G[u.bname].data_ptr(), None if dwout is None else dwout.data_ptr(),
                                           u.c1.data_ptr(), u.c2.data_ptr(), st),
                   "bn_bwd_finalize")
+        if self._saved_eval:
+            # eval-mode BatchNorm is the affine map raw * scale + shift: d_raw = scale * dz, i.e. the train-mode expression with
+            # c1 = c2 = 0 (dgamma = sum dz * xhat and dbeta = sum dz above hold as they are, xhat from the running statistics)
+            u.c1.zero_()
+            u.c2.zero_()
         if u.fused_dw:
             self._on_side(lambda sst, ws: check(
                 lib.gsd_conv3x3_wgrad_bn(u.srcs, u.g.data_ptr(), u.raw.data_ptr(), u.scale.data_ptr(), u.mean.data_ptr(),
@@ -574,11 +599,53 @@ class UNetEngine:
               "conv3x3_dgrad_bnrelu")
         self._log_end(ev, u.cin, u.cout, n, lh, lw, u.form_d.algo)
 
-    def backward(self, dout: torch.Tensor, P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor]) -> None:
+    def _input_dgrad(self, u: _Unit, P, dx: torch.Tensor, st: int) -> None:
+        """dX of the first conv (the gradient w.r.t. the network's input) into dx, after u's BatchNorm backward is final.
+        u.fused_dw: d_raw was never stored, gsd_conv3x3_dgrad_bn forms it from dz and raw.  Otherwise gsd_bn_bwd_apply has left it
+        in u.dsrc and the general direct-form dX runs on it."""
+        n = u.raw.shape[0]
+        lh, lw = self.hs[u.level], self.ws[u.level]
+        if u.fused_dw:
+            check(lib.gsd_conv3x3_dgrad_bn(u.g.data_ptr(), u.raw.data_ptr(), u.scale.data_ptr(), u.mean.data_ptr(),
+                                           u.invstd.data_ptr(), u.c1.data_ptr(), u.c2.data_ptr(), P[u.wname].data_ptr(), u.cin,
+                                           u.cout, dx.data_ptr(), n, lh, lw, st), "conv3x3_dgrad_bn")
+            return
+        check(lib.gsd_weight_layout(1, P[u.wname].data_ptr(), u.cout, u.cin, u.wt_d.data_ptr(), st), "weight_layout")
+        s = L.src_array([L.make_src(u.dsrc)])
+        rc = lib.gsd_conv3x3(s, 1, u.wt_d.data_ptr(), u.cout, u.cin, L.dst_array([L.make_dst(dx)]), 1, None, n, lh, lw, st)
+        if rc == GSD_ERR_UNSUPPORTED:
+            raise NotImplementedError(f"gelslim_depth_amd.UNet: no kernel computes the input gradient of the first conv3x3 at "
+                                      f"N={n} H={lh} W={lw} Cin={u.cin} Cout={u.cout}: "
+                                      + lib.gsd_last_error().decode("utf-8", "replace"))
+        check(rc, "conv3x3 dgrad (input)")
+
+    def input_grad_supported(self, n: int, h: int, w: int) -> bool:
+        """Whether backward(..., dx=...) has a kernel for an (n, n_channels, h, w) input: gsd_conv3x3_dgrad_bn when the first
+        layer's fused dW is on (it serves every shape that one does), else the direct-form dX (any shape the direct form serves)."""
+        u = self.enc[0][0]
+        if lib.gsd_conv3x3_wgrad_bn_supported(n, h, w, u.cin, u.cout):
+            return bool(lib.gsd_conv3x3_dgrad_bn_supported(n, h, w, u.cin, u.cout))
+        return h < 32768 and w < 32768
+
+    def backward(self, dout: torch.Tensor, P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor],
+                 dx: Optional[torch.Tensor] = None) -> None:
         """dout: (N, n_classes, H, W) gradient of the loss w.r.t. the output.
-        G: name -> tensor to receive every parameter's gradient (overwritten, not accumulated)."""
-        if not self._saved_train:
+        G: name -> tensor to receive every parameter's gradient (overwritten, not accumulated).
+        dx: optional contiguous fp32 (N, n_channels, H, W) tensor to receive the gradient w.r.t. the input (overwritten).
+        After an eval-mode forward(keep=True) the gradients are those of eval-mode BatchNorm (an affine map with the running
+        statistics); nothing is all-reduced there, so a data-parallel engine (sync_fn set) refuses that case."""
+        if not self._saved:
             raise L.GsdError("backward() needs a preceding train-mode forward()")
+        if self._saved_eval and self.sync_fn is not None:
+            raise NotImplementedError("UNetEngine.backward after an eval-mode forward is single-process only (sync_fn is set)")
+        if dx is not None:
+            x = self._x
+            if dx.shape != x.shape or dx.dtype != torch.float32 or not dx.is_contiguous() or dx.device != x.device:
+                raise L.GsdError(f"backward(dx=...): expected a contiguous float32 {tuple(x.shape)} tensor on {x.device}")
+            u = self.enc[0][0]
+            if u.fused_dw and not lib.gsd_conv3x3_dgrad_bn_supported(x.shape[0], x.shape[2], x.shape[3], u.cin, u.cout):
+                raise NotImplementedError(f"gelslim_depth_amd.UNet: no kernel computes the input gradient at input shape "
+                                          f"{tuple(x.shape)} with {u.cout} first-layer channels")
         dout = dout.contiguous()
         st = L.stream_ptr()
         n = dout.shape[0]
@@ -646,6 +713,8 @@ class UNetEngine:
             dwout = None
             self._dgrad_fused(u1, u0, P, st)
             self._bn_bwd_tail(u0, P, G, st, fused=True)
+            if lvl == 0 and dx is not None:
+                self._input_dgrad(u0, P, dx, st)   # c1 / c2 are final; the first layer's dW runs beside it on the side stream
             self._announce(f"enc{lvl}")
             if lvl > 0:
                 self._dgrad(u0, P, [L.make_dst(self.dpooled[lvl])], st)

@@ -6,7 +6,12 @@ Boundary reproduced (reference file:line, /root/reference/):
   * attributes   n_channels, n_classes, bilinear                           unet.py:63-65
   * forward(x)   accepts the `x=` keyword (train_utils/train_unet.py:347,
                  test_utils/test_depth_estimation.py:17); returns fp32 (N, n_classes, H, W) on x's device,
-                 differentiable w.r.t. the parameters in train mode
+                 differentiable w.r.t. the parameters in train mode, and w.r.t. x (fp32 only, not while a TrainStep owns
+                 the gradients) in train and in eval mode
+                 when x.requires_grad is set.  In eval mode that graph also yields the parameters' gradients under
+                 eval-mode BatchNorm (the running statistics, which it does not update); an eval-mode forward of an x that
+                 does not require grad builds no graph and returns a detached output (the reference would still track the
+                 parameters there)
   * state_dict   the reference's 118 keys / shapes / dtypes, so its .pth files load with strict=True
                  (test_depth_estimation.py:63): the module tree below has the same attribute names and
                  Sequential indices (double_conv.{0,1,3,4}, maxpool_conv.1, up.{j}.up, up.{j}.conv, outc.conv)
@@ -105,12 +110,18 @@ class OutConv(nn.Module):
 
 
 class _UNetFunction(torch.autograd.Function):
-    """The whole U-Net as one autograd node: forward = engine.forward, backward = engine.backward."""
+    """The whole U-Net as one autograd node: forward = engine.forward, backward = engine.backward.  train=False: the eval-mode
+    forward (same bits as the no-grad one) that keeps what the backward needs; the backward then differentiates eval-mode
+    BatchNorm.  The gradient w.r.t. x is computed only when autograd asks for it."""
 
     @staticmethod
-    def forward(ctx, module: "UNet", x: torch.Tensor, *params: torch.Tensor):
+    def forward(ctx, module: "UNet", train: bool, x: torch.Tensor, *params: torch.Tensor):
         P = module._tensor_map()
-        out = module._engine.forward(x, P, train=True)
+        if train:   # (the bf16 engine takes this path only: it has no eval backward and no input gradient)
+            out = module._engine.forward(x, P, train=True)
+        else:
+            out = module._engine.forward(x, P, train=False, keep=True)
+        ctx.xshape = tuple(x.shape)
         ctx.module = module
         ctx.pnames = module._pnames
         ctx.engine = module._engine
@@ -130,8 +141,13 @@ class _UNetFunction(torch.autograd.Function):
                 "forward/backward pairs.")
         P = module._tensor_map()
         G = module._grad_targets()
-        module._engine.backward(dout, P, G)
-        return (None, None) + tuple(G[n] for n in ctx.pnames)
+        dx = None
+        if ctx.needs_input_grad[2]:
+            dx = torch.empty(ctx.xshape, device=dout.device, dtype=torch.float32)
+            module._engine.backward(dout, P, G, dx=dx)
+        else:
+            module._engine.backward(dout, P, G)
+        return (None, None, dx) + tuple(G[n] for n in ctx.pnames)
 
 
 class UNet(nn.Module):
@@ -195,13 +211,25 @@ class UNet(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("gelslim_depth_amd.UNet runs on an MI355X through libgsd; move the model and the input "
                                "to the GPU (there is no CPU path in this package)")
-        if x.requires_grad and torch.is_grad_enabled():
-            # the reference module is differentiable w.r.t. its input (unet.py:79-88); nothing in the reference asks for that
-            # gradient (train_unet.py:344-347) and the first convolution's dX is not built: say so instead of returning None
-            raise NotImplementedError("gelslim_depth_amd.UNet does not compute the gradient with respect to its input "
-                                      "(x.requires_grad is set); detach x, or use the reference model for input gradients")
+        input_grad = x.requires_grad and torch.is_grad_enabled()
+        if input_grad:
+            # the reference module is differentiable w.r.t. its input (unet.py:79-88) in train and in eval mode
+            if self._grad_views:
+                # a TrainStep owns this model's gradients (its flat arena, reused every step): the input gradient is built for
+                # the module's own autograd path only
+                raise NotImplementedError("gelslim_depth_amd.UNet does not compute the gradient with respect to its input "
+                                          "while a TrainStep owns its gradients (x.requires_grad is set); detach x, or use a "
+                                          "model without a TrainStep for input gradients")
+            if self.precision != "fp32":
+                raise NotImplementedError("gelslim_depth_amd.UNet: the gradient with respect to its input is fp32-only "
+                                          f"(precision={self.precision!r} and x.requires_grad is set); use precision='fp32' "
+                                          "or detach x")
+            n, _, h, w = x.shape
+            if not self._engine.input_grad_supported(n, h, w):
+                raise NotImplementedError(f"gelslim_depth_amd.UNet: no kernel computes the gradient with respect to an input "
+                                          f"of shape {tuple(x.shape)}; detach x")
         x = x.float()
-        if self.training and torch.is_grad_enabled():
-            return _UNetFunction.apply(self, x, *self.parameters())
+        if torch.is_grad_enabled() and (self.training or input_grad):
+            return _UNetFunction.apply(self, self.training, x, *self.parameters())
         with torch.no_grad():
             return self._engine.forward(x, self._tensor_map(), train=self.training)

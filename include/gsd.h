@@ -267,6 +267,17 @@ int gsd_conv3x3_wgrad_bn(const gsd_src* a, const float* dz, const float* raw, co
                          const float* mean, const float* invstd, const float* c1, const float* c2,
                          int Cin, int Cout, float* dw, float* workspace, int64_t workspace_elems,
                          int N, int H, int W, void* stream);
+/* dX of the same few-input-channel conv3x3 (Cin * 9 <= 32: the network's first layer) with the same BatchNorm backward applied
+ * on the fly: dx = conv3x3_dX(d_raw, w), d_raw = scale * (dz - c1 - (raw - mean) * invstd * c2) formed in registers exactly as
+ * gsd_conv3x3_wgrad_bn forms it (scale == raw == NULL: dz is the conv output's gradient as it is).  dz, raw: contiguous
+ * (N,Cout,H,W); w: the reference's (Cout,Cin,3,3) weights, no layout pass; dx: contiguous (N,Cin,H,W), every element written.
+ * Deterministic (no atomics), no workspace.  Replaces the dX half of aten::convolution_backward at unet.py:11 for `inc` plus the
+ * apply half of aten::native_batch_norm_backward -- the gradient with respect to the network's input.
+ * gsd_conv3x3_dgrad_bn_supported: 1 when the shape is served (Cin * 9 <= 32, 1 <= Cout <= 65535). */
+int gsd_conv3x3_dgrad_bn_supported(int N, int H, int W, int Cin, int Cout);
+int gsd_conv3x3_dgrad_bn(const float* dz, const float* raw, const float* scale, const float* mean,
+                         const float* invstd, const float* c1, const float* c2, const float* w,
+                         int Cin, int Cout, float* dx, int N, int H, int W, void* stream);
 /* dW and db of ConvTranspose2d(k2,s2): x (h,w) with deferred BN, dy (2h,2w) plain;
  * dW in the reference's (Ci,Co,2,2) layout. */
 int64_t gsd_convT2x2_wgrad_workspace(int N, int H, int W, int Cin, int Cout);
@@ -297,6 +308,12 @@ int gsd_bn_finalize(const double* sums, int C, double count, const float* gamma,
 /* eval mode: (scale, shift) from running stats. */
 int gsd_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean,
                        const float* running_var, float eps, int C, float* scale, float* shift, void* stream);
+
+/* eval mode with a backward to follow: gsd_bn_eval_coeffs's (scale, shift) -- the same fp32 expressions, so the same bits --
+ * plus mean = running_mean and invstd = 1 / sqrt(running_var + eps), the statistics the backward kernels normalise with. */
+int gsd_bn_eval_coeffs_bwd(const float* gamma, const float* beta, const float* running_mean,
+                           const float* running_var, float eps, int C, float* scale, float* shift,
+                           float* mean, float* invstd, void* stream);
 
 /* Backward of relu(bn(raw)), pass 1.  dz = da * [raw*scale+shift > 0]; writes dz and per-block
  * partials of (sum dz, sum dz*xhat) [+ sum dout*a for mode OUTC].
