@@ -245,15 +245,9 @@ __device__ __forceinline__ void w43_epilogue(const W43Params& P, int n, int pt, 
 // sources of the forward): the operand transform drops its 12 fma/max per kernel row and the per-chunk scale / shift
 // reads.  Measured with the transform forced plain over the layer set: -2.5 % kernel time.
 //
-// X4M = 2 ("U4"): the halo moves as 16-byte pieces straight from UNALIGNED rows (a global_load_lds_dwordx4 takes any 4-byte
-// aligned global address at full rate, profiles/ubench/dma_global_align.hip).  The four channel planes of a chunk lie back to
-// back in LDS (plane = PS / 4 pieces: WR rows x WCp / 4 pieces + the bank-spread dummies) and an instruction's 64 lanes are 64
-// consecutive pieces of that image: ceil(PS / 64) (7 for a 6 x 68 window) instead of 32 exec-masked dword instructions per
-// chunk and block.  Pieces wholly outside the image come from a 16-byte sentinel (no prefilled padding, nothing masked);
-// a piece that STRADDLES the left or right image edge is loaded as it lies in memory (the caller vouches for 4 readable floats
-// around the tensor: gsd_src.slack) and the lane that moved it overwrites its outside floats with the padding value once its
-// own fills have landed (vmcnt(0)), in front of the chunk's barrier.  Ablation (fills removed, profiles/build_diag.sh
-// -DW43_ABL): the dword halo fills cost 9.5 % of the kernel's time, the weight fills 3 %, the barrier 2 %.
+// X4M: 0 the dword halo gathers, 1 the X4 form above.  Ablation (fills removed, profiles/build_diag.sh -DW43_ABL): the dword halo
+// fills cost 9.5 % of the kernel's time, the weight fills 3 %, the barrier 2 % -- memory traffic and latency, not instruction
+// count: 16-byte pieces from unaligned rows were measured neutral over the step (docs/LOG_r01-r04.md).
 //
 // SPLIT ("K slabs"): a launch whose tile grid covers a fraction of the chip's 512 block slots (the 40 x 53 and 20 x 26 levels at
 // small per-GPU batches: 152-600 blocks of 128-256 chunks each) is cut along the input channels instead: block (tile, slab k)
@@ -267,13 +261,12 @@ template <int X4M, bool FAST, bool PLAIN, bool SPLIT = false>
 #define W43_MIN_WAVES 2
 #endif
 __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W43Params P) {
-  constexpr bool X4 = X4M == 1, U4 = X4M == 2;
-  static_assert(!U4 || FAST, "unaligned 16-byte halo pieces: the straight-fill form");
-  static_assert(!SPLIT || (FAST && !U4), "K slabs: the straight-fill form");
+  constexpr bool X4 = X4M == 1;
+  static_assert(!SPLIT || FAST, "K slabs: the straight-fill form");
   constexpr int MT = 4, BM = W43_BM, WS = BM, WTILE = W43_WTILE, NT = 256, NWAVE = 4, NWI = W43_NWI;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int PS = P.PS;
-  const int BUF = U4 ? WTILE + P.NI * 256 : WTILE + 4 * PS;   // U4: whole 64-piece instructions
+  const int BUF = WTILE + 4 * PS;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -362,51 +355,6 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
       }
     }
   }
-  // U4: instruction i = wave + 4 k of a chunk moves pieces 64 i .. 64 i + 63 of the chunk's [4 planes][PS / 4 pieces] image.
-  // Per source segment: the lane's float offset from the chunk's first channel plane (W43_SENT: sentinel piece) and the floats of
-  // the piece that lie outside the image (bits 0..3: patched with the padding value after landing).
-  constexpr int KH = 2, W43_SENT = -2147483647 - 1;
-  int h_off0[KH], h_off1[KH], h_pm0[KH], h_pm1[KH];
-  bool u_patch = false;   // block constant: some window row has a piece that straddles the left or right edge of a segment
-  if constexpr (U4) {
-    const int o0 = w0 - 1 - P.src0.ow, o1 = w0 - 1 - P.src1.ow;
-    u_patch = (o0 < 0 && (-o0 & 3)) || (P.src0.W > o0 && P.src0.W < o0 + P.WCp && ((P.src0.W - o0) & 3));
-    if (P.src1.C > 0) u_patch = u_patch || (o1 < 0 && (-o1 & 3)) || (P.src1.W > o1 && P.src1.W < o1 + P.WCp && ((P.src1.W - o1) & 3));
-    const int NPr = P.WCp >> 2, NPc = PS >> 2;
-#pragma unroll
-    for (int k = 0; k < KH; ++k) {
-      const int i = wave8 + 4 * k;
-      const int pid = 64 * i + lane;
-      const int ch = pid / NPc, pq = pid - ch * NPc;
-      const int row = pq / NPr, pc = pq - row * NPr;
-      h_off0[k] = h_off1[k] = W43_SENT;   // (an offset of -1 is a real one: the piece in front of the tensor's first row)
-      h_pm0[k] = h_pm1[k] = 0;
-      if (i < P.NI && ch < 4 && row < P.WR) {
-        int nn, gh;
-        w43_row(P, n, h0 - 1 + row, nn, gh);
-        const int gw = w0 - 1 + 4 * pc;
-        const int fo0 = P.fold ? nn * (int)P.src0.ns : 0, fo1 = P.fold ? nn * (int)P.src1.ns : 0;
-        int hs = gh - P.src0.oh, c0 = gw - P.src0.ow;
-        if ((unsigned)hs < (unsigned)P.src0.H && c0 + 3 >= 0 && c0 < P.src0.W) {
-          h_off0[k] = ch * (int)P.src0.cs + fo0 + hs * P.src0.ws + c0;
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (c0 + e < 0 || c0 + e >= P.src0.W) h_pm0[k] |= 1 << e;
-        }
-        hs = gh - P.src1.oh;
-        c0 = gw - P.src1.ow;
-        if (P.src1.C > 0 && (unsigned)hs < (unsigned)P.src1.H && c0 + 3 >= 0 && c0 < P.src1.W) {
-          h_off1[k] = ch * (int)P.src1.cs + fo1 + hs * P.src1.ws + c0;
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (c0 + e < 0 || c0 + e >= P.src1.W) h_pm1[k] |= 1 << e;
-        }
-      }
-    }
-  }
-  const float* u_base = P.src0.p + (long long)n * P.src0.ns;   // U4: first channel plane of the next chunk to fill
-  const float* u_sent = P.src0.relu ? &gsd_pad16_w43[4] : &gsd_pad16_w43[0];
-  long long u_cs = P.src0.cs;
   const float* wsrc0 = P.wt + (size_t)mbb * P.nchunks * WTILE;   // the block's weight image
   const long long wlane = tid * 4;   // this lane's float offset inside a 1 KiB weight piece group
   long long xl0[NPP];   // first segment's offsets as 64-bit lane values (the address add is then a single instruction)
@@ -414,26 +362,23 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
   for (int pp = 0; pp < NPP; ++pp) xl0[pp] = xo0[pp];
   // SPLIT: a slab that lies wholly in the second (concat) segment starts there -- its padding positions, plane pointer and lane offsets
   const bool s1_start = SPLIT && P.src1.C > 0 && c_lo * 4 > P.src0.C;
-  if constexpr (!U4)
-  {
-    // padding positions of the first segment, once, in all 2 x 4 channel planes (own positions only: the lanes that
-    // would otherwise DMA the sentinel there on every fill); visible to the consumers after the first barrier
-    const float pad0 = (s1_start ? P.src1.relu : P.src0.relu) ? __builtin_nanf("") : 0.f;
+  // padding positions of the first segment, once, in all 2 x 4 channel planes (own positions only: the lanes that
+  // would otherwise DMA the sentinel there on every fill); visible to the consumers after the first barrier
+  const float pad0 = (s1_start ? P.src1.relu : P.src0.relu) ? __builtin_nanf("") : 0.f;
 #pragma unroll
-    for (int pp = 0; pp < NPP; ++pp)
-      if (p_on[pp] && (s1_start ? xo1[pp] : xo0[pp]) == -1) {
+  for (int pp = 0; pp < NPP; ++pp)
+    if (p_on[pp] && (s1_start ? xo1[pp] : xo0[pp]) == -1) {
 #pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          if constexpr (X4) {   // the unit's own plane: the other planes' pieces belong to other units
+      for (int b = 0; b < 2; ++b) {
+        if constexpr (X4) {   // the unit's own plane: the other planes' pieces belong to other units
 #pragma unroll
-            for (int e = 0; e < 4; ++e) smem[b * BUF + WTILE + u_ch[pp] * PS + u_lds[pp] + lane * 4 + e] = pad0;
-          } else {
+          for (int e = 0; e < 4; ++e) smem[b * BUF + WTILE + u_ch[pp] * PS + u_lds[pp] + lane * 4 + e] = pad0;
+        } else {
 #pragma unroll
-            for (int ch = 0; ch < 4; ++ch) smem[b * BUF + WTILE + ch * PS + (wave8 + NWAVE * pp) * 64 + lane] = pad0;
-          }
+          for (int ch = 0; ch < 4; ++ch) smem[b * BUF + WTILE + ch * PS + (wave8 + NWAVE * pp) * 64 + lane] = pad0;
         }
       }
-  }
+    }
   int d_seg = 0, d_left = P.src0.C;
   const float* d_base = P.src0.p + (long long)n * P.src0.ns;
   long long d_cs = P.src0.cs;
@@ -463,16 +408,6 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
     f_xl[pp] = f_xo[pp];
   }
   auto begin_fill = [&](int chunk, int buf) {
-    if constexpr (U4) {
-      if (chunk == f_sw) {   // the second (concat) segment from here on
-        u_base = P.src1.p + (long long)n * P.src1.ns;
-        u_sent = P.src1.relu ? &gsd_pad16_w43[4] : &gsd_pad16_w43[0];
-        u_cs = P.src1.cs;
-#pragma unroll
-        for (int k = 0; k < KH; ++k) h_off0[k] = h_off1[k];
-      }
-      return;
-    }
     if (f_sw < 0 || (chunk != f_sw && chunk != f_sw + 1)) return;
     if (chunk == f_sw) {
       d_base = P.src1.p + (long long)n * P.src1.ns;
@@ -497,19 +432,6 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
       }
   };
   auto fast_halo = [&](int ch, float* Xb) {
-    if constexpr (U4) {
-      // the wave's (at most) two instructions of the chunk ride in halo slots 0 and 2; slot 3 moves on to the next chunk
-      if (ch == 0 || ch == 2) {
-        const int k = ch >> 1;
-        if (wave8 + 4 * k < P.NI) {
-          const float* gp = h_off0[k] != W43_SENT ? u_base + h_off0[k] : u_sent;
-          float* dstp = Xb + (wave8 + 4 * k) * 256;
-          __builtin_amdgcn_global_load_lds(gp, dstp, 16, 0, 0);
-        }
-      }
-      if (ch == 3) u_base += 4 * u_cs;
-      return;
-    }
 #pragma unroll
     for (int pp = 0; pp < NPP; ++pp) {
       if constexpr (X4) {
@@ -665,25 +587,7 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
   W43_STAMP(5)   // prologue
   for (int chunk = c_lo; chunk < c_hi; ++chunk) {
     const int cur = (chunk - c_lo) & 1;
-    if constexpr (U4) {
-      __builtin_amdgcn_s_waitcnt(0x0F70);   // this wave's fills of the chunk have landed
-      if (u_patch) {   // a block at the left / right image edge: the outside floats of the straddling pieces this lane moved
-        const bool seg1 = f_sw >= 0 && chunk >= f_sw;
-        const float padv = (seg1 ? P.src1.relu : P.src0.relu) ? __builtin_nanf("") : 0.f;
-        float* Xh = smem + cur * BUF + WTILE;
-#pragma unroll
-        for (int k = 0; k < KH; ++k) {
-          const int pm = seg1 ? h_pm1[k] : h_pm0[k];
-          if (pm) {
-            float* pp = Xh + (wave8 + 4 * k) * 256 + lane * 4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (pm >> e & 1) pp[e] = padv;
-          }
-        }
-      }
-      if (!((W43_ABL) & 4)) __syncthreads();
-    } else if ((W43_ABL) & 4) {
+    if ((W43_ABL) & 4) {
       __builtin_amdgcn_s_waitcnt(0x0F70);
     } else if ((W43_ABL) & 8) {   // barrier without waiting for the fills: what their latency costs
       __syncthreads();
@@ -996,8 +900,7 @@ int launch_split(const W43Params& P, int base_grid, size_t lds, hipStream_t st, 
   return GSD_OK;
 }
 
-int launch_w43(const W43Params& P, int grid, size_t lds, hipStream_t st, bool x4, bool fast, bool plain, bool u4) {
-  if (u4) return plain ? launch_one<2, true, true>(P, grid, lds, st) : launch_one<2, true, false>(P, grid, lds, st);
+int launch_w43(const W43Params& P, int grid, size_t lds, hipStream_t st, bool x4, bool fast, bool plain) {
   if (fast && plain) return x4 ? launch_one<1, true, true>(P, grid, lds, st) : launch_one<0, true, true>(P, grid, lds, st);
   if (fast) return x4 ? launch_one<1, true>(P, grid, lds, st) : launch_one<0, true>(P, grid, lds, st);
   return x4 ? launch_one<1, false>(P, grid, lds, st) : launch_one<0, false>(P, grid, lds, st);
@@ -1157,37 +1060,16 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
       }
     }
   }
-  // unaligned 16-byte halo pieces (U4): straight-fill 4-wave form, every source vouches for 4 readable floats around its tensor
-  // measured (profiles/bench_conv_ab.py, U4 against the dword form): +2..3 % where most blocks lie inside the image (7 and 4 tile
-  // columns: levels 0, 1), -4..-10 % where every block touches both edges (levels 3, 4); over the whole train step the auto
-  // rule is within noise (109.6 against 109.6 ms), so the form stays an option.  The fills removed altogether (-DW43_ABL) are
-  // worth 9.5 %: it is the halo's memory traffic and latency the kernel waits for, not the instruction count -- unlike the dW
-  // kernel, where the same change bought 11 %.  GSD_W43_U4 = 0 off (default), 1 where tiles_x >= 4, 2 always
-  const int u4_env = gsd_env_int("GSD_W43_U4", 0);
-  bool u4 = (u4_env == 2 || (u4_env == 1 && pl.tiles_x >= 4)) && fast;
-  for (int i = 0; i < nsrc; ++i)
-    u4 = u4 && src[i].slack >= 4 && 4 * src[i].c_stride + (int64_t)(pl.fold ? N : 1) * src[i].n_stride < (1LL << 31);
-  if (u4) {
-    const int wcp = round_up(pl.WC, 4), ps = round_up(pl.WR * wcp, 4) + 4;
-    if (ceil_div(ps, 64) <= 8) {
-      x4 = false;
-      P.WCp = wcp; P.PS = ps; P.RO = 0;
-      P.NP = wcp / 4;
-      P.NI = ceil_div(ps, 64);   // 4 planes x PS / 4 pieces, 64 pieces per instruction
-    } else {
-      u4 = false;
-    }
-  }
   P.fold = pl.fold;
   P.nslab = 1;
   P.slabs = nullptr;
   const long grid = (long)(pl.fold ? 1 : N) * pl.tiles_y * pl.tiles_x * P.mblocks;
   GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w43: grid too large");
-  const size_t lds = (size_t)(2 * (W43_WTILE + (u4 ? P.NI * 256 : 4 * P.PS)) + 2 * 4 * P.nchunks + 4 * W43_BM) * sizeof(float);
+  const size_t lds = (size_t)(2 * (W43_WTILE + 4 * P.PS) + 2 * 4 * P.nchunks + 4 * W43_BM) * sizeof(float);
   bool plain = gsd_env_int("GSD_W43_PLAIN", 1) != 0;   // no deferred BatchNorm / ReLU on any source segment
   for (int i = 0; i < nsrc; ++i) plain = plain && src[i].scale == nullptr && src[i].relu == 0;
   // K slabs (the caller lends scratch): straight-fill form only; the slab count shrinks to what the scratch holds
-  if (ws != nullptr && fast && !u4) {
+  if (ws != nullptr && fast) {
     GSD_REQUIRE(((uintptr_t)ws & 15) == 0, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: workspace must be 16-byte aligned");
     int S = w43_pick_slabs(grid, P.nchunks, bw_raw != nullptr);
     while (S > 1 && (int64_t)S * grid * W43_BM * 256 > ws_elems) --S;
@@ -1197,7 +1079,7 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
       return launch_split(P, (int)grid, lds, (hipStream_t)stream, x4, plain);
     }
   }
-  return launch_w43(P, (int)grid, lds, (hipStream_t)stream, x4, fast, plain, u4);
+  return launch_w43(P, (int)grid, lds, (hipStream_t)stream, x4, fast, plain);
 }
 
 extern "C" int gsd_conv3x3_w43(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst,

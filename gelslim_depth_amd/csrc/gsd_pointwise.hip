@@ -678,6 +678,8 @@ struct BnBwdParams {
   int N, C, H, W, chunks;
 };
 
+// Modes 0 and 2, one thread per element: the form for planes the 16-byte kernel below does not take (unaligned operands, H * W
+// not a multiple of 4, mode 2 with K > 1)
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams P) {
   // grid: (chunks, C, N)
@@ -685,7 +687,6 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams P)
   const int HW = P.H * P.W;
   const size_t plane = ((size_t)n * P.C + c) * HW;
   const float sc = P.scale[c], sh = P.shift[c], mu = P.mean[c], is = P.invstd[c];
-  const int Hp = P.H >> 1, Wp = P.W >> 1;
   float s1 = 0.f, s2 = 0.f, s3 = 0.f;
   const int e_end = min((chunk + 1) * BWD_CHUNK, HW);
   for (int e = chunk * BWD_CHUNK + threadIdx.x; e < e_end; e += 256) {
@@ -704,23 +705,6 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams P)
       if (P.da.p != nullptr) {
         const int h = e / P.W, w = e - h * P.W;
         g = P.da.p[(size_t)n * P.da.ns + (size_t)c * P.da.cs + (size_t)h * P.da.W + w];
-      }
-      if constexpr (MODE == 1) {
-        const int h = e / P.W, w = e - h * P.W;
-        const int hp = h >> 1, wp = w >> 1;
-        if (hp < Hp && wp < Wp) {
-          // recompute the 2x2 arg-max of relu(bn(raw)); first maximum in (0,0),(0,1),(1,0),(1,1) order wins
-          const float* wbase = P.raw + plane + (size_t)(2 * hp) * P.W + 2 * wp;
-          float best = fmaxf(fmaf(wbase[0], sc, sh), 0.f);
-          int bi = 0;
-          float v = fmaxf(fmaf(wbase[1], sc, sh), 0.f);
-          if (v > best) { best = v; bi = 1; }
-          v = fmaxf(fmaf(wbase[P.W], sc, sh), 0.f);
-          if (v > best) { best = v; bi = 2; }
-          v = fmaxf(fmaf(wbase[P.W + 1], sc, sh), 0.f);
-          if (v > best) { best = v; bi = 3; }
-          if (bi == ((h & 1) << 1 | (w & 1))) g += P.dpool[(((size_t)n * P.C + c) * Hp + hp) * Wp + wp];
-        }
       }
     }
     const float dzv = y > 0.f ? g : 0.f;
@@ -793,8 +777,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_vec_kernel(const BnBwdParam
 }
 
 // Mode 1 (gradient = da + the max-pool backward of dpool), one thread per 2x2 POOLING WINDOW: its four raw values are read once
-// (two 8-byte loads) and serve both the arg-max and the four dz -- the element-per-thread kernel re-read the window for every
-// element (3.7 TB/s).  Windows cut by an odd H / W keep the elements that exist and get no pooled gradient (floor mode).
+// (two 8-byte loads) and serve both the arg-max and the four dz -- an element-per-thread form re-reads the window for every
+// element (measured 3.7 TB/s).  Windows cut by an odd H / W keep the elements that exist and get no pooled gradient (floor mode).
 constexpr int BWD_WCHUNK = BWD_CHUNK / 4;   // windows per block
 __global__ __launch_bounds__(256) void bn_bwd_reduce_pool_kernel(const BnBwdParams P) {
   typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
@@ -914,15 +898,13 @@ extern "C" int gsd_bn_bwd_reduce(int mode, const float* raw, const float* scale,
   P.N = N; P.C = C; P.H = H; P.W = W;
   P.chunks = bwd_chunks(H, W);
   dim3 grid(P.chunks, C, N);
-  const bool scalar = gsd_env_int("GSD_BN_BWD_SCALAR", 0) != 0;   // the element-per-thread kernels (A/B, tests)
   const float* gsrc = mode == 2 ? dout : P.da.p;
-  const bool vec = !scalar && (H * W) % 4 == 0 && (((uintptr_t)raw | (uintptr_t)dz | (uintptr_t)gsrc) & 15) == 0 &&
+  const bool vec = (H * W) % 4 == 0 && (((uintptr_t)raw | (uintptr_t)dz | (uintptr_t)gsrc) & 15) == 0 &&
                    (mode == 2 || (P.da.ns % 4 == 0 && P.da.cs % 4 == 0));
-  if (mode == 1 && !scalar) hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel, grid, dim3(256), 0, (hipStream_t)stream, P);
+  if (mode == 1) hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel, grid, dim3(256), 0, (hipStream_t)stream, P);
   else if (mode == 0 && vec) hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<0>), grid, dim3(256), 0, (hipStream_t)stream, P);
   else if (mode == 2 && vec && K == 1) hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<2>), grid, dim3(256), 0, (hipStream_t)stream, P);
   else if (mode == 0) hipLaunchKernelGGL((bn_bwd_reduce_kernel<0>), grid, dim3(256), 0, (hipStream_t)stream, P);
-  else if (mode == 1) hipLaunchKernelGGL((bn_bwd_reduce_kernel<1>), grid, dim3(256), 0, (hipStream_t)stream, P);
   else hipLaunchKernelGGL((bn_bwd_reduce_kernel<2>), grid, dim3(256), 0, (hipStream_t)stream, P);
   GSD_LAUNCH_CHECK("gsd_bn_bwd_reduce");
   return GSD_OK;

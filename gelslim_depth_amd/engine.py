@@ -165,8 +165,6 @@ class UNetEngine:
         # by CU: dX keeps its stand-alone speed and dW fills the CUs dX's tails and the chain's small launches leave idle
         self.side_dw = os.environ.get("GSD_SIDE_DW", "1") != "0"
         self.side: Optional[torch.cuda.Stream] = None
-        self.convt_dg_bn = os.environ.get("GSD_CONVT_DG_BN", "1") != "0"   # ConvT dX + pass 1 of the BatchNorm backward below it
-        self.batch_wl = os.environ.get("GSD_WL_BATCH", "1") != "0"   # a pass's weight layouts through gsd_weight_layout_batch
         self._handoff: Optional[torch.cuda.Stream] = None   # bucket hand-off to the all-reduce (see _announce)
         self.kernel_log: Optional[list] = None
         self.wgrad_log: Optional[list] = None      # bench hook: conv3x3 dW launches (+ slab reducer), same rows as kernel_log
@@ -264,7 +262,7 @@ class UNetEngine:
                     up.wt_d = torch.empty((need,), **f32)
                 # the LDS-DMA dX kernel can leave dz of the unit below and its per-channel sums (gsd_convT2x2_dgrad_bnrelu)
                 up.bn_rows = 0
-                if up.mode_d == 7 and self.convt_dg_bn:
+                if up.mode_d == 7:
                     up.bn_rows = lib.gsd_convT2x2_dgrad_bnrelu_partial_rows(C.byref(L.make_src(up.dout, slack=L.SLACK)), up.cin,
                                                                             up.cout, n, hs[li], ws[li])
                     max_part = max(max_part, up.bn_rows * 2 * _r64(up.cin))
@@ -310,8 +308,6 @@ class UNetEngine:
         n = u.raw.shape[0]
         lh, lw = self.hs[u.level], self.ws[u.level]
         u.form_f = u.forms_f[train]
-        if not self.batch_wl:
-            check(lib.gsd_weight_layout(u.form_f.mode_f, P[u.wname].data_ptr(), u.cout, u.cin, u.wt_f.data_ptr(), st), "weight_layout")
         arr = L.src_array(srcs)
         u.srcs = arr
         dst = L.dst_array([L.make_dst(u.raw)])
@@ -405,9 +401,9 @@ class UNetEngine:
         self._saved = train or keep
         self._saved_eval = keep
         self.generation += 1       # every forward overwrites the saved activations
-        if self.batch_wl:          # every forward-mode weight layout of the pass: the 2-D Winograd images in one launch
-            self._layouts([(u.forms_f[train].mode_f, P[u.wname], u.cout, u.cin, u.wt_f) for u in self.units] +
-                          [(6, P[up.wname], up.cout, up.cin, up.wt_f) for up in self.ups], st)
+        # every forward-mode weight layout of the pass: the 2-D Winograd images in one launch
+        self._layouts([(u.forms_f[train].mode_f, P[u.wname], u.cout, u.cin, u.wt_f) for u in self.units] +
+                      [(6, P[up.wname], up.cout, up.cin, up.wt_f) for up in self.ups], st)
         region = self._log_begin() if self.region_log is not None else None
         for lvl in range(self.L + 1):
             u0, u1 = self.enc[lvl]
@@ -433,8 +429,6 @@ class UNetEngine:
         for j in range(self.L):
             up = self.ups[j]
             lvl = self.L - 1 - j
-            if not self.batch_wl:
-                check(lib.gsd_weight_layout(6, P[up.wname].data_ptr(), up.cout, up.cin, up.wt_f.data_ptr(), st), "weight_layout")
             s = self._act_src(cur)
             d = L.make_dst(up.out)
             check(lib.gsd_convT2x2(C.byref(s), up.wt_f.data_ptr(), P[up.bname].data_ptr(), up.cin, up.cout, C.byref(d), n,
@@ -574,8 +568,6 @@ class UNetEngine:
         stored in self.partials (the conv epilogue's BatchNorm-statistics path); returns their row count."""
         n = u.raw.shape[0]
         lh, lw = self.hs[u.level], self.ws[u.level]
-        if not self.batch_wl:
-            check(lib.gsd_weight_layout(u.form_d.mode_d, P[u.wname].data_ptr(), u.cout, u.cin, u.wt_d.data_ptr(), st), "weight_layout")
         s = L.src_array([L.make_src(u.dsrc)])
         ev = self._log_begin()
         check(u.form_d.run(self.conv_ws, s, 1, u.wt_d.data_ptr(), u.cout, u.cin, L.dst_array(dsts), len(dsts),
@@ -587,8 +579,6 @@ class UNetEngine:
         """dX of unit u straight into prev.g as dz of prev's relu(bn(.)) (+ partial sums): u's input is prev's output."""
         n = u.raw.shape[0]
         lh, lw = self.hs[u.level], self.ws[u.level]
-        if not self.batch_wl:
-            check(lib.gsd_weight_layout(u.form_d.mode_d, P[u.wname].data_ptr(), u.cout, u.cin, u.wt_d.data_ptr(), st), "weight_layout")
         s = L.make_src(u.dsrc)
         d = L.make_dst(prev.g)
         prev.fused_rows = u.form_d.partial_rows(n, lh, lw, u.cin)
@@ -649,9 +639,9 @@ class UNetEngine:
         dout = dout.contiguous()
         st = L.stream_ptr()
         n = dout.shape[0]
-        if self.batch_wl:          # the dX-mode weight layouts (the weights have not changed since the forward)
-            self._layouts([(u.form_d.mode_d, P[u.wname], u.cout, u.cin, u.wt_d) for u in self.units if u.need_dgrad] +
-                          [(up.mode_d, P[up.wname], up.cout, up.cin, up.wt_d) for up in self.ups], st)
+        # the dX-mode weight layouts (the weights have not changed since the forward)
+        self._layouts([(u.form_d.mode_d, P[u.wname], u.cout, u.cin, u.wt_d) for u in self.units if u.need_dgrad] +
+                      [(up.mode_d, P[up.wname], up.cout, up.cin, up.wt_d) for up in self.ups], st)
         last = self.dec[-1][1] if self.L > 0 else self.enc[0][1]
         self._reduce(2, last, st, dout=dout, wout=P["outc.conv.weight"])
         check(lib.gsd_sum_planes(dout.data_ptr(), n, self.n_classes, dout.shape[2] * dout.shape[3],
@@ -690,8 +680,6 @@ class UNetEngine:
                 lib.gsd_convT2x2_wgrad(C.byref(xs), C.byref(dys), up.cin, up.cout, G[up.wname].data_ptr(),
                                        None if db_fused else G[up.bname].data_ptr(), ws.data_ptr(), ws.numel(), n, hi, wi, sst),
                 "convT2x2_wgrad"))
-            if not self.batch_wl:
-                check(lib.gsd_weight_layout(up.mode_d, P[up.wname].data_ptr(), up.cout, up.cin, up.wt_d.data_ptr(), st), "weight_layout")
             d = L.make_dst(prev.g)
             if up.bn_rows:
                 check(lib.gsd_convT2x2_dgrad_bnrelu(C.byref(dys), up.wt_d.data_ptr(), up.cin, up.cout, C.byref(d), prev.raw.data_ptr(),

@@ -12,7 +12,7 @@ flow (/root/reference/gelslim_depth/models/unet.py:79-88), different data layout
     buffer as one tensor.  gcat[l] is its gradient: one dX launch, whose two channel slices feed the skip unit's
     BatchNorm backward and the transposed convolution's dX / dW.
   * fp32: master parameters (the module's own tensors), every accumulation, BatchNorm statistics, gradients, Adam/EMA.
-    Per step each weight is re-laid-out to its bf16 GEMM image (gsd_bf16_weight_image).
+    Per step each weight is re-laid-out to its bf16 GEMM image (gsd_bf16_weight_images, one launch per 32 images).
   * eval mode: BatchNorm (running statistics) + ReLU ride in the conv epilogue (gsd_bf16_conv3x3_bnrelu): y is not stored.
   * backward: pass 1 of BatchNorm+ReLU backward (mask, per-channel sums) is fused into the dX launch that produces the
     gradient (conv3x3 and transposed-conv dX); only skip units (gradient = dX slice + max-pool routing) and the last unit
@@ -132,7 +132,6 @@ class UNetEngineBF16:
         f32 = dict(device=dev, dtype=torch.float32)
         # first layer: straight from x (gsd_bf16_conv3x3_first / gsd_bf16_wgrad_first) where the shape is served, else through the
         # im2col'd input (col0) and the dense-tap kernels; GSD_BF16_FIRST=0 forces the im2col path
-        self._wready, self._wevents, self._wdone = {}, {}, set()
         self.first_direct = bool(lib.gsd_bf16_conv3x3_first_supported(self.n_channels, self.dims[0])) and \
             os.environ.get("GSD_BF16_FIRST", "1") != "0"
         self.col0 = None if self.first_direct else torch.empty((n, h, w, _r32(9 * self.n_channels)), **bf)
@@ -181,7 +180,6 @@ class UNetEngineBF16:
                 max_part = max(max_part, lib.gsd_bf16_conv_dense_partial_rows(n, hs[li], ws[li], up.cout, up.cin, 4, 2) * 2 *
                                lib.gsd_bf16_conv_mpad(up.cin))
                 max_ws = max(max_ws, lib.gsd_bf16_wgrad_workspace(4, n, hs[li], ws[li], up.cin, up.cout))
-                max_ws = max(max_ws, lib.gsd_bf16_channel_sums_workspace(n, 2 * hs[li], 2 * ws[li], up.cout))
                 oy_, ox_ = self._pad_off(li - 1)
                 max_ws = max(max_ws, lib.gsd_bf16_convT_bias_grad_workspace(n, hs[li - 1], ws[li - 1], oy_, ox_, 2 * hs[li], 2 * ws[li], up.cout))
         self.partials = torch.empty((max_part,), **f32)
@@ -193,20 +191,18 @@ class UNetEngineBF16:
         # BatchNorm apply + max-pool of the encoder's skip units in one pass (gsd_bf16_bn_apply_pool); GSD_BF16_APPLY_POOL=0: two
         self.apply_pool = os.environ.get("GSD_BF16_APPLY_POOL", "1") != "0"
         # ... and that pass leaves the pool's arg-max (2 bits per element) for the backward, which then does not re-read the
-        # window's activations (gsd_bf16_bn_apply_pool_idx / gsd_bf16_bn_bwd_reduce_pool_idx); GSD_BF16_POOL_IDX=0: it does
-        self.pool_index = train and self.apply_pool and os.environ.get("GSD_BF16_POOL_IDX", "1") != "0"
+        # window's activations (gsd_bf16_bn_apply_pool_idx / gsd_bf16_bn_bwd_reduce_pool_idx)
         self.pool_idx = [None] + [torch.empty((n, hs[l], ws[l], self.dims[l - 1] // 8), device=dev, dtype=torch.int16)
-                                  if self.pool_index else None for l in range(1, self.L + 1)]
+                                  if train and self.apply_pool else None for l in range(1, self.L + 1)]
         # 64 -> 64 convolutions (forward and dX) on the weights-resident kernel (gsd_bf16_c64.hip); GSD_BF16_C64=0: the DMA-filled one
         self.c64 = os.environ.get("GSD_BF16_C64", "1") != "0"
         # train mode: the last unit's BatchNorm + ReLU rides in the 1x1 output convolution (gsd_bf16_bn_relu_conv1x1_out): its
         # activation has no other reader (the backward recomputes it from the raw output) and is never written.  GSD_BF16_FUSED_OUT=0: apply + conv
         self.fused_out = os.environ.get("GSD_BF16_FUSED_OUT", "1") != "0"
         # the transposed convolutions' bias gradient from the statistics rows of the dX launch that writes the gradient slice (the
-        # decoder's first convolution) instead of a pass over the slice (gsd_bf16_convT_bias_grad); GSD_BF16_DB_FROM_DX=0: gsd_bf16_channel_sums
-        self.db_from_dx = train and os.environ.get("GSD_BF16_DB_FROM_DX", "1") != "0"
+        # decoder's first convolution) instead of a pass over the slice (gsd_bf16_convT_bias_grad)
         self.db_part = [torch.empty((lib.gsd_bf16_conv_partial_rows(n, hs[l], ws[l], self.cat[l].shape[3]) * 2 *
-                                     lib.gsd_bf16_conv_mpad(self.cat[l].shape[3]),), **f32) if self.db_from_dx else None
+                                     lib.gsd_bf16_conv_mpad(self.cat[l].shape[3]),), **f32) if train else None
                         for l in range(self.L)]
         self.side_dw = train and os.environ.get("GSD_BF16_SIDE_DW", "1") != "0"
         self.side = torch.cuda.Stream(device=dev) if self.side_dw else None
@@ -278,35 +274,29 @@ class UNetEngineBF16:
                                          P[u.rvname].data_ptr(), BN_EPS, u.cout, u.scale.data_ptr(), u.shift.data_ptr(), st),
                   "bn_eval_coeffs")
             if u.first and self.first_direct:
-                self._wimage(2, P[u.wname], u.cout, u.cin, u.wt_f, st)
                 check(lib.gsd_bf16_conv3x3_first(self._x.data_ptr(), n, u.cin, lh, lw, u.wt_f.data_ptr(), C.byref(u.a), u.cout, None,
                                                  u.scale.data_ptr(), u.shift.data_ptr(), st), "conv3x3_first")
             elif u.first:
-                self._wimage(2, P[u.wname], u.cout, u.cin, u.wt_f, st)
                 check(lib.gsd_bf16_conv1x1_bnrelu(C.byref(din), u.wt_f.data_ptr(), C.byref(u.a), src[2], u.cout, u.scale.data_ptr(),
                                                   u.shift.data_ptr(), st), "conv1x1_bnrelu")
             else:
-                self._wimage(0, P[u.wname], u.cout, u.cin, u.wt_f, st)
                 done = self._log("bf16_conv3x3", 2.0 * u.cout * u.cin * 9 * n * lh * lw, (u.cout, u.cin, lh, lw))
                 check(lib.gsd_bf16_conv3x3_bnrelu(C.byref(din), u.wt_f.data_ptr(), C.byref(u.a), u.cin, u.cout, u.scale.data_ptr(),
                                                   u.shift.data_ptr(), st), "conv3x3_bnrelu")
                 done()
             return
         if u.first and self.first_direct:
-            self._wimage(2, P[u.wname], u.cout, u.cin, u.wt_f, st)
             done = self._log("bf16_conv_first", 2.0 * u.cout * 9 * u.cin * n * lh * lw)
             check(lib.gsd_bf16_conv3x3_first(self._x.data_ptr(), n, u.cin, lh, lw, u.wt_f.data_ptr(), C.byref(dy), u.cout, part, None,
                                              None, st), "conv3x3_first")
             done()
         elif u.first:
-            self._wimage(2, P[u.wname], u.cout, u.cin, u.wt_f, st)
             z = L.int_array([0])
             done = self._log("bf16_conv_dense", 2.0 * u.cout * src[2] * n * lh * lw)
             check(lib.gsd_bf16_conv_dense(C.byref(din), u.wt_f.data_ptr(), C.byref(dy), src[2], u.cout, 1, 1, z, z, lh, lw, 0, 0, 0,
                                           None, part, None, st), "conv_dense(first)")
             done()
         elif self._use_c64(u.cin, u.cout):
-            self._wimage(0, P[u.wname], u.cout, u.cin, u.wt_f, st)
             done = self._log("bf16_conv3x3", 2.0 * u.cout * u.cin * 9 * n * lh * lw, (u.cout, u.cin, lh, lw))
             check(lib.gsd_bf16_conv3x3_c64(C.byref(din), u.wt_f.data_ptr(), C.byref(dy), part, None, st), "conv3x3_c64")
             done()
@@ -314,7 +304,6 @@ class UNetEngineBF16:
             self._apply(u, dy, st, pool_to)
             return
         else:
-            self._wimage(0, P[u.wname], u.cout, u.cin, u.wt_f, st)
             done = self._log("bf16_conv3x3", 2.0 * u.cout * u.cin * 9 * n * lh * lw, (u.cout, u.cin, lh, lw))
             check(lib.gsd_bf16_conv3x3(C.byref(din), u.wt_f.data_ptr(), C.byref(dy), u.cin, u.cout, part, None, st), "conv3x3")
             done()
@@ -335,8 +324,6 @@ class UNetEngineBF16:
         x = self._x
         u0.src, u1.src = (None, 0, 0), (u0.a_t, u0.a_off, u0.cout)
         part = self.partials.data_ptr()
-        self._wimage(2, P[u0.wname], u0.cout, u0.cin, u0.wt_f, st)
-        self._wimage(0, P[u1.wname], u1.cout, u1.cin, u1.wt_f, st)
         done = self._log("bf16_conv_first", 2.0 * u0.cout * 9 * u0.cin * n * lh * lw)
         check(lib.gsd_bf16_conv3x3_first(x.data_ptr(), n, u0.cin, lh, lw, u0.wt_f.data_ptr(), None, u0.cout, part, None, None, st),
               "conv3x3_first (statistics)")
@@ -379,9 +366,8 @@ class UNetEngineBF16:
             return      # forward() folds it into the output convolution
         if pool_to is not None:
             dp = L.make_nhwc(pool_to)
-            idx = self.pool_idx[u.level + 1] if self.pool_index else None
             check(lib.gsd_bf16_bn_apply_pool_idx(C.byref(dy), u.scale.data_ptr(), u.shift.data_ptr(), C.byref(u.a), C.byref(dp),
-                                                 L.ptr(idx), st), "bn_apply_pool")
+                                                 self.pool_idx[u.level + 1].data_ptr(), st), "bn_apply_pool")
         else:
             check(lib.gsd_bf16_bn_apply(C.byref(dy), u.scale.data_ptr(), u.shift.data_ptr(), C.byref(u.a), 1, st), "bn_apply")
 
@@ -429,7 +415,6 @@ class UNetEngineBF16:
         for j in range(self.L):
             up = self.ups[j]
             lvl = self.L - 1 - j
-            self._wimage(3, P[up.wname], up.cout, up.cin, up.wt_f, st)
             oy, ox = self._pad_off(lvl)
             dslice = L.make_nhwc(self.cat[lvl], self.dims[lvl], up.cout)
             done = self._log("bf16_convT", 2.0 * 4 * up.cout * up.cin * n * self.hs[lvl + 1] * self.ws[lvl + 1])
@@ -538,7 +523,8 @@ class UNetEngineBF16:
 
     def _image_jobs(self, P, train: bool):
         """(mode, weights, cout, cin, image buffer) of every weight image a step reads: the forward images, and in train mode
-        the dX images of the units that have a dX."""
+        the dX images of the units that have a dX.  The convolutions read these images as _prepare_weight_images left them: an
+        image that is not listed here is never formed."""
         jobs = []
         for pair in self.enc:
             for u in pair:
@@ -562,39 +548,12 @@ class UNetEngineBF16:
     def _prepare_weight_images(self, P, train: bool) -> None:
         """Every bf16 weight image of the step in ONE launch per 32 images at the start of the forward (gsd_bf16_weight_images):
         they depend on nothing but the parameters, and as 43 latency-bound launches between the convolutions they cost 0.45 ms
-        of a 30-ms step.  `_wimage` then finds the image done.  GSD_BF16_BATCH_WIMG=0: one launch per image, where it is used.
-        (GSD_BF16_SIDE_WIMG=1, the per-image launches on the side stream instead, measured slower: 30.7 vs 30.4 ms.)"""
-        self._wready = {}
-        self._wdone = set()
-        if os.environ.get("GSD_BF16_BATCH_WIMG", "1") != "0":
-            jobs = self._image_jobs(P, train)
-            arr = (L.gsd_bf16_wimg_job * len(jobs))()
-            for i, (mode, w, cout, cin, buf) in enumerate(jobs):
-                arr[i].w, arr[i].out, arr[i].mode, arr[i].Cout, arr[i].Cin = w.data_ptr(), buf.data_ptr(), mode, cout, cin
-                self._wdone.add(buf.data_ptr())
-            check(lib.gsd_bf16_weight_images(arr, len(jobs), L.stream_ptr()), "weight_images")
-            return
-        if not (train and self.side_dw and os.environ.get("GSD_BF16_SIDE_WIMG", "0") == "1"):
-            return
-        self.side.wait_stream(torch.cuda.current_stream())     # the previous step's Adam update, and its last readers of the images
-        with torch.cuda.stream(self.side):
-            sst = L.stream_ptr()
-            for mode, w, cout, cin, buf in self._image_jobs(P, train):
-                check(lib.gsd_bf16_weight_image(mode, w.data_ptr(), cout, cin, buf.data_ptr(), sst), "weight_image")
-                ev = self._wevents.get(buf.data_ptr())
-                if ev is None:
-                    ev = self._wevents[buf.data_ptr()] = torch.cuda.Event()
-                ev.record()
-                self._wready[buf.data_ptr()] = ev
-
-    def _wimage(self, mode: int, w: torch.Tensor, cout: int, cin: int, buf: torch.Tensor, st: int) -> None:
-        if buf.data_ptr() in self._wdone:                     # produced by the batched launch at the start of this step
-            return
-        ev = self._wready.pop(buf.data_ptr(), None)
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)        # produced on the side stream at the start of this step
-            return
-        check(lib.gsd_bf16_weight_image(mode, w.data_ptr(), cout, cin, buf.data_ptr(), st), "weight_image")
+        of a 30-ms step."""
+        jobs = self._image_jobs(P, train)
+        arr = (L.gsd_bf16_wimg_job * len(jobs))()
+        for i, (mode, w, cout, cin, buf) in enumerate(jobs):
+            arr[i].w, arr[i].out, arr[i].mode, arr[i].Cout, arr[i].Cin = w.data_ptr(), buf.data_ptr(), mode, cout, cin
+        check(lib.gsd_bf16_weight_images(arr, len(jobs), L.stream_ptr()), "weight_images")
 
     def _on_side(self, launch) -> None:
         """Run launch(stream pointer, workspace tensor) -- one weight-gradient launch -- behind everything issued so far, on the
@@ -640,7 +599,6 @@ class UNetEngineBF16:
         u's input, dst == fuse.g) the epilogue also does pass 1 of that unit's BatchNorm+ReLU backward; with `stats_to` (and no
         fuse) it leaves the per-channel sums of what it stores there (gsd_bf16_conv_partial_rows rows of 2*mpad(u.cin))."""
         n, lh, lw = u.y.shape[0], self.hs[u.level], self.ws[u.level]
-        self._wimage(1, P[u.wname], u.cout, u.cin, u.wt_d, st)
         din, dout = L.make_nhwc(u.g), L.make_nhwc(dst)
         bw = keep = None
         if fuse is not None:
@@ -679,7 +637,7 @@ class UNetEngineBF16:
             dwout = None
             self._dgrad(u1, P, u0.g, st, fuse=u0)
             self._tail(u0, G, st, fused=True)
-            self._dgrad(u0, P, self.gcat[lvl], st, stats_to=self.db_part[lvl] if self.db_from_dx else None)
+            self._dgrad(u0, P, self.gcat[lvl], st, stats_to=self.db_part[lvl])
             prev = self.dec[j - 1][1] if j > 0 else self.enc[self.L][1]
             hi, wi = self.hs[lvl + 1], self.ws[lvl + 1]
             oy, ox = self._pad_off(lvl)
@@ -690,17 +648,13 @@ class UNetEngineBF16:
                 check(lib.gsd_bf16_wgrad(C.byref(prev.a), C.byref(gup), 4, 2, ty, tx, G[up.wname].data_ptr(), up.cout, ws.data_ptr(),
                                          ws.numel(), sst), "convT wgrad")
                 done()
-                # (the bias gradient -- per-channel sums of the same gradient slice -- is off the critical path too)
-                if self.db_from_dx:      # from the statistics rows the dX launch above left: no pass over the slice
-                    ctot = self.cat[lvl].shape[3]
-                    check(lib.gsd_bf16_convT_bias_grad(self.db_part[lvl].data_ptr(), lib.gsd_bf16_conv_partial_rows(n, self.hs[lvl], self.ws[lvl], ctot),
-                                                       2 * lib.gsd_bf16_conv_mpad(ctot), ctot - up.cout, C.byref(gup), oy, ox, 2 * hi, 2 * wi,
-                                                       G[up.bname].data_ptr(), ws.data_ptr(), ws.numel(), sst), "convT bias grad")
-                else:
-                    check(lib.gsd_bf16_channel_sums(C.byref(gup), oy, ox, 2 * hi, 2 * wi, G[up.bname].data_ptr(), ws.data_ptr(),
-                                                    ws.numel(), sst), "convT bias grad")
+                # (the bias gradient -- per-channel sums of the same gradient slice -- is off the critical path too): from the
+                # statistics rows the dX launch above left, no pass over the slice
+                ctot = self.cat[lvl].shape[3]
+                check(lib.gsd_bf16_convT_bias_grad(self.db_part[lvl].data_ptr(), lib.gsd_bf16_conv_partial_rows(n, self.hs[lvl], self.ws[lvl], ctot),
+                                                   2 * lib.gsd_bf16_conv_mpad(ctot), ctot - up.cout, C.byref(gup), oy, ox, 2 * hi, 2 * wi,
+                                                   G[up.bname].data_ptr(), ws.data_ptr(), ws.numel(), sst), "convT bias grad")
             self._on_side(launch)
-            self._wimage(4, P[up.wname], up.cout, up.cin, up.wt_d, st)
             dprev = L.make_nhwc(prev.g)
             done = self._log("bf16_convT", 2.0 * 4 * up.cout * up.cin * n * hi * wi)
             bw, keep = self._bnbwd(prev)
@@ -714,13 +668,13 @@ class UNetEngineBF16:
             u0, u1 = self.enc[lvl]
             if lvl < self.L:
                 gskip = L.make_nhwc(self.gcat[lvl], 0, u1.cout)
-                if self.pool_index:
+                if self.apply_pool:      # the forward's apply + pool pass left the arg-max codes
                     dyv, dzv, dpv = L.make_nhwc(u1.y), L.make_nhwc(u1.g), L.make_nhwc(self.dpooled[lvl + 1])
                     check(lib.gsd_bf16_bn_bwd_reduce_pool_idx(C.byref(dyv), u1.scale.data_ptr(), u1.shift.data_ptr(), u1.mean.data_ptr(),
                                                               u1.invstd.data_ptr(), C.byref(gskip), self.pool_idx[lvl + 1].data_ptr(),
                                                               C.byref(dpv), C.byref(dzv), self.partials.data_ptr(), st),
                           "bn_bwd_reduce_pool_idx")
-                else:
+                else:                    # a separate max-pool pass: the reduce re-reads the window's activations
                     self._reduce(1, u1, st, g=gskip, dpool=self.dpooled[lvl + 1])
             self._tail(u1, G, st, dwout, fused=prev_fused is u1)
             dwout = None

@@ -1,7 +1,7 @@
 """A/B of tuning variants of the fp32 Winograd conv3x3 kernel on the U-Net's layer shapes, all in ONE process (interleaved
 rounds), each checked against the direct-tap kernel.
 usage (GPU box): PYTHONPATH=. python profiles/bench_conv_ab.py B W0 "NAME:ENV=V,ENV=V;NAME:..." [rounds]
-   e.g. python profiles/bench_conv_ab.py 32 427 "base:GSD_W43_U4=0;u4:GSD_W43_U4=1;u4all:GSD_W43_U4=2" """
+   e.g. python profiles/bench_conv_ab.py 32 427 "base:;dword:GSD_W43_X4=0;nofold:GSD_W43_FOLD=0" """
 import os
 import sys
 import torch
@@ -30,7 +30,7 @@ for lvl, c in enumerate([64, 128, 256, 512, 1024]):
 st = L.stream_ptr()
 tot = {n: 0.0 for n, _ in variants}
 for lvl, ci, co, h, w in shapes:
-    x = L.slack_empty((B, ci, h, w), "cuda")   # 4 readable floats either side: lets the kernel move the halo as 16-byte pieces
+    x = L.slack_empty((B, ci, h, w), "cuda")   # as the engine allocates its activations (4 readable floats either side)
     x.copy_(torch.randn(B, ci, h, w, device="cuda"))
     sc, sh = torch.rand(ci, device="cuda") + 0.5, torch.randn(ci, device="cuda") * 0.1
     wt = torch.randn(co, ci, 3, 3, device="cuda") * 0.05
