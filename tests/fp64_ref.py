@@ -1,5 +1,5 @@
 """fp64 references of the fp32 engine's contractions, with a per-element condition tensor, and the bound check the fp32 kernel
-tests hold them to.  A helper module (imported by tests/test_fp64_ref_cpu.py and tests/test_gpu_fp64_bounds.py), not collected.
+tests hold them to.  A helper module (imported by tests/test_fp64_ref_cpu.py and the GPU bound modules), not collected.
 
 Every reference is plain torch float64 arithmetic on whatever device its operands live on: a 3x3 convolution is nine shifted-tap
 matmuls over a zero-padded copy, a 2x2/s2 transposed convolution four matmuls into the strided output planes.  No F.conv2d (which
@@ -13,6 +13,10 @@ removes a third of the products from cond, so a halo that reads garbage instead 
 
 check_bound(got, ref, cond, tau) asserts |got - ref| <= tau * cond at every element, and finite outputs everywhere (the tests
 NaN-fill outputs before the launch, so an element nobody wrote fails).
+
+The bf16 engine (tests/test_gpu_bf16_fp64_bounds.py) stores its results in bf16: check_bound_bf16 allows the RNE rounding of
+the result, 2^-8 |ref|, on top of tau * cond; the references of its bf16-only operations (first layer from fp32 x, BatchNorm
+apply, max-pool routing, BatchNorm backward, statistics of the stored values) sit at the end of this module.
 """
 from __future__ import annotations
 
@@ -31,6 +35,18 @@ TAU_DW = 4.0e-6        # conv3x3 dW (split-K reductions over N*H*W pixels): 1.03
 TAU_CONVT = 1.9e-6     # ConvTranspose2d 2x2/s2 forward, dX, dW, db: 4.80e-7 (up2.up, N = 32)
 TAU_1X1 = 8.0e-7       # output 1x1 conv forward / dX / dW / db, MSE loss and gradient: 2.16e-7 (outc forward, N = 32)
 TAU_STATS = 3.4e-8     # per-channel sums of a launch's statistics epilogue (vs sum of ref, over sum of cond): 8.51e-9 (inc.c1, N = 8)
+
+# bf16 engine (tests/test_gpu_bf16_fp64_bounds.py, check_bound_bf16): |got - ref| <= 2^-8 |ref| + TAU * cond.  2^-8 is the unit
+# roundoff of the RNE rounding of a stored bf16 result; TAU holds the fp32 accumulation in front of it.  Same rule: each at no
+# more than 4x the largest ratio measured on the MI355X (case named beside it); forward / dX taus also below ceiling(Cin).
+TAU_BF16_CONV = 2.1e-7     # conv3x3 / c64 / inc_conv forward, dX (plain or with fused BatchNorm-backward pass 1): 5.48e-8 (down2.c1 forward, N = 16)
+TAU_BF16_FIRST = 6.4e-8    # conv3x3_first (27 products from fp32 x), with or without BatchNorm+ReLU: 1.81e-8 (inc y0 in the engine step, N = 16)
+TAU_BF16_DW = 1.1e-6       # conv3x3 / first-layer / ConvT 4-tap dW (fp32 result, check_bound): 2.79e-7 (inc wgrad_first_recompute, N = 16)
+TAU_BF16_CONVT = 1.7e-7    # ConvT forward scattered into the concat buffer, dX, bias gradient: 4.29e-8 (up0.up, N = 7)
+TAU_BF16_PW = 5.6e-7       # BatchNorm apply, backward reduce (dz) and apply, 1x1 output conv and its gradients: 1.42e-7 (engine step, N = 16)
+TAU_BF16_STATS = 4.2e-6    # per-channel sums of a bf16 statistics epilogue, of the values as stored (each block lane sums its pixels
+#                            serially in fp32): 1.05e-6 (up3.c0 dX sum of squares over the concat gradient, N = 32)
+U_BF16 = 2.0 ** -8         # unit roundoff of round-to-nearest-even to 8 significant bits (f32_to_bf16 in gsd_bf16_common.h)
 
 # worst |got-ref|/cond seen per key (check_bound(..., key=...)): the GPU module reports them
 RATIOS: Dict[str, float] = {}
@@ -224,7 +240,8 @@ def _pos(flat: int, shape: Sequence[int]) -> Tuple[int, ...]:
 
 
 def check_bound(got: torch.Tensor, ref: torch.Tensor, cond: torch.Tensor, tau: float, what: str, n0: int = 0,
-                image: Optional[int] = None, key: Optional[str] = None, weights: bool = False) -> float:
+                image: Optional[int] = None, key: Optional[str] = None, weights: bool = False,
+                _base: Optional[torch.Tensor] = None) -> float:
     """Assert |got - ref| <= tau * cond and isfinite(got) at every element; return the worst ratio |got - ref| / cond.
 
     got / ref / cond: same shape (n, c, h, w) for activations -- (co, ci, kh, kw) or any shape for weights; n0: index of
@@ -243,6 +260,8 @@ def check_bound(got: torch.Tensor, ref: torch.Tensor, cond: torch.Tensor, tau: f
             p = (p[0] + n0,) + p[1:]
         raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements not finite (unwritten?), first at {p}")
     err = (g - ref).abs()
+    if _base is not None:       # check_bound_bf16: the rounding allowance of the stored result comes off before the ratio
+        err = (err - _base).clamp_min_(0.0)
     ratio = torch.where(cond > 0, err / cond.clamp_min(1e-300),
                         torch.where(err > 0, torch.full_like(err, math.inf), torch.zeros_like(err)))
     worst_flat = int(ratio.reshape(-1).argmax())
@@ -255,7 +274,8 @@ def check_bound(got: torch.Tensor, ref: torch.Tensor, cond: torch.Tensor, tau: f
     p = _pos(worst_flat, got.shape)
     act = got.dim() == 4 and not weights
     nover = int(over.sum())
-    msg = [f"{what}: |got-ref| > {tau:.3g}*cond at {nover} of {over.numel()} elements ({nover / over.numel():.3g}); "
+    lhs = "|got-ref| - 2^-8|ref|" if _base is not None else "|got-ref|"
+    msg = [f"{what}: {lhs} > {tau:.3g}*cond at {nover} of {over.numel()} elements ({nover / over.numel():.3g}); "
            f"worst ratio {worst:.3g} at {(p[0] + n0,) + p[1:] if act else p}"]
     if act:
         idx = over.nonzero()
@@ -278,3 +298,109 @@ def check_sums(got: torch.Tensor, ref: torch.Tensor, bound: torch.Tensor, tau: f
     """Per-channel sums of a launch's statistics epilogue: |got - ref| <= tau * bound (bound: the sum of the per-element cond,
     or of cond^2 for second moments)."""
     return check_bound(got, ref, bound, tau, what, key=key, weights=True)
+
+
+def check_bound_bf16(got: torch.Tensor, ref: torch.Tensor, cond: torch.Tensor, tau: float, what: str, n0: int = 0,
+                     image: Optional[int] = None, key: Optional[str] = None, weights: bool = False) -> float:
+    """A stored bf16 result: assert |got - ref| <= 2^-8 |ref| + tau * cond and isfinite(got) at every element; return the worst
+    ratio (|got - ref| - 2^-8 |ref|)+ / cond.  2^-8 |ref| is what the RNE rounding of the exact result to 8 significant bits may
+    cost (half an ulp is 2^-9 of the binade's bottom, i.e. up to 2^-8 relative there); tau * cond holds the fp32 evaluation in
+    front of the rounding.  Report and arguments as check_bound."""
+    return check_bound(got, ref, cond, tau, what, n0=n0, image=image, key=key, weights=weights,
+                       _base=U_BF16 * ref.abs())
+
+
+# ------------------------------------------------------------------------------------------- bf16 engine: operands, references
+def bf16(t: torch.Tensor) -> torch.Tensor:
+    """t rounded to bf16 (RNE, as f32_to_bf16) -- via fp32, as every kernel rounds an fp32 value -- widened to fp64."""
+    return t.float().to(torch.bfloat16).double()
+
+
+def nchw(t: torch.Tensor, off: int = 0, c: Optional[int] = None) -> torch.Tensor:
+    """Channels [off, off + c) of an NHWC buffer as an (n, c, h, w) fp64 tensor on its device."""
+    c = t.shape[3] - off if c is None else c
+    return t[..., off:off + c].permute(0, 3, 1, 2).double()
+
+
+def first_fwd(x: torch.Tensor, wt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The first layer from the fp32 input: the kernels (gsd_bf16_conv3x3_first, gsd_bf16_inc_conv) round x and the weights to
+    bf16 themselves, then contract 9 * Cin products in fp32."""
+    return conv3x3_fwd(bf16(x), bf16(wt))
+
+
+def bn_relu_bf16(y: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """BatchNorm apply + ReLU of a stored bf16 raw output as the kernels store it: bf16(max(fmaf(y, scale, shift), 0)).
+    Returns (stored, ref, cond): `stored` reproduces the fp32-then-bf16 rounding (the fp64 product of a bf16 and an fp32 value is
+    exact; as deferred_act, only a rare double rounding can separate it from a true fmaf) and is the next convolution's operand;
+    ref = relu(y*scale + shift) exactly, cond = |y*scale| + |shift| where it is positive (what fmaf's rounding scales with)."""
+    c = (1, -1, 1, 1)
+    t = y.double() * scale.double().view(c) + shift.double().view(c)
+    stored = bf16(t.float().double().clamp_min(0.0))
+    pos = t > 0
+    cond = torch.where(pos, (y.double() * scale.double().view(c)).abs() + shift.double().abs().view(c), torch.zeros_like(t))
+    return stored, t.clamp_min(0.0), cond
+
+
+def maxpool_route(a: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """2x2/s2 max-pool of the STORED activations (n, c, h, w) and the window position of each maximum, 0..3 in (0,0), (0,1),
+    (1,0), (1,1) order, the first maximum winning a tie; an odd last row / column is dropped (floor mode)."""
+    hp, wp = a.shape[2] // 2, a.shape[3] // 2
+    a = a[:, :, :2 * hp, :2 * wp]
+    win = [a[:, :, 0::2, 0::2], a[:, :, 0::2, 1::2], a[:, :, 1::2, 0::2], a[:, :, 1::2, 1::2]]
+    best, code = win[0].clone(), torch.zeros(win[0].shape, dtype=torch.int64, device=a.device)
+    for q in range(1, 4):
+        better = win[q] > best
+        code[better] = q
+        best = torch.where(better, win[q], best)
+    return best, code
+
+
+def pool_grad(dp: torch.Tensor, code: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """The pooled gradient dp routed to the window position `code` names, zero elsewhere (and in the dropped row / column)."""
+    n, c, hp, wp = dp.shape
+    out = torch.zeros((n, c, h, w), dtype=torch.float64, device=dp.device)
+    for q, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+        out[:, :, dy:2 * hp:2, dx:2 * wp:2] = torch.where(code == q, dp.double(), torch.zeros((), dtype=torch.float64,
+                                                                                               device=dp.device))
+    return out
+
+
+def bn_bwd_dz(y: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, g: torch.Tensor,
+              g_abs: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Pass 1 of the BatchNorm+ReLU backward, the stored dz: g where fmaf(y, scale, shift) > 0, else 0 (then rounded to bf16).
+    g: the gradient w.r.t. the activation in fp64 (a skip gradient plus the routed pooled gradient, the output conv's w * dout,
+    or a dX); g_abs: the magnitude its fp32 evaluation in the kernel scales with (default |g|).  Returns (ref, cond)."""
+    m = bnrelu_mask(y, scale, shift)
+    z = torch.zeros((), dtype=torch.float64, device=g.device)
+    return torch.where(m, g.double(), z), torch.where(m, (g.abs() if g_abs is None else g_abs).double(), z)
+
+
+def bn_bwd_sums(dz: torch.Tensor, y: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Pass 1's per-channel sums over the STORED dz (the kernels sum what they store): (sum dz, sum dz*xhat, sum |dz|,
+    sum |dz*xhat|) with xhat = (y - mean) * invstd; the kernels form xhat in fp32 (two roundings, inside the tau)."""
+    c = (1, -1, 1, 1)
+    xhat = (y.double() - mean.double().view(c)) * invstd.double().view(c)
+    p = dz.double() * xhat
+    return dz.double().sum((0, 2, 3)), p.sum((0, 2, 3)), dz.double().abs().sum((0, 2, 3)), p.abs().sum((0, 2, 3))
+
+
+def bn_bwd_apply(dz: torch.Tensor, y: torch.Tensor, scale: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
+                 c1: torch.Tensor, c2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Pass 2: d_raw = scale * (dz - c1 - xhat * c2) (gsd_bf16_bn_bwd_apply; c1 = sum dz / count, c2 = sum dz*xhat / count);
+    cond = |scale| (|dz| + |c1| + |xhat * c2|), the magnitude its fp32 evaluation scales with."""
+    c = (1, -1, 1, 1)
+    xhat = (y.double() - mean.double().view(c)) * invstd.double().view(c)
+    t = xhat * c2.double().view(c)
+    sc = scale.double().view(c)
+    ref = sc * (dz.double() - c1.double().view(c) - t)
+    cond = sc.abs() * (dz.double().abs() + c1.double().abs().view(c) + t.abs())
+    return ref, cond
+
+
+def stored_sums(y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A bf16 statistics epilogue sums the values AS STORED (gsd_bf16_conv.hip: `statistics of the values as stored`):
+    (sum y, sum y^2, sum |y|, sum y^2) per channel of the stored (n, c, h, w) output."""
+    y = y.double()
+    q = y * y
+    return y.sum((0, 2, 3)), q.sum((0, 2, 3)), y.abs().sum((0, 2, 3)), q.sum((0, 2, 3))

@@ -168,3 +168,115 @@ def test_unwritten_and_cond_zero():
     got = ref.clone()
     got[0, 0, 1, 3] = 1e-30          # a masked (cond == 0) element must be exactly 0
     _rejects(got, ref, cond, 1e-6, "worst ratio inf")
+
+
+# ---- the bf16 bound and the references of the bf16-only operations
+def _bf16_grid():
+    """fp64 values across binades: exact powers of two, ties half-way between two bf16 neighbours, values just off a tie."""
+    e = torch.arange(-20, 21, dtype=torch.float64)
+    p2 = torch.pow(2.0, e)
+    m = torch.arange(128, 256, dtype=torch.float64) / 128          # the 128 bf16 mantissas of [1, 2)
+    tie = (m + 0.5 / 128)[None, :] * p2[:, None]                   # half-way between neighbours (RNE: to the even one)
+    off = (m + 0.37 / 128)[None, :] * p2[:, None]
+    vals = torch.cat([p2, tie.reshape(-1), off.reshape(-1), rn(4096) * 3])
+    return torch.cat([vals, -vals]).view(1, 1, 1, -1)
+
+
+def test_check_bound_bf16_accepts_rne_across_binades():
+    ref = _bf16_grid()
+    cond = torch.zeros_like(ref)         # no accumulation at all: the rounding allowance alone must carry RNE
+    got = ref.float().to(torch.bfloat16).float()
+    assert R.check_bound_bf16(got, ref, cond, 0.0, "RNE") == 0.0
+    assert bool((got.double() != ref).any())       # (the grid does round)
+    # ties go to the even mantissa, and an exact power of two is kept exactly
+    assert float(torch.tensor(1.0 + 1.5 / 128).to(torch.bfloat16)) == 1.0 + 2.0 / 128
+    assert float(torch.tensor(2.0 ** -20).to(torch.bfloat16)) == 2.0 ** -20
+
+
+def test_check_bound_bf16_rejects_truncation_one_ulp_and_nan():
+    ref = rn(1, 8, 16, 16) * 10
+    cond = ref.abs() * 4
+    ok = ref.float().to(torch.bfloat16).float()
+    R.check_bound_bf16(ok, ref, cond, R.TAU_BF16_CONV, "RNE")
+    # round toward zero: the 16 low bits of the fp32 pattern cut off
+    rtz = (ref.float().view(torch.int32) & ~0xffff).view(torch.float32)
+    with pytest.raises(AssertionError, match="2\\^-8"):
+        R.check_bound_bf16(rtz, ref, cond, R.TAU_BF16_CONV, "RTZ")
+    # one element one bf16 ulp off the RNE result, away from the exact value: 1.3 rounds down to 1.296875 (ulp 2^-7 in [1, 2)),
+    # the wrong result is 1.2890625 (the ulp toward 1.3 would still lie within 2^-8 |ref| -- that is what the bound admits)
+    ref[0, 3, 5, 7] = 1.3
+    cond[0, 3, 5, 7] = 4 * 1.3
+    ok[0, 3, 5, 7] = 1.296875
+    R.check_bound_bf16(ok, ref, cond, R.TAU_BF16_CONV, "RNE")
+    one = ok.clone()
+    one[0, 3, 5, 7] = 1.296875 - 2.0 ** -7
+    with pytest.raises(AssertionError, match=r"at 1 of .* \(0, 3, 5, 7\)"):
+        R.check_bound_bf16(one, ref, cond, R.TAU_BF16_CONV, "one ulp")
+    nan = ok.clone()
+    nan[0, 1, 2, 3] = float("nan")
+    with pytest.raises(AssertionError, match=r"not finite .* \(0, 1, 2, 3\)"):
+        R.check_bound_bf16(nan, ref, cond, R.TAU_BF16_CONV, "NaN")
+
+
+def test_bf16_first_layer_and_batchnorm_refs_equal_torch():
+    """first_fwd == F.conv2d on bf16(x), bf16(w); pass 1 + pass 2 of the BatchNorm backward (bn_bwd_dz, bn_bwd_sums,
+    bn_bwd_apply with c1 = sum dz / count, c2 = sum dz*xhat / count) == torch's train-mode BatchNorm2d + ReLU autograd; the
+    apply is relu(fmaf(y, scale, shift)) rounded through fp32 to bf16."""
+    n, c, h, w = 2, 6, 7, 9
+    x = rn(n, 3, h, w).float()
+    wt = rn(c, 3, 3, 3).float()
+    ref, cond = R.first_fwd(x, wt)
+    t = F.conv2d(x.to(torch.bfloat16).double(), wt.to(torch.bfloat16).double(), padding=1)
+    assert rel(ref, t) < 1e-12 and bool((cond >= ref.abs()).all())
+    # BatchNorm2d(train) + ReLU forward and backward in float64
+    y = R.bf16(rn(n, c, h, w) * 2 + 0.3)
+    gamma, beta = rn(c).abs() + 0.5, rn(c) * 0.3
+    bn = torch.nn.BatchNorm2d(c, eps=1e-5).double().train()
+    with torch.no_grad():
+        bn.weight.copy_(gamma)
+        bn.bias.copy_(beta)
+    yv = y.clone().requires_grad_(True)
+    a = torch.relu(bn(yv))
+    da = rn(n, c, h, w)
+    a.backward(da)
+    mean, var = y.mean((0, 2, 3)), y.var((0, 2, 3), unbiased=False)
+    invstd = 1.0 / torch.sqrt(var + 1e-5)
+    scale, shift = gamma * invstd, beta - mean * gamma * invstd
+    stored, aref, acond = R.bn_relu_bf16(y, scale, shift)
+    assert rel(aref, a.detach()) < 1e-12
+    assert torch.equal(stored, a.detach().float().to(torch.bfloat16).double()) or \
+        float((stored - a.detach()).abs().max()) <= 2.0 ** -8 * float(a.abs().max())
+    R.check_bound_bf16(stored.float(), aref, acond, R.TAU_BF16_PW, "apply")
+    dz, dzc = R.bn_bwd_dz(y, scale, shift, da)
+    assert torch.equal(dz, da * (a.detach() > 0)) and torch.equal(dzc, dz.abs())
+    s1, s2, b1, b2 = R.bn_bwd_sums(dz, y, mean, invstd)
+    cnt = n * h * w
+    dx, dxc = R.bn_bwd_apply(dz, y, scale, mean, invstd, s1 / cnt, s2 / cnt)
+    assert rel(dx, yv.grad) < 1e-10 and bool((dxc >= dx.abs() * (1 - 1e-12)).all())
+    assert bool((b1 >= s1.abs()).all()) and bool((b2 >= s2.abs()).all())
+    # the statistics epilogue's sums
+    q1, q2, c1_, c2_ = R.stored_sums(y)
+    assert rel(q1 / cnt, mean) < 1e-12 and rel(q2 / cnt - (q1 / cnt) ** 2, var) < 1e-10 and bool((c1_ >= q1.abs()).all())
+
+
+@pytest.mark.parametrize("h,w", [(6, 8), (7, 9)])
+def test_maxpool_route_equals_torch_including_ties(h, w):
+    """maxpool_route / pool_grad == F.max_pool2d(return_indices) and its gradient, on coarse values with many ties (torch, like
+    the kernels, keeps the first maximum in window order) and with the odd last row / column dropped."""
+    n, c = 2, 5
+    a = (torch.randint(0, 3, (n, c, h, w), generator=G).double() - 1).clamp_min(0)     # ReLU'd, mostly 0 / 1: ties everywhere
+    a[0, 0, :2, :2] = torch.tensor([[1.0, 1.0], [1.0, 1.0]])                           # a 4-way tie: position 0
+    a[0, 1, :2, :2] = torch.tensor([[0.0, 2.0], [2.0, 2.0]])                           # a 3-way tie: position 1
+    pooled, code = R.maxpool_route(a)
+    tp, ti = F.max_pool2d(a, 2, return_indices=True)
+    assert torch.equal(pooled, tp)
+    hp, wp = h // 2, w // 2
+    rr = torch.arange(hp).view(1, 1, hp, 1) * 2
+    cc = torch.arange(wp).view(1, 1, 1, wp) * 2
+    flat = (rr + code // 2) * w + (cc + code % 2)
+    assert torch.equal(flat, ti)
+    assert int(code[0, 0, 0, 0]) == 0 and int(code[0, 1, 0, 0]) == 1
+    dp = rn(n, c, hp, wp)
+    av = a.clone().requires_grad_(True)
+    F.max_pool2d(av, 2).backward(dp)
+    assert torch.equal(R.pool_grad(dp, code, h, w), av.grad)

@@ -1,6 +1,6 @@
 """GPU parity of the bf16 mixed-precision kernel family (include/gsd_bf16.h) against fp64 torch-CPU evaluations of the
 same contractions on the SAME bf16-rounded operands: what is left is fp32 accumulation order and the final rounding of
-the result to bf16 (half an ulp = 2^-9 relative)."""
+the result to bf16 (half an ulp: at most 2^-8 relative, at the bottom of a binade; 2^-9 only at its top)."""
 import ctypes as C
 
 import numpy as np
