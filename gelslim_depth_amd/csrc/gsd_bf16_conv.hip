@@ -57,28 +57,9 @@ struct GConvP {
   const float* bw_scale; const float* bw_shift; const float* bw_mean; const float* bw_invstd;
 };
 
-#ifndef GCONV_ABL   // diagnostic builds (profiles/build_diag_one.sh; results are then garbage): 1 the iteration barrier does not wait
-#define GCONV_ABL 0 // for the fills, 2 no fills after an item's first, 4 no epilogue stores, 8 no barrier (wait only), 16 no operand
-                    // reads after an iteration's first tap, 32 no MFMAs
-#endif
-#ifndef GCONV_CONTIG   // 0 (default): instruction k of wave w fills piece 4k + w.  1 (diagnostic builds): a wave's DMA instructions fill
-#define GCONV_CONTIG 0 // ONE contiguous LDS range, up to four sharing an LDS base (M0 set once, the 1-KiB steps in the instruction's
-#endif                 // immediate offset) -- measured 17 % SLOWER over the layer set (5.93 vs 5.08 ms): the interleaved order stays
-// LDS-DMA of one 1-KiB piece into piece index `pc` of the buffer at `buf`: with GCONV_CONTIG the LDS base is that of the
-// piece's group of four and the remainder is the instruction's immediate, which moves the global address alike (undone here)
+// LDS-DMA of one 1-KiB piece into piece index `pc` of the buffer at `buf`
 __device__ __forceinline__ void gconv_dma_piece(const void* g, unsigned char* buf, int pc) {
-#if GCONV_CONTIG
-  unsigned char* base = buf + (pc & ~3) * 1024;
-  const char* gp = (const char*)g;
-  switch (pc & 3) {
-    case 0: __builtin_amdgcn_global_load_lds((const void*)gp, base, 16, 0, 0); break;
-    case 1: __builtin_amdgcn_global_load_lds((const void*)(gp - 1024), base, 16, 1024, 0); break;
-    case 2: __builtin_amdgcn_global_load_lds((const void*)(gp - 2048), base, 16, 2048, 0); break;
-    default: __builtin_amdgcn_global_load_lds((const void*)(gp - 3072), base, 16, 3072, 0); break;
-  }
-#else
   __builtin_amdgcn_global_load_lds(g, buf + pc * 1024, 16, 0, 0);
-#endif
 }
 // BUF (template, MODE 0): fills go through buffer descriptors (buffer_load_dwordx4 ... lds): one 32-bit offset per piece, the image /
 // weight base and the channel chunk in the scalar offset, and an out-of-image or pad piece is an offset beyond num_records -- the
@@ -87,15 +68,6 @@ __device__ __forceinline__ void gconv_dma_piece(const void* g, unsigned char* bu
 __device__ __forceinline__ void gconv_dma_piece_buf(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, unsigned char* buf, int pc) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(buf + pc * 1024), 16, voff, soff, 0, 0);
 }
-#ifndef GCONV_STAMP   // diagnostic builds only: every block leaves (shader cycles, 100-MHz ticks) of its K-loop life in a buffer of
-#define GCONV_STAMP 0 // its own -> the clock the chip holds under this kernel (profiles/bench_bf16_conv.py, GSD_DIAG_STAMPS=1)
-#endif
-#if GCONV_STAMP
-__device__ unsigned long long gconv_stamp_buf[2 * 4096];
-extern "C" int gsd_diag_gconv_stamps(unsigned long long* host, int nblocks) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(gconv_stamp_buf), sizeof(unsigned long long) * 2 * (nblocks < 4096 ? nblocks : 4096)) == hipSuccess ? 0 : 1;
-}
-#endif
 template <int MODE, int WM, int WN, int BUF = 0>
 __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
   static_assert(!BUF || MODE == 0, "buffer-addressed fills: the 3x3 form");
@@ -122,8 +94,10 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
   const int g = lane >> 4, j = lane & 15;
-  // piece (1 KiB) index inside a buffer that instruction k of this wave fills (NI = instructions per wave for that buffer)
-  auto piece = [&](int k, int ni) { return GCONV_CONTIG ? wave * ni + k : k * 4 + wave; };
+  // piece (1 KiB) index inside a buffer that instruction k of this wave fills: the waves' pieces interleave.  A wave filling ONE
+  // contiguous LDS range instead, up to four instructions sharing an LDS base (M0 set once, the 1-KiB steps in the instruction's
+  // immediate offset), measured 17 % SLOWER over the layer set (5.93 vs 5.08 ms).
+  auto piece = [&](int k) { return k * 4 + wave; };
 
   // Persistent block: it walks pixel tiles pt, pt + pt_step, ... < pt_end for ONE m-block (gridDim.x is a multiple of mblocks),
   // so every weight address and coefficient is fixed per block.
@@ -183,7 +157,7 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
   int woff[NWI];
 #pragma unroll
   for (int k = 0; k < NWI; ++k) {
-    const int idx = piece(k, NWI) * 64 + lane;
+    const int idx = piece(k) * 64 + lane;
     const int tapk = idx / (BM * 4);
     const int row = (idx >> 2) % BM;
     const int gg = (idx & 3) ^ ((0x1320 >> (((row >> 2) & 3) * 4)) & 3);   // {0,2,3,1}
@@ -197,7 +171,7 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
   int xpk[MAXX];
 #pragma unroll
   for (int k = 0; k < MAXX; ++k) {
-    const int o = piece(MODE == 0 ? k : k % XPP, MODE == 0 ? MAXX : XPP) * 1024 + lane * 16;
+    const int o = piece(MODE == 0 ? k : k % XPP) * 1024 + lane * 16;
     const int px = o / 96, slot = (o - px * 96) >> 4;
     const int rowlen = MODE == 0 ? P.HC : P.TW;
     int v = -2;
@@ -246,17 +220,17 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
       // descriptors are rebuilt here from uniform values (scalar ALU): the weight image, and image n of the activations
       if (slot < NWI) {
         const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)P.wt, 0, P.wt_bytes, 0x00020000);
-        gconv_dma_piece_buf(rw, (unsigned)woff[slot] * 2u, (unsigned)((tap0 * P.Mpad * P.K + chunk * 32) * 2), Wl + (git & 1) * WBUF, piece(slot, NWI));
+        gconv_dma_piece_buf(rw, (unsigned)woff[slot] * 2u, (unsigned)((tap0 * P.Mpad * P.K + chunk * 32) * 2), Wl + (git & 1) * WBUF, piece(slot));
       } else {
         const int k = slot - NWI;
         const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(P.in + (long long)n * P.Hin * P.Win * P.in_pitch), 0, P.img_bytes, 0x00020000);
-        gconv_dma_piece_buf(rx, (unsigned)xoff[k], (unsigned)(chunk * 64), Xl + ((git / 3) & 1) * XBUF, piece(k, MAXX));
+        gconv_dma_piece_buf(rx, (unsigned)xoff[k], (unsigned)(chunk * 64), Xl + ((git / 3) & 1) * XBUF, piece(k));
       }
       return;
     }
     if (slot < NWI) {
       const u16* wsrc = P.wt + (long long)tap0 * P.Mpad * P.K + chunk * 32;
-      gconv_dma_piece((const void*)(wsrc + woff[slot]), Wl + (git & 1) * WBUF, piece(slot, NWI));
+      gconv_dma_piece((const void*)(wsrc + woff[slot]), Wl + (git & 1) * WBUF, piece(slot));
       return;
     }
     const int k = slot - NWI;
@@ -264,14 +238,14 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
     const void* sp = (const void*)gsd_zero16;
     if (MODE == 0) {
       if (xoff[k] >= 0) sp = (const void*)(src + xoff[k]);
-      gconv_dma_piece(sp, Xl + ((git / 3) & 1) * XBUF, piece(k, MAXX));
+      gconv_dma_piece(sp, Xl + ((git / 3) & 1) * XBUF, piece(k));
     } else {
       if (xoff[k] >= 0) {
         const int hi = P.stride * (h0 + (xoff[k] >> 16)) + P.ty[tap0], wi = P.stride * (w0 + ((xoff[k] >> 4) & 0xfff)) + P.tx[tap0];
         if ((unsigned)hi < (unsigned)P.Hin && (unsigned)wi < (unsigned)P.Win)
           sp = (const void*)(src + (long long)(hi * P.Win + wi) * P.in_pitch + (k / XPP) * 32 + (xoff[k] & 15) * 8);
       }
-      gconv_dma_piece(sp, Xl + (git & 1) * XBUF + (k / XPP) * (XPP * 4096), piece(k % XPP, XPP));   // plane k / XPP
+      gconv_dma_piece(sp, Xl + (git & 1) * XBUF + (k / XPP) * (XPP * 4096), piece(k % XPP));   // plane k / XPP
     }
   };
   // slots of one iteration: the weights always; the activations with every iteration (MODE 1) or with a chunk's first
@@ -310,9 +284,6 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
   decode(pt, n, h0, w0);
   prep(h0, w0);
   issue(0, 0, n, h0, w0);
-#if GCONV_STAMP
-  const unsigned long long st_c0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
   float s1[MT][4], s2[MT][4];   // this lane's running BatchNorm sums over all the block's items
 #pragma unroll
   for (int m = 0; m < MT; ++m)
@@ -348,13 +319,7 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
     constexpr int KH = decltype(khc)::value;
     constexpr int NS = (MODE == 1 || KH == 2) ? NWI + MAXX : NWI;     // DMA slots of this iteration
     constexpr int SPT = (NS + NTAPI - 1) / NTAPI;                       // per tap
-#if (GCONV_ABL) & 1
-    __syncthreads();
-#elif (GCONV_ABL) & 8
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-#else
     gsd_dma_barrier();   // iteration git's DMA has landed (vmcnt(0) + barrier) and every wave has left the other buffers
-#endif
     int f_it = it + 1, f_n = n, f_h0 = h0, f_w0 = w0;
     if (it + 1 == iters) {   // the fill belongs to the next item: it flies during this item's last iteration and epilogue
       f_it = 0;              // (after the last item it repeats this item's first fill, which nobody reads: no branch)
@@ -382,14 +347,8 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
 #pragma unroll
       for (int i = 0; i < MT * NT / 2; ++i) {
         const int m = i % MT, t = 2 * (i / MT);
-#if (GCONV_ABL) & 32   // no MFMAs (one VALU op keeps the operand reads alive)
-        acc[m][t][0] += __uint_as_float(a[kw & 1][m][0] ^ b[t][0]);
-        acc[m][t + 1][0] += __uint_as_float(a[kw & 1][m][1] ^ b[t + 1][1]);
-#else
         acc[m][t] = mfma_bf16(a[kw & 1][m], b[t], acc[m][t]);
         acc[m][t + 1] = mfma_bf16(a[kw & 1][m], b[t + 1], acc[m][t + 1]);
-#endif
-#if !((GCONV_ABL) & 16)   // 16: no operand reads after an iteration's first tap
         if (kw + 1 < NTAPI) {
           if (i < MT) a[(kw + 1) & 1][i] = *reinterpret_cast<const u32x4*>(Wc + (kw + 1) * BM * 64 + i * 1024);
           if (i >= MT && (i % MT) < 2) {   // i = 4, 5 -> b[0], b[1]; 8, 9 -> b[2], b[3]; 12, 13 -> b[4], b[5]
@@ -398,8 +357,7 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
           }
         }
         if (kw > 0 && i < 2) b[NT - 2 + i] = *reinterpret_cast<const u32x4*>(Xc + boff[NT - 2 + i] + kw * BSTEP);   // the last pair
-#endif
-        if (i < SPT && kw * SPT + i < NS && !(((GCONV_ABL) & 2) && git > 0)) dma_slot(kw * SPT + i, f_it, git + 1, f_n, f_h0, f_w0);
+        if (i < SPT && kw * SPT + i < NS) dma_slot(kw * SPT + i, f_it, git + 1, f_n, f_h0, f_w0);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -486,8 +444,8 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
               }
             }
           }
-          if (ch_ok[0] && pix_ok && !((GCONV_ABL) & 4)) *reinterpret_cast<u32x4s*>(ot) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-          if (ch_ok[1] && pix_ok && !((GCONV_ABL) & 4)) *reinterpret_cast<u32x4s*>(ot + 32) = u32x4{pk[4], pk[5], pk[6], pk[7]};
+          if (ch_ok[0] && pix_ok) *reinterpret_cast<u32x4s*>(ot) = u32x4{pk[0], pk[1], pk[2], pk[3]};
+          if (ch_ok[1] && pix_ok) *reinterpret_cast<u32x4s*>(ot + 32) = u32x4{pk[4], pk[5], pk[6], pk[7]};
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -522,8 +480,8 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
             s1[m][3] += q3; s2[m][3] = fmaf(q3, q3, s2[m][3]);
           }
         }
-        if (ch_ok[0] && pix_ok && !((GCONV_ABL) & 4)) *reinterpret_cast<u32x4s*>(ot + ooff[0]) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-        if (ch_ok[1] && pix_ok && !((GCONV_ABL) & 4)) *reinterpret_cast<u32x4s*>(ot + ooff[1]) = u32x4{pk[4], pk[5], pk[6], pk[7]};
+        if (ch_ok[0] && pix_ok) *reinterpret_cast<u32x4s*>(ot + ooff[0]) = u32x4{pk[0], pk[1], pk[2], pk[3]};
+        if (ch_ok[1] && pix_ok) *reinterpret_cast<u32x4s*>(ot + ooff[1]) = u32x4{pk[4], pk[5], pk[6], pk[7]};
       }
     }
   };
@@ -536,12 +494,6 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
   w0 = nw0;
   }
   gsd_dma_barrier();   // vmcnt(0): the last (unread) fill must have landed before the block gives its LDS back
-#if GCONV_STAMP
-  if (tid == 0 && blockIdx.x < 4096) {
-    gconv_stamp_buf[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st_c0;
-    gconv_stamp_buf[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - st_r0;
-  }
-#endif
   if (P.partials != nullptr) {
     // The block is persistent, so its statistics are too: every lane has summed its pixels of ALL the block's items in
     // registers; the 16-lane rows are summed with DPP once, here, and ONE partial row per (block, wave) leaves for HBM (a few

@@ -82,29 +82,8 @@ struct IncP {
 
 typedef unsigned u32x4s __attribute__((ext_vector_type(4), aligned(8)));
 
-#ifndef INC_NT      // 1: a0 / y1 leave as non-temporal stores (diagnostic switch while measuring)
-#define INC_NT 0
-#endif
-__device__ __forceinline__ void inc_store16(u16* p, u32x4 v) {
-#if INC_NT
-  __builtin_nontemporal_store(v, reinterpret_cast<u32x4s*>(p));
-#else
-  *reinterpret_cast<u32x4s*>(p) = v;
-#endif
-}
-
-#ifndef INC_ABL     // diagnostic builds only (results are then garbage): 1 no a0 stores, 2 no y1 stores, 4 no statistics,
-#define INC_ABL 0   // 8 no K loop, 16 the rebuild's activation is not staged in LDS
-#endif
-#ifndef INC_STAMP   // diagnostic builds only (profiles/build_diag_one.sh, profiles/bench_inc_block.py): wave 0 of every block
-#define INC_STAMP 0 // leaves the shader cycles it spent per phase (rebuild, K loop, epilogue, waiting at the barriers) in a buffer
-#endif
-#if INC_STAMP
-__device__ unsigned long long inc_stamp_buf[512 * 8];
-#define INC_T(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#else
-#define INC_T(v)
-#endif
+// a0 / y1 leave as plain 16-byte stores: non-temporal ones changed nothing (docs/LOG_r01-r04.md)
+__device__ __forceinline__ void inc_store16(u16* p, u32x4 v) { *reinterpret_cast<u32x4s*>(p) = v; }
 
 // Block = 8 waves, two per SIMD: with ONE wave per SIMD a vector instruction issues every ~4 cycles instead of 2
 // (MI355X_MICROARCH.md, 'vector-instruction ISSUE cost'), and this kernel's rebuild and epilogue are vector-bound -- in-kernel
@@ -225,14 +204,9 @@ __global__ __launch_bounds__(512) void inc_fused_bf16_kernel(const IncP P) {
     put_x();
   }
   gsd_dma_barrier();   // the weights have landed (vmcnt(0)); the first x tile is visible
-#if INC_STAMP
-  unsigned long long st_b = 0, st_c = 0, st_d = 0, st_w = 0, st_w2 = 0, st_w3 = 0, st_items = 0;
-  const unsigned long long st_begin = __builtin_amdgcn_s_memtime(), st_rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
   for (; tile < P.ntiles; tile += gridDim.x) {
     int n, h0, w0;
     decode(tile, n, h0, w0);
-    INC_T(t0);
     // ---- rebuild a0 = relu(bn(conv(x))) over the halo: one MFMA k-step per 16 halo pixels and m-tile -----------------
     // Two tiles (tt, tt + 8) per iteration, their gathers issued an iteration ahead.
     auto gather = [&](int tt, unsigned (&v)[8]) {
@@ -276,14 +250,9 @@ __global__ __launch_bounds__(512) void inc_fused_bf16_kernel(const IncP P) {
       }
       if (q < G::NPH) {
         const int sw = (g ^ ((c >> 1) & 2)) << 4;
-#if (INC_ABL) & 16   // diagnostic: the rebuilt activation is not staged (the never-true test keeps pk alive)
-        if (pk[0] == 0x12345u)
-#endif
-        {
-          *reinterpret_cast<u32x4*>(Al + q * 64 + sw) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-          *reinterpret_cast<u32x4*>(Al + G::ACT_PLANE + q * 64 + sw) = u32x4{pk[4], pk[5], pk[6], pk[7]};
-        }
-        if (!((INC_ABL) & 1) && inimg && r >= 1 && r <= TH && c >= 1 && c <= I_TW) {   // the tile's own pixels: a0 goes to HBM once
+        *reinterpret_cast<u32x4*>(Al + q * 64 + sw) = u32x4{pk[0], pk[1], pk[2], pk[3]};
+        *reinterpret_cast<u32x4*>(Al + G::ACT_PLANE + q * 64 + sw) = u32x4{pk[4], pk[5], pk[6], pk[7]};
+        if (inimg && r >= 1 && r <= TH && c >= 1 && c <= I_TW) {   // the tile's own pixels: a0 goes to HBM once
           u16* o = P.a0 + ((long long)(n * P.H + h) * P.W + w) * P.a0_pitch + g * 8;
           inc_store16(o, u32x4{pk[0], pk[1], pk[2], pk[3]});
           inc_store16(o + 32, u32x4{pk[4], pk[5], pk[6], pk[7]});
@@ -309,9 +278,7 @@ __global__ __launch_bounds__(512) void inc_fused_bf16_kernel(const IncP P) {
         finish(tt + NW, accb);
       }
     }
-    INC_T(t1);
     __syncthreads();   // the activation tile is complete
-    INC_T(t2);
     const int next = tile + (int)gridDim.x;
     if (next < P.ntiles) fetch(next);   // flies during the K loop
 
@@ -336,7 +303,7 @@ __global__ __launch_bounds__(512) void inc_fused_bf16_kernel(const IncP P) {
     for (int t = 0; t < TR; ++t) b[0][t] = rdB(0, t);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int s = 0; s < (((INC_ABL) & 8) ? 1 : 18); ++s) {
+    for (int s = 0; s < 18; ++s) {
       // 2 TR micro-steps of {two MFMAs, one operand read for the next k-step}, pinned in this order (the LDS instructions keep
       // their program order anyway, so the interleaving has to be written out)
 #pragma unroll
@@ -351,9 +318,7 @@ __global__ __launch_bounds__(512) void inc_fused_bf16_kernel(const IncP P) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    INC_T(t3);
     __syncthreads();   // every wave has left the activation tile
-    INC_T(t4);
     if (next < P.ntiles) put_x();   // (the x tile's readers finished before the barrier in front of the K loop)
 
     // ---- epilogue: y1 (raw, bf16) + the BatchNorm partial sums of the values as stored --------------------------------
@@ -373,7 +338,7 @@ __global__ __launch_bounds__(512) void inc_fused_bf16_kernel(const IncP P) {
           const unsigned lo = pack_bf16(v[0], v[1]), hi = pack_bf16(v[2], v[3]);
           pk[2 * m] = lo;
           pk[2 * m + 1] = hi;
-          if (ok && !((INC_ABL) & 4)) {
+          if (ok) {
             const float q0 = __uint_as_float(lo << 16), q1 = __uint_as_float(lo & 0xffff0000u);
             const float q2 = __uint_as_float(hi << 16), q3 = __uint_as_float(hi & 0xffff0000u);
             s1[m][0] += q0; s2[m][0] = fmaf(q0, q0, s2[m][0]);
@@ -382,7 +347,7 @@ __global__ __launch_bounds__(512) void inc_fused_bf16_kernel(const IncP P) {
             s1[m][3] += q3; s2[m][3] = fmaf(q3, q3, s2[m][3]);
           }
         }
-        if (ok && (!((INC_ABL) & 2) || pk[0] == 0x12345u)) {
+        if (ok) {
           u16* o = y_o0 + t * y_row;
           inc_store16(o, u32x4{pk[0], pk[1], pk[2], pk[3]});
           inc_store16(o + 32, u32x4{pk[4], pk[5], pk[6], pk[7]});
@@ -391,20 +356,8 @@ __global__ __launch_bounds__(512) void inc_fused_bf16_kernel(const IncP P) {
     };
     if (interior) epilogue(std::integral_constant<bool, false>{});
     else epilogue(std::integral_constant<bool, true>{});
-    INC_T(t5);
     __syncthreads();   // the next x tile is visible
-#if INC_STAMP
-    const unsigned long long t6 = __builtin_amdgcn_s_memtime();
-    st_b += t1 - t0; st_c += t3 - t2; st_d += t5 - t4; st_w += t2 - t1; st_w2 += t4 - t3; st_w3 += t6 - t5; ++st_items;
-#endif
   }
-#if INC_STAMP
-  if (tid == 0 && blockIdx.x < 512) {
-    unsigned long long* o = inc_stamp_buf + 8 * blockIdx.x;
-    o[0] = st_b; o[1] = st_c; o[2] = st_d; o[3] = st_w; o[4] = st_items;
-    o[5] = __builtin_amdgcn_s_memtime() - st_begin; o[6] = __builtin_amdgcn_s_memrealtime() - st_rt0; o[7] = st_w2 | (st_w3 << 32);
-  }
-#endif
   // ---- one partial row per block: 16-lane DPP sums, then the eight waves through LDS (the x tile's space) ---------------
   __syncthreads();
 #pragma unroll
@@ -444,12 +397,6 @@ int inc_cu_count() {
 long inc_tiles(int N, int H, int W) { return (long)N * ceil_div(H, INC_TH) * ceil_div(W, I_TW); }
 
 }  // namespace
-
-#if INC_STAMP
-extern "C" int gsd_diag_inc_stamps(unsigned long long* host, int nblocks) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(inc_stamp_buf), sizeof(unsigned long long) * 8 * (nblocks < 512 ? nblocks : 512)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 extern "C" int gsd_bf16_inc_supported(int C, int M) { return (C >= 1 && 9 * C <= 32 && M == I_M) ? 1 : 0; }
 

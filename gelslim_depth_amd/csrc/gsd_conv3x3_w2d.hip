@@ -57,16 +57,6 @@ struct W2DParams {
   float* slabs; // 2 x 4 outputs per channel and Winograd tile to [tile][slab][m-block][64 channels][16 NWP tiles][8] floats
 };
 
-#ifndef W2D_PIPE   // 1: pin the interleave of a frequency row's MFMAs with the next row's transform (sched_group_barrier)
-#define W2D_PIPE 1
-#endif
-#ifndef W2D_PK   // 1: the operand transform on pairs of floats (v_pk_add_f32 / v_pk_fma_f32): same operations in the same order on
-#define W2D_PK 1  // every element -- bit-identical -- in about half the vector instructions
-#endif
-#ifndef W2D_ABL   // diagnostic builds only (profiles/build_diag_one.sh; results are then garbage): 1 no weight fills after a block's first,
-#define W2D_ABL 0 // 2 no halo fills after the first, 4 barrier without the wait for the fills, 8 no MFMAs, 16 no operand transform,
-                  // 32 no barrier (own fills only)
-#endif
 namespace {
 constexpr int W2D_BM = 64;
 constexpr int W2D_WTILE = 96 * W2D_BM;   // floats per weight chunk (24 KiB)
@@ -472,18 +462,6 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
 #pragma unroll
     for (int f = 0; f < 24; ++f) acc[m][f] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // V row = B4^T t of one frequency row: the 6 values of a (column-transformed) window row -> the 6 row frequencies
-  auto row_transform = [&](const float (&d)[6], float (&v)[6]) {
-    const float a = fmaf(-4.f, d[2], d[4]), b = fmaf(-4.f, d[1], d[3]);
-    const float c = d[4] - d[2], e = 2.f * (d[3] - d[1]);
-    v[0] = fmaf(4.f, d[0], fmaf(-5.f, d[2], d[4]));
-    v[1] = a + b;
-    v[2] = a - b;
-    v[3] = c + e;
-    v[4] = c - e;
-    v[5] = fmaf(4.f, d[1], fmaf(-5.f, d[3], d[5]));
-  };
-
   const int a_lane = mh * 64 + l16 * 4;   // this wave's (f, f+1) x two m-tiles of a frequency pair: 16 lanes read 256 contiguous bytes
   begin_fill(c_lo, 0);
   weight_fill(c_lo, smem);
@@ -516,10 +494,6 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
         }
       }
       __syncthreads();
-    } else if ((W2D_ABL) & 32) {
-      __builtin_amdgcn_s_waitcnt(0x0F70);   // diagnostic: own fills only, no barrier at all (racy: what the barrier itself costs)
-    } else if ((W2D_ABL) & 4) {
-      __syncthreads();
     } else {
       gsd_dma_barrier();   // the chunk's fills have landed; everyone has left the other image
     }
@@ -543,7 +517,6 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
     f32x4 av[2];
     av[0] = *reinterpret_cast<const f32x4*>(&Wc[(j * 12) * 128 + a_lane]);
     if constexpr (!PLAIN) {
-#if W2D_PK
       const f32x2v sc2 = {sc, sc}, sh2 = {sh, sh};
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -553,12 +526,6 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
           d[i][c] = fmaxf(y[0], lo);
           d[i][c + 1] = fmaxf(y[1], lo);
         }
-#else
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) d[i][c] = fmaxf(fmaf(d[i][c], sc, sh), lo);
-#endif
     }
     __builtin_amdgcn_sched_barrier(0);
     // frequency rows in the order that retires window rows early: t0 = d0 - d2, t3 = d1 - d3, t1 = d1 + d2, t2 = d2 - d1.
@@ -566,11 +533,11 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
     // 12 MFMAs of row fi -- an MFMA holds the SIMD's vector issue for 8 of its 32 cycles, three vector instructions fit its shadow.
     constexpr int FR[4] = {0, 3, 1, 2};
     auto freq_row = [&](int fr, float (&v)[6]) {
-#if (W2D_PK) && !((W2D_ABL) & 16)
+      // V row = B4^T t of one frequency row, on pairs of floats (v_pk_add_f32 / v_pk_fma_f32: about half the vector instructions):
       // pairs (t0,t1), (t2,t3), (t4,t5) of the column-transformed row, then
       //   (a, c) = t4 + (-4,-1) t2      (b, e) = t3 + (-4,-1) t1      (v1, v2) = a + (1,-1) b      (v3, v4) = c + (2,-2) e
       //   (v0, v5) = 4 (t0,t1) + ((t4,t5) - 5 (t2,t3))
-      // -- element for element the fused multiply-adds of row_transform (a multiplication by 1, 2 or -1 is exact)
+      // -- element for element the fused multiply-adds of the scalar transform (a multiplication by 1, 2 or -1 is exact)
       f32x2v tp[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -585,18 +552,6 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       const f32x2v v34 = __builtin_elementwise_fma(f32x2v{be[1], be[1]}, p2m2, f32x2v{ac[1], ac[1]});
       const f32x2v v05 = __builtin_elementwise_fma(tp[0], p4, __builtin_elementwise_fma(tp[1], m5, tp[2]));
       v[0] = v05[0], v[1] = v12[0], v[2] = v12[1], v[3] = v34[0], v[4] = v34[1], v[5] = v05[1];
-      return;
-#endif
-      float t[6];
-#pragma unroll
-      for (int c = 0; c < 6; ++c)
-        t[c] = fr == 0 ? d[0][c] - d[2][c] : fr == 3 ? d[1][c] - d[3][c] : fr == 1 ? d[1][c] + d[2][c] : d[2][c] - d[1][c];
-#if (W2D_ABL) & 16
-#pragma unroll
-      for (int c = 0; c < 6; ++c) v[c] = t[c];
-#else
-      row_transform(t, v);
-#endif
     };
     float v[2][6];
     freq_row(FR[0], v[0]);
@@ -613,20 +568,15 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
           av[((s >> 1) + 1) & 1] = *reinterpret_cast<const f32x4*>(&Wc[(j * 12 + (fn >> 1)) * 128 + a_lane]);
         }
         const f32x4& ap = av[(s >> 1) & 1];
-#if (W2D_ABL) & 8
-        acc[0][f][0] += ap[(s & 1) * 2] * v[fi & 1][fc];
-        acc[1][f][0] += ap[(s & 1) * 2 + 1] * v[fi & 1][fc];
-#else
         acc[0][f] = mfma16(ap[(s & 1) * 2], v[fi & 1][fc], acc[0][f]);
         acc[1][f] = mfma16(ap[(s & 1) * 2 + 1], v[fi & 1][fc], acc[1][f]);
-#endif
         // the next chunk's fills ride in the first k-steps: the weights in one k-step (shared LDS bases), then the halo
         if (more && s < 3) {
           float* Wn = smem + (cur ^ 1) * BUF;
           if (s == 0) {
             begin_fill(chunk + 1, cur ^ 1);
-            if (!((W2D_ABL) & 1)) weight_fill(chunk + 1, Wn);
-          } else if (!((W2D_ABL) & 2)) {
+            weight_fill(chunk + 1, Wn);
+          } else {
             if constexpr (PC) {
               halo_unit(s - 1, Wn + WTILE);
             } else {
@@ -637,8 +587,8 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-#if W2D_PIPE
-      if (fi > 0 || !more) {   // (row 0 carries the fills: its k-steps are pinned above)
+      // the interleave of the row's MFMAs with the next row's transform, pinned (row 0 carries the fills: its k-steps are pinned above)
+      if (fi > 0 || !more) {
 #pragma unroll
         for (int g = 0; g < 6; ++g) {
           __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);   // two MFMAs
@@ -646,7 +596,6 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
           __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);   // four vector instructions of the next row's transform
         }
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -657,7 +606,6 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
 
   // Y = A2^T M A4 of one channel's tile: down the columns first (24 -> 12 values), then along the rows (12 -> 2 x 4 outputs)
   auto out_transform = [&](int m, int reg, float (&y)[2][4]) __attribute__((always_inline)) {
-#if W2D_PK
     // two channels at once: accumulator registers (2 rp, 2 rp + 1) of a quad are an aligned pair, so the same additions and fused
     // multiply-adds run as v_pk_add_f32 / v_pk_fma_f32; an odd reg takes the second halves of what its even neighbour computed
     // (the compiler merges the two calls' identical packed instructions)
@@ -676,22 +624,6 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       const f32x2v y0 = R[0] + p12 + p34, y1 = __builtin_elementwise_fma(c2, m34, m12), y2 = __builtin_elementwise_fma(c4, p34, p12);
       const f32x2v y3 = __builtin_elementwise_fma(c8, m34, m12) + R[5];
       y[a][0] = y0[reg & 1], y[a][1] = y1[reg & 1], y[a][2] = y2[reg & 1], y[a][3] = y3[reg & 1];
-    }
-    return;
-#endif
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      float R[6];
-#pragma unroll
-      for (int fc = 0; fc < 6; ++fc) {
-        const float M1 = acc[m][6 + fc][reg], M2 = acc[m][12 + fc][reg];
-        R[fc] = a == 0 ? acc[m][fc][reg] + M1 + M2 : M1 - M2 - acc[m][18 + fc][reg];
-      }
-      const float p12 = R[1] + R[2], m12 = R[1] - R[2], p34 = R[3] + R[4], m34 = R[3] - R[4];
-      y[a][0] = R[0] + p12 + p34;
-      y[a][1] = fmaf(2.f, m34, m12);
-      y[a][2] = fmaf(4.f, p34, p12);
-      y[a][3] = fmaf(8.f, m34, m12) + R[5];
     }
   };
 

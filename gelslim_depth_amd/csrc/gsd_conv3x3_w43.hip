@@ -35,24 +35,6 @@ __device__ __attribute__((aligned(16))) const float gsd_pad16_w43[8] = {0.f, 0.f
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// Diagnostic build only (-DGSD_W43_STAMPS; never in the product library): s_memtime stamps around the segments of a K-chunk,
-// summed per wave in scalar registers and written to a buffer of their own (cdna_hip_programming.md sec. 7, In-kernel stamps).
-#ifdef GSD_W43_STAMPS
-static unsigned long long* g_w43_stamp_buf = nullptr;
-extern "C" void gsd_w43_set_stamp_buffer(void* p) { g_w43_stamp_buf = (unsigned long long*)p; }
-#define W43_STAMP(i)                                                                             \
-  {                                                                                              \
-    unsigned long long t_;                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                   \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    st_acc[i] += t_ - st_prev;                                                                   \
-    st_prev = t_;                                                                                \
-  }
-#else
-#define W43_STAMP(i) {}
-#endif
-
 struct W43Params {
   SrcD src0, src1;
   DstD dst0, dst1;
@@ -70,7 +52,6 @@ struct W43Params {
   int fold;              // tile rows run over the padded flat rows of the whole batch (see w43_row)
   int nslab;             // K-slab form (SPLIT): the block's channel chunks are slab k's share, its y goes to `slabs`
   float* slabs;          // [nslab][tile blocks][64 channels][64 Winograd tiles][4 pixels]: un-reduced outputs of the K slabs
-  unsigned long long* stamps;   // diagnostic builds only
 };
 
 namespace {
@@ -238,14 +219,14 @@ __device__ __forceinline__ void w43_epilogue(const W43Params& P, int n, int pt, 
 //
 // FAST: straight halo fills, no per-slot bookkeeping (which segment, how many channels it has left, which sentinel: a
 // chain of scalar branches per slot in the general form): possible when a chunk of 4 channels never straddles the two
-// source segments and Cin % 4 == 0 (always true in the U-Net).  Stamps (profiles/stamp_conv.py) put the per-slot form at
-// ~1200 of the cycles a wave spends per chunk; measured -7 % kernel time over the U-Net's layer set.
+// source segments and Cin % 4 == 0 (always true in the U-Net).  In-kernel stamps put the per-slot form at ~1200 of the cycles a
+// wave spends per chunk (docs/LOG_r01-r04.md, round 2); measured -7 % kernel time over the U-Net's layer set.
 //
 // PLAIN: no source segment carries a deferred BatchNorm or ReLU (every dX launch: dy is plain; the pooled and upsampled
 // sources of the forward): the operand transform drops its 12 fma/max per kernel row and the per-chunk scale / shift
 // reads.  Measured with the transform forced plain over the layer set: -2.5 % kernel time.
 //
-// X4M: 0 the dword halo gathers, 1 the X4 form above.  Ablation (fills removed, profiles/build_diag.sh -DW43_ABL): the dword halo
+// X4M: 0 the dword halo gathers, 1 the X4 form above.  Ablation (fills removed, docs/LOG_r01-r04.md, round 2): the dword halo
 // fills cost 9.5 % of the kernel's time, the weight fills 3 %, the barrier 2 % -- memory traffic and latency, not instruction
 // count: 16-byte pieces from unaligned rows were measured neutral over the step (docs/LOG_r01-r04.md).
 //
@@ -254,13 +235,7 @@ __device__ __forceinline__ void w43_epilogue(const W43Params& P, int n, int pt, 
 // runs chunks [k nchunks / S, (k+1) nchunks / S) and stores its UN-reduced y = A^T M tile to P.slabs; w43_slab_reduce_kernel adds
 // the S slabs in slab order and runs this kernel's epilogue (crop, statistics, fused BatchNorm-backward) on the sums.
 template <int X4M, bool FAST, bool PLAIN, bool SPLIT = false>
-#ifndef W43_ABL   // diagnostic builds: 1 no weight fills, 2 no halo fills, 4 no barrier per chunk, 8 no wait for the fills, 16 / 32 halo fills from hot addresses (results are then garbage)
-#define W43_ABL 0
-#endif
-#ifndef W43_MIN_WAVES   // diagnostic builds: waves per SIMD the register allocation must admit for the 4-wave form
-#define W43_MIN_WAVES 2
-#endif
-__global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W43Params P) {
+__global__ __launch_bounds__(256, 2) void conv3x3_w43_kernel(const W43Params P) {
   constexpr bool X4 = X4M == 1;
   static_assert(!SPLIT || FAST, "K slabs: the straight-fill form");
   constexpr int MT = 4, BM = W43_BM, WS = BM, WTILE = W43_WTILE, NT = 256, NWAVE = 4, NWI = W43_NWI;
@@ -273,10 +248,6 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
   // wave: pixel group of the wave.  wm (0 in a 256-thread block) stays a run-time value: folding it to 0 changes the register
   // allocation of the kernel, and this form is the one that was measured
   const int wm = wave8 >> 2, wave = wave8 & 3;
-#ifdef GSD_W43_STAMPS
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
-#endif
   const int j = lane >> 4, l16 = lane & 15;
 
   // The m-blocks of one pixel tile read the same halo: hardware deals blocks round-robin over the 8 XCDs, so give every XCD
@@ -442,13 +413,7 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
         }
       } else {
         if (p_on[pp] && f_xo[pp] >= 0) {
-#if (W43_ABL) & 16   // diagnostic: every halo lane reads chunk 0's address (same instructions, bytes from the L1 / L2 instead of HBM)
-          const float* gp = P.src0.p + f_xl[pp];
-#elif (W43_ABL) & 32   // diagnostic: every halo lane reads ONE address
-          const float* gp = P.src0.p;
-#else
           const float* gp = d_base + f_xl[pp];
-#endif
           float* dstp = Xb + ch * PS + (wave8 + NWAVE * pp) * 64;
           __builtin_amdgcn_global_load_lds(gp, dstp, 4, 0, 0);
         }
@@ -584,17 +549,9 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
   if constexpr (FAST) begin_fill(c_lo, 0);
 #pragma unroll
   for (int slot = 0; slot < NWI + 4; ++slot) dma_slot(slot, c_lo, 0);
-  W43_STAMP(5)   // prologue
   for (int chunk = c_lo; chunk < c_hi; ++chunk) {
     const int cur = (chunk - c_lo) & 1;
-    if ((W43_ABL) & 4) {
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-    } else if ((W43_ABL) & 8) {   // barrier without waiting for the fills: what their latency costs
-      __syncthreads();
-    } else {
-      gsd_dma_barrier();
-    }
-    W43_STAMP(0)   // wait for the chunk's DMA + barrier
+    gsd_dma_barrier();
     const int kc = chunk * 4 + j;
     float sc = 1.f, sh = 0.f, lo = 0.f;
     if constexpr (!PLAIN) {
@@ -603,17 +560,15 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
     }
     const bool more = chunk + 1 < c_hi;
     const float* Wc = smem + cur * BUF;
-#ifndef W43_PF   // k-steps the weight operand is read ahead of its MFMAs
-#define W43_PF 1
-#endif
-    f32x4 av[W43_PF + 1];
+    constexpr int PF = 1;   // k-steps the weight operand is read ahead of its MFMAs
+    f32x4 av[PF + 1];
     f32x4 ra[2];
     f32x2 rb[2];
     float v[6];
     ra[0] = *reinterpret_cast<const f32x4*>(&Wc[baddr]);
     rb[0] = *reinterpret_cast<const f32x2*>(&Wc[baddr + 4]);
 #pragma unroll
-    for (int s = 0; s < W43_PF; ++s) av[s] = *reinterpret_cast<const f32x4*>(&Wc[(j * 18 + s) * WS + a_lane]);
+    for (int s = 0; s < PF; ++s) av[s] = *reinterpret_cast<const f32x4*>(&Wc[(j * 18 + s) * WS + a_lane]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -623,12 +578,11 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
         rb[(r + 1) & 1] = *reinterpret_cast<const f32x2*>(&Wc[baddr + (r + 1) * P.WCp + 4]);
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (r == 0) W43_STAMP(1)   // first operand reads + first transform: no MFMA of this wave yet
 #pragma unroll
       for (int f = 0; f < 6; ++f) {
-        const int s = r * 6 + f, cs = s % (W43_PF + 1);
-        if (s + W43_PF < 18)
-          av[(s + W43_PF) % (W43_PF + 1)] = *reinterpret_cast<const f32x4*>(&Wc[(j * 18 + s + W43_PF) * WS + a_lane]);
+        const int s = r * 6 + f, cs = s % (PF + 1);
+        if (s + PF < 18)
+          av[(s + PF) % (PF + 1)] = *reinterpret_cast<const f32x4*>(&Wc[(j * 18 + s + PF) * WS + a_lane]);
 #pragma unroll
         for (int m = 0; m < MT; ++m) acc[m][f] = mfma16(av[cs][m], v[f], acc[m][f]);
         if constexpr (FAST) {
@@ -638,7 +592,6 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
           if (more && s < 3) {
             if (s == 0) {
               begin_fill(chunk + 1, cur ^ 1);
-              if (!((W43_ABL) & 1)) {
               float* Wn = smem + (cur ^ 1) * BUF;
               const float* wg = wsrc0 + (size_t)(chunk + 1) * WTILE + wave8 * 1024 + lane * 4;
               float* wl = Wn + wave8 * 1024;
@@ -651,27 +604,18 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
                 float* wl2 = Wn + (14 + wave8) * 256;
                 __builtin_amdgcn_global_load_lds(wg2, wl2, 16, 0, 0);
               }
-              }
-            } else if (!((W43_ABL) & 2)) {
+            } else {
               dma_slot(NWI + 2 * s - 2, chunk + 1, cur ^ 1);
               dma_slot(NWI + 2 * s - 1, chunk + 1, cur ^ 1);
             }
           }
         } else if (more && s < 5) {
-#ifdef W43_STAMP_DMA
-          W43_STAMP(2)
-#endif
           dma_slot(2 * s, chunk + 1, cur ^ 1);
           dma_slot(2 * s + 1, chunk + 1, cur ^ 1);
-#ifdef W43_STAMP_DMA
-          W43_STAMP(6)   // the DMA slots alone
-#endif
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (s == (FAST ? 2 : 4)) W43_STAMP(2)   // the k-steps that carry the next chunk's DMA issue
       }
     }
-    W43_STAMP(3)     // the other thirteen k-steps (52 MFMAs)
   }
 
   // ---- epilogue: y = A^T M, NCHW stores (two destination segments with crop), BatchNorm partial sums ----------------------
@@ -699,13 +643,6 @@ __global__ __launch_bounds__(256, W43_MIN_WAVES) void conv3x3_w43_kernel(const W
   } else {
     w43_epilogue(P, n, pt, wave, wm, m0, j, l16, n_t, h_t, w0, tq, vmask, sBw, out_transform);
   }
-#ifdef GSD_W43_STAMPS
-  W43_STAMP(4)   // epilogue
-  if (P.stamps != nullptr && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) P.stamps[((size_t)blockIdx.x * NWAVE + wave8) * 8 + i] = st_acc[i];
-  }
-#endif
 }
 
 // K-slab reducer: block (pixel tile, m-block) adds the S un-reduced 64 x 256 tiles the SPLIT blocks left in P.slabs, in slab order
@@ -1018,10 +955,6 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   P.dst0 = to_dstd(dst[0]);
   P.dst1 = ndst > 1 ? to_dstd(dst[1]) : null_dstd();
   P.wt = wt;
-  P.stamps = nullptr;
-#ifdef GSD_W43_STAMPS
-  P.stamps = g_w43_stamp_buf;
-#endif
   P.partials = partials;
   P.bw_raw = bw_raw; P.bw_scale = bw_scale; P.bw_shift = bw_shift; P.bw_mean = bw_mean; P.bw_invstd = bw_invstd;
   P.Cin = Cin;

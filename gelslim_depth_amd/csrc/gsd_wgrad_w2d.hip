@@ -46,14 +46,6 @@
 
 typedef float f32x2d __attribute__((ext_vector_type(2)));
 
-// Diagnostic builds only (-DWG2D_ABL=mask via profiles/build_diag_one.sh; never in the product library; results are then garbage):
-// 1 no MFMAs, 2 no LDS-DMA fills after the first two k-steps, 4 no transform after the first two, 8 no operand reads, 16 no barrier,
-// 32 no dy fills, 64 no window fills, 128 every fill reads offset 0 (issue cost without the memory system's).  Any non-zero mask
-// also runs the phase-separated loop (transform, fills, MFMAs one after the other) instead of the pipelined one.
-#ifndef WG2D_ABL
-#define WG2D_ABL 0
-#endif
-
 struct WgW2dParams {
   SrcD a0, a1;   // activation (B operand), up to two concatenated segments
   SrcD dy;       // gradient w.r.t. the raw conv output (plain, row pitch % 4 == 0, 16-byte aligned)
@@ -247,32 +239,26 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
     auto fill = [&](const char* base, unsigned off, float* dst) __attribute__((always_inline)) {
       __builtin_amdgcn_global_load_lds(reinterpret_cast<const float*>(base + off), dst, 16, 0, 0);
     };
-    if constexpr (WG2D_ABL & 128) o_y0 = o_y1 = 0u;
     // window pieces: one with a column inside the segment lies within 3 floats of its row's ends (slack >= 4) and is read where it
     // lies, partly outside or not (the transform masks by column); one without is not read where it lies (offset 0)
-    if constexpr (!(WG2D_ABL & 64)) {
 #pragma unroll
-      for (int k = 0; k < KB; ++k)
-        if (wave + 8 * k < P.NI) {
-          unsigned off = (unsigned)v_org + x_off[k];
-          if (!inside) {
-            int mt = x_meta;
-            asm volatile("" : "+v"(mt));   // (unpacked HERE, in border k-steps only: hipcc would hoist the fields out of the loop into registers)
-            mt >>= 8 * k;
-            const int row = hs + (mt & 15), c0 = wsx + 4 * (mt >> 4 & 7);
-            const bool ok = !(mt & 128) && (unsigned)row < (unsigned)S_H && c0 + 3 >= 0 && c0 < S_W;
-            off = ok ? off : 0u;
-          }
-          if constexpr (WG2D_ABL & 128) off = 0u;
-          fill(vblk, off, smem + WIN + wb * (WINI * 256) + (wave + 8 * k) * 256);
+    for (int k = 0; k < KB; ++k)
+      if (wave + 8 * k < P.NI) {
+        unsigned off = (unsigned)v_org + x_off[k];
+        if (!inside) {
+          int mt = x_meta;
+          asm volatile("" : "+v"(mt));   // (unpacked HERE, in border k-steps only: hipcc would hoist the fields out of the loop into registers)
+          mt >>= 8 * k;
+          const int row = hs + (mt & 15), c0 = wsx + 4 * (mt >> 4 & 7);
+          const bool ok = !(mt & 128) && (unsigned)row < (unsigned)S_H && c0 + 3 >= 0 && c0 < S_W;
+          off = ok ? off : 0u;
         }
-    }
+        fill(vblk, off, smem + WIN + wb * (WINI * 256) + (wave + 8 * k) * 256);
+      }
     // dy pieces go into the slots this thread reads its raw dy rows from: those reads have to have RETURNED before a fill can land
     __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-    if constexpr (!(WG2D_ABL & 32)) {
-      fill(dblk, o_y0, raw_w);
-      if constexpr (!UROW) fill(dblk, o_y1, raw_w + 8 * 256);
-    }
+    fill(dblk, o_y0, raw_w);
+    if constexpr (!UROW) fill(dblk, o_y1, raw_w + 8 * 256);
   };
 
   // transform this thread's raw pieces into LDS image `buf` (compile-time constant)
@@ -379,35 +365,6 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
   const int a_rd = IMG + j * TSU + (wm * 32 + l16) * 24;
   const int b_rd = IMG + 4 * TSU + j * TSV + (wn * 16 + l16) * 24;
 
-  // One operand group = four frequencies of (channel l16, tile j) per ds_read_b128: 3 reads feed 8 MFMAs.  The groups are NOT
-  // double-buffered in the source: 12 operand registers instead of 24 keep the kernel inside 256 registers without scratch, and the
-  // SIMD's other wave multiplies while this one waits for its reads.
-  auto multiply = [&](auto buf_c) __attribute__((always_inline)) {
-    constexpr int buf = decltype(buf_c)::value;
-    const float* const Sb = smem + buf * BUF;
-#pragma unroll
-    for (int g = 0; g < 6; ++g) {
-      f32x4 a0, a1, b;
-      if constexpr (WG2D_ABL & 8) {
-        a0 = a1 = b = f32x4{1.f, 2.f, 3.f, (float)g};
-      } else {
-        a0 = *reinterpret_cast<const f32x4*>(Sb + a_rd + 4 * g);
-        a1 = *reinterpret_cast<const f32x4*>(Sb + a_rd + 16 * 24 + 4 * g);
-        b = *reinterpret_cast<const f32x4*>(Sb + b_rd + 4 * g);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if constexpr (WG2D_ABL & 1) {
-          acc[0][4 * g + e][e] += a0[e] * b[e];
-          acc[1][4 * g + e][e] += a1[e] * b[e];
-        } else {
-          acc[0][4 * g + e] = mfma16(a0[e], b[e], acc[0][4 * g + e]);
-          acc[1][4 * g + e] = mfma16(a1[e], b[e], acc[1][4 * g + e]);
-        }
-      }
-    }
-  };
-
   // ---- pipeline: image (it & 1) holds the transforms of k-step `it`; the raw registers hold k-step it + 1 ---------------------
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -423,29 +380,20 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
 #pragma unroll
     for (int f = 0; f < 24; ++f) acc[m][f] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (nst > 0) {
-    auto step = [&](const int it, auto cur_c) __attribute__((always_inline)) {
-      constexpr int cur = decltype(cur_c)::value;
-      if (it + 1 < nst && !((WG2D_ABL & 4) && it > 1)) transform(std::integral_constant<int, cur ^ 1>{});
-      __builtin_amdgcn_sched_barrier(0);   // (phases in program order: the register budget is 192 accumulators + one phase's values)
-      if (it + 2 < nst && !((WG2D_ABL & 2) && it > 1)) load(cur_c);   // k-step it + 2 has this one's parity
-      __builtin_amdgcn_sched_barrier(0);
-      multiply(cur_c);
-      // the fills of k-step it + 2 have the MFMA phase to land; published to the other waves (window pieces) by the barrier
-      if constexpr (!(WG2D_ABL & 16)) gsd_dma_barrier();
-    };
-#ifndef WG2D_PIPE   // 1: the transform of k-step it + 1 in pieces BETWEEN the MFMA groups of k-step it (software pipeline inside the wave)
-#define WG2D_PIPE 1
-#endif
+    // The transform of k-step it + 1 runs in pieces BETWEEN the MFMA groups of k-step it (a software pipeline inside the wave).
     // With separate phases a k-step was a chain of exposed latencies: raw reads -> transform -> stores | fills | operand reads ->
     // MFMAs, every wave of the CU in the same phase (barrier): stamps showed a wave in its MFMA phase for 36 % of a k-step and
     // removing a third of the vector instructions changed nothing.  Here the vector work rides between the MFMA groups: a piece
     // of ~10-16 instructions works on values that were read a group earlier, clustered (the first vector instruction in an MFMA gap
     // costs 12.6 cycles, each further one 4: profiles/r05_mfma_f32_issue_ubench.txt), and its LDS latencies lie behind MFMAs.
-    auto step_pipe = [&](const int it, auto cur_c) __attribute__((always_inline)) {
+    auto step = [&](const int it, auto cur_c) __attribute__((always_inline)) {
       constexpr int cur = decltype(cur_c)::value, nxt = cur ^ 1;
       const bool tr = it + 1 < nst, ld = it + 2 < nst;
       const float* const Sb = smem + cur * BUF;
       const f32x2d p1m1 = {1.f, -1.f}, p2m2 = {2.f, -2.f}, c4 = {4.f, 4.f};
+      // One operand group = four frequencies of (channel l16, tile j) per ds_read_b128: 3 reads feed 8 MFMAs.  The groups are NOT
+      // double-buffered in the source: 12 operand registers instead of 24 keep the kernel inside 256 registers without scratch, and
+      // the SIMD's other wave multiplies while this one waits for its reads.
       f32x4 a0, a1, b;
       auto rd_ops = [&](const int g) __attribute__((always_inline)) {
         a0 = *reinterpret_cast<const f32x4*>(Sb + a_rd + 4 * g);
@@ -555,43 +503,17 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
         *reinterpret_cast<f32x2d*>(op + 2) = __builtin_elementwise_fma(sg, x34, v34);
         *reinterpret_cast<f32x2d*>(op + 4) = __builtin_elementwise_fma(sg, x05, v05);
       };
-#define WG2D_SB __builtin_amdgcn_sched_barrier(0)
-#ifndef WG2D_VPRIO     // diagnostic: wave priority during the vector pieces
-#define WG2D_VPRIO 0
-#endif
-#ifndef WG2D_SPLITMM   // diagnostic: a piece between the two halves of an MFMA group instead of behind it
-#define WG2D_SPLITMM 0
-#endif
-      auto mm_half = [&](const int g, const int h) __attribute__((always_inline)) {
-#pragma unroll
-        for (int e = 2 * h; e < 2 * h + 2; ++e) {
-          acc[0][4 * g + e] = mfma16(a0[e], b[e], acc[0][4 * g + e]);
-          acc[1][4 * g + e] = mfma16(a1[e], b[e], acc[1][4 * g + e]);
-        }
-      };
       // one MFMA group, the next group's operand reads behind it, and a vector piece
       auto group = [&](const int g, auto piece) __attribute__((always_inline)) {
-        if constexpr (WG2D_SPLITMM) {
-          mm_half(g, 0); WG2D_SB;
-          if constexpr (WG2D_VPRIO) __builtin_amdgcn_s_setprio(WG2D_VPRIO);
-          piece();
-          if constexpr (WG2D_VPRIO) __builtin_amdgcn_s_setprio(0);
-          WG2D_SB;
-          mm_half(g, 1); WG2D_SB;
-          if (g + 1 < 6) rd_ops(g + 1);
-          WG2D_SB;
-        } else {
-          mm(g); WG2D_SB;
-          if (g + 1 < 6) rd_ops(g + 1);
-          if constexpr (WG2D_VPRIO) __builtin_amdgcn_s_setprio(WG2D_VPRIO);
-          piece();
-          if constexpr (WG2D_VPRIO) __builtin_amdgcn_s_setprio(0);
-          WG2D_SB;
-        }
+        mm(g);
+        __builtin_amdgcn_sched_barrier(0);
+        if (g + 1 < 6) rd_ops(g + 1);
+        piece();
+        __builtin_amdgcn_sched_barrier(0);
       };
       rd_ops(0);
       if (tr) rd_y();
-      WG2D_SB;
+      __builtin_amdgcn_sched_barrier(0);
       group(0, [&]() __attribute__((always_inline)) { if (ld) load(cur_c); });   // fills of k-step it + 2 (this one's parity); waits for rd_y
       group(1, [&]() __attribute__((always_inline)) { if (tr) { u_rows(); if constexpr (UROW) u_cols(); } });
       group(2, [&]() __attribute__((always_inline)) { if (tr) { rd_v(0); if constexpr (!UROW) u_cols(); } });
@@ -602,17 +524,12 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
           if (tr) { v_rows(1); v_cols(1); }
         }
       });
-#undef WG2D_SB
+      // the fills of k-step it + 2 have had the MFMA groups to land; published to the other waves (window pieces) by the barrier
       gsd_dma_barrier();
     };
     for (int it = 0; it < nst; it += 2) {
-      if constexpr (WG2D_PIPE != 0 && WG2D_ABL == 0) {
-        step_pipe(it, I0{});
-        if (it + 1 < nst) step_pipe(it + 1, I1{});
-      } else {
-        step(it, I0{});
-        if (it + 1 < nst) step(it + 1, I1{});
-      }
+      step(it, I0{});
+      if (it + 1 < nst) step(it + 1, I1{});
     }
   }
 

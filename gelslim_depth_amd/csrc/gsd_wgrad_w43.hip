@@ -33,23 +33,6 @@ __device__ __attribute__((aligned(16))) const float gsd_nan16_wg43[4] = {__built
 
 typedef float f32x2w __attribute__((ext_vector_type(2)));
 
-// Diagnostic build only (-DGSD_WG43_STAMPS; never in the product library): s_memtime stamps around the segments of a stage.
-#ifdef GSD_WG43_STAMPS
-static unsigned long long* g_wg43_stamp_buf = nullptr;
-extern "C" void gsd_wg43_set_stamp_buffer(void* p) { g_wg43_stamp_buf = (unsigned long long*)p; }
-#define WG43_STAMP(i)                                                                            \
-  {                                                                                              \
-    unsigned long long t_;                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                   \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    st_acc[i] += t_ - st_prev;                                                                   \
-    st_prev = t_;                                                                                \
-  }
-#else
-#define WG43_STAMP(i) {}
-#endif
-
 struct WgW43Params {
   SrcD a0, a1;  // activation (B operand), up to two concatenated segments
   SrcD dy;      // gradient w.r.t. the raw conv output (plain)
@@ -58,7 +41,6 @@ struct WgW43Params {
   int N, H, W;
   int TH, TW, TWq, tiles_y, tiles_x, WR, WC, WCp, XS;
   int stages_total, splits, mblocks, nblocks;
-  unsigned long long* stamps;   // diagnostic builds only
 };
 
 namespace {
@@ -72,7 +54,7 @@ constexpr int WG_DS_X4 = 64;   // AX4: rows are contiguous 256-byte runs (one DM
 //
 // AX4: dy comes from a PITCHED buffer (rows 16-byte aligned: gsd_bn_bwd_apply's out-of-place form) and moves as aligned
 // 16-byte pieces -- a piece is one Winograd tile (4 pixels), an instruction fills four 64-pixel rows: 32 instead of 128
-// DMA instructions per stage for dy, i.e. 12 instead of 24 per wave (stamps, profiles/stamp_wgrad.py: the waves spend ~40 %
+// DMA instructions per stage for dy, i.e. 12 instead of 24 per wave (in-kernel stamps, docs/LOG_r01-r04.md: the waves spend ~40 %
 // of their time issuing the fills, ~250 cycles per instruction).  The LDS rows are then contiguous (no padding between
 // them), so the 16 rows of a ds_read_b128 would collide on 4 banks: tile t of row r is stored at slot t ^ (r & 15)
 // (swizzle on the SOURCE address of the DMA and on the read; cdna_hip_programming.md rule 21).
@@ -98,14 +80,12 @@ constexpr int WG_DS_X4 = 64;   // AX4: rows are contiguous 256-byte runs (one DM
 // order, bit-identical.
 // RR == 2: the same for the 8 x 8 stage (TWq == 2: k-step ks holds tile rows 2ks and 2ks+1, lane groups j < 2 / j >= 2; a lane's
 // window rows are 2ks + (j>>1) + {0,1,2}, the last of which is the first of its next k-step): 9 instead of 12 row transforms.
-#ifndef WG43_LATE_KS   // the k-step after which the late half of an 8-wave block issues its fills
-#define WG43_LATE_KS 0
-#endif
 template <int NWM, int NWN, bool AX4, bool PLAIN, bool BX4, int RR>
 __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3x3_w43_kernel(const WgW43Params P) {
   static_assert(!BX4 || AX4, "16-byte window pieces come with 16-byte dy pieces");
   static_assert(RR == 0 || BX4, "row reuse is instantiated for the 16-byte-piece form only");
   constexpr int BM = 32 * NWM, BN = 16 * NWN, NW = NWM * NWN, DS = AX4 ? WG_DS_X4 : WG_DS, MT = 2;
+  constexpr int LATE_KS = 0;   // the k-step after which the late half of an 8-wave block issues its fills
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int XS = P.XS;
   // BX4: the window image is whole 64-piece instructions long (the last one's surplus lanes write dummies behind the planes)
@@ -113,10 +93,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef GSD_WG43_STAMPS
-  unsigned long long st_acc[4] = {0, 0, 0, 0}, st_prev;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev)::"memory");
-#endif
   const int wm = wave / NWN, wn = wave % NWN;
   const int j = lane >> 4, l16 = lane & 15;
 
@@ -235,11 +211,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
     }
     float* Ab = smem + buf * BUF;
     float* Bb = Ab + BM * DS;
-#ifdef WG43_ABL
-    const bool skipA = ((WG43_ABL) & 1) && stage > s_begin + 1, skipB = ((WG43_ABL) & 2) && stage > s_begin + 1;
-#else
-    const bool skipA = false, skipB = false;
-#endif
     // ---- A: dy rows ----
     if constexpr (AX4) {
       const bool inside = h0 + P.TH <= P.H && w0 + P.TW <= P.dy.ws && m0 + BM <= P.M;
@@ -247,7 +218,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
       const float* rbase = P.dy.p + (long long)n * P.dy.ns + (long long)(m0 + 4 * wave + a_lr) * P.dy.cs +
                            ((long long)(h0 + a_r) * P.dy.ws + (w0 + a_c));
       const long long rstep = (long long)(4 * NW) * P.dy.cs;
-      const int ninstr = skipA ? 0 : BM / 4 / NW;
+      constexpr int ninstr = BM / 4 / NW;
       if (inside) {
 #pragma unroll 4
         for (int i = 0; i < ninstr; ++i) {
@@ -268,7 +239,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
       const int aoff = (h0 + a_r) * P.dy.ws + (w0 + a_c);
       const float* rbase = P.dy.p + (long long)n * P.dy.ns + (long long)(m0 + wave) * P.dy.cs;
       const long long rstep = (long long)NW * P.dy.cs;
-      const int nrows = skipA ? 0 : BM / NW;
+      constexpr int nrows = BM / NW;
       if (inside && m0 + BM <= P.M) {
 #pragma unroll 4
         for (int i = 0; i < nrows; ++i) {
@@ -296,7 +267,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
           if (wave + NW * k < NI) {
             const float* gp = cb + x_off[k];
             float* dstp = Bb + (wave + NW * k) * 256;
-            if (!skipB) __builtin_amdgcn_global_load_lds(gp, dstp, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(gp, dstp, 16, 0, 0);
           }
       } else {
 #pragma unroll 1   // (edge stages: one piece at a time keeps the address temporaries of four out of the register budget)
@@ -307,7 +278,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
             const bool ok = m >= 0 && ch < S_chan && (unsigned)r < (unsigned)S_H && c0 + 3 >= 0 && c0 < S_W;
             const float* gp = ok ? cb + x_off[k] : S_sent16;
             float* dstp = Bb + (wave + NW * k) * 256;
-            if (!skipB) __builtin_amdgcn_global_load_lds(gp, dstp, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(gp, dstp, 16, 0, 0);
           }
         // the outside part of a straddling piece: window columns [4 (cl / 4), cl) on the left, [cr, 4 ceil(cr / 4)) on the right
         const int cl = ws < 0 ? -ws : 0, cr = S_W - ws;
@@ -317,7 +288,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
       if (buf) fix1 = fx; else fix0 = fx;
       return;
     }
-    if (b_one && !skipB) {
+    if (b_one) {
       // one segment for the whole block: a scalar plane pointer that advances by NW channels + the lanes' fixed window offsets;
       // interior stages need nothing else, border stages one validity bit per window position
       const int hs = h0 - 1 - S_oh, ws = w0 - 1 - S_ow;
@@ -377,7 +348,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
       for (int p = 0; p < 4; ++p)
         if ((unsigned)(hsB + b_rr[p]) < (unsigned)P.a1.H && (unsigned)(wsB + b_cc[p]) < (unsigned)P.a1.W) vmB |= 1 << p;
     }
-    const int nch = skipB ? 0 : BN / NW;
+    constexpr int nch = BN / NW;
 #pragma unroll 2
     for (int i = 0; i < nch; ++i) {
       const int ch = wave + NW * i;
@@ -490,24 +461,10 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
           for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int f = 0; f < 6; ++f) acc[m][r * 6 + f] = mfma16(U[m][f], V[(ks + r) % 3][f], acc[m][r * 6 + f]);
-#ifdef WG43_LATE_HALF   // diagnostic: the late half issues after the first 18 MFMAs of the stage
-          if (ks == 0 && m == 0 && late && more) issue_dma(next_stage, cur ^ 1);
-#endif
         }
-#if defined(WG43_ABL) && ((WG43_ABL) & 8)   // diagnostic: no row transform after the first three
-        if (ks + 1 < 4) { V[ks % 3][0] = xa[0]; V[ks % 3][1] = xa[1]; V[ks % 3][2] = xa[2]; V[ks % 3][3] = xa[3]; V[ks % 3][4] = xb[0]; V[ks % 3][5] = xb[1]; }
-#else
         if (ks + 1 < 4) row_transform(xa, xb, V[ks % 3]);   // window row ks + 3 takes the place of row ks
-#endif
-#ifndef WG43_LATE_HALF
-        if (ks == WG43_LATE_KS && late && more) {
-          WG43_STAMP(2)
-          issue_dma(next_stage, cur ^ 1);
-          WG43_STAMP(1)
-        }
-#endif
+        if (ks == LATE_KS && late && more) issue_dma(next_stage, cur ^ 1);
       }
-      WG43_STAMP(2)
       return;
     }
     if constexpr (RR == 2) {
@@ -559,13 +516,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
           row_transform(xa[0], xb[0], V[(2 * ks + 3) % 3]);
           row_transform(xa[1], xb[1], V[(2 * ks + 4) % 3]);
         }
-        if (ks == WG43_LATE_KS && late && more) {
-          WG43_STAMP(2)
-          issue_dma(next_stage, cur ^ 1);
-          WG43_STAMP(1)
-        }
+        if (ks == LATE_KS && late && more) issue_dma(next_stage, cur ^ 1);
       }
-      WG43_STAMP(2)
       return;
     }
     f32x4 ya[2][MT];
@@ -625,18 +577,12 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
         for (int r = 0; r < 3; ++r)
 #pragma unroll
           for (int f = 0; f < 6; ++f) acc[m][r * 6 + f] = mfma16(U[m][f], V[r][f], acc[m][r * 6 + f]);
-      if (ks == WG43_LATE_KS && late && more) {
-        WG43_STAMP(2)
-        issue_dma(next_stage, cur ^ 1);
-        WG43_STAMP(1)
-      }
+      if (ks == LATE_KS && late && more) issue_dma(next_stage, cur ^ 1);
     }
-    WG43_STAMP(2)   // reads + transforms + 144 MFMAs
   };
 
   const int nst = s_end - s_begin;
   if (nst > 0) issue_dma(s_begin, 0);
-  WG43_STAMP(3)   // prologue
   // the stage loop, unrolled by two: which of the two LDS images a stage reads is a constant of each copy, so the image offsets
   // fold into the instructions' immediate fields (as in gsd_conv3x3_w2d.hip)
   auto run_stage = [&](const int it, auto cur_c) {
@@ -660,24 +606,15 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
           }
         }
       }
-#if defined(WG43_ABL) && ((WG43_ABL) & 4)   // diagnostic: no barrier per stage (results are then garbage)
-#else
       __syncthreads();   // everyone's fills (and patches) are in; everyone has left the other image
-#endif
     } else {
       gsd_dma_barrier();   // this stage's DMA has landed; everyone has left the other image
     }
-    WG43_STAMP(0)
     // The barrier puts the two waves of a SIMD in phase, and a wave that issues its ~24 gathers (plus their address
     // work) keeps the matrix pipe idle: the SIMD's second wave (waves 4..7 of an 8-wave block) therefore multiplies its
     // first k-step BEFORE it issues its share of the next stage's DMA.
-#ifdef WG43_NO_LATE   // diagnostic: every wave issues its fills in front of the stage
-    const bool late = false;
-#else
     const bool late = NW == 8 && wave >= 4;
-#endif
     if (!late && it + 1 < nst) issue_dma(s_begin + it + 1, cur ^ 1);
-    WG43_STAMP(1)   // this wave's share of the next stage's DMA
     compute(cur, late, s_begin + it + 1, it + 1 < nst);
   };
   for (int it = 0; it < nst; it += 2) {
@@ -706,13 +643,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
         }
       }
     }
-#ifdef GSD_WG43_STAMPS
-  WG43_STAMP(3)   // epilogue (slab stores)
-  if (P.stamps != nullptr && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) P.stamps[((size_t)blockIdx.x * NW + wave) * 4 + i] = st_acc[i];
-  }
-#endif
 }
 
 // slab[split][r*3+s][co][ci] -> dW[co][ci][r][s] = sum over splits, in a fixed order (the blocks applied G^T themselves).
@@ -853,10 +783,6 @@ int gsd_wgrad_w43_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, in
   P.a1 = nsrc > 1 ? to_srcd(a[1]) : null_srcd();
   P.dy = to_srcd(*dy);
   P.slabs = workspace;
-  P.stamps = nullptr;
-#ifdef GSD_WG43_STAMPS
-  P.stamps = g_wg43_stamp_buf;
-#endif
   P.M = Cout; P.Ncols = Cin;
   P.N = N; P.H = H; P.W = W;
   P.TH = pl.TH; P.TW = pl.TW; P.TWq = pl.TWq; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;

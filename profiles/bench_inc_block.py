@@ -1,8 +1,6 @@
 #!/usr/bin/env python3
 """The bf16 `inc` double-conv forward (3 -> 64 -> 64 @320x427, batch N) kernel by kernel, fused (gsd_bf16_inc.hip) and unfused, each
-launch timed with HIP events on its own; with a -DINC_STAMP=1 diagnostic build (profiles/build_diag_one.sh gsd_bf16_inc.hip
-"-DINC_STAMP=1" incstamp; GSD_LIB_PATH=profiles/ubench/libgsd_incstamp.so GSD_DIAG_STAMPS=1) also where a wave of the fused kernel
-spends its cycles."""
+launch timed with HIP events on its own."""
 import ctypes as C
 import os
 import sys
@@ -62,16 +60,3 @@ for name, fn in ops.items():
     b.record()
     torch.cuda.synchronize()
     print(f"{name:40s} {a.elapsed_time(b) / 5:.4f} ms", flush=True)
-    if name.startswith("inc_conv") and os.environ.get("GSD_DIAG_STAMPS"):
-        import numpy as np
-        buf = (C.c_ulonglong * (8 * 256))()
-        lib.gsd_diag_inc_stamps(buf, 256)
-        raw = np.frombuffer(buf, dtype=np.uint64).reshape(-1, 8)
-        w2, w3 = (raw[:, 7] & np.uint64(0xffffffff)).astype(np.float64), (raw[:, 7] >> np.uint64(32)).astype(np.float64)
-        t = raw.astype(np.float64)
-        keep = t[:, 4] > 0
-        t, w2, w3 = t[keep], w2[keep], w3[keep]
-        it = t[:, 4]
-        print(f"   per item (median over {len(t)} blocks, {np.median(it):.0f} items per block): rebuild {np.median(t[:, 0] / it):.0f}  K loop "
-              f"{np.median(t[:, 1] / it):.0f}  put_x + epilogue {np.median(t[:, 2] / it):.0f}  barrier waits after them {np.median(t[:, 3] / it):.0f} / {np.median(w2 / it):.0f} / {np.median(w3 / it):.0f} cycles; "
-              f"block life {np.median(t[:, 5]) / 1e3:.0f} kcycles at {np.median(t[:, 5] / t[:, 6]) * 0.1:.2f} GHz")
