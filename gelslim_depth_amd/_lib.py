@@ -142,6 +142,8 @@ SIGNATURES = {
     "gsd_bn_bwd_reduce_finalize": (_I, [_P, _I, _I, _I, _P, _D, _P, _P, _P, _P, _P, _P]),
     "gsd_area_resize_affine": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _F, _F, _P]),
     "gsd_ingest_images": (_I, [_P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _I, _F, _F, _P]),
+    "gsd_resize_affine": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _F, _F, _P]),
+    "gsd_ingest_images_interp": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _I, _F, _F, _P]),
     "gsd_gaussian_blur": (_I, [_P, _L, _I, _I, _P, _I, _P, _P]),
     "gsd_channel_stats_workspace": (_L, [_I]),
     "gsd_channel_stats": (_I, [_P, _L, _I, _L, _P, _P, _P]),

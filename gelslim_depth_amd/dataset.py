@@ -4,7 +4,7 @@ tensors kept in HBM and every per-pixel operation a libgsd kernel.
 Mirrors (paths under /root/reference/):
   GeneralDataset.__init__ keywords / attributes   gelslim_depth/datasets/general_dataset.py:12-58
   load_object_dataset / load_extra_object_dataset general_dataset.py:60-97, 99-134   (finger split, difference image,
-                                                  area resize, per-object subsample through torch.randperm)
+                                                  resize with interp_method, per-object subsample through torch.randperm)
   load_entire_dataset                             general_dataset.py:136-192  (sequential order: main list, then extra)
   calculate_*_normalization_params                general_dataset.py:199-220
   normalize_sample / __getitem__                  general_dataset.py:222-245
@@ -25,7 +25,7 @@ import torch
 
 from . import _lib as L
 from ._lib import lib, check
-from .processing import tactile_affine
+from .processing import INTERP_MODES, interp_mode, tactile_affine
 
 
 def depth_norm_affine(method: str, norm_scale: float, params=None) -> Tuple[float, float]:
@@ -53,8 +53,10 @@ def _need_cuda(device) -> torch.device:
 
 
 def ingest_images(raw: torch.Tensor, base: Optional[torch.Tensor], c0: int, c1: int, size: Tuple[int, int],
-                  out: torch.Tensor) -> None:
-    """out (K, c1-c0, OH, OW) <- area_resize(diff(raw[:, c0:c1], base[:, c0:c1])) -- one kernel, channel view by stride."""
+                  out: torch.Tensor, interp_method: str = "area") -> None:
+    """out (K, c1-c0, OH, OW) <- F.interpolate(diff(raw[:, c0:c1], base[:, c0:c1]), size, mode=interp_method) -- one
+    kernel, channel view by stride ('area': gsd_ingest_images, every other mode: gsd_ingest_images_interp)."""
+    code = interp_mode(interp_method)
     if raw.dtype not in (torch.float32, torch.uint8):
         raw = raw.float()
     if base is not None and base.dtype != raw.dtype:
@@ -69,10 +71,14 @@ def ingest_images(raw: torch.Tensor, base: Optional[torch.Tensor], c0: int, c1: 
         raise L.GsdError("ingest_images: bad output tensor")
     for s in range(0, k, 32768):        # grid.z limit
         e = min(k, s + 32768)
-        check(lib.gsd_ingest_images(raw.data_ptr() + (s * c + c0) * h * w * raw.element_size(),
-                                    None if bptr is None else bptr + s * c * h * w * base.element_size(),
-                                    0 if raw.dtype == torch.float32 else 1, e - s, c1 - c0, h, w, c * h * w, h * w, bns, bcs,
-                                    out[s:e].data_ptr(), size[0], size[1], 255.0, 0.5, L.stream_ptr()), "ingest_images")
+        args = (raw.data_ptr() + (s * c + c0) * h * w * raw.element_size(),
+                None if bptr is None else bptr + s * c * h * w * base.element_size(),
+                0 if raw.dtype == torch.float32 else 1, e - s, c1 - c0, h, w, c * h * w, h * w, bns, bcs,
+                out[s:e].data_ptr(), size[0], size[1], 255.0, 0.5, L.stream_ptr())
+        if code == INTERP_MODES["area"]:
+            check(lib.gsd_ingest_images(*args), "ingest_images")
+        else:
+            check(lib.gsd_ingest_images_interp(code, *args), "ingest_images")
 
 
 def gaussian_kernel2d(kernel_size: int, sigma: Optional[float] = None) -> torch.Tensor:
@@ -138,8 +144,9 @@ class DeviceDataset:
                  extra_objects=None) -> None:
         if objects is None:
             assert directory is not None and os.path.exists(directory), f"Dataset path {directory} does not exist"
-        if interp_method not in (None, "area"):
-            raise NotImplementedError("only interp_method='area' (what the reference's configs use) is implemented")
+        if interp_method is None:
+            interp_method = "area"
+        interp_mode(interp_method)          # an unknown mode raises here, naming the accepted ones
         if depth_image_blur_kernel > 1:
             gaussian_kernel2d(depth_image_blur_kernel)      # an even size raises here, as torchvision does
         self.use_difference_image = use_difference_image
@@ -152,7 +159,7 @@ class DeviceDataset:
         self.max_datapoints_per_object = max_datapoints_per_object
         self.separate_fingers = separate_fingers
         self.device = _need_cuda(device)
-        self.interp_method = interp_method or "area"
+        self.interp_method = interp_method
         self.input_tactile_image_size = None
         self._objects, self._extra_objects = objects, extra_objects
         self.entire_dataset = self.load_entire_dataset()
@@ -201,14 +208,14 @@ class DeviceDataset:
             t_out = torch.empty((2 * k, tc, *size), device=dev, dtype=torch.float32)
             d_out = torch.empty((2 * k, dc, *size), device=dev, dtype=torch.float32)
             for f in range(2):      # torch.cat((x[:, 0:3], x[:, 3:6]), dim=0): all left fingers, then all right fingers
-                ingest_images(tac_d, base_d, f * tc, (f + 1) * tc, size, t_out[f * k:(f + 1) * k])
-                ingest_images(dep_d, None, f * dc, (f + 1) * dc, size, d_out[f * k:(f + 1) * k])
+                ingest_images(tac_d, base_d, f * tc, (f + 1) * tc, size, t_out[f * k:(f + 1) * k], self.interp_method)
+                ingest_images(dep_d, None, f * dc, (f + 1) * dc, size, d_out[f * k:(f + 1) * k], self.interp_method)
         else:
             t_out = torch.empty((k, tac.shape[1], *size), device=dev, dtype=torch.float32)
             d_out = torch.empty((k, dep.shape[1], *size), device=dev, dtype=torch.float32)
-            ingest_images(tac_d, base_d, 0, tac.shape[1], size, t_out)
-            ingest_images(dep_d, None, 0, dep.shape[1], size, d_out)
-        if self.depth_image_blur_kernel > 1:        # general_dataset.py:74-76,84-86: blur AFTER the area resize
+            ingest_images(tac_d, base_d, 0, tac.shape[1], size, t_out, self.interp_method)
+            ingest_images(dep_d, None, 0, dep.shape[1], size, d_out, self.interp_method)
+        if self.depth_image_blur_kernel > 1:        # general_dataset.py:74-76,84-86: blur AFTER the resize
             d_out = gaussian_blur(d_out, self.depth_image_blur_kernel)
         obj = torch.full((rows,), object_index, dtype=torch.int64, device=dev)
         if keep is not None:

@@ -395,6 +395,23 @@ int gsd_adam_ema(float* p, const float* g, float* m, float* v, float* ema, int64
 int gsd_area_resize_affine(const float* in, const float* base, int N, int C, int H, int W, float* out, int OH, int OW,
                            const float* A, const float* B, int nab, float pre_add, float pre_mul, void* stream);
 
+/* F.interpolate(size=(OH, OW), mode=interp_method, align_corners=None, antialias=False) for every 4-D mode the reference's
+ * one resampling knob `interp_method` can reach (train_unet.py:18, image_utils.py:12-15).  Indices and weights are those of
+ * ATen's CPU kernels in fp32 (gsd_resize.hip states them); nearest modes copy a pixel, bilinear / bicubic are separable.
+ * GSD_INTERP_AREA forwards to gsd_area_resize_affine / gsd_ingest_images unchanged. */
+typedef enum {
+  GSD_INTERP_AREA = 0,
+  GSD_INTERP_NEAREST = 1,
+  GSD_INTERP_NEAREST_EXACT = 2,
+  GSD_INTERP_BILINEAR = 3,
+  GSD_INTERP_BICUBIC = 4
+} gsd_interp;
+/* gsd_area_resize_affine with any gsd_interp mode:
+ *   out[n,c,oh,ow] = A[min(c,nab-1)] * resize(pre(in))[n,c,oh,ow] + B[min(c,nab-1)].
+ * A mode outside gsd_interp, a null pointer or a non-positive size returns GSD_ERR_BAD_ARG; N, C <= 65535 per call. */
+int gsd_resize_affine(int mode, const float* in, const float* base, int N, int C, int H, int W, float* out, int OH, int OW,
+                      const float* A, const float* B, int nab, float pre_add, float pre_mul, void* stream);
+
 /* ---- device-resident dataset path (gelslim_depth/datasets/general_dataset.py) ----------------- */
 /* Ingest of one object file's images into the dataset arena: finger split (the caller passes the channel view
  * through strides; general_dataset.py:69-72), difference image (image_utils.py:6-10, when base != NULL:
@@ -403,6 +420,10 @@ int gsd_area_resize_affine(const float* in, const float* base, int N, int C, int
 int gsd_ingest_images(const void* in, const void* base, int dtype, int N, int C, int H, int W, int64_t in_n_stride,
                       int64_t in_c_stride, int64_t base_n_stride, int64_t base_c_stride, float* out, int OH, int OW,
                       float pre_add, float pre_mul, void* stream);
+/* gsd_ingest_images with any gsd_interp mode (same arguments after `mode`; general_dataset.py:71-121 with interp_method). */
+int gsd_ingest_images_interp(int mode, const void* in, const void* base, int dtype, int N, int C, int H, int W,
+                             int64_t in_n_stride, int64_t in_c_stride, int64_t base_n_stride, int64_t base_c_stride, float* out,
+                             int OH, int OW, float pre_add, float pre_mul, void* stream);
 /* torchvision.transforms.functional.gaussian_blur of `planes` contiguous HxW planes (blur_depth_images, image_utils.py:17-19;
  * general_dataset.py:74-76,84-86 when depth_image_blur_kernel > 1): reflect padding of K/2, then the depthwise correlation
  * with the K x K kernel (device pointer, row-major; the caller builds it as torchvision does -- gelslim_depth_amd/dataset.py).
