@@ -35,6 +35,10 @@ TAU_DW = 4.0e-6        # conv3x3 dW (split-K reductions over N*H*W pixels): 1.03
 TAU_CONVT = 1.9e-6     # ConvTranspose2d 2x2/s2 forward, dX, dW, db: 4.80e-7 (up2.up, N = 32)
 TAU_1X1 = 8.0e-7       # output 1x1 conv forward / dX / dW / db, MSE loss and gradient: 2.16e-7 (outc forward, N = 32)
 TAU_STATS = 3.4e-8     # per-channel sums of a launch's statistics epilogue (vs sum of ref, over sum of cond): 8.51e-9 (inc.c1, N = 8)
+# fp32 pointwise kernels and the optimiser (tests/test_gpu_fp32_pointwise_fp64.py, tests/test_gpu_fp32_step_fp64.py), same rule
+TAU_PW = 7.8e-7        # gsd_bn_bwd_apply (in place / pitched), gsd_bn_eval_coeffs[_bwd]: 1.95e-7 (apply, level 2, 16-byte form, N = 32)
+TAU_ADAM = 2.3e-7      # gsd_adam_ema, cond of adam_ema_ref (p, m, v, ema): 5.93e-8 (arena of 31 M, step 1, wd 0.1, grad_scale 1/2)
+U32 = 2.0 ** -24       # unit roundoff of round-to-nearest fp32: one fp32 rounding of an fp64 value x costs at most U32 |x|
 
 # bf16 engine (tests/test_gpu_bf16_fp64_bounds.py, check_bound_bf16): |got - ref| <= 2^-8 |ref| + TAU * cond.  2^-8 is the unit
 # roundoff of the RNE rounding of a stored bf16 result; TAU holds the fp32 accumulation in front of it.  Same rule: each at no
@@ -65,6 +69,33 @@ def deferred_act(raw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) ->
     c = (1, -1, 1, 1)
     y = raw.double() * scale.double().view(c) + shift.double().view(c)
     return y.float().double().clamp_min_(0.0)
+
+
+def fmaf32(x: torch.Tensor, s: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """fp32 fmaf(x, s, b) exactly, for fp32-valued operands, as an fp64 tensor.  The product of two fp32 values is exact in fp64;
+    TwoSum gives the fp64 sum t and its error e (x*s + b == t + e exactly).  Rounding t to fp32 is then right except when t lies
+    exactly on an fp32 midpoint and e != 0: the tie belongs to the side e points to (a double rounding deferred_act accepts)."""
+    x, s, b = x.double(), s.double(), b.double()
+    p = x * s
+    t = p + b
+    bb = t - p
+    e = (p - (t - bb)) + (b - bb)
+    r = t.float()
+    rd = r.double()
+    up = torch.nextafter(r, torch.full_like(r, math.inf))
+    dn = torch.nextafter(r, torch.full_like(r, -math.inf))
+    other = torch.where(t > rd, up, dn)
+    mid = (2.0 * t == rd + other.double()) & (t != rd)
+    fix = mid & (((t > rd) & (e > 0)) | ((t < rd) & (e < 0)))
+    return torch.where(fix, other, r).double()
+
+
+def bnrelu_act(raw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
+    """max(fmaf(raw, scale, shift), 0) bit for bit (fmaf32): the activation gsd_maxpool2 pools and the pool-routed BatchNorm
+    backward takes its arg-max of.  Selections and single roundings are compared with torch.equal, so deferred_act's rare
+    one-ulp double rounding is not good enough there."""
+    c = (1, -1, 1, 1)
+    return fmaf32(raw, scale.view(c), shift.view(c)).clamp_min_(0.0)
 
 
 def bnrelu_mask(raw: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
@@ -105,15 +136,16 @@ def conv3x3_fwd(a: torch.Tensor, wt: torch.Tensor) -> Tuple[torch.Tensor, torch.
     return ref.view(n, co, h, w), cond.view(n, co, h, w)
 
 
-def conv3x3_dx(dy: torch.Tensor, wt: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """dx[n,ci,y,x] = sum_{co,kh,kw} wt[co,ci,kh,kw] dy[n,co,y-kh+1,x-kw+1].  dy: (n,co,h,w)."""
+def conv3x3_dx(dy: torch.Tensor, wt: torch.Tensor, dy_abs: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dx[n,ci,y,x] = sum_{co,kh,kw} wt[co,ci,kh,kw] dy[n,co,y-kh+1,x-kw+1].  dy: (n,co,h,w); dy_abs: the bound on |dy| to use
+    in cond (default |dy|), as conv3x3_dw."""
     n, _, h, w = dy.shape
     ci = wt.shape[1]
     ref = torch.zeros((n, ci, h * w), dtype=torch.float64, device=dy.device)
     cond = torch.zeros_like(ref)
     wtt = wt.transpose(0, 1)
     wta = wtt.abs()
-    for (kh, kw, s), (_, _, sa) in zip(_taps(dy, h, w), _taps(dy.abs(), h, w)):
+    for (kh, kw, s), (_, _, sa) in zip(_taps(dy, h, w), _taps(dy.abs() if dy_abs is None else dy_abs, h, w)):
         # tap (kh, kw) of the padded dy is dy[y + kh - 1]: it meets weight (2 - kh, 2 - kw)
         ref += torch.matmul(wtt[:, :, 2 - kh, 2 - kw], s)
         cond += torch.matmul(wta[:, :, 2 - kh, 2 - kw], sa)
@@ -404,3 +436,92 @@ def stored_sums(y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tens
     y = y.double()
     q = y * y
     return y.sum((0, 2, 3)), q.sum((0, 2, 3)), y.abs().sum((0, 2, 3)), q.sum((0, 2, 3))
+
+
+# ------------------------------------------------------------------------------ fp32 engine: BatchNorm finalize, Adam + EMA
+def check_bound_rounded(got: torch.Tensor, ref: torch.Tensor, cond: torch.Tensor, tau: float, what: str,
+                        key: Optional[str] = None, weights: bool = True, n0: int = 0) -> float:
+    """An fp32 result that a kernel computes in fp64 and rounds once (BatchNorm finalize, running statistics) or in a short fp32
+    chain whose last rounding is of the result itself: |got - ref| <= U32 |ref| + tau * cond.  Report as check_bound."""
+    return check_bound(got, ref, cond, tau, what, n0=n0, key=key, weights=weights, _base=U32 * ref.abs())
+
+
+def bn_finalize_ref(s1: torch.Tensor, s2: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor, count: float, gamma: torch.Tensor,
+                    beta: torch.Tensor, eps: float = 1e-5, momentum: float = 0.1, running_mean: Optional[torch.Tensor] = None,
+                    running_var: Optional[torch.Tensor] = None) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+    """gsd_bn_finalize / gsd_bn_reduce_finalize from per-channel sums: s1 = sum y, s2 = sum y^2 (fp64 references) and the bounds
+    of the kernel's sums, |sum - s1| <= tau b1, |sum of squares - s2| <= tau b2.  Returns name -> (ref, cond) for mean, var
+    (biased), invstd, scale, shift and, given the prior buffers, running_mean / running_var (momentum, unbiased variance, as
+    BatchNorm2d): each output obeys |got - ref| <= U32 |ref| + tau * cond (check_bound_rounded).
+
+    The kernels take the one-pass variance q / count - mean^2 in fp64, so the sums' errors carry into it as
+    (b2 + 2 |mean| b1) / count: relative to var + eps that is (E[y^2] + 2 |mean| E|y|) / (var + eps) times the sums' relative
+    bound -- large for a channel whose |mean| / std is large, and the bound grows with it.  invstd = (var + eps)^-1/2 carries
+    half the relative error of var + eps; scale, shift and the running statistics are carried from mean and invstd.  A negative
+    one-pass variance (rounding, a constant channel) is clamped to 0 before it is used, as the kernels do."""
+    f = lambda v: torch.as_tensor(v, dtype=torch.float32).double().item()   # noqa: E731  (the kernels' float eps / momentum)
+    eps, mom = f(eps), f(momentum)
+    s1, s2, b1, b2 = s1.double(), s2.double(), b1.double(), b2.double()
+    g, bt = gamma.double(), beta.double()
+    mu = s1 / count
+    cmu = b1 / count
+    var = s2 / count - mu * mu
+    cvar = (b2 + 2.0 * mu.abs() * b1) / count
+    istd = 1.0 / torch.sqrt(var.clamp_min(0.0) + eps)
+    cis = 0.5 * istd * cvar / (var.clamp_min(0.0) + eps)
+    out = {"mean": (mu, cmu), "var": (var, cvar), "invstd": (istd, cis), "scale": (g * istd, g.abs() * cis),
+           "shift": (bt - mu * g * istd, g.abs() * (cmu * istd + mu.abs() * cis))}
+    if running_mean is not None:
+        unb = count / (count - 1.0) if count > 1 else 1.0
+        out["running_mean"] = ((1.0 - mom) * running_mean.double() + mom * mu, mom * cmu)
+        out["running_var"] = ((1.0 - mom) * running_var.double() + mom * unb * var.clamp_min(0.0), mom * unb * cvar)
+    return out
+
+
+def f32c(v: float) -> float:
+    """A host constant as the kernel receives it: rounded to fp32, widened back."""
+    return torch.tensor(v, dtype=torch.float32).double().item()
+
+
+def adam_ema_ref(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, ema: Optional[torch.Tensor], step: int,
+                 lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0,
+                 ema_decay: float = 0.0, grad_scale: float = 1.0, kernel_constants: bool = True
+                 ) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+    """One gsd_adam_ema step in fp64 from the fp32 state: torch's single-tensor Adam with coupled L2 (g' = g * grad_scale + wd p,
+    m' = m.lerp(g', 1 - b1), v' = b2 v + (1 - b2) g'^2, p' = p - lr / bc1 * m' / (sqrt(v') / sqrt(bc2) + eps)) and torch_ema's
+    shadow update ema' = ema - (1 - d) (ema - p').  kernel_constants: use the constants exactly as the kernel holds them (every
+    host float rounded to fp32, lr / bc1 and sqrt(bc2) formed in double from the fp32 betas and rounded once, 1 - d in fp32);
+    False: plain fp64 constants (torch.optim.Adam in float64).
+
+    Returns name -> (ref, cond) for p, m, v (and ema): cond sums the magnitudes that the fp32 evaluation's roundings scale with
+    -- every intermediate once, and the errors of m' and of the denominator carried into the step through their relative
+    sizes -- so |got - ref| <= tau * cond with tau a few fp32 unit roundoffs."""
+    k = f32c if kernel_constants else float
+    b1, b2, ep, wd, lr_, gs = k(beta1), k(beta2), k(eps), k(weight_decay), k(lr), k(grad_scale)
+    bc1 = 1.0 - b1 ** step
+    bc2 = 1.0 - b2 ** step
+    lr_bc1, sbc2 = (f32c(lr_ / bc1), f32c(math.sqrt(bc2))) if kernel_constants else (lr_ / bc1, math.sqrt(bc2))
+    omb1, omb2 = 1.0 - b1, 1.0 - b2
+    omd = f32c(1.0 - k(ema_decay)) if kernel_constants else 1.0 - ema_decay
+    p, g, m, v = p.double(), g.double(), m.double(), v.double()
+    gv = g * gs + wd * p
+    cg = (g * gs).abs() + (wd * p).abs()
+    m1 = m + (gv - m) * omb1
+    cm = m.abs() + (gv - m).abs() * omb1 + omb1 * cg + m1.abs()
+    v1 = v * b2 + omb2 * gv * gv
+    cv = b2 * v.abs() + omb2 * (gv * gv + 2.0 * gv.abs() * cg) + v1.abs()
+    sv = torch.sqrt(v1) / sbc2
+    csv = torch.where(v1 > 0, sv * (0.5 * cv / v1.clamp_min(1e-300) + 2.0), cv.sqrt() / sbc2)
+    den = sv + ep
+    cden = csv + den
+    q = m1 / den
+    cq = cm / den + q.abs() * cden / den + q.abs()
+    dp = lr_bc1 * q
+    p1 = p - dp
+    cp = lr_bc1 * cq + dp.abs() + p1.abs()
+    out = {"p": (p1, cp), "m": (m1, cm), "v": (v1, cv)}
+    if ema is not None:
+        e = ema.double()
+        e1 = e - omd * (e - p1)
+        out["ema"] = (e1, omd * (2.0 * (e - p1).abs() + cp) + e1.abs())
+    return out

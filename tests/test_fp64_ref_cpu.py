@@ -3,6 +3,8 @@ cond bounds |ref| (and equals it for non-negative operands), and check_bound at 
 the exact result while rejecting the small, local mistakes the GPU kernel tests exist to catch: one product missing at a corner,
 one 2x4 Winograd tile off by 1e-4, two images swapped, one column's halo read one column too far, one image row missing from
 dW, one element never written."""
+import math
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -280,3 +282,196 @@ def test_maxpool_route_equals_torch_including_ties(h, w):
     av = a.clone().requires_grad_(True)
     F.max_pool2d(av, 2).backward(dp)
     assert torch.equal(R.pool_grad(dp, code, h, w), av.grad)
+
+
+# --------------------------------------------------------------------------- fp32 engine: fmaf, finalize, Adam + EMA
+def _round_f32(x):
+    """An exact rational rounded to fp32, nearest, ties to even (the reference for fmaf32)."""
+    from fractions import Fraction
+    c = torch.tensor(float(x), dtype=torch.float64).float()
+    cands = [c, torch.nextafter(c, torch.tensor(math.inf)), torch.nextafter(c, torch.tensor(-math.inf))]
+    return float(min(cands, key=lambda t: (abs(Fraction(float(t)) - x), int(t.view(torch.int32)) & 1)))
+
+
+def test_fmaf32_is_fmaf_bit_for_bit():
+    """fmaf32 against exact rational arithmetic: random operands, and constructed cases whose fp64 sum lands exactly on an fp32
+    midpoint while the exact sum lies just below it -- there the plain fp64-then-fp32 rounding (deferred_act) is one ulp off."""
+    from fractions import Fraction
+    g = torch.Generator().manual_seed(11)
+    x, s, b = (torch.randn(400, generator=g) * 3 for _ in range(3))
+    got = R.fmaf32(x, s, b)
+    for i in range(400):
+        ex = Fraction(float(x[i])) * Fraction(float(s[i])) + Fraction(float(b[i]))
+        assert float(got[i]) == _round_f32(ex), i
+    # b with an odd last mantissa bit, x * s = ulp(b)/2 * (1 - 2^-46): t = b + ulp/2 (a midpoint) in fp64, the exact sum is
+    # just below it, so fmaf gives b while ties-to-even of t gives the even neighbour b + ulp
+    r = (torch.rand(64, generator=g) + 1.0).float()
+    r = torch.where((r.view(torch.int32) & 1) == 1, r, torch.nextafter(r, torch.full_like(r, 3.0)))
+    r = r * torch.where(torch.arange(64) % 2 == 0, 1.0, -1.0) * 2.0 ** torch.randint(-20, 20, (64,), generator=g).float()
+    ulp = (torch.nextafter(r.abs(), torch.full_like(r, math.inf)) - r.abs()).double()
+    xs = torch.full_like(r, 1.0 + 2.0 ** -23)
+    ss = (torch.sign(r).double() * ulp / 2 * (1 - 2.0 ** -23)).float()
+    got = R.fmaf32(xs, ss, r)
+    plain = (xs.double() * ss.double() + r.double()).float().double()
+    for i in range(64):
+        ex = Fraction(float(xs[i])) * Fraction(float(ss[i])) + Fraction(float(r[i]))
+        assert float(got[i]) == _round_f32(ex) == float(r[i]), i
+    assert bool((plain != got).all()), "the constructed cases are double-rounding cases"
+
+
+def _bn_toy(offset=0.0):
+    g = torch.Generator().manual_seed(5)
+    n, c, h, w = 4, 6, 5, 7
+    x = torch.randn((n, c, h, w), generator=g, dtype=torch.float64) * torch.linspace(0.2, 3.0, c).view(1, c, 1, 1)
+    x = x + offset * torch.linspace(-1, 1, c).view(1, c, 1, 1)
+    gamma, beta = torch.rand(c, generator=g, dtype=torch.float64) + 0.5, torch.randn(c, generator=g, dtype=torch.float64)
+    rm, rv = torch.randn(c, generator=g, dtype=torch.float64) * 0.1, torch.rand(c, generator=g, dtype=torch.float64) + 0.5
+    return x, gamma, beta, rm, rv
+
+
+@pytest.mark.parametrize("offset", [0.0, 30.0])
+def test_bn_finalize_ref_equals_batch_norm(offset):
+    """bn_finalize_ref from exact sums == F.batch_norm(training=True) in fp64 (normalised output through scale / shift, running
+    mean / unbiased running variance), also for channels whose |mean| / std is about 30; its cond of var is the carried sums
+    bound (b2 + 2 |mean| b1) / count."""
+    x, gamma, beta, rm, rv = _bn_toy(offset)
+    cnt = x.numel() / x.shape[1]
+    s = lambda t: t.sum((0, 2, 3))  # noqa: E731
+    r = R.bn_finalize_ref(s(x), s(x * x), s(x.abs()), s(x * x), cnt, gamma, beta, running_mean=rm, running_var=rv)
+    rm_t, rv_t = rm.clone(), rv.clone()
+    y = F.batch_norm(x, rm_t, rv_t, gamma, beta, training=True, momentum=R.f32c(0.1), eps=R.f32c(1e-5))
+    v = (1, -1, 1, 1)
+    assert rel(x * r["scale"][0].view(v) + r["shift"][0].view(v), y) < 1e-10
+    assert rel(r["running_mean"][0], rm_t) < 1e-12 and rel(r["running_var"][0], rv_t) < 1e-10
+    mu = x.mean((0, 2, 3))
+    assert torch.allclose(r["var"][1], (s(x * x) + 2 * mu.abs() * s(x.abs())) / cnt, rtol=1e-14)
+    if offset:
+        assert float((mu.abs() / x.std((0, 2, 3))).max()) > 25
+
+
+def test_bn_finalize_bound_rejects_mutations():
+    """At toy size the carried bound rejects normalising with the unbiased variance, and a running variance updated with the
+    biased one, while it accepts an fp32 rounding of each output."""
+    x, gamma, beta, rm, rv = _bn_toy()
+    cnt = x.numel() / x.shape[1]
+    s = lambda t: t.sum((0, 2, 3))  # noqa: E731
+    r = R.bn_finalize_ref(s(x), s(x * x), s(x.abs()), s(x * x), cnt, gamma, beta, running_mean=rm, running_var=rv)
+    for k in ("mean", "invstd", "scale", "shift", "running_mean", "running_var"):
+        R.check_bound_rounded(r[k][0].float(), r[k][0], r[k][1], R.TAU_STATS, k)
+    var = r["var"][0]
+    unb = 1.0 / torch.sqrt(var * cnt / (cnt - 1) + R.f32c(1e-5))
+    with pytest.raises(AssertionError):
+        R.check_bound_rounded(unb.float(), *r["invstd"], R.TAU_STATS, "invstd from the unbiased variance")
+    biased = (1 - R.f32c(0.1)) * rv + R.f32c(0.1) * var
+    with pytest.raises(AssertionError):
+        R.check_bound_rounded(biased.float(), *r["running_var"], R.TAU_STATS, "running_var from the biased variance")
+
+
+def _adam_f32(p, g, m, v, ema, step, lr, b1, b2, eps, wd, d, gs):
+    """gsd_adam_ema's arithmetic in fp32, operation by operation (fmaf exactly, through fmaf32)."""
+    f = lambda t: t.float().double()  # noqa: E731
+    c = lambda a: torch.full_like(p, R.f32c(a))  # noqa: E731
+    b1, b2 = R.f32c(b1), R.f32c(b2)
+    lr_bc1, sbc2 = R.f32c(R.f32c(lr) / (1 - b1 ** step)), R.f32c(math.sqrt(1 - b2 ** step))
+    gv = R.fmaf32(c(wd), p, f(g * R.f32c(gs)))
+    mv = f(m + f(f(gv - m) * (1 - b1)))
+    vv = R.fmaf32(c(1 - b2), f(gv * gv), f(v * b2))
+    den = f(f(f(torch.sqrt(vv)) / sbc2) + R.f32c(eps))
+    pv = f(p - f(lr_bc1 * f(mv / den)))
+    out = {"p": pv, "m": mv, "v": vv}
+    if ema is not None:
+        omd = R.f32c(1 - R.f32c(d))
+        out["ema"] = f(ema - f(omd * f(ema - pv)))
+    return out
+
+
+def _opt_state(n=4000, seed=3):
+    g = torch.Generator().manual_seed(seed)
+    f = lambda t: t.float().double()  # noqa: E731
+    p = f(torch.randn(n, generator=g, dtype=torch.float64) * 0.05)
+    gr = f(torch.randn(n, generator=g, dtype=torch.float64) * 1e-3 * torch.rand(n, generator=g, dtype=torch.float64))
+    m = f(torch.randn(n, generator=g, dtype=torch.float64) * 1e-4)
+    v = f(torch.rand(n, generator=g, dtype=torch.float64) * 1e-7)
+    ema = f(p + torch.randn(n, generator=g, dtype=torch.float64) * 1e-3)
+    return p, gr, m, v, ema
+
+
+def test_adam_ema_ref_equals_torch_adam_and_ema():
+    """adam_ema_ref with plain fp64 constants over four steps == torch.optim.Adam(weight_decay=0.1) in float64, and its EMA ==
+    torch_ema's update with the warm-up decay min(d, (1 + n) / (10 + n))."""
+    p, gr, _, _, _ = _opt_state()
+    pt = p.clone().requires_grad_(True)
+    opt = torch.optim.Adam([pt], lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.1)
+    m, v, ema, pr = torch.zeros_like(p), torch.zeros_like(p), p.clone(), p.clone()
+    for step in range(1, 5):
+        gs = gr * (1.0 + 0.3 * step)
+        pt.grad = gs.clone()
+        opt.step()
+        d = min(0.995, (1.0 + step) / (10.0 + step))
+        r = R.adam_ema_ref(pr, gs, m, v, ema, step, 1e-3, weight_decay=0.1, ema_decay=d, kernel_constants=False)
+        shadow = ema - (1.0 - d) * (ema - pt.detach())
+        pr, m, v, ema = r["p"][0], r["m"][0], r["v"][0], r["ema"][0]
+        st = opt.state[pt]
+        assert rel(pr, pt.detach()) < 1e-13 and rel(m, st["exp_avg"]) < 1e-13 and rel(v, st["exp_avg_sq"]) < 1e-13
+        assert rel(ema, shadow) < 1e-13
+
+
+@pytest.mark.parametrize("step,wd,gs", [(1, 0.0, 1.0), (2, 1e-6, 1.0), (1000, 0.1, 0.5)])
+def test_adam_ema_bound_accepts_fp32_and_rejects_mutations(step, wd, gs):
+    """The kernel's fp32 arithmetic lands within TAU_ADAM * cond of adam_ema_ref; the bias correction of step - 1 used at step,
+    and the EMA decay of the other warm-up step, are rejected (as is dropping the weight decay where it is 0.1)."""
+    p, gr, m, v, ema = _opt_state(seed=step)
+    d = min(0.995, (1.0 + step) / (10.0 + step))
+    r = R.adam_ema_ref(p, gr, m, v, ema, step, 1e-3, weight_decay=wd, ema_decay=d, grad_scale=gs)
+    got = _adam_f32(p, gr, m, v, ema, step, 1e-3, 0.9, 0.999, 1e-8, wd, d, gs)
+    for k in ("p", "m", "v", "ema"):
+        R.check_bound(got[k], r[k][0], r[k][1], R.TAU_ADAM, f"adam {k}")
+    if step > 1:
+        bad = _adam_f32(p, gr, m, v, ema, 1 if step == 2 else step - 1, 1e-3, 0.9, 0.999, 1e-8, wd, d, gs)
+        with pytest.raises(AssertionError):
+            R.check_bound(bad["p"], *r["p"], R.TAU_ADAM, "bias correction of the previous step")
+    other = min(0.995, (1.0 + step + 1) / (10.0 + step + 1))
+    bad = _adam_f32(p, gr, m, v, ema, step, 1e-3, 0.9, 0.999, 1e-8, wd, other, gs)
+    with pytest.raises(AssertionError):
+        R.check_bound(bad["ema"], *r["ema"], R.TAU_ADAM, "EMA decay of the next step")
+    if wd >= 0.1:
+        bad = _adam_f32(p, gr, m, v, ema, step, 1e-3, 0.9, 0.999, 1e-8, 0.0, d, gs)
+        with pytest.raises(AssertionError):
+            R.check_bound(bad["p"], *r["p"], R.TAU_ADAM, "weight decay dropped")
+
+
+def test_pool_routing_and_c2_mutations_are_rejected():
+    """A pooled gradient routed to the second-largest element of its window, and c2 dropped for one channel of d_raw, fail the
+    bounds the engine step holds dz and d_raw to."""
+    g = torch.Generator().manual_seed(9)
+    n, c, h, w = 2, 3, 6, 7
+    raw = torch.randn((n, c, h, w), generator=g).double()
+    sc, sh = torch.rand(c, generator=g).double() + 0.5, torch.randn(c, generator=g).double() * 0.1
+    a = R.bnrelu_act(raw, sc, sh)
+    best, code = R.maxpool_route(a)
+    dp = torch.randn((n, c, h // 2, w // 2), generator=g).double() * 1e-3
+    da = torch.randn((n, c, h, w), generator=g).double() * 1e-3
+    routed = R.pool_grad(dp, code, h, w)
+    ref, cond = R.bn_bwd_dz(raw, sc, sh, da + routed, da.abs() + routed.abs())
+    R.check_bound(ref.float(), ref, cond, R.TAU_WINO, "dz")
+    # the window of (0, 0, 0, 0) with the largest two positive entries: route to the second one instead
+    win = a[:, :, :2 * (h // 2), :2 * (w // 2)].reshape(n, c, h // 2, 2, w // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(n, c, h // 2, w // 2, 4)
+    srt = win.sort(-1, descending=True)
+    ok = (srt.values[..., 1] > 0).nonzero()
+    assert len(ok) > 0
+    i0, c0, y0, x0 = ok[0].tolist()
+    second = int(srt.indices[i0, c0, y0, x0, 1])
+    code2 = code.clone()
+    code2[i0, c0, y0, x0] = second
+    bad, _ = R.bn_bwd_dz(raw, sc, sh, da + R.pool_grad(dp, code2, h, w))
+    with pytest.raises(AssertionError):
+        R.check_bound(bad.float(), ref, cond, R.TAU_WINO, "routed to the second-largest element")
+    mean, invstd = raw.mean((0, 2, 3)), 1.0 / raw.std((0, 2, 3))
+    c1, c2 = torch.randn(c, generator=g).double() * 1e-4, torch.randn(c, generator=g).double() * 1e-4
+    d, dc = R.bn_bwd_apply(ref, raw, sc, mean, invstd, c1, c2)
+    R.check_bound(d.float(), d, dc, R.TAU_PW, "d_raw")
+    bad = d.clone()
+    k = int(c2.abs().argmax())
+    bad[:, k] += sc[k] * (raw[:, k] - mean[k]) * invstd[k] * c2[k]
+    with pytest.raises(AssertionError):
+        R.check_bound(bad.float(), d, dc, R.TAU_PW, "c2 dropped")
