@@ -13,10 +13,12 @@
 // F(2,3) is the mildest Winograd transform there is (constants 1 and 1/2): the op-level tests bound the combined form at the same
 // 1e-5 relative L1 against the fp64 oracle as the row-only form (north-star tolerance: 1e-3).
 //
-// Block = 4 waves on a 64-channel x 256-pixel tile, as the row-only kernel, but the waves split it 2 (channel halves) x 2 (pixel
-// halves): a wave owns 32 output channels x 16 tiles (128 pixels) = 2 MFMA m-tiles x 24 frequencies = 192 accumulator registers
-// (64 channels x 16 tiles would need 384), two blocks per CU.  Per 4-channel chunk a wave issues 24 k-steps x 2 MFMAs = 48 MFMAs for
-// 128 pixels where the row-only kernel issues 72 for 64.  The weight image of a chunk is 96 x 64 floats = 24 KiB (U = G2 g G4^T,
+// Block = 4 waves on a 64-channel x 256-pixel tile, as the row-only kernel, but the waves split it 2 (frequency-row halves) x 2 (pixel
+// halves): a wave owns all 64 output channels x 16 tiles (128 pixels) x 12 of the 24 frequencies = 4 MFMA m-tiles x 12 = 192
+// accumulator registers (all 24 would need 384), two blocks per CU.  Per 4-channel chunk a wave issues 12 frequencies x 4 MFMAs = 48
+// MFMAs for 128 pixels where the row-only kernel issues 72 for 64, and transforms only the 18 window values and the two frequency
+// rows its MFMAs use (the channel-half split computed all 24 and four rows in both waves of a pixel group, and fed each V value to
+// two MFMAs instead of four).  The two halves of a pixel group trade accumulators once, after the chunk loop.  The weight image of a chunk is 96 x 64 floats = 24 KiB (U = G2 g G4^T,
 // laid out once per optimiser step by gsd_weight_layout modes 8 / 9); the (TH + 2) x (TW + 2) halo window, the LDS-DMA fills, the
 // deferred BatchNorm + ReLU of the sources (NaN-sentinel padding), the two source segments (concat), the two cropped destinations,
 // the BatchNorm partial sums and the fused BatchNorm-backward dX epilogue are those of gsd_conv3x3_w43.hip (its straight-fill
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ph = wave8 % NWP, mh = wave8 / NWP;   // the wave's pixel group (16 of the block's 16 NWP tiles) and 32-channel half
+  const int ph = wave8 % NWP, fh = wave8 / NWP;   // the wave's pixel group (16 of the block's 16 NWP tiles) and frequency-row half
   const int j = lane >> 4, l16 = lane & 15;
 
   // the m-blocks of one pixel tile read the same halo: every XCD gets a contiguous range of logical ids (pixel tile major)
@@ -298,56 +300,51 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
   }
 
   // ---- halo DMA lane geometry: the block's waves cover the (up to) 128 NW window positions once, dword gathers --------------------
-  int xo0[2], xo1[2];
+  // seg_offsets: this lane's source element offsets in segment seg (W2D_PAD: a padding position, W2D_NONE: no position) -- worked
+  // out again at the segment switch rather than held in registers through the chunk loop
   bool p_on[2];
   int pmask = 0;   // U4: floats of this lane's pieces that lie outside their row (bits 4 pp .. 4 pp + 3: first segment, + 8: second)
+  auto seg_offsets = [&](const int seg, int (&xo)[2], const bool mark) __attribute__((always_inline)) {
+    const SrcD& S = seg ? P.src1 : P.src0;
 #pragma unroll
-  for (int pp = 0; pp < 2; ++pp) {
-    xo0[pp] = xo1[pp] = W2D_NONE;
-    if constexpr (PC) {
-      // unit u = (channel plane u / NI, instruction u % NI) of the chunk: its 64 lanes are 64 consecutive pieces of the plane
-      const int u = wave8 + NW * pp;
-      p_on[pp] = u < 4 * P.NI;
-      const int piece = (u % P.NI) * 64 + lane;
-      const int rr = piece / P.NP, pc = piece - rr * P.NP;
-      if (rr < P.WR) {
-        const int gh = h0 - 1 + rr, gw = w0 - 4 + 4 * pc;
-        if constexpr (X4) {
-          xo0[pp] = ((unsigned)gh < (unsigned)P.src0.H && gw >= 0 && gw + 4 <= P.src0.ws) ? gh * P.src0.ws + gw : W2D_PAD;
-        } else {
-          int hs = gh - P.src0.oh, c0 = gw - P.src0.ow;
-          xo0[pp] = W2D_PAD;
-          if ((unsigned)hs < (unsigned)P.src0.H && c0 + 3 >= 0 && c0 < P.src0.W) {
-            xo0[pp] = hs * P.src0.ws + c0;
+    for (int pp = 0; pp < 2; ++pp) {
+      xo[pp] = W2D_NONE;
+      if constexpr (PC) {
+        // unit u = (channel plane u / NI, instruction u % NI) of the chunk: its 64 lanes are 64 consecutive pieces of the plane
+        const int u = wave8 + NW * pp;
+        p_on[pp] = u < 4 * P.NI;
+        const int piece = (u % P.NI) * 64 + lane;
+        const int rr = piece / P.NP, pc = piece - rr * P.NP;
+        if (rr < P.WR) {
+          const int gh = h0 - 1 + rr, gw = w0 - 4 + 4 * pc;
+          if constexpr (X4) {
+            xo[pp] = ((unsigned)gh < (unsigned)S.H && gw >= 0 && gw + 4 <= S.ws) ? gh * S.ws + gw : W2D_PAD;
+          } else {
+            const int hs = gh - S.oh, c0 = gw - S.ow;
+            xo[pp] = W2D_PAD;
+            if (S.C > 0 && (unsigned)hs < (unsigned)S.H && c0 + 3 >= 0 && c0 < S.W) {
+              xo[pp] = hs * S.ws + c0;
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (c0 + e < 0 || c0 + e >= P.src0.W) pmask |= 1 << (4 * pp + e);
-          }
-          hs = gh - P.src1.oh;
-          c0 = gw - P.src1.ow;
-          xo1[pp] = W2D_PAD;
-          if (P.src1.C > 0 && (unsigned)hs < (unsigned)P.src1.H && c0 + 3 >= 0 && c0 < P.src1.W) {
-            xo1[pp] = hs * P.src1.ws + c0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (c0 + e < 0 || c0 + e >= P.src1.W) pmask |= 1 << (8 + 4 * pp + e);
+              for (int e = 0; e < 4; ++e)
+                if (mark && (c0 + e < 0 || c0 + e >= S.W)) pmask |= 1 << (8 * seg + 4 * pp + e);
+            }
           }
         }
+        continue;
       }
-      continue;
+      p_on[pp] = wave8 + NW * pp < P.NPV;
+      const int pos = (wave8 + NW * pp) * 64 + lane;
+      const int rr = pos / P.WCp, cc = pos - rr * P.WCp;
+      if (rr < P.WR && cc < P.WC) {
+        const int gh = h0 - 1 + rr, gw = w0 - 1 + cc;
+        const int hs = gh - S.oh, ws = gw - S.ow;
+        xo[pp] = ((unsigned)hs < (unsigned)S.H && (unsigned)ws < (unsigned)S.W) ? hs * S.ws + ws : W2D_PAD;
+      }
     }
-    p_on[pp] = wave8 + NW * pp < P.NPV;
-    const int pos = (wave8 + NW * pp) * 64 + lane;
-    const int rr = pos / P.WCp, cc = pos - rr * P.WCp;
-    if (rr < P.WR && cc < P.WC) {
-      const int gh = h0 - 1 + rr, gw = w0 - 1 + cc;
-      int hs = gh - P.src0.oh, ws = gw - P.src0.ow;
-      xo0[pp] = ((unsigned)hs < (unsigned)P.src0.H && (unsigned)ws < (unsigned)P.src0.W) ? hs * P.src0.ws + ws : W2D_PAD;
-      hs = gh - P.src1.oh;
-      ws = gw - P.src1.ow;
-      xo1[pp] = ((unsigned)hs < (unsigned)P.src1.H && (unsigned)ws < (unsigned)P.src1.W) ? hs * P.src1.ws + ws : W2D_PAD;
-    }
-  }
+  };
+  int xo0[2], xo1[2];
+  seg_offsets(0, xo0, true);
+  seg_offsets(1, xo1, true);   // (U4: its pmask bits; the offsets themselves are dropped unless the block starts in the second segment)
   const int f_sw = P.src1.C > 0 ? P.src0.C / 4 : -1;           // first chunk of the second (concat) segment
   const bool start1 = SPLIT && f_sw >= 0 && c_lo >= f_sw;      // this slab's chunks all lie in the second segment
   {
@@ -383,8 +380,10 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
     if (chunk == f_sw) {
       d_base = P.src1.p + (long long)n * P.src1.ns;
       d_cs = P.src1.cs;
+      int xs[2];
+      seg_offsets(1, xs, false);
 #pragma unroll
-      for (int pp = 0; pp < 2; ++pp) f_xl[pp] = xo1[pp];
+      for (int pp = 0; pp < 2; ++pp) f_xl[pp] = xs[pp];
     }
     const float pad1 = P.src1.relu ? __builtin_nanf("") : 0.f;
 #pragma unroll
@@ -456,13 +455,24 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
   }
   const float lo0 = P.src0.relu ? 0.f : -__builtin_inff(), lo1 = P.src1.relu ? 0.f : -__builtin_inff();
 
-  f32x4 acc[2][24];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int f = 0; f < 24; ++f) acc[m][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // ---- the wave's three window rows: its frequency rows (2 fh, 2 fh + 1) of B2^T d are tA = A - B and tB = B + sg C, with
+  //   fh = 0: A, B, C = window rows 0, 2, 1 and sg = +1   (t0 = d0 - d2, t1 = d1 + d2)
+  //   fh = 1: A, B, C = window rows 2, 1, 3 and sg = -1   (t2 = d2 - d1, t3 = d1 - d3)
+  // -- the same code for both halves, and 18 window values each (the pairing {t1, t2} / {t0, t3} would need 12 / 24).  A fused
+  // multiply-add by +-1 rounds as the addition or subtraction it stands for: V is bit for bit what the channel-half split computed.
+  const int rowA = baddr + (fh ? 2 : 0) * P.WCp, rowB = baddr + (fh ? 1 : 2) * P.WCp, rowC = baddr + (fh ? 3 : 1) * P.WCp;
+  const f32x2v sg2 = {fh ? -1.f : 1.f, fh ? -1.f : 1.f};
 
-  const int a_lane = mh * 64 + l16 * 4;   // this wave's (f, f+1) x two m-tiles of a frequency pair: 16 lanes read 256 contiguous bytes
+  f32x4 acc[4][12];   // [m-tile][frequency 6 r + fc of the wave's rows r = 0, 1]
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int f = 0; f < 12; ++f) acc[m][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // A operands: MFMA group g = 0..11 of a chunk is frequency pair g / 2 of the wave (weight-image pair 6 fh + g / 2) for two m-tiles
+  // of the pair's two frequencies -- one ds_read_b128 (16 lanes read 256 contiguous bytes), four MFMAs.  acc[0..1] are the m-tiles the
+  // wave keeps (2 fh, 2 fh + 1: the even groups read that half of the image pair), acc[2..3] the two it hands to its partner.
+  const int a_keep = (j * 12 + fh * 6) * 128 + l16 * 4 + fh * 64, a_give = a_keep + (fh ? -64 : 64);
   begin_fill(c_lo, 0);
   weight_fill(c_lo, smem);
   if constexpr (PC) {
@@ -504,96 +514,115 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       lo = kc < P.src0.C ? lo0 : (kc < P.Cin ? lo1 : -__builtin_inff());
     }
     const bool more = chunk + 1 < c_hi;
-    const float* Wc = smem + cur * BUF;
-    float d[4][6];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const f32x4 ra = *reinterpret_cast<const f32x4*>(&Wc[baddr + i * P.WCp]);
-      const f32x2v rb = *reinterpret_cast<const f32x2v*>(&Wc[baddr + i * P.WCp + 4]);
-      d[i][0] = ra[0], d[i][1] = ra[1], d[i][2] = ra[2], d[i][3] = ra[3], d[i][4] = rb[0], d[i][5] = rb[1];
-    }
-    // A operands: one ds_read_b128 = this wave's two m-tiles of TWO consecutive frequencies (the weight image pairs them), read one
-    // pair (four MFMAs) ahead
-    f32x4 av[2];
-    av[0] = *reinterpret_cast<const f32x4*>(&Wc[(j * 12) * 128 + a_lane]);
-    if constexpr (!PLAIN) {
-      const f32x2v sc2 = {sc, sc}, sh2 = {sh, sh};
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
+    // the image's offset as an opaque scalar: the LDS bases of the two images are then one set of registers plus an addition each,
+    // not two sets held through the loop (registers the accumulators need)
+    int ioff = cur * BUF;
+    __asm__ volatile("" : "+s"(ioff));
+    const float* Wc = smem + ioff;
+    auto load_row = [&](const int addr, float (&r)[6]) {
+      const f32x4 ra = *reinterpret_cast<const f32x4*>(&Wc[addr]);
+      const f32x2v rb = *reinterpret_cast<const f32x2v*>(&Wc[addr + 4]);
+      r[0] = ra[0], r[1] = ra[1], r[2] = ra[2], r[3] = ra[3], r[4] = rb[0], r[5] = rb[1];
+    };
+    float dA[6], dB[6], dC[6];
+    load_row(rowA, dA);
+    load_row(rowB, dB);
+    load_row(rowC, dC);
+    f32x4 av[2];   // read one group (four MFMAs) ahead
+    av[0] = *reinterpret_cast<const f32x4*>(&Wc[a_keep]);
+    auto affine = [&](float (&r)[6]) {
+      if constexpr (!PLAIN) {
+        const f32x2v sc2 = {sc, sc}, sh2 = {sh, sh};
 #pragma unroll
         for (int c = 0; c < 6; c += 2) {   // (the fused multiply-add on pairs; there is no packed fp32 max)
-          const f32x2v y = __builtin_elementwise_fma(f32x2v{d[i][c], d[i][c + 1]}, sc2, sh2);
-          d[i][c] = fmaxf(y[0], lo);
-          d[i][c + 1] = fmaxf(y[1], lo);
+          const f32x2v y = __builtin_elementwise_fma(f32x2v{r[c], r[c + 1]}, sc2, sh2);
+          r[c] = fmaxf(y[0], lo);
+          r[c + 1] = fmaxf(y[1], lo);
         }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // frequency rows in the order that retires window rows early: t0 = d0 - d2, t3 = d1 - d3, t1 = d1 + d2, t2 = d2 - d1.
-    // Software pipeline over the rows: the operand transform of row fi + 1 (about 19 vector instructions) is issued between the
-    // 12 MFMAs of row fi -- an MFMA holds the SIMD's vector issue for 8 of its 32 cycles, three vector instructions fit its shadow.
-    constexpr int FR[4] = {0, 3, 1, 2};
-    auto freq_row = [&](int fr, float (&v)[6]) {
-      // V row = B4^T t of one frequency row, on pairs of floats (v_pk_add_f32 / v_pk_fma_f32: about half the vector instructions):
-      // pairs (t0,t1), (t2,t3), (t4,t5) of the column-transformed row, then
-      //   (a, c) = t4 + (-4,-1) t2      (b, e) = t3 + (-4,-1) t1      (v1, v2) = a + (1,-1) b      (v3, v4) = c + (2,-2) e
-      //   (v0, v5) = 4 (t0,t1) + ((t4,t5) - 5 (t2,t3))
-      // -- element for element the fused multiply-adds of the scalar transform (a multiplication by 1, 2 or -1 is exact)
-      f32x2v tp[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const f32x2v r0 = {d[0][2 * k], d[0][2 * k + 1]}, r1 = {d[1][2 * k], d[1][2 * k + 1]};
-        const f32x2v r2 = {d[2][2 * k], d[2][2 * k + 1]}, r3 = {d[3][2 * k], d[3][2 * k + 1]};
-        tp[k] = fr == 0 ? r0 - r2 : fr == 3 ? r1 - r3 : fr == 1 ? r1 + r2 : r2 - r1;
       }
-      const f32x2v m41 = {-4.f, -1.f}, p1m1 = {1.f, -1.f}, p2m2 = {2.f, -2.f}, m5 = {-5.f, -5.f}, p4 = {4.f, 4.f};
-      const f32x2v ac = __builtin_elementwise_fma(f32x2v{tp[1][0], tp[1][0]}, m41, f32x2v{tp[2][0], tp[2][0]});
-      const f32x2v be = __builtin_elementwise_fma(f32x2v{tp[0][1], tp[0][1]}, m41, f32x2v{tp[1][1], tp[1][1]});
+    };
+    // V row = B4^T t of one frequency row, on pairs of floats (v_pk_add_f32 / v_pk_fma_f32: about half the vector instructions), in
+    // three stages so that the second row's can be spread over the first row's MFMAs: pairs (t0,t1), (t2,t3), (t4,t5) of the
+    // column-transformed row, then
+    //   (a, c) = t4 + (-4,-1) t2      (b, e) = t3 + (-4,-1) t1      (v1, v2) = a + (1,-1) b      (v3, v4) = c + (2,-2) e
+    //   (v0, v5) = 4 (t0,t1) + ((t4,t5) - 5 (t2,t3))
+    // -- element for element the fused multiply-adds of the scalar transform (a multiplication by 1, 2 or -1 is exact)
+    const f32x2v m41 = {-4.f, -1.f}, p1m1 = {1.f, -1.f}, p2m2 = {2.f, -2.f}, m5 = {-5.f, -5.f}, p4 = {4.f, 4.f};
+    auto rt_a = [&](const f32x2v (&tp)[3], f32x2v& ac, f32x2v& be) {
+      ac = __builtin_elementwise_fma(f32x2v{tp[1][0], tp[1][0]}, m41, f32x2v{tp[2][0], tp[2][0]});
+      be = __builtin_elementwise_fma(f32x2v{tp[0][1], tp[0][1]}, m41, f32x2v{tp[1][1], tp[1][1]});
+    };
+    auto rt_b = [&](const f32x2v& ac, const f32x2v& be, float (&v)[6]) {
       const f32x2v v12 = __builtin_elementwise_fma(f32x2v{be[0], be[0]}, p1m1, f32x2v{ac[0], ac[0]});
       const f32x2v v34 = __builtin_elementwise_fma(f32x2v{be[1], be[1]}, p2m2, f32x2v{ac[1], ac[1]});
-      const f32x2v v05 = __builtin_elementwise_fma(tp[0], p4, __builtin_elementwise_fma(tp[1], m5, tp[2]));
-      v[0] = v05[0], v[1] = v12[0], v[2] = v12[1], v[3] = v34[0], v[4] = v34[1], v[5] = v05[1];
+      v[1] = v12[0], v[2] = v12[1], v[3] = v34[0], v[4] = v34[1];
     };
+    auto rt_c = [&](const f32x2v (&tp)[3], float (&v)[6]) {
+      const f32x2v v05 = __builtin_elementwise_fma(tp[0], p4, __builtin_elementwise_fma(tp[1], m5, tp[2]));
+      v[0] = v05[0], v[5] = v05[1];
+    };
+    // frequency row 2 fh: tA = A - B; tB = B + sg C as well where the sources are activated (the activated rows would otherwise
+    // stay live into the MFMAs beside the affine's coefficients: more than the 256 registers hold)
+    affine(dA);
+    affine(dB);
+    f32x2v tA[3], tB[3], acB, beB;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tA[k] = f32x2v{dA[2 * k], dA[2 * k + 1]} - f32x2v{dB[2 * k], dB[2 * k + 1]};
+    auto col_b = [&]() {
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        tB[k] = __builtin_elementwise_fma(f32x2v{dC[2 * k], dC[2 * k + 1]}, sg2, f32x2v{dB[2 * k], dB[2 * k + 1]});
+    };
+    if constexpr (!PLAIN) {
+      affine(dC);
+      col_b();
+    }
     float v[2][6];
-    freq_row(FR[0], v[0]);
+    {
+      f32x2v ac, be;
+      rt_a(tA, ac, be);
+      rt_b(ac, be, v[0]);
+      rt_c(tA, v[0]);
+    }
     __builtin_amdgcn_sched_barrier(0);
+    // the chunk's 48 MFMAs in 12 groups of four (one A read each, issued a group ahead).  Row 2 fh + 1 is transformed in small
+    // pieces inside the first row's groups -- an MFMA holds the SIMD's vector issue for 8 of its 32 cycles and every gap that carries
+    // vector work costs cycles of its own (profiles/r05_mfma_f32_issue_ubench.txt), so the pieces are few and short; the second
+    // row's groups carry no vector work.  The next chunk's fills ride in the first three groups.
 #pragma unroll
-    for (int fi = 0; fi < 4; ++fi) {
-      const int fr = FR[fi];
-      if (fi + 1 < 4) freq_row(FR[fi + 1], v[(fi + 1) & 1]);
-#pragma unroll
-      for (int fc = 0; fc < 6; ++fc) {
-        const int s = fi * 6 + fc, f = fr * 6 + fc;
-        if ((s & 1) == 0 && s + 2 < 24) {
-          const int fn = FR[(s + 2) / 6] * 6 + (s + 2) % 6;
-          av[((s >> 1) + 1) & 1] = *reinterpret_cast<const f32x4*>(&Wc[(j * 12 + (fn >> 1)) * 128 + a_lane]);
-        }
-        const f32x4& ap = av[(s >> 1) & 1];
-        acc[0][f] = mfma16(ap[(s & 1) * 2], v[fi & 1][fc], acc[0][f]);
-        acc[1][f] = mfma16(ap[(s & 1) * 2 + 1], v[fi & 1][fc], acc[1][f]);
-        // the next chunk's fills ride in the first k-steps: the weights in one k-step (shared LDS bases), then the halo
-        if (more && s < 3) {
-          float* Wn = smem + (cur ^ 1) * BUF;
-          if (s == 0) {
-            begin_fill(chunk + 1, cur ^ 1);
-            weight_fill(chunk + 1, Wn);
+    for (int g = 0; g < 12; ++g) {
+      const int r = g / 6, fe = (g >> 1) * 2 - 6 * r, mt = 2 * (g & 1);
+      if (g + 1 < 12) av[(g + 1) & 1] = *reinterpret_cast<const f32x4*>(&Wc[((g + 1) & 1 ? a_give : a_keep) + ((g + 1) >> 1) * 128]);
+      const f32x4& ap = av[g & 1];
+      acc[mt][6 * r + fe] = mfma16(ap[0], v[r][fe], acc[mt][6 * r + fe]);
+      acc[mt + 1][6 * r + fe] = mfma16(ap[1], v[r][fe], acc[mt + 1][6 * r + fe]);
+      acc[mt][6 * r + fe + 1] = mfma16(ap[2], v[r][fe + 1], acc[mt][6 * r + fe + 1]);
+      acc[mt + 1][6 * r + fe + 1] = mfma16(ap[3], v[r][fe + 1], acc[mt + 1][6 * r + fe + 1]);
+      // the second row's transform: tB (plain sources), then the three stages
+      const int piece = PLAIN ? g + 1 : g + 2;
+      if (piece == 1) col_b();
+      if (piece == 2) rt_a(tB, acB, beB);
+      if (piece == 3) rt_b(acB, beB, v[1]);
+      if (piece == 4) rt_c(tB, v[1]);
+      if (more && g < 3) {
+        float* Wn = smem + (cur ^ 1) * BUF;
+        if (g == 0) {
+          begin_fill(chunk + 1, cur ^ 1);
+          weight_fill(chunk + 1, Wn);
+        } else {
+          if constexpr (PC) {
+            halo_unit(g - 1, Wn + WTILE);
           } else {
-            if constexpr (PC) {
-              halo_unit(s - 1, Wn + WTILE);
-            } else {
-              halo_slot(2 * s - 2, Wn + WTILE);
-              halo_slot(2 * s - 1, Wn + WTILE);
-            }
+            halo_slot(2 * g - 2, Wn + WTILE);
+            halo_slot(2 * g - 1, Wn + WTILE);
           }
-          __builtin_amdgcn_sched_barrier(0);
         }
       }
-      // the interleave of the row's MFMAs with the next row's transform, pinned (row 0 carries the fills: its k-steps are pinned above)
-      if (fi > 0 || !more) {
+      if (g < 6) {
 #pragma unroll
-        for (int g = 0; g < 6; ++g) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);   // two MFMAs
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // at most one LDS read
-          __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);   // four vector instructions of the next row's transform
+        for (int i = 0; i < 4; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // an MFMA
+          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // at most one vector instruction of the piece
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -604,8 +633,30 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
     if (chunk + 1 < c_hi) run_chunk(chunk + 1, std::integral_constant<int, 1>{});
   }
 
+  // ---- the two frequency halves of a pixel group meet: each wave hands its accumulators of the partner's m-tiles (acc[2..3]) to the
+  // partner (wave ph + NWP (1 - fh)) and takes the partner's of its own in their place, through the two chunk images (48 KiB a
+  // round, two rounds).  Then acc[0..1] hold the wave's frequency rows 2 fh, 2 fh + 1 of its m-tiles 2 fh + m and acc[2..3] the other
+  // two rows: the output transform below is the one of the channel-half split, bit for bit.
+  {
+    float* const xs = smem + (wave8 * 12) * 256 + lane * 4;
+    const float* const xr = smem + ((ph + NWP * (1 - fh)) * 12) * 256 + lane * 4;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      __syncthreads();   // round 0: every wave has left the last chunk's image; round 1: the partner has read round 0
+#pragma unroll
+      for (int f = 0; f < 12; ++f) *reinterpret_cast<f32x4*>(xs + f * 256) = acc[2 + r][f];
+      __syncthreads();
+#pragma unroll
+      for (int f = 0; f < 12; ++f) acc[2 + r][f] = *reinterpret_cast<const f32x4*>(xr + f * 256);
+    }
+  }
+
   // Y = A2^T M A4 of one channel's tile: down the columns first (24 -> 12 values), then along the rows (12 -> 2 x 4 outputs)
-  auto out_transform = [&](int m, int reg, float (&y)[2][4]) __attribute__((always_inline)) {
+  // (HI: a wave of the second frequency half, whose acc[m] hold rows 2, 3 and acc[2 + m] rows 0, 1 -- two copies of the epilogue
+  // behind a wave-uniform branch rather than a register shuffle)
+  auto out_transform = [&](auto hi_c, int m, int reg, float (&y)[2][4]) __attribute__((always_inline)) {
+    constexpr bool HI = decltype(hi_c)::value;
+    const int lo = HI ? 2 + m : m, hi = HI ? m : 2 + m;
     // two channels at once: accumulator registers (2 rp, 2 rp + 1) of a quad are an aligned pair, so the same additions and fused
     // multiply-adds run as v_pk_add_f32 / v_pk_fma_f32; an odd reg takes the second halves of what its even neighbour computed
     // (the compiler merges the two calls' identical packed instructions)
@@ -615,8 +666,8 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       f32x2v R[6];
 #pragma unroll
       for (int fc = 0; fc < 6; ++fc) {
-        const f32x2v M0 = {acc[m][fc][r0], acc[m][fc][r0 + 1]}, M1 = {acc[m][6 + fc][r0], acc[m][6 + fc][r0 + 1]};
-        const f32x2v M2 = {acc[m][12 + fc][r0], acc[m][12 + fc][r0 + 1]}, M3 = {acc[m][18 + fc][r0], acc[m][18 + fc][r0 + 1]};
+        const f32x2v M0 = {acc[lo][fc][r0], acc[lo][fc][r0 + 1]}, M1 = {acc[lo][6 + fc][r0], acc[lo][6 + fc][r0 + 1]};
+        const f32x2v M2 = {acc[hi][fc][r0], acc[hi][fc][r0 + 1]}, M3 = {acc[hi][6 + fc][r0], acc[hi][6 + fc][r0 + 1]};
         R[fc] = a == 0 ? M0 + M1 + M2 : M1 - M2 - M3;
       }
       const f32x2v p12 = R[1] + R[2], m12 = R[1] - R[2], p34 = R[3] + R[4], m34 = R[3] - R[4];
@@ -627,22 +678,29 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
     }
   };
 
-  if constexpr (SPLIT) {
-    // the un-reduced outputs of this slab: 32 bytes per lane and channel, 512-byte runs per 16 lanes
-    float* const sl = P.slabs + ((size_t)((size_t)pt * P.nslab + slab) * P.mblocks + mbb) * (size_t)(BM * 128 * NWP);
+  auto finish = [&](auto hi_c) __attribute__((always_inline)) {
+    auto get_y = [&](int m, int reg, float (&y)[2][4]) __attribute__((always_inline)) { out_transform(hi_c, m, reg, y); };
+    if constexpr (SPLIT) {
+      // the un-reduced outputs of this slab: 32 bytes per lane and channel, 512-byte runs per 16 lanes
+      float* const sl = P.slabs + ((size_t)((size_t)pt * P.nslab + slab) * P.mblocks + mbb) * (size_t)(BM * 128 * NWP);
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+      for (int m = 0; m < 2; ++m)
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        float y[2][4];
-        out_transform(m, reg, y);
-        float* const o = sl + ((size_t)(mh * 32 + m * 16 + j * 4 + reg) * (16 * NWP) + q) * 8;
-        *reinterpret_cast<f32x4*>(o) = f32x4{y[0][0], y[0][1], y[0][2], y[0][3]};
-        *reinterpret_cast<f32x4*>(o + 4) = f32x4{y[1][0], y[1][1], y[1][2], y[1][3]};
-      }
-    return;
-  }
-  w2d_epilogue(P, sBw, n, h0, w0, tr2, tq, vmask, m0, mh, ph, j, l16, pt, out_transform);
+        for (int reg = 0; reg < 4; ++reg) {
+          float y[2][4];
+          get_y(m, reg, y);
+          float* const o = sl + ((size_t)(fh * 32 + m * 16 + j * 4 + reg) * (16 * NWP) + q) * 8;
+          *reinterpret_cast<f32x4*>(o) = f32x4{y[0][0], y[0][1], y[0][2], y[0][3]};
+          *reinterpret_cast<f32x4*>(o + 4) = f32x4{y[1][0], y[1][1], y[1][2], y[1][3]};
+        }
+    } else {
+      w2d_epilogue(P, sBw, n, h0, w0, tr2, tq, vmask, m0, fh, ph, j, l16, pt, get_y);
+    }
+  };
+  if (fh == 0)
+    finish(std::false_type{});
+  else
+    finish(std::true_type{});
 }
 
 // The second half of a K-slab launch: one block per (pixel tile, m-block) with the conv kernel's thread -> (tile, channel) map adds
