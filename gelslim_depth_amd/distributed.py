@@ -132,9 +132,11 @@ class GradSync:
                 "buckets": {k: {"ms": round(v[0] / steps, 4), "MB": round(v[1] / steps / 1e6, 3)} for k, v in per.items()}}
 
 
-def broadcast_state(p_flat: torch.Tensor, buffers: Sequence[torch.Tensor], group=None, src: int = 0) -> None:
-    """Rank `src`'s parameters and BatchNorm buffers become everyone's (what DDP does at construction)."""
+def broadcast_state(p_flat: torch.Tensor, buffers: Sequence[torch.Tensor], group=None, src: int = 0,
+                    extra: Sequence[torch.Tensor] = ()) -> None:
+    """Rank `src`'s parameters and BatchNorm buffers become everyone's (what DDP does at construction); so do the `extra`
+    arenas (TrainStep.load_state: Adam moments, EMA shadow, guard words)."""
     import torch.distributed as dist
     dist.broadcast(p_flat, src=src, group=group)
-    for b in buffers:
+    for b in list(buffers) + list(extra):
         dist.broadcast(b, src=src, group=group)

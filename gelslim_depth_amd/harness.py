@@ -55,6 +55,23 @@ class EarlyStopping:
         self.e += 1
         return stop, stalled, new_min
 
+    def state_dict(self) -> Dict[str, object]:
+        """Every field, as plain Python values."""
+        return {"window": self.window, "count_threshold": self.count_threshold, "train_indefinitely": self.train_indefinitely,
+                "validation_array": [float(v) for v in self.validation_array],
+                "prev_validation_loss": float(self.prev_validation_loss),
+                "validation_loss_upward_counter": self.validation_loss_upward_counter,
+                "min_validation_loss": float(self.min_validation_loss), "e": self.e}
+
+    def load_state_dict(self, sd: Dict[str, object]) -> None:
+        self.window, self.count_threshold = int(sd["window"]), int(sd["count_threshold"])
+        self.train_indefinitely = bool(sd["train_indefinitely"])
+        self.validation_array = np.array(sd["validation_array"], dtype=np.float64)
+        self.prev_validation_loss = sd["prev_validation_loss"]
+        self.validation_loss_upward_counter = int(sd["validation_loss_upward_counter"])
+        self.min_validation_loss = sd["min_validation_loss"]
+        self.e = int(sd["e"])
+
 
 def _mean_loss(losses: List[float], n_batches: int) -> float:
     return float(sum(losses) / n_batches) if n_batches else 0.0
@@ -112,15 +129,61 @@ def evaluate_loader(step, loader: Iterable[Dict], loss_kind: str = "mse") -> flo
     return _mean_loss([0.0 if v != v else v for v in vals], len(vals))
 
 
+FIT_STATE_FORMAT = "gelslim_depth_amd.harness.fit"
+
+
+def _save_fit_state(step, path: str, loop: Dict[str, object]) -> None:
+    import torch
+    from .train import atomic_save
+    loop = dict(loop, torch_rng=torch.get_rng_state(),
+                cuda_rng=torch.cuda.get_rng_state_all() if torch.cuda.is_available() else None)
+    atomic_save({"format": FIT_STATE_FORMAT, "version": 1, "train_step": step.state_dict(), "loop": loop}, path)
+
+
+def _restore_fit_state(step, path: str, is_main: bool) -> Optional[Dict[str, object]]:
+    """The loop's saved state, after the step's and the RNG states have been restored; None when there is no file.  Data
+    parallel: rank 0 reads the file, the loop's state goes to every rank with broadcast_object_list, the step's arenas by
+    its own broadcast (TrainStep.load_state_dict)."""
+    import torch
+    from .train import read_state
+    blob = read_state(path) if (is_main and os.path.exists(path)) else None
+    if blob is not None and (not isinstance(blob, dict) or blob.get("format") != FIT_STATE_FORMAT):
+        raise ValueError(f"{path} is not a harness.fit state file (written by fit(..., state_path=...))")
+    loop = None if blob is None else blob["loop"]
+    if getattr(step, "world", 1) > 1:
+        box = [loop]
+        step.dist.broadcast_object_list(box, src=0, group=step.pg)
+        loop = box[0]
+    if loop is None:
+        return None
+    step.load_state_dict(None if blob is None else blob["train_step"])
+    torch.set_rng_state(loop["torch_rng"])
+    if loop["cuda_rng"] is not None and torch.cuda.is_available():
+        for i, s in enumerate(loop["cuda_rng"][:torch.cuda.device_count()]):
+            torch.cuda.set_rng_state(s, i)
+    return loop
+
+
 def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_name: str, loss_values_path: Optional[str] = None,
         val_loss_SMA_window: int = 10, validation_loss_count_threshold: int = 5, train_indefinitely: bool = False,
         save_at_epochs: Sequence[int] = (), max_epochs: Optional[int] = None,
         train_pass: Optional[Callable] = None, eval_pass: Optional[Callable] = None, save: Optional[Callable] = None,
-        echo: Callable[[str], None] = print) -> Dict[str, List[float]]:
+        echo: Callable[[str], None] = print, state_path: Optional[str] = None, resume: bool = False,
+        state_every: int = 1) -> Dict[str, List[float]]:
     """Run epochs until the stopping rule fires (or `max_epochs`).  Returns H = {train_loss, validation_loss, test_loss}.
 
     `train_pass(step, loader) -> (sum_of_batch_losses, n_batches)`, `eval_pass(step, loader) -> mean_loss` and
     `save(step, path)` default to the libgsd implementations; tests substitute host stubs for them.
+
+    Resumable runs (an addition; off by default): with `state_path`, rank 0 writes one file at the end of every
+    `state_every`-th epoch and of the last epoch, after that epoch's log lines and checkpoints -- the step's
+    `state_dict()` and the loop's own state: the next epoch, the stopping rule's fields, H, the elapsed training time and
+    the torch RNG states (the CPU generator orders DeviceLoader's shuffles).  With `resume=True` and that file present, all
+    of it is restored before the first epoch and the run continues at the saved epoch (a run the stopping rule ended
+    stays ended); `max_epochs` counts every epoch, the interrupted ones included.  The resumed part writes only the lines of its own epochs to the log file (a one-line
+    notice goes to `echo`), so the concatenated log equals an uninterrupted run's apart from the timing lines and the
+    first part's closing lines.  Resume is per epoch: a run killed after the last file repeats the epochs since, log lines
+    included.
 
     Data parallel (a build-side addition, the reference is single-process): every rank runs the same epochs on its shard
     of each batch; the epoch losses are averaged over the ranks (`step.mean_across_ranks`) so that all ranks take the
@@ -128,6 +191,8 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
     test passes walk the GLOBAL batches with every rank scoring its own share (`evaluate_loader`): the value is the
     single-process one (no wrap-around padding in the loss early stopping reads), identical on every rank, at the per-rank
     train shape; `across()` of it is then the identity up to the last bit."""
+    if state_every < 1:
+        raise ValueError(f"state_every must be at least 1, got {state_every}")
     if train_pass is None:
         from .dataset import train_epoch as train_pass
     if eval_pass is None:
@@ -153,8 +218,17 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
             log.write(line + "\n")
     start = time.time()
     try:
-        e = 0
-        while True:
+        e, done = 0, False
+        if resume and state_path is not None:
+            saved = _restore_fit_state(step, state_path, is_main)
+            if saved is not None:
+                e, H = int(saved["epoch"]), {k: list(v) for k, v in saved["H"].items()}
+                stopper.load_state_dict(saved["early_stopping"])
+                start -= float(saved["elapsed"])
+                done = bool(saved["stopped"]) or (max_epochs is not None and e >= max_epochs)
+                if is_main:
+                    echo(f"Resuming from {state_path} at epoch {e + 1}")
+        while not done:
             t0 = time.time()
             total, nb = train_pass(step, train_loader)
             train_loss = across(total / nb if nb else 0.0)
@@ -178,8 +252,12 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
             emit("Train loss: {:.6f},  Validation loss: {:.6f}, Test loss: {:.6f}".format(train_loss, validation_loss, test_loss))
             emit(f"Time for epoch: {time.time() - t0}")
             e += 1
-            if stop or (max_epochs is not None and e >= max_epochs):
-                break
+            done = stop or (max_epochs is not None and e >= max_epochs)
+            if state_path is not None and is_main and (e % state_every == 0 or done):
+                if log is not None:
+                    log.flush()              # the log on disk holds every line of the epochs the state has behind it
+                _save_fit_state(step, state_path, {"epoch": e, "stopped": stop, "early_stopping": stopper.state_dict(),
+                                                   "H": H, "elapsed": time.time() - start})
         emit("Training complete")
         emit("Training time: {}s".format(time.time() - start))
     finally:

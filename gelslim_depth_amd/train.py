@@ -35,6 +35,21 @@ from .models.unet import UNet
 
 LOSS_KINDS = {"mse": 0, "l1": 1}
 
+STATE_FORMAT = "gelslim_depth_amd.TrainStep"
+STATE_VERSION = 1
+STATE_HPARAMS = ("lr", "betas", "eps", "weight_decay", "ema_decay", "loss", "nan_policy")
+
+
+def atomic_save(obj, path: str) -> None:
+    """torch.save to `path + ".tmp"`, flushed to disk, then renamed over `path`: a kill during the write leaves the previous
+    file (or none), never a truncated one."""
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        torch.save(obj, f)
+        f.flush()
+        os.fsync(f.fileno())
+    os.replace(tmp, path)
+
 
 def loss_fwd_bwd(kind: str, out: torch.Tensor, target: torch.Tensor, grad: Optional[torch.Tensor],
                  loss_buf: torch.Tensor, ws: torch.Tensor, grad_scale: float = 1.0, guard=None) -> None:
@@ -283,3 +298,164 @@ class TrainStep:
             else:
                 out[k] = v.clone()
         return out
+
+    # -- the full training state: save, then continue bit for bit ---------------------------------------------------------
+    def _arena_table(self) -> List[Tuple[str, int, Tuple[int, ...]]]:
+        shapes = {n: tuple(p.shape) for n, p in self.model.named_parameters()}
+        return [(n, o, shapes[n]) for n, (o, _) in self.offsets.items()]
+
+    def _hparams(self) -> Dict[str, object]:
+        return {"lr": float(self.lr), "betas": tuple(float(b) for b in self.betas), "eps": float(self.eps),
+                "weight_decay": float(self.wd), "ema_decay": None if self.ema_decay is None else float(self.ema_decay),
+                "loss": self.loss_kind, "nan_policy": self.nan_policy}
+
+    def state_dict(self) -> Dict[str, object]:
+        """The whole training state as CPU tensors and host scalars: the model's state_dict (live parameters, BatchNorm
+        buffers, num_batches_tracked), the Adam moments and the EMA shadow (None without EMA) as flat fp32 arenas with their
+        table of (name, offset, shape), the step and EMA-update counts that drive the bias correction and the EMA warm-up,
+        the non-finite guard's words (None without a nan_policy), the constructor's hyperparameters and the architecture.
+        `load_state_dict` of it into a TrainStep over the same architecture continues the run bit for bit (same precision,
+        same world size).  Unlike `save_checkpoint` (EMA weights, the reference's 118-key layout) this is not a model file."""
+        model = self.model
+
+        def cpu(t):
+            return None if t is None else t.detach().to("cpu", copy=True)
+        return {"format": STATE_FORMAT, "version": STATE_VERSION,
+                "precision": model.precision, "n_channels": model.n_channels, "n_classes": model.n_classes,
+                "layer_dimensions": list(model._dims),
+                "model": {k: cpu(v) for k, v in model.state_dict().items()},
+                "arena": self._arena_table(),
+                "m_flat": cpu(self.m_flat), "v_flat": cpu(self.v_flat), "ema_flat": cpu(self.ema_flat),
+                "step_count": self.step_count, "ema_updates": self.ema_updates,
+                "guard_words": cpu(self.guard_words),
+                "hparams": self._hparams()}
+
+    def load_state_dict(self, sd: Dict[str, object], strict: bool = True) -> None:
+        """Continue from a `state_dict()`.  Everything is copied IN PLACE into the existing arenas (parameters, BatchNorm
+        buffers, Adam moments, EMA shadow, guard words), so the parameter and gradient views, the arena check of every step
+        and a GraphedInference captured on the model stay valid.  fp32 <-> bf16 is allowed: both keep fp32 master state.
+
+        Raises ValueError, naming the field, before anything is copied: another architecture (the first parameter whose
+        name, offset or shape differs), EMA on one side only, or -- with strict=True -- another hyperparameter (lr, betas,
+        eps, weight_decay, ema_decay, loss, nan_policy); strict=False keeps this TrainStep's hyperparameters (the guard's
+        skipped-step count then starts at 0 when the state has none).  A weights-only checkpoint is refused.
+
+        Data parallel: a collective.  Rank 0's `sd` is checked and loaded (the other ranks may pass None), then its arenas
+        and buffers are broadcast and its host scalars sent with broadcast_object_list."""
+        self._load(lambda: sd, strict)
+
+    def save_state(self, path: str) -> None:
+        """Write `state_dict()` to `path` (through `path + ".tmp"` and an atomic rename: a kill never leaves a partial
+        file).  Data parallel: rank 0 writes, the other ranks return at once."""
+        if self.rank == 0:
+            atomic_save(self.state_dict(), path)
+
+    def load_state(self, path: str, strict: bool = True) -> None:
+        """`load_state_dict` of the file `save_state` wrote.  Data parallel: only rank 0 reads it (the ranks need no shared
+        filesystem; `path` is ignored elsewhere)."""
+        self._load(lambda: read_state(path), strict)
+
+    def _load(self, get, strict: bool) -> None:
+        if self.sync is None:
+            self._load_local(get(), strict)
+            return
+        err = None
+        if self.rank == 0:
+            try:
+                self._load_local(get(), strict)
+            except Exception as exc:         # the other ranks wait in the broadcast below: tell them, then raise everywhere
+                err = exc
+        box = [None if err is None else f"{type(err).__name__}: {err}", self.step_count, self.ema_updates]
+        self.dist.broadcast_object_list(box, src=0, group=self.pg)
+        if err is not None:
+            raise err
+        if box[0] is not None:
+            raise ValueError(f"TrainStep state: rank 0 could not load it: {box[0]}")
+        self.step_count, self.ema_updates = int(box[1]), int(box[2])
+        from .distributed import broadcast_state
+        broadcast_state(self.p_flat, [b for _, b in self.model.named_buffers()], group=self.pg,
+                        extra=[t for t in (self.m_flat, self.v_flat, self.ema_flat, self.guard_words) if t is not None])
+
+    def _load_local(self, sd, strict: bool) -> None:
+        _check_state_format(sd)
+        model = self.model
+        arch = (f"layer_dimensions {list(sd['layer_dimensions'])}, n_channels {sd['n_channels']}, n_classes {sd['n_classes']} "
+                f"in the state; {list(model._dims)}, {model.n_channels}, {model.n_classes} here")
+        theirs = [(str(n), int(o), tuple(int(d) for d in s)) for n, o, s in sd["arena"]]
+        mine = self._arena_table()
+        for i in range(max(len(theirs), len(mine))):
+            a = theirs[i] if i < len(theirs) else None
+            b = mine[i] if i < len(mine) else None
+            if a != b:
+                desc = [("absent" if t is None else f"'{t[0]}' of shape {t[2]} at offset {t[1]}") for t in (a, b)]
+                raise ValueError(f"TrainStep state: parameter '{(a or b)[0]}' differs: {desc[0]} in the state, {desc[1]} here "
+                                 f"(another architecture: {arch})")
+        here = model.state_dict()
+        for k in list(sd["model"]) + [k for k in here if k not in sd["model"]]:
+            a, b = sd["model"].get(k), here.get(k)
+            if a is None or b is None or tuple(a.shape) != tuple(b.shape) or a.dtype != b.dtype:
+                desc = [("absent" if t is None else f"{tuple(t.shape)} {t.dtype}") for t in (a, b)]
+                raise ValueError(f"TrainStep state: model entry '{k}' is {desc[0]} in the state, {desc[1]} here ({arch})")
+        if (sd["ema_flat"] is None) != (self.ema_flat is None):
+            raise ValueError("TrainStep state: ema_flat: " + ("the state has no EMA shadow and this TrainStep keeps one"
+                             if sd["ema_flat"] is None else "the state has an EMA shadow and this TrainStep was built with "
+                             "ema_decay=None"))
+        for key in ("m_flat", "v_flat", "ema_flat"):
+            t = sd[key]
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != self.numel):
+                raise ValueError(f"TrainStep state: {key} must be {self.numel} float32 values, got "
+                                 f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        g = sd["guard_words"]
+        if g is not None and (not isinstance(g, torch.Tensor) or g.dtype != torch.int32 or g.numel() != 2):
+            raise ValueError("TrainStep state: guard_words must be two int32 words")
+        if strict:
+            mine_h = self._hparams()
+            for k in STATE_HPARAMS:
+                v = sd["hparams"].get(k)
+                if k == "betas" and v is not None:
+                    v = tuple(float(b) for b in v)
+                elif k in ("lr", "eps", "weight_decay", "ema_decay") and v is not None:
+                    v = float(v)
+                if v != mine_h[k]:
+                    raise ValueError(f"TrainStep state: {k} is {v!r} in the state and {mine_h[k]!r} here; pass strict=False "
+                                     "to continue with this TrainStep's hyperparameters")
+        with torch.no_grad():
+            model.load_state_dict(sd["model"], strict=True)
+            self.m_flat.copy_(sd["m_flat"])
+            self.v_flat.copy_(sd["v_flat"])
+            if self.ema_flat is not None:
+                self.ema_flat.copy_(sd["ema_flat"])
+            if self.guard_words is not None:
+                if g is not None:
+                    self.guard_words.copy_(g)
+                else:
+                    self.guard_words.zero_()
+        self.step_count = int(sd["step_count"])
+        self.ema_updates = int(sd["ema_updates"])
+        self._check_arenas()
+
+
+_STATE_KEYS = ("precision", "n_channels", "n_classes", "layer_dimensions", "model", "arena", "m_flat", "v_flat", "ema_flat",
+               "step_count", "ema_updates", "guard_words", "hparams")
+
+
+def read_state(path: str) -> Dict[str, object]:
+    """torch.load of a state file onto the CPU (tensors, numbers, strings and containers only: weights_only)."""
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+def _check_state_format(sd) -> None:
+    if isinstance(sd, dict) and sd.get("format") == STATE_FORMAT:
+        if int(sd.get("version", 0)) > STATE_VERSION:
+            raise ValueError(f"TrainStep state: version {sd['version']} is newer than this build reads ({STATE_VERSION})")
+        missing = [k for k in _STATE_KEYS if k not in sd]
+        if missing:
+            raise ValueError(f"TrainStep state: field '{missing[0]}' is missing")
+        return
+    if isinstance(sd, dict) and sd and all(isinstance(v, torch.Tensor) for v in sd.values()):
+        raise ValueError(f"TrainStep state: this is a weights-only checkpoint ({len(sd)} tensors, the model state_dict that "
+                         "TrainStep.save_checkpoint and the reference's training script write), with no Adam moments, EMA "
+                         "shadow or step counts -- it cannot continue a run.  To start from its weights, call "
+                         "model.load_state_dict(torch.load(path)) before building the TrainStep")
+    raise ValueError(f"TrainStep state: format: expected a dict tagged '{STATE_FORMAT}' (TrainStep.state_dict / save_state), "
+                     f"got {type(sd).__name__}")
