@@ -15,6 +15,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSD_LIB_PATH") or os.path.join(_HERE, "csrc", "libgsd.so")   # override: A/B builds while tuning
 
 
+# gsd_status (include/gsd.h)
+GSD_OK, GSD_ERR_BAD_ARG, GSD_ERR_UNSUPPORTED, GSD_ERR_HIP, GSD_ERR_WORKSPACE = 0, -1, -2, -3, -4
+
+
 class GsdError(RuntimeError):
     pass
 
@@ -209,7 +213,7 @@ lib = _load()
 
 
 def check(rc: int, what: str = "") -> None:
-    if rc != 0:
+    if rc != GSD_OK:
         msg = lib.gsd_last_error().decode("utf-8", "replace")
         raise GsdError(f"libgsd {what} failed (code {rc}): {msg}")
 

@@ -18,16 +18,13 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
 from . import _lib as L
 from ._lib import lib, check
-
-BN_EPS = 1e-5
-BN_MOMENTUM = 0.1
-GSD_ERR_UNSUPPORTED = -2   # include/gsd.h
+from .engine_base import BN_EPS, ConvUnit, EngineBase, UpUnit
 
 
 def _r64(c: int) -> int:
@@ -83,92 +80,44 @@ class _ConvForm:
         return self.dgrad_bnrelu(src, wt, cin, cout, dst, raw, scale, shift, mean, invstd, part, n, h, w, st)
 
 
-class _Unit:
-    """conv3x3(no bias) + BatchNorm2d + ReLU (unet.py:11-13 / :14-16)."""
-
+class _Unit(ConvUnit):
     def __init__(self, prefix: str, conv_idx: int, bn_idx: int, cin: int, cout: int, level: int):
-        self.prefix, self.conv_idx, self.bn_idx = prefix, conv_idx, bn_idx
-        self.cin, self.cout, self.level = cin, cout, level
-        self.wname = f"{prefix}.double_conv.{conv_idx}.weight"
-        bn = f"{prefix}.double_conv.{bn_idx}."
-        self.gname, self.bname = bn + "weight", bn + "bias"
-        self.rmname, self.rvname, self.nbtname = bn + "running_mean", bn + "running_var", bn + "num_batches_tracked"
-        self.need_dgrad = True
+        super().__init__(prefix, conv_idx, bn_idx, cin, cout, level)
         self.c0 = cin              # channels of the first source segment (the decoder's first convs: the skip tensor's)
-        # device buffers (filled by the engine)
-        self.wt_f = self.wt_d = None
-        self.scale = self.shift = self.mean = self.invstd = self.c1 = self.c2 = None
-        self.sums = None
-        self.raw = self.g = None
+        self.raw = None
         self.dsrc = None  # d_raw as the dW / dX kernels read it: g itself, or the pitched scratch buffer (engine.gp)
         self.pitched = False   # gsd_bn_bwd_apply writes d_raw out of place into the pitched buffer
         self.fused_dw = False  # first layer: no dX, so dW forms d_raw itself (gsd_conv3x3_wgrad_bn) and the apply pass is skipped
         self.srcs = None  # gsd_src array kept for wgrad
         self.form_f = self.form_d = None   # _ConvForm of the forward / dX launch for the current shape
         self.forms_f = None                # ... of the forward launch in eval (False) and train (True) mode
-        self.fused_rows = 0                # partial rows written by the dX launch that produced this unit's dz
 
 
-class _Up:
-    """ConvTranspose2d(cin, cin//2, 2, 2) (unet.py:36)."""
-
+class _Up(UpUnit):
     def __init__(self, j: int, cin: int, level_in: int):
-        self.j, self.cin, self.cout, self.level_in = j, cin, cin // 2, level_in
-        self.wname, self.bname = f"up.{j}.up.weight", f"up.{j}.up.bias"
-        self.wt_f = self.wt_d = None
+        super().__init__(j, cin, level_in)
         self.mode_d = 3            # gsd_weight_layout mode of wt_d (gsd_convT2x2_dgrad_layout)
         self.bn_rows = 0           # > 0: the dX launch also does pass 1 of the BatchNorm backward of the unit below (partial rows)
         self.out = self.dout = None
 
 
-class UNetEngine:
+class UNetEngine(EngineBase):
+    Unit, Up = _Unit, _Up
+
     def __init__(self, n_channels: int, n_classes: int, layer_dimensions: Sequence[int]):
-        dims = list(layer_dimensions)
-        self.n_channels, self.n_classes, self.dims = n_channels, n_classes, dims
-        self.L = len(dims) - 1
-        self.enc: List[Tuple[_Unit, _Unit]] = []
-        self.dec: List[Tuple[_Unit, _Unit]] = []
-        self.ups: List[_Up] = []
-        self.enc.append((_Unit("inc", 0, 1, n_channels, dims[0], 0), _Unit("inc", 3, 4, dims[0], dims[0], 0)))
-        self.enc[0][0].need_dgrad = False
-        for i in range(self.L):
-            p = f"down.{i}.maxpool_conv.1"
-            self.enc.append((_Unit(p, 0, 1, dims[i], dims[i + 1], i + 1), _Unit(p, 3, 4, dims[i + 1], dims[i + 1], i + 1)))
-        for j, i in enumerate(range(self.L, 0, -1)):
-            cin, cout = dims[i], dims[i - 1]
-            # Up(cin, cout): ConvTranspose2d(cin, cin//2) then DoubleConv(cin, cout) on cat[skip, up] (unet.py:36-37,48):
-            # the reference only runs when skip channels + cin//2 == cin.
-            if dims[i - 1] + cin // 2 != cin:
-                raise ValueError(f"layer_dimensions {dims}: level {i} needs dims[i-1] + dims[i]//2 == dims[i] "
-                                 "(the reference model fails at torch.cat/conv otherwise)")
-            self.ups.append(_Up(j, cin, i))
-            p = f"up.{j}.conv"
-            # DoubleConv(in_channels=cin, out=cout): input = cat[skip (dims[i-1]), up (cin//2)]
-            self.dec.append((_Unit(p, 0, 1, cin, cout, i - 1), _Unit(p, 3, 4, cout, cout, i - 1)))
-            self.dec[-1][0].c0 = dims[i - 1]
-        self.units: List[_Unit] = [u for pair in self.enc for u in pair] + [u for pair in self.dec for u in pair]
-        self._shape = None
-        self._dev = None
-        self.sync_fn: Optional[Callable[[torch.Tensor], None]] = None   # SyncBN hook: all-reduce fp64 sums in place
-        self.world = 1
+        super().__init__(n_channels, n_classes, layer_dimensions)
+        for j, (u0, _) in enumerate(self.dec):
+            u0.c0 = self.dims[self.L - 1 - j]      # cat[skip, up]: the skip tensor comes first
         self._saved = False        # the last forward kept what a backward needs (train mode, or eval mode with keep=True)
         self._saved_eval = False   # ... and ran in eval mode: BatchNorm normalised with the running statistics
-        self.block_done_cb: Optional[Callable[[str], None]] = None   # data-parallel hook: a block's grads are final
-        self._nbt: list = []   # num_batches_tracked buffers of the current train-mode forward
-        self.guard = None          # non-finite guard of the current step (_lib.make_guard), set by TrainStep per step
-        self.generation = 0        # forwards so far: a backward belongs to exactly one (models/unet.py checks it)
-        # bench hook: when a list, every conv3x3 launch appends (variant, flops, start_event, end_event)
         # partial-row count up to which BatchNorm's column sums and finalize run as ONE launch (gsd_bn_[bwd_]reduce_finalize)
         self.one_launch_rows = int(os.environ.get("GSD_BN_ONE_LAUNCH_ROWS", "4096"))
         # weight gradients on a side stream: dW of a unit runs beside its dX and the BatchNorm backward of the unit below (they only
         # share d_raw as an input).  A dW block owns its CU (8 waves x 240 registers, 96 KiB of LDS), so the two streams interleave CU
         # by CU: dX keeps its stand-alone speed and dW fills the CUs dX's tails and the chain's small launches leave idle
         self.side_dw = os.environ.get("GSD_SIDE_DW", "1") != "0"
-        self.side: Optional[torch.cuda.Stream] = None
-        self._handoff: Optional[torch.cuda.Stream] = None   # bucket hand-off to the all-reduce (see _announce)
-        self.kernel_log: Optional[list] = None
-        self.wgrad_log: Optional[list] = None      # bench hook: conv3x3 dW launches (+ slab reducer), same rows as kernel_log
-        self.region_log: Optional[list] = None     # bench hook: (region name, start event, end event)
+        # bench hooks.  kernel_log (EngineBase): every conv3x3 forward / dX launch appends the row _log_end builds
+        self.wgrad_log: Optional[list] = None      # conv3x3 dW launches (+ slab reducer), same rows as kernel_log
 
     # ------------------------------------------------------------------ buffers
     # Library switches that change launch plans (tile shapes, partial-row counts, slab counts, the form a launch takes): partials,
@@ -178,7 +127,7 @@ class UNetEngine:
                    "GSD_WGRAD_ALGO", "GSD_WGRAD_W2D", "GSD_WG2D_KX", "GSD_WG2D_BLOCKS", "GSD_WGRAD_BLOCKS", "GSD_WG43_TW")
 
     def _ensure(self, n: int, h: int, w: int, dev: torch.device, train: bool) -> None:
-        key = (n, h, w, str(dev), tuple(os.environ.get(k) for k in self._SIZING_ENV))
+        key = (n, h, w, str(dev), self._env_key())
         if self._shape == key and (not train or self.units[0].g is not None):
             return
         if self._shape != key:
@@ -187,13 +136,7 @@ class UNetEngine:
             for up in self.ups:
                 up.out = up.dout = None
         self._shape = key
-        self._dev = dev
-        hs, ws = [h], [w]
-        for _ in range(self.L):
-            hs.append(hs[-1] // 2)
-            ws.append(ws[-1] // 2)
-        assert hs[-1] >= 1 and ws[-1] >= 1, "input too small for this many max-pools"
-        self.hs, self.ws = hs, ws
+        hs, ws = self._set_pyramid(h, w)
         f32 = dict(device=dev, dtype=torch.float32)
         max_part = 1
         max_ws = 1
@@ -205,11 +148,7 @@ class UNetEngine:
                 u.raw = L.slack_empty((n, u.cout, lh, lw), dev)   # dW reads it as 16-byte window pieces
             if train and u.g is None:
                 u.g = torch.empty((n, u.cout, lh, lw), **f32)
-            if u.scale is None or u.scale.device != dev:
-                for nm in ("scale", "shift", "mean", "invstd", "c1", "c2"):
-                    setattr(u, nm, torch.empty((u.cout,), **f32))
-                u.sums = torch.empty((65 * 3 * u.cout,), device=dev, dtype=torch.float64)
-            # direct taps or Winograd F(4,3) rows, per layer shape and per direction (include/gsd.h: gsd_conv3x3_algo)
+            self._alloc_bn(u, dev)
             # direct taps, Winograd F(4,3) rows or two-dimensional Winograd, per layer shape, per direction and per mode: an
             # eval-mode forward takes the forms whose bits do not depend on the batch size (_ConvForm.choose)
             u.forms_f = {t: _ConvForm.choose(n, lh, lw, u.cin, u.c0, u.cout, t) for t in (False, True)}
@@ -318,28 +257,8 @@ class UNetEngine:
         self._log_end(ev, u.cout, u.cin, n, lh, lw, u.form_f.algo)
         if train:
             rows = u.form_f.partial_rows(n, lh, lw, u.cout)
-            count = float(n * lh * lw)
-            if self.sync_fn is None and rows <= self.one_launch_rows:
-                # a few hundred partial rows (the deep levels; every level at small batches): column sums + finalize in ONE
-                # launch instead of three (no SyncBN exchange in between)
-                check(lib.gsd_bn_reduce_finalize(self.partials.data_ptr(), rows, _r64(u.cout), u.cout, u.sums.data_ptr(), count,
-                                                 P[u.gname].data_ptr(), P[u.bname].data_ptr(), BN_EPS, BN_MOMENTUM,
-                                                 P[u.rmname].data_ptr(), P[u.rvname].data_ptr(), u.mean.data_ptr(),
-                                                 u.invstd.data_ptr(), u.scale.data_ptr(), u.shift.data_ptr(), self.guard, st),
-                      "bn_reduce_finalize")
-                self._nbt.append(P[u.nbtname])
-                return
-            check(lib.gsd_bn_reduce_partials(self.partials.data_ptr(), rows, _r64(u.cout), u.cout, u.sums.data_ptr(), st),
-                  "bn_reduce_partials")
-            if self.sync_fn is not None:
-                self.sync_fn(u.sums[:2 * u.cout])
-                count *= self.world
-            check(lib.gsd_bn_finalize(u.sums.data_ptr(), u.cout, count, P[u.gname].data_ptr(), P[u.bname].data_ptr(),
-                                      BN_EPS, BN_MOMENTUM, P[u.rmname].data_ptr(), P[u.rvname].data_ptr(),
-                                      u.mean.data_ptr(), u.invstd.data_ptr(), u.scale.data_ptr(), u.shift.data_ptr(),
-                                      self.guard, st),
-                  "bn_finalize")
-            self._nbt.append(P[u.nbtname])   # int64 counter buffers (BatchNorm2d.num_batches_tracked): one add for all, below
+            self._bn_stats(u, rows, _r64(u.cout), float(n * lh * lw), P, st,
+                           one_launch=self.sync_fn is None and rows <= self.one_launch_rows)
         elif keep:   # a backward follows: also the running statistics as mean / invstd (same scale / shift bits)
             check(lib.gsd_bn_eval_coeffs_bwd(P[u.gname].data_ptr(), P[u.bname].data_ptr(), P[u.rmname].data_ptr(),
                                              P[u.rvname].data_ptr(), BN_EPS, u.cout, u.scale.data_ptr(), u.shift.data_ptr(),
@@ -353,16 +272,13 @@ class UNetEngine:
     def _log_begin(self):
         if self.kernel_log is None and self.region_log is None:
             return None
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
+        return self._event()
 
     def _log_end(self, ev, m: int, k_ch: int, n: int, lh: int, lw: int, algo: int = 0) -> None:
         """(kernel, ALGORITHMIC flops of the convolution = 2*9*M*K*pixels, events, shape, flops the MFMAs executed)."""
         if ev is None or self.kernel_log is None:
             return
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
+        e = self._event()
         flops = 2.0 * m * k_ch * 9 * n * lh * lw
         if algo == 2:
             variant = "conv3x3_w2d_kernel"
@@ -375,12 +291,6 @@ class UNetEngine:
             executed = flops
         self.kernel_log.append((variant, flops, ev, e, (m, k_ch, lh, lw), executed))
 
-    def _pad_off(self, lvl: int) -> Tuple[int, int]:
-        # F.pad(x1, [dX//2, dX-dX//2, dY//2, dY-dY//2]) (unet.py:43-47)
-        dy = self.hs[lvl] - 2 * self.hs[lvl + 1]
-        dx = self.ws[lvl] - 2 * self.ws[lvl + 1]
-        return dy // 2, dx // 2
-
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], train: bool, out: Optional[torch.Tensor] = None,
                 keep: bool = False) -> torch.Tensor:
@@ -388,19 +298,12 @@ class UNetEngine:
         keep (eval mode): also keep what a backward() needs -- the launches and output bits are those of the plain eval forward
         (the eval forms, scale / shift from the running statistics; nothing updates the running statistics), the backward
         buffers are allocated and every unit's mean / invstd hold the running statistics."""
-        if x.dtype != torch.float32 or not x.is_cuda:
-            raise L.GsdError("UNetEngine.forward needs a float32 tensor on the GPU (no CPU fallback)")
-        self._nbt = []
-        x = x.contiguous()
-        n, c, h, w = x.shape
-        assert c == self.n_channels, f"expected {self.n_channels} input channels, got {c}"
         keep = keep and not train
-        self._ensure(n, h, w, x.device, train or keep)
+        x = self._begin_forward(x, train or keep)
+        n, _, h, w = x.shape
         st = L.stream_ptr()
-        self._x = x
         self._saved = train or keep
         self._saved_eval = keep
-        self.generation += 1       # every forward overwrites the saved activations
         # every forward-mode weight layout of the pass: the 2-D Winograd images in one launch
         self._layouts([(u.forms_f[train].mode_f, P[u.wname], u.cout, u.cin, u.wt_f) for u in self.units] +
                       [(6, P[up.wname], up.cout, up.cin, up.wt_f) for up in self.ups], st)
@@ -411,9 +314,7 @@ class UNetEngine:
                 srcs = [L.make_src(x)]
             else:
                 if lvl == 1 and region is not None:       # bench hook: the `inc` double-conv forward (2 convs + BN statistics)
-                    e = torch.cuda.Event(enable_timing=True)
-                    e.record()
-                    self.region_log.append(("inc_forward", region, e))
+                    self.region_log.append(("inc_forward", region, self._event()))
                 prev = self.enc[lvl - 1][1]
                 s = self._act_src(prev)
                 check(lib.gsd_maxpool2(C.byref(s), self.pooled[lvl].data_ptr(), n, prev.cout, self.hs[lvl - 1],
@@ -422,9 +323,7 @@ class UNetEngine:
             self._run_unit(u0, srcs, P, train, st, keep)
             self._run_unit(u1, [self._act_src(u0)], P, train, st, keep)
         if self.L == 0 and region is not None:          # a one-level network (profiles/inc_block.py): the block ends here
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            self.region_log.append(("inc_forward", region, e))
+            self.region_log.append(("inc_forward", region, self._event()))
         cur = self.enc[self.L][1]
         for j in range(self.L):
             up = self.ups[j]
@@ -439,9 +338,7 @@ class UNetEngine:
                            keep)
             self._run_unit(u1, [self._act_src(u0)], P, train, st, keep)
             cur = u1
-        if self._nbt:
-            L.add_counters(self._nbt, 1)        # one libgsd launch for every BatchNorm layer's counter
-            self._nbt = []
+        self._flush_counters()
         if out is None:
             out = torch.empty((n, self.n_classes, h, w), device=x.device, dtype=torch.float32)
         s = self._act_src(cur)
@@ -456,28 +353,9 @@ class UNetEngine:
         n = u.raw.shape[0]
         lh, lw = self.hs[u.level], self.ws[u.level]
         rows = u.fused_rows if fused else lib.gsd_bn_bwd_partial_rows(n, u.cout, lh, lw)   # fused: of the dX launch (_dgrad_fused)
-        count = float(n * lh * lw)
-        if self.sync_fn is None and rows <= self.one_launch_rows and (dwout is None or not fused):
-            check(lib.gsd_bn_bwd_reduce_finalize(self.partials.data_ptr(), rows, _r64(u.cout) if fused else 0, u.cout,
-                                                 u.sums.data_ptr(), count, G[u.gname].data_ptr(), G[u.bname].data_ptr(),
-                                                 None if dwout is None else dwout.data_ptr(), u.c1.data_ptr(), u.c2.data_ptr(), st),
-                  "bn_bwd_reduce_finalize")
-        else:
-            if fused:
-                check(lib.gsd_bn_reduce_partials(self.partials.data_ptr(), rows, _r64(u.cout), u.cout, u.sums.data_ptr(), st),
-                      "bn_reduce_partials")
-            else:
-                check(lib.gsd_bn_bwd_reduce_partials(self.partials.data_ptr(), rows, u.cout, u.sums.data_ptr(), st),
-                      "bn_bwd_reduce_partials")
-            gsum = None
-            if self.sync_fn is not None:
-                gsum = u.sums[:2 * u.cout].clone()
-                self.sync_fn(gsum)
-                count *= self.world
-            check(lib.gsd_bn_bwd_finalize(u.sums.data_ptr(), L.ptr(gsum), u.cout, count, G[u.gname].data_ptr(),
-                                          G[u.bname].data_ptr(), None if dwout is None else dwout.data_ptr(),
-                                          u.c1.data_ptr(), u.c2.data_ptr(), st),
-                  "bn_bwd_finalize")
+        # the one-launch form takes the output conv's dW row only from stand-alone rows
+        self._bn_bwd_sums(u, rows, _r64(u.cout) if fused else 0, float(n * lh * lw), G, dwout, st,
+                          one_launch=self.sync_fn is None and rows <= self.one_launch_rows and (dwout is None or not fused))
         if self._saved_eval:
             # eval-mode BatchNorm is the affine map raw * scale + shift: d_raw = scale * dz, i.e. the train-mode expression with
             # c1 = c2 = 0 (dgamma = sum dz * xhat and dbeta = sum dz above hold as they are, xhat from the running statistics)
@@ -509,8 +387,7 @@ class UNetEngine:
             lib.gsd_conv3x3_wgrad(u.srcs, len(u.srcs), C.byref(dy), u.cin, u.cout, G[u.wname].data_ptr(), ws.data_ptr(), ws.numel(),
                                   n, lh, lw, sst), "conv3x3_wgrad"))
         if ev0 is not None and not on_side:
-            ev1 = torch.cuda.Event(enable_timing=True)
-            ev1.record()
+            ev1 = self._event()
             form = lib.gsd_conv3x3_wgrad_form(u.srcs, len(u.srcs), C.byref(dy), u.cin, u.cout, n, lh, lw)
             name = ("wgrad3x3_kernel", "wgrad3x3_w43_kernel", "wgrad3x3_w2d_kernel")[form]
             flops = 2.0 * u.cout * u.cin * 9 * n * lh * lw
@@ -519,39 +396,9 @@ class UNetEngine:
         if on_side and turn is not None:
             self.gp_free[turn] = self.side.record_event()
 
-    def _on_side(self, launch) -> bool:
-        """Run launch(stream pointer, workspace tensor) -- one weight-gradient launch -- behind everything issued so far: on the
-        side stream when there is one (True), else on the current stream."""
-        if self.side is None or self.kernel_log is not None:    # (a per-kernel timing pass wants every kernel alone on the chip)
-            launch(L.stream_ptr(), self.wgrad_ws)
-            return False
-        self.side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.side):
-            launch(L.stream_ptr(), self.wgrad_ws_side)
-        return True
-
     def _join_side(self) -> None:
-        if self.side is not None:
-            torch.cuda.current_stream().wait_stream(self.side)
-            self.gp_free = [None, None]
-
-    def _announce(self, tag: str) -> None:
-        """A block of gradients is final once BOTH streams have finished what was issued so far.  The callback (the bucket's
-        all-reduce: RCCL orders itself behind the stream that is current when it is called) therefore runs under a hand-off
-        stream that waits for the two -- the main stream does NOT: the dX chain of the next unit does not depend on this
-        block's weight gradients and used to stall behind them nine times per step."""
-        if self.block_done_cb is None:
-            return
-        if self.side is None or self.kernel_log is not None:
-            self.block_done_cb(tag)
-            return
-        if self._handoff is None:
-            self._handoff = torch.cuda.Stream(device=self.side.device)
-        h = self._handoff
-        h.wait_stream(torch.cuda.current_stream())
-        h.wait_stream(self.side)
-        with torch.cuda.stream(h):
-            self.block_done_cb(tag)
+        super()._join_side()
+        self.gp_free = [None, None]
 
     def _reduce(self, mode: int, u: _Unit, st: int, dpool: Optional[torch.Tensor] = None,
                 dout: Optional[torch.Tensor] = None, wout: Optional[torch.Tensor] = None) -> None:
@@ -603,7 +450,7 @@ class UNetEngine:
         check(lib.gsd_weight_layout(1, P[u.wname].data_ptr(), u.cout, u.cin, u.wt_d.data_ptr(), st), "weight_layout")
         s = L.src_array([L.make_src(u.dsrc)])
         rc = lib.gsd_conv3x3(s, 1, u.wt_d.data_ptr(), u.cout, u.cin, L.dst_array([L.make_dst(dx)]), 1, None, n, lh, lw, st)
-        if rc == GSD_ERR_UNSUPPORTED:
+        if rc == L.GSD_ERR_UNSUPPORTED:
             raise NotImplementedError(f"gelslim_depth_amd.UNet: no kernel computes the input gradient of the first conv3x3 at "
                                       f"N={n} H={lh} W={lw} Cin={u.cin} Cout={u.cout}: "
                                       + lib.gsd_last_error().decode("utf-8", "replace"))
@@ -642,7 +489,7 @@ class UNetEngine:
         # the dX-mode weight layouts (the weights have not changed since the forward)
         self._layouts([(u.form_d.mode_d, P[u.wname], u.cout, u.cin, u.wt_d) for u in self.units if u.need_dgrad] +
                       [(up.mode_d, P[up.wname], up.cout, up.cin, up.wt_d) for up in self.ups], st)
-        last = self.dec[-1][1] if self.L > 0 else self.enc[0][1]
+        last = self._last_unit()
         self._reduce(2, last, st, dout=dout, wout=P["outc.conv.weight"])
         check(lib.gsd_sum_planes(dout.data_ptr(), n, self.n_classes, dout.shape[2] * dout.shape[3],
                                  G["outc.conv.bias"].data_ptr(), self.wgrad_ws.data_ptr(), st), "sum_planes")

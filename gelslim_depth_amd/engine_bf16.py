@@ -22,15 +22,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib as L
 from ._lib import lib, check
+from .engine_base import BN_EPS, ConvUnit, EngineBase, UpUnit
 
-BN_EPS = 1e-5
-BN_MOMENTUM = 0.1
 T3Y = [t // 3 - 1 for t in range(9)]
 T3X = [t % 3 - 1 for t in range(9)]
 
@@ -39,38 +38,23 @@ def _r32(c: int) -> int:
     return (c + 31) // 32 * 32
 
 
-class _Unit:
-    """conv3x3(no bias) + BatchNorm2d + ReLU (unet.py:11-13 / :14-16)."""
+_Up = UpUnit       # the transposed convolutions need no field of their own here
 
+
+class _Unit(ConvUnit):
     def __init__(self, prefix: str, conv_idx: int, bn_idx: int, cin: int, cout: int, level: int):
-        self.cin, self.cout, self.level = cin, cout, level
-        self.wname = f"{prefix}.double_conv.{conv_idx}.weight"
-        bn = f"{prefix}.double_conv.{bn_idx}."
-        self.gname, self.bname = bn + "weight", bn + "bias"
-        self.rmname, self.rvname, self.nbtname = bn + "running_mean", bn + "running_var", bn + "num_batches_tracked"
+        super().__init__(prefix, conv_idx, bn_idx, cin, cout, level)
         self.first = False          # the im2col'd first layer
-        self.need_dgrad = True
-        self.wt_f = self.wt_d = None
-        self.scale = self.shift = self.mean = self.invstd = self.c1 = self.c2 = self.sums = None
-        self.fused_rows = 0         # partial rows written by the dX launch whose epilogue did pass 1 of this unit's BatchNorm backward
-        self.y = self.g = None      # (N,H,W,Cout) bf16
+        self.y = None               # (N,H,W,Cout) bf16, as g
         self.a = None               # gsd_nhwc view of the activation (own tensor or a slice of a concat buffer)
         self.a_t = None             # tensor backing `a`
         self.a_off = 0
         self.src = None             # (tensor, c_off, c_len) of the unit's input, kept for the weight gradient
 
 
-class _Up:
-    """ConvTranspose2d(cin, cin//2, 2, 2) (unet.py:36)."""
-
-    def __init__(self, j: int, cin: int, level_in: int):
-        self.j, self.cin, self.cout, self.level_in = j, cin, cin // 2, level_in
-        self.wname, self.bname = f"up.{j}.up.weight", f"up.{j}.up.bias"
-        self.wt_f = self.wt_d = None
-
-
-class UNetEngineBF16:
+class UNetEngineBF16(EngineBase):
     precision = "bf16"
+    Unit, Up = _Unit, _Up
 
     def __init__(self, n_channels: int, n_classes: int, layer_dimensions: Sequence[int]):
         dims = list(layer_dimensions)
@@ -78,35 +62,9 @@ class UNetEngineBF16:
             raise ValueError(f"bf16 path needs layer_dimensions that are multiples of 32 (MFMA k-step), got {dims}")
         if n_classes != 1:
             raise NotImplementedError("bf16 path implements n_classes == 1 (what every reference config uses)")
-        self.n_channels, self.n_classes, self.dims = n_channels, n_classes, dims
-        self.L = len(dims) - 1
-        self.enc: List[Tuple[_Unit, _Unit]] = []
-        self.dec: List[Tuple[_Unit, _Unit]] = []
-        self.ups: List[_Up] = []
-        self.enc.append((_Unit("inc", 0, 1, n_channels, dims[0], 0), _Unit("inc", 3, 4, dims[0], dims[0], 0)))
+        super().__init__(n_channels, n_classes, dims)
         self.enc[0][0].first = True
-        self.enc[0][0].need_dgrad = False
-        for i in range(self.L):
-            p = f"down.{i}.maxpool_conv.1"
-            self.enc.append((_Unit(p, 0, 1, dims[i], dims[i + 1], i + 1), _Unit(p, 3, 4, dims[i + 1], dims[i + 1], i + 1)))
-        for j, i in enumerate(range(self.L, 0, -1)):
-            cin, cout = dims[i], dims[i - 1]
-            if dims[i - 1] + cin // 2 != cin:
-                raise ValueError(f"layer_dimensions {dims}: level {i} needs dims[i-1] + dims[i]//2 == dims[i] "
-                                 "(the reference model fails at torch.cat/conv otherwise)")
-            self.ups.append(_Up(j, cin, i))
-            p = f"up.{j}.conv"
-            self.dec.append((_Unit(p, 0, 1, cin, cout, i - 1), _Unit(p, 3, 4, cout, cout, i - 1)))
-        self.units: List[_Unit] = [u for pair in self.enc for u in pair] + [u for pair in self.dec for u in pair]
-        self._shape = None
-        self.sync_fn: Optional[Callable[[torch.Tensor], None]] = None
-        self.world = 1
         self._saved_train = False
-        self.block_done_cb: Optional[Callable[[str], None]] = None
-        self.guard = None          # non-finite guard of the current step (_lib.make_guard), set by TrainStep per step
-        self.generation = 0        # forwards so far: a backward belongs to exactly one (models/unet.py checks it)
-        self.kernel_log: Optional[list] = None
-        self.region_log: Optional[list] = None     # bench hook: (region name, start event, end event)
 
     # ------------------------------------------------------------------ buffers
     # tuning switches the library re-reads on every call and that change how many partial rows a launch writes: the buffers below
@@ -115,19 +73,13 @@ class UNetEngineBF16:
     _SIZING_ENV = ("GSD_BF16_BN_BLOCKS", "GSD_BF16_CTGEMM", "GSD_BF16_CT_BM", "GSD_BF16_TW", "GSD_BF16_XCD")
 
     def _ensure(self, n: int, h: int, w: int, dev: torch.device, train: bool) -> None:
-        import os
-        key = (n, h, w, str(dev), tuple(os.environ.get(k) for k in self._SIZING_ENV), train)
+        key = (n, h, w, str(dev), self._env_key(), train)
         if self._shape == key:
             return
         if self._shape is not None and self._shape[:5] == key[:5] and not train:
             return                      # eval after train at the same shape: everything needed exists
         self._shape = key
-        hs, ws = [h], [w]
-        for _ in range(self.L):
-            hs.append(hs[-1] // 2)
-            ws.append(ws[-1] // 2)
-        assert hs[-1] >= 1 and ws[-1] >= 1, "input too small for this many max-pools"
-        self.hs, self.ws = hs, ws
+        hs, ws = self._set_pyramid(h, w)
         bf = dict(device=dev, dtype=torch.bfloat16)
         f32 = dict(device=dev, dtype=torch.float32)
         # first layer: straight from x (gsd_bf16_conv3x3_first / gsd_bf16_wgrad_first) where the shape is served, else through the
@@ -183,7 +135,7 @@ class UNetEngineBF16:
                 oy_, ox_ = self._pad_off(li - 1)
                 max_ws = max(max_ws, lib.gsd_bf16_convT_bias_grad_workspace(n, hs[li - 1], ws[li - 1], oy_, ox_, 2 * hs[li], 2 * ws[li], up.cout))
         self.partials = torch.empty((max_part,), **f32)
-        self.wspace = torch.empty((max(max_ws, 64),), **f32) if train else None
+        self.wgrad_ws = torch.empty((max(max_ws, 64),), **f32) if train else None
         # weight gradients on a SIDE stream: dW(u) only needs d_raw(u) and the unit's input, nothing downstream of it waits for
         # it, and it is MFMA-bound while the backward chain it leaves behind alternates with HBM-bound BatchNorm passes (20 % of
         # the bf16 step): the two overlap where neither fills the chip.  Own split-K workspace; joined before a block's
@@ -206,58 +158,35 @@ class UNetEngineBF16:
                         for l in range(self.L)]
         self.side_dw = train and os.environ.get("GSD_BF16_SIDE_DW", "1") != "0"
         self.side = torch.cuda.Stream(device=dev) if self.side_dw else None
-        self.wspace_side = torch.empty((max(max_ws, 64),), **f32) if self.side_dw else None
+        self.wgrad_ws_side = torch.empty((max(max_ws, 64),), **f32) if self.side_dw else None
 
     def _alloc_unit(self, u: _Unit, n: int, dev: torch.device, train: bool) -> None:
         lh, lw = self.hs[u.level], self.ws[u.level]
         bf = dict(device=dev, dtype=torch.bfloat16)
-        f32 = dict(device=dev, dtype=torch.float32)
         if u.y is None or tuple(u.y.shape) != (n, lh, lw, u.cout):
             u.y = torch.empty((n, lh, lw, u.cout), **bf)
             u.g = None
             u.a_t = None
         if train and u.g is None:
             u.g = torch.empty((n, lh, lw, u.cout), **bf)
-        if u.scale is None or u.scale.device != dev:
-            for nm in ("scale", "shift", "mean", "invstd", "c1", "c2"):
-                setattr(u, nm, torch.empty((u.cout,), **f32))
-            u.sums = torch.empty((65 * 3 * u.cout,), device=dev, dtype=torch.float64)
+        if self._alloc_bn(u, dev):
             u.wt_f = torch.empty((lib.gsd_bf16_weight_image_size(2 if u.first else 0, u.cout, u.cin),), **bf)
             u.wt_d = torch.empty((lib.gsd_bf16_weight_image_size(1, u.cout, u.cin),), **bf) if u.need_dgrad else None
 
     # ------------------------------------------------------------------ helpers
-    def _pad_off(self, lvl: int) -> Tuple[int, int]:
-        # F.pad(x1, [dX//2, dX-dX//2, dY//2, dY-dY//2]) (unet.py:43-47)
-        dy = self.hs[lvl] - 2 * self.hs[lvl + 1]
-        dx = self.ws[lvl] - 2 * self.ws[lvl + 1]
-        return dy // 2, dx // 2
-
     def _region_begin(self):
-        if self.region_log is None:
-            return None
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
+        return None if self.region_log is None else self._event()
 
     def _region_end(self, name: str, e0) -> None:
-        if e0 is None:
-            return
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        self.region_log.append((name, e0, e1))
+        if e0 is not None:
+            self.region_log.append((name, e0, self._event()))
 
     def _log(self, name: str, flops: float, sig=None):
         """bench hook: returns a closer that records (name, flops, start, end, shape signature)."""
         if self.kernel_log is None:
             return lambda: None
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-
-        def close():
-            e1 = torch.cuda.Event(enable_timing=True)
-            e1.record()
-            self.kernel_log.append((name, flops, e0, e1, sig))
-        return close
+        e0 = self._event()
+        return lambda: self.kernel_log.append((name, flops, e0, self._event(), sig))
 
     def _run_unit(self, u: _Unit, src: Tuple[torch.Tensor, int, int], P, train: bool, st: int,
                   pool_to: Optional[torch.Tensor] = None) -> None:
@@ -338,27 +267,9 @@ class UNetEngineBF16:
         self._apply(u1, dy1, st, pool_to)
 
     def _finalize_stats(self, u: _Unit, rows: int, count: float, P, st: int) -> None:
-        """self.partials holds `rows` BatchNorm partial rows of unit u's raw output: batch statistics -> (mean, invstd, scale,
-        shift), running statistics, the batch counter."""
-        if self.sync_fn is None:     # a few hundred partial rows: column sums and finalize in ONE launch
-            check(lib.gsd_bn_reduce_finalize(self.partials.data_ptr(), rows, lib.gsd_bf16_conv_mpad(u.cout), u.cout, u.sums.data_ptr(),
-                                             count, P[u.gname].data_ptr(), P[u.bname].data_ptr(), BN_EPS, BN_MOMENTUM,
-                                             P[u.rmname].data_ptr(), P[u.rvname].data_ptr(), u.mean.data_ptr(), u.invstd.data_ptr(),
-                                             u.scale.data_ptr(), u.shift.data_ptr(), self.guard, st), "bn_reduce_finalize")
-        else:                        # SyncBN: the fp64 sums are all-reduced between the two halves
-            check(lib.gsd_bn_reduce_partials(self.partials.data_ptr(), rows, lib.gsd_bf16_conv_mpad(u.cout), u.cout,
-                                             u.sums.data_ptr(), st), "bn_reduce_partials")
-            self.sync_fn(u.sums[:2 * u.cout])
-            count *= self.world
-            check(lib.gsd_bn_finalize(u.sums.data_ptr(), u.cout, count, P[u.gname].data_ptr(), P[u.bname].data_ptr(),
-                                      BN_EPS, BN_MOMENTUM, P[u.rmname].data_ptr(), P[u.rvname].data_ptr(),
-                                      u.mean.data_ptr(), u.invstd.data_ptr(), u.scale.data_ptr(), u.shift.data_ptr(),
-                                      self.guard, st),
-                  "bn_finalize")
-        self._nbt.append(P[u.nbtname])   # int64 counters: one libgsd launch for all of them at the end of the forward
-
-    def _last_unit(self) -> _Unit:
-        return self.dec[-1][1] if self.L > 0 else self.enc[0][1]
+        """EngineBase._bn_stats in this engine's partial-row layout: ONE launch whatever the row count (a few hundred rows),
+        unless SyncBN exchanges the sums in between."""
+        self._bn_stats(u, rows, lib.gsd_bf16_conv_mpad(u.cout), count, P, st, one_launch=self.sync_fn is None)
 
     def _apply(self, u: _Unit, dy, st: int, pool_to: Optional[torch.Tensor]) -> None:
         """train mode: a = relu(bn(y)) (+ the max-pool of a skip unit in the same pass)."""
@@ -374,17 +285,10 @@ class UNetEngineBF16:
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], train: bool, out: Optional[torch.Tensor] = None
                 ) -> torch.Tensor:
-        if x.dtype != torch.float32 or not x.is_cuda:
-            raise L.GsdError("UNetEngineBF16.forward needs a float32 tensor on the GPU (no CPU fallback)")
-        x = x.contiguous()
+        x = self._begin_forward(x, train)
         n, c, h, w = x.shape
-        assert c == self.n_channels, f"expected {self.n_channels} input channels, got {c}"
-        self._ensure(n, h, w, x.device, train)
         st = L.stream_ptr()
         self._saved_train = train
-        self._nbt = []
-        self.generation += 1       # every forward overwrites the saved activations
-        self._x = x
         self._prepare_weight_images(P, train)
         region = self._region_begin()         # bench hook: the `inc` double-conv forward (2 convs, BN statistics + apply)
         if not self.first_direct:
@@ -426,9 +330,7 @@ class UNetEngineBF16:
             self._run_unit(u0, (self.cat[lvl], 0, u0.cin), P, train, st)
             self._run_unit(u1, (u0.a_t, u0.a_off, u0.cout), P, train, st)
             cur = u1
-        if self._nbt:
-            L.add_counters(self._nbt, 1)
-            self._nbt = []
+        self._flush_counters()
         if out is None:
             out = torch.empty((n, self.n_classes, h, w), device=x.device, dtype=torch.float32)
         if train and self.fused_out:
@@ -466,23 +368,8 @@ class UNetEngineBF16:
             check(lib.gsd_bf16_first_bn_bwd_reduce(self._x.data_ptr(), n, u.cin, lh, lw, u.wt_f.data_ptr(), C.byref(da), u.scale.data_ptr(),
                                                    u.shift.data_ptr(), u.mean.data_ptr(), u.invstd.data_ptr(), self.partials.data_ptr(), st),
                   "first_bn_bwd_reduce")
-        dw_ptr = None if dwout is None else dwout.data_ptr()
-        if self.sync_fn is None:
-            check(lib.gsd_bn_bwd_reduce_finalize(self.partials.data_ptr(), rows, lib.gsd_bf16_conv_mpad(u.cout) if fused else 0, u.cout,
-                                                 u.sums.data_ptr(), count, G[u.gname].data_ptr(), G[u.bname].data_ptr(), dw_ptr,
-                                                 u.c1.data_ptr(), u.c2.data_ptr(), st), "bn_bwd_reduce_finalize")
-        else:
-            if fused:
-                check(lib.gsd_bn_reduce_partials(self.partials.data_ptr(), rows, lib.gsd_bf16_conv_mpad(u.cout), u.cout,
-                                                 u.sums.data_ptr(), st), "bn_reduce_partials")
-            else:
-                check(lib.gsd_bn_bwd_reduce_partials(self.partials.data_ptr(), rows, u.cout, u.sums.data_ptr(), st),
-                      "bn_bwd_reduce_partials")
-            gsum = u.sums[:2 * u.cout].clone()
-            self.sync_fn(gsum)
-            count *= self.world
-            check(lib.gsd_bn_bwd_finalize(u.sums.data_ptr(), gsum.data_ptr(), u.cout, count, G[u.gname].data_ptr(),
-                                          G[u.bname].data_ptr(), dw_ptr, u.c1.data_ptr(), u.c2.data_ptr(), st), "bn_bwd_finalize")
+        self._bn_bwd_sums(u, rows, lib.gsd_bf16_conv_mpad(u.cout) if fused else 0, count, G, dwout, st,
+                          one_launch=self.sync_fn is None)
         dz, dy = L.make_nhwc(u.g), L.make_nhwc(u.y)
         if recompute:
             def launch(sst, ws):
@@ -555,35 +442,6 @@ class UNetEngineBF16:
             arr[i].w, arr[i].out, arr[i].mode, arr[i].Cout, arr[i].Cin = w.data_ptr(), buf.data_ptr(), mode, cout, cin
         check(lib.gsd_bf16_weight_images(arr, len(jobs), L.stream_ptr()), "weight_images")
 
-    def _on_side(self, launch) -> None:
-        """Run launch(stream pointer, workspace tensor) -- one weight-gradient launch -- behind everything issued so far, on the
-        side stream when there is one."""
-        if not self.side_dw or self.kernel_log is not None:   # (a per-kernel timing pass wants every kernel alone on the chip)
-            launch(L.stream_ptr(), self.wspace)
-            return
-        self.side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.side):
-            launch(L.stream_ptr(), self.wspace_side)
-
-    def _join_side(self) -> None:
-        if self.side_dw:
-            torch.cuda.current_stream().wait_stream(self.side)
-
-    def _announce(self, tag: str) -> None:
-        """As engine.UNetEngine._announce: the bucket's all-reduce is called under a hand-off stream that waits for the main and
-        the side stream; the main stream (the dX chain) does not wait for the weight gradients."""
-        if self.block_done_cb is None:
-            return
-        if not self.side_dw or self.kernel_log is not None:
-            self.block_done_cb(tag)
-            return
-        if getattr(self, "_handoff", None) is None:
-            self._handoff = torch.cuda.Stream(device=self.side.device)
-        self._handoff.wait_stream(torch.cuda.current_stream())
-        self._handoff.wait_stream(self.side)
-        with torch.cuda.stream(self._handoff):
-            self.block_done_cb(tag)
-
     def _bnbwd(self, tgt: _Unit):
         """gsd_bf16_bnbwd for fusing pass 1 of tgt's BatchNorm+ReLU backward into the dX launch that produces tgt.g."""
         yv = L.make_nhwc(tgt.y)
@@ -623,10 +481,10 @@ class UNetEngineBF16:
         dout = dout.contiguous()
         st = L.stream_ptr()
         n = dout.shape[0]
-        last = self.dec[-1][1] if self.L > 0 else self.enc[0][1]
+        last = self._last_unit()
         self._reduce(2, last, st, dout=dout, wout=P["outc.conv.weight"])
         check(lib.gsd_sum_planes(dout.data_ptr(), n, self.n_classes, dout.shape[2] * dout.shape[3], G["outc.conv.bias"].data_ptr(),
-                                 self.wspace.data_ptr(), st), "sum_planes")
+                                 self.wgrad_ws.data_ptr(), st), "sum_planes")
         dwout = G["outc.conv.weight"]
         prev_fused = None           # unit whose pass-1 sums came from the transposed convolution's dX epilogue
         for j in reversed(range(self.L)):

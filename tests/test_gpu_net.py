@@ -329,7 +329,7 @@ def test_winograd_and_direct_forms_agree(monkeypatch):
 
 @pytest.mark.parametrize("dims,n,h,w", [([16, 32, 64, 128], 3, 72, 101), ([64, 128, 256], 2, 80, 107)])
 def test_side_stream_weight_gradients_are_bit_identical(monkeypatch, dims, n, h, w):
-    """The weight-gradient launches run on a side stream next to the dX chain (engine.py: _on_side; two d_raw scratch buffers used
+    """The weight-gradient launches run on a side stream next to the dX chain (engine_base.py: _on_side; two d_raw scratch buffers used
     in turn).  Same kernels on the same operands: every gradient must equal the single-stream schedule's bit for bit, over several
     steps (a missing dependency between the streams shows up as a difference here)."""
     from gelslim_depth_amd.train import mse_loss
