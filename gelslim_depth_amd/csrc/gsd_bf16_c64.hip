@@ -341,14 +341,7 @@ int c64_launch(C64P& P, size_t lds, void* stream, const char* what) {
   P.ntiles = (int)nt;
   const int cus = c64_cu_count();
   const int grid = (int)(nt < cus ? nt : cus);
-  static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&conv64_bf16_kernel<EP, TH>)); e != hipSuccess) {
-    gsd_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  hipLaunchKernelGGL((conv64_bf16_kernel<EP, TH>), dim3(grid), dim3(512), lds, (hipStream_t)stream, P);
-  GSD_LAUNCH_CHECK(what);
-  return GSD_OK;
+  return gsd_launch<conv64_bf16_kernel<EP, TH>>(what, dim3(grid), dim3(512), lds, (hipStream_t)stream, P);
 }
 
 int c64_common(C64P& P, const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, float* partials, const char* what) {

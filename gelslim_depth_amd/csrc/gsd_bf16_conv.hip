@@ -579,16 +579,8 @@ int launch(GConvP& P, long items, size_t lds, hipStream_t st, const char* what) 
   P.nitems = (int)items;
   const long grid = launch_grid(items, P.mblocks);
   P.xcd = (gsd_env_int("GSD_BF16_XCD", 1) != 0 && grid % 8 == 0 && (grid / 8) % P.mblocks == 0) ? 1 : 0;
-  static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&gconv_bf16_kernel<MODE, WM, WN, BUF>)); e != hipSuccess) {
-    gsd_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
   GSD_REQUIRE(grid > 0 && grid < 2147483647L, GSD_ERR_UNSUPPORTED, "%s: grid %ld out of range", what, grid);
-  GSD_REQUIRE(lds <= 160 * 1024, GSD_ERR_UNSUPPORTED, "%s: LDS %zu B too large", what, lds);
-  hipLaunchKernelGGL((gconv_bf16_kernel<MODE, WM, WN, BUF>), dim3((unsigned)grid), dim3(256), lds, st, P);
-  GSD_LAUNCH_CHECK(what);
-  return GSD_OK;
+  return gsd_launch<gconv_bf16_kernel<MODE, WM, WN, BUF>>(what, dim3((unsigned)grid), dim3(256), lds, st, P);
 }
 
 }  // namespace

@@ -404,15 +404,7 @@ template <int DX, int WM, int WN, int NT>
 int launch_ct(const CtP& P, int grid, hipStream_t st) {
   constexpr int BM = WM * 64, NPX = WN * NT * 16;
   const size_t lds = (size_t)2 * (BM + NPX) * 128 + (size_t)(4 * BM + 8 * 128) * sizeof(float);
-  static gsd_attr_once big_lds;
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&ctgemm_bf16_kernel<DX, WM, WN, NT>)); e != hipSuccess) {
-    gsd_set_error("gsd_bf16_conv_dense (large tile): hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  GSD_REQUIRE(lds <= 160 * 1024, GSD_ERR_UNSUPPORTED, "gsd_bf16_conv_dense (large tile): LDS %zu B too large", lds);
-  hipLaunchKernelGGL((ctgemm_bf16_kernel<DX, WM, WN, NT>), dim3((unsigned)grid), dim3(512), lds, st, P);
-  GSD_LAUNCH_CHECK("gsd_bf16_conv_dense (large tile)");
-  return GSD_OK;
+  return gsd_launch<ctgemm_bf16_kernel<DX, WM, WN, NT>>("gsd_bf16_conv_dense (large tile)", dim3((unsigned)grid), dim3(512), lds, st, P);
 }
 
 }  // namespace

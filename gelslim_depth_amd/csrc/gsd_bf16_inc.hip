@@ -430,12 +430,5 @@ extern "C" int gsd_bf16_inc_conv(const float* x, int N, int C, int H, int W, con
   GSD_REQUIRE(nt < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_bf16_inc_conv: too many tiles");
   P.ntiles = (int)nt;
   const int grid = gsd_bf16_inc_conv_partial_rows(N, H, W);
-  static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&inc_fused_bf16_kernel<INC_TH>)); e != hipSuccess) {
-    gsd_set_error("gsd_bf16_inc_conv: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  hipLaunchKernelGGL(inc_fused_bf16_kernel<INC_TH>, dim3(grid), dim3(512), IncGeo<INC_TH>::LDS, (hipStream_t)stream, P);
-  GSD_LAUNCH_CHECK("gsd_bf16_inc_conv");
-  return GSD_OK;
+  return gsd_launch<inc_fused_bf16_kernel<INC_TH>>("gsd_bf16_inc_conv", dim3(grid), dim3(512), IncGeo<INC_TH>::LDS, (hipStream_t)stream, P);
 }

@@ -541,15 +541,7 @@ WPlan make_wplan(bool halo, int T, int N, int H, int W, int M, int Ncols) {
 
 template <int HALO, int TT, int WM, int WN>
 int launch_w(const GWgradP& P, int grid, size_t lds, hipStream_t st, const char* what) {
-  static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&gwgrad_bf16_kernel<HALO, TT, WM, WN>)); e != hipSuccess) {
-    gsd_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  GSD_REQUIRE(lds <= 160 * 1024, GSD_ERR_UNSUPPORTED, "%s: LDS %zu B too large", what, lds);
-  hipLaunchKernelGGL((gwgrad_bf16_kernel<HALO, TT, WM, WN>), dim3(grid), dim3(256), lds, st, P);
-  GSD_LAUNCH_CHECK(what);
-  return GSD_OK;
+  return gsd_launch<gwgrad_bf16_kernel<HALO, TT, WM, WN>>(what, dim3(grid), dim3(256), lds, st, P);
 }
 
 }  // namespace
@@ -588,15 +580,7 @@ template <int WM, int WN>
 int launch_big(const GWBigP& P, int grid, hipStream_t st) {
   constexpr int BM = WM * 64;
   constexpr size_t img = ((size_t)(64 * (BM * 2 + 32) + 1023) / 1024 + (size_t)(4 * 64 * (64 * 2 + 32) + 1023) / 1024) * 1024;
-  static gsd_attr_once big_lds;
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&gwgrad_big_bf16_kernel<WM, WN>)); e != hipSuccess) {
-    gsd_set_error("gsd_bf16_wgrad (large tile): hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  GSD_REQUIRE(2 * img + 512 <= 160 * 1024, GSD_ERR_UNSUPPORTED, "gsd_bf16_wgrad (large tile): LDS %zu B too large", 2 * img + 512);
-  hipLaunchKernelGGL((gwgrad_big_bf16_kernel<WM, WN>), dim3(grid), dim3(512), 2 * img + 512, st, P);
-  GSD_LAUNCH_CHECK("gsd_bf16_wgrad (large tile)");
-  return GSD_OK;
+  return gsd_launch<gwgrad_big_bf16_kernel<WM, WN>>("gsd_bf16_wgrad (large tile)", dim3(grid), dim3(512), 2 * img + 512, st, P);
 }
 
 }  // namespace

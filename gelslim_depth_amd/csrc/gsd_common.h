@@ -164,6 +164,21 @@ static inline hipError_t gsd_allow_big_lds(gsd_attr_once& once, const void* fn, 
   if (e == hipSuccess && dev < 64) once.mask.fetch_or(bit, std::memory_order_relaxed);
   return e;
 }
+// Launch of a kernel whose dynamic LDS may exceed the 64 KiB a kernel gets without the attribute: allow it (the instantiation's
+// own once-per-device cache: one per kernel), launch, check.  `what` names the entry point in the error strings.  Kernels that
+// never ask for more are launched with hipLaunchKernelGGL + GSD_LAUNCH_CHECK and have no attribute set.
+template <auto Kernel, class... Args>
+int gsd_launch(const char* what, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  static gsd_attr_once big_lds;
+  GSD_REQUIRE(lds <= 160 * 1024, GSD_ERR_UNSUPPORTED, "%s: LDS image %zu B too large", what, lds);
+  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(Kernel)); e != hipSuccess) {
+    gsd_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
+    return GSD_ERR_HIP;
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+  GSD_LAUNCH_CHECK(what);
+  return GSD_OK;
+}
 // Tuning knobs are read from the environment on EVERY call (no cached statics: a test or an A/B harness may change them
 // inside one process, and the library keeps no mutable state that a result depends on).
 static inline int gsd_env_int(const char* name, int dflt) {

@@ -16,7 +16,7 @@
 //
 // Pixels sit on the MFMA column (lane&15): one accumulator register = 16 consecutive floats of an NCHW row.
 // Wave tile 64 (m) x 64 (pixels) = 4x4 MFMA tiles; block = 4 waves: 64x256 for M <= 64, 128x128 otherwise.
-#include "gsd_common.h"
+#include "gsd_conv3x3_host.h"
 
 #include <cstdlib>
 
@@ -382,18 +382,6 @@ ConvPlan plan_conv3x3(int H, int W, int M) {
   return p;
 }
 
-template <int WM, int WN>
-int launch(const Conv3Params& P, int grid, size_t lds, hipStream_t st) {
-  static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&conv3x3_dma_kernel<WM, WN>)); e != hipSuccess) {
-    gsd_set_error("gsd_conv3x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  hipLaunchKernelGGL((conv3x3_dma_kernel<WM, WN>), dim3(grid), dim3(256), lds, st, P);
-  GSD_LAUNCH_CHECK("gsd_conv3x3");
-  return GSD_OK;
-}
-
 }  // namespace
 
 extern "C" int gsd_conv3x3_partial_rows(int N, int H, int W, int Cout) {
@@ -405,10 +393,8 @@ extern "C" int gsd_conv3x3_partial_rows(int N, int H, int W, int Cout) {
 // Which conv3x3 kernel serves this shape: 0 = direct taps (this file), 1 = Winograd F(4,3) along rows (gsd_conv3x3_w43.hip).
 // Both count MFMA instructions per launch including tile padding; the Winograd form wins when it needs clearly fewer
 // (ideal: half; measured x1.3-1.7 on the U-Net's layers, profiles/bench_conv_forms.py).  GSD_CONV_ALGO=0|1 forces one.
-extern "C" int64_t gsd_conv3x3_w43_mfma_count(int N, int H, int W, int Cin, int Cout);
 extern "C" int gsd_conv3x3_algo(int N, int H, int W, int Cin, int Cout) {
-  const char* env = getenv("GSD_CONV_ALGO");   // read per call: the tests switch forms inside one process
-  const int forced = env ? atoi(env) : -1;
+  const int forced = gsd_env_int("GSD_CONV_ALGO", -1);
   if (forced == 0 || forced == 1) return forced;
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
   if (Cin < 16) return 0;   // a K loop of 1-3 chunks is all prologue + epilogue, and the Winograd epilogue is the longer one
@@ -419,44 +405,13 @@ extern "C" int gsd_conv3x3_algo(int N, int H, int W, int Cin, int Cout) {
 }
 
 static int conv3x3_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst,
-                        float* partials, const float* bw_raw, const float* bw_scale, const float* bw_shift,
-                        const float* bw_mean, const float* bw_invstd, int N, int H, int W, void* stream) {
-  GSD_REQUIRE(src && dst && wt, GSD_ERR_BAD_ARG, "gsd_conv3x3: null argument");
-  GSD_REQUIRE(nsrc >= 1 && nsrc <= 2 && ndst >= 1 && ndst <= 2, GSD_ERR_BAD_ARG, "gsd_conv3x3: nsrc/ndst must be 1 or 2");
-  GSD_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, GSD_ERR_BAD_ARG, "gsd_conv3x3: bad sizes");
-  GSD_REQUIRE(H < 32768 && W < 32768, GSD_ERR_UNSUPPORTED, "gsd_conv3x3: H, W must be < 32768");
-  GSD_REQUIRE(((uintptr_t)wt & 15) == 0, GSD_ERR_BAD_ARG, "gsd_conv3x3: weight layout must be 16-byte aligned");
-  int csum = 0;
-  for (int i = 0; i < nsrc; ++i) {
-    if (int e = gsd_check_src(src[i], "gsd_conv3x3 src")) return e;
-    GSD_REQUIRE(src[i].scale == nullptr || src[i].relu != 0, GSD_ERR_UNSUPPORTED,
-                "gsd_conv3x3: an affine source segment must also have relu (zero padding uses a NaN sentinel)");
-    GSD_REQUIRE((int64_t)src[i].H * src[i].W < (1LL << 31), GSD_ERR_UNSUPPORTED, "gsd_conv3x3: plane too large");
-    csum += src[i].C;
-  }
-  GSD_REQUIRE(csum == Cin, GSD_ERR_BAD_ARG, "gsd_conv3x3: source segments hold %d channels, Cin=%d", csum, Cin);
-  csum = 0;
-  for (int i = 0; i < ndst; ++i) {
-    if (int e = gsd_check_dst(dst[i], "gsd_conv3x3 dst", true)) return e;   // the epilogue addresses rows through w_stride
-    csum += dst[i].C;
-  }
-  GSD_REQUIRE(csum == Cout, GSD_ERR_BAD_ARG, "gsd_conv3x3: destination segments hold %d channels, Cout=%d", csum, Cout);
+                        float* partials, const Conv3Bw& bw, int N, int H, int W, void* stream) {
+  if (int e = conv3_check_operands("gsd_conv3x3", false, false, src, nsrc, wt, Cin, Cout, dst, ndst, N, H, W)) return e;
 
   ConvPlan pl = plan_conv3x3(H, W, Cout);
   Conv3Params P;
-  P.src0 = to_srcd(src[0]);
-  P.src1 = nsrc > 1 ? to_srcd(src[1]) : null_srcd();
-  P.dst0 = to_dstd(dst[0]);
-  P.dst1 = ndst > 1 ? to_dstd(dst[1]) : null_dstd();
-  P.wt = wt;
-  P.partials = partials;
-  P.bw_raw = bw_raw; P.bw_scale = bw_scale; P.bw_shift = bw_shift; P.bw_mean = bw_mean; P.bw_invstd = bw_invstd;
-  P.Cin = Cin;
-  P.Cout = Cout;
-  P.Mpad = round_up(Cout, 64);
-  P.nchunks = ceil_div(Cin, 4);
+  conv3_fill_common(P, src, nsrc, wt, Cin, Cout, dst, ndst, partials, bw, N, H, W);
   P.mblocks = pl.mblocks;
-  P.N = N; P.H = H; P.W = W;
   P.TH = pl.TH; P.TW = pl.TW; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;
   P.WR = pl.TH + 2; P.WC = pl.TW + 2;
   P.PS = plane_stride_16mod32(P.WR * P.WC);
@@ -465,22 +420,19 @@ static int conv3x3_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, 
   const long grid = (long)N * pl.tiles_y * pl.tiles_x * pl.mblocks;
   GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_conv3x3: grid too large");
   const size_t lds = (size_t)(2 * (36 * pl.BM + 4 * P.PS) + 2 * 4 * P.nchunks + 4 * pl.BM) * sizeof(float);   // 2 tile images + BN coefficients (input side, output side)
-  if (pl.wide) return launch<1, 4>(P, (int)grid, lds, (hipStream_t)stream);
-  return launch<2, 2>(P, (int)grid, lds, (hipStream_t)stream);
+  if (pl.wide) return gsd_launch<conv3x3_dma_kernel<1, 4>>("gsd_conv3x3", dim3((int)grid), dim3(256), lds, (hipStream_t)stream, P);
+  return gsd_launch<conv3x3_dma_kernel<2, 2>>("gsd_conv3x3", dim3((int)grid), dim3(256), lds, (hipStream_t)stream, P);
 }
 
 extern "C" int gsd_conv3x3(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst,
                            int ndst, float* partials, int N, int H, int W, void* stream) {
-  return conv3x3_impl(src, nsrc, wt, Cin, Cout, dst, ndst, partials, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W,
-                      stream);
+  return conv3x3_impl(src, nsrc, wt, Cin, Cout, dst, ndst, partials, Conv3Bw{}, N, H, W, stream);
 }
 
 extern "C" int gsd_conv3x3_dgrad_bnrelu(const gsd_src* src, const float* wt, int Cin, int Cout, const gsd_dst* dst,
                                         const float* raw, const float* scale, const float* shift, const float* mean,
                                         const float* invstd, float* partials, int N, int H, int W, void* stream) {
-  GSD_REQUIRE(dst && raw && scale && shift && mean && invstd && partials, GSD_ERR_BAD_ARG,
-              "gsd_conv3x3_dgrad_bnrelu: null argument");
-  GSD_REQUIRE(dst->C == Cout && dst->H == H && dst->W == W && dst->off_h == 0 && dst->off_w == 0, GSD_ERR_BAD_ARG,
-              "gsd_conv3x3_dgrad_bnrelu: dst must be the full (Cout,H,W) gradient buffer (raw shares its strides)");
-  return conv3x3_impl(src, 1, wt, Cin, Cout, dst, 1, partials, raw, scale, shift, mean, invstd, N, H, W, stream);
+  const Conv3Bw bw{raw, scale, shift, mean, invstd};
+  if (int e = conv3_check_dgrad_bnrelu("gsd_conv3x3_dgrad_bnrelu", dst, bw, partials, Cout, H, W)) return e;
+  return conv3x3_impl(src, 1, wt, Cin, Cout, dst, 1, partials, bw, N, H, W, stream);
 }

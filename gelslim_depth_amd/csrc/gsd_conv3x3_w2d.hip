@@ -29,7 +29,7 @@
 // and the output transform on PAIRS of floats (packed fp32 instructions, bit-identical to the scalar form); the chunk loop unrolled
 // by two so that the LDS image offsets are instruction immediates; 16-byte halo pieces wherever the source admits them (HM);
 // plane offsets of the epilogue as scalar arithmetic.  K slabs (SPLIT) for the launches that would leave the chip idle.
-#include "gsd_common.h"
+#include "gsd_conv3x3_host.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -770,52 +770,6 @@ struct W2DPlan {
   int TH, TW, TWq, tiles_y, tiles_x, mblocks, WR, WC, WCp, PS;
 };
 
-// LDS bank cost of the consumers' halo reads (one ds_read_b128 + one ds_read_b64 per window row; a lane's tile rows are 2 apart):
-// sum over the two pixel halves of the LDS cycles per read pair.
-int w2d_read_cycles(int TWq, int LP, int PS) {
-  static const int g128[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
-                                  {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
-  int total = 0;
-  for (int ph = 0; ph < NWP; ++ph) {
-    int addr[64];
-    for (int lane = 0; lane < 64; ++lane) {
-      const int q = ph * 16 + (lane & 15);
-      addr[lane] = (lane >> 4) * PS + 2 * (q / TWq) * LP + 4 * (q % TWq);
-    }
-    for (int half = 0; half < 2; ++half) {
-      for (int g = 0; g < 2; ++g) {   // ds_read_b128: 16-lane groups, 16 slots of 16 B
-        int worst = 0;
-        for (int slot = 0; slot < 16; ++slot) {
-          int distinct = 0, seen[16];
-          for (int i = 0; i < 16; ++i) {
-            const int a = addr[g128[g][i] + 32 * half];
-            if ((a / 4) % 16 != slot) continue;
-            bool dup = false;
-            for (int k = 0; k < distinct; ++k) dup = dup || seen[k] == a;
-            if (!dup) seen[distinct++] = a;
-          }
-          worst = distinct > worst ? distinct : worst;
-        }
-        total += worst;
-      }
-      int worst = 0;   // ds_read_b64 at +4 floats: 32-lane halves, 32 slots of 8 B
-      for (int slot = 0; slot < 32; ++slot) {
-        int distinct = 0, seen[32];
-        for (int i = 0; i < 32; ++i) {
-          const int a = addr[i + 32 * half] + 4;
-          if ((a / 2) % 32 != slot) continue;
-          bool dup = false;
-          for (int k = 0; k < distinct; ++k) dup = dup || seen[k] == a;
-          if (!dup) seen[distinct++] = a;
-        }
-        worst = distinct > worst ? distinct : worst;
-      }
-      total += worst;
-    }
-  }
-  return total;
-}
-
 // TH x TW output tile of 16 NWP two-row Winograd tiles (256 pixels) whose padded halo window fits the 128 NW DMA positions:
 // fewest blocks; among equals 32-wide rows, then the widest.  The LDS row pitch and plane stride are the ones with the fewest
 // bank conflicts.
@@ -868,7 +822,7 @@ bool plan_w2d(int N, int H, int W, int M, W2DPlan* best) {
   int bc = -1;
   for (int c = wcp0; c <= wcp0 + 12 && (th + 2) * c <= maxpos; c += 4)
     for (int ps = round_up((th + 2) * c, 4) + 4; ps < round_up((th + 2) * c, 4) + 4 + 36; ps += 4) {
-      const int cyc = w2d_read_cycles(best->TWq, c, ps);
+      const int cyc = conv3_halo_read_cycles(NWP, 2, best->TWq, c, ps, 0);
       if (bc < 0 || cyc < bc) {
         bc = cyc;
         best->WCp = c;
@@ -891,7 +845,7 @@ int w2d_x4_plane_stride(int TWq, int WCp, int WR) {
   }
   int best = -1, ps_best = WR * WCp + 4;
   for (int ps = WR * WCp + 4; ps < WR * WCp + 4 + 68; ps += 4) {
-    const int c = w2d_read_cycles(TWq, WCp, ps);
+    const int c = conv3_halo_read_cycles(NWP, 2, TWq, WCp, ps, 0);
     if (best < 0 || c < best) {
       best = c;
       ps_best = ps;
@@ -903,15 +857,7 @@ int w2d_x4_plane_stride(int TWq, int WCp, int WR) {
 
 template <bool PLAIN, int HM = 0, bool SPLIT = false>
 int launch_w2d(const W2DParams& P, int grid, size_t lds, hipStream_t st) {
-  static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  const void* fn = reinterpret_cast<const void*>(&conv3x3_w2d_kernel<PLAIN, HM, SPLIT>);
-  if (hipError_t e = gsd_allow_big_lds(big_lds, fn); e != hipSuccess) {
-    gsd_set_error("gsd_conv3x3_w2d: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  GSD_REQUIRE(lds <= 160 * 1024, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w2d: LDS image %zu B too large", lds);
-  hipLaunchKernelGGL((conv3x3_w2d_kernel<PLAIN, HM, SPLIT>), dim3(grid), dim3(128 * NWP), lds, st, P);
-  GSD_LAUNCH_CHECK("gsd_conv3x3_w2d");
+  if (int e = gsd_launch<conv3x3_w2d_kernel<PLAIN, HM, SPLIT>>("gsd_conv3x3_w2d", dim3(grid), dim3(128 * NWP), lds, st, P)) return e;
   if constexpr (SPLIT) {
     hipLaunchKernelGGL(w2d_slab_reduce_kernel, dim3(grid / P.nslab), dim3(128 * NWP), 0, st, P);
     GSD_LAUNCH_CHECK("gsd_conv3x3_w2d (slab sums)");
@@ -919,34 +865,11 @@ int launch_w2d(const W2DParams& P, int grid, size_t lds, hipStream_t st) {
   return GSD_OK;
 }
 
-// Modelled run time in microseconds of a launch of `base` (tile, m-block) blocks of `nchunks` chunks cut into S slabs: a CU with
-// k = ceil(blocks / 256) blocks runs pairs at 2.07 us per chunk and block (+ 5 us per block) and an odd last block at 0.66 of that;
-// the slab sums cost 12 us + the slabs' bytes at 6 TB/s (the constants of gsd_conv3x3_w43.hip's model, the kernel's own rate).
-double w2d_time_us(long base, int nchunks, int S, bool bw) {
-  const long cus = gsd_cu_count();
-  const long k = (base * S + cus - 1) / cus;
-  const double cu = (double)(k / 2) + (k & 1 ? 0.66 : 0.0);
-  double t = cu * (2.07 * nchunks / S + 5.0);
-  if (S > 1) t += 12.0 + (double)(S + 1 + (bw ? 1 : 0)) * base * 65536.0 / 6.0e6;
-  return t;
-}
-
-// GSD_W2D_SPLIT: 0 / 1 never, S >= 2 that many slabs (tuning); default: what the model picks (a split has to buy 3 %)
-int w2d_pick_slabs(long base, int nchunks, bool bw) {
-  const int forced = gsd_env_int("GSD_W2D_SPLIT", -1);
-  if (forced == 0 || forced == 1) return 1;
-  int best = 1;
-  double tb = w2d_time_us(base, nchunks, 1, bw) * (forced > 1 ? 1e9 : 0.97);
-  for (int S = 2; S <= 8 && nchunks / S >= 8; ++S) {
-    if (forced > 1 && S != forced) continue;
-    const double t = w2d_time_us(base, nchunks, S, bw);
-    if (t < tb) {
-      tb = t;
-      best = S;
-    }
-  }
-  return best;
-}
+// The K-slab model (gsd_conv3x3_host.h) at this kernel's own rate: pairs of blocks at 2.07 us per chunk and block (+ 5 us per
+// block), an odd last block at 0.66 of that (the per-block cost and the lone-block factor fitted to profiles/r05_w2d_vs_w43.txt:
+// the 20 x 26 and 40 x 53 layers at batch 8, where k is 1-3); the slab sums cost what the row form's do.  GSD_W2D_SPLIT: 0 / 1
+// never, S >= 2 that many slabs (tuning).
+constexpr Conv3SlabModel w2d_slabs = {2.07, 5.0, 0.66, "GSD_W2D_SPLIT"};
 
 }  // namespace
 
@@ -969,14 +892,12 @@ extern "C" int64_t gsd_conv3x3_w2d_mfma_count(int N, int H, int W, int Cin, int 
   return (int64_t)N * p.tiles_y * p.tiles_x * p.mblocks * ceil_div(Cin, 4) * (2 * NWP * 48);
 }
 
-// Modelled run time of the launch in microseconds, as gsd_conv3x3_w43_estimate_us: a CU with k = ceil(blocks / 256) blocks runs
-// pairs at 2.17 us per chunk and block (+ 5 us per block) and an odd last block at 0.66 of that (fitted to
-// profiles/r05_w2d_vs_w43.txt: the 20 x 26 and 40 x 53 layers at batch 8, where k is 1-3).
+// Modelled run time of the launch in microseconds, as gsd_conv3x3_w43_estimate_us
 extern "C" double gsd_conv3x3_w2d_estimate_us(int N, int H, int W, int Cin, int Cout) {
   W2DPlan p;
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !plan_w2d(N, H, W, Cout, &p)) return 0.0;
   const long blocks = (long)N * p.tiles_y * p.tiles_x * p.mblocks;
-  return w2d_time_us(blocks, ceil_div(Cin, 4), 1, false);
+  return w2d_slabs.time_us(blocks, ceil_div(Cin, 4), 1, false);
 }
 
 // ... with the K-slab form where it pays (train mode with a workspace: what the engine's launches run)
@@ -984,7 +905,7 @@ extern "C" double gsd_conv3x3_w2d_estimate_slabs_us(int N, int H, int W, int Cin
   W2DPlan p;
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !plan_w2d(N, H, W, Cout, &p)) return 0.0;
   const long blocks = (long)N * p.tiles_y * p.tiles_x * p.mblocks;
-  return w2d_time_us(blocks, ceil_div(Cin, 4), w2d_pick_slabs(blocks, ceil_div(Cin, 4), false), false);
+  return w2d_slabs.time_us(blocks, ceil_div(Cin, 4), w2d_slabs.pick(blocks, ceil_div(Cin, 4), false), false);
 }
 
 // Floats of K-slab scratch a train-mode launch of this shape wants (0: it runs unsplit); the launcher takes the capacity and
@@ -993,11 +914,9 @@ extern "C" int64_t gsd_conv3x3_w2d_workspace(int N, int H, int W, int Cin, int C
   W2DPlan p;
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 4 != 0 || !plan_w2d(N, H, W, Cout, &p)) return 0;
   const long blocks = (long)N * p.tiles_y * p.tiles_x * p.mblocks;
-  const int S = std::max(w2d_pick_slabs(blocks, Cin / 4, false), w2d_pick_slabs(blocks, Cin / 4, true));
+  const int S = std::max(w2d_slabs.pick(blocks, Cin / 4, false), w2d_slabs.pick(blocks, Cin / 4, true));
   return S > 1 ? (int64_t)blocks * S * (W2D_BM * 256) : 0;
 }
-
-extern "C" double gsd_conv3x3_w43_estimate_us(int N, int H, int W, int Cin, int Cout, int slabs);
 
 // 1: a caller that has both forms' weight layouts at hand should run this launch through gsd_conv3x3_w2d instead of
 // gsd_conv3x3_w43.  train == 0 (eval-mode inference): always -- the two-dimensional form neither folds rows across images nor
@@ -1013,47 +932,16 @@ extern "C" int gsd_conv3x3_prefers_w2d(int N, int H, int W, int Cin, int Cout, i
 }
 
 static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst, float* partials,
-                    const float* bw_raw, const float* bw_scale, const float* bw_shift, const float* bw_mean, const float* bw_invstd,
-                    int N, int H, int W, void* stream, float* ws = nullptr, int64_t ws_elems = 0) {
-  GSD_REQUIRE(src && dst && wt, GSD_ERR_BAD_ARG, "gsd_conv3x3_w2d: null argument");
-  GSD_REQUIRE(nsrc >= 1 && nsrc <= 2 && ndst >= 1 && ndst <= 2, GSD_ERR_BAD_ARG, "gsd_conv3x3_w2d: nsrc/ndst must be 1 or 2");
-  GSD_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, GSD_ERR_BAD_ARG, "gsd_conv3x3_w2d: bad sizes");
-  GSD_REQUIRE(H < 32768 && W < 32768, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w2d: H, W must be < 32768");
-  GSD_REQUIRE(((uintptr_t)wt & 15) == 0, GSD_ERR_BAD_ARG, "gsd_conv3x3_w2d: weight layout must be 16-byte aligned");
+                    const Conv3Bw& bw, int N, int H, int W, void* stream, float* ws = nullptr, int64_t ws_elems = 0) {
+  if (int e = conv3_check_operands("gsd_conv3x3_w2d", true, true, src, nsrc, wt, Cin, Cout, dst, ndst, N, H, W)) return e;
   GSD_REQUIRE(gsd_conv3x3_w2d_supported(Cin, src[0].C), GSD_ERR_UNSUPPORTED,
               "gsd_conv3x3_w2d: Cin=%d and the first segment's %d channels must be multiples of 4 (use gsd_conv3x3_w43)", Cin, src[0].C);
-  int csum = 0;
-  for (int i = 0; i < nsrc; ++i) {
-    if (int e = gsd_check_src(src[i], "gsd_conv3x3_w2d src", true)) return e;
-    GSD_REQUIRE(src[i].scale == nullptr || src[i].relu != 0, GSD_ERR_UNSUPPORTED,
-                "gsd_conv3x3_w2d: an affine source segment must also have relu (zero padding uses a NaN sentinel)");
-    GSD_REQUIRE((int64_t)src[i].H * src[i].w_stride < (1LL << 31), GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w2d: plane too large");
-    csum += src[i].C;
-  }
-  GSD_REQUIRE(csum == Cin, GSD_ERR_BAD_ARG, "gsd_conv3x3_w2d: source segments hold %d channels, Cin=%d", csum, Cin);
-  csum = 0;
-  for (int i = 0; i < ndst; ++i) {
-    if (int e = gsd_check_dst(dst[i], "gsd_conv3x3_w2d dst", true)) return e;
-    GSD_REQUIRE((int64_t)dst[i].H * dst[i].w_stride < (1LL << 31), GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w2d: plane too large");
-    csum += dst[i].C;
-  }
-  GSD_REQUIRE(csum == Cout, GSD_ERR_BAD_ARG, "gsd_conv3x3_w2d: destination segments hold %d channels, Cout=%d", csum, Cout);
 
   W2DPlan pl;
   GSD_REQUIRE(plan_w2d(N, H, W, Cout, &pl), GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w2d: no tile shape");
   W2DParams P;
-  P.src0 = to_srcd(src[0]);
-  P.src1 = nsrc > 1 ? to_srcd(src[1]) : null_srcd();
-  P.dst0 = to_dstd(dst[0]);
-  P.dst1 = ndst > 1 ? to_dstd(dst[1]) : null_dstd();
-  P.wt = wt;
-  P.partials = partials;
-  P.bw_raw = bw_raw; P.bw_scale = bw_scale; P.bw_shift = bw_shift; P.bw_mean = bw_mean; P.bw_invstd = bw_invstd;
-  P.Cin = Cin; P.Cout = Cout;
-  P.Mpad = round_up(Cout, 64);
-  P.nchunks = Cin / 4;
+  conv3_fill_common(P, src, nsrc, wt, Cin, Cout, dst, ndst, partials, bw, N, H, W);   // (nchunks = Cin / 4: no remainder)
   P.mblocks = pl.mblocks;
-  P.N = N; P.H = H; P.W = W;
   P.TH = pl.TH; P.TW = pl.TW; P.TWq = pl.TWq; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;
   P.WR = pl.WR; P.WC = pl.WC; P.WCp = pl.WCp; P.PS = pl.PS;
   P.NPV = ceil_div(P.WR * P.WCp, 64);
@@ -1072,7 +960,7 @@ static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   }
   const long base = (long)N * pl.tiles_y * pl.tiles_x * P.mblocks;
   // K slabs: only with a workspace (the engine lends one in train mode), only in the four-wave form, and never more than fit
-  int S = ws != nullptr ? w2d_pick_slabs(base, P.nchunks, bw_raw != nullptr) : 1;
+  int S = ws != nullptr ? w2d_slabs.pick(base, P.nchunks, bw.raw != nullptr) : 1;
   while (S > 1 && (int64_t)base * S * (W2D_BM * 256) > ws_elems) --S;
   if (S > 1 && P.nchunks / S < 2) S = 1;
   P.nslab = S;
@@ -1116,17 +1004,13 @@ static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
 
 extern "C" int gsd_conv3x3_w2d(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst,
                                float* partials, int N, int H, int W, void* stream) {
-  return w2d_impl(src, nsrc, wt, Cin, Cout, dst, ndst, partials, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, stream);
+  return w2d_impl(src, nsrc, wt, Cin, Cout, dst, ndst, partials, Conv3Bw{}, N, H, W, stream);
 }
 
 extern "C" int gsd_conv3x3_w2d_dgrad_bnrelu(const gsd_src* src, const float* wt, int Cin, int Cout, const gsd_dst* dst,
                                             const float* raw, const float* scale, const float* shift, const float* mean,
                                             const float* invstd, float* partials, int N, int H, int W, void* stream) {
-  GSD_REQUIRE(dst && raw && scale && shift && mean && invstd && partials, GSD_ERR_BAD_ARG,
-              "gsd_conv3x3_w2d_dgrad_bnrelu: null argument");
-  GSD_REQUIRE(dst->C == Cout && dst->H == H && dst->W == W && dst->off_h == 0 && dst->off_w == 0, GSD_ERR_BAD_ARG,
-              "gsd_conv3x3_w2d_dgrad_bnrelu: dst must be the full (Cout,H,W) gradient buffer (raw shares its strides)");
-  return w2d_impl(src, 1, wt, Cin, Cout, dst, 1, partials, raw, scale, shift, mean, invstd, N, H, W, stream);
+  return gsd_conv3x3_w2d_dgrad_bnrelu_ws(src, wt, Cin, Cout, dst, raw, scale, shift, mean, invstd, partials, nullptr, 0, N, H, W, stream);
 }
 
 // The same two with K-slab scratch lent by the caller (gsd_conv3x3_w2d_workspace floats; any capacity is safe: the launcher shrinks
@@ -1134,17 +1018,14 @@ extern "C" int gsd_conv3x3_w2d_dgrad_bnrelu(const gsd_src* src, const float* wt,
 // channels is then taken slab by slab in a fixed order -- run-to-run bitwise, not bit-equal to the unsplit launch.
 extern "C" int gsd_conv3x3_w2d_ws(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst,
                                   float* partials, float* workspace, int64_t workspace_elems, int N, int H, int W, void* stream) {
-  return w2d_impl(src, nsrc, wt, Cin, Cout, dst, ndst, partials, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, stream, workspace,
-                  workspace_elems);
+  return w2d_impl(src, nsrc, wt, Cin, Cout, dst, ndst, partials, Conv3Bw{}, N, H, W, stream, workspace, workspace_elems);
 }
 
 extern "C" int gsd_conv3x3_w2d_dgrad_bnrelu_ws(const gsd_src* src, const float* wt, int Cin, int Cout, const gsd_dst* dst,
                                                const float* raw, const float* scale, const float* shift, const float* mean,
                                                const float* invstd, float* partials, float* workspace, int64_t workspace_elems, int N,
                                                int H, int W, void* stream) {
-  GSD_REQUIRE(dst && raw && scale && shift && mean && invstd && partials, GSD_ERR_BAD_ARG,
-              "gsd_conv3x3_w2d_dgrad_bnrelu: null argument");
-  GSD_REQUIRE(dst->C == Cout && dst->H == H && dst->W == W && dst->off_h == 0 && dst->off_w == 0, GSD_ERR_BAD_ARG,
-              "gsd_conv3x3_w2d_dgrad_bnrelu: dst must be the full (Cout,H,W) gradient buffer (raw shares its strides)");
-  return w2d_impl(src, 1, wt, Cin, Cout, dst, 1, partials, raw, scale, shift, mean, invstd, N, H, W, stream, workspace, workspace_elems);
+  const Conv3Bw bw{raw, scale, shift, mean, invstd};
+  if (int e = conv3_check_dgrad_bnrelu("gsd_conv3x3_w2d_dgrad_bnrelu", dst, bw, partials, Cout, H, W)) return e;
+  return w2d_impl(src, 1, wt, Cin, Cout, dst, 1, partials, bw, N, H, W, stream, workspace, workspace_elems);
 }

@@ -24,7 +24,7 @@
 // so the L2 -> LDS rate per MFMA-second equals the direct 128 x 128 kernel's although the MFMA time halves.
 // Data movement, deferred BatchNorm, NaN-sentinel padding, concat sources, two cropped destinations, BatchNorm
 // partial sums and the fused BatchNorm-backward dX epilogue are those of gsd_conv3x3.hip.
-#include "gsd_common.h"
+#include "gsd_conv3x3_host.h"
 
 #include <cstdlib>
 
@@ -710,8 +710,6 @@ struct W43Plan {
   int TH, TW, TWq, tiles_y, tiles_x, mblocks, WR, WC, WCp, fold;
 };
 
-int halo_read_cycles(int TWq, int LP, int PS, int off);
-
 // TH x TW output tile of up to 64 Winograd tiles whose padded halo window fits the 512 DMA positions.  Every block does the
 // work of 64 tiles whatever it covers, so: fewest blocks; among equals 32-wide rows, then the widest.
 // Small images (levels 3-4 of the U-Net: 40 x 53, 20 x 26) fill such a tile badly (83 % / 68 %): for them the tile rows run
@@ -744,7 +742,7 @@ bool plan_w43(int N, int H, int W, int M, W43Plan* best) {
       if ((twq & (twq - 1)) != 0 || fold) {   // odd widths: pick the LDS row pitch with the fewest bank conflicts
         int bc = -1;
         for (int c = round_up(tw + 2, 4); c <= round_up(tw + 2, 4) + 12 && (th + 2) * c <= 512; c += 4) {
-          const int cyc = halo_read_cycles(twq, c, round_up((th + 2) * c, 4) + 4, 0);
+          const int cyc = conv3_halo_read_cycles(4, 1, twq, c, round_up((th + 2) * c, 4) + 4, 0);
           if (bc < 0 || cyc < bc) {
             bc = cyc;
             wcp = c;
@@ -765,65 +763,9 @@ bool plan_w43(int N, int H, int W, int M, W43Plan* best) {
   return best_cost >= 0;
 }
 
-// LDS bank cost of the consumers' halo reads (one ds_read_b128 + one ds_read_b64 per kernel row; lane -> tile as in the
-// kernel) for a row pitch LP and plane stride PS: sum over the four pixel groups of the LDS cycles per read pair.
-int halo_read_cycles(int TWq, int LP, int PS, int off) {
-  static const int g128[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
-                                  {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
-  int total = 0;
-  for (int wave = 0; wave < 4; ++wave) {
-    int addr[64];
-    for (int lane = 0; lane < 64; ++lane) {
-      const int q = wave * 16 + (lane & 15);
-      addr[lane] = (lane >> 4) * PS + (q / TWq) * LP + 4 * (q % TWq) + off;
-    }
-    for (int half = 0; half < 2; ++half) {
-      for (int g = 0; g < 2; ++g) {   // ds_read_b128: 16-lane groups, 16 slots of 16 B
-        int worst = 0;
-        for (int slot = 0; slot < 16; ++slot) {
-          int distinct = 0, seen[16];
-          for (int i = 0; i < 16; ++i) {
-            const int a = addr[g128[g][i] + 32 * half];
-            if ((a / 4) % 16 != slot) continue;
-            bool dup = false;
-            for (int k = 0; k < distinct; ++k) dup = dup || seen[k] == a;
-            if (!dup) seen[distinct++] = a;
-          }
-          worst = distinct > worst ? distinct : worst;
-        }
-        total += worst;
-      }
-      int worst = 0;                  // ds_read_b64 at +4 floats: 32-lane halves, 32 slots of 8 B
-      for (int slot = 0; slot < 32; ++slot) {
-        int distinct = 0, seen[32];
-        for (int i = 0; i < 32; ++i) {
-          const int a = addr[i + 32 * half] + 4;
-          if ((a / 2) % 32 != slot) continue;
-          bool dup = false;
-          for (int k = 0; k < distinct; ++k) dup = dup || seen[k] == a;
-          if (!dup) seen[distinct++] = a;
-        }
-        worst = distinct > worst ? distinct : worst;
-      }
-      total += worst;
-    }
-  }
-  return total;
-}
-
-// one launcher per kernel instantiation (the address of the kernel keys the per-device launch-attribute cache)
 template <int X4, bool FAST, bool PLAIN = false, bool SPLIT = false>
 int launch_one(const W43Params& P, int grid, size_t lds, hipStream_t st) {
-  static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  const void* fn = reinterpret_cast<const void*>(&conv3x3_w43_kernel<X4, FAST, PLAIN, SPLIT>);
-  if (hipError_t e = gsd_allow_big_lds(big_lds, fn); e != hipSuccess) {
-    gsd_set_error("gsd_conv3x3_w43: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  GSD_REQUIRE(lds <= 160 * 1024, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w43: LDS image %zu B too large", lds);
-  hipLaunchKernelGGL((conv3x3_w43_kernel<X4, FAST, PLAIN, SPLIT>), dim3(grid), dim3(256), lds, st, P);
-  GSD_LAUNCH_CHECK("gsd_conv3x3_w43");
-  return GSD_OK;
+  return gsd_launch<conv3x3_w43_kernel<X4, FAST, PLAIN, SPLIT>>("gsd_conv3x3_w43", dim3(grid), dim3(256), lds, st, P);
 }
 
 // K-slab form: the SPLIT blocks (grid = tile blocks x slabs), then the reducer over the tile blocks
@@ -843,40 +785,11 @@ int launch_w43(const W43Params& P, int grid, size_t lds, hipStream_t st, bool x4
   return x4 ? launch_one<1, false>(P, grid, lds, st) : launch_one<0, false>(P, grid, lds, st);
 }
 
-// K slabs of a launch of `base` tile blocks of `nchunks` 4-channel chunks (1: the launch runs as it is).  Two blocks are resident
-// per CU and the dispatcher deals blocks over the 256 CUs, so a CU ends up with k = ceil(blocks / 256) of them and the launch takes
-// as long as that CU: pairs of blocks at the shared rate and, for an odd k, one block that has the CU to itself and runs 1.8x
-// faster.  The 20 x 26 level at batch 8 is 304 (152) blocks of 128-256 chunks: k = 2 (1) where 1.19 (0.59) would do.  Cutting the
-// chunks into S slabs multiplies the blocks and divides their length; it costs the fixed part of a block S times over and the
-// reducer's launch and pass over (S + 1) x 64 KiB per tile block.  Constants fitted to profiles/r05_kslabs_b{8,16,32}.txt (117
-// timings of 22 launch shapes, S = 1..8: rms error 4 %; the fitted model picks the fastest measured S on 20 of the 22 shapes
-// and is within 0.5 % on the other two): 2.6 us per chunk of a block that shares its CU, 4 us per block, a lone block at 0.55 of a
-// pair's time, the reducer at 12 us + 6 TB/s.  GSD_W43_SPLIT: 0 / 1 never, S >= 2 that many wherever the shape admits it.
-double w43_time_us(long base, int nchunks, int S, bool bw) {
-  const long cus = gsd_cu_count();
-  const long k = (base * S + cus - 1) / cus;
-  const double cu = (double)(k / 2) + (k & 1 ? 0.55 : 0.0);
-  double t = cu * (2.6 * nchunks / S + 4.0);
-  if (S > 1) t += 12.0 + (double)(S + 1 + (bw ? 1 : 0)) * base * 65536.0 / 6.0e6;
-  return t;
-}
-
-int w43_pick_slabs(long base, int nchunks, bool bw) {
-  const int forced = gsd_env_int("GSD_W43_SPLIT", -1);
-  if (forced == 0 || forced == 1) return 1;
-  auto t_us = [&](int S) { return w43_time_us(base, nchunks, S, bw); };
-  int best = 1;
-  double tb = t_us(1) * (forced > 1 ? 1e9 : 0.97);   // a split has to buy 3 %
-  for (int S = 2; S <= 8 && nchunks / S >= 8; ++S) {
-    if (forced > 1 && S != forced) continue;
-    const double t = t_us(S);
-    if (t < tb) {
-      tb = t;
-      best = S;
-    }
-  }
-  return best;
-}
+// The K-slab model (gsd_conv3x3_host.h) with this kernel's constants, fitted to profiles/r05_kslabs_b{8,16,32}.txt (117 timings of
+// 22 launch shapes, S = 1..8: rms error 4 %; the fitted model picks the fastest measured S on 20 of the 22 shapes and is within
+// 0.5 % on the other two): 2.6 us per chunk of a block that shares its CU, 4 us per block, a lone block at 0.55 of a pair's time
+// (it runs 1.8x faster).  GSD_W43_SPLIT: 0 / 1 never, S >= 2 that many wherever the shape admits it.
+constexpr Conv3SlabModel w43_slabs = {2.6, 4.0, 0.55, "GSD_W43_SPLIT"};
 
 }  // namespace
 
@@ -887,20 +800,20 @@ extern "C" int64_t gsd_conv3x3_w43_workspace(int N, int H, int W, int Cin, int C
   if (!plan_w43(N, H, W, Cout, &p)) return 0;
   const long base = (long)(p.fold ? 1 : N) * p.tiles_y * p.tiles_x * p.mblocks;
   // (the launch picks its own S with bw as it is called, and never more than fits: size for the larger of the two)
-  const int Sa = w43_pick_slabs(base, Cin / 4, true), Sb = w43_pick_slabs(base, Cin / 4, false);
+  const int Sa = w43_slabs.pick(base, Cin / 4, true), Sb = w43_slabs.pick(base, Cin / 4, false);
   const int S = Sa > Sb ? Sa : Sb;
   return S > 1 ? (int64_t)S * base * W43_BM * 256 : 0;
 }
 
-// Modelled run time of the launch in microseconds (w43_pick_slabs' model; slabs != 0: with the K-slab form where it pays):
+// Modelled run time of the launch in microseconds (the model of w43_slabs; slabs != 0: with the K-slab form where it pays):
 // what gsd_conv3x3_prefers_w2d compares the two-dimensional form against.
 extern "C" double gsd_conv3x3_w43_estimate_us(int N, int H, int W, int Cin, int Cout, int slabs) {
   W43Plan p;
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !plan_w43(N, H, W, Cout, &p)) return 0.0;
   const long base = (long)(p.fold ? 1 : N) * p.tiles_y * p.tiles_x * p.mblocks;
   const int nchunks = ceil_div(Cin, 4);
-  const int S = (slabs && Cin % 4 == 0) ? w43_pick_slabs(base, nchunks, false) : 1;
-  return w43_time_us(base, nchunks, S, false);
+  const int S = (slabs && Cin % 4 == 0) ? w43_slabs.pick(base, nchunks, false) : 1;
+  return w43_slabs.time_us(base, nchunks, S, false);
 }
 
 extern "C" int gsd_conv3x3_w43_partial_rows(int N, int H, int W, int Cout) {
@@ -918,28 +831,8 @@ extern "C" int64_t gsd_conv3x3_w43_mfma_count(int N, int H, int W, int Cin, int 
 }
 
 static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst,
-                    float* partials, const float* bw_raw, const float* bw_scale, const float* bw_shift, const float* bw_mean,
-                    const float* bw_invstd, int N, int H, int W, void* stream, float* ws = nullptr, int64_t ws_elems = 0) {
-  GSD_REQUIRE(src && dst && wt, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: null argument");
-  GSD_REQUIRE(nsrc >= 1 && nsrc <= 2 && ndst >= 1 && ndst <= 2, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: nsrc/ndst must be 1 or 2");
-  GSD_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: bad sizes");
-  GSD_REQUIRE(H < 32768 && W < 32768, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w43: H, W must be < 32768");
-  GSD_REQUIRE(((uintptr_t)wt & 15) == 0, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: weight layout must be 16-byte aligned");
-  int csum = 0;
-  for (int i = 0; i < nsrc; ++i) {
-    if (int e = gsd_check_src(src[i], "gsd_conv3x3_w43 src", true)) return e;
-    GSD_REQUIRE(src[i].scale == nullptr || src[i].relu != 0, GSD_ERR_UNSUPPORTED,
-                "gsd_conv3x3_w43: an affine source segment must also have relu (zero padding uses a NaN sentinel)");
-    GSD_REQUIRE((int64_t)src[i].H * src[i].w_stride < (1LL << 31), GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w43: plane too large");
-    csum += src[i].C;
-  }
-  GSD_REQUIRE(csum == Cin, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: source segments hold %d channels, Cin=%d", csum, Cin);
-  csum = 0;
-  for (int i = 0; i < ndst; ++i) {
-    if (int e = gsd_check_dst(dst[i], "gsd_conv3x3_w43 dst", true)) return e;
-    csum += dst[i].C;
-  }
-  GSD_REQUIRE(csum == Cout, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: destination segments hold %d channels, Cout=%d", csum, Cout);
+                    float* partials, const Conv3Bw& bw, int N, int H, int W, void* stream, float* ws = nullptr, int64_t ws_elems = 0) {
+  if (int e = conv3_check_operands("gsd_conv3x3_w43", true, false, src, nsrc, wt, Cin, Cout, dst, ndst, N, H, W)) return e;
 
   W43Plan pl;
   GSD_REQUIRE(plan_w43(N, H, W, Cout, &pl), GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w43: no tile shape");
@@ -950,23 +843,12 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
       GSD_REQUIRE((int64_t)N * dst[i].n_stride < (1LL << 31), GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w43: batch too large for row folding");
   }
   W43Params P;
-  P.src0 = to_srcd(src[0]);
-  P.src1 = nsrc > 1 ? to_srcd(src[1]) : null_srcd();
-  P.dst0 = to_dstd(dst[0]);
-  P.dst1 = ndst > 1 ? to_dstd(dst[1]) : null_dstd();
-  P.wt = wt;
-  P.partials = partials;
-  P.bw_raw = bw_raw; P.bw_scale = bw_scale; P.bw_shift = bw_shift; P.bw_mean = bw_mean; P.bw_invstd = bw_invstd;
-  P.Cin = Cin;
-  P.Cout = Cout;
-  P.Mpad = round_up(Cout, 64);
-  P.nchunks = ceil_div(Cin, 4);
+  conv3_fill_common(P, src, nsrc, wt, Cin, Cout, dst, ndst, partials, bw, N, H, W);
   // 4-wave blocks, two per CU: they hide each other's barriers better than one 8-wave block shares its halo (measured +6 %
   // at Cin <= 512, profiles/bench_conv_forms.py); a loader wave cannot keep up without a deeper ring
   // straight fills (no per-slot bookkeeping): every 4-channel chunk lies inside one source segment
   const bool fast = Cin % 4 == 0 && (nsrc == 1 || src[0].C % 4 == 0);
   P.mblocks = pl.mblocks;
-  P.N = N; P.H = H; P.W = W;
   P.TH = pl.TH; P.TW = pl.TW; P.TWq = pl.TWq; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;
   P.WR = pl.WR; P.WC = pl.WC; P.WCp = pl.WCp;
   P.PS = round_up(P.WR * P.WCp, 4) + 4;   // + one bank group: the four channel planes of a k-step start 16 B apart (mod 4)
@@ -986,7 +868,7 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
     P.RO = 4;
     int best = -1;
     for (int ps = P.WR * P.WCp + 4; ps < P.WR * P.WCp + 4 + 68; ps += 4) {
-      const int c = halo_read_cycles(pl.TWq, P.WCp, ps, P.RO);
+      const int c = conv3_halo_read_cycles(4, 1, pl.TWq, P.WCp, ps, P.RO);
       if (best < 0 || c < best) {
         best = c;
         P.PS = ps;
@@ -1004,7 +886,7 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   // K slabs (the caller lends scratch): straight-fill form only; the slab count shrinks to what the scratch holds
   if (ws != nullptr && fast) {
     GSD_REQUIRE(((uintptr_t)ws & 15) == 0, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: workspace must be 16-byte aligned");
-    int S = w43_pick_slabs(grid, P.nchunks, bw_raw != nullptr);
+    int S = w43_slabs.pick(grid, P.nchunks, bw.raw != nullptr);
     while (S > 1 && (int64_t)S * grid * W43_BM * 256 > ws_elems) --S;
     if (S > 1 && grid * S < 2147483647L) {
       P.nslab = S;
@@ -1017,32 +899,25 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
 
 extern "C" int gsd_conv3x3_w43(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst,
                                float* partials, int N, int H, int W, void* stream) {
-  return w43_impl(src, nsrc, wt, Cin, Cout, dst, ndst, partials, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, stream);
+  return w43_impl(src, nsrc, wt, Cin, Cout, dst, ndst, partials, Conv3Bw{}, N, H, W, stream);
 }
 
 extern "C" int gsd_conv3x3_w43_ws(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst,
                                   float* partials, float* ws, int64_t ws_elems, int N, int H, int W, void* stream) {
-  return w43_impl(src, nsrc, wt, Cin, Cout, dst, ndst, partials, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, stream, ws,
-                  ws_elems);
+  return w43_impl(src, nsrc, wt, Cin, Cout, dst, ndst, partials, Conv3Bw{}, N, H, W, stream, ws, ws_elems);
 }
 
 extern "C" int gsd_conv3x3_w43_dgrad_bnrelu(const gsd_src* src, const float* wt, int Cin, int Cout, const gsd_dst* dst,
                                             const float* raw, const float* scale, const float* shift, const float* mean,
                                             const float* invstd, float* partials, int N, int H, int W, void* stream) {
-  GSD_REQUIRE(dst && raw && scale && shift && mean && invstd && partials, GSD_ERR_BAD_ARG,
-              "gsd_conv3x3_w43_dgrad_bnrelu: null argument");
-  GSD_REQUIRE(dst->C == Cout && dst->H == H && dst->W == W && dst->off_h == 0 && dst->off_w == 0, GSD_ERR_BAD_ARG,
-              "gsd_conv3x3_w43_dgrad_bnrelu: dst must be the full (Cout,H,W) gradient buffer (raw shares its strides)");
-  return w43_impl(src, 1, wt, Cin, Cout, dst, 1, partials, raw, scale, shift, mean, invstd, N, H, W, stream);
+  return gsd_conv3x3_w43_dgrad_bnrelu_ws(src, wt, Cin, Cout, dst, raw, scale, shift, mean, invstd, partials, nullptr, 0, N, H, W, stream);
 }
 
 extern "C" int gsd_conv3x3_w43_dgrad_bnrelu_ws(const gsd_src* src, const float* wt, int Cin, int Cout, const gsd_dst* dst,
                                                const float* raw, const float* scale, const float* shift, const float* mean,
                                                const float* invstd, float* partials, float* ws, int64_t ws_elems, int N, int H,
                                                int W, void* stream) {
-  GSD_REQUIRE(dst && raw && scale && shift && mean && invstd && partials, GSD_ERR_BAD_ARG,
-              "gsd_conv3x3_w43_dgrad_bnrelu: null argument");
-  GSD_REQUIRE(dst->C == Cout && dst->H == H && dst->W == W && dst->off_h == 0 && dst->off_w == 0, GSD_ERR_BAD_ARG,
-              "gsd_conv3x3_w43_dgrad_bnrelu: dst must be the full (Cout,H,W) gradient buffer (raw shares its strides)");
-  return w43_impl(src, 1, wt, Cin, Cout, dst, 1, partials, raw, scale, shift, mean, invstd, N, H, W, stream, ws, ws_elems);
+  const Conv3Bw bw{raw, scale, shift, mean, invstd};
+  if (int e = conv3_check_dgrad_bnrelu("gsd_conv3x3_w43_dgrad_bnrelu", dst, bw, partials, Cout, H, W)) return e;
+  return w43_impl(src, 1, wt, Cin, Cout, dst, 1, partials, bw, N, H, W, stream, ws, ws_elems);
 }

@@ -688,18 +688,8 @@ extern "C" int gsd_convT2x2(const gsd_src* src, const float* wt, const float* bi
   // 16-byte activation pieces: channel planes start 16-byte aligned and hold a multiple of 4 pixels
   const bool x4 = gsd_env_int("GSD_CONVT_X4", 1) != 0 && ((uintptr_t)src->ptr & 15) == 0 && src->c_stride % 4 == 0 &&
                   src->n_stride % 4 == 0 && (H * W) % 4 == 0;
-  static gsd_attr_once big_lds[2];   // per-device caches of an idempotent launch attribute (gsd_common.h)
-  const void* fn = x4 ? reinterpret_cast<const void*>(&convT_fwd_dma_kernel<true>) : reinterpret_cast<const void*>(&convT_fwd_dma_kernel<false>);
-  if (hipError_t e = gsd_allow_big_lds(big_lds[x4 ? 1 : 0], fn); e != hipSuccess) {
-    gsd_set_error("gsd_convT2x2: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  if (x4)
-    hipLaunchKernelGGL(convT_fwd_dma_kernel<true>, dim3((int)grid), dim3(256), lds, (hipStream_t)stream, P);
-  else
-    hipLaunchKernelGGL(convT_fwd_dma_kernel<false>, dim3((int)grid), dim3(256), lds, (hipStream_t)stream, P);
-  GSD_LAUNCH_CHECK("gsd_convT2x2");
-  return GSD_OK;
+  if (x4) return gsd_launch<convT_fwd_dma_kernel<true>>("gsd_convT2x2", dim3((int)grid), dim3(256), lds, (hipStream_t)stream, P);
+  return gsd_launch<convT_fwd_dma_kernel<false>>("gsd_convT2x2", dim3((int)grid), dim3(256), lds, (hipStream_t)stream, P);
 }
 
 // Which gsd_weight_layout mode gsd_convT2x2_dgrad expects for these arguments: 7 (the LDS-DMA kernel) unless an odd-width
@@ -757,17 +747,10 @@ extern "C" int gsd_convT2x2_dgrad_as(int wt_mode, const gsd_src* src, const floa
     const long grid = (long)Q.tiles_flat * Q.mblocks;
     GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_convT2x2_dgrad: grid too large");
     const size_t lds = (size_t)(2 * (32 * 128 + 16 * 256)) * sizeof(float);   // 64 KiB: two blocks per CU
-    static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
     Q.bw_raw = Q.bw_scale = Q.bw_shift = Q.bw_mean = Q.bw_invstd = nullptr;
     Q.partials = nullptr;
     Q.Mpad = 0;
-    if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&convT_dgrad_dma_kernel<false>)); e != hipSuccess) {
-      gsd_set_error("gsd_convT2x2_dgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return GSD_ERR_HIP;
-    }
-    hipLaunchKernelGGL(convT_dgrad_dma_kernel<false>, dim3((int)grid), dim3(256), lds, (hipStream_t)stream, Q);
-    GSD_LAUNCH_CHECK("gsd_convT2x2_dgrad");
-    return GSD_OK;
+    return gsd_launch<convT_dgrad_dma_kernel<false>>("gsd_convT2x2_dgrad", dim3((int)grid), dim3(256), lds, (hipStream_t)stream, Q);
   }
   ConvTParams P;
   P.src = to_srcd(*src);
@@ -832,12 +815,5 @@ extern "C" int gsd_convT2x2_dgrad_bnrelu(const gsd_src* src, const float* wt, in
   const long grid = (long)Q.tiles_flat * Q.mblocks;
   GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_convT2x2_dgrad_bnrelu: grid too large");
   const size_t lds = (size_t)(2 * (32 * 128 + 16 * 256)) * sizeof(float);
-  static gsd_attr_once big_lds;
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&convT_dgrad_dma_kernel<true>)); e != hipSuccess) {
-    gsd_set_error("gsd_convT2x2_dgrad_bnrelu: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  hipLaunchKernelGGL(convT_dgrad_dma_kernel<true>, dim3((int)grid), dim3(256), lds, (hipStream_t)stream, Q);
-  GSD_LAUNCH_CHECK("gsd_convT2x2_dgrad_bnrelu");
-  return GSD_OK;
+  return gsd_launch<convT_dgrad_dma_kernel<true>>("gsd_convT2x2_dgrad_bnrelu", dim3((int)grid), dim3(256), lds, (hipStream_t)stream, Q);
 }

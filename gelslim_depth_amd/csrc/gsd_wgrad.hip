@@ -14,6 +14,7 @@
 // Reduction over pixels is split across blocks (split-K); every block writes a partial slab and a
 // second kernel sums the slabs in a fixed order => bitwise reproducible.
 #include "gsd_common.h"
+#include "gsd_wgrad_internal.h"
 
 #include <cstdlib>
 
@@ -685,45 +686,7 @@ int check_plain(const gsd_src& s, const char* what) {
   return 0;
 }
 
-template <int WM, int WN>
-int launch_convT_wgrad(const WgradParams& P, int grid, size_t lds, hipStream_t st) {
-  static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&convT_wgrad_kernel<WM, WN>)); e != hipSuccess) {
-    gsd_set_error("gsd_convT2x2_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  hipLaunchKernelGGL((convT_wgrad_kernel<WM, WN>), dim3(grid), dim3(256), lds, st, P);
-  GSD_LAUNCH_CHECK("gsd_convT2x2_wgrad");
-  return GSD_OK;
-}
-
-template <int WM, int WN, bool KSP>
-int launch_dma(const WgradParams& P, int grid, size_t lds, hipStream_t st) {
-  static gsd_attr_once big_lds;   // per-device cache of an idempotent launch attribute (gsd_common.h)
-  if (hipError_t e = gsd_allow_big_lds(big_lds, reinterpret_cast<const void*>(&wgrad3x3_dma_kernel<WM, WN, KSP>)); e != hipSuccess) {
-    gsd_set_error("gsd_conv3x3_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  GSD_REQUIRE(lds <= 160 * 1024, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_wgrad: LDS tile %zu B too large", lds);
-  hipLaunchKernelGGL((wgrad3x3_dma_kernel<WM, WN, KSP>), dim3(grid), dim3(256), lds, st, P);
-  GSD_LAUNCH_CHECK("gsd_conv3x3_wgrad");
-  return GSD_OK;
-}
-
 }  // namespace
-
-// Winograd F(4,3) form (gsd_wgrad_w43.hip): same arguments, same result layout; chosen per shape
-int gsd_wgrad_w43_use(int N, int H, int W, int Cin, int Cout);
-int64_t gsd_wgrad_w43_workspace(int N, int H, int W, int Cin, int Cout);
-int gsd_wgrad_w43_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, int Cout, float* dw, float* workspace,
-                      int64_t workspace_elems, int N, int H, int W, void* stream);
-int gsd_wgrad_w43_reduce_run(const float* workspace, float* dw, int splits, int Cout, int Cin, void* stream);
-// two-dimensional Winograd F(2x4,3x3) form (gsd_wgrad_w2d.hip): chosen per CALL (it needs the row-pitched dy, slack around the
-// activation segments and channel counts that are multiples of its block); same slab layout and reducer as the row form
-int gsd_wgrad_w2d_use(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, int Cout, int N, int H, int W);
-int64_t gsd_wgrad_w2d_workspace(int N, int H, int W, int Cin, int Cout);
-int gsd_wgrad_w2d_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, int Cout, float* workspace, int64_t workspace_elems,
-                      int N, int H, int W, int* splits_out, void* stream);
 
 extern "C" int64_t gsd_conv3x3_wgrad_workspace(int N, int H, int W, int Cin, int Cout) {
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
@@ -732,9 +695,6 @@ extern "C" int64_t gsd_conv3x3_wgrad_workspace(int N, int H, int W, int Cin, int
   const int64_t m = direct > wino ? direct : wino;   // any form may serve the call (GSD_WGRAD_ALGO, GSD_WGRAD_W2D, the operands)
   return m > w2d ? m : w2d;
 }
-
-int64_t gsd_wgrad_w43_mfma_count(int N, int H, int W, int Cin, int Cout);
-int64_t gsd_wgrad_w2d_mfma_count(int N, int H, int W, int Cin, int Cout);
 
 extern "C" int gsd_conv3x3_wgrad_form(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, int Cout, int N, int H, int W) {
   if (!a || !dy || nsrc < 1 || nsrc > 2 || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
@@ -805,12 +765,12 @@ extern "C" int gsd_conv3x3_wgrad(const gsd_src* a, int nsrc, const gsd_src* dy, 
     GSD_REQUIRE(a[i].scale == nullptr || a[i].relu != 0, GSD_ERR_UNSUPPORTED,
                 "gsd_conv3x3_wgrad: an affine activation segment must also have relu (zero padding uses a NaN sentinel)");
   const int nslabs = pl.ksplit ? 4 * pl.splits : pl.splits;
-  int rc;
-  if (pl.ksplit)
-    rc = launch_dma<1, 4, true>(P, grid, lds, (hipStream_t)stream);
-  else
-    rc = pl.wide ? launch_dma<1, 4, false>(P, grid, lds, (hipStream_t)stream) : launch_dma<2, 2, false>(P, grid, lds, (hipStream_t)stream);
-  if (rc) return rc;
+  const char* const what = "gsd_conv3x3_wgrad";
+  const hipStream_t st = (hipStream_t)stream;
+  if (int e = pl.ksplit ? gsd_launch<wgrad3x3_dma_kernel<1, 4, true>>(what, dim3(grid), dim3(256), lds, st, P)
+              : pl.wide ? gsd_launch<wgrad3x3_dma_kernel<1, 4, false>>(what, dim3(grid), dim3(256), lds, st, P)
+                        : gsd_launch<wgrad3x3_dma_kernel<2, 2, false>>(what, dim3(grid), dim3(256), lds, st, P))
+    return e;
   launch_wgrad_reduce<0>(workspace, dw, nslabs, Cout, Cin, (hipStream_t)stream);
   GSD_LAUNCH_CHECK("gsd_conv3x3_wgrad reduce");
   return GSD_OK;
@@ -853,30 +813,19 @@ extern "C" int gsd_convT2x2_wgrad(const gsd_src* x, const gsd_src* dy, int Cin, 
   P.stages_total = pl.stages_total; P.splits = pl.splits; P.mblocks = pl.mblocks; P.nblocks = pl.nblocks;
   const int grid = pl.splits * pl.mblocks * pl.nblocks;
   const size_t lds = (size_t)(pl.BMw * 66 + pl.BNw * 66) * sizeof(float);
-  int rc;
-  if (pl.wide) {   // M = 4*Cout <= 64: never the case for this network; the register-staged kernel keeps it working
-    rc = launch_convT_wgrad<1, 4>(P, grid, lds, (hipStream_t)stream);
-  } else {
-    // activation rows as aligned 16-byte pieces when 64 consecutive pixels of a plane are 256 aligned bytes
-    const bool bx = gsd_env_int("GSD_CONVT_WG_BX", 1) != 0 && (H * W) % 4 == 0 && ((uintptr_t)x->ptr & 15) == 0 &&
-                    x->c_stride % 4 == 0 && x->n_stride % 4 == 0;
-    // ... and the gradient rows as 16-byte pieces of dy rows (8-byte aligned pixel pairs: dy is 8-byte aligned with even strides)
-    const bool ax = bx && gsd_env_int("GSD_CONVT_WG_AX", 1) != 0;
-    static gsd_attr_once big_lds_ax, big_lds_bx, big_lds;   // per-device caches of an idempotent launch attribute (gsd_common.h)
-    const void* fn = ax ? reinterpret_cast<const void*>(&convT_wgrad_dma_kernel<2>)
-                        : (bx ? reinterpret_cast<const void*>(&convT_wgrad_dma_kernel<1>)
-                              : reinterpret_cast<const void*>(&convT_wgrad_dma_kernel<0>));
-    if (hipError_t e = gsd_allow_big_lds(ax ? big_lds_ax : (bx ? big_lds_bx : big_lds), fn); e != hipSuccess) {
-      gsd_set_error("gsd_convT2x2_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return GSD_ERR_HIP;
-    }
-    if (ax) hipLaunchKernelGGL(convT_wgrad_dma_kernel<2>, dim3(grid), dim3(256), lds, (hipStream_t)stream, P);
-    else if (bx) hipLaunchKernelGGL(convT_wgrad_dma_kernel<1>, dim3(grid), dim3(256), lds, (hipStream_t)stream, P);
-    else hipLaunchKernelGGL(convT_wgrad_dma_kernel<0>, dim3(grid), dim3(256), lds, (hipStream_t)stream, P);
-    GSD_LAUNCH_CHECK("gsd_convT2x2_wgrad");
-    rc = GSD_OK;
-  }
-  if (rc) return rc;
+  // activation rows as aligned 16-byte pieces when 64 consecutive pixels of a plane are 256 aligned bytes
+  const bool bx = gsd_env_int("GSD_CONVT_WG_BX", 1) != 0 && (H * W) % 4 == 0 && ((uintptr_t)x->ptr & 15) == 0 &&
+                  x->c_stride % 4 == 0 && x->n_stride % 4 == 0;
+  // ... and the gradient rows as 16-byte pieces of dy rows (8-byte aligned pixel pairs: dy is 8-byte aligned with even strides)
+  const bool ax = bx && gsd_env_int("GSD_CONVT_WG_AX", 1) != 0;
+  const char* const what = "gsd_convT2x2_wgrad";
+  const hipStream_t st = (hipStream_t)stream;
+  // (wide: M = 4*Cout <= 64, never the case for this network; the register-staged kernel keeps it working)
+  if (int e = pl.wide ? gsd_launch<convT_wgrad_kernel<1, 4>>(what, dim3(grid), dim3(256), lds, st, P)
+              : ax    ? gsd_launch<convT_wgrad_dma_kernel<2>>(what, dim3(grid), dim3(256), lds, st, P)
+              : bx    ? gsd_launch<convT_wgrad_dma_kernel<1>>(what, dim3(grid), dim3(256), lds, st, P)
+                      : gsd_launch<convT_wgrad_dma_kernel<0>>(what, dim3(grid), dim3(256), lds, st, P))
+    return e;
   launch_wgrad_reduce<1>(workspace, dw, pl.splits, M, Cin, (hipStream_t)stream);
   GSD_LAUNCH_CHECK("gsd_convT2x2_wgrad reduce");
   if (dbias != nullptr) {

@@ -256,19 +256,9 @@ extern "C" int gsd_conv3x3_wgrad_bn(const gsd_src* a, const float* dz, const flo
   P.S = pl.S; P.XP = pl.XP; P.qpi = pl.qpi; P.nquads = pl.nquads;
   const dim3 grid(pl.grid, ceil_div(Cout, 64));
   const hipStream_t st = (hipStream_t)stream;
-  // one attribute cache per instantiation: the kernel's address keys it (gsd_common.h)
-  static gsd_attr_once once_bn, once_plain;
-  const void* fn = scale != nullptr ? reinterpret_cast<const void*>(&wgrad3x3_first_kernel<true>)
-                                    : reinterpret_cast<const void*>(&wgrad3x3_first_kernel<false>);
-  if (hipError_t e = gsd_allow_big_lds(scale != nullptr ? once_bn : once_plain, fn); e != hipSuccess) {
-    gsd_set_error("gsd_conv3x3_wgrad_bn: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  if (scale != nullptr)
-    hipLaunchKernelGGL(wgrad3x3_first_kernel<true>, grid, dim3(256), pl.lds, st, P);
-  else
-    hipLaunchKernelGGL(wgrad3x3_first_kernel<false>, grid, dim3(256), pl.lds, st, P);
-  GSD_LAUNCH_CHECK("gsd_conv3x3_wgrad_bn");
+  if (int e = scale != nullptr ? gsd_launch<wgrad3x3_first_kernel<true>>("gsd_conv3x3_wgrad_bn", grid, dim3(256), pl.lds, st, P)
+                               : gsd_launch<wgrad3x3_first_kernel<false>>("gsd_conv3x3_wgrad_bn", grid, dim3(256), pl.lds, st, P))
+    return e;
   const int per = Cout * Cin * 9;
   hipLaunchKernelGGL(wgrad_first_reduce_kernel, dim3(ceil_div(per, 64)), dim3(1024), 0, st, workspace, dw, pl.grid, per);
   GSD_LAUNCH_CHECK("gsd_conv3x3_wgrad_bn reduce");

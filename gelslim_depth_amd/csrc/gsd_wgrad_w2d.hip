@@ -39,6 +39,7 @@
 // Conventions: U row 3 is +dY row 1 and V row 3 is d3 - d1 (both signs of the textbook F(2,3) flipped: same products); the six
 // frequencies of a row are stored in the order [1, 2, 3, 4, 0, 5] (what the packed transforms produce as register pairs).
 #include "gsd_common.h"
+#include "gsd_wgrad_internal.h"
 #include <type_traits>
 
 #include <cstdio>
@@ -673,25 +674,12 @@ int gsd_wgrad_w2d_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, in
             N, pl.KY, pl.KX, pl.ksteps_total, pl.splits, grid, pl.BM, pl.BN, (int)plain, lds);
   const dim3 g((int)grid);
   const hipStream_t st = (hipStream_t)stream;
-#define WG2D_LAUNCH(NWM_, NWN_, PL_)                                                                              \
-  do {                                                                                                            \
-    static gsd_attr_once once;                                                                                    \
-    const void* fn = reinterpret_cast<const void*>(&wgrad3x3_w2d_kernel<NWM_, NWN_, PL_>);                        \
-    if (hipError_t e = gsd_allow_big_lds(once, fn); e != hipSuccess) {                                            \
-      gsd_set_error("gsd_conv3x3_wgrad (w2d): hipFuncSetAttribute: %s", hipGetErrorString(e));                    \
-      return GSD_ERR_HIP;                                                                                         \
-    }                                                                                                             \
-    hipLaunchKernelGGL((wgrad3x3_w2d_kernel<NWM_, NWN_, PL_>), g, dim3(512), lds, st, P);                         \
-  } while (0)
-  if (pl.BM == 128) {
-    if (plain) WG2D_LAUNCH(4, 2, true);
-    else WG2D_LAUNCH(4, 2, false);
-  } else {
-    if (plain) WG2D_LAUNCH(2, 4, true);
-    else WG2D_LAUNCH(2, 4, false);
-  }
-#undef WG2D_LAUNCH
-  GSD_LAUNCH_CHECK("gsd_conv3x3_wgrad (w2d)");
+  const char* const what = "gsd_conv3x3_wgrad (w2d)";
+  if (int e = pl.BM == 128 ? (plain ? gsd_launch<wgrad3x3_w2d_kernel<4, 2, true>>(what, g, dim3(512), lds, st, P)
+                                    : gsd_launch<wgrad3x3_w2d_kernel<4, 2, false>>(what, g, dim3(512), lds, st, P))
+                           : (plain ? gsd_launch<wgrad3x3_w2d_kernel<2, 4, true>>(what, g, dim3(512), lds, st, P)
+                                    : gsd_launch<wgrad3x3_w2d_kernel<2, 4, false>>(what, g, dim3(512), lds, st, P)))
+    return e;
   *splits_out = pl.splits;
   return GSD_OK;
 }

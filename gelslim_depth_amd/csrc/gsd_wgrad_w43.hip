@@ -21,6 +21,7 @@
 // fixed), then B^T; A dy needs 9 VALU operations per 4 values.  Split-K over stages with ordered slab reduction as in
 // gsd_wgrad.hip: bitwise reproducible.
 #include "gsd_common.h"
+#include "gsd_wgrad_internal.h"
 #include <type_traits>
 
 #include <cstdio>
@@ -729,12 +730,28 @@ WgW43Plan plan_wg43(int N, int H, int W, int M, int Ncols) {
   return p;
 }
 
+// The kernel of one wave shape that serves the launch's operand forms: dy as aligned 16-byte pieces (ax4), the activation
+// windows as 16-byte pieces (bx4) with row reuse rr, no deferred BatchNorm / ReLU (plain).
+template <int NWM, int NWN>
+int launch_wg43(const WgW43Params& P, dim3 g, size_t lds, hipStream_t st, bool ax4, bool bx4, int rr, bool plain) {
+  const char* const what = "gsd_conv3x3_wgrad (w43)";
+  const dim3 b(64 * NWM * NWN);
+  if (bx4 && rr == 1 && plain) return gsd_launch<wgrad3x3_w43_kernel<NWM, NWN, true, true, true, 1>>(what, g, b, lds, st, P);
+  if (bx4 && rr == 2 && plain) return gsd_launch<wgrad3x3_w43_kernel<NWM, NWN, true, true, true, 2>>(what, g, b, lds, st, P);
+  if (bx4 && rr == 1) return gsd_launch<wgrad3x3_w43_kernel<NWM, NWN, true, false, true, 1>>(what, g, b, lds, st, P);
+  if (bx4 && rr == 2) return gsd_launch<wgrad3x3_w43_kernel<NWM, NWN, true, false, true, 2>>(what, g, b, lds, st, P);
+  if (bx4 && plain) return gsd_launch<wgrad3x3_w43_kernel<NWM, NWN, true, true, true, 0>>(what, g, b, lds, st, P);
+  if (bx4) return gsd_launch<wgrad3x3_w43_kernel<NWM, NWN, true, false, true, 0>>(what, g, b, lds, st, P);
+  if (ax4 && plain) return gsd_launch<wgrad3x3_w43_kernel<NWM, NWN, true, true, false, 0>>(what, g, b, lds, st, P);
+  if (ax4) return gsd_launch<wgrad3x3_w43_kernel<NWM, NWN, true, false, false, 0>>(what, g, b, lds, st, P);
+  return gsd_launch<wgrad3x3_w43_kernel<NWM, NWN, false, false, false, 0>>(what, g, b, lds, st, P);
+}
+
 }  // namespace
 
 // 1: gsd_conv3x3_wgrad serves this shape with the Winograd form.  GSD_WGRAD_ALGO=0|1 forces one (tuning, A/B runs).
 int gsd_wgrad_w43_use(int N, int H, int W, int Cin, int Cout) {
-  const char* env = getenv("GSD_WGRAD_ALGO");   // read per call: the tests switch forms inside one process
-  const int forced = env ? atoi(env) : -1;
+  const int forced = gsd_env_int("GSD_WGRAD_ALGO", -1);
   if (forced == 0) return 0;
   if (forced == 1) return 1;
   return Cin >= 16 && Cout >= 16;   // the 3-channel first layer keeps the pixel-split direct kernel
@@ -818,49 +835,9 @@ int gsd_wgrad_w43_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, in
             Cin, H, W, N, pl.TH, pl.TW, pl.stages_total, pl.splits, grid, pl.BM, pl.BN, (int)ax4, (int)bx4, rr, (int)plain, lds);
   const dim3 g((int)grid);
   const hipStream_t st = (hipStream_t)stream;
-  // one launcher per instantiation: the kernel's address keys the per-device cache of the launch attribute (gsd_common.h)
-#define WG43_LAUNCH(NWM_, NWN_, AX4_, PL_, BX_, RR_)                                                                    \
-  do {                                                                                                                  \
-    static gsd_attr_once once;                                                                                          \
-    const void* fn = reinterpret_cast<const void*>(&wgrad3x3_w43_kernel<NWM_, NWN_, AX4_, PL_, BX_, RR_>);              \
-    if (hipError_t e = gsd_allow_big_lds(once, fn); e != hipSuccess) {                                                  \
-      gsd_set_error("gsd_conv3x3_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));                                \
-      return GSD_ERR_HIP;                                                                                               \
-    }                                                                                                                   \
-    hipLaunchKernelGGL((wgrad3x3_w43_kernel<NWM_, NWN_, AX4_, PL_, BX_, RR_>), g, dim3(64 * NWM_ * NWN_), lds, st, P);  \
-  } while (0)
-  if (pl.BM == 128) {
-    if (bx4 && rr == 1 && plain) WG43_LAUNCH(4, 2, true, true, true, 1);
-    else if (bx4 && rr == 2 && plain) WG43_LAUNCH(4, 2, true, true, true, 2);
-    else if (bx4 && rr == 1) WG43_LAUNCH(4, 2, true, false, true, 1);
-    else if (bx4 && rr == 2) WG43_LAUNCH(4, 2, true, false, true, 2);
-    else if (bx4 && plain) WG43_LAUNCH(4, 2, true, true, true, 0);
-    else if (bx4) WG43_LAUNCH(4, 2, true, false, true, 0);
-    else if (ax4 && plain) WG43_LAUNCH(4, 2, true, true, false, 0);
-    else if (ax4) WG43_LAUNCH(4, 2, true, false, false, 0);
-    else WG43_LAUNCH(4, 2, false, false, false, 0);
-  } else if (pl.BN == 64) {
-    if (bx4 && rr == 1 && plain) WG43_LAUNCH(2, 4, true, true, true, 1);
-    else if (bx4 && rr == 2 && plain) WG43_LAUNCH(2, 4, true, true, true, 2);
-    else if (bx4 && rr == 1) WG43_LAUNCH(2, 4, true, false, true, 1);
-    else if (bx4 && rr == 2) WG43_LAUNCH(2, 4, true, false, true, 2);
-    else if (bx4 && plain) WG43_LAUNCH(2, 4, true, true, true, 0);
-    else if (bx4) WG43_LAUNCH(2, 4, true, false, true, 0);
-    else if (ax4 && plain) WG43_LAUNCH(2, 4, true, true, false, 0);
-    else if (ax4) WG43_LAUNCH(2, 4, true, false, false, 0);
-    else WG43_LAUNCH(2, 4, false, false, false, 0);
-  } else {
-    if (bx4 && rr == 1 && plain) WG43_LAUNCH(2, 2, true, true, true, 1);
-    else if (bx4 && rr == 2 && plain) WG43_LAUNCH(2, 2, true, true, true, 2);
-    else if (bx4 && rr == 1) WG43_LAUNCH(2, 2, true, false, true, 1);
-    else if (bx4 && rr == 2) WG43_LAUNCH(2, 2, true, false, true, 2);
-    else if (bx4 && plain) WG43_LAUNCH(2, 2, true, true, true, 0);
-    else if (bx4) WG43_LAUNCH(2, 2, true, false, true, 0);
-    else if (ax4 && plain) WG43_LAUNCH(2, 2, true, true, false, 0);
-    else if (ax4) WG43_LAUNCH(2, 2, true, false, false, 0);
-    else WG43_LAUNCH(2, 2, false, false, false, 0);
-  }
-#undef WG43_LAUNCH
-  GSD_LAUNCH_CHECK("gsd_conv3x3_wgrad (w43)");
+  if (int e = pl.BM == 128  ? launch_wg43<4, 2>(P, g, lds, st, ax4, bx4, rr, plain)
+              : pl.BN == 64 ? launch_wg43<2, 4>(P, g, lds, st, ax4, bx4, rr, plain)
+                            : launch_wg43<2, 2>(P, g, lds, st, ax4, bx4, rr, plain))
+    return e;
   return gsd_wgrad_w43_reduce_run(workspace, dw, pl.splits, Cout, Cin, stream);
 }
