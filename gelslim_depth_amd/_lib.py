@@ -47,6 +47,19 @@ class gsd_nhwc(C.Structure):
                 ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32)]
 
 
+class gsd_augment(C.Structure):
+    """Augmentation of one train pass (include/gsd.h): the stream's (seed, epoch) and the knobs."""
+    _fields_ = [("seed", C.c_uint64), ("epoch", C.c_int64), ("p_hflip", C.c_float), ("p_vflip", C.c_float),
+                ("max_dy", C.c_int32), ("max_dx", C.c_int32), ("gain", C.c_float), ("offset", C.c_float),
+                ("noise_std", C.c_float), ("pivot", C.c_float)]
+
+
+class gsd_augment_draw(C.Structure):
+    """What gsd_gather_augment draws for one dataset row (gsd_augment_sample)."""
+    _fields_ = [("hflip", C.c_int32), ("vflip", C.c_int32), ("dy", C.c_int32), ("dx", C.c_int32),
+                ("gain", C.c_float * 8), ("offset", C.c_float * 8)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -72,6 +85,7 @@ class gsd_bf16_wimg_job(C.Structure):
 _NHWC = C.POINTER(gsd_nhwc)
 _BNBWD = C.POINTER(gsd_bf16_bnbwd)
 _IP = C.POINTER(C.c_int)
+_AUG = C.POINTER(gsd_augment)
 
 # name -> (restype, argtypes); mirrors include/gsd.h and include/gsd_bf16.h one to one (tests check every symbol loads)
 SIGNATURES = {
@@ -152,6 +166,9 @@ SIGNATURES = {
     "gsd_channel_stats_workspace": (_L, [_I]),
     "gsd_channel_stats": (_I, [_P, _L, _I, _L, _P, _P, _P]),
     "gsd_gather_affine": (_I, [_P, _P, _L, _I, _I, _L, _P, _P, _I, _P, _P]),
+    "gsd_gather_augment": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _AUG, _P, _P, _P]),
+    "gsd_augment_sample": (_I, [_AUG, _L, _I, C.POINTER(gsd_augment_draw)]),
+    "gsd_augment_noise": (_I, [_AUG, _L, _L, _L, _P]),
     # ---- include/gsd_bf16.h
     "gsd_bf16_conv_mpad": (_I, [_I]),
     "gsd_bf16_conv_partial_rows": (_I, [_I, _I, _I, _I]),
@@ -343,6 +360,16 @@ def make_guard(words: Optional[torch.Tensor], tick: int):
     g.words = words.data_ptr()
     g.tick = tick
     return C.pointer(g)
+
+
+def make_augment(seed: int = 0, epoch: int = 0, p_hflip: float = 0.0, p_vflip: float = 0.0, max_dy: int = 0, max_dx: int = 0,
+                 gain: float = 0.0, offset: float = 0.0, noise_std: float = 0.0, pivot: float = 0.0) -> gsd_augment:
+    """gsd_augment from plain values; the seed is taken modulo 2^64.  Ranges are checked by the library, per call."""
+    a = gsd_augment()
+    a.seed, a.epoch = int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch)
+    a.p_hflip, a.p_vflip, a.max_dy, a.max_dx = float(p_hflip), float(p_vflip), int(max_dy), int(max_dx)
+    a.gain, a.offset, a.noise_std, a.pivot = float(gain), float(offset), float(noise_std), float(pivot)
+    return a
 
 
 def add_counters(tensors: Sequence[torch.Tensor], delta: int = 1) -> None:

@@ -18,6 +18,7 @@ it, so with the same torch seed the batches are the ones the reference's DataLoa
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
@@ -126,6 +127,103 @@ def gather_affine(src: torch.Tensor, idx: torch.Tensor, A: torch.Tensor, B: torc
     check(lib.gsd_gather_affine(src.data_ptr(), idx.data_ptr(), m, idx.numel(), c, h * w, A.data_ptr(), B.data_ptr(),
                                 A.numel(), out.data_ptr(), L.stream_ptr()), "gather_affine")
     return out
+
+
+class Augment:
+    """On-device data augmentation of TRAIN batches (an addition: the reference's __getitem__ only normalises), applied by
+    the batch gather itself (gsd_gather_augment) -- one pass over the pixels instead of two plain gathers.
+
+    Geometry, the same draw for a sample's tactile image and its depth image: a horizontal / vertical mirror with
+    probability `hflip` / `vflip`, then a shift by whole pixels uniform on [-max_shift[0], max_shift[0]] rows and
+    [-max_shift[1], max_shift[1]] columns with edge replication.  Photometry, tactile image only, in raw (0..255) units
+    before normalisation: per channel a gain uniform on 1 +- `gain` about `pivot` and an offset uniform on +- `offset`, per
+    pixel noise of standard deviation `noise_std` (a sum of four uniforms, |n| <= 3.47 noise_std).
+
+    Flips are OFF by default, like everything else: GelSlim's lighting is directional, so a mirrored image is only a valid
+    sample to the extent the illumination is symmetric -- switch them on knowingly.
+
+    `pivot=None` means 127.5 when the dataset was built with `use_difference_image` (the neutral value of
+    (x - base + 255) / 2), otherwise 0.
+
+    Every draw is a pure function of (seed, epoch, dataset row) evaluated in the kernel (include/gsd.h gives the stream): no
+    host generator is consumed, nothing synchronises, a sample's augmentation does not depend on its position in the batch,
+    on the batch size or on the rank, and a resumed run draws what the uninterrupted one would."""
+
+    def __init__(self, seed: int = 0, hflip: float = 0.0, vflip: float = 0.0, max_shift: Sequence[int] = (0, 0),
+                 gain: float = 0.0, offset: float = 0.0, noise_std: float = 0.0, pivot: Optional[float] = None) -> None:
+        def finite(name, v):
+            v = float(v)
+            if v != v or v in (float("inf"), float("-inf")):
+                raise ValueError(f"Augment: {name} must be finite, got {v!r}")
+            return v
+        self.seed = int(seed)
+        self.hflip, self.vflip = finite("hflip", hflip), finite("vflip", vflip)
+        for name, v in (("hflip", self.hflip), ("vflip", self.vflip)):
+            if not 0.0 <= v <= 1.0:
+                raise ValueError(f"Augment: {name} is a probability and must lie in [0, 1], got {v!r}")
+        try:
+            shift = tuple(int(v) for v in max_shift)
+        except TypeError:
+            shift = ()
+        if len(shift) != 2 or any(v != w for v, w in zip(shift, max_shift)):
+            raise ValueError(f"Augment: max_shift must be two whole numbers of pixels (rows, columns), got {max_shift!r}")
+        if min(shift) < 0 or max(shift) > 1 << 20:
+            raise ValueError(f"Augment: max_shift must lie in [0, 2^20], got {max_shift!r}")
+        self.max_shift = shift
+        self.gain, self.offset, self.noise_std = finite("gain", gain), finite("offset", offset), finite("noise_std", noise_std)
+        if not 0.0 <= self.gain < 1.0:
+            raise ValueError(f"Augment: gain must lie in [0, 1), got {self.gain!r}")
+        if self.offset < 0.0:
+            raise ValueError(f"Augment: offset must not be negative, got {self.offset!r}")
+        if self.noise_std < 0.0:
+            raise ValueError(f"Augment: noise_std must not be negative, got {self.noise_std!r}")
+        self.pivot = None if pivot is None else finite("pivot", pivot)
+
+    def spec(self) -> Dict[str, object]:
+        """Every field as a plain Python value (harness.fit saves it with a resumable run's state)."""
+        return {"seed": self.seed, "hflip": self.hflip, "vflip": self.vflip, "max_shift": list(self.max_shift),
+                "gain": self.gain, "offset": self.offset, "noise_std": self.noise_std, "pivot": self.pivot}
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Augment) and self.spec() == other.spec()
+
+    def __hash__(self) -> int:
+        return hash(tuple((k, tuple(v) if isinstance(v, list) else v) for k, v in self.spec().items()))
+
+    def __repr__(self) -> str:
+        return "Augment(" + ", ".join(f"{k}={v!r}" for k, v in self.spec().items()) + ")"
+
+    def struct(self, epoch: int, default_pivot: float = 0.0) -> "L.gsd_augment":
+        """The C-ABI form for one epoch; `default_pivot` stands in for pivot=None."""
+        return L.make_augment(self.seed, epoch, self.hflip, self.vflip, self.max_shift[0], self.max_shift[1], self.gain,
+                              self.offset, self.noise_std, default_pivot if self.pivot is None else self.pivot)
+
+
+def gather_augment(img: torch.Tensor, dep: torch.Tensor, idx: torch.Tensor, Ai: torch.Tensor, Bi: torch.Tensor,
+                   Ad: torch.Tensor, Bd: torch.Tensor, augment, epoch: int = 0,
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(gather_affine(img, idx, Ai, Bi), gather_affine(dep, idx, Ad, Bd)) with the samples' augmentation applied on the way,
+    ONE libgsd launch.  `augment` is an Augment (pivot=None read as 0) or a ready `_lib.gsd_augment` (its own epoch is
+    used).  `out`: contiguous float32 (image, depth) tensors to write instead of fresh ones."""
+    m, ci, h, w = img.shape
+    if dep.dim() != 4 or dep.shape[0] != m or tuple(dep.shape[2:]) != (h, w):
+        raise L.GsdError(f"gather_augment: image {tuple(img.shape)} and depth {tuple(dep.shape)} arenas do not match")
+    for t in (img, dep):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise L.GsdError("gather_augment: expected contiguous float32 arenas")
+    aug = augment if isinstance(augment, L.gsd_augment) else augment.struct(epoch)
+    b = idx.numel()
+    if out is None:
+        out = (torch.empty((b, ci, h, w), device=img.device, dtype=torch.float32),
+               torch.empty((b, dep.shape[1], h, w), device=img.device, dtype=torch.float32))
+    out_img, out_dep = out
+    for t, cc in ((out_img, ci), (out_dep, dep.shape[1])):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (b, cc, h, w) or t.device != img.device:
+            raise L.GsdError("gather_augment: bad output tensor")
+    check(lib.gsd_gather_augment(img.data_ptr(), dep.data_ptr(), idx.data_ptr(), m, b, ci, dep.shape[1], h, w, Ai.data_ptr(),
+                                 Bi.data_ptr(), Ai.numel(), Ad.data_ptr(), Bd.data_ptr(), Ad.numel(), C.byref(aug),
+                                 out_img.data_ptr(), out_dep.data_ptr(), L.stream_ptr()), "gather_augment")
+    return out_img, out_dep
 
 
 class DeviceDataset:
@@ -257,13 +355,19 @@ class DeviceDataset:
             self._affine_cache = (f(tA), f(tB), f([dA]), f([dB]))
         return self._affine_cache
 
-    def batch(self, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """Normalised samples for a device int64 index vector: the collated result of [self[i] for i in idx]."""
+    def batch(self, idx: torch.Tensor, augment: Optional[Augment] = None, epoch: int = 0) -> Dict[str, torch.Tensor]:
+        """Normalised samples for a device int64 index vector: the collated result of [self[i] for i in idx].  With an
+        `augment`, tactile and depth images come from ONE gather_augment launch keyed by (augment.seed, epoch, dataset row)."""
         idx = idx.to(self.device, dtype=torch.int64).contiguous()
         m = len(self)
         if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= m):
             raise IndexError(f"index out of range for a dataset of {m} samples")
         tA, tB, dA, dB = self._affines()
+        if augment is not None:
+            aug = augment.struct(epoch, 127.5 if self.use_difference_image else 0.0)
+            tac, dep = gather_augment(self.entire_dataset["tactile_image"], self.entire_dataset["depth_image"], idx, tA, tB,
+                                      dA, dB, aug)
+            return {"tactile_image": tac, "depth_image": dep, "object_index": self.entire_dataset["object_index"][idx]}
         return {"tactile_image": gather_affine(self.entire_dataset["tactile_image"], idx, tA, tB),
                 "depth_image": gather_affine(self.entire_dataset["depth_image"], idx, dA, dB),
                 "object_index": self.entire_dataset["object_index"][idx]}
@@ -284,19 +388,32 @@ class DeviceLoader:
     Batches are dicts of device tensors.  With shuffle=True the permutation is drawn the way torch's RandomSampler does
     under a DataLoader iterator (two draws from the global CPU generator -- the iterator's base seed, then the sampler's
     seed -- and torch.randperm under a private generator seeded with the latter), so under the same torch.manual_seed the
-    sample order equals the reference loader's (checked against torch's own DataLoader in tests/test_oracle.py)."""
+    sample order equals the reference loader's (checked against torch's own DataLoader in tests/test_oracle.py).
+
+    `augment` (an Augment, default None) augments the batches `__iter__` yields -- and only those: `eval_shares()` never
+    augments and `unsharded()` drops the augmentation, so validation and test passes see the data as stored.  A pass uses
+    the loader's current epoch for all of its batches and then advances it by one; `set_epoch(e)` overrides it (harness.fit
+    calls it before every train pass, so a resumed run continues the stream where it stopped).  The augmentation draws
+    nothing from torch's generators: the shuffle order is the same with it on or off."""
 
     def __init__(self, dataset: DeviceDataset, batch_size: int = 1, shuffle: bool = False, drop_last: bool = False,
-                 rank: int = 0, world_size: int = 1) -> None:
+                 rank: int = 0, world_size: int = 1, augment: Optional[Augment] = None) -> None:
+        if augment is not None and not isinstance(augment, Augment):
+            raise TypeError(f"DeviceLoader: augment must be an Augment or None, got {type(augment).__name__}")
         self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, int(batch_size), shuffle, drop_last
         self.rank, self.world_size = rank, world_size
+        self.augment, self.epoch = augment, 0
+
+    def set_epoch(self, epoch: int) -> None:
+        """The epoch the next `__iter__` pass augments with (every rank must set the same)."""
+        self.epoch = int(epoch)
 
     def unsharded(self) -> "DeviceLoader":
         """The same loader as ONE process sees it: the global batches (batch_size * world_size samples each, ragged tail as
         DataLoader(drop_last=False) leaves it), no wrap-around padding.  harness.fit evaluates validation / test passes
         through it on every rank: an evaluation issues no collective, and a padded shard would count the wrapped samples
-        twice in the loss that early stopping reads."""
-        if self.world_size == 1:
+        twice in the loss that early stopping reads.  The result never augments."""
+        if self.world_size == 1 and self.augment is None:
             return self
         return DeviceLoader(self.dataset, self.batch_size * self.world_size, self.shuffle, self.drop_last, rank=0, world_size=1)
 
@@ -307,7 +424,7 @@ class DeviceLoader:
         ragged tail leaves this rank nothing.  A short share is padded up to batch_size by repeating its last sample, so every
         forward keeps the per-rank train shape (no activation buffer is reallocated); only the first `valid` samples count.
         harness.evaluate_loader sums per-sample losses over them and all-reduces (sum, count) per global batch: every rank
-        gets the single-process value without evaluating the whole set."""
+        gets the single-process value without evaluating the whole set.  Never augmented."""
         perm = self.order().to(self.dataset.device)
         n, bs, per = perm.numel(), self.batch_size, self.batch_size * self.world_size
         for s in range(0, n, per):
@@ -345,8 +462,13 @@ class DeviceLoader:
         Every rank yields the SAME number of batches, each of the same size on every rank (the step issues collectives:
         a rank that skipped the last step would leave the others blocked in the gradient all-reduce, and unequal shares
         would mis-weight the 1/world gradient mean): a ragged last global batch is padded to a multiple of world_size by
-        wrapping around to the start of the permutation, as torch's DistributedSampler does, or dropped with drop_last."""
+        wrapping around to the start of the permutation, as torch's DistributedSampler does, or dropped with drop_last.
+
+        With an `augment`, every batch of the pass is augmented under the loader's current epoch, which then advances by one
+        (when the pass is set up, so a pass abandoned half way still counts)."""
         perm = self.order().to(self.dataset.device)
+        epoch = self.epoch
+        self.epoch = epoch + 1
         n, per, world = perm.numel(), self.batch_size * self.world_size, self.world_size
         for s in range(0, n, per):
             g = perm[s:s + per]
@@ -356,7 +478,8 @@ class DeviceLoader:
             if pad:
                 g = torch.cat([g, perm[torch.arange(pad, device=perm.device) % n]])
             share = g.numel() // world
-            yield self.dataset.batch(g[self.rank * share:(self.rank + 1) * share])
+            mine = g[self.rank * share:(self.rank + 1) * share]
+            yield self.dataset.batch(mine) if self.augment is None else self.dataset.batch(mine, self.augment, epoch)
 
 
 def train_epoch(step, loader: DeviceLoader) -> Tuple[float, int]:

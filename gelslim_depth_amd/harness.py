@@ -140,7 +140,20 @@ def _save_fit_state(step, path: str, loop: Dict[str, object]) -> None:
     atomic_save({"format": FIT_STATE_FORMAT, "version": 1, "train_step": step.state_dict(), "loop": loop}, path)
 
 
-def _restore_fit_state(step, path: str, is_main: bool) -> Optional[Dict[str, object]]:
+def _check_augment_spec(saved: Optional[Dict[str, object]], now: Optional[Dict[str, object]]) -> None:
+    """A resumed run continues the SAME augmentation stream: refuse a train loader whose Augment differs from the saved one
+    (a state file written before augmentation existed carries no spec and is read as None)."""
+    if saved == now:
+        return
+    if saved is None or now is None:
+        raise ValueError("fit(resume=True): augment differs from the saved run's (saved %r, now %r)" % (saved, now))
+    for k in sorted(set(saved) | set(now)):
+        if saved.get(k) != now.get(k):
+            raise ValueError("fit(resume=True): augment field %r differs from the saved run's (saved %r, now %r)"
+                             % (k, saved.get(k), now.get(k)))
+
+
+def _restore_fit_state(step, path: str, is_main: bool, augment_spec: Optional[Dict[str, object]] = None) -> Optional[Dict[str, object]]:
     """The loop's saved state, after the step's and the RNG states have been restored; None when there is no file.  Data
     parallel: rank 0 reads the file, the loop's state goes to every rank with broadcast_object_list, the step's arenas by
     its own broadcast (TrainStep.load_state_dict)."""
@@ -156,6 +169,7 @@ def _restore_fit_state(step, path: str, is_main: bool) -> Optional[Dict[str, obj
         loop = box[0]
     if loop is None:
         return None
+    _check_augment_spec(loop.get("augment"), augment_spec)      # refused before anything is restored
     step.load_state_dict(None if blob is None else blob["train_step"])
     torch.set_rng_state(loop["torch_rng"])
     if loop["cuda_rng"] is not None and torch.cuda.is_available():
@@ -178,7 +192,10 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
     Resumable runs (an addition; off by default): with `state_path`, rank 0 writes one file at the end of every
     `state_every`-th epoch and of the last epoch, after that epoch's log lines and checkpoints -- the step's
     `state_dict()` and the loop's own state: the next epoch, the stopping rule's fields, H, the elapsed training time and
-    the torch RNG states (the CPU generator orders DeviceLoader's shuffles).  With `resume=True` and that file present, all
+    the torch RNG states (the CPU generator orders DeviceLoader's shuffles) and the train loader's `Augment.spec()` (None
+    without augmentation).  Before every train pass the loader is told the epoch (`train_loader.set_epoch(e)`, when it
+    has that method): the augmentation stream is a function of (seed, epoch, dataset row), so a resumed run draws what the
+    uninterrupted one would; resuming with a loader whose spec differs raises ValueError naming the field.  With `resume=True` and that file present, all
     of it is restored before the first epoch and the run continues at the saved epoch (a run the stopping rule ended
     stays ended); `max_epochs` counts every epoch, the interrupted ones included.  The resumed part writes only the lines of its own epochs to the log file (a one-line
     notice goes to `echo`), so the concatenated log equals an uninterrupted run's apart from the timing lines and the
@@ -219,8 +236,10 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
     start = time.time()
     try:
         e, done = 0, False
+        augment = getattr(train_loader, "augment", None)
+        augment_spec = augment.spec() if augment is not None else None
         if resume and state_path is not None:
-            saved = _restore_fit_state(step, state_path, is_main)
+            saved = _restore_fit_state(step, state_path, is_main, augment_spec)
             if saved is not None:
                 e, H = int(saved["epoch"]), {k: list(v) for k, v in saved["H"].items()}
                 stopper.load_state_dict(saved["early_stopping"])
@@ -230,6 +249,8 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
                     echo(f"Resuming from {state_path} at epoch {e + 1}")
         while not done:
             t0 = time.time()
+            if hasattr(train_loader, "set_epoch"):
+                train_loader.set_epoch(e)       # the augmentation stream is keyed by (seed, epoch, dataset row)
             total, nb = train_pass(step, train_loader)
             train_loss = across(total / nb if nb else 0.0)
             H["train_loss"].append(train_loss)
@@ -257,7 +278,7 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
                 if log is not None:
                     log.flush()              # the log on disk holds every line of the epochs the state has behind it
                 _save_fit_state(step, state_path, {"epoch": e, "stopped": stop, "early_stopping": stopper.state_dict(),
-                                                   "H": H, "elapsed": time.time() - start})
+                                                   "H": H, "elapsed": time.time() - start, "augment": augment_spec})
         emit("Training complete")
         emit("Training time: {}s".format(time.time() - start))
     finally:

@@ -441,6 +441,55 @@ int gsd_channel_stats(const float* x, int64_t N, int C, int64_t HW, double* out,
 int gsd_gather_affine(const float* src, const int64_t* idx, int64_t M, int B, int C, int64_t HW, const float* A,
                       const float* Bc, int nab, float* out, void* stream);
 
+/* On-device data augmentation riding in the batch gather (an addition: the reference's __getitem__ only normalises).
+ * Every random choice is a pure function of (seed, epoch, dataset row) -- never of the position in the batch, of the batch
+ * size, of the rank or of any host generator -- so a resumed run, a data-parallel run and a single process see the same
+ * samples.  The stream (uint64, wrap-around; g = 0x9E3779B97F4A7C15; fin = splitmix64's finaliser; mix(z) = fin(z + g)):
+ *   K   = mix(mix(mix(seed) ^ epoch) ^ index)                 the sample key
+ *   r_k = fin(K + (k+1) g)                                    draw k of the sample
+ *   r_0: hflip = (r_0 >> 40) 2^-24 < p_hflip,  vflip = ((r_0 >> 16) & 0xFFFFFF) 2^-24 < p_vflip
+ *   r_1: dy = -max_dy + (((r_1 >> 32) (2 max_dy + 1)) >> 32),  dx the same from the low 32 bits with max_dx
+ *   r_{2+c}: u, u' as in r_0;  gain[c] = fmaf(gain, 2u - 1, 1),  offset[c] = offset (2u' - 1)
+ *   noise: Kn = mix(K ^ 0x6E6F697365), r = fin(Kn + (e+1) g), n = float(sum of r's four 16-bit fields - 131070) * fp32(sqrt(3)/65536)
+ *          for element e = c*H*W + h*W + w of the OUTPUT image: unit variance, |n| <= 3.47, no transcendental function.
+ * Geometry (image AND depth, the same draw): output pixel (h, w) reads
+ *   hs = clamp(h - dy, 0, H-1), ws = clamp(w - dx, 0, W-1), then hs = H-1-hs if vflip, ws = W-1-ws if hflip
+ * -- shift(flip(src)) with edge replication; every read stays inside the sample's own plane.
+ * Photometry (image only, raw units, fp32): t = x - pivot; x1 = fmaf(gain[c], t, pivot) + offset[c];
+ *   x2 = fmaf(noise_std, n, x1); y = fmaf(x2, A[c], B[c]).  With gain == offset == noise_std == 0 it is exactly
+ *   y = fmaf(x, A[c], B[c]): a geometry-only augmentation is a bitwise permutation of gsd_gather_affine's output.
+ *   Depth is always fmaf(x, A, B). */
+typedef struct gsd_augment {
+  uint64_t seed;
+  int64_t epoch;
+  float p_hflip, p_vflip;  /* probabilities in [0, 1]                             */
+  int32_t max_dy, max_dx;  /* shifts uniform on [-max, max] pixels, 0 <= max <= 2^20 */
+  float gain;              /* per-channel gain uniform on 1 +- gain, in [0, 1)     */
+  float offset;            /* per-channel offset uniform on +- offset, >= 0        */
+  float noise_std;         /* per-pixel noise scale, >= 0                          */
+  float pivot;             /* the value the gain leaves in place                   */
+} gsd_augment;
+
+/* One launch assembles the image batch and the depth batch of a train step: gsd_gather_affine of img (M,Ci,H,W) and of
+ * dep (M,Cd,H,W) with the sample's augmentation applied on the way; out_img (B,Ci,H,W), out_dep (B,Cd,H,W).
+ * A null pointer, a non-positive size, a probability outside [0,1], a shift outside [0, 2^20], gain outside [0,1), a
+ * negative offset / noise_std or any non-finite field returns GSD_ERR_BAD_ARG before any launch; Ci > 8 (or B,
+ * Ci + Cd > 65535, H*W >= 2^30) returns GSD_ERR_UNSUPPORTED.  An index outside [0,M) fills that sample's image and depth rows
+ * with NaN and reads nothing out of bounds. */
+int gsd_gather_augment(const float* img, const float* dep, const int64_t* idx, int64_t M, int B, int Ci, int Cd, int H, int W,
+                       const float* Ai, const float* Bi, int nabi, const float* Ad, const float* Bd, int nabd,
+                       const gsd_augment* aug, float* out_img, float* out_dep, void* stream);
+
+/* Host only, touches no device: what the kernel draws for dataset row `index` (gain / offset of channels >= Ci: 1 / 0). */
+typedef struct gsd_augment_draw {
+  int32_t hflip, vflip, dy, dx;
+  float gain[8], offset[8];
+} gsd_augment_draw;
+int gsd_augment_sample(const gsd_augment* aug, int64_t index, int Ci, gsd_augment_draw* out);
+/* Host only: the unit-variance noise values of image elements [first, first+n) of row `index`
+ * (element e = c*H*W + h*W + w of the OUTPUT image). */
+int gsd_augment_noise(const gsd_augment* aug, int64_t index, int64_t first, int64_t n, float* out);
+
 #ifdef __cplusplus
 }
 #endif
