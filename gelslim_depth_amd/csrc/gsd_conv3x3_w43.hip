@@ -884,15 +884,20 @@ static int w43_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   bool plain = gsd_env_int("GSD_W43_PLAIN", 1) != 0;   // no deferred BatchNorm / ReLU on any source segment
   for (int i = 0; i < nsrc; ++i) plain = plain && src[i].scale == nullptr && src[i].relu == 0;
   // K slabs (the caller lends scratch): straight-fill form only; the slab count shrinks to what the scratch holds
+  int S = 1;
   if (ws != nullptr && fast) {
     GSD_REQUIRE(((uintptr_t)ws & 15) == 0, GSD_ERR_BAD_ARG, "gsd_conv3x3_w43: workspace must be 16-byte aligned");
-    int S = w43_slabs.pick(grid, P.nchunks, bw.raw != nullptr);
+    S = w43_slabs.pick(grid, P.nchunks, bw.raw != nullptr);
     while (S > 1 && (int64_t)S * grid * W43_BM * 256 > ws_elems) --S;
-    if (S > 1 && grid * S < 2147483647L) {
-      P.nslab = S;
-      P.slabs = ws;
-      return launch_split(P, (int)grid, lds, (hipStream_t)stream, x4, plain);
-    }
+    if (grid * S >= 2147483647L) S = 1;
+  }
+  if (gsd_env_set("GSD_W43_TRACE"))   // tuning: one line per launch, the kernel instantiation that runs
+    fprintf(stderr, "w43 M%d K%d %dx%d N%d nsrc %d ndst %d plain %d x4 %d fast %d fold %d tile %dx%d slabs %d\n", Cout, Cin, H, W, N, nsrc,
+            ndst, (int)plain, (int)x4, (int)fast, pl.fold, pl.TH, pl.TW, S);
+  if (S > 1) {
+    P.nslab = S;
+    P.slabs = ws;
+    return launch_split(P, (int)grid, lds, (hipStream_t)stream, x4, plain);
   }
   return launch_w43(P, (int)grid, lds, (hipStream_t)stream, x4, fast, plain);
 }

@@ -716,7 +716,9 @@ WgW43Plan plan_wg43(int N, int H, int W, int M, int Ncols) {
   // channels of a ds_read_b128 hit 16 different bank groups
   p.XS = round_up(((p.WR * p.WCp + 63) / 64) * 64, 8) + 4;
   p.BM = M >= 128 ? 128 : 64;
-  p.BN = (p.BM == 64 && Ncols >= 64) ? 64 : 32;
+  // (a 1 x 64 stage's windows are 3 rows of 68 floats a channel: 64 of them beside the dy image are 162 KiB for the two LDS images
+  //  unless they move as 16-byte pieces, which the plan cannot know -- such a launch was refused: 32-column blocks there)
+  p.BN = (p.BM == 64 && Ncols >= 64 && p.TW != 64) ? 64 : 32;
   p.mblocks = ceil_div(M, p.BM);
   p.nblocks = ceil_div(Ncols, p.BN);
   p.stages_total = N * p.tiles_y * p.tiles_x;
