@@ -21,9 +21,16 @@ not have counted it; either factor changes by less than 1/t from tick t to t+1, 
 the step count -- "skip" carries on, "raise" raises GsdError at
 the next `check_finite()` (train_epoch calls it once per epoch: one host sync per epoch instead of two per step),
 None (default) runs the reference's arithmetic unguarded.
+
+Two additions the reference lacks, both off by default: `max_grad_norm` clips the all-reduced, averaged
+gradient by its global L2 norm as torch.nn.utils.clip_grad_norm_ would -- one reduction over the gradient arena
+(gsd_grad_norm) whose coefficient stays on the device and is applied inside the optimiser kernel (gsd_adam_ema_clip) --
+and `lr_schedule` (LRSchedule: linear warm-up, then constant, linear or cosine decay) makes the learning rate a pure
+function of the step count, so a resumed run continues its schedule.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -36,8 +43,75 @@ from .models.unet import UNet
 LOSS_KINDS = {"mse": 0, "l1": 1}
 
 STATE_FORMAT = "gelslim_depth_amd.TrainStep"
-STATE_VERSION = 1
-STATE_HPARAMS = ("lr", "betas", "eps", "weight_decay", "ema_decay", "loss", "nan_policy")
+STATE_VERSION = 2          # the newest this build reads; a state without max_grad_norm / lr_schedule is still written as 1
+STATE_HPARAMS = ("lr", "betas", "eps", "weight_decay", "ema_decay", "loss", "nan_policy", "max_grad_norm", "lr_schedule")
+
+LR_DECAYS = ("constant", "linear", "cosine")
+
+
+class LRSchedule:
+    """Learning rate as a function of the 1-based step count t (an addition: the reference trains at one constant rate):
+    a linear warm-up over `warmup_steps` steps, lr * t / warmup_steps, then `decay` from the base rate towards `min_lr`,
+    reached at step `total_steps` and held from there on -- "constant" (no decay), "linear" or "cosine" (half a cosine
+    wave).  `lr_at` is the formula.  A value class: comparable, hashable, `LRSchedule(**s.spec()) == s`."""
+
+    def __init__(self, warmup_steps: int = 0, decay: str = "constant", total_steps: Optional[int] = None,
+                 min_lr: float = 0.0) -> None:
+        def whole(name, v):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"LRSchedule: {name} must be a whole number of steps, got {v!r}")
+            return int(v)
+        self.warmup_steps = whole("warmup_steps", warmup_steps)
+        if self.warmup_steps < 0:
+            raise ValueError(f"LRSchedule: warmup_steps must not be negative, got {warmup_steps!r}")
+        if decay not in LR_DECAYS:
+            raise ValueError(f"LRSchedule: decay must be one of {', '.join(repr(d) for d in LR_DECAYS)}, got {decay!r}")
+        self.decay = decay
+        self.total_steps = None if total_steps is None else whole("total_steps", total_steps)
+        if self.total_steps is not None and self.total_steps <= 0:
+            raise ValueError(f"LRSchedule: total_steps must be positive, got {total_steps!r}")
+        if decay != "constant" and (self.total_steps is None or self.total_steps <= self.warmup_steps):
+            raise ValueError(f"LRSchedule: total_steps must exceed warmup_steps ({self.warmup_steps}) for decay={decay!r}, "
+                             f"got {total_steps!r}")
+        try:
+            self.min_lr = float(min_lr)
+        except (TypeError, ValueError):
+            raise ValueError(f"LRSchedule: min_lr must be a number, got {min_lr!r}") from None
+        if not (0.0 <= self.min_lr < math.inf):
+            raise ValueError(f"LRSchedule: min_lr must be finite and not negative, got {min_lr!r}")
+
+    def spec(self) -> Dict[str, object]:
+        """Every field as a plain Python value (TrainStep.state_dict saves it with the hyperparameters)."""
+        return {"warmup_steps": self.warmup_steps, "decay": self.decay, "total_steps": self.total_steps, "min_lr": self.min_lr}
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, LRSchedule) and self.spec() == other.spec()
+
+    def __hash__(self) -> int:
+        return hash(tuple(self.spec().items()))
+
+    def __repr__(self) -> str:
+        return "LRSchedule(" + ", ".join(f"{k}={v!r}" for k, v in self.spec().items()) + ")"
+
+
+def lr_at(lr: float, schedule: Optional[LRSchedule], t: int) -> float:
+    """The learning rate of the 1-based step t, in float64 on the host:  warm(t) * base(t)  with
+        warm = min(1, t / warmup_steps)                         (1 without warm-up)
+        q    = clamp((t - warmup_steps) / (total_steps - warmup_steps), 0, 1)
+        base = lr | min_lr + (lr - min_lr)(1 - q) | min_lr + (lr - min_lr)(1 + cos(pi q)) / 2     (constant | linear | cosine).
+    Without a schedule, and for constant decay behind the warm-up, it is `lr` exactly."""
+    lr = float(lr)
+    if schedule is None:
+        return lr
+    w = schedule.warmup_steps
+    warm = min(1.0, t / w) if w > 0 else 1.0
+    if schedule.decay == "constant":
+        base = lr
+    else:
+        q = min(1.0, max(0.0, (t - w) / (schedule.total_steps - w)))
+        shape = 1.0 - q if schedule.decay == "linear" else 0.5 * (1.0 + math.cos(math.pi * q))
+        base = schedule.min_lr + (lr - schedule.min_lr) * shape
+    return warm * base
 
 
 def atomic_save(obj, path: str) -> None:
@@ -98,14 +172,29 @@ class TrainStep:
     shadow are arenas of the same size.  With `process_group` set, gradients are summed across ranks with
     RCCL all-reduce (torch.distributed backend "nccl") in per-block buckets launched as soon as a block's
     backward is done, and scaled by 1/world inside the Adam kernel.
+
+    `max_grad_norm`: clip the averaged gradient to this global L2 norm (torch.nn.utils.clip_grad_norm_'s coefficient), behind
+    the all-reduce and in front of the optimiser, with no host synchronisation; `last_grad_norm` / `last_clip_coef` are
+    device tensors like `last_loss`.  A non-finite norm raises the guard (nan_policy) or, without one, reaches the parameters
+    as a NaN -- it is never clipped away.  `lr_schedule`: an LRSchedule; the rate of a step is lr_at(lr, lr_schedule, t) with
+    t the step count Adam's bias correction uses (skipped steps count).  Both are saved with the state.
     """
 
     def __init__(self, model: UNet, lr: float = 1e-3, weight_decay: float = 1e-6, betas: Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8, ema_decay: Optional[float] = 0.995, loss: str = "mse",
                  process_group=None, sync_bn: bool = False, overlap_allreduce: bool = True,
-                 nan_policy: Optional[str] = None, force_sync: bool = False, time_allreduce: bool = False):
+                 nan_policy: Optional[str] = None, force_sync: bool = False, time_allreduce: bool = False,
+                 max_grad_norm: Optional[float] = None, lr_schedule: Optional[LRSchedule] = None):
         if nan_policy not in (None, "skip", "raise"):
             raise ValueError(f"nan_policy must be None, 'skip' or 'raise', got {nan_policy!r}")
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError(f"max_grad_norm must be positive (None: no clipping), got {max_grad_norm!r}")
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise ValueError(f"lr_schedule must be an LRSchedule or None, got {type(lr_schedule).__name__}")
+        self.max_grad_norm = max_grad_norm
+        self.lr_schedule = lr_schedule
         self.model = model
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.ema_decay = ema_decay
@@ -145,6 +234,11 @@ class TrainStep:
         self.ema_flat = self.p_flat.clone() if ema_decay is not None else None
         self.loss_buf = torch.zeros((1,), device=dev, dtype=torch.float32)
         self.loss_ws = torch.empty((2048,), device=dev, dtype=torch.float64)
+        # clip = (norm of the averaged gradient before clipping, coefficient in (0, 1]), written by gsd_grad_norm every step
+        self.clip_buf = self.norm_ws = None
+        if max_grad_norm is not None:
+            self.clip_buf = torch.zeros((2,), device=dev, dtype=torch.float32)
+            self.norm_ws = torch.empty((lib.gsd_grad_norm_workspace(total),), device=dev, dtype=torch.float64)
         # non-finite guard: words[0] = tick of the last bad step, words[1] = steps skipped (include/gsd.h: gsd_guard)
         self.guard_words = torch.zeros((2,), device=dev, dtype=torch.int32) if nan_policy is not None else None
         # With a nan_policy a skipped step must leave no trace in the BatchNorm running statistics either (layers in front of
@@ -220,22 +314,52 @@ class TrainStep:
             eng.guard = None
         if self.sync is not None:
             self.sync.finish()
-            if guard is not None:     # every rank must take the same skip decision: the summed gradient carries any rank's NaN
-                self.dist.all_reduce(self.guard_words[0:1], op=self.dist.ReduceOp.MAX, group=self.pg)
+        if self.clip_buf is not None:
+            # behind the all-reduce, in front of the guard's MAX: every rank measures the same summed arena, and a non-finite
+            # norm found here is part of the skip decision the ranks agree on
+            check(lib.gsd_grad_norm(self.g_flat.data_ptr(), self.numel, 1.0 / self.world, self.max_grad_norm,
+                                    self.clip_buf.data_ptr(), self.norm_ws.data_ptr(), self.norm_ws.numel(), guard,
+                                    L.stream_ptr()), "grad_norm")
+        if self.sync is not None and guard is not None:
+            # every rank must take the same skip decision: the summed gradient carries any rank's NaN
+            self.dist.all_reduce(self.guard_words[0:1], op=self.dist.ReduceOp.MAX, group=self.pg)
         self.step_count += 1
         d = 0.0
         if self.ema_flat is not None:
             # torch_ema 0.3 (requirements.txt:6): decay = min(decay, (1+n)/(10+n)), n counted after increment
             self.ema_updates += 1
             d = min(self.ema_decay, (1.0 + self.ema_updates) / (10.0 + self.ema_updates))
-        check(lib.gsd_adam_ema(self.p_flat.data_ptr(), self.g_flat.data_ptr(), self.m_flat.data_ptr(),
-                               self.v_flat.data_ptr(), L.ptr(self.ema_flat), self.numel, self.step_count, self.lr,
-                               self.betas[0], self.betas[1], self.eps, self.wd, d, 1.0 / self.world, guard, L.stream_ptr()),
-              "adam_ema")
+        lr = self.current_lr()
+        if self.clip_buf is None:
+            check(lib.gsd_adam_ema(self.p_flat.data_ptr(), self.g_flat.data_ptr(), self.m_flat.data_ptr(),
+                                   self.v_flat.data_ptr(), L.ptr(self.ema_flat), self.numel, self.step_count, lr,
+                                   self.betas[0], self.betas[1], self.eps, self.wd, d, 1.0 / self.world, guard, L.stream_ptr()),
+                  "adam_ema")
+        else:
+            check(lib.gsd_adam_ema_clip(self.p_flat.data_ptr(), self.g_flat.data_ptr(), self.m_flat.data_ptr(),
+                                        self.v_flat.data_ptr(), L.ptr(self.ema_flat), self.numel, self.step_count, lr,
+                                        self.betas[0], self.betas[1], self.eps, self.wd, d, 1.0 / self.world,
+                                        self.clip_buf.data_ptr(), guard, L.stream_ptr()), "adam_ema_clip")
         if self.bn_flat is not None:
             check(lib.gsd_guard_restore(guard, self.bn_flat.data_ptr(), self.bn_snap.data_ptr(), self.bn_flat.numel(), L.stream_ptr()),
                   "guard_restore")
         return self.loss_buf
+
+    def current_lr(self) -> float:
+        """The learning rate of the last step taken (of the first one before any): lr_at(lr, lr_schedule, step_count)."""
+        return lr_at(self.lr, self.lr_schedule, max(1, self.step_count))
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """L2 norm of the last step's averaged gradient BEFORE clipping: a one-element device tensor that every step
+        overwrites (no host sync; .item() when you want it).  None without max_grad_norm."""
+        return None if self.clip_buf is None else self.clip_buf[0:1]
+
+    @property
+    def last_clip_coef(self) -> Optional[torch.Tensor]:
+        """The last step's clip coefficient min(1, max_grad_norm / (norm + 1e-6)), NaN for a non-finite norm; a device tensor
+        like last_grad_norm."""
+        return None if self.clip_buf is None else self.clip_buf[1:2]
 
     def skipped_steps(self) -> int:
         """Optimiser steps the non-finite guard has skipped so far (one host sync; 0 without a nan_policy)."""
@@ -307,7 +431,8 @@ class TrainStep:
     def _hparams(self) -> Dict[str, object]:
         return {"lr": float(self.lr), "betas": tuple(float(b) for b in self.betas), "eps": float(self.eps),
                 "weight_decay": float(self.wd), "ema_decay": None if self.ema_decay is None else float(self.ema_decay),
-                "loss": self.loss_kind, "nan_policy": self.nan_policy}
+                "loss": self.loss_kind, "nan_policy": self.nan_policy, "max_grad_norm": self.max_grad_norm,
+                "lr_schedule": None if self.lr_schedule is None else self.lr_schedule.spec()}
 
     def state_dict(self) -> Dict[str, object]:
         """The whole training state as CPU tensors and host scalars: the model's state_dict (live parameters, BatchNorm
@@ -320,7 +445,10 @@ class TrainStep:
 
         def cpu(t):
             return None if t is None else t.detach().to("cpu", copy=True)
-        return {"format": STATE_FORMAT, "version": STATE_VERSION,
+        # version 2 only when clipping or a schedule is on: a build that knows neither then refuses the state ("newer than
+        # this build reads") instead of silently training on unclipped or at the base rate
+        version = 1 if self.max_grad_norm is None and self.lr_schedule is None else 2
+        return {"format": STATE_FORMAT, "version": version,
                 "precision": model.precision, "n_channels": model.n_channels, "n_classes": model.n_classes,
                 "layer_dimensions": list(model._dims),
                 "model": {k: cpu(v) for k, v in model.state_dict().items()},
@@ -337,7 +465,8 @@ class TrainStep:
 
         Raises ValueError, naming the field, before anything is copied: another architecture (the first parameter whose
         name, offset or shape differs), EMA on one side only, or -- with strict=True -- another hyperparameter (lr, betas,
-        eps, weight_decay, ema_decay, loss, nan_policy); strict=False keeps this TrainStep's hyperparameters (the guard's
+        eps, weight_decay, ema_decay, loss, nan_policy, max_grad_norm, lr_schedule -- absent from a state written before the
+        last two existed, which reads as None); strict=False keeps this TrainStep's hyperparameters (the guard's
         skipped-step count then starts at 0 when the state has none).  A weights-only checkpoint is refused.
 
         Data parallel: a collective.  Rank 0's `sd` is checked and loaded (the other ranks may pass None), then its arenas
@@ -414,8 +543,10 @@ class TrainStep:
                 v = sd["hparams"].get(k)
                 if k == "betas" and v is not None:
                     v = tuple(float(b) for b in v)
-                elif k in ("lr", "eps", "weight_decay", "ema_decay") and v is not None:
+                elif k in ("lr", "eps", "weight_decay", "ema_decay", "max_grad_norm") and v is not None:
                     v = float(v)
+                elif k == "lr_schedule" and v is not None:
+                    v = dict(v)
                 if v != mine_h[k]:
                     raise ValueError(f"TrainStep state: {k} is {v!r} in the state and {mine_h[k]!r} here; pass strict=False "
                                      "to continue with this TrainStep's hyperparameters")

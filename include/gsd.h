@@ -387,6 +387,32 @@ int gsd_adam_ema(float* p, const float* g, float* m, float* v, float* ema, int64
                  int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                  float ema_decay, float grad_scale, const gsd_guard* guard, void* stream);
 
+/* ---- gradient clipping by global norm (an addition: the reference trains unclipped) --------- */
+/* torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2) over the flat gradient arena, on the device:
+ *   S       = sum g[i]^2, accumulated in fp64 (the square of an fp32 value is exact there)
+ *   clip[0] = total = (float)(sqrt(S) * (double)grad_scale)   the L2 norm of the averaged gradient, rounded once
+ *   clip[1] = coef  = min(1, max_norm / (total + 1e-6f))      in fp32: clip_grad_norm_'s clip_coef_clamped
+ * g is left as it is; the coefficient is applied by gsd_adam_ema_clip.  grad_scale is gsd_adam_ema's (1/world_size
+ * after the all-reduce).  max_norm = +inf is legal: coef is 1 and the call only measures.
+ * A non-finite total is never hidden: coef becomes NaN (not 1), and with a guard `tick` is stored into words[0] as
+ * gsd_loss_fwd_bwd does, so gsd_adam_ema_clip skips and counts the step.
+ * Two stages, no floating-point atomics: group k of four consecutive floats belongs to thread k mod (blocks * 256),
+ * with blocks = gsd_grad_norm_workspace(numel) a function of numel alone, so the result is bitwise reproducible and does
+ * not depend on the alignment of g (any 4-byte aligned address; a 16-byte aligned one is read with 16-byte loads).
+ * workspace: gsd_grad_norm_workspace(numel) doubles, 8-byte aligned.  clip: two floats on the device.
+ * GSD_ERR_BAD_ARG (null pointer, numel <= 0, max_norm <= 0 or NaN, a guard without words or tick) and
+ * GSD_ERR_WORKSPACE (workspace_elems too small) are returned before any launch. */
+int64_t gsd_grad_norm_workspace(int64_t numel);
+int gsd_grad_norm(const float* g, int64_t numel, float grad_scale, float max_norm, float* clip, double* workspace,
+                  int64_t workspace_elems, const gsd_guard* guard, void* stream);
+/* gsd_adam_ema with the gradient scale grad_scale * clip[1], the product formed in fp32 on the device from
+ * gsd_grad_norm's coefficient (clip: its two floats).  Same arithmetic otherwise: with clip[1] == 1.0f the results are
+ * gsd_adam_ema's bit for bit.  Same guard behaviour: skip and count when words[0] == tick.  A NaN coefficient without
+ * a guard reaches the parameters, as a NaN gradient would. */
+int gsd_adam_ema_clip(float* p, const float* g, float* m, float* v, float* ema, int64_t numel,
+                      int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                      float ema_decay, float grad_scale, const float* clip, const gsd_guard* guard, void* stream);
+
 /* ---- inference pre/post-processing (test_utils/test_depth_estimation.py:14-20, complete_prediction.py:4-10) ---- */
 /* F.interpolate(mode='area') (image_utils.py:12-15; == adaptive_avg_pool2d) fused with the difference image
  * (image_utils.py:6-10, when base != NULL: pre(x) = (x - base + pre_add) * pre_mul) and a per-channel affine
