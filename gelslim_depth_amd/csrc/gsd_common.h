@@ -8,7 +8,7 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// ---- host-side error plumbing (thread-local message, see gsd_api.hip) ----------------------
+// ---- host-side error plumbing (thread-local message, defined in gsd_api.hip) ---------------
 void gsd_set_error(const char* fmt, ...);
 #define GSD_REQUIRE(cond, code, ...)                 \
   do {                                               \
@@ -211,3 +211,17 @@ static inline int gsd_cu_count() {
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+// grid of a grid-stride kernel with 256-thread blocks: one block per 256 items, at most `cap`
+static inline int gsd_grid_256(int64_t items, int cap) {
+  const int64_t b = ceil_div64(items, 256);
+  return (int)(b < cap ? b : cap);
+}
+
+// ---- gsd_guard (include/gsd.h) on the host side: the kernel arguments of an optional guard, and its argument check ----
+static inline int32_t* gsd_guard_words(const gsd_guard* g) { return g ? g->words : nullptr; }
+static inline int32_t gsd_guard_tick(const gsd_guard* g) { return g ? g->tick : 0; }
+static inline int gsd_check_guard(const gsd_guard* g, const char* what) {
+  GSD_REQUIRE(g == nullptr || (g->words != nullptr && g->tick != 0), GSD_ERR_BAD_ARG,
+              "%s: a guard needs its two device words and a non-zero tick", what);
+  return 0;
+}

@@ -1,7 +1,7 @@
 // gsd_resize.hip -- F.interpolate(size=..., mode in {'nearest', 'nearest-exact', 'bilinear', 'bicubic'}, align_corners=False,
 // antialias=False) for the reference's one resampling knob, interp_method (image_utils.py:12-15, read by
-// general_dataset.py:71-121, test_depth_estimation.py:15,19, complete_prediction.py:5,9).  mode='area' stays with the
-// existing kernels (gsd_area_resize_affine in gsd_pointwise.hip, gsd_ingest_images in gsd_dataset.hip); the two entry
+// general_dataset.py:71-121, test_depth_estimation.py:15,19, complete_prediction.py:5,9).  mode='area' stays with its
+// own kernels (gsd_area_resize_affine at the head of this file, gsd_ingest_images in gsd_dataset.hip); the two entry
 // points below forward it there unchanged.
 //
 // Same fused forms as the area path, one pass, one thread per output pixel, coalesced along the output pixel index:
@@ -12,8 +12,8 @@
 //
 // Indices and weights are those of ATen's CPU kernels (UpSample.h + UpSampleKernel.cpp of torch 2.10), op for op in fp32,
 // including the places where the CPU build contracts a multiply-add into an FMA.  Those contractions move the bilinear /
-// bicubic weights by up to ~1e-5 (the source coordinate is an FMA: its rounding at ~400 is 3e-5), so this file turns
-// contraction off and writes every FMA the CPU build forms explicitly:
+// bicubic weights by up to ~1e-5 (the source coordinate is an FMA: its rounding at ~400 is 3e-5), so these modes turn
+// contraction off and write every FMA the CPU build forms explicitly:
 //   scale     s = (float)in / (float)out
 //   nearest   min(floor((float)d * s), in-1)
 //   n.-exact  min(floor((float)((d + 0.5) * (double)s)), in-1)
@@ -26,6 +26,48 @@
 // weights are products w_h * w_w: the same result within a few ulps).
 #include "gsd_common.h"
 
+// ---------------------------------------------------------------------------------------------
+// inference pre/post-processing: F.interpolate(mode='area') == adaptive average pooling,
+// fused with the difference image ((a - base + 255) / 2, image_utils.py:6-10) and the per-channel affine of
+// normalize_tactile_image / denormalize_depth_image (normalization_utils.py:4-35,101-129).
+//   out[n,c,oh,ow] = A[c'] * mean_{window(oh,ow)} pre(in[n,c,h,w]) + B[c'],  c' = min(c, nab-1)
+//   window rows [floor(oh*H/OH), ceil((oh+1)*H/OH)), same for columns (ATen adaptive_avg_pool2d)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void area_resize_affine_kernel(const float* __restrict__ in, const float* __restrict__ base,
+                                                                 int C, int H, int W, float* __restrict__ out, int OH, int OW,
+                                                                 const float* __restrict__ A, const float* __restrict__ B, int nab,
+                                                                 float pre_add, float pre_mul) {
+  const int c = blockIdx.y, n = blockIdx.z;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= OH * OW) return;
+  const int oh = e / OW, ow = e - oh * OW;
+  const int h0 = (int)(((long long)oh * H) / OH), h1 = (int)(((long long)(oh + 1) * H + OH - 1) / OH);
+  const int w0 = (int)(((long long)ow * W) / OW), w1 = (int)(((long long)(ow + 1) * W + OW - 1) / OW);
+  const size_t plane = ((size_t)n * C + c) * H * W;
+  float s = 0.f;
+  for (int h = h0; h < h1; ++h)
+    for (int w = w0; w < w1; ++w) {
+      float v = in[plane + (size_t)h * W + w];
+      if (base != nullptr) v = (v - base[plane + (size_t)h * W + w] + pre_add) * pre_mul;
+      s += v;
+    }
+  s /= (float)((h1 - h0) * (w1 - w0));
+  const int cc = c < nab ? c : nab - 1;
+  out[((size_t)n * C + c) * OH * OW + e] = fmaf(s, A[cc], B[cc]);
+}
+extern "C" int gsd_area_resize_affine(const float* in, const float* base, int N, int C, int H, int W, float* out, int OH, int OW,
+                                      const float* A, const float* B, int nab, float pre_add, float pre_mul, void* stream) {
+  GSD_REQUIRE(in && out && A && B && N > 0 && C > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && nab > 0, GSD_ERR_BAD_ARG,
+              "gsd_area_resize_affine: bad argument");
+  GSD_REQUIRE(N <= 65535 && C <= 65535, GSD_ERR_UNSUPPORTED, "gsd_area_resize_affine: N, C must be <= 65535");
+  hipLaunchKernelGGL(area_resize_affine_kernel, dim3(ceil_div(OH * OW, 256), C, N), dim3(256), 0, (hipStream_t)stream, in, base,
+                     C, H, W, out, OH, OW, A, B, nab, pre_add, pre_mul);
+  GSD_LAUNCH_CHECK("gsd_area_resize_affine");
+  return GSD_OK;
+}
+
+// Everything below restates ATen's arithmetic and writes its FMAs out (see the head of the file); the area form above keeps
+// the compiler's default contraction.
 #pragma clang fp contract(off)
 
 namespace {

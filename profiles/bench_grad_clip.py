@@ -1,6 +1,6 @@
 """Train steps of BASELINE's network (31.0 M parameters, 3x320x427) with or without TrainStep(max_grad_norm=...), to be run
 under rocprofv3 --kernel-trace --stats: the kernel times of DESIGN.md section 13 (grad_norm_stage1 / grad_norm_stage2 /
-adam_ema_clip_kernel with --clip on, adam_ema_kernel with --clip off).  Also prints the step time from device events.
+adam_ema_kernel<true> with --clip on, adam_ema_kernel<false> with --clip off).  Also prints the step time from device events.
 usage (GPU box): PYTHONPATH=. python profiles/bench_grad_clip.py --dtype fp32|bf16 --clip on|off [--batch 32] [--steps 8]"""
 import argparse
 import statistics

@@ -1,4 +1,4 @@
-"""Element-wise fp64 bounds for the fp32 engine's non-contraction kernels (gelslim_depth_amd/csrc/gsd_pointwise.hip) in the
+"""Element-wise fp64 bounds for the fp32 engine's non-contraction kernels (gelslim_depth_amd/csrc/gsd_bn.hip, gsd_head.hip, gsd_optim.hip) in the
 cases one default train step cannot reach: both forms of every launch, K > 1 output classes, odd H, windows built to tie, the
 SyncBN finalize, channels with a large |mean| / std, eval coefficients, and the optimiser at step 1, 2 and 1000 with a visible
 coupled L2 term, grad_scale 1/2, without EMA and under a guard that marks the step bad.
