@@ -29,6 +29,11 @@
 // and the output transform on PAIRS of floats (packed fp32 instructions, bit-identical to the scalar form); the chunk loop unrolled
 // by two so that the LDS image offsets are instruction immediates; 16-byte halo pieces wherever the source admits them (HM);
 // plane offsets of the epilogue as scalar arithmetic.  K slabs (SPLIT) for the launches that would leave the chip idle.
+// The loop's BOOKKEEPING runs on the scalar unit: fills address a wave-uniform base plus an unsigned 32-bit lane offset under an
+// exec mask held in a scalar register pair, and wave-uniform conditions are scalar integers, not bools (hipcc carries a uniform
+// bool that crosses a block boundary through a vector register).  The kernel lives at 256 registers: state the loop does not need
+// waits in LDS or packed in one register, and tests/test_w2d_isa.py holds every instantiation to zero scratch and the loop to its
+// vector-instruction count (profiles/r07_w2d_isa_counts.txt).
 #include "gsd_conv3x3_host.h"
 
 #include <cstdio>
@@ -39,6 +44,34 @@ __device__ const float gsd_pad_w2d[2] = {0.f, __builtin_nanf("")};
 
 typedef float f32x4v __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
+// global-memory views at a scalar 64-bit base plus an unsigned 32-bit lane offset (the address space is spelled out: a pointer that
+// went through an opaque scalar is generic otherwise, and a generic access is a flat instruction with a 64-bit vector address)
+typedef __attribute__((address_space(1))) f32x4v g_f32x4v;
+typedef __attribute__((address_space(1))) float g_float;
+typedef __attribute__((address_space(1))) char g_char;
+__device__ __forceinline__ g_f32x4v* w2d_g4(g_char* base, unsigned off) { return (g_f32x4v*)(base + off); }
+__device__ __forceinline__ g_float* w2d_g1(g_char* base, unsigned off) { return (g_float*)(base + off); }
+
+// Division of a non-negative int by a launch constant d >= 1 as a multiply-high and two shifts (Granlund & Montgomery): the host
+// computes l = ceil(log2 d), mul = floor(2^32 (2^l - d) / d) + 1, and q = (t + ((x - t) >> min(l, 1))) >> max(l - 1, 0) with
+// t = mulhi(x, mul) is floor(x / d) for every 32-bit x.  On wave-uniform operands it is five scalar instructions; hipcc's own
+// expansion of a division is some twenty vector instructions (v_rcp_iflag_f32 and a correction), uniform operands or not.
+struct W2DDiv {
+  unsigned mul, s1, s2;
+};
+static inline W2DDiv w2d_div_of(unsigned d) {
+  unsigned l = 0;
+  while ((1ull << l) < d) ++l;
+  W2DDiv r;
+  r.mul = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
+  r.s1 = l < 1 ? l : 1;
+  r.s2 = l > 0 ? l - 1 : 0;
+  return r;
+}
+__device__ __forceinline__ int w2d_div(int x, const W2DDiv& d) {
+  const unsigned t = __umulhi((unsigned)x, d.mul);
+  return (int)((t + (((unsigned)x - t) >> d.s1)) >> d.s2);
+}
 
 struct W2DParams {
   SrcD src0, src1;
@@ -55,6 +88,9 @@ struct W2DParams {
   int TH, TW, TWq, tiles_y, tiles_x, WR, WC, WCp, PS, NPV;
   int NP, NI;   // X4: 16-byte pieces per window row (TW / 4 + 2), DMA instructions per channel plane
   int mgrp, pgrp, ptiles;   // block order of the deep levels: passes of mgrp m-blocks over groups of pgrp of the ptiles pixel tiles
+  W2DDiv d_mblocks, d_nslab, d_tpi, d_tiles_x, d_NP, d_WCp;   // divisions by mblocks, nslab, tiles_y * tiles_x, tiles_x, NP, WCp
+  int TWq_sh;   // log2 TWq (tiles are 8, 16, 32 or 64 pixels wide)
+  int dfast;    // bit d: destination d's planes are within an unsigned 32-bit byte offset of each other (the interior epilogue)
   int nslab;    // K slabs (SPLIT): block (tile, slab k, m-block) runs chunks [k n / S, (k + 1) n / S) and stores its un-reduced
   float* slabs; // 2 x 4 outputs per channel and Winograd tile to [tile][slab][m-block][64 channels][16 NWP tiles][8] floats
 };
@@ -65,16 +101,96 @@ constexpr int W2D_WTILE = 96 * W2D_BM;   // floats per weight chunk (24 KiB)
 constexpr int NWP = 2;                    // pixel groups of 16 tiles (128 pixels) per block
 }  // namespace
 
-// ---- epilogue (shared by the conv kernel and the K-slab reducer): a lane holds, per (m-tile, register) = channel, the 2 x 4 outputs
-// of its Winograd tile (get_y); NCHW stores (two destination segments with crop), BatchNorm partial sums, or the fused
-// BatchNorm-backward form.  sBw: the block's [4][64] coefficients of that form in LDS.
-template <class GetY>
+// ---- epilogue (shared by the conv kernel and the K-slab reducer): a lane holds the 2 x 4 outputs of its Winograd tile for the
+// wave's eight channel groups (m-tile m, register reg: channel cu + 4 j, cu = m0 + 32 mh + 16 m + reg) and hands them over two at a
+// time, get_pair(p, y): y[e][row][column] of (m, reg) = (p >> 1, 2 (p & 1) + e).  NCHW stores (two destination segments with crop),
+// BatchNorm partial sums, or the fused BatchNorm-backward form.  sBw: the block's [4][64] coefficients of that form in LDS.
+//
+// Two paths behind one wave-uniform test.  INTERIOR waves -- every lane's tile lies wholly inside the image and inside the crop of
+// the one destination that holds all 32 channels of the wave -- run without a mask: unconditional 16-byte stores at a scalar plane
+// base plus one unsigned 32-bit lane offset per tile row (P.dfast: the host vouches that such an offset spans the wave's planes).
+// Every other wave (edge tiles, a channel tail, a wave that straddles the two destinations) takes the masked path.  Both add the
+// statistics in the same order, pixel by pixel: the paths are bit-identical where both apply.
+template <class GetPair>
 __device__ __forceinline__ void w2d_epilogue(const W2DParams& P, const float* sBw, const int n, const int h0, const int w0, const int tr2,
                                              const int tq, const int vmask, const int m0, const int mh, const int ph, const int j,
-                                             const int l16, const int pt, GetY get_y) {
+                                             const int l16, const int pt, GetPair get_pair) {
   constexpr int BM = 64;
-  // ---- epilogue: Y = A2^T M A4, NCHW stores (two destination segments with crop), BatchNorm partial sums -------------------------
-  // per destination and tile row: element offset of the row's first pixel inside a plane, and the mask of its pixels that are stored
+  float* const prow = P.partials != nullptr ? P.partials + (size_t)(pt * NWP + ph) * (2 * P.Mpad) : nullptr;
+  const int mc = m0 + mh * 32;   // the wave's channels: mc .. mc + 31
+  {
+    const bool in1 = mc >= P.dst0.C;
+    const int d_oh = in1 ? P.dst1.oh : P.dst0.oh, d_ow = in1 ? P.dst1.ow : P.dst0.ow, d_H = in1 ? P.dst1.H : P.dst0.H;
+    const int d_W = in1 ? P.dst1.W : P.dst0.W, d_ws = in1 ? P.dst1.ws : P.dst0.ws;
+    const long long d_cs = in1 ? P.dst1.cs : P.dst0.cs, d_ns = in1 ? P.dst1.ns : P.dst0.ns;
+    const int hd = h0 + 2 * tr2 - d_oh, wd = w0 + 4 * tq - d_ow;
+    const bool lane_in = vmask == 0xff && hd >= 0 && hd + 2 <= d_H && wd >= 0 && wd + 4 <= d_W;
+    const bool chan_in = (in1 ? mc + 32 <= P.Cout : mc + 32 <= P.dst0.C) && (P.dfast >> (in1 ? 1 : 0) & 1) != 0;
+    if (chan_in && __builtin_amdgcn_ballot_w64(lane_in) == ~0ull) {
+      // lane offsets in bytes from the plane of channel cu (the lane's own plane is 4 j further)
+      unsigned o0 = ((unsigned)(j * 4) * (unsigned)d_cs + (unsigned)(hd * d_ws + wd)) * 4u;
+      unsigned o1 = o0 + (unsigned)d_ws * 4u;
+      unsigned oj = (unsigned)j * 16u;
+      asm volatile("" : "+v"(o0), "+v"(o1), "+v"(oj));
+      const long long pl0 = (long long)n * d_ns + (long long)(mc - (in1 ? P.dst0.C : 0)) * d_cs;   // the wave's first plane
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+      float y[2][2][4], s1v[2], s2v[2];
+      get_pair(p, y);
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const int cw = (p >> 1) * 16 + (p & 1) * 2 + c;   // channel cu - mc
+        g_char* dp = (g_char*)((in1 ? P.dst1.p : P.dst0.p) + pl0 + (long long)cw * d_cs);
+        asm volatile("" : "+s"(dp));
+        float s1 = 0.f, s2 = 0.f;
+        if (P.bw_raw == nullptr) {
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              s1 += y[c][a][i];
+              s2 = fmaf(y[c][a][i], y[c][a][i], s2);
+            }
+        } else {
+          g_char* rp = (g_char*)(P.bw_raw + pl0 + (long long)cw * d_cs);
+          asm volatile("" : "+s"(rp));
+          asm volatile("" : "+v"(o0), "+v"(o1));
+          const f32x4 x0 = *w2d_g4(rp, o0), x1 = *w2d_g4(rp, o1);
+          const int cl = mh * 32 + (p >> 1) * 16 + j * 4 + (p & 1) * 2 + c;
+          const float bsc = sBw[cl], bsh = sBw[BM + cl], bmu = sBw[2 * BM + cl], bis = sBw[3 * BM + cl];
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const float x = a == 0 ? x0[i] : x1[i];
+              const float dz = fmaf(x, bsc, bsh) > 0.f ? y[c][a][i] : 0.f;
+              y[c][a][i] = dz;
+              s1 += dz;
+              s2 = fmaf(dz, (x - bmu) * bis, s2);
+            }
+        }
+        asm volatile("" : "+v"(o0), "+v"(o1));   // (in the store's own block: hipcc otherwise zero-extends them once, as 64-bit vector addends)
+        *w2d_g4(dp, o0) = f32x4{y[c][0][0], y[c][0][1], y[c][0][2], y[c][0][3]};
+        *w2d_g4(dp, o1) = f32x4{y[c][1][0], y[c][1][1], y[c][1][2], y[c][1][3]};
+        s1v[c] = reduce16_to_lane15(s1);
+        s2v[c] = reduce16_to_lane15(s2);
+      }
+      if (prow != nullptr && l16 == 15) {   // (mc + 32 <= Cout <= Mpad: every channel has its column)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          g_char* pp = (g_char*)(prow + mc + (p >> 1) * 16 + (p & 1) * 2 + c);
+          asm volatile("" : "+s"(pp));
+          asm volatile("" : "+v"(oj));
+          *w2d_g1(pp, oj) = s1v[c];
+          *w2d_g1(pp + (size_t)P.Mpad * 4, oj) = s2v[c];
+        }
+      }
+      }
+      return;
+    }
+  }
+  // ---- the masked path.  Per destination and tile row: element offset of the row's first pixel inside a plane, and the mask of its
+  // pixels that are stored
   // (scalars, not arrays: `first ? off0(a) : off1(a)` on arrays makes hipcc select between two ADDRESSES and keep the arrays in scratch)
   int off0_0 = 0, off0_1 = 0, off1_0 = 0, off1_1 = 0, sm0_0 = 0, sm0_1 = 0, sm1_0 = 0, sm1_1 = 0;
 #pragma unroll
@@ -104,109 +220,91 @@ __device__ __forceinline__ void w2d_epilogue(const W2DParams& P, const float* sB
   const long long lane0 = (long long)(j * 4) * P.dst0.cs, lane1 = (long long)(j * 4) * P.dst1.cs;
   float* const d0 = P.dst0.p + (long long)n * P.dst0.ns;
   float* const d1 = P.dst1.p + (long long)n * P.dst1.ns;
-  float* const prow = P.partials != nullptr ? P.partials + (size_t)(pt * NWP + ph) * (2 * P.Mpad) : nullptr;
 
-  if (P.bw_raw == nullptr) {
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
+  for (int p = 0; p < 4; ++p) {
+  float y[2][2][4];
+  get_pair(p, y);
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        // channel = wave-uniform part cu + the lane's 4 j: the plane offset of cu is scalar arithmetic, the lane's share (lane0 / lane1)
-        // is multiplied once -- a 64-bit vector multiply per channel otherwise
-        const int cu = m0 + mh * 32 + m * 16 + reg, co = cu + j * 4;
-        const bool first = co < P.dst0.C;
-        const int cd = first ? co : co - P.dst0.C;
-        const bool co_ok = co < P.Cout && (first || cd < P.dst1.C);
-        float* const plane = first ? d0 + (long long)cu * P.dst0.cs + lane0 : d1 + (long long)(cu - P.dst0.C) * P.dst1.cs + lane1;
-        float y[2][4];
-        get_y(m, reg, y);
-        // statistics over the pixels that are STORED (for a cropped second destination -- the backward of F.pad -- the sums are
-        // those of the crop, e.g. the ConvT bias gradient)
-        float s1 = 0.f, s2 = 0.f;
+  for (int c = 0; c < 2; ++c) {
+    // channel = wave-uniform part cu + the lane's 4 j: the plane offset of cu is scalar arithmetic, the lane's share (lane0 / lane1)
+    // is multiplied once -- a 64-bit vector multiply per channel otherwise
+    const int m = p >> 1, reg = (p & 1) * 2 + c;
+    const int cu = mc + m * 16 + reg, co = cu + j * 4;
+    float s1 = 0.f, s2 = 0.f;
+    if (P.bw_raw == nullptr) {
+      const bool first = co < P.dst0.C;
+      const int cd = first ? co : co - P.dst0.C;
+      const bool co_ok = co < P.Cout && (first || cd < P.dst1.C);
+      float* const plane = first ? d0 + (long long)cu * P.dst0.cs + lane0 : d1 + (long long)(cu - P.dst0.C) * P.dst1.cs + lane1;
+      // statistics over the pixels that are STORED (for a cropped second destination -- the backward of F.pad -- the sums are
+      // those of the crop, e.g. the ConvT bias gradient)
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          const int sm = co_ok ? (first ? SM0(a) : SM1(a)) : 0;
-          float* const px = plane + (first ? OFF0(a) : OFF1(a));
+      for (int a = 0; a < 2; ++a) {
+        const int sm = co_ok ? (first ? SM0(a) : SM1(a)) : 0;
+        float* const px = plane + (first ? OFF0(a) : OFF1(a));
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            if (sm >> i & 1) {
-              s1 += y[a][i];
-              s2 = fmaf(y[a][i], y[a][i], s2);
-            }
-          }
-          if (sm == 15) {
-            *reinterpret_cast<f32x4v*>(px) = f32x4{y[a][0], y[a][1], y[a][2], y[a][3]};
-          } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-              if (sm >> i & 1) px[i] = y[a][i];
+        for (int i = 0; i < 4; ++i) {
+          if (sm >> i & 1) {
+            s1 += y[c][a][i];
+            s2 = fmaf(y[c][a][i], y[c][a][i], s2);
           }
         }
-        if (prow != nullptr) {
-          s1 = reduce16_to_lane15(s1);
-          s2 = reduce16_to_lane15(s2);
-          if (l16 == 15 && co < P.Mpad) {
-            prow[co] = s1;
-            prow[P.Mpad + co] = s2;
-          }
+        if (sm == 15) {
+          *reinterpret_cast<f32x4v*>(px) = f32x4{y[c][a][0], y[c][a][1], y[c][a][2], y[c][a][3]};
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (sm >> i & 1) px[i] = y[c][a][i];
+        }
+      }
+    } else {
+      // dst0 is the gradient buffer of a conv+BN+ReLU unit whose raw output has the same geometry: dz = relu'(bn(raw)) * dX
+      const long long cplane = (long long)n * P.dst0.ns + (co < P.Cout ? (long long)cu * P.dst0.cs + lane0 : 0);
+      float xr[2][4];
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        const float* const rp = P.bw_raw + cplane + OFF0(a);
+        if (SM0(a) == 15) {
+          const f32x4 t = *reinterpret_cast<const f32x4v*>(rp);
+          xr[a][0] = t[0], xr[a][1] = t[1], xr[a][2] = t[2], xr[a][3] = t[3];
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) xr[a][i] = (SM0(a) >> i & 1) ? rp[i] : 0.f;
+        }
+      }
+      const int cl = mh * 32 + m * 16 + j * 4 + reg;
+      const float bsc = sBw[cl], bsh = sBw[BM + cl], bmu = sBw[2 * BM + cl], bis = sBw[3 * BM + cl];
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        const int sm = co < P.Cout ? SM0(a) : 0;
+        float* const px = d0 + ((long long)cu * P.dst0.cs + lane0) + OFF0(a);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float x = xr[a][i];
+          const float dz = ((sm >> i & 1) && fmaf(x, bsc, bsh) > 0.f) ? y[c][a][i] : 0.f;
+          y[c][a][i] = dz;
+          s1 += dz;
+          s2 = fmaf(dz, (x - bmu) * bis, s2);
+        }
+        if (sm == 15) {
+          *reinterpret_cast<f32x4v*>(px) = f32x4{y[c][a][0], y[c][a][1], y[c][a][2], y[c][a][3]};
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (sm >> i & 1) px[i] = y[c][a][i];
         }
       }
     }
-  } else {
-    // dst0 is the gradient buffer of a conv+BN+ReLU unit whose raw output has the same geometry: dz = relu'(bn(raw)) * dX
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int cu = m0 + mh * 32 + m * 16 + reg, co = cu + j * 4;
-        const long long cplane = (long long)n * P.dst0.ns + (co < P.Cout ? (long long)cu * P.dst0.cs + lane0 : 0);
-        float xr[2][4];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          const float* const rp = P.bw_raw + cplane + OFF0(a);
-          if (SM0(a) == 15) {
-            const f32x4 t = *reinterpret_cast<const f32x4v*>(rp);
-            xr[a][0] = t[0], xr[a][1] = t[1], xr[a][2] = t[2], xr[a][3] = t[3];
-          } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) xr[a][i] = (SM0(a) >> i & 1) ? rp[i] : 0.f;
-          }
-        }
-        const int cl = mh * 32 + m * 16 + j * 4 + reg;
-        const float bsc = sBw[cl], bsh = sBw[BM + cl], bmu = sBw[2 * BM + cl], bis = sBw[3 * BM + cl];
-        float y[2][4];
-        get_y(m, reg, y);
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          const int sm = co < P.Cout ? SM0(a) : 0;
-          float* const px = d0 + ((long long)cu * P.dst0.cs + lane0) + OFF0(a);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float x = xr[a][i];
-            const float dz = ((sm >> i & 1) && fmaf(x, bsc, bsh) > 0.f) ? y[a][i] : 0.f;
-            y[a][i] = dz;
-            s1 += dz;
-            s2 = fmaf(dz, (x - bmu) * bis, s2);
-          }
-          if (sm == 15) {
-            *reinterpret_cast<f32x4v*>(px) = f32x4{y[a][0], y[a][1], y[a][2], y[a][3]};
-          } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-              if (sm >> i & 1) px[i] = y[a][i];
-          }
-        }
-        if (prow != nullptr) {
-          s1 = reduce16_to_lane15(s1);
-          s2 = reduce16_to_lane15(s2);
-          if (l16 == 15 && co < P.Mpad) {
-            prow[co] = s1;
-            prow[P.Mpad + co] = s2;
-          }
-        }
+    if (prow != nullptr) {
+      s1 = reduce16_to_lane15(s1);
+      s2 = reduce16_to_lane15(s2);
+      if (l16 == 15 && co < P.Mpad) {
+        prow[co] = s1;
+        prow[P.Mpad + co] = s2;
       }
     }
+  }
   }
 }
 
@@ -237,11 +335,13 @@ template <bool PLAIN, int HM = 0, bool SPLIT = false>
 __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DParams P) {
   constexpr bool X4 = HM == 1, U4 = HM == 2, PC = HM != 0;   // PC: the halo lies in LDS as 16-byte pieces
   constexpr int W2D_NONE = -2147483647 - 1, W2D_PAD = -2147483647;   // lane offsets: no position / a padding position (prefilled)
+  constexpr unsigned W2D_OFF_PAD = 0xFFFFFFFFu;                        // ... as a byte offset of the fills
   static_assert(!X4 || PLAIN, "aligned 16-byte halo pieces: a plain, row-pitched source");
   constexpr int BM = W2D_BM, WTILE = W2D_WTILE, NT = 128 * NWP, NW = 2 * NWP;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int PS = P.PS;
   const int BUF = WTILE + 4 * PS;
+  const int Kpad = P.nchunks * 4;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -250,9 +350,10 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
 
   // the m-blocks of one pixel tile read the same halo: every XCD gets a contiguous range of logical ids (pixel tile major)
   const int lid = xcd_swizzle(blockIdx.x, gridDim.x);
-  int mbb = lid % P.mblocks;
-  const int slab = SPLIT ? (lid / P.mblocks) % P.nslab : 0;
-  int pt = SPLIT ? lid / P.mblocks / P.nslab : lid / P.mblocks;
+  const int lid_m = w2d_div(lid, P.d_mblocks);
+  int mbb = lid - lid_m * P.mblocks;
+  int pt = SPLIT ? w2d_div(lid_m, P.d_nslab) : lid_m;
+  const int slab = SPLIT ? lid_m - pt * P.nslab : 0;
   if (!SPLIT && P.mgrp < P.mblocks) {
     // Deep levels: an m-block's weight image (24 KiB per chunk) is megabytes, and the blocks in flight on an XCD are at arbitrary
     // phases of their chunk loops once the first round is over -- with every m-block of a pixel tile in flight at once, the eight or
@@ -273,19 +374,19 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
     pt = p0 + pl;
     mbb = mg * P.mgrp + (r - pl * gn);
   }
-  const int c_lo = SPLIT ? (int)((long)slab * P.nchunks / P.nslab) : 0;
-  const int c_hi = SPLIT ? (int)((long)(slab + 1) * P.nchunks / P.nslab) : P.nchunks;
+  const int c_lo = SPLIT ? __builtin_amdgcn_readfirstlane((int)((long)slab * P.nchunks / P.nslab)) : 0;
+  const int c_hi = SPLIT ? __builtin_amdgcn_readfirstlane((int)((long)(slab + 1) * P.nchunks / P.nslab)) : P.nchunks;
   const int m0 = mbb * BM;
   const int tpi = P.tiles_y * P.tiles_x;
-  const int n = pt / tpi;
+  const int n = w2d_div(pt, P.d_tpi);
   const int rt = pt - n * tpi;
-  const int ty = rt / P.tiles_x;
+  const int ty = w2d_div(rt, P.d_tiles_x);
   const int h0 = ty * P.TH, w0 = (rt - ty * P.tiles_x) * P.TW;
 
   // ---- this lane's Winograd tile: 2 x 4 pixels (rows 2*tr2, 2*tr2+1; columns 4*tq .. 4*tq+3) of the block's TH x TW tile ------
   const int q = ph * 16 + l16;
   const bool q_ok = q < (P.TH >> 1) * P.TWq && q < 16 * NWP;
-  const int tr2 = q_ok ? q / P.TWq : 0;
+  const int tr2 = q_ok ? q >> P.TWq_sh : 0;
   const int tq = q_ok ? q - tr2 * P.TWq : 0;
   const int baddr = WTILE + j * PS + (2 * tr2) * P.WCp + 4 * tq + (PC ? 4 : 0);   // halo columns 4*tq .. 4*tq+5 of halo rows 2*tr2 .. 2*tr2+3
   int vmask = 0;   // bits 0..3: pixels of the tile's first row that exist in the image, bits 4..7: of its second row
@@ -299,12 +400,16 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       }
   }
 
+  // (the epilogue's lane geometry crosses the loop in ONE register: the accumulators leave none to spare)
+  int geo = tr2 | tq << 8 | vmask << 16;
+  asm volatile("" : "+v"(geo));
+
   // ---- halo DMA lane geometry: the block's waves cover the (up to) 128 NW window positions once, dword gathers --------------------
-  // seg_offsets: this lane's source element offsets in segment seg (W2D_PAD: a padding position, W2D_NONE: no position) -- worked
-  // out again at the segment switch rather than held in registers through the chunk loop
+  // seg_offsets: this lane's source element offsets in segment seg (W2D_PAD: a padding position, W2D_NONE: no position); the
+  // second segment's wait in LDS for the switch rather than in registers through the chunk loop
   bool p_on[2];
   int pmask = 0;   // U4: floats of this lane's pieces that lie outside their row (bits 4 pp .. 4 pp + 3: first segment, + 8: second)
-  auto seg_offsets = [&](const int seg, int (&xo)[2], const bool mark) __attribute__((always_inline)) {
+  auto seg_offsets = [&](const int seg, int (&xo)[2]) __attribute__((always_inline)) {
     const SrcD& S = seg ? P.src1 : P.src0;
 #pragma unroll
     for (int pp = 0; pp < 2; ++pp) {
@@ -313,8 +418,8 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
         // unit u = (channel plane u / NI, instruction u % NI) of the chunk: its 64 lanes are 64 consecutive pieces of the plane
         const int u = wave8 + NW * pp;
         p_on[pp] = u < 4 * P.NI;
-        const int piece = (u % P.NI) * 64 + lane;
-        const int rr = piece / P.NP, pc = piece - rr * P.NP;
+        const int piece = (u & (P.NI - 1)) * 64 + lane;   // (NI is 1 or 2: the launcher takes the 16-byte pieces only then)
+        const int rr = w2d_div(piece, P.d_NP), pc = piece - rr * P.NP;
         if (rr < P.WR) {
           const int gh = h0 - 1 + rr, gw = w0 - 4 + 4 * pc;
           if constexpr (X4) {
@@ -326,7 +431,7 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
               xo[pp] = hs * S.ws + c0;
 #pragma unroll
               for (int e = 0; e < 4; ++e)
-                if (mark && (c0 + e < 0 || c0 + e >= S.W)) pmask |= 1 << (8 * seg + 4 * pp + e);
+                if (c0 + e < 0 || c0 + e >= S.W) pmask |= 1 << (8 * seg + 4 * pp + e);
             }
           }
         }
@@ -334,7 +439,7 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       }
       p_on[pp] = wave8 + NW * pp < P.NPV;
       const int pos = (wave8 + NW * pp) * 64 + lane;
-      const int rr = pos / P.WCp, cc = pos - rr * P.WCp;
+      const int rr = w2d_div(pos, P.d_WCp), cc = pos - rr * P.WCp;
       if (rr < P.WR && cc < P.WC) {
         const int gh = h0 - 1 + rr, gw = w0 - 1 + cc;
         const int hs = gh - S.oh, ws = gw - S.ow;
@@ -342,23 +447,38 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       }
     }
   };
+  // unit pp of this wave, 16-byte pieces: its channel plane inside the chunk and its LDS offset inside a window image (scalars)
+  const int nis = P.NI >> 1;
+  int u_pl[2], u_lds[2];
+#pragma unroll
+  for (int pp = 0; pp < 2; ++pp) {
+    const int u = wave8 + NW * pp;
+    u_pl[pp] = u >> nis;
+    u_lds[pp] = (u >> nis) * PS + 1 + (u & (P.NI - 1)) * 256;
+  }
   int xo0[2], xo1[2];
-  seg_offsets(0, xo0, true);
-  seg_offsets(1, xo1, true);   // (U4: its pmask bits; the offsets themselves are dropped unless the block starts in the second segment)
+  seg_offsets(0, xo0);
+  seg_offsets(1, xo1);
   const int f_sw = P.src1.C > 0 ? P.src0.C / 4 : -1;           // first chunk of the second (concat) segment
+  const int c_sw = f_sw >= 0 ? f_sw : 2147483647;              // chunks >= c_sw read the second segment
   const bool start1 = SPLIT && f_sw >= 0 && c_lo >= f_sw;      // this slab's chunks all lie in the second segment
+  // U4: does any lane of the wave have outside floats to overwrite, per segment (wave-uniform: the chunks of nearly every wave skip
+  // the repair without a vector instruction)
+  // (lane counts in scalar registers, not bools: hipcc parks a wave-uniform bool that crosses the loop in a vector register)
+  int pm_any0 = U4 ? __builtin_popcountll(__builtin_amdgcn_ballot_w64((pmask & 0xff) != 0)) : 0;
+  int pm_any1 = U4 ? __builtin_popcountll(__builtin_amdgcn_ballot_w64((pmask >> 8) != 0)) : 0;
+  asm volatile("" : "+s"(pm_any0), "+s"(pm_any1));
   {
     // padding positions of the block's first segment, once, in all 2 x 4 channel planes (own positions only); visible after the first barrier
     const float pad0 = (start1 ? P.src1.relu : P.src0.relu) ? __builtin_nanf("") : 0.f;
 #pragma unroll
     for (int pp = 0; pp < 2; ++pp)
-      if (p_on[pp] && (start1 ? xo1[pp] : xo0[pp]) == W2D_PAD) {
+      if (p_on[pp] && (start1 ? xo1[pp] : xo0[pp]) == W2D_PAD) {   // (p_on is wave-uniform)
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
           if constexpr (PC) {   // the unit's own plane
-            const int u = wave8 + NW * pp;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) smem[b * BUF + WTILE + (u / P.NI) * PS + 1 + (u % P.NI) * 256 + lane * 4 + e] = pad0;
+            for (int e = 0; e < 4; ++e) smem[b * BUF + WTILE + u_lds[pp] + lane * 4 + e] = pad0;
           } else {
 #pragma unroll
             for (int ch = 0; ch < 4; ++ch) smem[b * BUF + WTILE + ch * PS + (wave8 + NW * pp) * 64 + lane] = pad0;
@@ -366,70 +486,108 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
         }
       }
   }
-  long long d_cs = start1 ? P.src1.cs : P.src0.cs;
+  // Fill addresses: a wave-uniform 64-bit base in scalar registers plus an UNSIGNED 32-bit byte offset per lane (as
+  // gsd_wgrad_w2d.hip).  The base lies 16 bytes IN FRONT of the channel plane: a U4 piece that straddles the left edge of a segment
+  // with a column offset starts up to 3 floats in front of row 0, and a zero-extended negative offset is 4 GiB away.  Advancing
+  // the plane is scalar arithmetic.  Which lanes move something is loop-invariant but for the one segment switch: an exec mask in
+  // a scalar register pair (f_msk), not a vector compare per fill.
+  long long d_csb = (start1 ? P.src1.cs : P.src0.cs) * 4;   // plane stride, bytes
   // channel plane of the next halo slot: the slab's first channel inside its segment
-  const float* d_base = (start1 ? P.src1.p + (long long)n * P.src1.ns : P.src0.p + (long long)n * P.src0.ns) +
-                        (long long)(c_lo - (start1 ? f_sw : 0)) * 4 * d_cs;
-  long long f_xl[2];   // the current segment's lane offsets as 64-bit values (the address add is then a single instruction)
+  const char* d_base = reinterpret_cast<const char*>((start1 ? P.src1.p + (long long)n * P.src1.ns : P.src0.p + (long long)n * P.src0.ns) +
+                                                     (long long)(c_lo - (start1 ? f_sw : 0)) * 4 * (d_csb >> 2)) - 16;
+  unsigned f_off[2];             // the current segment's lane offsets (W2D_OFF_PAD: a padding position)
+  unsigned long long f_msk[2];   // ... and the lanes that move a piece / pixel
+  // (an offset that moves something is >= 4: 0 stands for no position, W2D_OFF_PAD for a padding position)
+  auto off_of = [&](const int xo) { return xo == W2D_PAD ? W2D_OFF_PAD : (xo > W2D_PAD ? (unsigned)(xo + 4) * 4u : 0u); };
+  auto lane_state = [&](const unsigned (&o)[2]) __attribute__((always_inline)) {
 #pragma unroll
-  for (int pp = 0; pp < 2; ++pp) f_xl[pp] = start1 ? xo1[pp] : xo0[pp];
+    for (int pp = 0; pp < 2; ++pp) {
+      f_off[pp] = o[pp];
+      f_msk[pp] = __builtin_amdgcn_ballot_w64(p_on[pp] && o[pp] + 1u > 1u);
+      asm volatile("" : "+s"(f_msk[pp]));
+    }
+  };
+  // the second segment's lane offsets wait in LDS for the switch (own values, read back by the thread that wrote them: no barrier)
+  unsigned* const sSw = reinterpret_cast<unsigned*>(smem + 2 * BUF + 2 * Kpad + 4 * BM);   // (behind sAff [2][Kpad] and sBw [4][64])
+  {
+    const unsigned o0[2] = {off_of(xo0[0]), off_of(xo0[1])}, o1[2] = {off_of(xo1[0]), off_of(xo1[1])};
+    if constexpr (!X4) sSw[tid] = o1[0], sSw[NT + tid] = o1[1];
+    if constexpr (U4) sSw[2 * NT + tid] = (unsigned)pmask;   // (read back by the few chunks that repair a piece)
+    lane_state(start1 ? o1 : o0);
+  }
   // the switch to the second segment happens once per block, between two chunks: new plane pointer and lane offsets, and that
   // segment's padding positions are written into each LDS image the first time it is filled from it
   auto begin_fill = [&](int chunk, int buf) {
+    if constexpr (X4) return;   // (one source)
     if (f_sw < 0 || start1 || (chunk != f_sw && chunk != f_sw + 1)) return;
     if (chunk == f_sw) {
-      d_base = P.src1.p + (long long)n * P.src1.ns;
-      d_cs = P.src1.cs;
-      int xs[2];
-      seg_offsets(1, xs, false);
-#pragma unroll
-      for (int pp = 0; pp < 2; ++pp) f_xl[pp] = xs[pp];
+      d_base = reinterpret_cast<const char*>(P.src1.p + (long long)n * P.src1.ns) - 16;
+      d_csb = P.src1.cs * 4;
+      int t = tid;
+      asm volatile("" : "+v"(t));   // (or hipcc forwards the stored values to this read: through the loop, in registers)
+      const unsigned o1[2] = {sSw[t], sSw[NT + t]};
+      lane_state(o1);
     }
     const float pad1 = P.src1.relu ? __builtin_nanf("") : 0.f;
 #pragma unroll
     for (int pp = 0; pp < 2; ++pp)
-      if (p_on[pp] && f_xl[pp] == W2D_PAD) {
+      if (p_on[pp] && f_off[pp] == W2D_OFF_PAD) {
         if constexpr (PC) {
-          const int u = wave8 + NW * pp;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) smem[buf * BUF + WTILE + (u / P.NI) * PS + 1 + (u % P.NI) * 256 + lane * 4 + e] = pad1;
+          for (int e = 0; e < 4; ++e) smem[buf * BUF + WTILE + u_lds[pp] + lane * 4 + e] = pad1;
         } else {
 #pragma unroll
           for (int ch = 0; ch < 4; ++ch) smem[buf * BUF + WTILE + ch * PS + (wave8 + NW * pp) * 64 + lane] = pad1;
         }
       }
   };
+  // (the lane offset is made opaque INSIDE the predicated block: hipcc otherwise zero-extends it once, outside the loop, and adds
+  //  64-bit vector registers per fill instead of taking the scalar-base form of the instruction)
   auto halo_slot = [&](int ch, float* Xb) {   // input channel ch of the chunk: the lanes that have a pixel move it
+    const char* b = d_base;
+    asm volatile("" : "+s"(b));
 #pragma unroll
     for (int pp = 0; pp < 2; ++pp)
-      if (p_on[pp] && f_xl[pp] > W2D_PAD) __builtin_amdgcn_global_load_lds(d_base + f_xl[pp], Xb + ch * PS + (wave8 + NW * pp) * 64, 4, 0, 0);
-    d_base += d_cs;
+      if (__builtin_amdgcn_inverse_ballot_w64(f_msk[pp])) {
+        asm volatile("" : "+v"(f_off[pp]));
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const float*>(b + f_off[pp]), Xb + ch * PS + (wave8 + NW * pp) * 64, 4, 0, 0);
+      }
+    d_base += d_csb;
   };
   // X4: unit pp of this wave (one instruction of one of the chunk's four planes); d_base stays at the chunk's first plane
   auto halo_unit = [&](int pp, float* Xb) {
-    const int u = wave8 + NW * pp;
-    if (p_on[pp] && f_xl[pp] > W2D_PAD)
-      __builtin_amdgcn_global_load_lds(d_base + (u / P.NI) * d_cs + f_xl[pp], Xb + (u / P.NI) * PS + 1 + (u % P.NI) * 256, 16, 0, 0);
-    if (pp == 1) d_base += 4 * d_cs;
+    const char* b = d_base + u_pl[pp] * d_csb;
+    asm volatile("" : "+s"(b));
+    if (__builtin_amdgcn_inverse_ballot_w64(f_msk[pp])) {
+      asm volatile("" : "+v"(f_off[pp]));
+      __builtin_amdgcn_global_load_lds(reinterpret_cast<const float*>(b + f_off[pp]), Xb + u_lds[pp], 16, 0, 0);
+    }
+    if (pp == 1) d_base += 4 * d_csb;
   };
   constexpr int WPW = 24 / NW;   // 1-KiB weight pieces per wave and chunk (6)
-  const float* const wsrc0 = P.wt + (size_t)mbb * P.nchunks * WTILE + wave8 * (WPW * 256) + lane * 4;
+  const char* const wsrc0 = reinterpret_cast<const char*>(P.wt + (size_t)mbb * P.nchunks * WTILE + wave8 * (WPW * 256));
+  unsigned w_off = (unsigned)lane * 16u;
   // the wave's pieces of the 24 are adjacent: they share LDS bases (M0) and differ in the instruction's immediate offset, which
-  // moves the global and the LDS address alike
+  // moves the global and the LDS address alike; the global base is scalar, the lane's 16 bytes a constant offset
   auto weight_fill = [&](int chunk, float* Wn) {
-    const float* wg = wsrc0 + (size_t)chunk * WTILE;
+    const char* wb = wsrc0 + (size_t)chunk * (WTILE * 4);
+    asm volatile("" : "+s"(wb));
+    asm volatile("" : "+v"(w_off));
+    const float* wg = reinterpret_cast<const float*>(wb + w_off);
     float* wl = Wn + wave8 * (WPW * 256);
     __builtin_amdgcn_global_load_lds(wg, wl, 16, 0, 0);
     __builtin_amdgcn_global_load_lds(wg, wl, 16, 1024, 0);
     __builtin_amdgcn_global_load_lds(wg, wl, 16, 2048, 0);
     if constexpr (WPW == 6) {
       __builtin_amdgcn_global_load_lds(wg, wl, 16, 3072, 0);
-      __builtin_amdgcn_global_load_lds(wg + 1024, wl + 1024, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(wg + 1024, wl + 1024, 16, 1024, 0);
+      const char* wb2 = wb + 4096;
+      asm volatile("" : "+s"(wb2));
+      const float* wg2 = reinterpret_cast<const float*>(wb2 + w_off);
+      __builtin_amdgcn_global_load_lds(wg2, wl + 1024, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(wg2, wl + 1024, 16, 1024, 0);
     }
   };
 
-  const int Kpad = P.nchunks * 4;
   float* sAff = smem + 2 * BUF;
   for (int c = tid; c < Kpad; c += NT) {
     const bool first = c < P.src0.C;
@@ -460,7 +618,9 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
   //   fh = 1: A, B, C = window rows 2, 1, 3 and sg = -1   (t2 = d2 - d1, t3 = d1 - d3)
   // -- the same code for both halves, and 18 window values each (the pairing {t1, t2} / {t0, t3} would need 12 / 24).  A fused
   // multiply-add by +-1 rounds as the addition or subtraction it stands for: V is bit for bit what the channel-half split computed.
-  const int rowA = baddr + (fh ? 2 : 0) * P.WCp, rowB = baddr + (fh ? 1 : 2) * P.WCp, rowC = baddr + (fh ? 3 : 1) * P.WCp;
+  // (the rows' offsets from the lane's window corner `baddr` are scalars, added per chunk with the image's offset: one address
+  //  register held through the loop instead of three)
+  const int rowA = (2 * fh) * P.WCp, rowB = (2 - fh) * P.WCp, rowC = (1 + 2 * fh) * P.WCp;   // (arithmetic in fh: they stay scalar)
   const f32x2v sg2 = {fh ? -1.f : 1.f, fh ? -1.f : 1.f};
 
   f32x4 acc[4][12];   // [m-tile][frequency 6 r + fc of the wave's rows r = 0, 1]
@@ -472,7 +632,7 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
   // A operands: MFMA group g = 0..11 of a chunk is frequency pair g / 2 of the wave (weight-image pair 6 fh + g / 2) for two m-tiles
   // of the pair's two frequencies -- one ds_read_b128 (16 lanes read 256 contiguous bytes), four MFMAs.  acc[0..1] are the m-tiles the
   // wave keeps (2 fh, 2 fh + 1: the even groups read that half of the image pair), acc[2..3] the two it hands to its partner.
-  const int a_keep = (j * 12 + fh * 6) * 128 + l16 * 4 + fh * 64, a_give = a_keep + (fh ? -64 : 64);
+  const int a_keep = (j * 12 + fh * 6) * 128 + l16 * 4 + fh * 64, a_give = 64 - 128 * fh;   // (a_give: scalar, from a_keep)
   begin_fill(c_lo, 0);
   weight_fill(c_lo, smem);
   if constexpr (PC) {
@@ -490,14 +650,16 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
     if constexpr (U4) {
       __builtin_amdgcn_s_waitcnt(0x0F70);   // this wave's fills of the chunk have landed
       // the outside floats of the straddling pieces this lane moved (the lane state still is the one the chunk was filled with)
-      const bool seg1 = f_sw >= 0 && chunk >= f_sw;
-      const int pm = seg1 ? pmask >> 8 : pmask & 0xff;
-      if (pm != 0) {
+      const bool seg1 = chunk >= c_sw;
+      if ((seg1 ? pm_any1 : pm_any0) != 0) {
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        const int pmk = (int)sSw[2 * NT + t];
+        const int pm = seg1 ? pmk >> 8 : pmk & 0xff;
         const float padv = (seg1 ? P.src1.relu : P.src0.relu) ? __builtin_nanf("") : 0.f;
 #pragma unroll
         for (int pp = 0; pp < 2; ++pp) {
-          const int u = wave8 + NW * pp;
-          float* pq = smem + cur * BUF + WTILE + (u / P.NI) * PS + 1 + (u % P.NI) * 256 + lane * 4;
+          float* pq = smem + cur * BUF + WTILE + u_lds[pp] + lane * 4;
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             if (pm >> (4 * pp + e) & 1) pq[e] = padv;
@@ -511,23 +673,26 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
     float sc = 1.f, sh = 0.f, lo = 0.f;
     if constexpr (!PLAIN) {
       sc = sAff[kc], sh = sAff[Kpad + kc];
-      lo = kc < P.src0.C ? lo0 : (kc < P.Cin ? lo1 : -__builtin_inff());
+      lo = chunk < c_sw ? lo0 : lo1;   // (a chunk lies inside one segment and Cin is a multiple of 4: a scalar select)
     }
-    const bool more = chunk + 1 < c_hi;
+    int more = (chunk + 1 - c_hi) >> 31;   // chunk + 1 < c_hi, as an integer made scalar by hand: hipcc carries the bool through a vector register to branch on it, twice
+    more = __builtin_amdgcn_readfirstlane(more);
     // the image's offset as an opaque scalar: the LDS bases of the two images are then one set of registers plus an addition each,
     // not two sets held through the loop (registers the accumulators need)
-    int ioff = cur * BUF;
-    __asm__ volatile("" : "+s"(ioff));
+    int ioff = cur * BUF, ioA = cur * BUF + rowA, ioB = cur * BUF + rowB, ioC = cur * BUF + rowC, ioG = cur * BUF + a_give;
+    __asm__ volatile("" : "+s"(ioff), "+s"(ioA), "+s"(ioB), "+s"(ioC), "+s"(ioG));
     const float* Wc = smem + ioff;
-    auto load_row = [&](const int addr, float (&r)[6]) {
-      const f32x4 ra = *reinterpret_cast<const f32x4*>(&Wc[addr]);
-      const f32x2v rb = *reinterpret_cast<const f32x2v*>(&Wc[addr + 4]);
+    const float* Wg = smem + ioG;
+    auto load_row = [&](const int io, float (&r)[6]) {
+      const float* Wr = smem + io;
+      const f32x4 ra = *reinterpret_cast<const f32x4*>(&Wr[baddr]);
+      const f32x2v rb = *reinterpret_cast<const f32x2v*>(&Wr[baddr + 4]);
       r[0] = ra[0], r[1] = ra[1], r[2] = ra[2], r[3] = ra[3], r[4] = rb[0], r[5] = rb[1];
     };
     float dA[6], dB[6], dC[6];
-    load_row(rowA, dA);
-    load_row(rowB, dB);
-    load_row(rowC, dC);
+    load_row(ioA, dA);
+    load_row(ioB, dB);
+    load_row(ioC, dC);
     f32x4 av[2];   // read one group (four MFMAs) ahead
     av[0] = *reinterpret_cast<const f32x4*>(&Wc[a_keep]);
     auto affine = [&](float (&r)[6]) {
@@ -592,7 +757,7 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
 #pragma unroll
     for (int g = 0; g < 12; ++g) {
       const int r = g / 6, fe = (g >> 1) * 2 - 6 * r, mt = 2 * (g & 1);
-      if (g + 1 < 12) av[(g + 1) & 1] = *reinterpret_cast<const f32x4*>(&Wc[((g + 1) & 1 ? a_give : a_keep) + ((g + 1) >> 1) * 128]);
+      if (g + 1 < 12) av[(g + 1) & 1] = *reinterpret_cast<const f32x4*>(&((g + 1) & 1 ? Wg : Wc)[a_keep + ((g + 1) >> 1) * 128]);
       const f32x4& ap = av[g & 1];
       acc[mt][6 * r + fe] = mfma16(ap[0], v[r][fe], acc[mt][6 * r + fe]);
       acc[mt + 1][6 * r + fe] = mfma16(ap[1], v[r][fe], acc[mt + 1][6 * r + fe]);
@@ -604,7 +769,9 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       if (piece == 2) rt_a(tB, acB, beB);
       if (piece == 3) rt_b(acB, beB, v[1]);
       if (piece == 4) rt_c(tB, v[1]);
-      if (more && g < 3) {
+      int more_g = more;   // (opaque per group: one scalar compare each instead of a lane mask carried from group to group)
+      asm volatile("" : "+s"(more_g));
+      if (g < 3 && more_g != 0) {
         float* Wn = smem + (cur ^ 1) * BUF;
         if (g == 0) {
           begin_fill(chunk + 1, cur ^ 1);
@@ -651,16 +818,19 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
     }
   }
 
-  // Y = A2^T M A4 of one channel's tile: down the columns first (24 -> 12 values), then along the rows (12 -> 2 x 4 outputs)
-  // (HI: a wave of the second frequency half, whose acc[m] hold rows 2, 3 and acc[2 + m] rows 0, 1 -- two copies of the epilogue
-  // behind a wave-uniform branch rather than a register shuffle)
-  auto out_transform = [&](auto hi_c, int m, int reg, float (&y)[2][4]) __attribute__((always_inline)) {
+  // Y = A2^T M A4 of one tile: down the columns first (24 -> 12 values), then along the rows (12 -> 2 x 4 outputs), two channels at
+  // once: accumulator registers (r0, r0 + 1) of a quad are an aligned pair, so the additions and fused multiply-adds run as
+  // v_pk_add_f32 / v_pk_fma_f32.
+  // (HI: a wave of the second frequency half, whose acc[m] hold rows 2, 3 and acc[2 + m] rows 0, 1 -- two copies of the TRANSFORM
+  // behind a wave-uniform branch rather than a register shuffle; the stores and statistics behind it exist once per path)
+  // (j and l16 again from the thread id: cheaper than two registers held through the loop)
+  int tid_e = tid;
+  asm volatile("" : "+v"(tid_e));
+  const int j_e = (tid_e & 63) >> 4, l16_e = tid_e & 15, q_e = ph * 16 + l16_e;
+  auto out_pair = [&](auto hi_c, const int p, float (&y)[2][2][4]) __attribute__((always_inline)) {
     constexpr bool HI = decltype(hi_c)::value;
+    const int m = p >> 1, r0 = (p & 1) * 2;
     const int lo = HI ? 2 + m : m, hi = HI ? m : 2 + m;
-    // two channels at once: accumulator registers (2 rp, 2 rp + 1) of a quad are an aligned pair, so the same additions and fused
-    // multiply-adds run as v_pk_add_f32 / v_pk_fma_f32; an odd reg takes the second halves of what its even neighbour computed
-    // (the compiler merges the two calls' identical packed instructions)
-    const int r0 = reg & ~1;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
       f32x2v R[6];
@@ -674,33 +844,34 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       const f32x2v c2 = {2.f, 2.f}, c4 = {4.f, 4.f}, c8 = {8.f, 8.f};
       const f32x2v y0 = R[0] + p12 + p34, y1 = __builtin_elementwise_fma(c2, m34, m12), y2 = __builtin_elementwise_fma(c4, p34, p12);
       const f32x2v y3 = __builtin_elementwise_fma(c8, m34, m12) + R[5];
-      y[a][0] = y0[reg & 1], y[a][1] = y1[reg & 1], y[a][2] = y2[reg & 1], y[a][3] = y3[reg & 1];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) y[e][a][0] = y0[e], y[e][a][1] = y1[e], y[e][a][2] = y2[e], y[e][a][3] = y3[e];
     }
+  };
+  auto get_pair = [&](const int p, float (&y)[2][2][4]) __attribute__((always_inline)) {
+    if (fh == 0)
+      out_pair(std::false_type{}, p, y);
+    else
+      out_pair(std::true_type{}, p, y);
   };
 
-  auto finish = [&](auto hi_c) __attribute__((always_inline)) {
-    auto get_y = [&](int m, int reg, float (&y)[2][4]) __attribute__((always_inline)) { out_transform(hi_c, m, reg, y); };
-    if constexpr (SPLIT) {
-      // the un-reduced outputs of this slab: 32 bytes per lane and channel, 512-byte runs per 16 lanes
-      float* const sl = P.slabs + ((size_t)((size_t)pt * P.nslab + slab) * P.mblocks + mbb) * (size_t)(BM * 128 * NWP);
+  if constexpr (SPLIT) {
+    // the un-reduced outputs of this slab: 32 bytes per lane and channel, 512-byte runs per 16 lanes
+    float* const sl = P.slabs + ((size_t)((size_t)pt * P.nslab + slab) * P.mblocks + mbb) * (size_t)(BM * 128 * NWP);
 #pragma unroll
-      for (int m = 0; m < 2; ++m)
+    for (int p = 0; p < 4; ++p) {
+      float y[2][2][4];
+      get_pair(p, y);
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          float y[2][4];
-          get_y(m, reg, y);
-          float* const o = sl + ((size_t)(fh * 32 + m * 16 + j * 4 + reg) * (16 * NWP) + q) * 8;
-          *reinterpret_cast<f32x4*>(o) = f32x4{y[0][0], y[0][1], y[0][2], y[0][3]};
-          *reinterpret_cast<f32x4*>(o + 4) = f32x4{y[1][0], y[1][1], y[1][2], y[1][3]};
-        }
-    } else {
-      w2d_epilogue(P, sBw, n, h0, w0, tr2, tq, vmask, m0, fh, ph, j, l16, pt, get_y);
+      for (int e = 0; e < 2; ++e) {
+        float* const o = sl + ((size_t)(fh * 32 + (p >> 1) * 16 + j_e * 4 + (p & 1) * 2 + e) * (16 * NWP) + q_e) * 8;
+        *reinterpret_cast<f32x4*>(o) = f32x4{y[e][0][0], y[e][0][1], y[e][0][2], y[e][0][3]};
+        *reinterpret_cast<f32x4*>(o + 4) = f32x4{y[e][1][0], y[e][1][1], y[e][1][2], y[e][1][3]};
+      }
     }
-  };
-  if (fh == 0)
-    finish(std::false_type{});
-  else
-    finish(std::true_type{});
+  } else {
+    w2d_epilogue(P, sBw, n, h0, w0, geo & 255, geo >> 8 & 255, geo >> 16 & 255, m0, fh, ph, j_e, l16_e, pt, get_pair);
+  }
 }
 
 // The second half of a K-slab launch: one block per (pixel tile, m-block) with the conv kernel's thread -> (tile, channel) map adds
@@ -713,17 +884,17 @@ __global__ __launch_bounds__(128 * NWP) void w2d_slab_reduce_kernel(const W2DPar
   const int ph = wave8 % NWP, mh = wave8 / NWP;
   const int j = lane >> 4, l16 = lane & 15;
   const int lid = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int mbb = lid % P.mblocks;
-  const int pt = lid / P.mblocks;
+  const int pt = w2d_div(lid, P.d_mblocks);
+  const int mbb = lid - pt * P.mblocks;
   const int m0 = mbb * BM;
   const int tpi = P.tiles_y * P.tiles_x;
-  const int n = pt / tpi;
+  const int n = w2d_div(pt, P.d_tpi);
   const int rt = pt - n * tpi;
-  const int ty = rt / P.tiles_x;
+  const int ty = w2d_div(rt, P.d_tiles_x);
   const int h0 = ty * P.TH, w0 = (rt - ty * P.tiles_x) * P.TW;
   const int q = ph * 16 + l16;
   const bool q_ok = q < (P.TH >> 1) * P.TWq && q < 16 * NWP;
-  const int tr2 = q_ok ? q / P.TWq : 0;
+  const int tr2 = q_ok ? q >> P.TWq_sh : 0;
   const int tq = q_ok ? q - tr2 * P.TWq : 0;
   int vmask = 0;
   if (q_ok) {
@@ -747,18 +918,21 @@ __global__ __launch_bounds__(128 * NWP) void w2d_slab_reduce_kernel(const W2DPar
   }
   const size_t tile_elems = (size_t)(BM * 128 * NWP);
   const float* const s0 = P.slabs + ((size_t)pt * P.nslab * P.mblocks + mbb) * tile_elems;
-  auto get_y = [&](int m, int reg, float (&y)[2][4]) __attribute__((always_inline)) {
-    const float* o = s0 + ((size_t)(mh * 32 + m * 16 + j * 4 + reg) * (16 * NWP) + q) * 8;
-    f32x4 a = *reinterpret_cast<const f32x4*>(o), b = *reinterpret_cast<const f32x4*>(o + 4);
-    for (int s = 1; s < P.nslab; ++s) {
-      o += (size_t)P.mblocks * tile_elems;
-      a += *reinterpret_cast<const f32x4*>(o);
-      b += *reinterpret_cast<const f32x4*>(o + 4);
+  auto get_pair = [&](const int p, float (&y)[2][2][4]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const float* o = s0 + ((size_t)(mh * 32 + (p >> 1) * 16 + j * 4 + (p & 1) * 2 + e) * (16 * NWP) + q) * 8;
+      f32x4 a = *reinterpret_cast<const f32x4*>(o), b = *reinterpret_cast<const f32x4*>(o + 4);
+      for (int s = 1; s < P.nslab; ++s) {
+        o += (size_t)P.mblocks * tile_elems;
+        a += *reinterpret_cast<const f32x4*>(o);
+        b += *reinterpret_cast<const f32x4*>(o + 4);
+      }
+      y[e][0][0] = a[0], y[e][0][1] = a[1], y[e][0][2] = a[2], y[e][0][3] = a[3];
+      y[e][1][0] = b[0], y[e][1][1] = b[1], y[e][1][2] = b[2], y[e][1][3] = b[3];
     }
-    y[0][0] = a[0], y[0][1] = a[1], y[0][2] = a[2], y[0][3] = a[3];
-    y[1][0] = b[0], y[1][1] = b[1], y[1][2] = b[2], y[1][3] = b[3];
   };
-  w2d_epilogue(P, sBw, n, h0, w0, tr2, tq, vmask, m0, mh, ph, j, l16, pt, get_y);
+  w2d_epilogue(P, sBw, n, h0, w0, tr2, tq, vmask, m0, mh, ph, j, l16, pt, get_pair);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -937,6 +1111,10 @@ static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   GSD_REQUIRE(gsd_conv3x3_w2d_supported(Cin, src[0].C), GSD_ERR_UNSUPPORTED,
               "gsd_conv3x3_w2d: Cin=%d and the first segment's %d channels must be multiples of 4 (use gsd_conv3x3_w43)", Cin, src[0].C);
 
+  // (fills address a plane by an unsigned 32-bit BYTE offset from 16 bytes in front of it)
+  for (int i = 0; i < nsrc; ++i)
+    GSD_REQUIRE((int64_t)src[i].H * src[i].w_stride + 4 < (1LL << 30), GSD_ERR_UNSUPPORTED,
+                "gsd_conv3x3_w2d: a source plane must stay below 2^30 floats");
   W2DPlan pl;
   GSD_REQUIRE(plan_w2d(N, H, W, Cout, &pl), GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w2d: no tile shape");
   W2DParams P;
@@ -967,6 +1145,15 @@ static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   P.slabs = S > 1 ? ws : nullptr;
   if (S > 1) GSD_REQUIRE(((uintptr_t)ws & 15) == 0, GSD_ERR_BAD_ARG, "gsd_conv3x3_w2d: the K-slab workspace must be 16-byte aligned");
   const long grid = base * S;
+  P.d_mblocks = w2d_div_of(P.mblocks);
+  P.d_nslab = w2d_div_of(S);
+  P.d_tpi = w2d_div_of(pl.tiles_y * pl.tiles_x);
+  P.d_tiles_x = w2d_div_of(pl.tiles_x);
+  P.TWq_sh = pl.TWq == 2 ? 1 : pl.TWq == 4 ? 2 : pl.TWq == 8 ? 3 : 4;
+  P.dfast = 0;
+  for (int i = 0; i < ndst; ++i)
+    // (the largest lane offset: 12 planes further, the last tile row, in bytes)
+    if (4 * (12 * (int64_t)dst[i].c_stride + (int64_t)dst[i].H * dst[i].w_stride) < (1LL << 32)) P.dfast |= 1 << i;
   GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_w2d: grid too large");
   bool plain = true;
   for (int i = 0; i < nsrc; ++i) plain = plain && src[i].scale == nullptr && src[i].relu == 0;
@@ -987,7 +1174,9 @@ static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
     P.WCp = 4 * P.NP;
     P.PS = w2d_x4_plane_stride(pl.TWq, P.WCp, P.WR);
   }
-  const size_t lds = (size_t)(2 * (W2D_WTILE + 4 * P.PS) + 2 * 4 * P.nchunks + 4 * W2D_BM) * sizeof(float);
+  P.d_NP = w2d_div_of(P.NP);
+  P.d_WCp = w2d_div_of(P.WCp);
+  const size_t lds = (size_t)(2 * (W2D_WTILE + 4 * P.PS) + 2 * 4 * P.nchunks + 4 * W2D_BM + 3 * 128 * NWP) * sizeof(float);
   if (gsd_env_set("GSD_W2D_TRACE"))
     fprintf(stderr, "w2d M%d K%d %dx%d N%d nsrc %d ndst %d plain %d x4 %d u4 %d | ptr&15 %d ws %d cs%%4 %d ns%%4 %d NI %d tile %dx%d slabs %d\n", Cout, Cin, H, W, N,
             nsrc, ndst, (int)plain, (int)x4, (int)u4, (int)((uintptr_t)src[0].ptr & 15), src[0].w_stride, (int)(src[0].c_stride % 4),
