@@ -425,7 +425,7 @@ int gsd_ctgemm_partial_rows(int N, int H, int W, int M) {
 }
 
 // the operand conditions of a shape gsd_ctgemm_shape accepted: 32-bit element offsets, the four taps are the 2 x 2 block at (oy, ox)
-// and stay inside the buffer (the kernel has no zero line)
+// and stay inside the buffer (the kernel has no zero line), and the dX output buffer has exactly the GEMM's pixel grid
 bool gsd_ctgemm_operands(const gsd_nhwc* in, const gsd_nhwc* out, const gsd_bf16_bnbwd* bw, int ntaps, const int* ty, const int* tx, int H,
                          int W) {
   // 32-bit BYTE offsets per pixel, also for the (up to 512) pixel slots past the last item's end: (pixels + 512) * pitch * 2 < 2^32
@@ -433,6 +433,7 @@ bool gsd_ctgemm_operands(const gsd_nhwc* in, const gsd_nhwc* out, const gsd_bf16
   if (!fits(in) || !fits(out)) return false;
   if (bw != nullptr && !fits(bw->y)) return false;
   if (ntaps == 1) return ty[0] == 0 && tx[0] == 0 && in->H == H && in->W == W;
+  if (out->H != H || out->W != W) return false;   // the dX epilogue addresses out by the flattened pixel index: out is the pixel grid
   const int oy = ty[0], ox = tx[0];
   if (oy < 0 || ox < 0 || ty[1] != oy || tx[1] != ox + 1 || ty[2] != oy + 1 || tx[2] != ox || ty[3] != oy + 1 || tx[3] != ox + 1) return false;
   return 2 * (H - 1) + oy + 1 < in->H && 2 * (W - 1) + ox + 1 < in->W;

@@ -157,6 +157,9 @@ def test_weight_images_batched_equal_one_by_one():
 
 
 def test_dense_1x1_and_convT_bf16():
+    """The 1x1, the ConvT forward (Cin 64 -> Cout 32: M = 128) and its dX (M = 64) at one small shape each.  These shapes stay on
+    the general kernel gconv_bf16_kernel<1, ..>; the large-tile ConvT kernels (gsd_bf16_ctgemm.hip) and every tile of the general
+    one are checked element-wise against fp64 in tests/test_gpu_bf16_tile_forms_fp64.py."""
     L = _lib()
     g = torch.Generator().manual_seed(5)
     # 1x1 (the im2col'd first layer): K 32 -> M 64
@@ -228,6 +231,9 @@ T3X = [t % 3 - 1 for t in range(9)]
     (1, 40, 53, 128, 256, 128, 0),     # two m-blocks
 ])
 def test_wgrad_conv3x3_bf16(n, h, w, cin, cout, b_tot, b_off):
+    """conv3x3 dW at four shapes of the general kernel gwgrad_bf16_kernel<1, 9, ..>, to a bound tied to the largest element; which
+    tile each (HALO, T, block) form picks, and a per-element fp64 bound for both tile widths of every form, are in
+    tests/test_gpu_bf16_tile_forms_fp64.py."""
     L = _lib()
     g = torch.Generator().manual_seed(h * 100 + cout)
     a_in = bf16r(torch.randn((n, cin, h, w), generator=g))
@@ -240,6 +246,9 @@ def test_wgrad_conv3x3_bf16(n, h, w, cin, cout, b_tot, b_off):
 
 
 def test_wgrad_first_layer_and_convT_bf16():
+    """The 1-tap (first layer) and the 4-tap stride-2 (ConvT, Cin 64 -> Cout 32) dW.  Ncols = 32 keeps the ConvT shape on the
+    general kernel gwgrad_bf16_kernel<0, 4, ..>; the large-tile form gwgrad_big_bf16_kernel (M % 128 == 0, Ncols % 64 == 0) is
+    checked against fp64 in tests/test_gpu_bf16_tile_forms_fp64.py."""
     L = _lib()
     g = torch.Generator().manual_seed(9)
     # first layer: dy (64 ch) against the im2col'd 3-channel input produced by gsd_bf16_im2col3x3
