@@ -33,6 +33,34 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
 }
 
+// ---- 8-wide pieces: a thread's 16 bytes of a pixel (8 consecutive channels) ------------------------------------------------
+__device__ __forceinline__ void unpack8(const uint4 v, float f[8]) {
+  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
+  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
+  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
+  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
+}
+__device__ __forceinline__ uint4 pack8(const float f[8]) {
+  return make_uint4(pack_bf16(f[0], f[1]), pack_bf16(f[2], f[3]), pack_bf16(f[4], f[5]), pack_bf16(f[6], f[7]));
+}
+__device__ __forceinline__ uint4 ld16(const u16* p) { return *reinterpret_cast<const uint4*>(p); }
+__device__ __forceinline__ void st16(u16* p, uint4 v) { *reinterpret_cast<uint4*>(p) = v; }
+
+// ---- 4-wide pieces: the four channels of one MFMA result register group, two packed words ------------------------------
+__device__ __forceinline__ void unpack4(unsigned lo, unsigned hi, float f[4]) {
+  f[0] = __uint_as_float(lo << 16); f[1] = __uint_as_float(lo & 0xffff0000u);
+  f[2] = __uint_as_float(hi << 16); f[3] = __uint_as_float(hi & 0xffff0000u);
+}
+// statistics of the values as stored (what the BatchNorm kernel will read back): s1 += q, s2 += q * q
+__device__ __forceinline__ void stats4_stored(unsigned lo, unsigned hi, float (&s1)[4], float (&s2)[4]) {
+  const float q0 = __uint_as_float(lo << 16), q1 = __uint_as_float(lo & 0xffff0000u);
+  const float q2 = __uint_as_float(hi << 16), q3 = __uint_as_float(hi & 0xffff0000u);
+  s1[0] += q0; s2[0] = fmaf(q0, q0, s2[0]);
+  s1[1] += q1; s2[1] = fmaf(q1, q1, s2[1]);
+  s1[2] += q2; s2[2] = fmaf(q2, q2, s2[2]);
+  s1[3] += q3; s2[3] = fmaf(q3, q3, s2[3]);
+}
+
 // ReLU of two packed bf16 values: as 16-bit integers a bf16 is negative exactly when its sign bit is set, so a packed signed
 // max with 0 clears the negative ones (and turns -0 into +0, as fmaxf(x, 0) does); one instruction for two values
 __device__ __forceinline__ unsigned relu_pk_bf16(unsigned v) {

@@ -425,18 +425,16 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
             const int cl = wm * 64 + (m >> 1) * 32 + g * 8 + (m & 1) * 4;
             const f32x4 sc = *reinterpret_cast<const f32x4*>(sBw + cl), sh = *reinterpret_cast<const f32x4*>(sBw + BM + cl);
             const f32x4 mu = *reinterpret_cast<const f32x4*>(sBw + 2 * BM + cl), is = *reinterpret_cast<const f32x4*>(sBw + 3 * BM + cl);
-            const unsigned y01 = yr[tt][m >> 1][(m & 1) * 2], y23 = yr[tt][m >> 1][(m & 1) * 2 + 1];
-            float yv[4] = {__uint_as_float(y01 << 16), __uint_as_float(y01 & 0xffff0000u), __uint_as_float(y23 << 16),
-                           __uint_as_float(y23 & 0xffff0000u)};
-            float dz[4];
+            float yv[4], dz[4];
+            unpack4(yr[tt][m >> 1][(m & 1) * 2], yr[tt][m >> 1][(m & 1) * 2 + 1], yv);
 #pragma unroll
             for (int e = 0; e < 4; ++e) dz[e] = fmaf(yv[e], sc[e], sh[e]) > 0.f ? acc[m][t][e] : 0.f;
             const unsigned lo = pack_bf16(dz[0], dz[1]), hi = pack_bf16(dz[2], dz[3]);
             pk[2 * m] = lo;
             pk[2 * m + 1] = hi;
             if (ch_ok[m >> 1] && pix_ok) {
-              const float q[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16),
-                                  __uint_as_float(hi & 0xffff0000u)};   // sums of the values as stored
+              float q[4];
+              unpack4(lo, hi, q);   // sums of the values as stored
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 s1[m][e] += q[e];
@@ -471,14 +469,7 @@ __global__ __launch_bounds__(256) void gconv_bf16_kernel(const GConvP P) {
           const unsigned hi = pack_bf16(v[2], v[3]);
           pk[2 * m] = lo;
           pk[2 * m + 1] = hi;
-          if (ch_ok[m >> 1] && pix_ok && P.partials != nullptr) {   // statistics of the values as stored (what the BatchNorm kernel will read back)
-            const float q0 = __uint_as_float(lo << 16), q1 = __uint_as_float(lo & 0xffff0000u);
-            const float q2 = __uint_as_float(hi << 16), q3 = __uint_as_float(hi & 0xffff0000u);
-            s1[m][0] += q0; s2[m][0] = fmaf(q0, q0, s2[m][0]);
-            s1[m][1] += q1; s2[m][1] = fmaf(q1, q1, s2[m][1]);
-            s1[m][2] += q2; s2[m][2] = fmaf(q2, q2, s2[m][2]);
-            s1[m][3] += q3; s2[m][3] = fmaf(q3, q3, s2[m][3]);
-          }
+          if (ch_ok[m >> 1] && pix_ok && P.partials != nullptr) stats4_stored(lo, hi, s1[m], s2[m]);
         }
         if (ch_ok[0] && pix_ok) *reinterpret_cast<u32x4s*>(ot + ooff[0]) = u32x4{pk[0], pk[1], pk[2], pk[3]};
         if (ch_ok[1] && pix_ok) *reinterpret_cast<u32x4s*>(ot + ooff[1]) = u32x4{pk[4], pk[5], pk[6], pk[7]};

@@ -272,17 +272,14 @@ __global__ __launch_bounds__(512) void ctgemm_bf16_kernel(const CtP P) {
               for (int mm = 0; mm < 2; ++mm) {
                 const int m = 2 * k + mm;
                 const f32x4 nm = *reinterpret_cast<const f32x4*>(cf + 2 * BM + mm * 4), is = *reinterpret_cast<const f32x4*>(cf + 3 * BM + mm * 4);
-                const unsigned y01 = yr[tt][mm * 2], y23 = yr[tt][mm * 2 + 1];
-                float yv[4] = {__uint_as_float(y01 << 16), __uint_as_float(y01 & 0xffff0000u), __uint_as_float(y23 << 16),
-                               __uint_as_float(y23 & 0xffff0000u)};
-                float dz[4];
+                float yv[4], dz[4], q[4];
+                unpack4(yr[tt][mm * 2], yr[tt][mm * 2 + 1], yv);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) dz[e] = (fmaf(yv[e], sc[mm][e], sh[mm][e]) > 0.f && pix_ok) ? acc[m][t][e] : 0.f;
                 const unsigned lo = pack_bf16(dz[0], dz[1]), hi = pack_bf16(dz[2], dz[3]);
                 pk[2 * mm] = lo;
                 pk[2 * mm + 1] = hi;
-                const float q[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16),
-                                    __uint_as_float(hi & 0xffff0000u)};   // sums of the values as stored
+                unpack4(lo, hi, q);   // sums of the values as stored
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                   s1[mm][e] += q[e];

@@ -155,9 +155,8 @@ __global__ __launch_bounds__(256, FM == FM_BWD ? 2 : 3) void conv_first_bf16_ker
             const int c = (m >> 1) * 32 + ch0 + (m & 1) * 4;
             const f32x4 sc = *reinterpret_cast<const f32x4*>(sBw + c), sh = *reinterpret_cast<const f32x4*>(sBw + 64 + c);
             const f32x4 mu = *reinterpret_cast<const f32x4*>(sBw + 128 + c), is = *reinterpret_cast<const f32x4*>(sBw + 192 + c);
-            const unsigned d01 = da[m >> 1][(m & 1) * 2], d23 = da[m >> 1][(m & 1) * 2 + 1];
-            const float dv[4] = {__uint_as_float(d01 << 16), __uint_as_float(d01 & 0xffff0000u), __uint_as_float(d23 << 16),
-                                 __uint_as_float(d23 & 0xffff0000u)};
+            float dv[4];
+            unpack4(da[m >> 1][(m & 1) * 2], da[m >> 1][(m & 1) * 2 + 1], dv);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const float yv = bf16_to_f32(f32_to_bf16(acc[e]));
@@ -176,14 +175,7 @@ __global__ __launch_bounds__(256, FM == FM_BWD ? 2 : 3) void conv_first_bf16_ker
           const unsigned lo = pack_bf16(acc[0], acc[1]), hi = pack_bf16(acc[2], acc[3]);
           pk[2 * m] = lo;
           pk[2 * m + 1] = hi;
-          if (!EP && P.partials != nullptr && w < P.W) {   // statistics of the values as stored
-            const float q0 = __uint_as_float(lo << 16), q1 = __uint_as_float(lo & 0xffff0000u);
-            const float q2 = __uint_as_float(hi << 16), q3 = __uint_as_float(hi & 0xffff0000u);
-            s1[m][0] += q0; s2[m][0] = fmaf(q0, q0, s2[m][0]);
-            s1[m][1] += q1; s2[m][1] = fmaf(q1, q1, s2[m][1]);
-            s1[m][2] += q2; s2[m][2] = fmaf(q2, q2, s2[m][2]);
-            s1[m][3] += q3; s2[m][3] = fmaf(q3, q3, s2[m][3]);
-          }
+          if (!EP && P.partials != nullptr && w < P.W) stats4_stored(lo, hi, s1[m], s2[m]);
         }
         if (FM == FM_STORE || FM == FM_EVAL) {
           if (MT == 4) {   // whole 128-byte lines per instruction (gsd_line_pieces): pixels 0..7 of the step, then 8..15
@@ -357,10 +349,8 @@ __global__ __launch_bounds__(256) void wgrad_first_bf16_kernel(const WgFirstBP P
           const f32x4 sc = *reinterpret_cast<const f32x4*>(sCf + c), sh = *reinterpret_cast<const f32x4*>(sCf + 64 + c);
           const f32x4 mu = *reinterpret_cast<const f32x4*>(sCf + 128 + c), is = *reinterpret_cast<const f32x4*>(sCf + 192 + c);
           const f32x4 k1 = *reinterpret_cast<const f32x4*>(sCf + 256 + c), k2 = *reinterpret_cast<const f32x4*>(sCf + 320 + c);
-          const unsigned d01 = da[m >> 1][(m & 1) * 2], d23 = da[m >> 1][(m & 1) * 2 + 1];
-          const float dv[4] = {__uint_as_float(d01 << 16), __uint_as_float(d01 & 0xffff0000u), __uint_as_float(d23 << 16),
-                               __uint_as_float(d23 & 0xffff0000u)};
-          float d[4];
+          float dv[4], d[4];
+          unpack4(da[m >> 1][(m & 1) * 2], da[m >> 1][(m & 1) * 2 + 1], dv);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float yv = bf16_to_f32(f32_to_bf16(acc[e]));                     // y as the forward would have stored it
@@ -387,16 +377,10 @@ __global__ __launch_bounds__(256) void wgrad_first_bf16_kernel(const WgFirstBP P
         for (int i = 0; i < 8; ++i) d[i] = 0.f;
         if (h < P.H && w < P.W && gk_ok) {
           const long long pix = ((long long)n * P.H + h) * P.W + w;
-          const uint4 dv = *reinterpret_cast<const uint4*>(P.dz + pix * P.dz_pitch + gk * 8);
-          d[0] = __uint_as_float(dv.x << 16); d[1] = __uint_as_float(dv.x & 0xffff0000u);
-          d[2] = __uint_as_float(dv.y << 16); d[3] = __uint_as_float(dv.y & 0xffff0000u);
-          d[4] = __uint_as_float(dv.z << 16); d[5] = __uint_as_float(dv.z & 0xffff0000u);
-          d[6] = __uint_as_float(dv.w << 16); d[7] = __uint_as_float(dv.w & 0xffff0000u);
+          unpack8(ld16(P.dz + pix * P.dz_pitch + gk * 8), d);
           if (fused) {
-            const uint4 yv4 = *reinterpret_cast<const uint4*>(P.y + pix * P.y_pitch + gk * 8);
-            const float yv[8] = {__uint_as_float(yv4.x << 16), __uint_as_float(yv4.x & 0xffff0000u), __uint_as_float(yv4.y << 16),
-                                 __uint_as_float(yv4.y & 0xffff0000u), __uint_as_float(yv4.z << 16), __uint_as_float(yv4.z & 0xffff0000u),
-                                 __uint_as_float(yv4.w << 16), __uint_as_float(yv4.w & 0xffff0000u)};
+            float yv[8];
+            unpack8(ld16(P.y + pix * P.y_pitch + gk * 8), yv);
   #pragma unroll
             for (int i = 0; i < 8; ++i) {      // the expression of bn_bwd_apply_bf16_kernel, rounded to bf16 as it stores it
               const float xh = (yv[i] - mu[i]) * is[i];
@@ -404,8 +388,7 @@ __global__ __launch_bounds__(256) void wgrad_first_bf16_kernel(const WgFirstBP P
             }
           }
         }
-        *reinterpret_cast<uint4*>(dl + pxl * G_RS + gk * 16) =
-            make_uint4(pack_bf16(d[0], d[1]), pack_bf16(d[2], d[3]), pack_bf16(d[4], d[5]), pack_bf16(d[6], d[7]));
+        *reinterpret_cast<uint4*>(dl + pxl * G_RS + gk * 16) = pack8(d);
       }
     }
     __syncthreads();

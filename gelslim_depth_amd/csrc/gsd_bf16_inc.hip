@@ -338,14 +338,7 @@ __global__ __launch_bounds__(512) void inc_fused_bf16_kernel(const IncP P) {
           const unsigned lo = pack_bf16(v[0], v[1]), hi = pack_bf16(v[2], v[3]);
           pk[2 * m] = lo;
           pk[2 * m + 1] = hi;
-          if (ok) {
-            const float q0 = __uint_as_float(lo << 16), q1 = __uint_as_float(lo & 0xffff0000u);
-            const float q2 = __uint_as_float(hi << 16), q3 = __uint_as_float(hi & 0xffff0000u);
-            s1[m][0] += q0; s2[m][0] = fmaf(q0, q0, s2[m][0]);
-            s1[m][1] += q1; s2[m][1] = fmaf(q1, q1, s2[m][1]);
-            s1[m][2] += q2; s2[m][2] = fmaf(q2, q2, s2[m][2]);
-            s1[m][3] += q3; s2[m][3] = fmaf(q3, q3, s2[m][3]);
-          }
+          if (ok) stats4_stored(lo, hi, s1[m], s2[m]);   // statistics of the values as stored
         }
         if (ok) {
           u16* o = y_o0 + t * y_row;
