@@ -149,6 +149,10 @@ SIGNATURES = {
     "gsd_bn_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "gsd_sum_planes": (_I, [_P, _I, _I, _L, _P, _P, _P]),
     "gsd_maxpool2": (_I, [_SRC, _P, _I, _I, _I, _I, _P]),
+    "gsd_maxpool2_pitched": (_I, [_SRC, _DST, _DST, _I, _P]),
+    "gsd_bnrelu_pitched": (_I, [_SRC, _DST, _I, _P]),
+    "gsd_act_once_pays": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "gsd_conv3x3_wgrad_takes_pitched_act": (_I, [_I, _I, _I, _I, _I]),
     "gsd_conv1x1_out": (_I, [_SRC, _P, _P, _I, _I, _P, _I, _I, _I, _P]),
     "gsd_conv1x1_out_wgrad_rows": (_I, [_I, _I, _I]),
     "gsd_conv1x1_out_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
@@ -323,6 +327,16 @@ def slack_empty(shape, device) -> torch.Tensor:
     buf[:SLACK].zero_()
     buf[-SLACK:].zero_()
     return buf[SLACK:SLACK + numel].view(*shape)
+
+
+def pitched_slack_zeros(shape, device) -> torch.Tensor:
+    """pitched_empty with slack_empty's readable floats around it, zero-filled: an (N,C,H,W) view of a buffer whose rows are
+    padded to a multiple of 4 floats.  What a kernel never writes (the pad columns) holds zeros."""
+    n, c, h, w = shape
+    p = -(-w // 4) * 4
+    numel = n * c * h * p
+    buf = torch.zeros((numel + 2 * SLACK,), device=device, dtype=torch.float32)
+    return buf[SLACK:SLACK + numel].view(n, c, h, p)[..., :w]
 
 
 def make_dst(t: torch.Tensor, c_off: int = 0, c_len: Optional[int] = None, off: Tuple[int, int] = (0, 0)) -> gsd_dst:

@@ -681,3 +681,50 @@ extern "C" int gsd_bn_bwd_apply(float* dz, const float* raw, const float* scale,
   GSD_LAUNCH_CHECK("gsd_bn_bwd_apply");
   return GSD_OK;
 }
+
+// relu(bn(raw)) written ONCE into a PITCHED buffer (gsd_bnrelu_pitched): what every m-block of a conv3x3 consumer would otherwise
+// recompute on its halo window.  Rows of `pitch` floats start 16-byte aligned, so the consumer moves them as aligned 16-byte
+// LDS-DMA pieces -- the launch class of the dX convs.  As bn_bwd_apply_pitched_kernel: a thread owns 4 consecutive columns of one
+// row, one unaligned 16-byte load, one aligned 16-byte store; columns W .. pitch-1 are written 0 on every call.  The value is
+// apply_affine's (one fmaf, one fmaxf): the bits the deferred consumers compute.
+__global__ __launch_bounds__(256) void bnrelu_pitched_kernel(const SrcD S, const DstD D) {
+  const int c = blockIdx.y, n = blockIdx.z;
+  const int q4 = D.ws >> 2;
+  const int total = S.H * q4;
+  const float* const in = S.p + (size_t)n * S.ns + (size_t)c * S.cs;
+  float* const o = D.p + (size_t)n * D.ns + (size_t)c * D.cs;
+  const float sc = S.scale[c], sh = S.shift[c];
+  typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < total; e += gridDim.x * 256) {
+    const int h = e / q4, w = (e - h * q4) * 4;
+    const float* const r = in + (size_t)h * S.W + w;
+    f32x4 d;
+    if (w + 4 <= S.W) {
+      const f32x4 v = *reinterpret_cast<const f32x4u*>(r);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) d[i] = apply_affine(v[i], sc, sh, 1);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) d[i] = w + i < S.W ? apply_affine(r[i], sc, sh, 1) : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(o + (size_t)h * D.ws + w) = d;
+  }
+}
+extern "C" int gsd_bnrelu_pitched(const gsd_src* src, const gsd_dst* dst, int N, void* stream) {
+  GSD_REQUIRE(src && dst && src->ptr && dst->ptr && N > 0, GSD_ERR_BAD_ARG, "gsd_bnrelu_pitched: bad argument");
+  GSD_REQUIRE(src->scale && src->shift && src->relu != 0 && src->off_h == 0 && src->off_w == 0, GSD_ERR_BAD_ARG,
+              "gsd_bnrelu_pitched: the source must carry a deferred BatchNorm + ReLU");
+  if (int e = gsd_check_src(*src, "gsd_bnrelu_pitched src")) return e;
+  if (int e = gsd_check_dst(*dst, "gsd_bnrelu_pitched dst", true)) return e;
+  GSD_REQUIRE(dst->C == src->C && dst->H == src->H && dst->W == src->W && dst->off_h == 0 && dst->off_w == 0, GSD_ERR_BAD_ARG,
+              "gsd_bnrelu_pitched: dst must be the source's (C,H,W)");
+  GSD_REQUIRE(dst->w_stride % 4 == 0 && ((uintptr_t)dst->ptr & 15) == 0 && dst->c_stride % 4 == 0 && dst->n_stride % 4 == 0,
+              GSD_ERR_BAD_ARG, "gsd_bnrelu_pitched: the destination needs a 16-byte aligned base and pitch, plane and image strides "
+              "%% 4 == 0 (pitch %d for W %d)", dst->w_stride, dst->W);
+  GSD_REQUIRE(N <= 65535 && src->C <= 65535, GSD_ERR_UNSUPPORTED, "gsd_bnrelu_pitched: N, C must be <= 65535");
+  const int total = src->H * (dst->w_stride / 4);
+  const int bx = ceil_div(total, 256) < 64 ? ceil_div(total, 256) : 64;
+  hipLaunchKernelGGL(bnrelu_pitched_kernel, dim3(bx, src->C, N), dim3(256), 0, (hipStream_t)stream, to_srcd(*src), to_dstd(*dst));
+  GSD_LAUNCH_CHECK("gsd_bnrelu_pitched");
+  return GSD_OK;
+}

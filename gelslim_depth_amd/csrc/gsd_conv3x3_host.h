@@ -156,3 +156,36 @@ struct Conv3SlabModel {
     return best;
   }
 };
+
+// Activate-once model: should relu(bn(raw)) of an (N, C, H, W) tensor be written once, row-pitched (gsd_bnrelu_pitched), so that
+// its two-dimensional Winograd forward consumer runs as the plain aligned launch (the dX class) instead of activating its halo
+// windows per m-block and moving them as unaligned pieces?  Both sides are linear in the batch, so among the batches at which
+// the consumer keeps its form the answer is monotone:
+//   saving = blocks x (chunks_act x s_full + chunks_plain x s_align) / (2 x CUs)     (two resident blocks per CU, as Conv3SlabModel)
+//   cost   = launch_us + bytes the pass moves / copy_bytes_per_us
+// s_full: us a block saves per 4-channel chunk that is deferred today and plain aligned then; s_align: per chunk that is plain
+// but dense (unaligned 16-byte pieces, edge repair) today -- the up-sampled half of a concat, the pooled tensor.  Both grow with
+// the consumer's m-blocks (the blocks that share one halo window): s = s0 + slope x log2(m-blocks), capped.
+// Fitted to profiles/act_once_layers_b32.txt (batch 32, us saved per block-chunk x 512):
+//   second convs (s_full)       m-blocks 1 / 2 / 4 / 8 / 16:  0.150  0.200  0.278  0.347  0.333   -> 0.15 + 0.06 log2, cap 0.33
+//   encoder first convs (s_align)        2 / 4 / 8 / 16:      0.124  0.179  0.323  0.279           -> 0.07 + 0.055 log2, cap 0.28
+//   decoder first convs, per skip chunk  1 / 2 / 4 / 8:       0.284  0.349  0.583  0.492  (model s_full + s_align: 0.22 0.335 0.45 0.565)
+// The a-priori figure (0.205 of the K-slab model's 2.07 us per chunk = 0.42, from the two classes' static instruction counts) holds
+// at the deep levels only: the shallow levels' launches save 7-10 %, not 21 %.  The copy rate is bn_bwd_apply_pitched_kernel's
+// (25.6 GB in 3.87 ms).
+struct ActOnceModel {
+  double full0, full_slope, full_cap, align0, align_slope, align_cap, copy_bytes_per_us, launch_us;
+  static double lg2(int v) { double r = 0.0; while (v > 1) { v >>= 1; r += 1.0; } return r; }
+  double saving_us(long blocks, int chunks_act, int chunks_plain, int mblocks) const {
+    const double l = lg2(mblocks);
+    const double sf = full0 + full_slope * l < full_cap ? full0 + full_slope * l : full_cap;
+    const double sa = align0 + align_slope * l < align_cap ? align0 + align_slope * l : align_cap;
+    return (double)blocks * (chunks_act * sf + chunks_plain * sa) / (2.0 * gsd_cu_count());
+  }
+  // pass_kind 0: a pass of its own (read + write); 1: another kernel reads the tensor anyway and writes it on the way (the skip
+  // tensor from the pitched max-pool); 2: the producer writes pitched rows INSTEAD of dense ones (the pooled tensor): free
+  double cost_us(int N, int C, int H, int W, int pass_kind) const {
+    if (pass_kind >= 2) return 0.0;
+    return (pass_kind == 0 ? launch_us : 0.0) + (double)N * C * H * ((pass_kind == 0 ? W : 0) + round_up(W, 4)) * 4.0 / copy_bytes_per_us;
+  }
+};

@@ -1105,6 +1105,27 @@ extern "C" int gsd_conv3x3_prefers_w2d(int N, int H, int W, int Cin, int Cout, i
   return a > 0.0 && b > 0.0 && a < b ? 1 : 0;
 }
 
+// Activate-once query (ActOnceModel, gsd_conv3x3_host.h): 1 when writing relu(bn(.)) of an (N, Cact, H, W) tensor once, row-pitched,
+// pays for its train-mode conv3x3 consumer Cin -> Cout (Cact of its Cin input channels are that tensor's).  0 when that consumer is not the two-dimensional form (small batches and
+// the row form, channel counts), when it reads the tensor at a pad offset, or when its tile's halo has too many 16-byte pieces for
+// the aligned fills (the `x4` condition of w2d_impl).  GSD_ACT_ONCE_FORCE = 0 / 1 overrides the model where the launch admits it.
+constexpr ActOnceModel act_once = {0.15, 0.06, 0.33, 0.07, 0.055, 0.28, 6.3e6, 4.0};
+extern "C" int gsd_act_once_pays(int N, int H, int W, int Cact, int Cin, int Cout, int off_h, int off_w, int pass_kind) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cact <= 0 || Cin < Cact || Cout <= 0 || off_h != 0 || off_w != 0) return 0;
+  if (!gsd_conv3x3_w2d_supported(Cin, Cact) || gsd_conv3x3_algo(N, H, W, Cin, Cout) != 1 || !gsd_conv3x3_prefers_w2d(N, H, W, Cin, Cout, 1))
+    return 0;
+  W2DPlan p;
+  if (!plan_w2d(N, H, W, Cout, &p)) return 0;
+  if (4 * ceil_div(p.WR * (p.TW / 4 + 2), 64) > 8 || gsd_env_int("GSD_W2D_X4", 1) == 0) return 0;
+  const int forced = gsd_env_int("GSD_ACT_ONCE_FORCE", -1);
+  if (forced == 0 || forced == 1) return forced;
+  const long blocks = (long)N * p.tiles_y * p.tiles_x * p.mblocks;
+  // pass_kind 2 (the pooled tensor) is plain today: its chunks save the alignment part only; a concat's other Cin - Cact channels
+  // (the up-sampled half) are plain and dense today and aligned then
+  const int act = pass_kind >= 2 ? 0 : Cact / 4, plain_chunks = Cin / 4 - act;
+  return act_once.saving_us(blocks, act, plain_chunks, p.mblocks) > act_once.cost_us(N, Cact, H, W, pass_kind) ? 1 : 0;
+}
+
 static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout, const gsd_dst* dst, int ndst, float* partials,
                     const Conv3Bw& bw, int N, int H, int W, void* stream, float* ws = nullptr, int64_t ws_elems = 0) {
   if (int e = conv3_check_operands("gsd_conv3x3_w2d", true, true, src, nsrc, wt, Cin, Cout, dst, ndst, N, H, W)) return e;

@@ -661,7 +661,10 @@ extern "C" int gsd_convT2x2(const gsd_src* src, const float* wt, const float* bi
   GSD_REQUIRE(src && dst && wt, GSD_ERR_BAD_ARG, "gsd_convT2x2: null argument");
   GSD_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, GSD_ERR_BAD_ARG, "gsd_convT2x2: bad sizes");
   if (int e = gsd_check_src(*src, "gsd_convT2x2 src")) return e;
-  if (int e = gsd_check_dst(*dst, "gsd_convT2x2 dst")) return e;
+  // (the epilogue addresses output rows through w_stride: a pitched destination -- the up-sampled half of a decoder level's
+  //  concat buffer -- is written in place; only the 8-byte stores ask for an even pitch)
+  if (int e = gsd_check_dst(*dst, "gsd_convT2x2 dst", true)) return e;
+  GSD_REQUIRE((dst->w_stride & 1) == 0, GSD_ERR_UNSUPPORTED, "gsd_convT2x2: dst needs an even row pitch (got %d)", dst->w_stride);
   GSD_REQUIRE(src->C == Cin && src->H == H && src->W == W && src->off_h == 0 && src->off_w == 0, GSD_ERR_BAD_ARG,
               "gsd_convT2x2: src must be the full (Cin,H,W) tensor");
   GSD_REQUIRE(dst->C == Cout && dst->H == 2 * H && dst->W == 2 * W && dst->off_h == 0 && dst->off_w == 0,

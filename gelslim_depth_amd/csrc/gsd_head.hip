@@ -33,6 +33,89 @@ extern "C" int gsd_maxpool2(const gsd_src* src, float* y, int N, int C, int H, i
   return GSD_OK;
 }
 
+// The same pool with PITCHED outputs (gsd_maxpool2_pitched): `pooled` goes to rows of pooled->w_stride floats (16-byte aligned,
+// columns W/2 .. pitch-1 written 0), and with `act` the activated full-resolution tensor relu(bn(raw)) -- the skip tensor of the
+// decoder -- goes to a second pitched destination on the way: one extra write, no extra read.  A thread owns columns 4k .. 4k+3
+// of the source rows 2hp and 2hp+1: two unaligned 16-byte loads, two aligned 16-byte stores (act) and one 8-byte store (pooled
+// columns 2k, 2k+1).  The pooled value is maxpool2_kernel's expression on the same fmaf results, act is apply_affine's.
+__global__ __launch_bounds__(256) void maxpool2_pitched_kernel(const SrcD S, const DstD Pd, const DstD A, int Hp, int Wp, int rows, int K) {
+  const int c = blockIdx.y, n = blockIdx.z;
+  const float* const in = S.p + (size_t)n * S.ns + (size_t)c * S.cs;
+  float* const po = Pd.p + (size_t)n * Pd.ns + (size_t)c * Pd.cs;
+  float* const ao = A.p != nullptr ? A.p + (size_t)n * A.ns + (size_t)c * A.cs : nullptr;
+  float sc = 1.f, sh = 0.f;
+  if (S.scale != nullptr) { sc = S.scale[c]; sh = S.shift[c]; }
+  typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+  const int total = rows * K;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < total; e += gridDim.x * 256) {
+    const int hp = e / K, k = e - hp * K;
+    const int w = 4 * k;
+    float v[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int h = 2 * hp + r;
+      const float* const b = in + (size_t)h * S.W + w;
+      if (h < S.H && w + 4 <= S.W) {
+        const f32x4 t = *reinterpret_cast<const f32x4u*>(b);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[r][i] = fmaf(t[i], sc, sh);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[r][i] = (h < S.H && w + i < S.W) ? fmaf(b[i], sc, sh) : 0.f;
+      }
+    }
+    if (ao != nullptr && w < A.ws) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int h = 2 * hp + r;
+        if (h >= S.H) continue;
+        f32x4 d;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) d[i] = w + i < S.W ? (S.relu ? fmaxf(v[r][i], 0.f) : v[r][i]) : 0.f;
+        *reinterpret_cast<f32x4*>(ao + (size_t)h * A.ws + w) = d;
+      }
+    }
+    if (hp < Hp && 2 * k < Pd.ws) {
+      float m[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        m[i] = fmaxf(fmaxf(v[0][2 * i], v[0][2 * i + 1]), fmaxf(v[1][2 * i], v[1][2 * i + 1]));
+        if (S.relu) m[i] = fmaxf(m[i], 0.f);
+        if (2 * k + i >= Wp) m[i] = 0.f;
+      }
+      *reinterpret_cast<float2*>(po + (size_t)hp * Pd.ws + 2 * k) = make_float2(m[0], m[1]);
+    }
+  }
+}
+extern "C" int gsd_maxpool2_pitched(const gsd_src* src, const gsd_dst* pooled, const gsd_dst* act, int N, void* stream) {
+  GSD_REQUIRE(src && src->ptr && pooled && pooled->ptr && N > 0 && src->C > 0 && src->H > 1 && src->W > 1 && src->off_h == 0 &&
+                  src->off_w == 0, GSD_ERR_BAD_ARG, "gsd_maxpool2_pitched: bad argument");
+  if (int e = gsd_check_src(*src, "gsd_maxpool2_pitched src")) return e;
+  if (int e = gsd_check_dst(*pooled, "gsd_maxpool2_pitched pooled", true)) return e;
+  const int Hp = src->H / 2, Wp = src->W / 2;
+  GSD_REQUIRE(pooled->C == src->C && pooled->H == Hp && pooled->W == Wp && pooled->off_h == 0 && pooled->off_w == 0, GSD_ERR_BAD_ARG,
+              "gsd_maxpool2_pitched: pooled must be (C,H/2,W/2)");
+  GSD_REQUIRE(pooled->w_stride % 4 == 0 && ((uintptr_t)pooled->ptr & 15) == 0 && pooled->c_stride % 4 == 0 && pooled->n_stride % 4 == 0,
+              GSD_ERR_BAD_ARG, "gsd_maxpool2_pitched: pooled needs a 16-byte aligned base and pitch, plane and image strides %% 4 == 0");
+  if (act != nullptr) {
+    if (int e = gsd_check_dst(*act, "gsd_maxpool2_pitched act", true)) return e;
+    GSD_REQUIRE(act->ptr && act->C == src->C && act->H == src->H && act->W == src->W && act->off_h == 0 && act->off_w == 0, GSD_ERR_BAD_ARG,
+                "gsd_maxpool2_pitched: act must be the source's (C,H,W)");
+    GSD_REQUIRE(act->w_stride % 4 == 0 && ((uintptr_t)act->ptr & 15) == 0 && act->c_stride % 4 == 0 && act->n_stride % 4 == 0,
+                GSD_ERR_BAD_ARG, "gsd_maxpool2_pitched: act needs a 16-byte aligned base and pitch, plane and image strides %% 4 == 0");
+  }
+  GSD_REQUIRE(N <= 65535 && src->C <= 65535, GSD_ERR_UNSUPPORTED, "gsd_maxpool2_pitched: N, C must be <= 65535");
+  // source-row pairs: with `act` also the unpaired last row of an odd H; pieces per pair: whatever covers both destinations' pitches
+  const int rows = act != nullptr ? (src->H + 1) / 2 : Hp;
+  const int ka = act != nullptr ? act->w_stride / 4 : 0, kp = pooled->w_stride / 2;
+  const int K = ka > kp ? ka : kp;
+  const int bx = ceil_div(rows * K, 256) < 64 ? ceil_div(rows * K, 256) : 64;
+  hipLaunchKernelGGL(maxpool2_pitched_kernel, dim3(bx, src->C, N), dim3(256), 0, (hipStream_t)stream, to_srcd(*src), to_dstd(*pooled),
+                     act != nullptr ? to_dstd(*act) : null_dstd(), Hp, Wp, rows, K);
+  GSD_LAUNCH_CHECK("gsd_maxpool2_pitched");
+  return GSD_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // 1x1 output conv (+bias) of relu(bn(raw))
 // ---------------------------------------------------------------------------------------------

@@ -702,6 +702,12 @@ extern "C" int gsd_conv3x3_wgrad_form(const gsd_src* a, int nsrc, const gsd_src*
   return gsd_wgrad_w2d_use(a, nsrc, dy, Cin, Cout, N, H, W) ? 2 : 1;
 }
 
+// 1 when gsd_conv3x3_wgrad serves this shape with a kernel that takes PITCHED activation segments (w_stride > W): the Winograd forms
+extern "C" int gsd_conv3x3_wgrad_takes_pitched_act(int N, int H, int W, int Cin, int Cout) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
+  return gsd_wgrad_w43_use(N, H, W, Cin, Cout) ? 1 : 0;
+}
+
 extern "C" int64_t gsd_conv3x3_wgrad_mfma_count(int form, int N, int H, int W, int Cin, int Cout) {
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
   if (form == 2) return gsd_wgrad_w2d_mfma_count(N, H, W, Cin, Cout);
@@ -723,8 +729,14 @@ extern "C" int gsd_conv3x3_wgrad(const gsd_src* a, int nsrc, const gsd_src* dy, 
     csum += a[i].C;
   }
   GSD_REQUIRE(csum == Cin, GSD_ERR_BAD_ARG, "gsd_conv3x3_wgrad: activation segments hold %d channels, Cin=%d", csum, Cin);
-  for (int i = 0; i < nsrc; ++i)
-    if (int e = gsd_require_rows_contiguous(a[i], "gsd_conv3x3_wgrad activation")) return e;
+  // the two Winograd kernels address activation rows through w_stride and mask by W (a pitched activation or concat buffer is
+  // read in place); the direct form's rows must be contiguous
+  for (int i = 0; i < nsrc; ++i) {
+    GSD_REQUIRE(a[i].w_stride >= a[i].W && a[i].c_stride >= (int64_t)a[i].H * a[i].w_stride && a[i].n_stride >= a[i].c_stride,
+                GSD_ERR_BAD_ARG, "gsd_conv3x3_wgrad: activation segment %d: strides too small", i);
+    if (!gsd_conv3x3_wgrad_takes_pitched_act(N, H, W, Cin, Cout))
+      if (int e = gsd_require_rows_contiguous(a[i], "gsd_conv3x3_wgrad activation (direct form)")) return e;
+  }
   if (int e = check_plain(*dy, "gsd_conv3x3_wgrad dy")) return e;
   // dy may be pitched (w_stride > W) for the Winograd form, which then moves it as aligned 16-byte pieces
   if (!gsd_wgrad_w43_use(N, H, W, Cin, Cout))

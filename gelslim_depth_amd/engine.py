@@ -7,11 +7,15 @@ for device memory (buffers) and, in data-parallel runs, for the RCCL collectives
 computes any part of the path (tests/test_gpu_robust.py checks that a fused train step dispatches no ATen compute op).
 
 Data layout in HBM (all fp32 NCHW):
-  raw[u]    raw conv3x3 output of every conv unit (pre-BN); the normalised/activated tensor is
-            never stored, consumers apply (scale, shift, relu) on load            -- 18 tensors
+  raw[u]    raw conv3x3 output of every conv unit (pre-BN); ConvT, the head, dW and every eval-mode consumer apply
+            (scale, shift, relu) on load.  In a train-mode forward relu(bn(raw)) is written ONCE where the model says it
+            pays (GSD_ACT_ONCE, gsd_act_once_pays): row-pitched, so that the conv3x3 that reads it is the plain aligned
+            launch the dX convs are -- into a recycled scratch buffer, or (skip tensors) into the level's concat buffer
   g[u]      gradient buffer of the same shape: da -> dz -> d_raw in place         -- 18 tensors
   pooled[l] max-pool output feeding encoder level l (l>=1);  dpooled[l] its gradient
   up[j]     transposed-conv output (+bias) of decoder j at (2h,2w), unpadded;  dup[j] its gradient
+  cat[j]    (GSD_ACT_ONCE) concat buffer (N, 2C', H, pitch) of decoder j, zero-filled once: the activated skip tensor in
+            channels [0,C'), up[j] is the view of channels [C',2C') -- the decoder's first conv and its dW read ONE plain source
   wt_*      per-step re-laid-out weights (k-major, out-channel contiguous)
 """
 from __future__ import annotations
@@ -89,6 +93,7 @@ class _Unit(ConvUnit):
         self.pitched = False   # gsd_bn_bwd_apply writes d_raw out of place into the pitched buffer
         self.fused_dw = False  # first layer: no dX, so dW forms d_raw itself (gsd_conv3x3_wgrad_bn) and the apply pass is skipped
         self.srcs = None  # gsd_src array kept for wgrad
+        self.act_once = False  # train-mode forward: relu(bn(.)) of the input is written once, pitched, and read as a plain source
         self.form_f = self.form_d = None   # _ConvForm of the forward / dX launch for the current shape
         self.forms_f = None                # ... of the forward launch in eval (False) and train (True) mode
 
@@ -99,6 +104,7 @@ class _Up(UpUnit):
         self.mode_d = 3            # gsd_weight_layout mode of wt_d (gsd_convT2x2_dgrad_layout)
         self.bn_rows = 0           # > 0: the dX launch also does pass 1 of the BatchNorm backward of the unit below (partial rows)
         self.out = self.dout = None
+        self.cat = None            # the level's concat buffer when `out` is a view of it (GSD_ACT_ONCE)
 
 
 class UNetEngine(EngineBase):
@@ -124,7 +130,60 @@ class UNetEngine(EngineBase):
     # conv_ws and the weight-gradient workspaces are sized from them, so they are part of the shape key -- a switch flipped
     # between two steps (a test's monkeypatch, a sweep in one process) re-sizes the buffers instead of overrunning them
     _SIZING_ENV = ("GSD_W2D_TW", "GSD_W2D_TW8_PCT", "GSD_W43_TW", "GSD_W43_FOLD", "GSD_CONV_W2D", "GSD_CONV_ALGO", "GSD_W43_SPLIT",
-                   "GSD_WGRAD_ALGO", "GSD_WGRAD_W2D", "GSD_WG2D_KX", "GSD_WG2D_BLOCKS", "GSD_WGRAD_BLOCKS", "GSD_WG43_TW")
+                   "GSD_WGRAD_ALGO", "GSD_WGRAD_W2D", "GSD_WG2D_KX", "GSD_WG2D_BLOCKS", "GSD_WGRAD_BLOCKS", "GSD_WG43_TW",
+                   "GSD_ACT_ONCE", "GSD_ACT_ONCE_FORCE", "GSD_W2D_X4")
+
+    @staticmethod
+    def _desc(c: int, h: int, w: int, pitch: int, deferred: bool = False, n: int = 1) -> L.gsd_src:
+        """A gsd_src for the library's host-side queries (they read no device memory): a (c, h, w) segment with rows of `pitch`."""
+        s = L.gsd_src()
+        s.ptr = 256
+        s.scale = s.shift = 256 if deferred else None
+        s.C, s.H, s.W, s.relu, s.w_stride, s.slack = c, h, w, int(deferred), pitch, L.SLACK
+        s.c_stride = h * pitch
+        s.n_stride = c * h * pitch
+        return s
+
+    def _dw_form(self, u: "_Unit", n: int, lh: int, lw: int, segs) -> int:
+        arr = L.src_array(segs)
+        # (d_raw is pitched under the condition _ensure states for u.pitched, which it sets for train-mode forwards only)
+        pitched = bool(lib.gsd_conv3x3_wgrad_takes_pitched_dy(n, lh, lw, u.cin, u.cout)) and (not u.need_dgrad or u.form_d.algo >= 1)
+        dy = self._desc(u.cout, lh, lw, _r4(lw) if pitched else lw)
+        return lib.gsd_conv3x3_wgrad_form(arr, len(segs), C.byref(dy), u.cin, u.cout, n, lh, lw)
+
+    def _plan_act_once(self, n: int) -> None:
+        """Which tensors a train-mode forward writes activated and pitched (GSD_ACT_ONCE, default 1; 0: the deferred schedule).
+        Decided from the shape alone, whatever the mode of the forward that sizes the buffers: they serve both modes."""
+        on = os.environ.get("GSD_ACT_ONCE", "1") != "0"
+        hs, ws = self.hs, self.ws
+        self.pooled_pitched = [False] * (self.L + 1)
+        self.cat_on = [False] * self.L
+        for u in self.units:
+            u.act_once = False
+        if not on:
+            return
+        w2d = lambda u: all(f.algo == 2 for f in u.forms_f.values())   # the eval-mode forward reads the same buffers
+        for lvl, (u0, u1) in enumerate(self.enc):
+            lh, lw = hs[lvl], ws[lvl]
+            if lvl >= 1 and w2d(u0) and lib.gsd_act_once_pays(n, lh, lw, u0.cin, u0.cin, u0.cout, 0, 0, 2) and \
+                    lib.gsd_conv3x3_wgrad_takes_pitched_act(n, lh, lw, u0.cin, u0.cout) and \
+                    self._dw_form(u0, n, lh, lw, [self._desc(u0.cin, lh, lw, lw)]) == \
+                    self._dw_form(u0, n, lh, lw, [self._desc(u0.cin, lh, lw, _r4(lw))]):
+                self.pooled_pitched[lvl] = True
+        for pair in self.enc + self.dec:
+            u0, u1 = pair
+            lh, lw = hs[u1.level], ws[u1.level]
+            u1.act_once = u1.forms_f[True].algo == 2 and bool(lib.gsd_act_once_pays(n, lh, lw, u1.cin, u1.cin, u1.cout, 0, 0, 0))
+        for j, (u0, _) in enumerate(self.dec):
+            lvl = self.L - 1 - j
+            lh, lw = hs[lvl], ws[lvl]
+            cs, cu = u0.c0, u0.cin - u0.c0
+            p = _r4(lw)
+            two = [self._desc(cs, lh, lw, lw, deferred=True), self._desc(cu, 2 * hs[lvl + 1], 2 * ws[lvl + 1], 2 * ws[lvl + 1])]
+            self.cat_on[j] = self._pad_off(lvl) == (0, 0) and w2d(u0) and \
+                bool(lib.gsd_act_once_pays(n, lh, lw, cs, u0.cin, u0.cout, 0, 0, 1)) and \
+                bool(lib.gsd_conv3x3_wgrad_takes_pitched_act(n, lh, lw, u0.cin, u0.cout)) and \
+                self._dw_form(u0, n, lh, lw, two) == self._dw_form(u0, n, lh, lw, [self._desc(u0.cin, lh, lw, p)])
 
     def _ensure(self, n: int, h: int, w: int, dev: torch.device, train: bool) -> None:
         key = (n, h, w, str(dev), self._env_key())
@@ -134,7 +193,7 @@ class UNetEngine(EngineBase):
             for u in self.units:
                 u.raw = u.g = None
             for up in self.ups:
-                up.out = up.dout = None
+                up.out = up.dout = up.cat = None
         self._shape = key
         hs, ws = self._set_pyramid(h, w)
         f32 = dict(device=dev, dtype=torch.float32)
@@ -186,8 +245,17 @@ class UNetEngine(EngineBase):
                 u.fused_dw = (not u.need_dgrad) and bool(lib.gsd_conv3x3_wgrad_bn_supported(n, lh, lw, u.cin, u.cout))
                 if u.fused_dw:
                     max_ws = max(max_ws, lib.gsd_conv3x3_wgrad_bn_workspace(n, lh, lw, u.cin, u.cout))
+        self._plan_act_once(n)
+        # relu(bn(raw)) of a unit's input, pitched: ONE recycled scratch (the forward conv is its only reader; dW stays deferred)
+        max_act = max([n * u.cin * hs[u.level] * _r4(ws[u.level]) for u in self.units if u.act_once] + [0])
+        self.act_buf = torch.empty((max_act,), **f32) if (train and max_act) else None
         for up in self.ups:
             li = up.level_in
+            if up.out is None and self.cat_on[up.j]:
+                # the level's concat buffer, zero-filled ONCE: nothing ever writes its pad columns or, where 2w = W - 1, the last
+                # column of the up-sampled half -- the zero padding the plain aligned conv3x3 and dW launches read there
+                up.cat = L.pitched_slack_zeros((n, 2 * up.cout, hs[li - 1], ws[li - 1]), dev)
+                up.out = up.cat[:, up.cout:, :2 * hs[li], :2 * ws[li]]
             if up.out is None:
                 up.out = L.slack_empty((n, up.cout, 2 * hs[li], 2 * ws[li]), dev)
             if train and up.dout is None:
@@ -207,7 +275,8 @@ class UNetEngine(EngineBase):
                     max_part = max(max_part, up.bn_rows * 2 * _r64(up.cin))
             if train:
                 max_ws = max(max_ws, lib.gsd_convT2x2_wgrad_workspace(n, hs[li], ws[li], up.cin, up.cout))
-        self.pooled = [None] + [L.slack_empty((n, self.dims[l - 1], hs[l], ws[l]), dev) for l in range(1, self.L + 1)]
+        self.pooled = [None] + [(L.pitched_slack_zeros if self.pooled_pitched[l] else L.slack_empty)((n, self.dims[l - 1], hs[l], ws[l]), dev)
+                                for l in range(1, self.L + 1)]
         self.dpooled = [None] + ([torch.empty((n, self.dims[l - 1], hs[l], ws[l]), **f32)
                                  for l in range(1, self.L + 1)] if train else [None] * self.L)
         # pitched d_raw scratch: one unit at a time on one stream; with dW on the side stream two, used in turn (dW of a unit may
@@ -242,13 +311,26 @@ class UNetEngine(EngineBase):
     def _act_src(u: _Unit) -> L.gsd_src:
         return L.make_src(u.raw, u.scale, u.shift, relu=True, slack=L.SLACK)
 
+    def _activate(self, prev: _Unit, dst_t: torch.Tensor, st: int) -> None:
+        """relu(bn(prev.raw)) into the pitched tensor dst_t (gsd_bnrelu_pitched)."""
+        s, d = self._act_src(prev), L.make_dst(dst_t)
+        check(lib.gsd_bnrelu_pitched(C.byref(s), C.byref(d), prev.raw.shape[0], st), "bnrelu_pitched")
+
     def _run_unit(self, u: _Unit, srcs: List[L.gsd_src], P: Dict[str, torch.Tensor], train: bool, st: int,
-                  keep: bool = False) -> None:
+                  keep: bool = False, prev: Optional[_Unit] = None) -> None:
+        """prev: the unit whose deferred output `srcs` describes.  Where the plan says so (u.act_once, train mode) it is written
+        activated into the scratch buffer first and the conv reads that as a plain source; dW keeps the deferred one (u.srcs)."""
         n = u.raw.shape[0]
         lh, lw = self.hs[u.level], self.ws[u.level]
         u.form_f = u.forms_f[train]
-        arr = L.src_array(srcs)
-        u.srcs = arr
+        u.srcs = L.src_array(srcs)
+        arr = u.srcs
+        if train and prev is not None and u.act_once:
+            p = _r4(lw)
+            act = self.act_buf[:n * u.cin * lh * p].view(n, u.cin, lh, p)[..., :lw]
+            self._activate(prev, act, st)
+            srcs = [L.make_src(act)]
+            arr = L.src_array(srcs)
         dst = L.dst_array([L.make_dst(u.raw)])
         part = self.partials.data_ptr() if train else None
         ev = self._log_begin()
@@ -317,11 +399,21 @@ class UNetEngine(EngineBase):
                     self.region_log.append(("inc_forward", region, self._event()))
                 prev = self.enc[lvl - 1][1]
                 s = self._act_src(prev)
-                check(lib.gsd_maxpool2(C.byref(s), self.pooled[lvl].data_ptr(), n, prev.cout, self.hs[lvl - 1],
-                                       self.ws[lvl - 1], st), "maxpool2")
+                # train mode with a concat buffer at the level above: the pool also leaves the skip tensor activated in its channels
+                cat = self.ups[self.L - lvl].cat if train and self.cat_on[self.L - lvl] else None
+                skip_t = None if cat is None else cat[:, :prev.cout]
+                if self.pooled_pitched[lvl]:
+                    dp = L.make_dst(self.pooled[lvl])
+                    da = None if skip_t is None else C.byref(L.make_dst(skip_t))
+                    check(lib.gsd_maxpool2_pitched(C.byref(s), C.byref(dp), da, n, st), "maxpool2_pitched")
+                else:
+                    check(lib.gsd_maxpool2(C.byref(s), self.pooled[lvl].data_ptr(), n, prev.cout, self.hs[lvl - 1],
+                                           self.ws[lvl - 1], st), "maxpool2")
+                    if skip_t is not None:
+                        self._activate(prev, skip_t, st)
                 srcs = [L.make_src(self.pooled[lvl], slack=L.SLACK)]
             self._run_unit(u0, srcs, P, train, st, keep)
-            self._run_unit(u1, [self._act_src(u0)], P, train, st, keep)
+            self._run_unit(u1, [self._act_src(u0)], P, train, st, keep, prev=u0)
         if self.L == 0 and region is not None:          # a one-level network (profiles/inc_block.py): the block ends here
             self.region_log.append(("inc_forward", region, self._event()))
         cur = self.enc[self.L][1]
@@ -334,9 +426,12 @@ class UNetEngine(EngineBase):
                                    self.hs[lvl + 1], self.ws[lvl + 1], st), "convT2x2")
             skip = self.enc[lvl][1]
             u0, u1 = self.dec[j]
-            self._run_unit(u0, [self._act_src(skip), L.make_src(up.out, off=self._pad_off(lvl), slack=L.SLACK)], P, train, st,
-                           keep)
-            self._run_unit(u1, [self._act_src(u0)], P, train, st, keep)
+            if train and self.cat_on[j]:     # [activated skip | up]: one plain pitched source, for the conv and for its dW
+                self._run_unit(u0, [L.make_src(up.cat, slack=L.SLACK)], P, train, st, keep)
+            else:
+                self._run_unit(u0, [self._act_src(skip), L.make_src(up.out, off=self._pad_off(lvl), slack=L.SLACK)], P, train, st,
+                               keep)
+            self._run_unit(u1, [self._act_src(u0)], P, train, st, keep, prev=u0)
             cur = u1
         self._flush_counters()
         if out is None:

@@ -254,6 +254,8 @@ int gsd_conv3x3_wgrad_form(const gsd_src* a, int nsrc, const gsd_src* dy, int Ci
 int64_t gsd_conv3x3_wgrad_mfma_count(int form, int N, int H, int W, int Cin, int Cout);
 /* 1 when gsd_conv3x3_wgrad serves this shape with a kernel that takes a pitched dy (dy->w_stride > W, see gsd_src). */
 int gsd_conv3x3_wgrad_takes_pitched_dy(int N, int H, int W, int Cin, int Cout);
+/* 1 when it serves this shape with a kernel that takes pitched ACTIVATION segments (a[i].w_stride > W): the Winograd forms. */
+int gsd_conv3x3_wgrad_takes_pitched_act(int N, int H, int W, int Cin, int Cout);
 /* dW of a conv3x3 with FEW input channels (Cin * 9 <= 32: the network's first layer, unet.py:15) with the BatchNorm
  * backward of its output applied on the fly: d_raw = scale * (dz - c1 - (raw - mean) * invstd * c2) is formed in registers
  * from dz and raw -- what gsd_bn_bwd_apply would have written.  The first layer has no dX, so dW is d_raw's only reader and
@@ -355,6 +357,18 @@ int gsd_bn_bwd_reduce_finalize(const float* partials, int rows, int layout_mpad,
 int gsd_bn_bwd_apply(float* dz, const float* raw, const float* scale, const float* mean,
                      const float* invstd, const float* c1, const float* c2,
                      int N, int C, int H, int W, float* out, int out_w_stride, void* stream);
+/* relu(bn(raw)) written ONCE: dst = max(0, fma(raw, scale, shift)) -- the single-rounded expression every deferred consumer
+ * applies on load, so a consumer of dst as a plain source gets the bits it computes itself from src.  src: a deferred segment
+ * (scale, shift, relu) with dense rows; dst: the same (C,H,W) with PITCHED rows (16-byte aligned base, w_stride / c_stride /
+ * n_stride multiples of 4 floats; a channel-offset view of a larger buffer is fine).  Columns W .. w_stride-1 are written 0 on
+ * every call.  A conv3x3 in the two-dimensional form then reads dst as aligned 16-byte pieces (the launch class of the dX convs).
+ * gsd_act_once_pays: the host model's answer for an (N,Cin,H,W) tensor and its train-mode conv3x3 consumer Cin -> Cout that reads
+ * it at pad offset (off_h, off_w): 1 when the consumer's modelled saving exceeds the pass (bytes / copy rate + launch); 0 also
+ * when the consumer is not the two-dimensional form, the offset is not (0,0) or the tile's halo does not admit aligned pieces.
+ * pass_kind: 0 a pass of its own (read + write + launch), 1 written on the way by a kernel that reads the tensor anyway (the skip
+ * tensor from gsd_maxpool2_pitched), 2 the producer writes pitched rows instead of dense ones (the pooled tensor: no cost). */
+int gsd_bnrelu_pitched(const gsd_src* src, const gsd_dst* dst, int N, void* stream);
+int gsd_act_once_pays(int N, int H, int W, int Cact, int Cin, int Cout, int off_h, int off_w, int pass_kind);
 /* out[k] = sum over n, p of x[n][k][p] (contiguous [N][K][HW]); deterministic two-stage.
  * workspace >= 64*K floats. Used for dbias of the output conv / transposed conv. */
 int gsd_sum_planes(const float* x, int N, int K, int64_t HW, float* out, float* workspace, void* stream);
@@ -362,6 +376,12 @@ int gsd_sum_planes(const float* x, int N, int K, int64_t HW, float* out, float* 
 /* ---- MaxPool2d(2) floor mode (unet.py:26; aten::max_pool2d_with_indices) -------------------- */
 /* y = maxpool(max(0, raw*scale+shift)) materialised at (H/2, W/2). No index tensor is kept. */
 int gsd_maxpool2(const gsd_src* src, float* y, int N, int C, int H, int W, void* stream);
+/* The same pool with PITCHED outputs: `pooled` (C,H/2,W/2) and, when `act` is not NULL, the activated full-resolution tensor
+ * max(0, raw*scale+shift) itself (C,H,W) -- the decoder's skip tensor, one extra write and no extra read.  Both destinations:
+ * 16-byte aligned base, w_stride / c_stride / n_stride multiples of 4 floats (channel-offset views of a larger buffer are fine);
+ * columns W.. of every row are written 0 on every call.  pooled holds the bits gsd_maxpool2 writes, act the bits
+ * gsd_bnrelu_pitched writes.  src: the full tensor, dense rows. */
+int gsd_maxpool2_pitched(const gsd_src* src, const gsd_dst* pooled, const gsd_dst* act, int N, void* stream);
 
 /* ---- output conv + loss (unet.py:54; train_unet.py:51-52) ----------------------------------- */
 /* out[n,k,p] = b[k] + sum_c w[k][c] * max(0, raw[c]*scale[c]+shift[c]). */
