@@ -54,6 +54,13 @@ class gsd_augment(C.Structure):
                 ("noise_std", C.c_float), ("pivot", C.c_float)]
 
 
+class gsd_depth_loss(C.Structure):
+    """The depth-aware loss of gsd_depth_loss_fwd_bwd (include/gsd.h): kinds, scales and weights."""
+    _fields_ = [("data_kind", C.c_int32), ("grad_kind", C.c_int32), ("grad_scales", C.c_int32), ("reserved", C.c_int32),
+                ("huber_delta", C.c_float), ("contact_weight", C.c_float), ("contact_eps", C.c_float),
+                ("background", C.c_float), ("grad_weight", C.c_float)]
+
+
 class gsd_augment_draw(C.Structure):
     """What gsd_gather_augment draws for one dataset row (gsd_augment_sample)."""
     _fields_ = [("hflip", C.c_int32), ("vflip", C.c_int32), ("dy", C.c_int32), ("dx", C.c_int32),
@@ -157,6 +164,8 @@ SIGNATURES = {
     "gsd_conv1x1_out_wgrad_rows": (_I, [_I, _I, _I]),
     "gsd_conv1x1_out_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     "gsd_loss_fwd_bwd": (_I, [_I, _P, _P, _L, _F, _P, _P, _P, _GUARD, _P]),
+    "gsd_depth_loss_workspace": (_L, [_I, _I, _I, _I]),
+    "gsd_depth_loss_fwd_bwd": (_I, [C.POINTER(gsd_depth_loss), _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _L, _GUARD, _P]),
     "gsd_guard_snapshot": (_I, [_P, _P, _L, _P]),
     "gsd_guard_restore": (_I, [_GUARD, _P, _P, _L, _P]),
     "gsd_adam_ema": (_I, [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _GUARD, _P]),

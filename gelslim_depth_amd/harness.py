@@ -77,8 +77,9 @@ def _mean_loss(losses: List[float], n_batches: int) -> float:
     return float(sum(losses) / n_batches) if n_batches else 0.0
 
 
-def evaluate_loader(step, loader: Iterable[Dict], loss_kind: str = "mse") -> float:
+def evaluate_loader(step, loader: Iterable[Dict], loss_kind="mse") -> float:
     """Mean over the loader's batches of the loss under the EMA weights, NaN batches counted as 0 (train_unet.py:379-419).
+    `loss_kind`: "mse" (the reference's, and what `fit` scores), "l1", or a train.DepthLoss, whose total L is averaged.
 
     Data parallel (a `DeviceLoader` with world_size > 1): the walk is over the GLOBAL batches, every rank evaluates only its
     contiguous share of each at the per-rank train shape (`DeviceLoader.eval_shares`: no wrap-around padding, no activation
@@ -86,7 +87,8 @@ def evaluate_loader(step, loader: Iterable[Dict], loss_kind: str = "mse") -> flo
     global batch -- every rank then holds the single-process value of every batch loss, bit for bit the same on all ranks.
     The batch losses stay on the device until the pass ends (one host sync per pass; the reference syncs per batch)."""
     import torch
-    from .train import loss_fwd_bwd
+    from .train import DepthLoss, depth_loss_fwd_bwd, depth_loss_workspace, loss_fwd_bwd
+    depth = isinstance(loss_kind, DepthLoss)
     sharded = getattr(loader, "world_size", 1) > 1 and hasattr(loader, "eval_shares")
     if sharded and (getattr(step, "pg", None) is None or getattr(step, "dist", None) is None):
         raise RuntimeError("evaluate_loader: the loader is sharded over %d ranks but the step was built without a process_group; "
@@ -103,12 +105,17 @@ def evaluate_loader(step, loader: Iterable[Dict], loss_kind: str = "mse") -> flo
         out = step.evaluate(x, use_ema=True)
         if buf is None:
             dev = out.device
-            buf = torch.zeros((1,), device=dev, dtype=torch.float32)
+            buf = torch.zeros((6 if depth else 1,), device=dev, dtype=torch.float32)
             ws = torch.empty((2048,), device=dev, dtype=torch.float64)
         t = t.float().contiguous()
         if valid is not None and valid < out.shape[0]:
             out, t = out[:valid], t[:valid]       # leading-dimension slices stay contiguous: the padding is not scored
-        loss_fwd_bwd(loss_kind, out, t, None, buf, ws)
+        if depth:
+            if ws.numel() < depth_loss_workspace(out.shape):
+                ws = torch.empty((depth_loss_workspace(out.shape),), device=dev, dtype=torch.float64)
+            depth_loss_fwd_bwd(loss_kind, out, t, None, buf, ws)       # buf[0] is L; its normalisers are element counts
+        else:
+            loss_fwd_bwd(loss_kind, out, t, None, buf, ws)
         rows.append((buf[0].double().clone(), float(out.numel())))      # the element counts stay on the host
     if not rows:
         return 0.0

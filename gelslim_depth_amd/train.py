@@ -27,12 +27,16 @@ gradient by its global L2 norm as torch.nn.utils.clip_grad_norm_ would -- one re
 (gsd_grad_norm) whose coefficient stays on the device and is applied inside the optimiser kernel (gsd_adam_ema_clip) --
 and `lr_schedule` (LRSchedule: linear warm-up, then constant, linear or cosine decay) makes the learning rate a pure
 function of the step count, so a resumed run continues its schedule.
+
+A third: `loss` may be a DepthLoss -- a Huber / L1 / MSE data term, a heavier weight on contact pixels and a
+multi-scale slope term on the error image, one libgsd kernel (gsd_depth_loss_fwd_bwd) in the place of the plain loss launch.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple, Union
 
 import torch
 
@@ -114,6 +118,93 @@ def lr_at(lr: float, schedule: Optional[LRSchedule], t: int) -> float:
     return warm * base
 
 
+DEPTH_DATA_KINDS = {"mse": 0, "l1": 1, "huber": 2}
+DEPTH_GRAD_KINDS = {"l1": 0, "l2": 1}
+DEPTH_MAX_SCALES = 4
+
+
+class DepthLoss:
+    """A loss for depth maps (an addition: the reference trains on the plain MSE), with e = output - target over M elements:
+
+        L = (1/M) sum w * rho(e)  +  grad_weight * sum_{k < grad_scales} (1/M_k) sum over the grid of step s = 2^k of
+                                                  phi(e[h, w+s] - e[h, w]) + phi(e[h+s, w] - e[h, w])
+
+    `data`: rho = e^2 ("mse"), |e| ("l1") or Huber with threshold `huber_delta` ("huber": e^2/2 up to it, linear beyond).
+    `contact_weight`: w = 1 + contact_weight where |target - background| > contact_eps, 1 elsewhere (0: off).  `grad_kind`:
+    phi = |g| ("l1") or g^2 ("l2"); pairs never wrap around, leave the image or cross images and classes; M_k counts the grid
+    points of scale k.  The normalisers are element counts, never sum(w), so the loss of a batch is the mean of the losses of
+    its equal shards and data-parallel training needs nothing new.  include/gsd.h (gsd_depth_loss) has the formula in full.
+    A value class like LRSchedule: comparable, hashable, `DepthLoss(**d.spec()) == d`."""
+
+    def __init__(self, data: str = "mse", huber_delta: Optional[float] = None, contact_weight: float = 0.0,
+                 contact_eps: float = 0.0, background: float = 0.0, grad_weight: float = 0.0, grad_kind: str = "l1",
+                 grad_scales: int = 0) -> None:
+        def number(name, v, what="finite and not negative", low=0.0):
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"DepthLoss: {name} must be a number, got {v!r}") from None
+            if not (low <= f < math.inf):
+                raise ValueError(f"DepthLoss: {name} must be {what}, got {v!r}")
+            return f
+        if data not in DEPTH_DATA_KINDS:
+            raise ValueError(f"DepthLoss: data must be one of {', '.join(repr(d) for d in DEPTH_DATA_KINDS)}, got {data!r}")
+        self.data = data
+        if data == "huber":
+            if huber_delta is None:
+                raise ValueError("DepthLoss: huber_delta is required for data='huber'")
+            self.huber_delta = number("huber_delta", huber_delta, "finite and positive")
+            if not self.huber_delta > 0.0:
+                raise ValueError(f"DepthLoss: huber_delta must be finite and positive, got {huber_delta!r}")
+        else:
+            if huber_delta is not None:
+                raise ValueError(f"DepthLoss: huber_delta belongs to data='huber' only, got {huber_delta!r} with data={data!r}")
+            self.huber_delta = None
+        self.contact_weight = number("contact_weight", contact_weight)
+        self.contact_eps = number("contact_eps", contact_eps)
+        self.background = number("background", background, "finite", -math.inf)
+        if self.background == -math.inf:
+            raise ValueError(f"DepthLoss: background must be finite, got {background!r}")
+        self.grad_weight = number("grad_weight", grad_weight)
+        if grad_kind not in DEPTH_GRAD_KINDS:
+            raise ValueError(f"DepthLoss: grad_kind must be one of {', '.join(repr(d) for d in DEPTH_GRAD_KINDS)}, got {grad_kind!r}")
+        self.grad_kind = grad_kind
+        if isinstance(grad_scales, bool) or not isinstance(grad_scales, int) or not 0 <= grad_scales <= DEPTH_MAX_SCALES:
+            raise ValueError(f"DepthLoss: grad_scales must be a whole number from 0 to {DEPTH_MAX_SCALES}, got {grad_scales!r}")
+        self.grad_scales = int(grad_scales)
+        if self.grad_weight > 0.0 and self.grad_scales == 0:
+            raise ValueError(f"DepthLoss: grad_weight {grad_weight!r} needs grad_scales >= 1")
+
+    def spec(self) -> Dict[str, object]:
+        """Every field as a plain Python value (TrainStep.state_dict saves it as the `loss` hyperparameter)."""
+        return {"data": self.data, "huber_delta": self.huber_delta, "contact_weight": self.contact_weight,
+                "contact_eps": self.contact_eps, "background": self.background, "grad_weight": self.grad_weight,
+                "grad_kind": self.grad_kind, "grad_scales": self.grad_scales}
+
+    def c_struct(self) -> "L.gsd_depth_loss":
+        """The gsd_depth_loss the kernel reads (its weights as fp32)."""
+        c = L.gsd_depth_loss()
+        c.data_kind, c.grad_kind, c.grad_scales = DEPTH_DATA_KINDS[self.data], DEPTH_GRAD_KINDS[self.grad_kind], self.grad_scales
+        c.huber_delta = 0.0 if self.huber_delta is None else self.huber_delta
+        c.contact_weight, c.contact_eps, c.background = self.contact_weight, self.contact_eps, self.background
+        c.grad_weight = self.grad_weight
+        return c
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, DepthLoss) and self.spec() == other.spec()
+
+    def __hash__(self) -> int:
+        return hash(tuple(self.spec().items()))
+
+    def __repr__(self) -> str:
+        return "DepthLoss(" + ", ".join(f"{k}={v!r}" for k, v in self.spec().items()) + ")"
+
+
+def as_depth_loss(spec) -> DepthLoss:
+    """A DepthLoss from itself or from its `.spec()` dict."""
+    return spec if isinstance(spec, DepthLoss) else DepthLoss(**spec)
+
+
 def atomic_save(obj, path: str) -> None:
     """torch.save to `path + ".tmp"`, flushed to disk, then renamed over `path`: a kill during the write leaves the previous
     file (or none), never a truncated one."""
@@ -164,6 +255,56 @@ def l1_loss(input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return _LossFn.apply(input, target, "l1")
 
 
+def depth_loss_workspace(shape) -> int:
+    """Doubles of scratch depth_loss_fwd_bwd needs for an (N, K, H, W) output: a function of the shape alone."""
+    n, k, h, w = (int(d) for d in shape)
+    return int(lib.gsd_depth_loss_workspace(n, k, h, w))
+
+
+def depth_loss_fwd_bwd(spec: DepthLoss, out: torch.Tensor, target: torch.Tensor, grad: Optional[torch.Tensor],
+                       terms: torch.Tensor, ws: torch.Tensor, grad_scale: float = 1.0, guard=None) -> None:
+    """terms[0:6] = L, L_data, L_grad, mean (o-t)^2, mean |o-t|, contact fraction of the DepthLoss `spec` over the (N, K, H, W)
+    output; grad (None: evaluation) = d L / d out * grad_scale.  ws: depth_loss_workspace(out.shape) float64."""
+    for name, t in (("output", out), ("target", target)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise L.GsdError(f"depth_loss_fwd_bwd: {name} must be a contiguous float32 tensor on the GPU, got {t.dtype} on "
+                             f"{t.device} (the kernel reads raw fp32; cast with .float() first)")
+    if out.dim() != 4 or out.shape != target.shape:
+        raise L.GsdError(f"depth_loss_fwd_bwd: output {tuple(out.shape)} and target {tuple(target.shape)} must be one "
+                         "(N, K, H, W) shape")
+    if grad is not None and (grad.dtype != torch.float32 or not grad.is_cuda or not grad.is_contiguous() or grad.shape != out.shape):
+        raise L.GsdError("depth_loss_fwd_bwd: grad must be a contiguous float32 GPU tensor of the output's shape")
+    if terms.dtype != torch.float32 or not terms.is_cuda or terms.numel() < 6 or ws.dtype != torch.float64 or not ws.is_cuda:
+        raise L.GsdError("depth_loss_fwd_bwd: terms must be 6 float32 and ws float64, both on the GPU")
+    n, k, h, w = out.shape
+    c = spec.c_struct()
+    check(lib.gsd_depth_loss_fwd_bwd(C.byref(c), out.data_ptr(), target.data_ptr(), n, k, h, w, grad_scale, terms.data_ptr(),
+                                     L.ptr(grad), ws.data_ptr(), ws.numel(), guard, L.stream_ptr()), "depth_loss_fwd_bwd")
+
+
+class _DepthLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out, target, spec):
+        out_c, tgt_c = out.contiguous(), target.contiguous().float()
+        terms = torch.empty((6,), device=out.device, dtype=torch.float32)
+        grad = torch.empty_like(out_c)
+        ws = torch.empty((depth_loss_workspace(out_c.shape),), device=out.device, dtype=torch.float64)
+        depth_loss_fwd_bwd(spec, out_c, tgt_c, grad, terms, ws)
+        ctx.save_for_backward(grad)
+        return terms[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+def depth_loss(input: torch.Tensor, target: torch.Tensor, spec) -> torch.Tensor:
+    """The DepthLoss `spec` (or its `.spec()` dict) of an (N, K, H, W) prediction, differentiable w.r.t. `input`: the autograd
+    form of what TrainStep(loss=spec) launches, beside mse_loss / l1_loss."""
+    return _DepthLossFn.apply(input, target, as_depth_loss(spec))
+
+
 class TrainStep:
     """Fused fwd + loss + bwd + Adam + EMA step for a gelslim_depth_amd UNet.
 
@@ -178,10 +319,13 @@ class TrainStep:
     device tensors like `last_loss`.  A non-finite norm raises the guard (nan_policy) or, without one, reaches the parameters
     as a NaN -- it is never clipped away.  `lr_schedule`: an LRSchedule; the rate of a step is lr_at(lr, lr_schedule, t) with
     t the step count Adam's bias correction uses (skipped steps count).  Both are saved with the state.
+
+    `loss`: "mse" (the reference's), "l1", or a DepthLoss, whose one launch takes the place of the plain loss kernel; the step
+    still returns L, and `last_loss_terms` holds its parts.  Saved with the state as the string or the DepthLoss's spec.
     """
 
     def __init__(self, model: UNet, lr: float = 1e-3, weight_decay: float = 1e-6, betas: Tuple[float, float] = (0.9, 0.999),
-                 eps: float = 1e-8, ema_decay: Optional[float] = 0.995, loss: str = "mse",
+                 eps: float = 1e-8, ema_decay: Optional[float] = 0.995, loss: Union[str, "DepthLoss"] = "mse",
                  process_group=None, sync_bn: bool = False, overlap_allreduce: bool = True,
                  nan_policy: Optional[str] = None, force_sync: bool = False, time_allreduce: bool = False,
                  max_grad_norm: Optional[float] = None, lr_schedule: Optional[LRSchedule] = None):
@@ -193,6 +337,10 @@ class TrainStep:
                 raise ValueError(f"max_grad_norm must be positive (None: no clipping), got {max_grad_norm!r}")
         if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
             raise ValueError(f"lr_schedule must be an LRSchedule or None, got {type(lr_schedule).__name__}")
+        if not isinstance(loss, (str, DepthLoss)):
+            raise ValueError(f"loss must be 'mse', 'l1' or a DepthLoss, got {type(loss).__name__}")
+        if isinstance(loss, str) and loss not in LOSS_KINDS:
+            raise ValueError(f"loss must be 'mse', 'l1' or a DepthLoss, got {loss!r}")
         self.max_grad_norm = max_grad_norm
         self.lr_schedule = lr_schedule
         self.model = model
@@ -232,7 +380,9 @@ class TrainStep:
             off += sz
         model._grad_views = gviews
         self.ema_flat = self.p_flat.clone() if ema_decay is not None else None
-        self.loss_buf = torch.zeros((1,), device=dev, dtype=torch.float32)
+        # a DepthLoss writes six terms, L first: the step's loss is their first element
+        self.terms_buf = torch.zeros((6,), device=dev, dtype=torch.float32) if isinstance(loss, DepthLoss) else None
+        self.loss_buf = torch.zeros((1,), device=dev, dtype=torch.float32) if self.terms_buf is None else self.terms_buf[0:1]
         self.loss_ws = torch.empty((2048,), device=dev, dtype=torch.float64)
         # clip = (norm of the averaged gradient before clipping, coefficient in (0, 1]), written by gsd_grad_norm every step
         self.clip_buf = self.norm_ws = None
@@ -306,7 +456,13 @@ class TrainStep:
                   "guard_snapshot")
         try:
             out = eng.forward(x, P, train=True, out=self._out)
-            loss_fwd_bwd(self.loss_kind, out, target, self._dout, self.loss_buf, self.loss_ws, guard=guard)
+            if self.terms_buf is None:
+                loss_fwd_bwd(self.loss_kind, out, target, self._dout, self.loss_buf, self.loss_ws, guard=guard)
+            else:
+                need = depth_loss_workspace(out.shape)
+                if self.loss_ws.numel() < need:
+                    self.loss_ws = torch.empty((need,), device=out.device, dtype=torch.float64)
+                depth_loss_fwd_bwd(self.loss_kind, out, target, self._dout, self.terms_buf, self.loss_ws, guard=guard)
             eng.block_done_cb = self.sync.on_block_done if self.sync is not None else None
             eng.backward(self._dout, P, model._grad_views)
         finally:
@@ -360,6 +516,12 @@ class TrainStep:
         """The last step's clip coefficient min(1, max_grad_norm / (norm + 1e-6)), NaN for a non-finite norm; a device tensor
         like last_grad_norm."""
         return None if self.clip_buf is None else self.clip_buf[1:2]
+
+    @property
+    def last_loss_terms(self) -> Optional[torch.Tensor]:
+        """The last step's six loss terms under a DepthLoss -- L, L_data, L_grad, mean (o-t)^2, mean |o-t|, the fraction of
+        contact pixels -- as a device tensor that every step overwrites (no host sync).  None for loss="mse" / "l1"."""
+        return self.terms_buf
 
     def skipped_steps(self) -> int:
         """Optimiser steps the non-finite guard has skipped so far (one host sync; 0 without a nan_policy)."""
@@ -428,10 +590,14 @@ class TrainStep:
         shapes = {n: tuple(p.shape) for n, p in self.model.named_parameters()}
         return [(n, o, shapes[n]) for n, (o, _) in self.offsets.items()]
 
+    def _loss_hparam(self):
+        """The saved form of `loss`: the string, or the DepthLoss's spec dict."""
+        return self.loss_kind.spec() if isinstance(self.loss_kind, DepthLoss) else self.loss_kind
+
     def _hparams(self) -> Dict[str, object]:
         return {"lr": float(self.lr), "betas": tuple(float(b) for b in self.betas), "eps": float(self.eps),
                 "weight_decay": float(self.wd), "ema_decay": None if self.ema_decay is None else float(self.ema_decay),
-                "loss": self.loss_kind, "nan_policy": self.nan_policy, "max_grad_norm": self.max_grad_norm,
+                "loss": self._loss_hparam(), "nan_policy": self.nan_policy, "max_grad_norm": self.max_grad_norm,
                 "lr_schedule": None if self.lr_schedule is None else self.lr_schedule.spec()}
 
     def state_dict(self) -> Dict[str, object]:
@@ -466,7 +632,8 @@ class TrainStep:
         Raises ValueError, naming the field, before anything is copied: another architecture (the first parameter whose
         name, offset or shape differs), EMA on one side only, or -- with strict=True -- another hyperparameter (lr, betas,
         eps, weight_decay, ema_decay, loss, nan_policy, max_grad_norm, lr_schedule -- absent from a state written before the
-        last two existed, which reads as None); strict=False keeps this TrainStep's hyperparameters (the guard's
+        last two existed, which reads as None; `loss` is the string or a DepthLoss's spec, and of two specs the first differing
+        field is named); strict=False keeps this TrainStep's hyperparameters (the guard's
         skipped-step count then starts at 0 when the state has none).  A weights-only checkpoint is refused.
 
         Data parallel: a collective.  Rank 0's `sd` is checked and loaded (the other ranks may pass None), then its arenas
@@ -547,6 +714,12 @@ class TrainStep:
                     v = float(v)
                 elif k == "lr_schedule" and v is not None:
                     v = dict(v)
+                elif k == "loss" and isinstance(v, dict) and isinstance(mine_h[k], dict):
+                    for f in list(mine_h[k]) + [f for f in v if f not in mine_h[k]]:      # two DepthLoss specs: name the field
+                        if f not in v or f not in mine_h[k] or v[f] != mine_h[k][f]:
+                            raise ValueError(f"TrainStep state: loss field {f} is {v.get(f)!r} in the state and "
+                                             f"{mine_h[k].get(f)!r} here; pass strict=False to continue with this TrainStep's "
+                                             "hyperparameters")
                 if v != mine_h[k]:
                     raise ValueError(f"TrainStep state: {k} is {v!r} in the state and {mine_h[k]!r} here; pass strict=False "
                                      "to continue with this TrainStep's hyperparameters")

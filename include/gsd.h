@@ -398,6 +398,44 @@ int gsd_conv1x1_out_wgrad(const float* raw, const float* scale, const float* shi
 int gsd_loss_fwd_bwd(int kind, const float* o, const float* t, int64_t numel, float grad_scale,
                      float* loss_out, float* grad, float* workspace, const gsd_guard* guard, void* stream);
 
+/* ---- depth-aware loss (an addition: the reference trains on the plain MSE above) ------------- */
+/* o, t: dense fp32 (N, K, H, W).  e = o - t in fp32, M = N*K*H*W.
+ *   L_data = (1/M) sum w * rho(e)     rho = e^2 (data_kind 0) | |e| (1) | huber (2): e^2/2 for |e| <= huber_delta, else
+ *                                     huber_delta * (|e| - huber_delta/2)
+ *                                     w = 1 + contact_weight * [ |t - background| > contact_eps ]   (both tests in fp32)
+ *   L_grad = sum_{k < grad_scales} (1/M_k) sum_{h mod s = 0, w mod s = 0} ( phi(e[h,w+s] - e[h,w]) [w+s < W]
+ *                                                                         + phi(e[h+s,w] - e[h,w]) [h+s < H] )
+ *            s = 2^k, M_k = N*K*ceil(H/s)*ceil(W/s), phi = |g| (grad_kind 0) | g^2 (1), differences in fp32; no wrap-around,
+ *            no padding, nothing across images or classes
+ *   L      = L_data + grad_weight * L_grad
+ * The normalisers are element counts, never sum(w): the loss of a batch is the mean of the losses of its equal shards.
+ * terms (6 device floats) = L, L_data, L_grad, mean e^2, mean |e|, the fraction of contact pixels.
+ * grad (may be NULL: evaluation) = dL/do * grad_scale, each element the sum of the derivatives of the pairs it is an end of
+ * (gather form, no atomics), sign(0) = 0, huber' = clamp(e, -huber_delta, huber_delta); fp32, within 2^-19 of the sum of the
+ * magnitudes of its at most 17 summands.
+ * guard (may be NULL): a non-finite L stores the tick, as gsd_loss_fwd_bwd does.
+ * Two stages, no floating-point atomics: per-block fp64 partial sums (w*rho, the slope term, e^2, |e|, contact count), then
+ * one wave adds them in a fixed order; the block count depends on the shape alone, so the terms are bitwise reproducible
+ * and the same bits with and without grad.  workspace: gsd_depth_loss_workspace doubles, 8-byte aligned.
+ * GSD_ERR_BAD_ARG (null pointer, a dimension <= 0, an unknown kind, grad_scales outside 0..4, a non-zero reserved word, a
+ * negative or non-finite contact_weight / grad_weight / contact_eps / huber_delta, huber_delta == 0 for huber, a non-finite
+ * background, a guard without words or tick) and GSD_ERR_WORKSPACE (workspace_elems too small) are returned before any launch. */
+typedef struct gsd_depth_loss {
+  int32_t data_kind;     /* 0 mse, 1 l1, 2 huber */
+  int32_t grad_kind;     /* 0 l1, 1 l2 */
+  int32_t grad_scales;   /* 0..4 */
+  int32_t reserved;      /* 0 */
+  float huber_delta;     /* read for data_kind 2 only */
+  float contact_weight;
+  float contact_eps;
+  float background;
+  float grad_weight;
+} gsd_depth_loss;
+int64_t gsd_depth_loss_workspace(int N, int K, int H, int W);
+int gsd_depth_loss_fwd_bwd(const gsd_depth_loss* spec, const float* o, const float* t, int N, int K, int H, int W,
+                           float grad_scale, float* terms, float* grad, double* workspace, int64_t workspace_elems,
+                           const gsd_guard* guard, void* stream);
+
 /* ---- optimiser (train_unet.py:306,375-376) -------------------------------------------------- */
 /* Fused torch.optim.Adam(lr, betas, eps, weight_decay: coupled L2) + torch_ema update over a flat
  * parameter arena. step is the 1-based Adam step; ema may be NULL; ema_decay already resolved
