@@ -61,6 +61,14 @@ class gsd_depth_loss(C.Structure):
                 ("background", C.c_float), ("grad_weight", C.c_float)]
 
 
+class gsd_depth_metrics(C.Structure):
+    """The spec of gsd_depth_metrics (include/gsd.h): background and contact threshold in the network's units."""
+    _fields_ = [("background", C.c_float), ("contact_eps", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+GSD_DM_COLS = 16      # doubles per row of gsd_depth_metrics' table
+
+
 class gsd_augment_draw(C.Structure):
     """What gsd_gather_augment draws for one dataset row (gsd_augment_sample)."""
     _fields_ = [("hflip", C.c_int32), ("vflip", C.c_int32), ("dy", C.c_int32), ("dx", C.c_int32),
@@ -166,6 +174,8 @@ SIGNATURES = {
     "gsd_loss_fwd_bwd": (_I, [_I, _P, _P, _L, _F, _P, _P, _P, _GUARD, _P]),
     "gsd_depth_loss_workspace": (_L, [_I, _I, _I, _I]),
     "gsd_depth_loss_fwd_bwd": (_I, [C.POINTER(gsd_depth_loss), _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _L, _GUARD, _P]),
+    "gsd_depth_metrics_workspace": (_L, [_I, _I, _I, _I]),
+    "gsd_depth_metrics": (_I, [C.POINTER(gsd_depth_metrics), _P, _P, _I, _I, _I, _I, _P, _P, _L, _P]),
     "gsd_guard_snapshot": (_I, [_P, _P, _L, _P]),
     "gsd_guard_restore": (_I, [_GUARD, _P, _P, _L, _P]),
     "gsd_adam_ema": (_I, [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _GUARD, _P]),

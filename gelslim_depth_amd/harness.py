@@ -77,29 +77,31 @@ def _mean_loss(losses: List[float], n_batches: int) -> float:
     return float(sum(losses) / n_batches) if n_batches else 0.0
 
 
-def evaluate_loader(step, loader: Iterable[Dict], loss_kind="mse") -> float:
-    """Mean over the loader's batches of the loss under the EMA weights, NaN batches counted as 0 (train_unet.py:379-419).
-    `loss_kind`: "mse" (the reference's, and what `fit` scores), "l1", or a train.DepthLoss, whose total L is averaged.
-
-    Data parallel (a `DeviceLoader` with world_size > 1): the walk is over the GLOBAL batches, every rank evaluates only its
-    contiguous share of each at the per-rank train shape (`DeviceLoader.eval_shares`: no wrap-around padding, no activation
-    buffer reallocated, nothing evaluated twice), and ONE all-reduce at the end of the pass sums (loss sum, element count) per
-    global batch -- every rank then holds the single-process value of every batch loss, bit for bit the same on all ranks.
-    The batch losses stay on the device until the pass ends (one host sync per pass; the reference syncs per batch)."""
+def _evaluate_walk(step, loader: Iterable[Dict], loss_kind, metrics, who: str):
+    """The one evaluation walk behind evaluate_loader and evaluate_metrics: (mean loss, table, (m, pairs)).  Without
+    `metrics` the table is None and nothing but the loss launch follows a forward; with a metrics.DepthMetrics the metrics
+    launch reads the same output and target as the loss launch, and the table -- one row per sample of the pass, in walk order,
+    float64 on the CPU -- comes back with the batch losses when the pass ends."""
     import torch
     from .train import DepthLoss, depth_loss_fwd_bwd, depth_loss_workspace, loss_fwd_bwd
     depth = isinstance(loss_kind, DepthLoss)
     sharded = getattr(loader, "world_size", 1) > 1 and hasattr(loader, "eval_shares")
     if sharded and (getattr(step, "pg", None) is None or getattr(step, "dist", None) is None):
-        raise RuntimeError("evaluate_loader: the loader is sharded over %d ranks but the step was built without a process_group; "
-                           "pass the group to TrainStep or evaluate loader.unsharded()" % loader.world_size)
-    buf = ws = None
+        raise RuntimeError("%s: the loader is sharded over %d ranks but the step was built without a process_group; "
+                           "pass the group to TrainStep or evaluate loader.unsharded()" % (who, loader.world_size))
+    if metrics is not None:
+        from .metrics import COLS, depth_metrics, depth_metrics_workspace, pairs_per_image
+    buf = ws = mws = None
     rows = []          # per (global) batch: device tensor [loss sum over this rank's valid elements, their count]
+    tabs = []          # with metrics, per scored share: (its first sample's position in the walk, its (valid, 16) device table)
+    seen = 0           # samples of the pass walked so far, over all ranks
+    image = (0, 0)     # elements and neighbour pairs of one image
     dev = None
     walk = loader.eval_shares() if sharded else ((data, None, None) for data in loader)
-    for data, valid, _ in walk:
+    for data, valid, global_count in walk:
         if data is None:                  # the ragged tail left this rank nothing of this global batch
             rows.append(None)
+            seen += global_count
             continue
         x, t = data["tactile_image"], data["depth_image"]
         out = step.evaluate(x, use_ema=True)
@@ -108,6 +110,8 @@ def evaluate_loader(step, loader: Iterable[Dict], loss_kind="mse") -> float:
             buf = torch.zeros((6 if depth else 1,), device=dev, dtype=torch.float32)
             ws = torch.empty((2048,), device=dev, dtype=torch.float64)
         t = t.float().contiguous()
+        first = seen + (loader.rank * loader.batch_size if sharded else 0)
+        seen += global_count if sharded else int(out.shape[0])
         if valid is not None and valid < out.shape[0]:
             out, t = out[:valid], t[:valid]       # leading-dimension slices stay contiguous: the padding is not scored
         if depth:
@@ -117,10 +121,31 @@ def evaluate_loader(step, loader: Iterable[Dict], loss_kind="mse") -> float:
         else:
             loss_fwd_bwd(loss_kind, out, t, None, buf, ws)
         rows.append((buf[0].double().clone(), float(out.numel())))      # the element counts stay on the host
-    if not rows:
-        return 0.0
+        if metrics is not None:
+            if mws is None or mws.numel() < depth_metrics_workspace(out.shape):
+                mws = torch.empty((depth_metrics_workspace(out.shape),), device=dev, dtype=torch.float64)
+            tabs.append((first, depth_metrics(out, t, metrics, None, mws)))      # a table of its own per batch: it is kept
+            image = (int(out[0].numel()), pairs_per_image(*(int(d) for d in out.shape[1:])))
     if dev is None:
         dev = getattr(getattr(step, "p_flat", None), "device", None) or torch.device("cpu")
+    table = None
+    if metrics is not None:
+        # every sample of the pass has one row; a rank fills in the rows it scored, the rest stay zero, and one all-reduce
+        # (adding zeros is exact) leaves every rank with the same complete table.  One more row carries the image size to a
+        # rank whose shares were all empty: (m, pairs, 1) from every rank that scored something -- small integers, exact
+        table = torch.zeros((seen + (1 if sharded else 0), COLS), device=dev, dtype=torch.float64)
+        for first, tab in tabs:
+            table[first:first + tab.shape[0]] = tab
+        if sharded:
+            if tabs:
+                table[seen, :3] = torch.tensor([float(image[0]), float(image[1]), 1.0], dtype=torch.float64).to(dev)
+            step.dist.all_reduce(table, group=step.pg)
+        table = table.cpu()
+        if sharded:
+            last, table = table[seen].tolist(), table[:seen].contiguous()
+            image = (int(last[0] / last[2]), int(last[1] / last[2])) if last[2] > 0 else (0, 0)
+    if not rows:
+        return 0.0, table, image
     counts = torch.tensor([r[1] if r is not None else 0.0 for r in rows], dtype=torch.float64)
     zero = torch.zeros((), device=dev, dtype=torch.float64)
     losses = torch.stack([r[0] if r is not None else zero for r in rows])
@@ -131,9 +156,41 @@ def evaluate_loader(step, loader: Iterable[Dict], loss_kind="mse") -> float:
         step.dist.all_reduce(tab, group=step.pg)
         tab = tab.cpu()
         if bool((tab[:, 1] == 0).any()):
-            raise RuntimeError("evaluate_loader: a global batch was scored by no rank (the ranks' loaders disagree on the batch order)")
+            raise RuntimeError("%s: a global batch was scored by no rank (the ranks' loaders disagree on the batch order)" % who)
         vals = (tab[:, 0] / tab[:, 1]).tolist()
-    return _mean_loss([0.0 if v != v else v for v in vals], len(vals))
+    return _mean_loss([0.0 if v != v else v for v in vals], len(vals)), table, image
+
+
+def evaluate_loader(step, loader: Iterable[Dict], loss_kind="mse") -> float:
+    """Mean over the loader's batches of the loss under the EMA weights, NaN batches counted as 0 (train_unet.py:379-419).
+    `loss_kind`: "mse" (the reference's, and what `fit` scores), "l1", or a train.DepthLoss, whose total L is averaged.
+
+    Data parallel (a `DeviceLoader` with world_size > 1): the walk is over the GLOBAL batches, every rank evaluates only its
+    contiguous share of each at the per-rank train shape (`DeviceLoader.eval_shares`: no wrap-around padding, no activation
+    buffer reallocated, nothing evaluated twice), and ONE all-reduce at the end of the pass sums (loss sum, element count) per
+    global batch -- every rank then holds the single-process value of every batch loss, bit for bit the same on all ranks.
+    The batch losses stay on the device until the pass ends (one host sync per pass; the reference syncs per batch)."""
+    return _evaluate_walk(step, loader, loss_kind, None, "evaluate_loader")[0]
+
+
+def evaluate_metrics(step, loader: Iterable[Dict], spec, loss_kind="mse", per_image: bool = False):
+    """`evaluate_loader`'s walk with the per-image depth metrics of `spec` (a metrics.DepthMetrics) taken on the way: returns
+    (loss, summary), or (loss, summary, table) with `per_image`.  `loss` is exactly evaluate_loader(step, loader, loss_kind);
+    `summary` is metrics.summarise of the pass; `table` holds one row per sample (the columns of gsd_depth_metrics,
+    include/gsd.h; float64, CPU) in walk order -- dataset row order for shuffle=False: the handle for finding the worst samples.
+
+    One forward per batch: the loss launch and the metrics launch read the same output, and nothing is synchronised until the
+    pass ends.  Data parallel: every rank scores only the valid leading images of its shares (padded repeats never), places
+    their rows by position in the global walk into a zero-filled table of all samples, and one all-reduce (128 bytes per
+    sample) gives every rank the complete table; the summary is computed from identical rows in identical order and is
+    therefore the same on every rank bit for bit.  A row's bits depend on its image alone, so the table equals the
+    single-process one whenever the eval forward's bits do not depend on the batch (the fp32 engine's do not)."""
+    from .metrics import DepthMetrics, summarise
+    if not isinstance(spec, DepthMetrics):
+        raise TypeError(f"evaluate_metrics: spec must be a metrics.DepthMetrics, got {type(spec).__name__}")
+    loss, table, image = _evaluate_walk(step, loader, loss_kind, spec, "evaluate_metrics")
+    summary = summarise(table, image, spec)
+    return (loss, summary, table) if per_image else (loss, summary)
 
 
 FIT_STATE_FORMAT = "gelslim_depth_amd.harness.fit"
@@ -190,7 +247,7 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
         save_at_epochs: Sequence[int] = (), max_epochs: Optional[int] = None,
         train_pass: Optional[Callable] = None, eval_pass: Optional[Callable] = None, save: Optional[Callable] = None,
         echo: Callable[[str], None] = print, state_path: Optional[str] = None, resume: bool = False,
-        state_every: int = 1) -> Dict[str, List[float]]:
+        state_every: int = 1, metrics=None) -> Dict[str, List[float]]:
     """Run epochs until the stopping rule fires (or `max_epochs`).  Returns H = {train_loss, validation_loss, test_loss}.
 
     `train_pass(step, loader) -> (sum_of_batch_losses, n_batches)`, `eval_pass(step, loader) -> mean_loss` and
@@ -214,11 +271,23 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
     same stopping and checkpoint decisions, and only rank 0 writes checkpoints, the log file and the echo.  Validation and
     test passes walk the GLOBAL batches with every rank scoring its own share (`evaluate_loader`): the value is the
     single-process one (no wrap-around padding in the loss early stopping reads), identical on every rank, at the per-rank
-    train shape; `across()` of it is then the identity up to the last bit."""
+    train shape; `across()` of it is then the identity up to the last bit.
+
+    `metrics` (a metrics.DepthMetrics; None: everything as without it): H gains `validation_metrics` and `test_metrics`, one
+    metrics.summarise dict per epoch, and rank 0 emits one more line per epoch, directly after the `Train loss: ...` line
+    (metrics.log_line has the format).  With the default `eval_pass` the validation and test passes become
+    `evaluate_metrics` walks -- no second forward over either set; with a caller-supplied `eval_pass` the metrics are a walk
+    of their own over the loaders that pass sees.  Both lists are saved with H; a resume from a file without them pads the
+    earlier epochs with None.  The stopping rule still reads the validation loss."""
     if state_every < 1:
         raise ValueError(f"state_every must be at least 1, got {state_every}")
     if train_pass is None:
         from .dataset import train_epoch as train_pass
+    if metrics is not None:
+        from .metrics import DepthMetrics, log_line
+        if not isinstance(metrics, DepthMetrics):
+            raise TypeError(f"fit: metrics must be a metrics.DepthMetrics or None, got {type(metrics).__name__}")
+    fused_metrics = metrics is not None and eval_pass is None
     if eval_pass is None:
         eval_pass = evaluate_loader
     elif getattr(val_loader, "world_size", 1) > 1 and hasattr(val_loader, "unsharded"):
@@ -229,6 +298,7 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
         def save(st, path):
             st.save_checkpoint(path, use_ema=True)
     H: Dict[str, List[float]] = {"train_loss": [], "validation_loss": [], "test_loss": []}
+    METRIC_KEYS = ("validation_metrics", "test_metrics")
     stopper = EarlyStopping(val_loss_SMA_window, validation_loss_count_threshold, train_indefinitely)
     is_main = getattr(step, "rank", 0) == 0
     across = getattr(step, "mean_across_ranks", float)
@@ -254,6 +324,9 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
                 done = bool(saved["stopped"]) or (max_epochs is not None and e >= max_epochs)
                 if is_main:
                     echo(f"Resuming from {state_path} at epoch {e + 1}")
+        if metrics is not None:
+            for k in METRIC_KEYS:
+                H.setdefault(k, [None] * e)      # a fresh run, or a file written without metrics
         while not done:
             t0 = time.time()
             if hasattr(train_loader, "set_epoch"):
@@ -261,10 +334,23 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
             total, nb = train_pass(step, train_loader)
             train_loss = across(total / nb if nb else 0.0)
             H["train_loss"].append(train_loss)
-            validation_loss = across(eval_pass(step, val_loader))
-            H["validation_loss"].append(validation_loss)
-            test_loss = across(eval_pass(step, test_loader))
-            H["test_loss"].append(test_loss)
+            summaries = [None, None]
+            for i, loader in enumerate((val_loader, test_loader)):
+                if fused_metrics:
+                    raw, summaries[i] = evaluate_metrics(step, loader, metrics)
+                else:
+                    raw = eval_pass(step, loader)
+                    if metrics is not None:
+                        summaries[i] = evaluate_metrics(step, loader, metrics)[1]
+                if i == 0:
+                    validation_loss = across(raw)
+                    H["validation_loss"].append(validation_loss)
+                else:
+                    test_loss = across(raw)
+                    H["test_loss"].append(test_loss)
+            for k, summary in zip(METRIC_KEYS, summaries):
+                if k in H:
+                    H[k].append(summary)      # None in a run resumed without `metrics` from a file that has the lists
             stop, stalled, new_min = stopper.update(validation_loss)
             if stalled:
                 emit(f"Validation loss stopped decreasing at epoch {e + 1}")
@@ -278,6 +364,8 @@ def fit(step, train_loader, val_loader, test_loader, weights_path: str, weights_
                 save(step, os.path.join(weights_path, weights_name + "_epoch" + str(e) + ".pth"))
             emit("[INFO] EPOCH: {}".format(e + 1))
             emit("Train loss: {:.6f},  Validation loss: {:.6f}, Test loss: {:.6f}".format(train_loss, validation_loss, test_loss))
+            if metrics is not None:
+                emit(log_line(summaries[0], summaries[1]))
             emit(f"Time for epoch: {time.time() - t0}")
             e += 1
             done = stop or (max_epochs is not None and e >= max_epochs)

@@ -436,6 +436,37 @@ int gsd_depth_loss_fwd_bwd(const gsd_depth_loss* spec, const float* o, const flo
                            float grad_scale, float* terms, float* grad, double* workspace, int64_t workspace_elems,
                            const gsd_guard* guard, void* stream);
 
+/* ---- per-image depth metrics (an addition: the reference reports one mean loss per pass) ---- */
+/* o, t: dense fp32 (N, K, H, W), never written.  e = o - t in fp32.  The kernel works in the network's units only (a
+ * conversion to physical units is one factor on the host), so every decision is an fp32 comparison.  Row n of `table`
+ * (N x GSD_DM_COLS doubles) describes image n alone, over its K*H*W elements:
+ *    0  sum e                    1  sum |e|                  2  sum e^2                3  max |e|
+ *    4  n_t: elements with the target in contact, |t - background| > contact_eps (gsd_depth_loss's test, in fp32)
+ *    5  n_p: the same test on o  6  n_tp: both
+ *    7  sum |e| over target-contact elements                 8  sum e^2 over target-contact elements
+ *    9  max |t - background|     10 max |o - background|     (the fp32 differences: peak indentation)
+ *    11 sum over existing pairs of |e[h,w+1] - e[h,w]| + |e[h+1,w] - e[h,w]|, differences in fp32, inside one (image, class)
+ *       plane, no wrap-around, no padding: scale 0 of gsd_depth_loss's slope term, not normalised
+ *    12 number of elements whose e is not finite             13..15  0
+ * Sums are fp64 of exact summands (|e|, e^2 formed in fp64 from the fp32 e), counts exact, maxima exact fp32 values; a NaN
+ * never wins a maximum (v > m ? v : m, from m = 0), a non-finite e makes the sums of its own image non-finite and is counted
+ * in column 12; no other row is affected.
+ * Two stages, no floating-point atomics: blocks of one image each write a partial row, then one wave per image adds its
+ * image's partial rows in a fixed order.  The number of blocks per image depends on K*H*W alone, so a row is bitwise
+ * reproducible and does not depend on N or on the image's position in the batch.
+ * workspace: gsd_depth_metrics_workspace doubles, 8-byte aligned (as table).  GSD_ERR_BAD_ARG (null pointer, a dimension <= 0,
+ * a non-zero reserved word, a negative or non-finite contact_eps, a non-finite background) and GSD_ERR_WORKSPACE
+ * (workspace_elems too small) are returned before any launch; GSD_ERR_UNSUPPORTED for more than 2^23 blocks (N above 131072). */
+struct gsd_depth_metrics {
+  float background;    /* value of the undeformed gel in the network's units (0 under min_max_to_0_-1) */
+  float contact_eps;   /* a pixel v is "contact" when |v - background| > contact_eps, tested in fp32: DepthLoss's test */
+  int32_t reserved[2]; /* 0 */
+};   /* no typedef: the function below bears the same name (as stat does), so the type is written `struct gsd_depth_metrics` */
+#define GSD_DM_COLS 16
+int64_t gsd_depth_metrics_workspace(int N, int K, int H, int W);            /* doubles */
+int gsd_depth_metrics(const struct gsd_depth_metrics* spec, const float* o, const float* t, int N, int K, int H, int W,
+                      double* table /* N x GSD_DM_COLS */, double* workspace, int64_t workspace_elems, void* stream);
+
 /* ---- optimiser (train_unet.py:306,375-376) -------------------------------------------------- */
 /* Fused torch.optim.Adam(lr, betas, eps, weight_decay: coupled L2) + torch_ema update over a flat
  * parameter arena. step is the 1-based Adam step; ema may be NULL; ema_decay already resolved
