@@ -31,13 +31,33 @@
 //     the CU sat in the same phase and the matrix pipes were 0.53 busy (docs/LOG_r06.md);
 //   * two transform images and two window images (k-step parity), one barrier per k-step.
 //
-// ~1.9 vector instructions per MFMA including addressing (row form: 2.7-3.3), on two thirds of the row form's MFMAs; 23.6 ms for
-// the network's 17 layers at batch 32 against 29.5.  The kernel lives at the register limit and must compile to ZERO scratch
-// (tests/test_abi.py): with spills hipcc stored two slots on some paths of a branchy prologue only and reloaded them on all.
+// On two thirds of the row form's MFMAs; 22.5 ms for the network's 17 layers at batch 32 (row form: 29.5; this kernel before its
+// bookkeeping left the vector pipe: 23.8 on the same box, profiles/wg2d_scalar_layers_b32.txt).  The kernel lives at the register
+// limit and must compile to ZERO scratch (tests/test_abi.py): with spills hipcc stored two slots on some paths of a branchy
+// prologue only and reloaded them on all.
 // Split-K over k-steps with ordered slab reduction (the row form's reducer and slab layout): bitwise reproducible.
 //
-// Conventions: U row 3 is +dY row 1 and V row 3 is d3 - d1 (both signs of the textbook F(2,3) flipped: same products); the six
-// frequencies of a row are stored in the order [1, 2, 3, 4, 0, 5] (what the packed transforms produce as register pairs).
+// Conventions: U row 3 is +dY row 1 and V row 3 is d3 - d1 (both signs of the textbook F(2,3) flipped: same products).
+//
+// Record order.  The 24 frequencies (fr, fc) of a (tile, channel) record are six 16-byte groups, one ds_read_b128 operand each, and
+// every group is made of the register pairs the packed transforms produce together ((1,2), (3,4) and, in a V row, (0,5)):
+//   group 0..3: frequencies fc = 1, 2, 3, 4 of row fr = 0, 3, 1, 2 (in this order: the 64 x 64 form's U lane then reaches its own row
+//               and the row it combines with its partner, 0 and 1 or 3 and 2, at one constant distance, 32 bytes);
+//   group 4:    [row 0 fc 0, row 3 fc 0, row 0 fc 5, row 3 fc 5];        group 5: the same of rows 1 and 2.
+// A U task stores groups as 16-byte pieces; the frequencies 0 and 5 of a row are y[0] and y[3] of a raw dy piece and never a
+// register pair, so groups 4 and 5 take 4-byte stores where a lane holds one row (V rows, the 64 x 64 form's U) and one 16-byte
+// store assembled by three v_mov where it holds both (the 128 x 32 form's U).  U, V and the epilogue agree on this order and
+// nothing else knows it: the accumulator of frequency (fr, fc) is acc[4 group + position].
+//
+// The loop keeps its bookkeeping off the vector pipe (an fp32 MFMA stream hides scalar instructions and LDS reads, no vector one):
+//   * every k-step loads and transforms: a block that has run out of k-steps fetches its last one again (the walk stops, by scalar
+//     selects) into the image of a k-step whose MFMAs never run -- no "is there a next k-step" flag in front of every piece;
+//   * what is wave-uniform (the border flag, the walk, the fill tests) is an integer in a scalar register;
+//   * border k-steps take their masks from two per-lane tables built once in the prologue (row_tab, col_tab below): a lane's masks
+//     are separable into a part that depends on the k-step's row position and one that depends on its column position, and only
+//     the first, the last and (with a cropped segment) the last-but-one position of a direction mask anything.  The border pieces
+//     lie out of line; an interior k-step runs straight through.
+// Static counts per instantiation: tests/test_wg2d_isa.py, profiles/wg2d_isa_counts.txt.
 #include "gsd_common.h"
 #include "gsd_wgrad_internal.h"
 #include <type_traits>
@@ -46,6 +66,14 @@
 #include <cstdlib>
 
 typedef float f32x2d __attribute__((ext_vector_type(2)));
+
+// An LDS location from its 32-bit byte address.  The lane's task addresses are formed ONCE, in the prologue, with the base of the
+// dynamic LDS block in them: `smem + offset` per access left a `v_add_u32 v, 0, v` in front of every task's LDS instructions (the
+// base is resolved to 0 only after instruction selection).
+template <class T>
+__device__ __forceinline__ __attribute__((address_space(3))) T* wg_lds(unsigned byte_addr) {
+  return (__attribute__((address_space(3))) T*)(size_t)byte_addr;
+}
 
 struct WgW2dParams {
   SrcD a0, a1;   // activation (B operand), up to two concatenated segments
@@ -58,6 +86,22 @@ struct WgW2dParams {
   int WR, NP, NI;        // window of a k-step: 2 KY + 2 rows x KX + 1 pieces of 4 floats per channel; NI 64-piece fills per block
   int ksteps_total, splits, mblocks, nblocks;
 };
+
+// x where bit `bit` of m is set, +0 elsewhere: a sign-extended bit and an AND.  (The mask is opaque: hipcc otherwise turns the AND
+// back into a bit test, a compare and a select, hoists the tests of two tasks out of a border block and speculates the block.)
+__device__ __forceinline__ int wg_bit_mask(int m, const int bit) {
+  int k = (m << (31 - bit)) >> 31;
+  asm volatile("" : "+v"(k));
+  return k;
+}
+__device__ __forceinline__ float wg_keep(float x, int m, const int bit) {
+  return __builtin_bit_cast(float, __builtin_bit_cast(int, x) & wg_bit_mask(m, bit));
+}
+__device__ __forceinline__ f32x4 wg_keep4(const f32x4 x, int m, const int bit) {
+  typedef int i32x4w __attribute__((ext_vector_type(4)));
+  const int k = wg_bit_mask(m, bit);
+  return __builtin_bit_cast(f32x4, __builtin_bit_cast(i32x4w, x) & i32x4w{k, k, k, k});
+}
 
 __device__ __forceinline__ float w2d_dpp(float v, const int ctrl_is_pair) {
   // quad_perm [2,2,1,1] (0x5A): V column transform partners; quad_perm [1,0,3,2] (0xB1): the other row of a dy pair
@@ -107,24 +151,30 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
   const int S_c0 = n0 - (seg1 ? P.a0.C : 0);   // first channel of the block inside the segment
 
   // ---- transform tasks of this thread -----------------------------------------------------------------------------------------
-  // (the tile coordinates inside the k-step are needed again in border k-steps only: packed into one register there)
+  // (the tile coordinates inside the k-step are needed again for the border masks only: the class tables below, built once)
   const int kxm = P.KX - 1;
   // U: (co, tile[, dy row])
   const int u_t = UROW ? (tid >> 1) & 3 : tid & 3;
   const int u_r = UROW ? tid & 1 : 0;
   const int u_co = UROW ? tid >> 3 : tid >> 2;
   const int u_tyl = u_t >> P.kx_log2, u_txl = u_t & kxm;
-  const unsigned u_voff = (unsigned)((long long)u_co * P.dy.cs + (long long)(2 * u_tyl + u_r) * P.dy.ws + 4 * u_txl) * 4u;
-  const unsigned u_wr = (unsigned)(IMG + u_t * TSU + u_co * 24) * 4u;                // byte offsets of the thread's results in image 0
+  unsigned u_voff = (unsigned)((long long)u_co * P.dy.cs + (long long)(2 * u_tyl + u_r) * P.dy.ws + 4 * u_txl) * 4u;
+  const unsigned smem_b = (unsigned)(size_t)(__attribute__((address_space(3))) void*)smem;   // LDS byte address of smem[0]
+  // LDS byte addresses of the thread's results in image 0 (record order: see the header).  UROW: u_wr is the lane's own row (fr 0
+  // or 3; the combined row fr 1 or 2 lies 32 bytes behind it), u_ws its frequency 0 (frequency 5 at + 8, the combined row's at + 16)
+  const unsigned u_rec = smem_b + (unsigned)(IMG + u_t * TSU + u_co * 24) * 4u;
+  const unsigned u_wr = u_rec + (UROW ? 16u * u_r : 0u);
+  const unsigned u_ws = u_rec + 64u + 4u * u_r;
   // V rows: (ci, tile, window row kr); lane quad = the four rows of one (ci, tile)
   const int v_kr = tid & 3, v_t = (tid >> 2) & 3, v_ci = tid >> 4;
   const int v_tyl = v_t >> P.kx_log2, v_txl = v_t & kxm;
-  const unsigned v_rd = (unsigned)(WIN + ((v_ci * P.WR + 2 * v_tyl + v_kr) * P.NP + v_txl) * 4) * 4u;   // its 6 floats in the window image
-  const unsigned v_wr = (unsigned)(IMG + 4 * TSU + v_t * TSV + v_ci * 24 + v_kr * 6) * 4u;
-  int geo_packed = u_tyl | u_txl << 3 | v_tyl << 6 | v_txl << 9 | v_kr << 12 | u_r << 15;
-  asm volatile("" : "+v"(geo_packed));   // opaque: otherwise hipcc keeps the six fields in six registers for the whole kernel
-  const float v_sgn = (tid & 3) == 1 ? 1.f : -1.f;   // kr0: r0 - r2, kr1: r1 + r2, kr2: r2 - r1, kr3: r3 - r1
-  const float u_sgn = (UROW && (tid & 1)) ? -1.f : 1.f;    // UROW: row 0 forms r0 + r1, row 1 forms r0 - r1
+  const unsigned v_rd = smem_b + (unsigned)(WIN + ((v_ci * P.WR + 2 * v_tyl + v_kr) * P.NP + v_txl) * 4) * 4u;   // its 6 floats in the window image
+  const int v_slot = (0x1320 >> (4 * v_kr)) & 3;   // frequency row kr -> its 16-byte group: rows are stored in the order 0, 3, 1, 2
+  const unsigned v_rec = smem_b + (unsigned)(IMG + 4 * TSU + v_t * TSV + v_ci * 24) * 4u;
+  const unsigned v_wr = v_rec + 16u * v_slot;                                  // the row's frequencies 1..4
+  const unsigned v_ws = v_rec + 64u + 16u * (v_slot >> 1) + 4u * (v_slot & 1);   // its frequency 0; frequency 5 at + 8
+  float v_sgn = (tid & 3) == 1 ? 1.f : -1.f;   // kr0: r0 - r2, kr1: r1 + r2, kr2: r2 - r1, kr3: r3 - r1
+  float u_sgn = (UROW && (tid & 1)) ? -1.f : 1.f;    // UROW: row 0 forms r0 + r1, row 1 forms r0 - r1
   // deferred BatchNorm of the block's BN channels: (scale, shift) pairs in LDS behind the images, read per task and k-step (one
   // ds_read_b64 instead of two registers per task held for the whole kernel; the kernel lives at the register limit)
   constexpr int SCS = IMG + 2 * BUF;
@@ -158,15 +208,22 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
   //     of the k-step (80 instead of 128 bytes per row at 1 x 4 tiles) and moved as runs of consecutive pieces by consecutive lanes
   //     (fill i = pieces 64 i .. 64 i + 63 of the image, wave w issues fills w, w + 8, ...).  Another wave's pieces are read, so
   //     there are two window images (k-step parity) and the fills are published by the k-step's barrier (vmcnt(0) in front of it).
-  int r_mask = 0;            // edge k-steps: bit 0/1 dy row ok, bits 2..7: window columns of the V tasks ok
-  bool r_edge = false;       // wave-uniform: the masks apply
+  int r_mask = 0;            // edge k-steps: bit 0/1 dy row ok, bits 2..7: window columns of the V tasks ok (bits 8..: the loaded k-step's fills)
+  int r_edge = 0;            // wave-uniform, an INTEGER in a scalar register: the masks apply (hipcc parks a uniform bool that crosses
+                             // the loop in a vector register and branches on it through v_cndmask / v_cmp / vcc)
+  int st_left = nst - 1;     // k-steps the walk below may still advance by
   float* const raw_w = smem + wave * 256;                       // this wave's slot of piece 0 (wave-uniform: the DMA's LDS base)
   const float* const raw_r = smem + wave * 256 + lane * 4;  // this lane's 16 bytes of piece 0
   // window fills of this wave: piece 64 (wave + 8 k) + lane = (channel, window row, piece) -> byte offset from the k-step's window
-  // origin in the first channel's plane; row and piece packed for border k-steps (-1: a dummy lane behind the image)
+  // origin in the first channel's plane (0 for a dummy lane behind the image); what a border k-step masks: row_tab / col_tab
   unsigned x_off[KB];
-  int x_meta = 0;   // 8 bits per fill: window row | piece << 4 | dummy << 7
+  auto fill_bit = [](const int k) { return k < 2 ? 256 << k : 2; };   // mask bit of window fill k
+  int row_tab, col_tab;   // border masks of this lane by k-step class (below)
+  // the last-but-one k-step of a direction is a border k-step only where the segment ends inside its window (-1: it does not)
+  const int sy_l2 = P.sy_n > 2 && 2 * (P.sy_n - 1) * P.KY + 1 - S_oh > S_H ? P.sy_n - 2 : -1;
+  const int sx_l2 = P.sx_n > 2 && 4 * (P.sx_n - 1) * P.KX + 1 - S_ow > S_W ? P.sx_n - 2 : -1;
   {
+    int x_wr[KB], x_pp[KB];   // window row and piece of fill k (-1: a dummy lane behind the image)
     const int per_ch = P.WR * P.NP;
 #pragma unroll
     for (int k = 0; k < KB; ++k) {
@@ -175,9 +232,47 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
       const int wr = rem / P.NP, pp = rem - wr * P.NP;
       const bool dummy = ch >= BN;
       x_off[k] = dummy ? 0u : (unsigned)((long long)ch * S_cs + (long long)wr * S_ws + 4 * pp) * 4u;
-      x_meta |= (dummy ? 128 : (wr | pp << 4)) << (8 * k);
+      x_wr[k] = dummy ? -1 : wr;
+      x_pp[k] = pp;
     }
-    asm volatile("" : "+v"(x_meta));
+    // Border masks.  What a lane must mask in a border k-step is separable: the dy rows and window rows that exist depend on the
+    // k-step's ROW position only, the tile columns and window columns on its COLUMN position only, and only the first, the last
+    // and -- where a cropped segment ends inside its window -- the last but one k-step of a direction need a mask in that direction
+    // (the host admits no other geometry).  So the lane's masks are computed ONCE, here, for these positions -- a 10-bit field each:
+    //   bits 0, 1: dy row 0 / 1 of the U task    bits 2..7: the six window columns of the V row task(s)    bits 8, 9: window fills 0, 1
+    //   (64 x 64 form: its U task has one dy row, bit 0, and bit 1 is window fill 2)
+    // (a row field has its V bits all equal, a column field its U bits) -- and a border k-step ANDs the row field and the column
+    // field of its two classes.  A table holds the fields of class 1 (first), 2 (last, not first) and 3 (last but one, where it
+    // needs a mask) at bit 10 x (class - 1): a lookup is a shift by a scalar; class 0 (no mask in this direction) is all ones, ORed
+    // in from a scalar.  A dummy fill lane has no bit in any field.
+    auto row_field = [&](const int ty0) {
+      const int hs = 2 * ty0 - 1 - S_oh;
+      const int uty = ty0 + u_tyl, h = 2 * uty + u_r;
+      int f = (uty < P.tiles_y && h < P.H ? 1 : 0) | (!UROW && uty < P.tiles_y && h + 1 < P.H ? 2 : 0);
+      if (ty0 + v_tyl < P.tiles_y && (unsigned)(hs + 2 * v_tyl + v_kr) < (unsigned)S_H) f |= 0xFC;
+#pragma unroll
+      for (int k = 0; k < KB; ++k)
+        if (x_wr[k] >= 0 && (unsigned)(hs + x_wr[k]) < (unsigned)S_H) f |= fill_bit(k);
+      return f;
+    };
+    auto col_field = [&](const int tx0) {
+      const int wsx = 4 * tx0 - 1 - S_ow;
+      int f = tx0 + u_txl < P.tiles_x ? (UROW ? 1 : 3) : 0;
+      // the valid columns of the 6-float row piece are the range [max(0, -c0), min(6, S_W - c0)): a mask from two shifts
+      const int c0 = wsx + 4 * v_txl;
+      const int lo_ = c0 < 0 ? -c0 : 0, hi_ = S_W - c0;
+      const int lo = lo_ < 6 ? lo_ : 6, hi = hi_ < 0 ? 0 : (hi_ < 6 ? hi_ : 6);   // shift counts in [0, 6]
+      if (tx0 + v_txl < P.tiles_x && hi > lo) f |= (((1 << hi) - 1) & ~((1 << lo) - 1)) << 2;
+#pragma unroll
+      for (int k = 0; k < KB; ++k) {
+        const int ck = wsx + 4 * x_pp[k];
+        if (x_wr[k] >= 0 && ck + 3 >= 0 && ck < S_W) f |= fill_bit(k);
+      }
+      return f;
+    };
+    row_tab = row_field(0) | row_field((P.sy_n - 1) * P.KY) << 10 | row_field((P.sy_n > 2 ? P.sy_n - 2 : 0) * P.KY) << 20;
+    col_tab = col_field(0) | col_field((P.sx_n - 1) * P.KX) << 10 | col_field((P.sx_n > 2 ? P.sx_n - 2 : 0) * P.KX) << 20;
+    asm volatile("" : "+v"(row_tab), "+v"(col_tab));
   }
 
   // Addresses: a wave-uniform 64-bit base that depends on the IMAGE only (the block's first channel plane) plus an unsigned 32-bit
@@ -186,15 +281,29 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
   // the MFMA phase; at 256 registers hipcc then spilled the zero-extended offsets on some paths of the branchy prologue only and
   // reloaded them on all -- wild addresses, a memory fault at the 160x213 level.  No 64-bit vector address selects here, the raw
   // values wait in LDS, and tests/test_abi.py checks that these kernels use no scratch.)
+  // the wave issues fill k: all but the last are always on (the host checks NI > 8 (KB - 1)); the last as a scalar integer
+  auto fill_on = [&](const int k) __attribute__((always_inline)) {
+    if (k < KB - 1) return true;
+    int w = wave;
+    asm volatile("" : "+s"(w));   // (opaque: the test is two scalar instructions here, not a flag that hipcc parks in a vector register)
+    return w + 8 * (KB - 1) < P.NI;
+  };
   auto load = [&](auto wb_c) __attribute__((always_inline)) {
     constexpr int wb = decltype(wb_c)::value;   // window image of the k-step (its parity inside the block's range)
     const int n = st_n, ty0 = st_sy * P.KY, tx0 = st_sx * P.KX;
-    if (++st_sx == P.sx_n) {
-      st_sx = 0;
-      if (++st_sy == P.sy_n) {
-        st_sy = 0;
-        ++st_n;
-      }
+    // the k-step's classes (0: no mask, 1: first, 2: last and not first, 3: last but one where that needs one), scalar integers
+    const int cy = st_sy == 0 ? 1 : (st_sy == P.sy_n - 1 ? 2 : (st_sy == sy_l2 ? 3 : 0));
+    const int cx = st_sx == 0 ? 1 : (st_sx == P.sx_n - 1 ? 2 : (st_sx == sx_l2 ? 3 : 0));
+    {
+      // advance the walk -- by scalar selects, and not past the block's last k-step: a load that comes after it fetches that k-step
+      // again (addresses a real load has read), into the image and slots of a k-step whose MFMAs never run
+      const int adv = st_left > 0 ? 1 : 0;
+      st_left -= adv;
+      const int sx1 = st_sx + 1, wx = sx1 == P.sx_n ? 1 : 0;
+      const int sy1 = st_sy + wx, wy = sy1 == P.sy_n ? 1 : 0;
+      st_sx = adv ? (wx ? 0 : sx1) : st_sx;
+      st_sy = adv ? (wy ? 0 : sy1) : st_sy;
+      st_n += adv & wy;
     }
     const char* const dblk = reinterpret_cast<const char*>(P.dy.p + (long long)n * P.dy.ns + (long long)m0 * P.dy.cs);
     // (the activation base is 4 floats IN FRONT of the plane, inside the slack the caller vouches for: the piece that starts at
@@ -205,36 +314,18 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
     const int hs = 2 * ty0 - 1 - S_oh, wsx = 4 * tx0 - 1 - S_ow;
     const unsigned d_org = (unsigned)(2 * ty0 * P.dy.ws + 4 * tx0) * 4u;   // k-step origin inside a dy plane, bytes
     const int v_org = (hs * S_ws + wsx) * 4 + 16;                          // ... from vblk (< 0 only where every lane is masked)
-    const bool tiles_in = ty0 + P.KY <= P.tiles_y && tx0 + P.KX <= P.tiles_x;
-    const bool inside = tiles_in && 2 * (ty0 + P.KY) <= P.H && hs >= 0 && hs + 2 * P.KY + 2 <= S_H && wsx >= 0 &&
-                        wsx + 4 * P.KX + 2 <= S_W;
-    r_edge = !inside;
-    unsigned o_y0 = d_org + u_voff, o_y1 = o_y0 + (unsigned)P.dy.ws * 4u;
-    if (!inside) {
-      int m = 0;
-      int geo = geo_packed;
-      asm volatile("" : "+v"(geo));   // (as x_meta below)
-      {
-        const int ty = ty0 + (geo & 7), tx = tx0 + (geo >> 3 & 7);
-        const bool t_ok = ty < P.tiles_y && tx < P.tiles_x;
-        const int h = 2 * ty + (geo >> 15 & 1);
-        const bool ok0 = t_ok && h < P.H, ok1 = t_ok && h + 1 < P.H;
-        o_y0 = ok0 ? o_y0 : 0u;
-        o_y1 = ok1 ? o_y1 : 0u;
-        m = (ok0 ? 1 : 0) | (ok1 ? 2 : 0);
-      }
-      {
-        const int vy = geo >> 6 & 7, vx = geo >> 9 & 7;
-        const int ty = ty0 + vy, tx = tx0 + vx;
-        const bool t_ok = ty < P.tiles_y && tx < P.tiles_x;
-        const int row = hs + 2 * vy + (geo >> 12 & 3), c0 = wsx + 4 * vx;
-        const bool r_ok = t_ok && (unsigned)row < (unsigned)S_H;
-        // the valid columns of the 6-float row piece are the range [max(0, -c0), min(6, S_W - c0)): a mask from two shifts
-        const int lo_ = c0 < 0 ? -c0 : 0, hi_ = S_W - c0;
-        const int lo = lo_ < 6 ? lo_ : 6, hi = hi_ < 0 ? 0 : (hi_ < 6 ? hi_ : 6);   // shift counts in [0, 6]
-        const int cm = (r_ok && hi > lo) ? ((1 << hi) - 1) & ~((1 << lo) - 1) : 0;
-        m |= cm << 2;
-      }
+    r_edge = __builtin_amdgcn_readfirstlane(cy | cx);
+    asm volatile("" : "+v"(u_voff));   // (opaque: hipcc otherwise re-associates the sum in element units, four vector instructions for two)
+    unsigned o_y0 = d_org + u_voff, o_y1 = d_org + (unsigned)P.dy.ws * 4u + u_voff;
+    unsigned x_o[KB];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) x_o[k] = (unsigned)v_org + x_off[k];
+    if (__builtin_expect(r_edge != 0, 0)) {
+      const int m = ((row_tab >> (cy ? 10 * cy - 10 : 0)) | (cy ? 0 : 0x3ff)) & ((col_tab >> (cx ? 10 * cx - 10 : 0)) | (cx ? 0 : 0x3ff));   // (bits 10.. are not looked at)
+      o_y0 &= (unsigned)wg_bit_mask(m, 0);
+      if constexpr (!UROW) o_y1 &= (unsigned)wg_bit_mask(m, 1);
+#pragma unroll
+      for (int k = 0; k < KB; ++k) x_o[k] &= (unsigned)wg_bit_mask(m, k < 2 ? 8 + k : 1);
       r_mask = m;
     }
     auto fill = [&](const char* base, unsigned off, float* dst) __attribute__((always_inline)) {
@@ -244,17 +335,8 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
     // lies, partly outside or not (the transform masks by column); one without is not read where it lies (offset 0)
 #pragma unroll
     for (int k = 0; k < KB; ++k)
-      if (wave + 8 * k < P.NI) {
-        unsigned off = (unsigned)v_org + x_off[k];
-        if (!inside) {
-          int mt = x_meta;
-          asm volatile("" : "+v"(mt));   // (unpacked HERE, in border k-steps only: hipcc would hoist the fields out of the loop into registers)
-          mt >>= 8 * k;
-          const int row = hs + (mt & 15), c0 = wsx + 4 * (mt >> 4 & 7);
-          const bool ok = !(mt & 128) && (unsigned)row < (unsigned)S_H && c0 + 3 >= 0 && c0 < S_W;
-          off = ok ? off : 0u;
-        }
-        fill(vblk, off, smem + WIN + wb * (WINI * 256) + (wave + 8 * k) * 256);
+      if (fill_on(k)) {
+        fill(vblk, x_o[k], smem + WIN + wb * (WINI * 256) + (wave + 8 * k) * 256);
       }
     // dy pieces go into the slots this thread reads its raw dy rows from: those reads have to have RETURNED before a fill can land
     __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
@@ -262,12 +344,58 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
     if constexpr (!UROW) fill(dblk, o_y1, raw_w + 8 * 256);
   };
 
+  // Stores of a task's 24 (U) or 6 (V row) values at byte offset `ib` (the image) from the task's addresses.  A 16-byte group is
+  // two register pairs that the transforms produce together, so hipcc's 16-byte stores need no v_mov -- except the one group of the
+  // 128 x 32 form's U task that holds y[0] and y[3] of its two raw pieces.  The 4-byte stores are volatile: left to itself hipcc
+  // pairs them into the two-address form, whose 8-bit offsets do not reach image 1 -- a v_add_u32 per pair.
+  auto st1 = [&](const unsigned a, const float v) __attribute__((always_inline)) { *wg_lds<volatile float>(a) = v; };
+  auto st_u = [&](const unsigned ib, const f32x4& y0, const f32x4& y1, const f32x2d a12, const f32x2d a34, const f32x2d b12,
+                  const f32x2d b34) __attribute__((always_inline)) {
+    if constexpr (UROW) {
+      // this lane holds A4 of ONE dy row; rows fr of U = [r0, r0 + r1, r0 - r1, r1]: lane r = 0 stores (own, own + x) as rows 0, 1,
+      // lane r = 1 stores (own, x - own) as rows 3, 2
+      asm volatile("" : "+v"(u_sgn));   // (as the V column sign)
+      const float sgn = u_sgn;
+      const f32x2d sg = {sgn, sgn};
+      const f32x2d x12 = {w2d_dpp(a12[0], 1), w2d_dpp(a12[1], 1)}, x34 = {w2d_dpp(a34[0], 1), w2d_dpp(a34[1], 1)};
+      const float x0 = w2d_dpp(y0[0], 1), x5 = w2d_dpp(y0[3], 1);
+      const f32x2d t12 = __builtin_elementwise_fma(a12, sg, x12), t34 = __builtin_elementwise_fma(a34, sg, x34);
+      *wg_lds<f32x4>(u_wr + ib) = f32x4{a12[0], a12[1], a34[0], a34[1]};
+      *wg_lds<f32x4>(u_wr + ib + 32) = f32x4{t12[0], t12[1], t34[0], t34[1]};
+      st1(u_ws + ib, y0[0]);
+      st1(u_ws + ib + 8, y0[3]);
+      st1(u_ws + ib + 16, __builtin_fmaf(y0[0], sgn, x0));
+      st1(u_ws + ib + 24, __builtin_fmaf(y0[3], sgn, x5));
+    } else {
+      // rows fr of U = [r0, r0 + r1, r0 - r1, r1]; (s0, d0) and (s5, d5) by one packed fma with (1, -1) each
+      const f32x2d pm = {1.f, -1.f};
+      const f32x2d sd0 = __builtin_elementwise_fma(f32x2d{y1[0], y1[0]}, pm, f32x2d{y0[0], y0[0]});
+      const f32x2d sd5 = __builtin_elementwise_fma(f32x2d{y1[3], y1[3]}, pm, f32x2d{y0[3], y0[3]});
+      *wg_lds<f32x2d>(u_wr + ib) = a12;
+      *wg_lds<f32x2d>(u_wr + ib + 8) = a34;
+      *wg_lds<f32x2d>(u_wr + ib + 16) = b12;
+      *wg_lds<f32x2d>(u_wr + ib + 24) = b34;
+      *wg_lds<f32x2d>(u_wr + ib + 32) = a12 + b12;
+      *wg_lds<f32x2d>(u_wr + ib + 40) = a34 + b34;
+      *wg_lds<f32x2d>(u_wr + ib + 48) = a12 - b12;
+      *wg_lds<f32x2d>(u_wr + ib + 56) = a34 - b34;
+      *wg_lds<f32x4>(u_wr + ib + 64) = f32x4{y0[0], y1[0], y0[3], y1[3]};
+      *wg_lds<f32x2d>(u_wr + ib + 80) = sd0;
+      *wg_lds<f32x2d>(u_wr + ib + 88) = sd5;
+    }
+  };
+  auto st_v = [&](const unsigned ib, const f32x2d o12, const f32x2d o34, const f32x2d o05) __attribute__((always_inline)) {
+    *wg_lds<f32x4>(v_wr + ib) = f32x4{o12[0], o12[1], o34[0], o34[1]};
+    st1(v_ws + ib, o05[0]);
+    st1(v_ws + ib + 8, o05[1]);
+  };
+
   // transform this thread's raw pieces into LDS image `buf` (compile-time constant)
   auto transform = [&](auto buf_c) __attribute__((always_inline)) {
     constexpr int buf = decltype(buf_c)::value;
     // Packed fp32 math (v_pk_add_f32 / v_pk_fma_f32: two floats for the issue slot of one; an fp32 MFMA stream does not hide vector
-    // instructions, profiles/r05_mfma_f32_issue_ubench.txt).  The six frequencies of a row are stored in the order
-    // [1, 2, 3, 4, 0, 5]: the transforms produce (1,2), (3,4) and (0,5) as register pairs, and U, V and the epilogue only have to agree.
+    // instructions, profiles/r05_mfma_f32_issue_ubench.txt).  The transforms produce the frequencies (1,2), (3,4) and (0,5) of a row
+    // as register pairs; st_u / st_v store them in the record order of the header.
     const f32x2d p1m1 = {1.f, -1.f}, p2m2 = {2.f, -2.f}, c4 = {4.f, 4.f};
     // A4 of one dy row (y0..y3) -> (U1, U2), (U3, U4); U0 = y0, U5 = y3
     auto a4_row = [&](const f32x4& y, f32x2d& u12, f32x2d& u34) __attribute__((always_inline)) {
@@ -282,50 +410,21 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
       f32x4 y0 = *reinterpret_cast<const f32x4*>(raw_r), y1 = y0;
       if constexpr (!UROW) y1 = *reinterpret_cast<const f32x4*>(raw_r + 8 * 256);
       if (r_edge) {
-        if (!(r_mask & 1)) y0 = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (!UROW)
-          if (!(r_mask & 2)) y1 = f32x4{0.f, 0.f, 0.f, 0.f};
+        y0 = wg_keep4(y0, r_mask, 0);
+        if constexpr (!UROW) y1 = wg_keep4(y1, r_mask, 1);
       }
       f32x2d a12, a34;
       a4_row(y0, a12, a34);
-      if constexpr (UROW) {
-        // this lane holds A4 of ONE dy row; rows fr of U = [r0, r0 + r1, r0 - r1, r1]: lane r = 0 stores (own, own + x) as rows 0, 1,
-        // lane r = 1 stores (x - own, own) as rows 2, 3
-        const f32x2d sg = {u_sgn, u_sgn};
-        const f32x2d a05 = {y0[0], y0[3]};
-        const f32x2d x12 = {w2d_dpp(a12[0], 1), w2d_dpp(a12[1], 1)}, x34 = {w2d_dpp(a34[0], 1), w2d_dpp(a34[1], 1)};
-        const f32x2d x05 = {w2d_dpp(a05[0], 1), w2d_dpp(a05[1], 1)};
-        const f32x2d t12 = __builtin_elementwise_fma(a12, sg, x12), t34 = __builtin_elementwise_fma(a34, sg, x34);
-        const f32x2d t05 = __builtin_elementwise_fma(a05, sg, x05);
-        float* const o_own = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + u_wr) + buf * BUF + ((tid & 1) ? 18 : 0);
-        float* const o_t1 = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + u_wr) + buf * BUF + ((tid & 1) ? 12 : 6);
-        *reinterpret_cast<f32x2d*>(o_own) = a12;
-        *reinterpret_cast<f32x2d*>(o_own + 2) = a34;
-        *reinterpret_cast<f32x2d*>(o_own + 4) = a05;
-        *reinterpret_cast<f32x2d*>(o_t1) = t12;
-        *reinterpret_cast<f32x2d*>(o_t1 + 2) = t34;
-        *reinterpret_cast<f32x2d*>(o_t1 + 4) = t05;
-      } else {
-        f32x2d b12, b34;
-        a4_row(y1, b12, b34);
-        const f32x2d s12 = a12 + b12, s34 = a34 + b34, d12 = a12 - b12, d34 = a34 - b34;
-        const float s0 = y0[0] + y1[0], s5 = y0[3] + y1[3], d0 = y0[0] - y1[0], d5 = y0[3] - y1[3];
-        // rows fr of U = [r0, r0 + r1, r0 - r1, r1], 24 consecutive floats as six 16-byte groups
-        float* const op = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + u_wr) + buf * BUF;
-        *reinterpret_cast<f32x4*>(op) = f32x4{a12[0], a12[1], a34[0], a34[1]};
-        *reinterpret_cast<f32x4*>(op + 4) = f32x4{y0[0], y0[3], s12[0], s12[1]};
-        *reinterpret_cast<f32x4*>(op + 8) = f32x4{s34[0], s34[1], s0, s5};
-        *reinterpret_cast<f32x4*>(op + 12) = f32x4{d12[0], d12[1], d34[0], d34[1]};
-        *reinterpret_cast<f32x4*>(op + 16) = f32x4{d0, d5, b12[0], b12[1]};
-        *reinterpret_cast<f32x4*>(op + 20) = f32x4{b34[0], b34[1], y1[0], y1[3]};
-      }
+      f32x2d b12 = a12, b34 = a34;
+      if constexpr (!UROW) a4_row(y1, b12, b34);
+      st_u(buf * BUF * 4u, y0, y1, a12, a34, b12, b34);
     }
     // ---- V rows ----
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const float* const wp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(smem) + v_rd) + buf * (WINI * 256) + i * 32 * (P.WR * P.NP * 4);
-      const f32x4 ra = *reinterpret_cast<const f32x4*>(wp);
-      const f32x2d rb = *reinterpret_cast<const f32x2d*>(wp + 4);
+      const unsigned wp = v_rd + buf * (WINI * 256) * 4u + (i ? (unsigned)(32 * 16 * (P.WR * P.NP)) : 0u);
+      const f32x4 ra = *wg_lds<const f32x4>(wp);
+      const f32x2d rb = *wg_lds<const f32x2d>(wp + 16);
       f32x2d t0 = {ra[0], ra[1]}, t1 = {ra[2], ra[3]}, t2 = rb;
       if constexpr (!PLAIN) {
         const f32x2d ss = *reinterpret_cast<const f32x2d*>(smem + SCS + 2 * ((tid >> 4) + 32 * i));
@@ -336,12 +435,9 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
       }
       if (r_edge) {
         const int m = r_mask;
-        if (!(m & 4)) t0[0] = 0.f;
-        if (!(m & 8)) t0[1] = 0.f;
-        if (!(m & 16)) t1[0] = 0.f;
-        if (!(m & 32)) t1[1] = 0.f;
-        if (!(m & 64)) t2[0] = 0.f;
-        if (!(m & 128)) t2[1] = 0.f;
+        t0 = f32x2d{wg_keep(t0[0], m, 2), wg_keep(t0[1], m, 3)};
+        t1 = f32x2d{wg_keep(t1[0], m, 4), wg_keep(t1[1], m, 5)};
+        t2 = f32x2d{wg_keep(t2[0], m, 6), wg_keep(t2[1], m, 7)};
       }
       // B4^T of the window row d0..d5 = (t0, t1, t2), as gsd_conv3x3_w2d.hip forms it
       const f32x2d m41 = {-4.f, -1.f}, m5 = {-5.f, -5.f};
@@ -354,17 +450,18 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
       const f32x2d sg = {v_sgn, v_sgn};
       const f32x2d x12 = {w2d_dpp(v12[0], 0), w2d_dpp(v12[1], 0)}, x34 = {w2d_dpp(v34[0], 0), w2d_dpp(v34[1], 0)};
       const f32x2d x05 = {w2d_dpp(v05[0], 0), w2d_dpp(v05[1], 0)};
-      float* const op = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + v_wr) + buf * BUF + i * (32 * 24);
-      *reinterpret_cast<f32x2d*>(op) = __builtin_elementwise_fma(sg, x12, v12);
-      *reinterpret_cast<f32x2d*>(op + 2) = __builtin_elementwise_fma(sg, x34, v34);
-      *reinterpret_cast<f32x2d*>(op + 4) = __builtin_elementwise_fma(sg, x05, v05);
+      st_v((buf * BUF + i * (32 * 24)) * 4u, __builtin_elementwise_fma(sg, x12, v12), __builtin_elementwise_fma(sg, x34, v34),
+           __builtin_elementwise_fma(sg, x05, v05));
     }
   };
 
   f32x4 acc[2][24];   // (zeroed behind the pipeline's prologue: 192 registers that the prologue's address work does not have to avoid)
 
-  const int a_rd = IMG + j * TSU + (wm * 32 + l16) * 24;
-  const int b_rd = IMG + 4 * TSU + j * TSV + (wn * 16 + l16) * 24;
+  // operand reads: ONE address register per operand, the image's offset (< 64 KiB) in the instruction's immediate
+  unsigned a_rd = smem_b + (unsigned)(IMG + j * TSU + (wm * 32 + l16) * 24) * 4u;
+  unsigned b_rd = smem_b + (unsigned)(IMG + 4 * TSU + j * TSV + (wn * 16 + l16) * 24) * 4u;
+  asm volatile("" : "+v"(a_rd), "+v"(b_rd));
+  static_assert((BUF + 16 * 24 + 24) * 4 < 65536, "image 1 within the 16-bit offset of a ds_read");
 
   // ---- pipeline: image (it & 1) holds the transforms of k-step `it`; the raw registers hold k-step it + 1 ---------------------
   using I0 = std::integral_constant<int, 0>;
@@ -373,7 +470,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
     load(I0{});
     gsd_dma_barrier();   // vmcnt(0) + barrier: everyone's fills of the first k-step are in
     transform(I0{});
-    if (nst > 1) load(I1{});
+    load(I1{});          // (the block's only k-step again if nst == 1)
     gsd_dma_barrier();
   }
 #pragma unroll
@@ -387,19 +484,17 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
     // removing a third of the vector instructions changed nothing.  Here the vector work rides between the MFMA groups: a piece
     // of ~10-16 instructions works on values that were read a group earlier, clustered (the first vector instruction in an MFMA gap
     // costs 12.6 cycles, each further one 4: profiles/r05_mfma_f32_issue_ubench.txt), and its LDS latencies lie behind MFMAs.
-    auto step = [&](const int it, auto cur_c) __attribute__((always_inline)) {
+    auto step = [&](auto cur_c) __attribute__((always_inline)) {
       constexpr int cur = decltype(cur_c)::value, nxt = cur ^ 1;
-      const bool tr = it + 1 < nst, ld = it + 2 < nst;
-      const float* const Sb = smem + cur * BUF;
       const f32x2d p1m1 = {1.f, -1.f}, p2m2 = {2.f, -2.f}, c4 = {4.f, 4.f};
       // One operand group = four frequencies of (channel l16, tile j) per ds_read_b128: 3 reads feed 8 MFMAs.  The groups are NOT
       // double-buffered in the source: 12 operand registers instead of 24 keep the kernel inside 256 registers without scratch, and
       // the SIMD's other wave multiplies while this one waits for its reads.
       f32x4 a0, a1, b;
       auto rd_ops = [&](const int g) __attribute__((always_inline)) {
-        a0 = *reinterpret_cast<const f32x4*>(Sb + a_rd + 4 * g);
-        a1 = *reinterpret_cast<const f32x4*>(Sb + a_rd + 16 * 24 + 4 * g);
-        b = *reinterpret_cast<const f32x4*>(Sb + b_rd + 4 * g);
+        a0 = *wg_lds<const f32x4>(a_rd + (cur * BUF + 4 * g) * 4u);
+        a1 = *wg_lds<const f32x4>(a_rd + (cur * BUF + 16 * 24 + 4 * g) * 4u);
+        b = *wg_lds<const f32x4>(b_rd + (cur * BUF + 4 * g) * 4u);
       };
       auto mm = [&](const int g) __attribute__((always_inline)) {
 #pragma unroll
@@ -417,55 +512,37 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
       };
       // masks of the k-step being transformed (load() below replaces r_mask / r_edge by the next one's)
       const int t_mask = r_mask;
-      const bool t_edge = r_edge;
+      int t_edge = r_edge;
+      asm volatile("" : "+s"(t_edge));
+      auto edge = [&]() __attribute__((always_inline)) {   // opaque per use: a scalar compare and branch each
+        int e = t_edge;
+        asm volatile("" : "+s"(e));
+        return e != 0;
+      };
       f32x4 y0, y1;
       f32x2d a12, a34, b12, b34;
       f32x4 ra;
       f32x2d rb, v12, v34, v05;
-      float* const u_out = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + u_wr) + nxt * BUF;
       auto rd_y = [&]() __attribute__((always_inline)) {
         y0 = *reinterpret_cast<const f32x4*>(raw_r);
         y1 = y0;
         if constexpr (!UROW) y1 = *reinterpret_cast<const f32x4*>(raw_r + 8 * 256);
       };
       auto u_rows = [&]() __attribute__((always_inline)) {      // A4 along the dy rows
-        if (t_edge) {
-          if (!(t_mask & 1)) y0 = f32x4{0.f, 0.f, 0.f, 0.f};
-          if constexpr (!UROW)
-            if (!(t_mask & 2)) y1 = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (__builtin_expect(edge(), 0)) {   // (the border pieces lie out of line: the interior path falls through)
+          y0 = wg_keep4(y0, t_mask, 0);
+          if constexpr (!UROW) y1 = wg_keep4(y1, t_mask, 1);
         }
         a4_row(y0, a12, a34);
         if constexpr (!UROW) a4_row(y1, b12, b34);
       };
       auto u_cols = [&]() __attribute__((always_inline)) {      // A2 down the columns, stores
-        if constexpr (UROW) {
-          const f32x2d sg = {u_sgn, u_sgn};
-          const f32x2d a05 = {y0[0], y0[3]};
-          const f32x2d x12 = {w2d_dpp(a12[0], 1), w2d_dpp(a12[1], 1)}, x34 = {w2d_dpp(a34[0], 1), w2d_dpp(a34[1], 1)};
-          const f32x2d x05 = {w2d_dpp(a05[0], 1), w2d_dpp(a05[1], 1)};
-          float* const o_own = u_out + ((tid & 1) ? 18 : 0);
-          float* const o_t1 = u_out + ((tid & 1) ? 12 : 6);
-          *reinterpret_cast<f32x2d*>(o_own) = a12;
-          *reinterpret_cast<f32x2d*>(o_own + 2) = a34;
-          *reinterpret_cast<f32x2d*>(o_own + 4) = a05;
-          *reinterpret_cast<f32x2d*>(o_t1) = __builtin_elementwise_fma(a12, sg, x12);
-          *reinterpret_cast<f32x2d*>(o_t1 + 2) = __builtin_elementwise_fma(a34, sg, x34);
-          *reinterpret_cast<f32x2d*>(o_t1 + 4) = __builtin_elementwise_fma(a05, sg, x05);
-        } else {
-          const f32x2d s12 = a12 + b12, s34 = a34 + b34, d12 = a12 - b12, d34 = a34 - b34;
-          const float s0 = y0[0] + y1[0], s5 = y0[3] + y1[3], d0 = y0[0] - y1[0], d5 = y0[3] - y1[3];
-          *reinterpret_cast<f32x4*>(u_out) = f32x4{a12[0], a12[1], a34[0], a34[1]};
-          *reinterpret_cast<f32x4*>(u_out + 4) = f32x4{y0[0], y0[3], s12[0], s12[1]};
-          *reinterpret_cast<f32x4*>(u_out + 8) = f32x4{s34[0], s34[1], s0, s5};
-          *reinterpret_cast<f32x4*>(u_out + 12) = f32x4{d12[0], d12[1], d34[0], d34[1]};
-          *reinterpret_cast<f32x4*>(u_out + 16) = f32x4{d0, d5, b12[0], b12[1]};
-          *reinterpret_cast<f32x4*>(u_out + 20) = f32x4{b34[0], b34[1], y1[0], y1[3]};
-        }
+        st_u(nxt * BUF * 4u, y0, y1, a12, a34, b12, b34);
       };
       auto rd_v = [&](const int i) __attribute__((always_inline)) {
-        const float* const wp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(smem) + v_rd) + nxt * (WINI * 256) + i * 32 * (P.WR * P.NP * 4);
-        ra = *reinterpret_cast<const f32x4*>(wp);
-        rb = *reinterpret_cast<const f32x2d*>(wp + 4);
+        const unsigned wp = v_rd + nxt * (WINI * 256) * 4u + (i ? (unsigned)(32 * 16 * (P.WR * P.NP)) : 0u);
+        ra = *wg_lds<const f32x4>(wp);
+        rb = *wg_lds<const f32x2d>(wp + 16);
       };
       auto v_rows = [&](const int i) __attribute__((always_inline)) {   // deferred BatchNorm + ReLU, masks, B4^T along the window row
         f32x2d t0 = {ra[0], ra[1]}, t1 = {ra[2], ra[3]}, t2 = rb;
@@ -476,14 +553,11 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
           t1 = __builtin_elementwise_max(__builtin_elementwise_fma(t1, sc2, sh2), lo2);
           t2 = __builtin_elementwise_max(__builtin_elementwise_fma(t2, sc2, sh2), lo2);
         }
-        if (t_edge) {
+        if (__builtin_expect(edge(), 0)) {   // (the border pieces lie out of line: the interior path falls through)
           const int m = t_mask;
-          if (!(m & 4)) t0[0] = 0.f;
-          if (!(m & 8)) t0[1] = 0.f;
-          if (!(m & 16)) t1[0] = 0.f;
-          if (!(m & 32)) t1[1] = 0.f;
-          if (!(m & 64)) t2[0] = 0.f;
-          if (!(m & 128)) t2[1] = 0.f;
+          t0 = f32x2d{wg_keep(t0[0], m, 2), wg_keep(t0[1], m, 3)};
+          t1 = f32x2d{wg_keep(t1[0], m, 4), wg_keep(t1[1], m, 5)};
+          t2 = f32x2d{wg_keep(t2[0], m, 6), wg_keep(t2[1], m, 7)};
         }
         const f32x2d m41 = {-4.f, -1.f}, m5 = {-5.f, -5.f};
         const f32x2d ac = __builtin_elementwise_fma(f32x2d{t1[0], t1[0]}, m41, f32x2d{t2[0], t2[0]});
@@ -493,16 +567,14 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
         v05 = __builtin_elementwise_fma(t0, c4, __builtin_elementwise_fma(t1, m5, t2));
       };
       auto v_cols = [&](const int i) __attribute__((always_inline)) {   // B2^T down the window column (quad partners by DPP), stores
-        int tq = threadIdx.x;
-        asm volatile("" : "+v"(tq));   // (the sign is re-derived here, three instructions, instead of living in a register: as geo_packed)
-        const float sgn = (tq & 3) == 1 ? 1.f : -1.f;
-        const f32x2d sg = {sgn, sgn};
+        // ONE register for the whole kernel (re-deriving it cost four vector instructions per task); opaque here, so that the pair
+        // is formed by the instruction's operand selects and not held as two registers
+        asm volatile("" : "+v"(v_sgn));
+        const f32x2d sg = {v_sgn, v_sgn};
         const f32x2d x12 = {w2d_dpp(v12[0], 0), w2d_dpp(v12[1], 0)}, x34 = {w2d_dpp(v34[0], 0), w2d_dpp(v34[1], 0)};
         const f32x2d x05 = {w2d_dpp(v05[0], 0), w2d_dpp(v05[1], 0)};
-        float* const op = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + v_wr) + nxt * BUF + i * (32 * 24);
-        *reinterpret_cast<f32x2d*>(op) = __builtin_elementwise_fma(sg, x12, v12);
-        *reinterpret_cast<f32x2d*>(op + 2) = __builtin_elementwise_fma(sg, x34, v34);
-        *reinterpret_cast<f32x2d*>(op + 4) = __builtin_elementwise_fma(sg, x05, v05);
+        st_v((nxt * BUF + i * (32 * 24)) * 4u, __builtin_elementwise_fma(sg, x12, v12), __builtin_elementwise_fma(sg, x34, v34),
+             __builtin_elementwise_fma(sg, x05, v05));
       };
       // one MFMA group, the next group's operand reads behind it, and a vector piece
       auto group = [&](const int g, auto piece) __attribute__((always_inline)) {
@@ -513,24 +585,25 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
         __builtin_amdgcn_sched_barrier(0);
       };
       rd_ops(0);
-      if (tr) rd_y();
+      rd_y();
       __builtin_amdgcn_sched_barrier(0);
-      group(0, [&]() __attribute__((always_inline)) { if (ld) load(cur_c); });   // fills of k-step it + 2 (this one's parity); waits for rd_y
-      group(1, [&]() __attribute__((always_inline)) { if (tr) { u_rows(); if constexpr (UROW) u_cols(); } });
-      group(2, [&]() __attribute__((always_inline)) { if (tr) { rd_v(0); if constexpr (!UROW) u_cols(); } });
-      group(3, [&]() __attribute__((always_inline)) { if (tr) v_rows(0); });
-      group(4, [&]() __attribute__((always_inline)) { if (tr) { v_cols(0); if constexpr (NV > 1) rd_v(1); } });
+      group(0, [&]() __attribute__((always_inline)) { load(cur_c); });   // fills of k-step it + 2 (this one's parity); waits for rd_y
+      group(1, [&]() __attribute__((always_inline)) { u_rows(); if constexpr (UROW) u_cols(); });
+      group(2, [&]() __attribute__((always_inline)) { rd_v(0); if constexpr (!UROW) u_cols(); });
+      group(3, [&]() __attribute__((always_inline)) { v_rows(0); });
+      group(4, [&]() __attribute__((always_inline)) { v_cols(0); if constexpr (NV > 1) rd_v(1); });
       group(5, [&]() __attribute__((always_inline)) {
         if constexpr (NV > 1) {
-          if (tr) { v_rows(1); v_cols(1); }
+          v_rows(1);
+          v_cols(1);
         }
       });
       // the fills of k-step it + 2 have had the MFMA groups to land; published to the other waves (window pieces) by the barrier
       gsd_dma_barrier();
     };
     for (int it = 0; it < nst; it += 2) {
-      step(it, I0{});
-      if (it + 1 < nst) step(it + 1, I1{});
+      step(I0{});
+      if (it + 1 < nst) step(I1{});
     }
   }
 
@@ -550,9 +623,10 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_w2d_kernel(const WgW2dParams 
       float E[4][3];
 #pragma unroll
       for (int fr = 0; fr < 4; ++fr) {
-        // (stored order of a row's frequencies: [1, 2, 3, 4, 0, 5])
-        const float D1 = acc[m][fr * 6 + 0][reg], D2 = acc[m][fr * 6 + 1][reg], D3 = acc[m][fr * 6 + 2][reg];
-        const float D4 = acc[m][fr * 6 + 3][reg], D0 = acc[m][fr * 6 + 4][reg], D5 = acc[m][fr * 6 + 5][reg];
+        // (record order: frequencies 1..4 of row fr in group sl, frequencies 0 and 5 in groups 4 and 5 -- see the header)
+        const int sl = (0x1320 >> (4 * fr)) & 3, f0 = 16 + 4 * (sl >> 1) + (sl & 1);
+        const float D1 = acc[m][4 * sl + 0][reg], D2 = acc[m][4 * sl + 1][reg], D3 = acc[m][4 * sl + 2][reg];
+        const float D4 = acc[m][4 * sl + 3][reg], D0 = acc[m][f0][reg], D5 = acc[m][f0 + 2][reg];
         E[fr][0] = 0.25f * D0 - (1.f / 6.f) * (D1 + D2) + (1.f / 24.f) * (D3 + D4);
         E[fr][1] = (1.f / 6.f) * (D2 - D1) + (1.f / 12.f) * (D3 - D4);
         E[fr][2] = (1.f / 6.f) * (D3 + D4 - D1 - D2) + D5;
@@ -581,7 +655,9 @@ WgW2dPlan plan_wg2d(int N, int H, int W, int M, int Ncols) {
   p.tiles_y = ceil_div(H, 2);
   p.tiles_x = ceil_div(W, 4);
   long best = -1;
-  const int force_kx = gsd_env_int("GSD_WG2D_KX", 0);   // tuning
+  int force_kx = gsd_env_int("GSD_WG2D_KX", 0);   // tuning: 1, 2 or 4 tiles across; any other value is ignored
+  if (force_kx != 1 && force_kx != 2 && force_kx != 4) force_kx = 0;
+  p.KY = 1; p.KX = 4;
   for (int kx = 4; kx >= 1; kx /= 2) {
     if (force_kx && kx != force_kx) continue;
     const int ky = 4 / kx;
@@ -602,7 +678,7 @@ WgW2dPlan plan_wg2d(int N, int H, int W, int M, int Ncols) {
   p.mblocks = ceil_div(M, p.BM);
   p.nblocks = ceil_div(Ncols, p.BN);
   p.ksteps_total = N * p.sy_n * p.sx_n;
-  const int target = gsd_env_int("GSD_WG2D_BLOCKS", 256);   // one block per CU
+  const int target = gsd_env_int("GSD_WG2D_BLOCKS", gsd_cu_count());   // one block per CU (256 on MI355X, and where no device is visible)
   int splits = ceil_div(target, p.mblocks * p.nblocks);
   if (splits > p.ksteps_total) splits = p.ksteps_total;
   if (splits > 2048) splits = 2048;
@@ -636,6 +712,10 @@ int gsd_wgrad_w2d_use(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, in
   if ((int64_t)p.BM * dy->c_stride * 4 >= (1LL << 31)) return 0;   // lane offsets are 32-bit byte offsets inside a block's planes
   if (nsrc == 2 && a[0].C % p.BN != 0) return 0;
   for (int i = 0; i < nsrc; ++i) {
+    // the kernel's border masks go by k-step class: a k-step that is not the first, the last or the last but one of a direction
+    // must lie inside the segment in that direction (true whenever the pad offsets are smaller than a k-step, as in the U-Net)
+    if (p.sy_n > 2 && (a[i].off_h < 0 || a[i].off_h > 2 * p.KY - 1 || 2 * (p.sy_n > 3 ? p.sy_n - 2 : 0) * p.KY + 1 - a[i].off_h > a[i].H)) return 0;
+    if (p.sx_n > 2 && (a[i].off_w < 0 || a[i].off_w > 4 * p.KX - 1 || 4 * (p.sx_n > 3 ? p.sx_n - 2 : 0) * p.KX + 1 - a[i].off_w > a[i].W)) return 0;
     if (a[i].slack < 4) return 0;
     if ((int64_t)p.BN * a[i].c_stride * 4 >= (1LL << 31)) return 0;
     if ((int64_t)(a[i].H + 4) * a[i].w_stride * 4 >= (1LL << 31)) return 0;   // (k-step origins inside a plane are 32-bit too)
@@ -668,7 +748,7 @@ int gsd_wgrad_w2d_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, in
   // LDS (floats): dy slots [1 or 2 pieces][8 waves][256] | two window images of 10 / 20 KiB | two images of [4 tiles][BM | BN][24] (+4) | (scale, shift)[BN]
   const size_t lds = ((size_t)(pl.BM == 64 ? 1 : 2) * 8 * 256 + (size_t)2 * (pl.BN == 32 ? 10 : 20) * 256 +
                       (size_t)2 * (4 * (pl.BM * 24 + 4) + 4 * (pl.BN * 24 + 4)) + 2 * pl.BN) * sizeof(float);
-  GSD_REQUIRE(P.NI <= 8 * (pl.BN == 32 ? 2 : 3) && P.NI <= (pl.BN == 32 ? 10 : 20), GSD_ERR_UNSUPPORTED, "gsd_conv3x3_wgrad (w2d): window image too large");
+  GSD_REQUIRE(P.NI <= 8 * (pl.BN == 32 ? 2 : 3) && P.NI <= (pl.BN == 32 ? 10 : 20) && P.NI > 8 * (pl.BN == 32 ? 1 : 2), GSD_ERR_UNSUPPORTED, "gsd_conv3x3_wgrad (w2d): window image too large");
   if (gsd_env_set("GSD_WG43_TRACE"))   // tuning: one line per launch
     fprintf(stderr, "wg2d M%d N%d %dx%d B%d kstep %dx%d ksteps %d splits %d blocks %ld BM %d BN %d plain %d lds %zu\n", Cout, Cin, H, W,
             N, pl.KY, pl.KX, pl.ksteps_total, pl.splits, grid, pl.BM, pl.BN, (int)plain, lds);
