@@ -69,6 +69,21 @@ class gsd_depth_metrics(C.Structure):
 GSD_DM_COLS = 16      # doubles per row of gsd_depth_metrics' table
 
 
+class gsd_mesh_grid(C.Structure):
+    """The uniform cell grid of one mesh (include/gsd.h, gsd_mesh_depth_*): origin, cell size, centre, cells per axis."""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("cell", C.c_float), ("inv_cell", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class gsd_mesh_view(C.Structure):
+    """How gsd_mesh_depth_render looks at the mesh (include/gsd.h): pixel pitch, width offset, axis order, pose sense, channels."""
+    _fields_ = [("mpp", C.c_float), ("width_offset", C.c_float), ("swap_axes", C.c_int32), ("invert_affine", C.c_int32),
+                ("lr_flip", C.c_int32), ("reserved", C.c_int32)]
+
+
+GSD_MESH_RECORD_FLOATS = 12   # floats per triangle record of gsd_mesh_depth_count
+
+
 class gsd_augment_draw(C.Structure):
     """What gsd_gather_augment draws for one dataset row (gsd_augment_sample)."""
     _fields_ = [("hflip", C.c_int32), ("vflip", C.c_int32), ("dy", C.c_int32), ("dx", C.c_int32),
@@ -176,6 +191,13 @@ SIGNATURES = {
     "gsd_depth_loss_fwd_bwd": (_I, [C.POINTER(gsd_depth_loss), _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _L, _GUARD, _P]),
     "gsd_depth_metrics_workspace": (_L, [_I, _I, _I, _I]),
     "gsd_depth_metrics": (_I, [C.POINTER(gsd_depth_metrics), _P, _P, _I, _I, _I, _I, _P, _P, _L, _P]),
+    "gsd_mesh_depth_plan": (_I, [C.POINTER(C.c_double), _D, C.POINTER(gsd_mesh_grid)]),
+    "gsd_mesh_depth_workspace": (_L, [C.POINTER(gsd_mesh_grid)]),
+    "gsd_mesh_depth_count": (_I, [C.POINTER(gsd_mesh_grid), _P, _I, _P, _P, _L, _P]),
+    "gsd_mesh_depth_fill": (_I, [C.POINTER(gsd_mesh_grid), _P, _I, _P, _L, _P, _L, _P]),
+    "gsd_mesh_depth_render_workspace": (_L, [_I]),
+    "gsd_mesh_depth_render": (_I, [C.POINTER(gsd_mesh_grid), C.POINTER(gsd_mesh_view), _P, _I, _P, _P, _L, _P, _P, _I, _I, _I,
+                                   _P, _P, _L, _P]),
     "gsd_guard_snapshot": (_I, [_P, _P, _L, _P]),
     "gsd_guard_restore": (_I, [_GUARD, _P, _P, _L, _P]),
     "gsd_adam_ema": (_I, [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _GUARD, _P]),

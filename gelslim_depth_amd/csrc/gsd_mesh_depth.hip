@@ -1,0 +1,384 @@
+// gsd_mesh_depth.hip -- ground-truth depth images of a rigid triangle mesh under a batch of in-hand poses (gfx950),
+// include/gsd.h: gsd_mesh_depth_*.  The definition is DESIGN.md section 16; in short, for every pixel of either finger
+//   right = -max(0, Qmax - g/2),   left = min(0, Qmin + g/2),
+// Qmax / Qmin the largest / smallest signed perpendicular coordinate q over all triangles whose in-plane projection covers
+// the pixel (edges inclusive, zero-area projections skipped, q interpolated linearly and clamped to the triangle's own range),
+// 0 where nothing covers it.
+//
+// The mesh is rigid: everything that depends on it is built once (count -> scan -> fill) and serves any number of poses.
+//
+//   record (12 floats, 48 B, three 16-byte loads): the triangle's in-plane vertices SORTED lexicographically by (x, y),
+//   V0 < V1 < V2, their q, and 1 / (signed doubled area), 0 for a triangle that is skipped.  Coverage is decided by the three
+//   edge functions  F_ij(p) = (Vj - Vi) x (p - Vi)  of the sorted pairs (0,1), (1,2), (0,2).  Two triangles that share an edge
+//   hold the same two vertex bit patterns in the same order, so both evaluate the SAME floating-point expression for that edge
+//   and take it with opposite signs: a point is never rejected by both (no cracks along shared edges), and with inclusive edges
+//   it may be accepted by both, which max / min do not notice.  (Vertex + two edge vectors, the textbook record, cannot give
+//   that: the third edge would be a difference of differences.)
+//
+//   grid: nx x ny square cells over the mesh's in-plane bounding box.  A triangle is listed in every cell its vertex bounding
+//   box overlaps; the render tests that same bounding box (the same fp32 values, compared exactly) before the edge functions,
+//   and both sides map a coordinate to a cell with one monotone expression, so a pixel a triangle covers always finds the
+//   triangle in its cell's list -- for ANY cell size.  The image therefore does not depend on the grid (tests render the same
+//   batch on a one-cell grid, the default and a four times finer one and compare bits).  The order inside a list depends on
+//   the atomic cursor and changes from build to build; the image does not, max and min are order-free.
+//
+//   render: a block of 256 threads owns a 16 x 16 pixel tile of one (pose, channel) image, a wave an 8 x 8 patch of it, so
+//   the 64 mesh points of a wave fall into few cells.  A thread maps its pixel into the mesh frame (pose table: cos, sin from
+//   the double-precision functions, rounded once), walks its cell's list, MD_WALK entries per trip, keeping one extreme in a
+//   register (the right finger only needs Qmax, the left only Qmin = -max(-q)), and stores one float.  No atomics on the
+//   image, no LDS.
+#include "gsd_common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int MD_REC = GSD_MESH_RECORD_FLOATS;   // floats per triangle record
+constexpr int MD_MAX_T = 1 << 24;                // triangles per mesh
+constexpr int MD_MAX_N = 2048;                   // cells per grid axis
+constexpr int MD_POSE = 8;                       // floats per row of the pose table
+constexpr int MD_WALK = 4;                       // list entries a render thread handles per trip
+
+struct MdGrid {
+  float x0, y0, inv_cell;
+  int nx, ny;
+};
+
+__device__ __forceinline__ int md_cell(float v, float g0, float inv_cell, int n) {
+#pragma clang fp contract(off)
+  const float f = (v - g0) * inv_cell;
+  int i = (int)floorf(f);
+  i = i < 0 ? 0 : i;
+  return i > n - 1 ? n - 1 : i;
+}
+
+struct MdTri {
+  float x0, y0, x1, y1, x2, y2, q0, q1, q2, inv;
+};
+__device__ __forceinline__ MdTri md_load(const float* __restrict__ rec, int id) {
+  const f32x4* p = reinterpret_cast<const f32x4*>(rec + (size_t)id * MD_REC);
+  const f32x4 a = p[0], b = p[1], c = p[2];
+  MdTri t;
+  t.x0 = a[0], t.y0 = a[1], t.x1 = a[2], t.y1 = a[3];
+  t.x2 = b[0], t.y2 = b[1], t.q0 = b[2], t.q1 = b[3];
+  t.q2 = c[0], t.inv = c[1];
+  return t;
+}
+
+// cells [ix0, ix1] x [iy0, iy1] that the vertex bounding box of a record overlaps: the x are sorted, the y are not
+__device__ __forceinline__ void md_cell_range(const MdTri& t, const MdGrid& G, int& ix0, int& ix1, int& iy0, int& iy1) {
+  ix0 = md_cell(t.x0, G.x0, G.inv_cell, G.nx);
+  ix1 = md_cell(t.x2, G.x0, G.inv_cell, G.nx);
+  iy0 = md_cell(fminf(t.y0, fminf(t.y1, t.y2)), G.y0, G.inv_cell, G.ny);
+  iy1 = md_cell(fmaxf(t.y0, fmaxf(t.y1, t.y2)), G.y0, G.inv_cell, G.ny);
+}
+
+__device__ __forceinline__ bool md_less(float ax, float ay, float bx, float by) { return ax < bx || (ax == bx && ay < by); }
+
+// one thread per triangle: the record, and +1 on every cell its bounding box overlaps
+__global__ __launch_bounds__(256) void mesh_records_count(const MdGrid G, const float* __restrict__ tri, int T,
+                                                          float* __restrict__ rec, int* __restrict__ count) {
+#pragma clang fp contract(off)
+  const int id = blockIdx.x * 256 + threadIdx.x;
+  if (id >= T) return;
+  const float* v = tri + (size_t)id * 9;
+  float ax = v[0], ay = v[1], aq = v[2], bx = v[3], by = v[4], bq = v[5], cx = v[6], cy = v[7], cq = v[8];
+#define MD_SWAP(px, py, pq, rx, ry, rq)                                   \
+  if (md_less(rx, ry, px, py)) {                                          \
+    float s_;                                                             \
+    s_ = px, px = rx, rx = s_, s_ = py, py = ry, ry = s_, s_ = pq, pq = rq, rq = s_; \
+  }
+  MD_SWAP(ax, ay, aq, bx, by, bq)
+  MD_SWAP(bx, by, bq, cx, cy, cq)
+  MD_SWAP(ax, ay, aq, bx, by, bq)
+#undef MD_SWAP
+  // doubled signed area from two rounded products: exactly 0 for coincident or proportional edge vectors (a vertical wall)
+  const float p1 = (bx - ax) * (cy - ay), p2 = (by - ay) * (cx - ax);
+  const float area = p1 - p2;
+  const float inv = 1.0f / area;
+  const bool ok = area != 0.f && isfinite(area) && isfinite(inv) && inv != 0.f && isfinite(aq) && isfinite(bq) && isfinite(cq);
+  MdTri t;
+  t.x0 = ax, t.y0 = ay, t.x1 = bx, t.y1 = by, t.x2 = cx, t.y2 = cy, t.q0 = aq, t.q1 = bq, t.q2 = cq, t.inv = ok ? inv : 0.f;
+  f32x4* out = reinterpret_cast<f32x4*>(rec + (size_t)id * MD_REC);
+  out[0] = f32x4{ax, ay, bx, by};
+  out[1] = f32x4{cx, cy, aq, bq};
+  out[2] = f32x4{cq, t.inv, 0.f, 0.f};
+  if (!ok) return;
+  int ix0, ix1, iy0, iy1;
+  md_cell_range(t, G, ix0, ix1, iy0, iy1);
+  for (int iy = iy0; iy <= iy1; ++iy)
+    for (int ix = ix0; ix <= ix1; ++ix) atomicAdd(count + (size_t)iy * G.nx + ix, 1);
+}
+
+// one block: exclusive scan of the cell counts, in place (start[c], start[ncells] = total), a copy as the fill's cursors,
+// and the total as an int64 (the int32 starts wrap beyond 2^31 - 1 pairs; the caller reads the total before it fills)
+__global__ __launch_bounds__(1024) void mesh_scan(int ncells, int* __restrict__ start, int* __restrict__ cursor,
+                                                  long long* __restrict__ total) {
+  __shared__ long long part[1024];
+  const int tid = threadIdx.x;
+  const int per = (ncells + 1023) / 1024;
+  const int lo = min(tid * per, ncells), hi = min(lo + per, ncells);
+  long long s = 0;
+  for (int c = lo; c < hi; ++c) s += start[c];
+  part[tid] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const long long add = tid >= o ? part[tid - o] : 0;
+    __syncthreads();
+    part[tid] += add;
+    __syncthreads();
+  }
+  long long run = part[tid] - s;   // exclusive prefix of this thread's run
+  for (int c = lo; c < hi; ++c) {
+    const int n = start[c];
+    start[c] = (int)run;
+    cursor[c] = (int)run;
+    run += n;
+  }
+  if (tid == 1023) {
+    start[ncells] = (int)part[1023];
+    *total = part[1023];
+  }
+}
+
+// one thread per triangle: its id into every cell of the same range the count pass walked
+__global__ __launch_bounds__(256) void mesh_fill(const MdGrid G, const float* __restrict__ rec, int T, int* __restrict__ cursor,
+                                                 int* __restrict__ list, long long list_elems) {
+  const int id = blockIdx.x * 256 + threadIdx.x;
+  if (id >= T) return;
+  const MdTri t = md_load(rec, id);
+  if (t.inv == 0.f) return;
+  int ix0, ix1, iy0, iy1;
+  md_cell_range(t, G, ix0, ix1, iy0, iy1);
+  for (int iy = iy0; iy <= iy1; ++iy)
+    for (int ix = ix0; ix <= ix1; ++ix) {
+      const int pos = atomicAdd(cursor + (size_t)iy * G.nx + ix, 1);
+      if (pos >= 0 && pos < list_elems) list[pos] = id;   // a list shorter than the counted total is never overrun
+    }
+}
+
+// row n of the pose table: cos, sin, 1000 t1, 1000 t2, g/2 (NaN when g is negative or not finite: the sample's images are NaN)
+__global__ __launch_bounds__(256) void mesh_pose_table(const float* __restrict__ poses, const float* __restrict__ widths, int N,
+                                                       float width_offset, float* __restrict__ table) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const float t1 = poses[3 * n], t2 = poses[3 * n + 1], th = poses[3 * n + 2];
+  const float g = widths[n] + width_offset;
+  float* row = table + (size_t)n * MD_POSE;
+  row[0] = (float)cos((double)th);
+  row[1] = (float)sin((double)th);
+  row[2] = 1000.f * t1;
+  row[3] = 1000.f * t2;
+  row[4] = (g >= 0.f && isfinite(g)) ? 0.5f * g : __builtin_nanf("");
+  row[5] = row[6] = row[7] = 0.f;
+}
+
+// sg * q of triangle t at the point (x, y), -inf where t does not cover it
+__device__ __forceinline__ float md_cover(const MdTri& t, float x, float y, float sg) {
+#pragma clang fp contract(off)
+  const float ylo = fminf(t.y0, fminf(t.y1, t.y2)), yhi = fmaxf(t.y0, fmaxf(t.y1, t.y2));
+  const float d0x = x - t.x0, d0y = y - t.y0, d1x = x - t.x1, d1y = y - t.y1;
+  const float e01x = t.x1 - t.x0, e01y = t.y1 - t.y0, e02x = t.x2 - t.x0, e02y = t.y2 - t.y0;
+  const float e12x = t.x2 - t.x1, e12y = t.y2 - t.y1;
+  const float f01 = fmaf(e01x, d0y, -(e01y * d0x));
+  const float f02 = fmaf(e02x, d0y, -(e02y * d0x));
+  const float f12 = fmaf(e12x, d1y, -(e12y * d1x));
+  const float l2 = f01 * t.inv, l1 = -(f02 * t.inv), l0 = f12 * t.inv;   // barycentric weights of V2, V1, V0
+  // the vertex bounding box first (what the binning used), then the three inclusive edges; a skipped triangle has inv = 0
+  const bool in = x >= t.x0 && x <= t.x2 && y >= ylo && y <= yhi && l0 >= 0.f && l1 >= 0.f && l2 >= 0.f && t.inv != 0.f;
+  float q = fmaf(l2, t.q2 - t.q0, fmaf(l1, t.q1 - t.q0, t.q0));
+  const float qlo = fminf(t.q0, fminf(t.q1, t.q2)), qhi = fmaxf(t.q0, fmaxf(t.q1, t.q2));
+  q = fminf(fmaxf(q, qlo), qhi);
+  return in ? sg * q : -INFINITY;
+}
+
+struct MdView {
+  float mpp, cx, cy;
+  int swap_axes, invert, lr_flip;
+  int H, W, tiles_x, tiles_y;
+  int T;
+  long long list_elems;
+};
+
+__global__ __launch_bounds__(256) void mesh_render(const MdGrid G, const MdView V, const float* __restrict__ rec,
+                                                   const int* __restrict__ start, const int* __restrict__ list,
+                                                   const float* __restrict__ table, float* __restrict__ out) {
+#pragma clang fp contract(off)
+  int b = blockIdx.x;
+  const int tx = b % V.tiles_x;
+  b /= V.tiles_x;
+  const int ty = b % V.tiles_y;
+  const int img = b / V.tiles_y;            // n * 2 + channel
+  const int n = img >> 1, ch = img & 1;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
+  const int c = tx * 16 + (wave & 1) * 8 + (lane & 7);
+  if (r >= V.H || c >= V.W) return;
+  const bool right = (ch == 1) != (V.lr_flip != 0);
+  const float* row = table + (size_t)n * MD_POSE;
+  const float cs = row[0], sn = row[1], t1 = row[2], t2 = row[3], hg = row[4];
+  // pixel -> transformed in-plane point: u along the unaligned axis (mirrored for the left finger), v along the aligned one
+  const float u = V.mpp * ((float)r - 0.5f * (float)V.H), v = V.mpp * ((float)c - 0.5f * (float)V.W);
+  const float uu = right ? u : -u;
+  const float pa = V.swap_axes ? v : uu, pb = V.swap_axes ? uu : v;   // ascending axis order
+  // back into the mesh frame, relative to the mesh's in-plane centre
+  float x, y;
+  if (V.invert) {      // the transformed cloud was R^T (P - t): P = R P' + t
+    x = fmaf(cs, pa, -(sn * pb)) + (t1 - V.cx);
+    y = fmaf(sn, pa, cs * pb) + (t2 - V.cy);
+  } else {             // the transformed cloud was R P + t: P = R^T (P' - t)
+    const float da = pa - t1, db = pb - t2;
+    x = fmaf(cs, da, sn * db) - V.cx;
+    y = fmaf(cs, db, -(sn * da)) - V.cy;
+  }
+  const float sg = right ? 1.f : -1.f;
+  float m = -INFINITY;                       // max of sg * q over the covering triangles
+  const float fx = (x - G.x0) * G.inv_cell, fy = (y - G.y0) * G.inv_cell;
+  // a point more than a cell outside the grid is outside every triangle's bounding box (a NaN fails the test as well)
+  if (fx >= -1.f && fx <= (float)G.nx + 1.f && fy >= -1.f && fy <= (float)G.ny + 1.f) {
+    const int cell = md_cell(y, G.y0, G.inv_cell, G.ny) * G.nx + md_cell(x, G.x0, G.inv_cell, G.nx);
+    // the list positions are clamped into the list and the ids into the mesh before they address anything
+    const int i0 = max(start[cell], 0), i1 = (int)min((long long)start[cell + 1], V.list_elems);
+    for (int i = i0; i < i1; i += MD_WALK) {
+      // MD_WALK entries per trip: their ids, then their records, are loaded together, so a trip costs two memory round trips
+      // instead of two per triangle.  Positions past the end repeat the last entry, which max does not notice.
+      int id[MD_WALK];
+#pragma unroll
+      for (int k = 0; k < MD_WALK; ++k) id[k] = list[min(i + k, i1 - 1)];
+      MdTri tri[MD_WALK];
+#pragma unroll
+      for (int k = 0; k < MD_WALK; ++k) tri[k] = md_load(rec, min(max(id[k], 0), V.T - 1));
+#pragma unroll
+      for (int k = 0; k < MD_WALK; ++k) m = fmaxf(m, md_cover(tri[k], x, y, sg));
+    }
+  }
+  // right: -max(0, Qmax - g/2); left: min(0, Qmin + g/2) = -max(0, -Qmin - g/2); nothing covering: m = -inf gives 0
+  float d = -fmaxf(0.f, m - hg);
+  d = d == 0.f ? 0.f : d;                    // no negative zero
+  if (!(hg == hg)) d = hg;                   // refused width: NaN
+  out[((size_t)img * V.H + r) * V.W + c] = d;
+}
+
+int md_check_grid(const gsd_mesh_grid* g, const char* what) {
+  GSD_REQUIRE(g != nullptr, GSD_ERR_BAD_ARG, "%s: null grid", what);
+  GSD_REQUIRE(g->nx >= 1 && g->ny >= 1 && g->nx <= MD_MAX_N && g->ny <= MD_MAX_N, GSD_ERR_BAD_ARG,
+              "%s: grid of %d x %d cells, 1..%d per axis", what, g->nx, g->ny, MD_MAX_N);
+  GSD_REQUIRE(isfinite(g->x0) && isfinite(g->y0) && isfinite(g->cx) && isfinite(g->cy) && isfinite(g->cell) && g->cell > 0.f &&
+                  isfinite(g->inv_cell) && g->inv_cell > 0.f,
+              GSD_ERR_BAD_ARG, "%s: grid origin, centre and cell size must be finite, the cell size positive", what);
+  GSD_REQUIRE(g->reserved[0] == 0 && g->reserved[1] == 0, GSD_ERR_BAD_ARG, "%s: the reserved words must be 0", what);
+  return 0;
+}
+MdGrid md_grid(const gsd_mesh_grid* g) {
+  MdGrid G;
+  G.x0 = g->x0, G.y0 = g->y0, G.inv_cell = g->inv_cell, G.nx = g->nx, G.ny = g->ny;
+  return G;
+}
+int64_t md_cells(const gsd_mesh_grid* g) { return (int64_t)g->nx * g->ny; }
+
+}   // namespace
+
+extern "C" int gsd_mesh_depth_plan(const double* bbox, double cell_mm, gsd_mesh_grid* grid) {
+  GSD_REQUIRE(bbox && grid, GSD_ERR_BAD_ARG, "gsd_mesh_depth_plan: null pointer");
+  const double x0 = bbox[0], y0 = bbox[1], x1 = bbox[2], y1 = bbox[3];
+  GSD_REQUIRE(isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1) && x1 >= x0 && y1 >= y0, GSD_ERR_BAD_ARG,
+              "gsd_mesh_depth_plan: bounding box (%g, %g)-(%g, %g) must be finite and ordered", x0, y0, x1, y1);
+  GSD_REQUIRE(isfinite(cell_mm) && cell_mm > 0.0, GSD_ERR_BAD_ARG, "gsd_mesh_depth_plan: cell size %g must be finite and positive",
+              cell_mm);
+  const double ext = fmax(fmax(x1 - x0, y1 - y0), 1e-30);
+  double cell = fmax(cell_mm, ext / (MD_MAX_N - 2));      // at most MD_MAX_N cells per axis
+  const double pad = 1e-3 * cell;                          // the fp32 vertices stay strictly inside the grid
+  const double cx = 0.5 * (x0 + x1), cy = 0.5 * (y0 + y1);
+  const int nx = (int)fmin((double)MD_MAX_N, fmax(1.0, ceil((x1 - x0 + 2 * pad) / cell)));
+  const int ny = (int)fmin((double)MD_MAX_N, fmax(1.0, ceil((y1 - y0 + 2 * pad) / cell)));
+  grid->cx = (float)cx, grid->cy = (float)cy;
+  grid->x0 = (float)(x0 - pad - cx), grid->y0 = (float)(y0 - pad - cy);    // records are relative to (cx, cy)
+  grid->cell = (float)cell, grid->inv_cell = (float)(1.0 / cell);
+  grid->nx = nx, grid->ny = ny;
+  grid->reserved[0] = grid->reserved[1] = 0;
+  return md_check_grid(grid, "gsd_mesh_depth_plan") ? GSD_ERR_BAD_ARG : GSD_OK;
+}
+
+extern "C" int64_t gsd_mesh_depth_workspace(const gsd_mesh_grid* grid) {
+  if (grid == nullptr || grid->nx < 1 || grid->ny < 1 || grid->nx > MD_MAX_N || grid->ny > MD_MAX_N) return 0;
+  return 2 + (md_cells(grid) + 1) + md_cells(grid);   // int64 total | starts (cells + 1) | cursors (cells)
+}
+
+extern "C" int gsd_mesh_depth_count(const gsd_mesh_grid* grid, const float* tri, int T, float* records, int32_t* cells,
+                                    int64_t cells_elems, void* stream) {
+  if (md_check_grid(grid, "gsd_mesh_depth_count")) return GSD_ERR_BAD_ARG;
+  GSD_REQUIRE(tri && records && cells, GSD_ERR_BAD_ARG, "gsd_mesh_depth_count: null pointer");
+  GSD_REQUIRE(T >= 1 && T <= MD_MAX_T, GSD_ERR_BAD_ARG, "gsd_mesh_depth_count: %d triangles, 1..%d", T, MD_MAX_T);
+  GSD_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)cells & 7) == 0, GSD_ERR_BAD_ARG,
+              "gsd_mesh_depth_count: records must be 16-byte aligned, cells 8-byte aligned");
+  GSD_REQUIRE(cells_elems >= gsd_mesh_depth_workspace(grid), GSD_ERR_WORKSPACE, "gsd_mesh_depth_count: cells of %lld words, need %lld",
+              (long long)cells_elems, (long long)gsd_mesh_depth_workspace(grid));
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t nc = md_cells(grid);
+  int* start = cells + 2;
+  if (hipError_t e = hipMemsetAsync(cells, 0, sizeof(int32_t) * (size_t)gsd_mesh_depth_workspace(grid), st); e != hipSuccess) {
+    gsd_set_error("gsd_mesh_depth_count: hipMemsetAsync: %s", hipGetErrorString(e));
+    return GSD_ERR_HIP;
+  }
+  hipLaunchKernelGGL(mesh_records_count, dim3((unsigned)ceil_div(T, 256)), dim3(256), 0, st, md_grid(grid), tri, T, records, start);
+  GSD_LAUNCH_CHECK("gsd_mesh_depth_count records");
+  hipLaunchKernelGGL(mesh_scan, dim3(1), dim3(1024), 0, st, (int)nc, start, start + nc + 1, reinterpret_cast<long long*>(cells));
+  GSD_LAUNCH_CHECK("gsd_mesh_depth_count scan");
+  return GSD_OK;
+}
+
+extern "C" int gsd_mesh_depth_fill(const gsd_mesh_grid* grid, const float* records, int T, int32_t* cells, int64_t cells_elems,
+                                   int32_t* list, int64_t list_elems, void* stream) {
+  if (md_check_grid(grid, "gsd_mesh_depth_fill")) return GSD_ERR_BAD_ARG;
+  GSD_REQUIRE(records && cells && list, GSD_ERR_BAD_ARG, "gsd_mesh_depth_fill: null pointer");
+  GSD_REQUIRE(T >= 1 && T <= MD_MAX_T, GSD_ERR_BAD_ARG, "gsd_mesh_depth_fill: %d triangles, 1..%d", T, MD_MAX_T);
+  GSD_REQUIRE(((uintptr_t)records & 15) == 0, GSD_ERR_BAD_ARG, "gsd_mesh_depth_fill: records must be 16-byte aligned");
+  GSD_REQUIRE(cells_elems >= gsd_mesh_depth_workspace(grid), GSD_ERR_WORKSPACE, "gsd_mesh_depth_fill: cells of %lld words, need %lld",
+              (long long)cells_elems, (long long)gsd_mesh_depth_workspace(grid));
+  GSD_REQUIRE(list_elems >= 1 && list_elems <= INT32_MAX, GSD_ERR_BAD_ARG, "gsd_mesh_depth_fill: list of %lld entries, 1..2^31-1",
+              (long long)list_elems);
+  const int64_t nc = md_cells(grid);
+  hipLaunchKernelGGL(mesh_fill, dim3((unsigned)ceil_div(T, 256)), dim3(256), 0, (hipStream_t)stream, md_grid(grid), records, T,
+                     cells + 2 + nc + 1, list, (long long)list_elems);
+  GSD_LAUNCH_CHECK("gsd_mesh_depth_fill");
+  return GSD_OK;
+}
+
+extern "C" int64_t gsd_mesh_depth_render_workspace(int N) { return N > 0 ? (int64_t)N * MD_POSE : 0; }
+
+extern "C" int gsd_mesh_depth_render(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
+                                     const int32_t* cells, const int32_t* list, int64_t list_elems, const float* poses,
+                                     const float* widths, int N, int H, int W, float* out, float* workspace,
+                                     int64_t workspace_elems, void* stream) {
+  if (md_check_grid(grid, "gsd_mesh_depth_render")) return GSD_ERR_BAD_ARG;
+  GSD_REQUIRE(view && records && cells && list && poses && widths && out && workspace, GSD_ERR_BAD_ARG,
+              "gsd_mesh_depth_render: null pointer");
+  GSD_REQUIRE(T >= 1 && T <= MD_MAX_T, GSD_ERR_BAD_ARG, "gsd_mesh_depth_render: %d triangles, 1..%d", T, MD_MAX_T);
+  GSD_REQUIRE(N >= 1 && H >= 1 && W >= 1, GSD_ERR_BAD_ARG, "gsd_mesh_depth_render: bad dims N=%d H=%d W=%d", N, H, W);
+  GSD_REQUIRE(list_elems >= 1 && list_elems <= INT32_MAX, GSD_ERR_BAD_ARG, "gsd_mesh_depth_render: list of %lld entries, 1..2^31-1",
+              (long long)list_elems);
+  GSD_REQUIRE(isfinite(view->mpp) && view->mpp > 0.f && isfinite(view->width_offset), GSD_ERR_BAD_ARG,
+              "gsd_mesh_depth_render: mm per pixel %g must be finite and positive, the width offset %g finite", (double)view->mpp,
+              (double)view->width_offset);
+  GSD_REQUIRE(view->reserved == 0, GSD_ERR_BAD_ARG, "gsd_mesh_depth_render: the reserved word must be 0");
+  GSD_REQUIRE(((uintptr_t)records & 15) == 0, GSD_ERR_BAD_ARG, "gsd_mesh_depth_render: records must be 16-byte aligned");
+  GSD_REQUIRE(workspace_elems >= (int64_t)N * MD_POSE, GSD_ERR_WORKSPACE, "gsd_mesh_depth_render: workspace of %lld floats, need %lld",
+              (long long)workspace_elems, (long long)N * MD_POSE);
+  const int tiles_x = ceil_div(W, 16), tiles_y = ceil_div(H, 16);
+  const int64_t blocks = (int64_t)tiles_x * tiles_y * 2 * N;
+  GSD_REQUIRE(blocks <= INT32_MAX, GSD_ERR_UNSUPPORTED, "gsd_mesh_depth_render: %lld blocks (N=%d of %d x %d), at most 2^31-1 per launch",
+              (long long)blocks, N, H, W);
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, poses, widths, N, view->width_offset,
+                     workspace);
+  GSD_LAUNCH_CHECK("gsd_mesh_depth_render pose table");
+  MdView V;
+  V.mpp = view->mpp, V.cx = grid->cx, V.cy = grid->cy;
+  V.swap_axes = view->swap_axes != 0, V.invert = view->invert_affine != 0, V.lr_flip = view->lr_flip != 0;
+  V.H = H, V.W = W, V.tiles_x = tiles_x, V.tiles_y = tiles_y, V.T = T, V.list_elems = list_elems;
+  hipLaunchKernelGGL(mesh_render, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), V, records, cells + 2, list,
+                     (const float*)workspace, out);
+  GSD_LAUNCH_CHECK("gsd_mesh_depth_render");
+  return GSD_OK;
+}

@@ -1,0 +1,384 @@
+"""Ground-truth depth images from an object's mesh, the recorded in-hand poses and the grasp widths, on the device: the label
+maker of the reference (gelslim_depth/mesh_utils/depth_from_mesh.py, driven by scripts/data_scripts/depth_generation.py),
+restated exactly instead of sampled.
+
+The reference draws 1e5 random surface points with open3d and runs two scipy Delaunay interpolations per sample.  Here a pixel's
+depth is DEFINED by the mesh: the outermost surface under the pixel, `right = -max(0, Qmax - g/2)`,
+`left = min(0, Qmin + g/2)`, 0 where no triangle covers it.  libgsd (gsd_mesh_depth_*, include/gsd.h) builds a cell grid over
+the mesh once (`MeshGrid`) and renders any number of poses with one launch per batch (`render_depth`); neither open3d nor scipy
+is needed, the result does not depend on a random cloud, and it never interpolates across surface layers.
+
+`DepthImageGenerator` keeps the reference's constructor and `generate_depth_images_v1`, so a data-generation script switches by
+changing its import."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import os
+import struct
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from ._lib import check, lib
+
+
+class MeshDepthError(L.GsdError, ValueError):
+    """What this module refuses: the package's error, and a ValueError where the definition names one (a negative width)."""
+
+
+# ---- STL ------------------------------------------------------------------------------------------------------------
+def _read_stl_ascii(text: str, path: str) -> np.ndarray:
+    verts: List[Tuple[float, float, float]] = []
+    facets = 0
+    for line in text.splitlines():
+        tok = line.split()
+        if not tok:
+            continue
+        if tok[0] == "vertex":
+            if len(tok) != 4:
+                raise MeshDepthError(f"read_stl: {path}: malformed vertex line {line.strip()!r}")
+            try:
+                verts.append((float(tok[1]), float(tok[2]), float(tok[3])))
+            except ValueError:
+                raise MeshDepthError(f"read_stl: {path}: malformed vertex line {line.strip()!r}") from None
+        elif tok[0] == "endfacet":
+            facets += 1
+            if len(verts) != 3 * facets:
+                raise MeshDepthError(f"read_stl: {path}: facet {facets} has {len(verts) - 3 * (facets - 1)} vertices, not 3")
+    if len(verts) != 3 * facets or "endsolid" not in text:
+        raise MeshDepthError(f"read_stl: {path}: truncated ASCII STL ({len(verts)} vertices in {facets} closed facets, "
+                             f"{'no ' if 'endsolid' not in text else ''}endsolid)")
+    return np.asarray(verts, dtype=np.float32).reshape(-1, 3, 3)
+
+
+def read_stl(path: str) -> np.ndarray:
+    """The triangles of a binary or an ASCII STL file as float32 (T, 3, 3) (triangle, vertex, xyz); normals and attribute
+    words are ignored.  numpy only.  A binary file is 80 header bytes, a uint32 count T and T records of 50 bytes: a file
+    shorter than 84 bytes, or whose size is not 84 + 50 T, is refused, as is an ASCII file without its `endsolid`."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    ascii_form = raw[:512].lstrip().startswith(b"solid")
+    if ascii_form and len(raw) >= 84 and len(raw) == 84 + 50 * struct.unpack_from("<I", raw, 80)[0]:
+        ascii_form = False      # a binary file whose header happens to start with "solid"
+    if ascii_form:
+        try:
+            return _read_stl_ascii(raw.decode("ascii"), path)
+        except UnicodeDecodeError:
+            pass            # binary after all: the size check below says what is wrong with it
+    if len(raw) < 84:
+        raise MeshDepthError(f"read_stl: {path}: {len(raw)} bytes, a binary STL has at least 84 (truncated file)")
+    (count,) = struct.unpack_from("<I", raw, 80)
+    if len(raw) != 84 + 50 * count:
+        raise MeshDepthError(f"read_stl: {path}: header announces {count} triangles = {84 + 50 * count} bytes, the file has "
+                             f"{len(raw)} (truncated, or not an STL file)")
+    rec = np.frombuffer(raw, dtype=np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("a", "<u2")]), count=count, offset=84)
+    return np.ascontiguousarray(rec["v"], dtype=np.float32)
+
+
+# ---- conventions (depth_from_mesh.py:85-146) ------------------------------------------------------------------------
+def plane_convention(gelslim_plane: str) -> Tuple[int, int, int, int]:
+    """(perp_ind, aligned_index, unaligned_index, multiplier) of a `gelslim_plane` string such as '+y+z' (the plane of the
+    RIGHT finger's image): the first letter names the unaligned axis (image rows), the second the aligned one (columns), the
+    remaining axis is perpendicular, and the right finger looks along multiplier * that axis with
+    multiplier = sign1 * sign2 * (+1 if first x second = +perp else -1) -- the reference's twelve-row table in one rule."""
+    if not isinstance(gelslim_plane, str):
+        raise ValueError("Invalid gelslim_plane")
+    axes = [c for c in gelslim_plane if c.isalpha()]
+    signs = [c for c in gelslim_plane if c in "+-"]
+    pair = next((p for p in ("xy", "xz", "yz") if p[0] in axes and p[1] in axes), None)
+    if pair is None or len(signs) < 2 or not axes or axes[0] not in pair:
+        raise ValueError("Invalid gelslim_plane")
+    first = "xyz".index(axes[0])
+    second = "xyz".index(pair[1] if axes[0] == pair[0] else pair[0])
+    perp = 3 - first - second
+    cyclic = 1 if (second - first) % 3 == 1 else -1          # first x second = cyclic * perp
+    same = 1 if signs[0] == signs[1] else -1
+    return perp, second, first, same * cyclic
+
+
+def dataset_key(pt_file: str) -> str:
+    """The object a dataset file belongs to (depth_from_mesh.py:51-54, 62-65): `<...>_<object>_{train,val,test}.pt` names it in
+    the field before the last underscore, any other name in what precedes the first dot.  The mesh is `<key>.stl`."""
+    if "_val" in pt_file or "_test" in pt_file or "_train" in pt_file:
+        return pt_file.split("_")[-2]
+    return pt_file.split(".")[0]
+
+
+def select_dataset_files(names: Sequence[str], object_list: Optional[Sequence[str]]) -> List[str]:
+    """The `.pt` files among `names` that generate_depth_images_v1 works on (depth_from_mesh.py:26-33): all of them without
+    an object list; with one, the name rule is chosen by the FIRST file, as the reference does."""
+    files = [f for f in names if f[-3:] == ".pt"]
+    if object_list is not None and files:
+        first = files[0]
+        if "_val" in first or "_test" in first or "_train" in first:
+            files = [f for f in files if f.split("_")[-2] in object_list]
+        else:
+            files = [f for f in files if f.split(".")[0] in object_list]
+    return files
+
+
+def parse_grasp_widths(lines: Sequence[str]) -> Dict[str, Optional[float]]:
+    """`object: inter_gelslim_distance` lines (depth_from_mesh.py:38-46): a float, or ` None` for "use the sample's own
+    grasp_widths entry"."""
+    out: Dict[str, Optional[float]] = {}
+    for line in lines:
+        part = line.split(":")
+        out[part[0]] = None if part[1] in (" None\n", " None") else float(part[1])
+    return out
+
+
+# ---- the mesh on the device -----------------------------------------------------------------------------------------
+def _need_cuda(device) -> torch.device:
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise MeshDepthError(f"mesh_depth: the rasteriser runs on the GPU, got device {dev}")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def default_cell_mm(a: np.ndarray, b: np.ndarray, target: float = 8.0) -> float:
+    """Cell size model.  A triangle whose in-plane bounding box is w x h lands in about (w/c + 1)(h/c + 1) cells of side c,
+    the grid has about A / c^2 cells over the mesh's bounding box of area A, so with s^2 the triangles' mean bounding-box
+    area the mean list length is T (c + s)^2 / A.  Solving for `target` = 8 entries (two trips of the render's four-entry walk;
+    the measured optimum on the 81,920-triangle sphere) gives c = sqrt(target A / T) - s; it is kept above
+    s / 2 (finer cells mostly multiply the entries of the triangles; 8.9 entries per cell on that sphere) and above 1/512 of the
+    extent."""
+    ext_a, ext_b = float(a.max() - a.min()), float(b.max() - b.min())
+    ext = max(ext_a, ext_b, 1e-30)
+    area = max(ext_a, 1e-3 * ext) * max(ext_b, 1e-3 * ext)
+    w = a.max(axis=1) - a.min(axis=1)
+    h = b.max(axis=1) - b.min(axis=1)
+    s = math.sqrt(max(float(np.mean(w * h)), 0.0))
+    return max(math.sqrt(target * area / a.shape[0]) - s, 0.5 * s, ext / 512.0)
+
+
+class MeshGrid:
+    """A mesh prepared for `render_depth`: the per-triangle records and the per-cell triangle lists on the device, built once.
+
+    triangles: (T, 3, 3) array or tensor (`read_stl`); pc_scale: factor to millimetres (the reference's `pc_scale`);
+    gelslim_plane: `plane_convention`; cell_mm: side of a grid cell, default `default_cell_mm`; the environment variable
+    GSD_MESH_CELL_MM overrides both.  The image does not depend on the cell size, only the time does.
+    Building reads one int64 back from the device (the number of (cell, triangle) pairs, to allocate the list)."""
+
+    def __init__(self, triangles, pc_scale: float = 1.0, gelslim_plane: str = "+y+z", device=None, cell_mm: Optional[float] = None) -> None:
+        self.perp_ind, self.aligned_index, self.unaligned_index, self.multiplier = plane_convention(gelslim_plane)
+        self.gelslim_plane = gelslim_plane
+        self.device = _need_cuda(device)
+        if isinstance(triangles, torch.Tensor):
+            triangles = triangles.detach().cpu().numpy()
+        v = np.asarray(triangles, dtype=np.float64)
+        if v.ndim != 3 or v.shape[1:] != (3, 3):
+            raise MeshDepthError(f"MeshGrid: triangles must be (T, 3, 3), got {v.shape}")
+        if v.shape[0] == 0:
+            raise MeshDepthError("MeshGrid: the mesh has no triangles")
+        if v.shape[0] > 1 << 24:
+            raise MeshDepthError(f"MeshGrid: {v.shape[0]} triangles, at most 2^24")
+        scale = float(pc_scale)
+        if not math.isfinite(scale) or scale == 0.0:
+            raise MeshDepthError(f"MeshGrid: pc_scale must be finite and not zero, got {pc_scale!r}")
+        v = v * scale
+        if not np.isfinite(v).all():
+            raise MeshDepthError("MeshGrid: the mesh has a non-finite vertex")
+        perp = v[:, :, self.perp_ind]
+        self.mid = 0.5 * (float(perp.max()) + float(perp.min()))
+        q = self.multiplier * (perp - self.mid)
+        lo, hi = sorted((self.aligned_index, self.unaligned_index))
+        a, b = v[:, :, lo], v[:, :, hi]
+        self.swap_axes = 1 if self.aligned_index < self.unaligned_index else 0
+        env = os.environ.get("GSD_MESH_CELL_MM")
+        if env is not None:
+            cell = float(env)
+        elif cell_mm is not None:
+            cell = float(cell_mm)
+        else:
+            cell = default_cell_mm(a, b)
+        if not (math.isfinite(cell) and cell > 0.0):
+            raise MeshDepthError(f"MeshGrid: cell_mm must be finite and positive, got {cell!r}")
+        self.grid = L.gsd_mesh_grid()
+        bbox = (C.c_double * 4)(float(a.min()), float(b.min()), float(a.max()), float(b.max()))
+        check(lib.gsd_mesh_depth_plan(bbox, cell, C.byref(self.grid)), "mesh_depth_plan")
+        self.cell_mm = float(self.grid.cell)
+        self.triangles = int(v.shape[0])
+        self.q_range = (float(q.min()), float(q.max()))
+        # prepared vertices (a, b, q), relative to the fp32 centre the kernel adds back, rounded to fp32 once
+        tri = np.stack((a - float(self.grid.cx), b - float(self.grid.cy), q), axis=2).astype(np.float32)
+        # the largest |coordinate| of the mesh in the frame the pixel-to-mesh map works in (for error budgets)
+        self.coord_max = float(max(np.abs(a).max(), np.abs(b).max()))
+        with torch.cuda.device(self.device):
+            self._tri = torch.from_numpy(tri.reshape(-1, 9)).to(self.device)
+            self.records = torch.empty((self.triangles, L.GSD_MESH_RECORD_FLOATS), device=self.device, dtype=torch.float32)
+            words = int(lib.gsd_mesh_depth_workspace(C.byref(self.grid)))
+            self.cells = torch.empty((words,), device=self.device, dtype=torch.int32)
+            check(lib.gsd_mesh_depth_count(C.byref(self.grid), self._tri.data_ptr(), self.triangles, self.records.data_ptr(),
+                                           self.cells.data_ptr(), words, L.stream_ptr()), "mesh_depth_count")
+            self.pairs = int(self.cells[:2].view(torch.int64).item())         # the one host read of a mesh
+            if self.pairs >= 1 << 31:
+                raise MeshDepthError(f"MeshGrid: {self.pairs} (cell, triangle) pairs, at most 2^31 - 1: use larger cells")
+            self.list = torch.empty((max(self.pairs, 1),), device=self.device, dtype=torch.int32)
+            if self.pairs == 0:
+                self.list.zero_()         # every triangle is degenerate in this plane: all lists are empty
+            else:
+                check(lib.gsd_mesh_depth_fill(C.byref(self.grid), self.records.data_ptr(), self.triangles, self.cells.data_ptr(),
+                                              words, self.list.data_ptr(), self.list.numel(), L.stream_ptr()), "mesh_depth_fill")
+            del self._tri
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        """(ny, nx) cells."""
+        return int(self.grid.ny), int(self.grid.nx)
+
+    def __repr__(self) -> str:
+        return (f"MeshGrid({self.triangles} triangles, plane {self.gelslim_plane!r}, {self.grid.nx} x {self.grid.ny} cells of "
+                f"{self.cell_mm:.4g} mm, {self.pairs} pairs)")
+
+
+def render_depth(grid: MeshGrid, poses: torch.Tensor, grasp_widths: torch.Tensor, image_size: Sequence[int] = (320, 427),
+                 image_height_mm: float = 12.0, grasp_width_offset: float = 0.0, LR_flip: bool = False,
+                 invert_affine: bool = False, out: Optional[torch.Tensor] = None, validate: bool = True) -> torch.Tensor:
+    """Depth images (N, 2, H, W) fp32 in mm, channels (left, right), or (right, left) with `LR_flip`, of `grid`'s mesh under
+    the N poses `poses` (N, 3) = (t1 [m], t2 [m], theta [rad]) with the inter-finger distances `grasp_widths` (N,) [mm]; both
+    are float32 tensors on the grid's device.  One libgsd call, on torch's current stream; `out` is written in place.
+
+    g = grasp_widths + grasp_width_offset must not be negative.  With `validate` (the default) the smallest g is read back
+    from the device and a negative or non-finite one raises MeshDepthError (a ValueError) before anything of libgsd runs: this
+    is the call's only synchronisation.  `validate=False` promises that the caller has checked (generate_depth_images_v1
+    checks the whole file on the host): then nothing is synchronised, and a sample with a bad g comes out as NaN."""
+    if not isinstance(grid, MeshGrid):
+        raise MeshDepthError(f"render_depth: grid must be a MeshGrid, got {type(grid).__name__}")
+    for name, t, shape in (("poses", poses, "(N, 3)"), ("grasp_widths", grasp_widths, "(N,)")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise MeshDepthError(f"render_depth: {name} must be a contiguous float32 {shape} tensor on the GPU, got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')}")
+        if t.device != grid.device:
+            raise MeshDepthError(f"render_depth: {name} is on {t.device}, the mesh on {grid.device}")
+    if poses.dim() != 2 or poses.shape[1] != 3 or poses.shape[0] < 1:
+        raise MeshDepthError(f"render_depth: poses must be (N, 3) with N >= 1, got {tuple(poses.shape)}")
+    n = int(poses.shape[0])
+    if tuple(grasp_widths.shape) != (n,):
+        raise MeshDepthError(f"render_depth: {n} poses but grasp_widths of shape {tuple(grasp_widths.shape)}")
+    h, w = (int(d) for d in image_size)
+    mpp = float(image_height_mm) / h if h > 0 else float("nan")
+    if h < 1 or w < 1 or not (math.isfinite(mpp) and mpp > 0.0):
+        raise MeshDepthError(f"render_depth: image_size {tuple(image_size)} and image_height_mm {image_height_mm!r} must be positive")
+    offset = float(grasp_width_offset)
+    if not math.isfinite(offset):
+        raise MeshDepthError(f"render_depth: grasp_width_offset must be finite, got {grasp_width_offset!r}")
+    if out is None:
+        out = torch.empty((n, 2, h, w), device=grid.device, dtype=torch.float32)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != grid.device or not out.is_contiguous()
+          or tuple(out.shape) != (n, 2, h, w)):
+        raise MeshDepthError(f"render_depth: out must be a contiguous float32 ({n}, 2, {h}, {w}) tensor on {grid.device}")
+    if validate:
+        g_min = float((grasp_widths + offset).min())          # NaN propagates through min
+        if not (g_min >= 0.0) or not bool(torch.isfinite(grasp_widths).all()):
+            raise MeshDepthError(f"render_depth: grasp width + offset must be finite and >= 0, the smallest is {g_min!r}")
+    view = L.gsd_mesh_view()
+    view.mpp, view.width_offset = mpp, offset
+    view.swap_axes, view.invert_affine, view.lr_flip, view.reserved = grid.swap_axes, int(bool(invert_affine)), int(bool(LR_flip)), 0
+    with torch.cuda.device(grid.device):
+        ws = torch.empty((int(lib.gsd_mesh_depth_render_workspace(n)),), device=grid.device, dtype=torch.float32)
+        check(lib.gsd_mesh_depth_render(C.byref(grid.grid), C.byref(view), grid.records.data_ptr(), grid.triangles,
+                                        grid.cells.data_ptr(), grid.list.data_ptr(), grid.list.numel(), poses.data_ptr(),
+                                        grasp_widths.data_ptr(), n, h, w, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        L.stream_ptr()), "mesh_depth_render")
+    return out
+
+
+# ---- the reference's class ------------------------------------------------------------------------------------------
+class DepthImageGenerator:
+    """Drop-in for gelslim_depth.mesh_utils.depth_from_mesh.DepthImageGenerator: the same constructor arguments and defaults,
+    except that `device` defaults to the GPU (the rasteriser has no CPU form) and that `pc_sampling` is accepted and unused --
+    nothing is sampled, the depth comes from the triangles themselves.  `batch` samples are rendered per launch."""
+
+    def __init__(self, mesh_dir, object_list, pc_scale, dataset_dir, grasp_widths_file, gelslim_plane="+y+z", LR_flip=False,
+                 image_size=(320, 427), image_height_mm=12, grasp_width_offset=0.0, pc_sampling=1e5, device="cuda",
+                 batch: int = 256) -> None:
+        self.image_height_mm = image_height_mm
+        self.image_size = tuple(int(d) for d in image_size)
+        self.mm_per_pixel = image_height_mm / image_size[0]
+        self.mesh_dir = mesh_dir
+        self.grasp_widths_file = grasp_widths_file
+        self.gelslim_plane = gelslim_plane
+        self.LR_flip = LR_flip
+        self.pc_scale = pc_scale
+        self.dataset_dir = dataset_dir
+        self.object_list = object_list
+        self.plane_axes = [c for c in self.gelslim_plane if c.isalpha()]
+        self.pc_sampling = pc_sampling          # unused
+        self.device = _need_cuda(device)
+        self.grasp_width_offset = grasp_width_offset
+        self.batch = int(batch)
+        plane_convention(gelslim_plane)         # an invalid plane raises here, not at the first sample
+        self._grids: Dict[str, MeshGrid] = {}
+
+    def mesh_grid(self, mesh) -> MeshGrid:
+        """`mesh` as a MeshGrid: one is passed through, a path is read with `read_stl` (and kept), triangles are prepared with
+        this generator's pc_scale and plane."""
+        if isinstance(mesh, MeshGrid):
+            return mesh
+        if isinstance(mesh, (str, os.PathLike)):
+            key = os.fspath(mesh)
+            if key not in self._grids:
+                self._grids[key] = MeshGrid(read_stl(key), self.pc_scale, self.gelslim_plane, self.device)
+            return self._grids[key]
+        return MeshGrid(mesh, self.pc_scale, self.gelslim_plane, self.device)
+
+    def generate_depth_image(self, mesh, translation1, translation2, angle, inter_gelslim_distance, invert_affine=False):
+        """(right, left) depth images (H, W) on the device for one pose.  `mesh` is a MeshGrid, an STL path or (T, 3, 3)
+        triangles in mesh units -- where the reference takes its scaled point cloud.  As there, `inter_gelslim_distance`
+        is used as given (generate_depth_images_v1 adds grasp_width_offset before it calls)."""
+        grid = self.mesh_grid(mesh)
+        g = float(inter_gelslim_distance)
+        if not (g >= 0.0 and math.isfinite(g)):
+            raise MeshDepthError(f"generate_depth_image: inter_gelslim_distance must be finite and >= 0, got {g!r}")
+        pose = torch.tensor([[float(translation1), float(translation2), float(angle)]], dtype=torch.float32, device=grid.device)
+        width = torch.tensor([g], dtype=torch.float32, device=grid.device)
+        img = render_depth(grid, pose, width, self.image_size, self.image_height_mm, 0.0, False, invert_affine, validate=False)
+        return img[0, 1], img[0, 0]
+
+    def generate_depth_images_v1(self, prompt: bool = True) -> None:
+        """depth_from_mesh.py:25-78: for every selected `.pt` file of dataset_dir, render the `depth_image` of all its samples
+        from `<object>.stl`, its `in_hand_pose` rows and the grasp widths (the file's number, or the samples' own
+        `grasp_widths` where the file says None), and write the file back -- through train.atomic_save, so a kill leaves the
+        old file.  The tensors are loaded to and saved from the host, as DeviceDataset reads them.  `prompt=False` skips the
+        reference's input()."""
+        from .train import atomic_save
+        dataset_list = select_dataset_files(os.listdir(self.dataset_dir), self.object_list)
+        if prompt:
+            user_in = input("Generating depth images for " + str(dataset_list) + ", Press enter to continue or q to quit.")
+            if user_in == "q":
+                return
+        with open(self.grasp_widths_file, "r") as f:
+            grasp_widths = parse_grasp_widths(f.readlines())
+        h, w = self.image_size
+        for pt_file in dataset_list:
+            path = os.path.join(self.dataset_dir, pt_file)
+            dataset_pt = torch.load(path, map_location="cpu")
+            n = int(dataset_pt["tactile_image"].shape[0])
+            key = dataset_key(pt_file)
+            grid = self.mesh_grid(os.path.join(self.mesh_dir, key + ".stl"))
+            poses = dataset_pt["in_hand_pose"][:n, :3].to(torch.float32).contiguous()
+            distance = grasp_widths[key]
+            if distance is None:
+                widths = dataset_pt["grasp_widths"].reshape(-1)[:n].to(torch.float32).contiguous()
+            else:
+                widths = torch.full((n,), float(distance), dtype=torch.float32)
+            if poses.shape[0] != n or widths.shape[0] != n:
+                raise MeshDepthError(f"{pt_file}: {n} samples but {poses.shape[0]} poses and {widths.shape[0]} grasp widths")
+            g = widths + float(self.grasp_width_offset)
+            if n and not bool((torch.isfinite(g) & (g >= 0)).all()):          # on the host: the batches below never synchronise
+                bad = int((~(torch.isfinite(g) & (g >= 0))).nonzero()[0])
+                raise MeshDepthError(f"{pt_file}: sample {bad}: grasp width + offset = {float(g[bad])!r} must be finite and >= 0")
+            depth = torch.zeros((n, 2, h, w), dtype=torch.float32)
+            poses_d, widths_d = poses.to(self.device), widths.to(self.device)
+            for i in range(0, n, max(self.batch, 1)):
+                j = min(i + max(self.batch, 1), n)
+                img = render_depth(grid, poses_d[i:j], widths_d[i:j], self.image_size, self.image_height_mm,
+                                   self.grasp_width_offset, self.LR_flip, False, validate=False)
+                depth[i:j] = img.cpu()
+            dataset_pt["depth_image"] = depth
+            atomic_save(dataset_pt, path)

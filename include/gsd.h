@@ -467,6 +467,54 @@ int64_t gsd_depth_metrics_workspace(int N, int K, int H, int W);            /* d
 int gsd_depth_metrics(const struct gsd_depth_metrics* spec, const float* o, const float* t, int N, int K, int H, int W,
                       double* table /* N x GSD_DM_COLS */, double* workspace, int64_t workspace_elems, void* stream);
 
+/* ---- ground-truth depth images from a mesh (gelslim_depth/mesh_utils/depth_from_mesh.py, restated exactly) ---- */
+/* The label maker: for every pixel of either finger, the outermost surface of a rigid triangle mesh under an in-hand pose
+ * (DESIGN.md section 16 has the definition; gsd_mesh_depth.hip the kernels).  Everything that depends on the mesh alone is
+ * built once, by plan -> count -> (one host read of the pair total, to allocate the list) -> fill; render then serves any
+ * number of poses and never synchronises.  The library allocates nothing.
+ *
+ * tri: T x 9 floats on the device, per triangle three prepared vertices (a, b, q): a, b the two in-plane coordinates in
+ *   ascending axis order, in mm, RELATIVE TO (grid.cx, grid.cy); q the signed perpendicular coordinate in mm.
+ * records: T x GSD_MESH_RECORD_FLOATS floats, 16-byte aligned (written by count, read by fill and render).
+ * cells: gsd_mesh_depth_workspace(grid) int32 words, 8-byte aligned: words 0..1 the pair total as one int64, then
+ *   nx*ny + 1 list starts (exclusive scan of the per-cell counts), then nx*ny fill cursors.
+ * list: triangle ids, grouped by cell; `list_elems` must be at least the pair total (fill never writes past it; a shorter
+ *   list loses triangles).  The order inside a cell is not deterministic; the rendered image is (max and min).
+ * poses: N x 3 floats (t1 [m], t2 [m], theta [rad]); widths: N floats, g = widths[n] + view.width_offset in mm.  A sample whose
+ *   g is negative or not finite gets NaN images (the caller, who may hold the widths on the host, refuses it beforehand).
+ * out: N x 2 x H x W floats in mm, channel 0 the left finger and 1 the right, swapped when view.lr_flip.
+ * workspace: gsd_mesh_depth_render_workspace(N) floats (the pose table).
+ * GSD_ERR_BAD_ARG (null pointer, a dimension <= 0, T above 2^24, a grid outside 1..2048 cells per axis or with a non-finite
+ * field, a non-zero reserved word, misaligned records / cells) and GSD_ERR_WORKSPACE are returned before any launch. */
+typedef struct gsd_mesh_grid {
+  float x0, y0;        /* grid origin in the centred in-plane frame, mm                                   */
+  float cell, inv_cell;/* side of a square cell in mm, and its reciprocal                                 */
+  float cx, cy;        /* the in-plane point the prepared vertices are relative to (the bounding box's centre) */
+  int32_t nx, ny;      /* cells per axis, 1..2048                                                         */
+  int32_t reserved[2]; /* 0 */
+} gsd_mesh_grid;
+typedef struct gsd_mesh_view {
+  float mpp;             /* mm per pixel: image_height_mm / H                                              */
+  float width_offset;    /* added to every grasp width, mm                                                 */
+  int32_t swap_axes;     /* 0: the unaligned axis is the lower-numbered in-plane axis, 1: the aligned one is */
+  int32_t invert_affine; /* the poses are those of the grasp frame in the mesh frame                       */
+  int32_t lr_flip;       /* channel order (right, left)                                                    */
+  int32_t reserved;      /* 0 */
+} gsd_mesh_view;
+#define GSD_MESH_RECORD_FLOATS 12
+/* Host only: the grid over the in-plane bounding box bbox = {amin, bmin, amax, bmax} (mm, not centred) with cells of
+ * cell_mm, raised where an axis would need more than 2048 cells. */
+int gsd_mesh_depth_plan(const double* bbox, double cell_mm, gsd_mesh_grid* grid);
+int64_t gsd_mesh_depth_workspace(const gsd_mesh_grid* grid);                 /* int32 words of `cells` */
+int gsd_mesh_depth_count(const gsd_mesh_grid* grid, const float* tri, int T, float* records, int32_t* cells, int64_t cells_elems,
+                         void* stream);
+int gsd_mesh_depth_fill(const gsd_mesh_grid* grid, const float* records, int T, int32_t* cells, int64_t cells_elems, int32_t* list,
+                        int64_t list_elems, void* stream);
+int64_t gsd_mesh_depth_render_workspace(int N);                              /* floats */
+int gsd_mesh_depth_render(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T, const int32_t* cells,
+                          const int32_t* list, int64_t list_elems, const float* poses, const float* widths, int N, int H, int W,
+                          float* out, float* workspace, int64_t workspace_elems, void* stream);
+
 /* ---- optimiser (train_unet.py:306,375-376) -------------------------------------------------- */
 /* Fused torch.optim.Adam(lr, betas, eps, weight_decay: coupled L2) + torch_ema update over a flat
  * parameter arena. step is the 1-based Adam step; ema may be NULL; ema_decay already resolved

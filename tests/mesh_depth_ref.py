@@ -1,0 +1,310 @@
+"""Test helpers for gelslim_depth_amd.mesh_depth (numpy, fp64; nothing here is product code):
+
+  * procedural meshes (float32-representable vertices, shared vertices bit-identical) and an STL writer,
+  * `raster_ref`: DESIGN.md section 16 by brute force, as an interval [lo, hi] per pixel that absorbs sixteen fp32 ulps of
+    position,
+  * `reference_from_points`: our restatement of gelslim_depth/mesh_utils/depth_from_mesh.py:80-248 on a given point cloud
+    (scipy's griddata, plotting left out), and uniform surface sampling with numpy's PCG64 in place of open3d's."""
+import math
+
+import numpy as np
+
+# the reference's table (depth_from_mesh.py:85-146), restated row by row:
+# plane letters in order, signs equal? -> (perp_ind, aligned_index, unaligned_index, right out-of-plane direction)
+PLANE_TABLE = {
+    ("xy", True): (2, 1, 0, "+z"), ("xy", False): (2, 1, 0, "-z"), ("yx", True): (2, 0, 1, "-z"), ("yx", False): (2, 0, 1, "+z"),
+    ("xz", True): (1, 2, 0, "-y"), ("xz", False): (1, 2, 0, "+y"), ("zx", True): (1, 0, 2, "+y"), ("zx", False): (1, 0, 2, "-y"),
+    ("yz", True): (0, 2, 1, "+x"), ("yz", False): (0, 2, 1, "-x"), ("zy", True): (0, 1, 2, "-x"), ("zy", False): (0, 1, 2, "+x"),
+}
+# twelve plane strings, one per row of the table
+PLANES = [f"+{k[0]}{'+' if same else '-'}{k[1]}" for (k, same) in PLANE_TABLE]
+
+
+def plane_table(gelslim_plane):
+    """(perp_ind, aligned_index, unaligned_index, multiplier) from the table above."""
+    axes = "".join(c for c in gelslim_plane if c.isalpha())
+    signs = [c for c in gelslim_plane if c in "+-"]
+    perp, aligned, unaligned, direction = PLANE_TABLE[(axes, signs[0] == signs[1])]
+    return perp, aligned, unaligned, (1 if "+" in direction else -1)
+
+
+# ---- meshes ---------------------------------------------------------------------------------------------------------
+def _f32(tri):
+    return np.ascontiguousarray(np.asarray(tri, dtype=np.float32))
+
+
+def box(size=(6.0, 4.0, 5.0), centre=(0.0, 0.0, 0.0)):
+    """12 triangles."""
+    s, c = np.asarray(size, float) / 2, np.asarray(centre, float)
+    v = np.array([[x, y, z] for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)], float) * s + c
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    tri = [[v[a], v[b], v[c_]] for q in quads for (a, b, c_) in ((q[0], q[1], q[2]), (q[0], q[2], q[3]))]
+    return _f32(tri)
+
+
+def icosphere(subdivisions=2, radius=1.0):
+    """20 * 4^subdivisions triangles on a sphere; midpoints are shared through a cache, so neighbours agree bit for bit."""
+    t = (1 + math.sqrt(5)) / 2
+    verts = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1),
+             (-t, 0, -1), (-t, 0, 1)]
+    verts = [tuple(np.asarray(v, float) / np.linalg.norm(v)) for v in verts]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+             (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(subdivisions):
+        cache, new = {}, []
+
+        def mid(i, j):
+            key = (min(i, j), max(i, j))
+            if key not in cache:
+                m = (np.asarray(verts[i]) + np.asarray(verts[j])) / 2
+                verts.append(tuple(m / np.linalg.norm(m)))
+                cache[key] = len(verts) - 1
+            return cache[key]
+        for a, b, c in faces:
+            ab, bc, ca = mid(a, b), mid(b, c), mid(c, a)
+            new += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        faces = new
+    v = np.asarray(verts, float) * radius
+    return v[np.asarray(faces)]      # fp64: callers transform, then round once
+
+
+def sphere(subdivisions=2, radius=4.0, centre=(0.0, 0.0, 0.0)):
+    return _f32(icosphere(subdivisions, radius) + np.asarray(centre, float))
+
+
+def ellipsoid(subdivisions=4, semi_axes=(6.0, 5.0, 7.0), shear=0.12, centre=(3.0, 1.5, -1.0)):
+    """A sheared, off-centre ellipsoid: unit icosphere -> diag(semi_axes) -> (I + shear * strictly upper triangle) -> + centre."""
+    m = np.eye(3)
+    m[0, 1], m[0, 2], m[1, 2] = shear, -0.5 * shear, 0.75 * shear
+    v = icosphere(subdivisions, 1.0) * np.asarray(semi_axes, float)
+    return _f32(v @ m.T + np.asarray(centre, float))
+
+
+def torus(major=3.0, minor=1.2, nu=24, nv=12, axis=0, centre=(0.0, 0.0, 0.0)):
+    """2 * nu * nv triangles; the ring lies in the plane perpendicular to `axis`, so that seen along another axis the surface
+    has four layers (and a hole seen along `axis`)."""
+    u = np.arange(nu) * (2 * np.pi / nu)
+    w = np.arange(nv) * (2 * np.pi / nv)
+    uu, ww = np.meshgrid(u, w, indexing="ij")
+    p = np.stack(((major + minor * np.cos(ww)) * np.cos(uu), (major + minor * np.cos(ww)) * np.sin(uu), minor * np.sin(ww)), axis=2)
+    p = np.roll(p, axis + 1, axis=2) + np.asarray(centre, float)     # (ring plane, ring plane, axis) -> axis order
+    tri = []
+    for i in range(nu):
+        for j in range(nv):
+            a, b, c, d = p[i, j], p[(i + 1) % nu, j], p[(i + 1) % nu, (j + 1) % nv], p[i, (j + 1) % nv]
+            tri += [[a, b, c], [a, c, d]]
+    return _f32(tri)
+
+
+def l_prism(height=3.0, axis=0, centre=(0.0, 0.0, 0.0)):
+    """An L-shaped prism extruded along `axis`: two caps of 4 triangles, 12 wall triangles that are vertical (zero projected
+    area) when seen along `axis`, and one degenerate triangle (two coincident corners) floating above the notch."""
+    poly = np.array([(-3, -2.5), (3, -2.5), (3, -0.5), (0, -0.5), (0, 2.5), (-3, 2.5)], float)
+    cap = [(0, 1, 2), (0, 2, 3), (0, 3, 4), (0, 4, 5)]
+
+    def p3(k, z):
+        v = np.zeros(3)
+        v[axis], v[(axis + 1) % 3], v[(axis + 2) % 3] = z, poly[k, 0], poly[k, 1]
+        return v + np.asarray(centre, float)
+    h = height / 2
+    tri = [[p3(a, z), p3(b, z), p3(c, z)] for z in (-h, h) for (a, b, c) in cap]
+    for k in range(6):
+        n = (k + 1) % 6
+        tri += [[p3(k, -h), p3(n, -h), p3(n, h)], [p3(k, -h), p3(n, h), p3(k, h)]]
+    far = np.zeros(3)
+    far[axis], far[(axis + 1) % 3], far[(axis + 2) % 3] = 5 * h, 2.0, 1.5
+    tri.append([far + centre, far + centre, p3(2, 5 * h)])
+    return _f32(tri)
+
+
+# ---- STL ------------------------------------------------------------------------------------------------------------
+def _normals(tri):
+    n = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    length = np.linalg.norm(n, axis=1, keepdims=True)
+    return np.where(length > 0, n / np.where(length > 0, length, 1), 0.0)
+
+
+def write_stl_binary(path, tri, header=b"binary stl"):
+    tri = np.asarray(tri, np.float32)
+    rec = np.zeros(tri.shape[0], dtype=np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("a", "<u2")]))
+    rec["n"], rec["v"] = _normals(tri.astype(float)), tri
+    with open(path, "wb") as fh:
+        fh.write(header.ljust(80, b"\0")[:80])
+        fh.write(np.uint32(tri.shape[0]).tobytes())
+        fh.write(rec.tobytes())
+
+
+def write_stl_ascii(path, tri, name="mesh"):
+    tri = np.asarray(tri, np.float32)
+    n = _normals(tri.astype(float))
+    with open(path, "w") as fh:
+        fh.write(f"solid {name}\n")
+        for t, k in zip(tri, n):
+            fh.write(f"  facet normal {k[0]:.9e} {k[1]:.9e} {k[2]:.9e}\n    outer loop\n")
+            for v in t:
+                fh.write(f"      vertex {float(v[0])!r} {float(v[1])!r} {float(v[2])!r}\n")
+            fh.write("    endloop\n  endfacet\n")
+        fh.write(f"endsolid {name}\n")
+
+
+# ---- the definition, by brute force ---------------------------------------------------------------------------------
+def prepare(tri, pc_scale, gelslim_plane):
+    """(a, b, q, aligned_is_first): the in-plane coordinates in ascending axis order and the signed perpendicular coordinate of
+    every vertex, (T, 3) each, in mm."""
+    perp, aligned, unaligned, mult = plane_table(gelslim_plane)
+    v = np.asarray(tri, np.float64) * float(pc_scale)
+    p = v[:, :, perp]
+    q = mult * (p - (p.max() + p.min()) / 2)
+    lo, hi = sorted((aligned, unaligned))
+    return v[:, :, lo], v[:, :, hi], q, aligned < unaligned
+
+
+def pose_matrix(pose, invert_affine):
+    t1, t2, th = (float(x) for x in pose)
+    m = np.array([[math.cos(th), -math.sin(th), 1000 * t1], [math.sin(th), math.cos(th), 1000 * t2], [0, 0, 1]])
+    return np.linalg.inv(m) if invert_affine else m
+
+
+def inverted_pose(pose):
+    """The pose whose invert_affine=True picture equals `pose`'s invert_affine=False picture."""
+    t1, t2, th = (float(x) for x in pose)
+    c, s = math.cos(th), math.sin(th)
+    return (-(c * t1 + s * t2), -(-s * t1 + c * t2), -th)
+
+
+def coord_max(tri, pc_scale, gelslim_plane, pose, image_size, image_height_mm):
+    """The largest |coordinate| in mm that enters the pixel-to-mesh map: pixel positions, translation, mesh in-plane vertices."""
+    a, b, _, _ = prepare(tri, pc_scale, gelslim_plane)
+    h, w = image_size
+    mpp = image_height_mm / h
+    return max(mpp * h / 2, mpp * w / 2, abs(1000 * float(pose[0])), abs(1000 * float(pose[1])), np.abs(a).max(), np.abs(b).max())
+
+
+def raster_ref(tri, pc_scale, gelslim_plane, pose, g, image_size, image_height_mm, LR_flip=False, invert_affine=False, delta=None):
+    """(lo, hi), each (2, H, W) fp64 in mm, channels as render_depth's: every value the definition admits when positions are
+    uncertain by `delta` (default 16 * 2^-23 * coord_max).  hi of Qmax uses triangles grown by delta and q + |grad q| delta
+    sqrt 2 clamped to the triangle's largest q; lo of Qmax uses triangles shrunk by delta and the mirrored value clamped to its
+    smallest; Qmin the other way round.  Triangles of zero projected area are skipped."""
+    a, b, q, aligned_first = prepare(tri, pc_scale, gelslim_plane)
+    h, w = image_size
+    mpp = image_height_mm / h
+    if delta is None:
+        delta = 16 * 2.0 ** -23 * coord_max(tri, pc_scale, gelslim_plane, pose, image_size, image_height_mm)
+    m = pose_matrix(pose, invert_affine)
+    ta = m[0, 0] * a + m[0, 1] * b + m[0, 2]
+    tb = m[1, 0] * a + m[1, 1] * b + m[1, 2]
+    un, al = (tb, ta) if aligned_first else (ta, tb)          # transformed unaligned / aligned coordinates
+    ur = mpp * (np.arange(h) - h / 2)
+    vc = mpp * (np.arange(w) - w / 2)
+    half = float(g) / 2
+    out_lo, out_hi = np.zeros((2, h, w)), np.zeros((2, h, w))
+    for finger in (0, 1):                                     # 0 left (mirrored), 1 right
+        px = un if finger == 1 else -un                       # along image rows
+        py = al                                               # along image columns
+        e1x, e1y = px[:, 1] - px[:, 0], py[:, 1] - py[:, 0]
+        e2x, e2y = px[:, 2] - px[:, 0], py[:, 2] - py[:, 0]
+        area = e1x * e2y - e1y * e2x
+        keep = np.abs(area) > 1e-12 * np.hypot(e1x, e1y) * np.hypot(e2x, e2y)
+        qmax_hi, qmax_lo = np.full((h, w), -np.inf), np.full((h, w), -np.inf)
+        qmin_hi, qmin_lo = np.full((h, w), np.inf), np.full((h, w), np.inf)
+        r0 = np.clip(np.floor((px.min(axis=1) - delta) / mpp + h / 2).astype(int) - 1, 0, h)
+        r1 = np.clip(np.ceil((px.max(axis=1) + delta) / mpp + h / 2).astype(int) + 2, 0, h)
+        c0 = np.clip(np.floor((py.min(axis=1) - delta) / mpp + w / 2).astype(int) - 1, 0, w)
+        c1 = np.clip(np.ceil((py.max(axis=1) + delta) / mpp + w / 2).astype(int) + 2, 0, w)
+        tmin, tmax = q.min(axis=1), q.max(axis=1)
+        for t in np.nonzero(keep & (r1 > r0) & (c1 > c0))[0]:
+            sgn = 1.0 if area[t] > 0 else -1.0
+            x = ur[r0[t]:r1[t], None]
+            y = vc[None, c0[t]:c1[t]]
+            inside_g = inside_s = True
+            for i, j in ((0, 1), (1, 2), (2, 0)):
+                ex, ey = px[t, j] - px[t, i], py[t, j] - py[t, i]
+                d = sgn * (ex * (y - py[t, i]) - ey * (x - px[t, i])) / math.hypot(ex, ey)     # inward distance to the edge
+                inside_g = inside_g & (d >= -delta)
+                inside_s = inside_s & (d >= delta)
+            if not np.any(inside_g):
+                continue
+            dq1, dq2 = q[t, 1] - q[t, 0], q[t, 2] - q[t, 0]
+            gx = (dq1 * e2y[t] - dq2 * e1y[t]) / area[t]
+            gy = (-dq1 * e2x[t] + dq2 * e1x[t]) / area[t]
+            ql = q[t, 0] + gx * (x - px[t, 0]) + gy * (y - py[t, 0])
+            slack = math.hypot(gx, gy) * delta * math.sqrt(2)
+            q_hi = np.clip(ql + slack, tmin[t], tmax[t])
+            q_lo = np.clip(ql - slack, tmin[t], tmax[t])
+            win = (slice(r0[t], r1[t]), slice(c0[t], c1[t]))
+            qmax_hi[win] = np.where(inside_g, np.maximum(qmax_hi[win], q_hi), qmax_hi[win])
+            qmin_lo[win] = np.where(inside_g, np.minimum(qmin_lo[win], q_lo), qmin_lo[win])
+            qmax_lo[win] = np.where(inside_s, np.maximum(qmax_lo[win], q_lo), qmax_lo[win])
+            qmin_hi[win] = np.where(inside_s, np.minimum(qmin_hi[win], q_hi), qmin_hi[win])
+        ch = finger if not LR_flip else 1 - finger
+        if finger == 1:
+            out_lo[ch] = -np.maximum(0.0, qmax_hi - half)
+            out_hi[ch] = -np.maximum(0.0, qmax_lo - half)
+        else:
+            out_lo[ch] = np.minimum(0.0, qmin_lo + half)
+            out_hi[ch] = np.minimum(0.0, qmin_hi + half)
+    return out_lo + 0.0, out_hi + 0.0
+
+
+# ---- the reference, restated on a point cloud -----------------------------------------------------------------------
+def sample_surface(tri, n, seed=0):
+    """n points uniform over the surface (area-weighted triangle choice, uniform barycentric), numpy's PCG64."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    v = np.asarray(tri, np.float64)
+    area = 0.5 * np.linalg.norm(np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]), axis=1)
+    idx = rng.choice(v.shape[0], size=int(n), p=area / area.sum())
+    r1, r2 = np.sqrt(rng.random(int(n))), rng.random(int(n))
+    w0, w1, w2 = 1 - r1, r1 * (1 - r2), r1 * r2
+    return w0[:, None] * v[idx, 0] + w1[:, None] * v[idx, 1] + w2[:, None] * v[idx, 2]
+
+
+def reference_from_points(points, gelslim_plane, pose, inter_gelslim_distance, image_size, image_height_mm, invert_affine=False):
+    """(right, left) as depth_from_mesh.py:80-248 computes them from the (already scaled) cloud `points` (P, 3)."""
+    import scipy.interpolate as interp
+    perp, aligned, unaligned, mult = plane_table(gelslim_plane)
+    pc = np.array(points, np.float64)
+    g = float(inter_gelslim_distance)
+    h, w = image_size
+    mpp = image_height_mm / h
+    pc[:, perp] -= (pc[:, perp].max() + pc[:, perp].min()) / 2                     # :153-154
+    m = pose_matrix(pose, invert_affine)                                           # :233-248
+    inplane = [i for i in (0, 1, 2) if i != perp]
+    p2 = pc[:, inplane] @ m[:2, :2].T + m[:2, 2]
+    pc[:, inplane] = p2
+    right = pc[mult * pc[:, perp] > 0].copy()                                      # :158-159
+    left = pc[mult * pc[:, perp] < 0].copy()
+    right[mult * right[:, perp] < mult * g / 2, perp] = mult * g / 2               # :160-161, as written
+    left[mult * left[:, perp] > -mult * g / 2, perp] = -mult * g / 2
+    right[:, perp] = -(right[:, perp] - mult * g / 2) * mult                       # :163-164
+    left[:, perp] = (left[:, perp] + mult * g / 2) * mult
+    left[:, unaligned] = -left[:, unaligned]                                       # :166
+    min_l, min_r = left[:, perp].min(), right[:, perp].min()                       # :168-169
+    uu, vv = np.meshgrid(mpp * (np.arange(h) - h / 2), mpp * (np.arange(w) - w / 2), indexing="ij")     # :171-174
+    samples = np.stack((uu.ravel(), vv.ravel()), axis=1)
+    out = []
+    for cloud, floor in ((right, min_r), (left, min_l)):                           # :189-218
+        d = interp.griddata(cloud[:, [unaligned, aligned]], cloud[:, perp], samples, method="linear").astype(np.float32)
+        d[d > 0] = 0
+        d[d < floor] = floor
+        d = d.reshape(h, w)
+        d[np.isnan(d)] = 0
+        out.append(d.astype(np.float64))
+    return out[0], out[1]
+
+
+def reference_depth_image(points, gelslim_plane, pose, g, image_size, image_height_mm, LR_flip=False, invert_affine=False):
+    """(2, H, W): reference_from_points stacked as depth_from_mesh.py:73-76 does."""
+    right, left = reference_from_points(points, gelslim_plane, pose, g, image_size, image_height_mm, invert_affine)
+    return np.stack((right, left) if LR_flip else (left, right))
+
+
+def erode(mask, k):
+    """Pixels of `mask` whose (2k+1) x (2k+1) neighbourhood lies inside it (outside the image counts as outside)."""
+    h, w = mask.shape
+    pad = np.zeros((h + 2 * k, w + 2 * k), bool)
+    pad[k:k + h, k:k + w] = mask
+    out = np.ones((h, w), bool)
+    for dy in range(2 * k + 1):
+        for dx in range(2 * k + 1):
+            out &= pad[dy:dy + h, dx:dx + w]
+    return out
