@@ -27,6 +27,10 @@
 //   the double-precision functions, rounded once), walks its cell's list, MD_WALK entries per trip, keeping one extreme in a
 //   register (the right finger only needs Qmax, the left only Qmin = -max(-q)), and stores one float.  No atomics on the
 //   image, no LDS.
+//
+//   pose score (gsd_mesh_pose_score): the same per-pixel function (md_pixel) on a lattice of pixels,
+//   compared with an observed image in registers and reduced to five doubles per candidate pose: tile partials are stored and
+//   summed by a second kernel in a fixed order, so a row is reproducible and does not depend on its batch.
 #include "gsd_common.h"
 
 #include <math.h>
@@ -157,14 +161,15 @@ __global__ __launch_bounds__(256) void mesh_fill(const MdGrid G, const float* __
     }
 }
 
-// row n of the pose table: cos, sin, 1000 t1, 1000 t2, g/2 (NaN when g is negative or not finite: the sample's images are NaN)
-__global__ __launch_bounds__(256) void mesh_pose_table(const float* __restrict__ poses, const float* __restrict__ widths, int N,
+// row n of the pose table: cos, sin, 1000 t1, 1000 t2, g/2 (NaN when g is negative or not finite: the sample's images are NaN).
+// `per` consecutive poses share a width: 1 for the render, the P candidates of an observation for the pose score.
+__global__ __launch_bounds__(256) void mesh_pose_table(const float* __restrict__ poses, const float* __restrict__ widths, int N, int per,
                                                        float width_offset, float* __restrict__ table) {
 #pragma clang fp contract(off)
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
-  const float t1 = poses[3 * n], t2 = poses[3 * n + 1], th = poses[3 * n + 2];
-  const float g = widths[n] + width_offset;
+  const float t1 = poses[3 * (size_t)n], t2 = poses[3 * (size_t)n + 1], th = poses[3 * (size_t)n + 2];
+  const float g = widths[n / per] + width_offset;
   float* row = table + (size_t)n * MD_POSE;
   row[0] = (float)cos((double)th);
   row[1] = (float)sin((double)th);
@@ -201,22 +206,11 @@ struct MdView {
   long long list_elems;
 };
 
-__global__ __launch_bounds__(256) void mesh_render(const MdGrid G, const MdView V, const float* __restrict__ rec,
-                                                   const int* __restrict__ start, const int* __restrict__ list,
-                                                   const float* __restrict__ table, float* __restrict__ out) {
+// The depth of pixel (r, c) of one finger under the pose-table row `row`: the float mesh_render stores, and the R that
+// mesh_pose_score compares -- both call this, so a scored candidate has the bits of its rendered image.
+__device__ __forceinline__ float md_pixel(const MdGrid& G, const MdView& V, const float* __restrict__ rec, const int* __restrict__ start,
+                                          const int* __restrict__ list, const float* __restrict__ row, int r, int c, bool right) {
 #pragma clang fp contract(off)
-  int b = blockIdx.x;
-  const int tx = b % V.tiles_x;
-  b /= V.tiles_x;
-  const int ty = b % V.tiles_y;
-  const int img = b / V.tiles_y;            // n * 2 + channel
-  const int n = img >> 1, ch = img & 1;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int r = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
-  const int c = tx * 16 + (wave & 1) * 8 + (lane & 7);
-  if (r >= V.H || c >= V.W) return;
-  const bool right = (ch == 1) != (V.lr_flip != 0);
-  const float* row = table + (size_t)n * MD_POSE;
   const float cs = row[0], sn = row[1], t1 = row[2], t2 = row[3], hg = row[4];
   // pixel -> transformed in-plane point: u along the unaligned axis (mirrored for the left finger), v along the aligned one
   const float u = V.mpp * ((float)r - 0.5f * (float)V.H), v = V.mpp * ((float)c - 0.5f * (float)V.W);
@@ -257,7 +251,113 @@ __global__ __launch_bounds__(256) void mesh_render(const MdGrid G, const MdView 
   float d = -fmaxf(0.f, m - hg);
   d = d == 0.f ? 0.f : d;                    // no negative zero
   if (!(hg == hg)) d = hg;                   // refused width: NaN
-  out[((size_t)img * V.H + r) * V.W + c] = d;
+  return d;
+}
+
+__global__ __launch_bounds__(256) void mesh_render(const MdGrid G, const MdView V, const float* __restrict__ rec,
+                                                   const int* __restrict__ start, const int* __restrict__ list,
+                                                   const float* __restrict__ table, float* __restrict__ out) {
+  int b = blockIdx.x;
+  const int tx = b % V.tiles_x;
+  b /= V.tiles_x;
+  const int ty = b % V.tiles_y;
+  const int img = b / V.tiles_y;            // n * 2 + channel
+  const int n = img >> 1, ch = img & 1;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
+  const int c = tx * 16 + (wave & 1) * 8 + (lane & 7);
+  if (r >= V.H || c >= V.W) return;
+  const bool right = (ch == 1) != (V.lr_flip != 0);
+  out[((size_t)img * V.H + r) * V.W + c] = md_pixel(G, V, rec, start, list, table + (size_t)n * MD_POSE, r, c, right);
+}
+
+// ---- pose score: render and compare in registers, one row of five doubles per candidate --------------
+constexpr int MD_ROW = GSD_POSE_ROW;      // sum e^2, sum |e|, #{R < -c and D < -c}, #{R < -c}, #{D < -c}
+
+struct MdLattice {      // the pixels r = off + i * stride < H, c = off + j * stride < W, cut into 16 x 16 tiles of lattice points
+  int stride, off, rows, cols, tiles_x, tiles_y;
+  int P;                // candidates per observation
+  float contact;
+};
+
+// A block owns a 16 x 16 tile of lattice points of one (observation, candidate, channel), a wave an 8 x 8 patch, a thread one
+// point: R from md_pixel, D from the observed image, e = R - D in fp64.  The block's five values are reduced in a fixed order
+// (xor butterfly inside a wave, counts by ballot, then (w0 + w1) + (w2 + w3) through LDS) and stored as partial row blockIdx.x;
+// nothing is added in memory, so a partial depends on its own tile alone.
+__global__ __launch_bounds__(256) void mesh_pose_score(const MdGrid G, const MdView V, const MdLattice S, const float* __restrict__ rec,
+                                                       const int* __restrict__ start, const int* __restrict__ list,
+                                                       const float* __restrict__ table, const float* __restrict__ observed,
+                                                       double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  int b = blockIdx.x;
+  const int tx = b % S.tiles_x;
+  b /= S.tiles_x;
+  const int ty = b % S.tiles_y;
+  const int img = b / S.tiles_y;            // (observation * P + candidate) * 2 + channel
+  const int n = img >> 1, ch = img & 1;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
+  const int j = tx * 16 + (wave & 1) * 8 + (lane & 7);
+  double sq = 0.0, ab = 0.0;
+  bool cr = false, cd = false;
+  if (i < S.rows && j < S.cols) {           // a point off the lattice adds zeros; every thread reaches the reduction
+    const int r = S.off + i * S.stride, c = S.off + j * S.stride;       // < H, < W: no overflow
+    const bool right = (ch == 1) != (V.lr_flip != 0);
+    const float R = md_pixel(G, V, rec, start, list, table + (size_t)n * MD_POSE, r, c, right);
+    const float D = observed[(((size_t)(n / S.P) * 2 + ch) * V.H + r) * V.W + c];
+    const double e = (double)R - (double)D;
+    sq = e * e;
+    ab = fabs(e);
+    cr = R < -S.contact;
+    cd = D < -S.contact && isfinite(D);     // a non-finite D is not contact
+  }
+  __shared__ double red[4][MD_ROW];
+  const double s_sq = wave_sum_d(sq), s_ab = wave_sum_d(ab);
+  const int n_i = __popcll(__ballot(cr && cd)), n_r = __popcll(__ballot(cr)), n_d = __popcll(__ballot(cd));
+  if (lane == 0) {
+    red[wave][0] = s_sq, red[wave][1] = s_ab;
+    red[wave][2] = (double)n_i, red[wave][3] = (double)n_r, red[wave][4] = (double)n_d;
+  }
+  __syncthreads();
+  if (threadIdx.x < MD_ROW) {
+    const int q = threadIdx.x;
+    partial[(size_t)blockIdx.x * MD_ROW + q] = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
+  }
+}
+
+// One wave per candidate: lane l adds the partial rows l, l + 64, ... of the candidate's `tpc` tiles in ascending order, the 64
+// lane sums meet in the xor butterfly.  The order is a function of tpc alone.  A refused width (NaN in the pose table) gives
+// five NaN.
+__global__ __launch_bounds__(64) void mesh_pose_rows(const double* __restrict__ partial, int tpc, const float* __restrict__ table,
+                                                     double* __restrict__ rows) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.x, lane = threadIdx.x;
+  double tot[MD_ROW];
+#pragma unroll
+  for (int q = 0; q < MD_ROW; ++q) tot[q] = 0.0;
+  for (int k = lane; k < tpc; k += 64) {
+    const double* p = partial + ((size_t)n * tpc + k) * MD_ROW;
+#pragma unroll
+    for (int q = 0; q < MD_ROW; ++q) tot[q] += p[q];
+  }
+#pragma unroll
+  for (int q = 0; q < MD_ROW; ++q) tot[q] = wave_sum_d(tot[q]);
+  const float hg = table[(size_t)n * MD_POSE + 4];
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < MD_ROW; ++q) rows[(size_t)n * MD_ROW + q] = hg == hg ? tot[q] : (double)hg;
+  }
+}
+
+// lattice points along an axis of `len` pixels
+int md_lattice_len(int len, int stride) {
+  const int off = stride / 2;
+  return off < len ? (len - 1 - off) / stride + 1 : 0;
+}
+// blocks of the score launch, or -1 when an argument is out of range
+int64_t md_score_blocks(int B, int P, int H, int W, int stride) {
+  if (B < 1 || P < 1 || H < 1 || W < 1 || stride < 1 || (int64_t)B * P > INT32_MAX) return -1;
+  return (int64_t)ceil_div(md_lattice_len(W, stride), 16) * ceil_div(md_lattice_len(H, stride), 16) * 2 * ((int64_t)B * P);
 }
 
 int md_check_grid(const gsd_mesh_grid* g, const char* what) {
@@ -370,7 +470,7 @@ extern "C" int gsd_mesh_depth_render(const gsd_mesh_grid* grid, const gsd_mesh_v
   GSD_REQUIRE(blocks <= INT32_MAX, GSD_ERR_UNSUPPORTED, "gsd_mesh_depth_render: %lld blocks (N=%d of %d x %d), at most 2^31-1 per launch",
               (long long)blocks, N, H, W);
   const hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, poses, widths, N, view->width_offset,
+  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, poses, widths, N, 1, view->width_offset,
                      workspace);
   GSD_LAUNCH_CHECK("gsd_mesh_depth_render pose table");
   MdView V;
@@ -380,5 +480,63 @@ extern "C" int gsd_mesh_depth_render(const gsd_mesh_grid* grid, const gsd_mesh_v
   hipLaunchKernelGGL(mesh_render, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), V, records, cells + 2, list,
                      (const float*)workspace, out);
   GSD_LAUNCH_CHECK("gsd_mesh_depth_render");
+  return GSD_OK;
+}
+
+extern "C" int64_t gsd_mesh_pose_score_workspace(int B, int P, int H, int W, int stride) {
+  const int64_t blocks = md_score_blocks(B, P, H, W, stride);
+  if (blocks < 0 || blocks > INT32_MAX) return 0;
+  return (int64_t)B * P * (MD_POSE / 2) + blocks * MD_ROW;   // the pose table (8 floats a row) | one partial row per block
+}
+
+extern "C" int gsd_mesh_pose_score(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
+                                   const int32_t* cells, const int32_t* list, int64_t list_elems, const float* observed, int B,
+                                   const float* candidates, const float* widths, int P, int H, int W, int stride, float contact_depth,
+                                   double* rows, double* workspace, int64_t workspace_elems, void* stream) {
+  if (md_check_grid(grid, "gsd_mesh_pose_score")) return GSD_ERR_BAD_ARG;
+  GSD_REQUIRE(view && records && cells && list && observed && candidates && widths && rows && workspace, GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score: null pointer");
+  GSD_REQUIRE(T >= 1 && T <= MD_MAX_T, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: %d triangles, 1..%d", T, MD_MAX_T);
+  GSD_REQUIRE(B >= 1 && P >= 1 && H >= 1 && W >= 1, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: bad dims B=%d P=%d H=%d W=%d", B, P, H, W);
+  GSD_REQUIRE(stride >= 1, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: stride %d must be at least 1", stride);
+  GSD_REQUIRE(isfinite(contact_depth) && contact_depth >= 0.f, GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score: contact_depth %g must be finite and >= 0", (double)contact_depth);
+  GSD_REQUIRE(list_elems >= 1 && list_elems <= INT32_MAX, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: list of %lld entries, 1..2^31-1",
+              (long long)list_elems);
+  GSD_REQUIRE(isfinite(view->mpp) && view->mpp > 0.f && isfinite(view->width_offset), GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score: mm per pixel %g must be finite and positive, the width offset %g finite", (double)view->mpp,
+              (double)view->width_offset);
+  GSD_REQUIRE(view->reserved == 0, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: the reserved word must be 0");
+  GSD_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)rows & 7) == 0 && ((uintptr_t)workspace & 7) == 0, GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score: records must be 16-byte aligned, rows and workspace 8-byte aligned");
+  const int64_t blocks = md_score_blocks(B, P, H, W, stride);
+  GSD_REQUIRE(blocks >= 0 && blocks <= INT32_MAX, GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score: %lld blocks (B=%d x P=%d of %d x %d, stride %d), at most 2^31-1 per launch", (long long)blocks, B, P, H,
+              W, stride);
+  const int64_t need = gsd_mesh_pose_score_workspace(B, P, H, W, stride);
+  GSD_REQUIRE(workspace_elems >= need, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: workspace of %lld doubles, need %lld",
+              (long long)workspace_elems, (long long)need);
+  const int N = B * P;
+  const hipStream_t st = (hipStream_t)stream;
+  float* table = reinterpret_cast<float*>(workspace);
+  double* partial = workspace + (int64_t)N * (MD_POSE / 2);
+  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, candidates, widths, N, P, view->width_offset,
+                     table);
+  GSD_LAUNCH_CHECK("gsd_mesh_pose_score pose table");
+  MdView V;
+  V.mpp = view->mpp, V.cx = grid->cx, V.cy = grid->cy;
+  V.swap_axes = view->swap_axes != 0, V.invert = view->invert_affine != 0, V.lr_flip = view->lr_flip != 0;
+  V.H = H, V.W = W, V.tiles_x = ceil_div(W, 16), V.tiles_y = ceil_div(H, 16), V.T = T, V.list_elems = list_elems;
+  MdLattice S;
+  S.stride = stride, S.off = stride / 2, S.rows = md_lattice_len(H, stride), S.cols = md_lattice_len(W, stride);
+  S.tiles_x = ceil_div(S.cols, 16), S.tiles_y = ceil_div(S.rows, 16), S.P = P, S.contact = contact_depth;
+  if (blocks > 0) {      // a stride that leaves no lattice point: every row is five zeros
+    hipLaunchKernelGGL(mesh_pose_score, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), V, S, records, cells + 2, list,
+                       (const float*)table, observed, partial);
+    GSD_LAUNCH_CHECK("gsd_mesh_pose_score");
+  }
+  hipLaunchKernelGGL(mesh_pose_rows, dim3((unsigned)N), dim3(64), 0, st, (const double*)partial, (int)(blocks / N), (const float*)table,
+                     rows);
+  GSD_LAUNCH_CHECK("gsd_mesh_pose_score rows");
   return GSD_OK;
 }

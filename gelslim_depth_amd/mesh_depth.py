@@ -382,3 +382,237 @@ class DepthImageGenerator:
                 depth[i:j] = img.cpu()
             dataset_pt["depth_image"] = depth
             atomic_save(dataset_pt, path)
+
+
+# ---- in-hand pose from a depth image ----------------------------------------------------------
+POSE_ROW = L.GSD_POSE_ROW      # columns of a score row: sum_sq, sum_abs, inter, n_rendered, n_observed
+
+
+def lattice_points(image_size: Sequence[int], stride: int = 1) -> int:
+    """Points that a row of `score_poses` sums over: both channels of the pixel lattice r = stride // 2 + i * stride < H,
+    c = stride // 2 + j * stride < W.  What `pose_cost` divides by."""
+    h, w = (int(d) for d in image_size)
+    s = int(stride)
+    if h < 1 or w < 1 or s < 1:
+        raise MeshDepthError(f"lattice_points: image_size {tuple(image_size)} and stride {stride!r} must be positive")
+    return 2 * len(range(s // 2, h, s)) * len(range(s // 2, w, s))
+
+
+def score_poses(grid: MeshGrid, observed: torch.Tensor, candidates: torch.Tensor, grasp_widths: torch.Tensor,
+                image_height_mm: float = 12.0, grasp_width_offset: float = 0.0, LR_flip: bool = False, invert_affine: bool = False,
+                stride: int = 1, contact_depth: float = 0.0, out: Optional[torch.Tensor] = None, validate: bool = True) -> torch.Tensor:
+    """Rows (B, P, 5) float64 that compare the depth images `observed` (B, 2, H, W) fp32 in mm, channels as `render_depth`'s
+    (with the same `LR_flip`), with the renders of `grid`'s mesh under the candidate poses `candidates` (B, P, 3) = (t1 [m],
+    t2 [m], theta [rad]) -- a (P, 3) tensor serves every observation -- at the widths `grasp_widths` (B,) [mm]:
+
+        sum_sq = sum e^2, sum_abs = sum |e|, inter = #{R < -c and D < -c}, n_rendered = #{R < -c}, n_observed = #{D < -c}
+
+    R the depth `render_depth` gives for that candidate and pixel (the same bits), D the observed one, e = R - D in fp64,
+    c = `contact_depth` >= 0, summed over both channels and the pixels r = stride // 2 + i * stride, c = stride // 2 + j * stride
+    of the full image (a stride thins the lattice and does not resample).  No image is written: one libgsd call
+    (gsd_mesh_pose_score) renders and compares in registers, on torch's current stream.  A row depends on its own observation,
+    candidate, stride and image alone, not on B, P or its position, and a repeated call gives the same bits.
+
+    A non-finite D on the lattice makes that row's two sums non-finite and is not contact; off the lattice it changes nothing.
+    `validate` is `render_depth`'s: by default the smallest grasp width + offset is read back (the call's only synchronisation)
+    and a negative or non-finite one raises MeshDepthError; with `validate=False` nothing is synchronised and such an
+    observation's rows are five NaN each."""
+    if not isinstance(grid, MeshGrid):
+        raise MeshDepthError(f"score_poses: grid must be a MeshGrid, got {type(grid).__name__}")
+    for name, t, shape in (("observed", observed, "(B, 2, H, W)"), ("candidates", candidates, "(B, P, 3) or (P, 3)"),
+                           ("grasp_widths", grasp_widths, "(B,)")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
+            raise MeshDepthError(f"score_poses: {name} must be a float32 {shape} tensor on the GPU, got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')}")
+        if t.device != grid.device:
+            raise MeshDepthError(f"score_poses: {name} is on {t.device}, the mesh on {grid.device}")
+    if observed.dim() != 4 or observed.shape[1] != 2 or min(observed.shape) < 1:
+        raise MeshDepthError(f"score_poses: observed must be (B, 2, H, W) with B, H, W >= 1, got {tuple(observed.shape)}")
+    b, _, h, w = (int(d) for d in observed.shape)
+    if candidates.dim() == 2:
+        candidates = candidates.unsqueeze(0).expand(b, -1, -1)
+    if candidates.dim() != 3 or candidates.shape[0] != b or candidates.shape[2] != 3 or candidates.shape[1] < 1:
+        raise MeshDepthError(f"score_poses: candidates must be ({b}, P, 3) or (P, 3) with P >= 1, got {tuple(candidates.shape)}")
+    p = int(candidates.shape[1])
+    if tuple(grasp_widths.shape) != (b,):
+        raise MeshDepthError(f"score_poses: {b} observations but grasp_widths of shape {tuple(grasp_widths.shape)}")
+    observed, candidates, grasp_widths = observed.contiguous(), candidates.contiguous(), grasp_widths.contiguous()
+    mpp = float(image_height_mm) / h
+    if not (math.isfinite(mpp) and mpp > 0.0):
+        raise MeshDepthError(f"score_poses: image_height_mm {image_height_mm!r} must be finite and positive")
+    offset = float(grasp_width_offset)
+    if not math.isfinite(offset):
+        raise MeshDepthError(f"score_poses: grasp_width_offset must be finite, got {grasp_width_offset!r}")
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
+        raise MeshDepthError(f"score_poses: stride must be an integer >= 1, got {stride!r}")
+    depth = float(contact_depth)
+    if not (math.isfinite(depth) and depth >= 0.0):
+        raise MeshDepthError(f"score_poses: contact_depth must be finite and >= 0, got {contact_depth!r}")
+    if out is None:
+        out = torch.empty((b, p, POSE_ROW), device=grid.device, dtype=torch.float64)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != grid.device or not out.is_contiguous()
+          or tuple(out.shape) != (b, p, POSE_ROW)):
+        raise MeshDepthError(f"score_poses: out must be a contiguous float64 ({b}, {p}, {POSE_ROW}) tensor on {grid.device}")
+    words = int(lib.gsd_mesh_pose_score_workspace(b, p, h, w, int(stride)))
+    if words < 1:
+        raise MeshDepthError(f"score_poses: {b} x {p} candidates of {h} x {w} at stride {stride} are more than one launch takes "
+                             "(2^31 - 1 blocks): score them in parts")
+    if validate:
+        g_min = float((grasp_widths + offset).min())          # NaN propagates through min
+        if not (g_min >= 0.0) or not bool(torch.isfinite(grasp_widths).all()):
+            raise MeshDepthError(f"score_poses: grasp width + offset must be finite and >= 0, the smallest is {g_min!r}")
+    view = L.gsd_mesh_view()
+    view.mpp, view.width_offset = mpp, offset
+    view.swap_axes, view.invert_affine, view.lr_flip, view.reserved = grid.swap_axes, int(bool(invert_affine)), int(bool(LR_flip)), 0
+    with torch.cuda.device(grid.device):
+        ws = torch.empty((words,), device=grid.device, dtype=torch.float64)
+        check(lib.gsd_mesh_pose_score(C.byref(grid.grid), C.byref(view), grid.records.data_ptr(), grid.triangles,
+                                      grid.cells.data_ptr(), grid.list.data_ptr(), grid.list.numel(), observed.data_ptr(), b,
+                                      candidates.data_ptr(), grasp_widths.data_ptr(), p, h, w, int(stride), depth, out.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), L.stream_ptr()), "mesh_pose_score")
+    return out
+
+
+_COSTS = ("mse", "l1", "iou")
+
+
+def pose_cost(rows: torch.Tensor, kind="mse", n_points: int = 1) -> torch.Tensor:
+    """The cost (...,) float64 of score rows (..., 5), in plain torch on the rows' device:
+    'mse' = sum_sq / n_points, 'l1' = sum_abs / n_points (`lattice_points` gives n_points),
+    'iou' = 1 - inter / (n_rendered + n_observed - inter), 0 where that union is empty, or a dict of weights over those three
+    names, e.g. {"mse": 1.0, "iou": 0.05}.  A NaN cost (a refused width, a NaN observation) becomes +inf, so that it never beats
+    a finite one."""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 or rows.dim() < 1 or rows.shape[-1] != POSE_ROW:
+        raise MeshDepthError(f"pose_cost: rows must be a float64 (..., {POSE_ROW}) tensor")
+    weights = kind if isinstance(kind, dict) else {kind: 1.0}
+    if not weights or any(k not in _COSTS for k in weights):
+        raise MeshDepthError(f"pose_cost: kind must be one of {_COSTS} or a dict of weights over them, got {kind!r}")
+    if not (isinstance(n_points, (int, np.integer)) and n_points >= 1):
+        raise MeshDepthError(f"pose_cost: n_points must be a positive integer, got {n_points!r}")
+    cost = None
+    for name, wt in weights.items():
+        if name == "mse":
+            part = rows[..., 0] / float(n_points)
+        elif name == "l1":
+            part = rows[..., 1] / float(n_points)
+        else:
+            union = rows[..., 3] + rows[..., 4] - rows[..., 2]
+            part = torch.where(union > 0, 1.0 - rows[..., 2] / torch.where(union > 0, union, torch.ones_like(union)),
+                               torch.zeros_like(union))
+            part = torch.where(torch.isnan(union), union, part)          # a NaN row stays NaN here, +inf below
+        part = part if isinstance(kind, str) else float(wt) * part
+        cost = part if cost is None else cost + part
+    return torch.where(torch.isnan(cost), torch.full_like(cost, float("inf")), cost)
+
+
+def first_argmin(cost: torch.Tensor) -> torch.Tensor:
+    """Index (B,) of the smallest entry of every row of `cost` (B, P), THE LOWEST INDEX AMONG EQUAL ONES -- `torch.argmin`'s
+    documented rule, spelled out so that the winner of a tie does not depend on how a reduction is scheduled.  A row of +inf
+    (nothing finite to choose from) gives index 0; +inf never beats a finite cost."""
+    best = cost.min(dim=1, keepdim=True).values
+    index = torch.arange(cost.shape[1], device=cost.device).expand_as(cost)
+    return torch.where(cost == best, index, torch.full_like(index, cost.shape[1])).min(dim=1).values.clamp_(max=cost.shape[1] - 1)
+
+
+def search_schedule(half_span: Sequence[float], counts: Sequence[int] = (7, 7, 9), levels: int = 4) -> Tuple[np.ndarray, np.ndarray]:
+    """The lattices of `estimate_pose`, on the host in fp32: (half_spans (levels + 1, 3), offsets (levels, P, 3)).
+    Level l has the half-span half_spans[l] and the step half_spans[l + 1] = 2 * half_spans[l] / (n - 1) per axis; its candidate
+    with the flat index (i1 * n2 + i2) * n3 + i3 lies offsets[l] = (i - (n - 1) / 2) * step from the centre, so the middle
+    candidate's offset is exactly 0.  The schedule depends on no data: it is computed once and uploaded."""
+    try:
+        counts = tuple(counts)
+    except TypeError:
+        counts = ()
+    if len(counts) != 3 or any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 3 or n % 2 == 0 for n in counts):
+        raise MeshDepthError(f"estimate_pose: counts must be three odd integers >= 3, got {counts!r}")
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1:
+        raise MeshDepthError(f"estimate_pose: levels must be an integer >= 1, got {levels!r}")
+    if isinstance(half_span, torch.Tensor):
+        half_span = half_span.detach().cpu().numpy()
+    half = np.asarray(half_span, dtype=np.float32)
+    if half.shape != (3,) or not np.isfinite(half).all() or (half < 0).any():
+        raise MeshDepthError(f"estimate_pose: half_span must be three finite values >= 0 (t1 [m], t2 [m], theta [rad]), got {half_span!r}")
+    div = np.asarray([n - 1 for n in counts], dtype=np.float32)
+    spans, offsets = [half], []
+    for _ in range(int(levels)):
+        step = (np.float32(2.0) * spans[-1]) / div
+        axes = [(np.arange(n, dtype=np.float32) - np.float32((n - 1) // 2)) * step[a] for a, n in enumerate(counts)]
+        mesh = np.meshgrid(*axes, indexing="ij")
+        offsets.append(np.stack([m.reshape(-1) for m in mesh], axis=1).astype(np.float32))
+        spans.append(step)
+    return np.stack(spans), np.stack(offsets)
+
+
+class PoseEstimate:
+    """What `estimate_pose` found, all tensors on the device: `pose` (B, 3) fp32 = (t1 [m], t2 [m], theta [rad]), `cost` (B,)
+    fp64 and `row` (B, 5) fp64 of that pose at the last level's stride, `trace` (levels, B) fp64, the best cost of every level."""
+
+    def __init__(self, pose: torch.Tensor, cost: torch.Tensor, row: torch.Tensor, trace: torch.Tensor) -> None:
+        self.pose, self.cost, self.row, self.trace = pose, cost, row, trace
+
+    def __repr__(self) -> str:
+        return f"PoseEstimate({self.pose.shape[0]} observations, {self.trace.shape[0]} levels)"
+
+
+def estimate_pose(grid: MeshGrid, observed: torch.Tensor, grasp_widths: torch.Tensor, init, half_span: Sequence[float],
+                  counts: Sequence[int] = (7, 7, 9), levels: int = 4, strides: Optional[Sequence[int]] = None, cost="mse",
+                  image_height_mm: float = 12.0, grasp_width_offset: float = 0.0, LR_flip: bool = False,
+                  invert_affine: bool = False, contact_depth: float = 0.0, validate: bool = True) -> PoseEstimate:
+    """The planar pose (t1, t2, theta) of `grid`'s mesh in the hand from depth images `observed` (B, 2, H, W) -- a prediction of the
+    net or a label -- and the grasp widths: a coarse-to-fine lattice search, render-and-compare through `score_poses`.
+
+    Level 0 is centred on `init` ((B, 3) or (3,): tensor or sequence) with the half-spans `half_span` (3,) (host values).  Level
+    l scores the n1 * n2 * n3 candidates centre + (i - (n - 1) / 2) * step per axis, step = 2 * half / (n - 1), in fp32 (`counts`
+    are odd and >= 3, so the middle candidate IS the centre, bit for bit), at `strides[l]` (default: 1 everywhere; at 320 x 427
+    something like (4, 2, 1, 1) saves most of the time).  The winner is the candidate of least `pose_cost(rows, cost, ...)`:
+    torch.argmin's rule, the LOWEST flat index (i1 * n2 + i2) * n3 + i3 among equal costs (`first_argmin`); NaN costs count as
+    +inf, which never beats a finite cost.  The next level is centred on the winner with half-span = this level's step.  Because
+    a row does not depend on its batch, the best cost cannot rise from one level to the next at an equal stride.
+
+    Everything runs on the device; nothing is read back (with `validate=True`, `score_poses`' one check of the widths is made
+    once, before the first level).  The view arguments are `score_poses`'."""
+    spans, offsets = search_schedule(half_span, counts, levels)
+    levels = int(levels)
+    strides = (1,) * levels if strides is None else tuple(strides)
+    if len(strides) != levels or any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) or s < 1 for s in strides):
+        raise MeshDepthError(f"estimate_pose: strides must be {levels} integers >= 1, one per level, got {strides!r}")
+    if not isinstance(grid, MeshGrid):
+        raise MeshDepthError(f"estimate_pose: grid must be a MeshGrid, got {type(grid).__name__}")
+    if not isinstance(observed, torch.Tensor) or observed.dim() != 4:
+        raise MeshDepthError("estimate_pose: observed must be a (B, 2, H, W) tensor")
+    b, _, h, w = (int(d) for d in observed.shape)
+    centre = torch.as_tensor(init, dtype=torch.float32).to(grid.device)
+    if centre.dim() == 1:
+        centre = centre.unsqueeze(0).expand(b, -1)
+    if tuple(centre.shape) != (b, 3):
+        raise MeshDepthError(f"estimate_pose: init must be ({b}, 3) or (3,), got {tuple(centre.shape)}")
+    centre = centre.contiguous()
+    with torch.cuda.device(grid.device):
+        offs = torch.from_numpy(offsets).to(grid.device)          # (levels, P, 3)
+        trace = torch.empty((levels, b), device=grid.device, dtype=torch.float64)
+        best_cost = best_row = None
+        for lvl in range(levels):
+            cand = (centre.unsqueeze(1) + offs[lvl].unsqueeze(0)).contiguous()          # one fp32 add: the middle one is the centre
+            rows = score_poses(grid, observed, cand, grasp_widths, image_height_mm, grasp_width_offset, LR_flip, invert_affine,
+                               strides[lvl], contact_depth, validate=validate and lvl == 0)
+            c = pose_cost(rows, cost, lattice_points((h, w), strides[lvl]))
+            win = first_argmin(c)
+            centre = torch.gather(cand, 1, win.view(b, 1, 1).expand(b, 1, 3)).squeeze(1).contiguous()
+            best_row = torch.gather(rows, 1, win.view(b, 1, 1).expand(b, 1, POSE_ROW)).squeeze(1)
+            best_cost = torch.gather(c, 1, win.view(b, 1)).squeeze(1)
+            trace[lvl] = best_cost
+    return PoseEstimate(centre, best_cost, best_row, trace)
+
+
+def pose_error(estimate, truth: torch.Tensor) -> torch.Tensor:
+    """(B, 3) float64: the translation errors of `estimate` (a PoseEstimate or a (B, 3) pose tensor) against `truth` (B, 3) or
+    (3,) -- a dataset file's `in_hand_pose[:, :3]` -- in MILLIMETRES, and the angle error in radians wrapped to (-pi, pi]."""
+    pose = estimate.pose if isinstance(estimate, PoseEstimate) else estimate
+    if not isinstance(pose, torch.Tensor) or pose.dim() != 2 or pose.shape[1] != 3:
+        raise MeshDepthError("pose_error: estimate must be a PoseEstimate or a (B, 3) tensor")
+    truth = torch.as_tensor(truth).to(pose.device)
+    if truth.shape[-1] != 3 or truth.dim() > 2:
+        raise MeshDepthError(f"pose_error: truth must be (B, 3) or (3,), got {tuple(truth.shape)}")
+    d = pose.to(torch.float64) - truth.to(torch.float64)
+    angle = d[:, 2] - 2.0 * math.pi * torch.ceil((d[:, 2] - math.pi) / (2.0 * math.pi))
+    return torch.stack((1000.0 * d[:, 0], 1000.0 * d[:, 1], angle), dim=1)

@@ -515,6 +515,33 @@ int gsd_mesh_depth_render(const gsd_mesh_grid* grid, const gsd_mesh_view* view, 
                           const int32_t* list, int64_t list_elems, const float* poses, const float* widths, int N, int H, int W,
                           float* out, float* workspace, int64_t workspace_elems, void* stream);
 
+/* ---- in-hand pose from a depth image: score candidate poses against an observed image ---- */
+/* Render-and-compare without the images: for each of B observations and each of its P candidate poses, one row of
+ * GSD_POSE_ROW doubles
+ *   sum_sq = sum e^2,  sum_abs = sum |e|,  inter = #{R < -c and D < -c},  n_rendered = #{R < -c},  n_observed = #{D < -c}
+ * with R the depth gsd_mesh_depth_render stores for that candidate, width and pixel (the same bits), D the observed depth,
+ * e = (double)R - (double)D and c = contact_depth >= 0.  The sums run over both channels and over the pixel lattice
+ * r = stride/2 + i*stride < H, c = stride/2 + j*stride < W of the full H x W image (mpp = image_height_mm / H: a stride thins
+ * the lattice, it does not resample the image).
+ * grid, view, records, T, cells, list, list_elems: as for gsd_mesh_depth_render.
+ * observed: B x 2 x H x W floats in mm, channels as gsd_mesh_depth_render writes them (view.lr_flip is honoured).
+ * candidates: B x P x 3 floats (t1 [m], t2 [m], theta [rad]); widths: B floats, g = widths[b] + view.width_offset.
+ * rows: B x P x GSD_POSE_ROW doubles, 8-byte aligned.  A non-finite D on the lattice makes the row's two sums non-finite and is
+ *   not contact in the counts; off the lattice it has no effect.  An observation whose g is negative or not finite gets rows of
+ *   five NaN.
+ * workspace: gsd_mesh_pose_score_workspace(B, P, H, W, stride) doubles, 8-byte aligned (0 for arguments the call refuses).
+ * A row depends on its own observation, candidate, stride and image alone -- not on B, P or its position -- and a repeated call
+ * gives the same bits: no float atomics; 16 x 16 tiles of lattice points are reduced in fp64 in a fixed order and a second
+ * kernel sums a candidate's tiles in a fixed order.  Nothing is allocated, every launch is on `stream`, nothing synchronises.
+ * GSD_ERR_BAD_ARG before any launch: a null pointer, B, P, H, W or stride below 1, contact_depth negative or not finite,
+ * a workspace that is too small, 2^31 or more blocks (2 * B * P * tiles), and what gsd_mesh_depth_render refuses. */
+#define GSD_POSE_ROW 5
+int64_t gsd_mesh_pose_score_workspace(int B, int P, int H, int W, int stride);   /* doubles */
+int gsd_mesh_pose_score(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T, const int32_t* cells,
+                        const int32_t* list, int64_t list_elems, const float* observed, int B, const float* candidates,
+                        const float* widths, int P, int H, int W, int stride, float contact_depth, double* rows, double* workspace,
+                        int64_t workspace_elems, void* stream);
+
 /* ---- optimiser (train_unet.py:306,375-376) -------------------------------------------------- */
 /* Fused torch.optim.Adam(lr, betas, eps, weight_decay: coupled L2) + torch_ema update over a flat
  * parameter arena. step is the 1-based Adam step; ema may be NULL; ema_decay already resolved
