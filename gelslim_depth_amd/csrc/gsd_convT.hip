@@ -18,6 +18,7 @@
 // chunks of 16 k-rows (4 k-steps); the next chunk's global loads are issued before the current
 // chunk's MFMAs (register prefetch) and written to LDS after them.  The 3x3 convolutions, which
 // dominate the step, live in gsd_conv3x3.hip / gsd_wgrad.hip; these two operators are ~4% of it.
+// The weight and bias gradients of this operator: gsd_convT_wgrad.hip.
 #include "gsd_common.h"
 
 namespace {

@@ -35,7 +35,8 @@
 // bookkeeping left the vector pipe: 23.8 on the same box, profiles/wg2d_scalar_layers_b32.txt).  The kernel lives at the register
 // limit and must compile to ZERO scratch (tests/test_abi.py): with spills hipcc stored two slots on some paths of a branchy
 // prologue only and reloaded them on all.
-// Split-K over k-steps with ordered slab reduction (the row form's reducer and slab layout): bitwise reproducible.
+// Split-K over k-steps; the slabs have the row form's layout and gsd_conv3x3_wgrad sums them in a fixed order (wgrad3x3_reduce_kernel,
+// gsd_wgrad.hip): bitwise reproducible.
 //
 // Conventions: U row 3 is +dY row 1 and V row 3 is d3 - d1 (both signs of the textbook F(2,3) flipped: same products).
 //
@@ -58,8 +59,7 @@
 //     the first, the last and (with a cropped segment) the last-but-one position of a direction mask anything.  The border pieces
 //     lie out of line; an interior k-step runs straight through.
 // Static counts per instantiation: tests/test_wg2d_isa.py, profiles/wg2d_isa_counts.txt.
-#include "gsd_common.h"
-#include "gsd_wgrad_internal.h"
+#include "gsd_wgrad_host.h"
 #include <type_traits>
 
 #include <cstdio>
@@ -679,12 +679,8 @@ WgW2dPlan plan_wg2d(int N, int H, int W, int M, int Ncols) {
   p.nblocks = ceil_div(Ncols, p.BN);
   p.ksteps_total = N * p.sy_n * p.sx_n;
   const int target = gsd_env_int("GSD_WG2D_BLOCKS", gsd_cu_count());   // one block per CU (256 on MI355X, and where no device is visible)
-  int splits = ceil_div(target, p.mblocks * p.nblocks);
-  if (splits > p.ksteps_total) splits = p.ksteps_total;
-  if (splits > 2048) splits = 2048;
-  if (splits < 1) splits = 1;
-  p.splits = splits;
-  p.slab_elems = (int64_t)splits * 9 * M * Ncols;
+  p.splits = wgrad_pick_splits(target, p.mblocks * p.nblocks, p.ksteps_total);
+  p.slab_elems = (int64_t)p.splits * 9 * M * Ncols;
   return p;
 }
 
@@ -707,7 +703,7 @@ int gsd_wgrad_w2d_use(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, in
   if (gsd_env_int("GSD_WGRAD_W2D", 1) == 0) return 0;
   const WgW2dPlan p = plan_wg2d(N, H, W, Cout, Cin);
   if (!p.ok) return 0;
-  if (dy->w_stride % 4 != 0 || ((uintptr_t)dy->ptr & 15) != 0 || dy->c_stride % 4 != 0 || dy->n_stride % 4 != 0) return 0;
+  if (!wgrad_dy_x4(*dy)) return 0;
   if (dy->w_stride < 4 * p.tiles_x) return 0;
   if ((int64_t)p.BM * dy->c_stride * 4 >= (1LL << 31)) return 0;   // lane offsets are 32-bit byte offsets inside a block's planes
   if (nsrc == 2 && a[0].C % p.BN != 0) return 0;
@@ -723,27 +719,18 @@ int gsd_wgrad_w2d_use(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, in
   return 1;
 }
 
-// arguments already validated by gsd_conv3x3_wgrad and gsd_wgrad_w2d_use
-int gsd_wgrad_w2d_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, int Cout, float* workspace, int64_t workspace_elems,
-                      int N, int H, int W, int* splits_out, void* stream) {
+// arguments and workspace already validated by gsd_conv3x3_wgrad, the form's own conditions by gsd_wgrad_w2d_use; returns the slab count
+int gsd_wgrad_w2d_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, int Cout, float* workspace, int N, int H, int W,
+                      void* stream) {
   const WgW2dPlan pl = plan_wg2d(N, H, W, Cout, Cin);
-  GSD_REQUIRE(pl.ok, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_wgrad (w2d): shape not served");
-  GSD_REQUIRE(workspace_elems >= pl.slab_elems, GSD_ERR_WORKSPACE, "gsd_conv3x3_wgrad: workspace %lld < %lld elements",
-              (long long)workspace_elems, (long long)pl.slab_elems);
   WgW2dParams P;
-  P.a0 = to_srcd(a[0]);
-  P.a1 = nsrc > 1 ? to_srcd(a[1]) : null_srcd();
-  P.dy = to_srcd(*dy);
-  P.slabs = workspace;
-  P.M = Cout; P.Ncols = Cin;
-  P.N = N; P.H = H; P.W = W;
+  wgrad_fill_common(P, a, nsrc, dy, Cin, Cout, workspace, N, H, W, pl.splits, pl.mblocks, pl.nblocks);
   P.KY = pl.KY; P.KX = pl.KX; P.kx_log2 = pl.kx_log2;
   P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x; P.sy_n = pl.sy_n; P.sx_n = pl.sx_n;
   P.WR = 2 * pl.KY + 2; P.NP = pl.KX + 1;
   P.NI = (pl.BN * P.WR * P.NP + 63) / 64;
-  P.ksteps_total = pl.ksteps_total; P.splits = pl.splits; P.mblocks = pl.mblocks; P.nblocks = pl.nblocks;
-  bool plain = true;
-  for (int i = 0; i < nsrc; ++i) plain = plain && a[i].scale == nullptr && a[i].relu == 0;
+  P.ksteps_total = pl.ksteps_total;
+  const bool plain = wgrad_plain(a, nsrc);
   const long grid = (long)pl.splits * pl.mblocks * pl.nblocks;
   // LDS (floats): dy slots [1 or 2 pieces][8 waves][256] | two window images of 10 / 20 KiB | two images of [4 tiles][BM | BN][24] (+4) | (scale, shift)[BN]
   const size_t lds = ((size_t)(pl.BM == 64 ? 1 : 2) * 8 * 256 + (size_t)2 * (pl.BN == 32 ? 10 : 20) * 256 +
@@ -760,6 +747,5 @@ int gsd_wgrad_w2d_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, in
                            : (plain ? gsd_launch<wgrad3x3_w2d_kernel<2, 4, true>>(what, g, dim3(512), lds, st, P)
                                     : gsd_launch<wgrad3x3_w2d_kernel<2, 4, false>>(what, g, dim3(512), lds, st, P)))
     return e;
-  *splits_out = pl.splits;
-  return GSD_OK;
+  return pl.splits;
 }

@@ -11,17 +11,16 @@
 // and G^T applied once at the very end.  Per (co, ci, kernel row r) and tile that is 6 products instead of 12:
 //
 //   D_{f,r}[co][ci] = sum_tiles U_f[co][tile] * V_{f,r}[tile][ci]          (18 accumulators per (co,ci) instead of 9)
-//   dW[co][ci][r][s] = sum_f G[f][s] * D_{f,r}[co][ci]                      (wgrad_w43_reduce_kernel, after the split sum)
+//   dW[co][ci][r][s] = sum_f G[f][s] * D_{f,r}[co][ci]                      (the epilogue, per split: it is linear)
 //
 // GEMM view: M = co, N = ci, K = tiles (4 per v_mfma_f32_16x16x4_f32).  Block = 4 or 8 waves (see the kernel); wave tile
 // 32 co x 16 ci x 18 = 144 accumulator registers.  A stage is 16 tiles (64 pixels, TH rows x TW columns): dy rows
 // [co][64 px, tile-major] and the activation halo windows [ci][(TH+2) x (TW+2)] reach LDS by global_load_lds (dword
 // gathers, zero padding / out-of-segment positions from a sentinel: NaN under a ReLU, else 0), double buffered, two
 // waves per SIMD.  The deferred BatchNorm+ReLU of the activation is applied after the ds_read (a lane's input channel is
-// fixed), then B^T; A dy needs 9 VALU operations per 4 values.  Split-K over stages with ordered slab reduction as in
-// gsd_wgrad.hip: bitwise reproducible.
-#include "gsd_common.h"
-#include "gsd_wgrad_internal.h"
+// fixed), then B^T; A dy needs 9 VALU operations per 4 values.  Split-K over stages; gsd_conv3x3_wgrad sums the slabs in a fixed order
+// (wgrad3x3_reduce_kernel, gsd_wgrad.hip): bitwise reproducible.
+#include "gsd_wgrad_host.h"
 #include <type_traits>
 
 #include <cstdio>
@@ -646,45 +645,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, NWM * NWN == 4 ? 2 : 1) void wgrad3
     }
 }
 
-// slab[split][r*3+s][co][ci] -> dW[co][ci][r][s] = sum over splits, in a fixed order (the blocks applied G^T themselves).
-// Block = 64 elements x 16 split lanes: the layers with few (co, ci) pairs are the ones with hundreds of splits, and one
-// thread per element would walk them serially (95 us per launch on average before, most of it latency).
-template <int WR_LANES>
-__global__ __launch_bounds__(WR_LANES == 1 ? 256 : 64 * WR_LANES) void wgrad_w43_reduce_kernel(const float* __restrict__ slabs,
-                                                                                              float* __restrict__ dw, int splits,
-                                                                                              int M, int Ncols) {
-  constexpr int EL = WR_LANES == 1 ? 256 : 64;   // elements per block
-  const long long plane = (long long)M * Ncols;
-  const long long total = 3 * plane;
-  const int el = threadIdx.x % EL, sl = threadIdx.x / EL;
-  __shared__ float red[3][WR_LANES][EL];
-  for (long long e0 = (long long)blockIdx.x * EL; e0 < total; e0 += (long long)gridDim.x * EL) {
-    const long long e = e0 + el;
-    const bool ok = e < total;
-    const int r = ok ? (int)(e / plane) : 0;
-    const long long mc = ok ? e - r * plane : 0;
-#pragma unroll
-    for (int f = 0; f < 3; ++f) {
-      float s = 0.f;
-      if (ok)
-        for (int k = sl; k < splits; k += WR_LANES) s += slabs[((size_t)k * 9 + r * 3 + f) * plane + mc];
-      red[f][sl][el] = s;
-    }
-    __syncthreads();
-    if (sl == 0 && ok) {
-      float* o = dw + (size_t)mc * 9 + r * 3;
-#pragma unroll
-      for (int f = 0; f < 3; ++f) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < WR_LANES; ++i) s += red[f][i][el];
-        o[f] = s;
-      }
-    }
-    __syncthreads();
-  }
-}
-
 namespace {
 
 struct WgW43Plan {
@@ -723,12 +683,8 @@ WgW43Plan plan_wg43(int N, int H, int W, int M, int Ncols) {
   p.nblocks = ceil_div(Ncols, p.BN);
   p.stages_total = N * p.tiles_y * p.tiles_x;
   const int target = gsd_env_int("GSD_WGRAD_BLOCKS", 512);
-  int splits = ceil_div(p.BM * p.BN > 64 * 32 ? target / 2 : target, p.mblocks * p.nblocks);   // one round of resident blocks
-  if (splits > p.stages_total) splits = p.stages_total;
-  if (splits > 2048) splits = 2048;
-  if (splits < 1) splits = 1;
-  p.splits = splits;
-  p.slab_elems = (int64_t)splits * 9 * M * Ncols;
+  p.splits = wgrad_pick_splits(p.BM * p.BN > 64 * 32 ? target / 2 : target, p.mblocks * p.nblocks, p.stages_total);   // one round of resident blocks
+  p.slab_elems = (int64_t)p.splits * 9 * M * Ncols;
   return p;
 }
 
@@ -751,21 +707,6 @@ int launch_wg43(const WgW43Params& P, dim3 g, size_t lds, hipStream_t st, bool a
 
 }  // namespace
 
-// 1: gsd_conv3x3_wgrad serves this shape with the Winograd form.  GSD_WGRAD_ALGO=0|1 forces one (tuning, A/B runs).
-int gsd_wgrad_w43_use(int N, int H, int W, int Cin, int Cout) {
-  const int forced = gsd_env_int("GSD_WGRAD_ALGO", -1);
-  if (forced == 0) return 0;
-  if (forced == 1) return 1;
-  return Cin >= 16 && Cout >= 16;   // the 3-channel first layer keeps the pixel-split direct kernel
-}
-
-// 1 when gsd_conv3x3_wgrad serves this shape with a kernel that takes a pitched dy (w_stride > W): the engine then lets
-// gsd_bn_bwd_apply write d_raw into a pitched buffer.
-extern "C" int gsd_conv3x3_wgrad_takes_pitched_dy(int N, int H, int W, int Cin, int Cout) {
-  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  return gsd_wgrad_w43_use(N, H, W, Cin, Cout);
-}
-
 // MFMA instructions of one launch: stages x 18 frequencies-rows x 16 tiles / 4 per (16 co x 16 ci) pair of the padded blocks
 int64_t gsd_wgrad_w43_mfma_count(int N, int H, int W, int Cin, int Cout) {
   const WgW43Plan p = plan_wg43(N, H, W, Cout, Cin);
@@ -774,44 +715,19 @@ int64_t gsd_wgrad_w43_mfma_count(int N, int H, int W, int Cin, int Cout) {
 
 int64_t gsd_wgrad_w43_workspace(int N, int H, int W, int Cin, int Cout) { return plan_wg43(N, H, W, Cout, Cin).slab_elems; }
 
-// slab[split][9][Cout][Cin] -> dW (Cout,Cin,3,3): the ordered split sum, shared with the 2-D form (gsd_wgrad_w2d.hip)
-int gsd_wgrad_w43_reduce_run(const float* workspace, float* dw, int splits, int Cout, int Cin, void* stream) {
-  const long long per = 3LL * Cout * Cin;
-  if (splits >= 64) {
-    const int rgrid = (int)(ceil_div64(per, 64) < 8192 ? ceil_div64(per, 64) : 8192);
-    hipLaunchKernelGGL(wgrad_w43_reduce_kernel<16>, dim3(rgrid), dim3(1024), 0, (hipStream_t)stream, workspace, dw, splits, Cout, Cin);
-  } else if (splits >= 8) {
-    const int rgrid = (int)(ceil_div64(per, 64) < 8192 ? ceil_div64(per, 64) : 8192);
-    hipLaunchKernelGGL(wgrad_w43_reduce_kernel<4>, dim3(rgrid), dim3(256), 0, (hipStream_t)stream, workspace, dw, splits, Cout, Cin);
-  } else {
-    const int rgrid = (int)(ceil_div64(per, 256) < 8192 ? ceil_div64(per, 256) : 8192);
-    hipLaunchKernelGGL(wgrad_w43_reduce_kernel<1>, dim3(rgrid), dim3(256), 0, (hipStream_t)stream, workspace, dw, splits, Cout, Cin);
-  }
-  GSD_LAUNCH_CHECK("gsd_conv3x3_wgrad (w43) reduce");
-  return GSD_OK;
-}
-
-// arguments already validated by gsd_conv3x3_wgrad
-int gsd_wgrad_w43_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, int Cout, float* dw, float* workspace,
-                      int64_t workspace_elems, int N, int H, int W, void* stream) {
+// arguments and workspace already validated by gsd_conv3x3_wgrad; returns the slab count
+int gsd_wgrad_w43_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, int Cout, float* workspace, int N, int H, int W,
+                      void* stream) {
   const WgW43Plan pl = plan_wg43(N, H, W, Cout, Cin);
-  GSD_REQUIRE(workspace_elems >= pl.slab_elems, GSD_ERR_WORKSPACE, "gsd_conv3x3_wgrad: workspace %lld < %lld elements",
-              (long long)workspace_elems, (long long)pl.slab_elems);
   WgW43Params P;
-  P.a0 = to_srcd(a[0]);
-  P.a1 = nsrc > 1 ? to_srcd(a[1]) : null_srcd();
-  P.dy = to_srcd(*dy);
-  P.slabs = workspace;
-  P.M = Cout; P.Ncols = Cin;
-  P.N = N; P.H = H; P.W = W;
+  wgrad_fill_common(P, a, nsrc, dy, Cin, Cout, workspace, N, H, W, pl.splits, pl.mblocks, pl.nblocks);
   P.TH = pl.TH; P.TW = pl.TW; P.TWq = pl.TWq; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;
   P.WR = pl.WR; P.WC = pl.WC; P.WCp = pl.WCp; P.XS = pl.XS;
-  P.stages_total = pl.stages_total; P.splits = pl.splits; P.mblocks = pl.mblocks; P.nblocks = pl.nblocks;
+  P.stages_total = pl.stages_total;
   GSD_REQUIRE(pl.WR * pl.WCp <= 256, GSD_ERR_UNSUPPORTED, "gsd_conv3x3_wgrad: halo window too large");
   const long grid = (long)pl.splits * pl.mblocks * pl.nblocks;
   // dy as aligned 16-byte pieces: rows, planes and images of the gradient buffer start 16-byte aligned
-  const bool ax4 = gsd_env_int("GSD_WG43_AX4", 1) != 0 && dy->w_stride % 4 == 0 && ((uintptr_t)dy->ptr & 15) == 0 &&
-                   dy->c_stride % 4 == 0 && dy->n_stride % 4 == 0 && pl.TW % 4 == 0;
+  const bool ax4 = gsd_env_int("GSD_WG43_AX4", 1) != 0 && wgrad_dy_x4(*dy) && pl.TW % 4 == 0;
   // activation windows as 16-byte pieces from the unaligned rows: every block's channels lie in one segment, the caller
   // vouches for 4 readable floats around each segment tensor (straddling pieces), at most 4 instructions per wave
   bool bx4 = gsd_env_int("GSD_WG43_BX4", 1) != 0 && ax4 && (nsrc == 1 || a[0].C % pl.BN == 0);
@@ -830,8 +746,7 @@ int gsd_wgrad_w43_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, in
   const int rr = (bx4 && gsd_env_int("GSD_WG43_RR", 1) != 0) ? (pl.TW == 16 && pl.TH == 4 ? 1 : (pl.TW == 8 && pl.TH == 8 ? 2 : 0)) : 0;
   const size_t img = (size_t)(pl.BM * (ax4 ? WG_DS_X4 : WG_DS) + (bx4 ? (pl.BN * (P.XS / 4) + 63) / 64 * 256 : pl.BN * P.XS)) * sizeof(float);
   const size_t lds = 2 * img;   // two images: a three-image ring with a half-stage stagger measured 2 % slower
-  bool plain = gsd_env_int("GSD_WG43_PLAIN", 1) != 0;   // no deferred BatchNorm / ReLU on any activation segment
-  for (int i = 0; i < nsrc; ++i) plain = plain && a[i].scale == nullptr && a[i].relu == 0;
+  const bool plain = gsd_env_int("GSD_WG43_PLAIN", 1) != 0 && wgrad_plain(a, nsrc);   // no deferred BatchNorm / ReLU on any activation segment
   if (gsd_env_set("GSD_WG43_TRACE"))   // tuning: one line per launch
     fprintf(stderr, "wg43 M%d N%d %dx%d B%d tile %dx%d stages %d splits %d blocks %ld BM %d BN %d ax4 %d bx4 %d rr %d plain %d lds %zu\n", Cout,
             Cin, H, W, N, pl.TH, pl.TW, pl.stages_total, pl.splits, grid, pl.BM, pl.BN, (int)ax4, (int)bx4, rr, (int)plain, lds);
@@ -841,5 +756,5 @@ int gsd_wgrad_w43_run(const gsd_src* a, int nsrc, const gsd_src* dy, int Cin, in
               : pl.BN == 64 ? launch_wg43<2, 4>(P, g, lds, st, ax4, bx4, rr, plain)
                             : launch_wg43<2, 2>(P, g, lds, st, ax4, bx4, rr, plain))
     return e;
-  return gsd_wgrad_w43_reduce_run(workspace, dw, pl.splits, Cout, Cin, stream);
+  return pl.splits;
 }

@@ -138,7 +138,10 @@ def test_conv3x3_deferred_bn_two_segments_and_crop(gsd, algo, c0, c1, co):
 
 
 @pytest.mark.parametrize("n,ci,co,h,w", [(2, 5, 7, 9, 11), (1, 64, 64, 21, 29), (2, 20, 130, 6, 70), (1, 3, 16, 40, 53),
-                                         (2, 16, 16, 1, 1), (1, 16, 32, 2, 3), (1, 32, 16, 3, 70), (3, 16, 200, 1, 130)])
+                                         (2, 16, 16, 1, 1), (1, 16, 32, 2, 3), (1, 32, 16, 3, 70), (3, 16, 200, 1, 130),
+                                         # the direct form's other two blocks: <2,2> (Cin < 16, Cout > 64) and the wide one that is
+                                         # not split over the waves (Cout < 16, Cin > 16)
+                                         (2, 5, 130, 9, 11), (2, 40, 8, 9, 11)])
 def test_conv3x3_wgrad(gsd, n, ci, co, h, w):
     from oracle import unet_numpy as on
     rng = np.random.default_rng(ci * 31 + co)

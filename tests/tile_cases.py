@@ -4,7 +4,7 @@ not collected; it imports neither torch nor the library.
 
 The restatements follow the host code line by line -- plan_w2d (gsd_conv3x3_w2d.hip), plan_w43 (gsd_conv3x3_w43.hip), choose_tile /
 plan_conv3x3 (gsd_conv3x3.hip), plan_wg43 (gsd_wgrad_w43.hip), plan_wg2d (gsd_wgrad_w2d.hip), choose_wgrad_tile / plan_wgrad
-(gsd_wgrad.hip) -- including their force knobs, read from `env` (default: the process environment, as the library reads it on
+(gsd_wgrad.hip: the direct dW form), wgrad_pick_splits (gsd_wgrad_host.h: _splits here) -- including their force knobs, read from `env` (default: the process environment, as the library reads it on
 every call).  tests/test_tile_form_coverage_cpu.py holds them to the library over a grid of shapes through the ABI's queries, and
 proves through them that the tables below reach every form.
 
@@ -244,7 +244,7 @@ def choose_wgrad_tile(h: int, w: int):
 
 
 def wgrad_direct_slab_elems(n: int, h: int, w: int, m: int, ncols: int, env=None) -> int:
-    """plan_wgrad(mode 0).slab_elems: the direct-tap dW form."""
+    """plan_wgrad(...).slab_elems: the direct-tap dW form."""
     wide = m <= 64
     ksplit = wide and ncols <= 16
     bnw = 16 if ksplit else (64 if wide else 32)
