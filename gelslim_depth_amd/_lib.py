@@ -83,6 +83,7 @@ class gsd_mesh_view(C.Structure):
 
 GSD_MESH_RECORD_FLOATS = 12   # floats per triangle record of gsd_mesh_depth_count
 GSD_POSE_ROW = 5              # doubles per row of gsd_mesh_pose_score: sum_sq, sum_abs, inter, n_rendered, n_observed
+GSD_POSE_WIDTHS_MAX = 32      # widths per observation of gsd_mesh_pose_score_widths
 
 
 class gsd_augment_draw(C.Structure):
@@ -202,6 +203,9 @@ SIGNATURES = {
     "gsd_mesh_pose_score_workspace": (_L, [_I, _I, _I, _I, _I]),
     "gsd_mesh_pose_score": (_I, [C.POINTER(gsd_mesh_grid), C.POINTER(gsd_mesh_view), _P, _I, _P, _P, _L, _P, _I, _P, _P, _I, _I, _I,
                                  _I, _F, _P, _P, _L, _P]),
+    "gsd_mesh_pose_score_widths_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
+    "gsd_mesh_pose_score_widths": (_I, [C.POINTER(gsd_mesh_grid), C.POINTER(gsd_mesh_view), _P, _I, _P, _P, _L, _P, _I, _P, _P, _I, _I,
+                                        _I, _I, _I, _F, _P, _P, _L, _P]),
     "gsd_guard_snapshot": (_I, [_P, _P, _L, _P]),
     "gsd_guard_restore": (_I, [_GUARD, _P, _P, _L, _P]),
     "gsd_adam_ema": (_I, [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _GUARD, _P]),

@@ -31,6 +31,11 @@
 //   pose score (gsd_mesh_pose_score): the same per-pixel function (md_pixel) on a lattice of pixels,
 //   compared with an observed image in registers and reduced to five doubles per candidate pose: tile partials are stored and
 //   summed by a second kernel in a fixed order, so a row is reproducible and does not depend on its batch.
+//
+//   pose score over G widths (gsd_mesh_pose_score_widths): md_pixel = md_depth(md_surface(pose), g/2), and
+//   only md_surface is expensive.  A thread finds its point's surface value once and forms the G depths, errors and contact
+//   predicates from it; the G rows are reduced in the same order as the single one, so row (b, p, k) has the bits of
+//   gsd_mesh_pose_score at the width widths[b][k].
 #include "gsd_common.h"
 
 #include <math.h>
@@ -206,12 +211,13 @@ struct MdView {
   long long list_elems;
 };
 
-// The depth of pixel (r, c) of one finger under the pose-table row `row`: the float mesh_render stores, and the R that
-// mesh_pose_score compares -- both call this, so a scored candidate has the bits of its rendered image.
-__device__ __forceinline__ float md_pixel(const MdGrid& G, const MdView& V, const float* __restrict__ rec, const int* __restrict__ start,
-                                          const int* __restrict__ list, const float* __restrict__ row, int r, int c, bool right) {
+// The surface under pixel (r, c) of one finger under the pose-table row `row`: m = the max of sg * q over the triangles that
+// cover the pixel, -inf where none does.  Everything expensive (the pixel -> mesh map, the cell lookup, the walk) is here and
+// depends on the pose alone; the width enters in md_depth.
+__device__ __forceinline__ float md_surface(const MdGrid& G, const MdView& V, const float* __restrict__ rec, const int* __restrict__ start,
+                                            const int* __restrict__ list, const float* __restrict__ row, int r, int c, bool right) {
 #pragma clang fp contract(off)
-  const float cs = row[0], sn = row[1], t1 = row[2], t2 = row[3], hg = row[4];
+  const float cs = row[0], sn = row[1], t1 = row[2], t2 = row[3];
   // pixel -> transformed in-plane point: u along the unaligned axis (mirrored for the left finger), v along the aligned one
   const float u = V.mpp * ((float)r - 0.5f * (float)V.H), v = V.mpp * ((float)c - 0.5f * (float)V.W);
   const float uu = right ? u : -u;
@@ -247,11 +253,24 @@ __device__ __forceinline__ float md_pixel(const MdGrid& G, const MdView& V, cons
       for (int k = 0; k < MD_WALK; ++k) m = fmaxf(m, md_cover(tri[k], x, y, sg));
     }
   }
-  // right: -max(0, Qmax - g/2); left: min(0, Qmin + g/2) = -max(0, -Qmin - g/2); nothing covering: m = -inf gives 0
+  return m;
+}
+
+// The depth of a surface value m (md_surface) at the half-width hg:
+// right: -max(0, Qmax - g/2); left: min(0, Qmin + g/2) = -max(0, -Qmin - g/2); nothing covering: m = -inf gives 0
+__device__ __forceinline__ float md_depth(float m, float hg) {
+#pragma clang fp contract(off)
   float d = -fmaxf(0.f, m - hg);
   d = d == 0.f ? 0.f : d;                    // no negative zero
   if (!(hg == hg)) d = hg;                   // refused width: NaN
   return d;
+}
+
+// The depth of pixel (r, c) of one finger under the pose-table row `row`: the float mesh_render stores, and the R that
+// mesh_pose_score compares -- both call this, so a scored candidate has the bits of its rendered image.
+__device__ __forceinline__ float md_pixel(const MdGrid& G, const MdView& V, const float* __restrict__ rec, const int* __restrict__ start,
+                                          const int* __restrict__ list, const float* __restrict__ row, int r, int c, bool right) {
+  return md_depth(md_surface(G, V, rec, start, list, row, r, c, right), row[4]);
 }
 
 __global__ __launch_bounds__(256) void mesh_render(const MdGrid G, const MdView V, const float* __restrict__ rec,
@@ -346,6 +365,121 @@ __global__ __launch_bounds__(64) void mesh_pose_rows(const double* __restrict__ 
   if (lane == 0) {
 #pragma unroll
     for (int q = 0; q < MD_ROW; ++q) rows[(size_t)n * MD_ROW + q] = hg == hg ? tot[q] : (double)hg;
+  }
+}
+
+// ---- pose score over many widths per render -------------------------------------------------------------
+constexpr int MD_WIDTHS = GSD_POSE_WIDTHS_MAX;
+
+// half-width k of observation b, entry b * G + k: the expression of mesh_pose_table's row[4]
+__global__ __launch_bounds__(256) void mesh_pose_half_widths(const float* __restrict__ widths, int n, float width_offset,
+                                                             float* __restrict__ half) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float g = widths[i] + width_offset;
+  half[i] = (g >= 0.f && isfinite(g)) ? 0.5f * g : __builtin_nanf("");
+}
+
+// wave_sum_d for CH values at once (CH = 2, 4): the same tree -- lane l meets l ^ 32, then l ^ 16, ... -- but while more than one
+// value is left an exchange halves them: a lane keeps the half that its bit selects and sends the other, so both lanes add the
+// pair of terms that wave_sum_d adds (a + b and b + a are the same bits).  Afterwards v[0] of lane l is the wave's sum of value
+// l / (64 / CH), bit for bit what wave_sum_d gives, for fewer exchanges: CH = 4 costs 2 + 1 + 4 of them instead of 4 * 6.
+template <int CH>
+__device__ __forceinline__ void md_wave_sums(double (&v)[CH], int lane) {
+#pragma clang fp contract(off)
+  int o = 32;
+#pragma unroll
+  for (int n = CH; n > 1; n >>= 1, o >>= 1) {
+    const bool hi = (lane & o) != 0;
+#pragma unroll
+    for (int j = 0; j < n / 2; ++j) {
+      const double keep = hi ? v[j + n / 2] : v[j], send = hi ? v[j] : v[j + n / 2];
+      v[j] = keep + __shfl_xor(send, o, 64);
+    }
+  }
+  for (; o > 0; o >>= 1) v[0] += __shfl_xor(v[0], o, 64);
+}
+
+// mesh_pose_score for NW widths per candidate: the same block, wave and thread shape, one md_surface and one D per thread, then
+// per width the tail md_depth, e, e^2, |e| and the contact predicates exactly as mesh_pose_score forms them.  Widths are taken CH
+// at a time (the last group repeats width NW - 1 and drops the repeats); the wave sums come from md_wave_sums, the counts from
+// ballots, the four waves meet as (w0 + w1) + (w2 + w3) through LDS.  The block stores NW partial rows, blockIdx.x * NW + k.
+template <int CH>
+__global__ __launch_bounds__(256) void mesh_pose_score_widths(const MdGrid G, const MdView V, const MdLattice S, int NW,
+                                                              const float* __restrict__ rec, const int* __restrict__ start,
+                                                              const int* __restrict__ list, const float* __restrict__ table,
+                                                              const float* __restrict__ half, const float* __restrict__ observed,
+                                                              double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  int b = blockIdx.x;
+  const int tx = b % S.tiles_x;
+  b /= S.tiles_x;
+  const int ty = b % S.tiles_y;
+  const int img = b / S.tiles_y;            // (observation * P + candidate) * 2 + channel
+  const int n = img >> 1, ch = img & 1;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
+  const int j = tx * 16 + (wave & 1) * 8 + (lane & 7);
+  const bool on = i < S.rows && j < S.cols;   // a point off the lattice adds zeros; every thread reaches the reductions
+  float m = 0.f, D = 0.f;
+  if (on) {
+    const int r = S.off + i * S.stride, c = S.off + j * S.stride;       // < H, < W: no overflow
+    const bool right = (ch == 1) != (V.lr_flip != 0);
+    m = md_surface(G, V, rec, start, list, table + (size_t)n * MD_POSE, r, c, right);
+    D = observed[(((size_t)(n / S.P) * 2 + ch) * V.H + r) * V.W + c];
+  }
+  const bool cd = on && D < -S.contact && isfinite(D);     // a non-finite D is not contact
+  const int n_d = __popcll(__ballot(cd));
+  const float* hw = half + (size_t)(n / S.P) * NW;
+  __shared__ double red[4][MD_WIDTHS][MD_ROW];
+  for (int k0 = 0; k0 < NW; k0 += CH) {
+    double sq[CH], ab[CH];
+    int n_i[CH], n_r[CH];
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+      const float R = md_depth(m, hw[min(k0 + u, NW - 1)]);
+      const double e = (double)R - (double)D;
+      sq[u] = on ? e * e : 0.0;
+      ab[u] = on ? fabs(e) : 0.0;
+      const bool cr = on && R < -S.contact;
+      n_i[u] = __popcll(__ballot(cr && cd)), n_r[u] = __popcll(__ballot(cr));
+    }
+    md_wave_sums<CH>(sq, lane);
+    md_wave_sums<CH>(ab, lane);
+#pragma unroll
+    for (int u = 0; u < CH; ++u)
+      if (lane == u * (64 / CH) && k0 + u < NW) {
+        double* w = red[wave][k0 + u];
+        w[0] = sq[0], w[1] = ab[0], w[2] = (double)n_i[u], w[3] = (double)n_r[u], w[4] = (double)n_d;
+      }
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < NW * MD_ROW; t += 256) {
+    const int k = t / MD_ROW, q = t - k * MD_ROW;
+    partial[((size_t)blockIdx.x * NW + k) * MD_ROW + q] = (red[0][k][q] + red[1][k][q]) + (red[2][k][q] + red[3][k][q]);
+  }
+}
+
+// mesh_pose_rows for one (candidate, width) per wave, block n * NW + k: the same lane order over that pair's partial rows.
+__global__ __launch_bounds__(64) void mesh_pose_rows_widths(const double* __restrict__ partial, int tpc, int NW, int P,
+                                                            const float* __restrict__ half, double* __restrict__ rows) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.x / NW, k = blockIdx.x - n * NW, lane = threadIdx.x;
+  double tot[MD_ROW];
+#pragma unroll
+  for (int q = 0; q < MD_ROW; ++q) tot[q] = 0.0;
+  for (int t = lane; t < tpc; t += 64) {
+    const double* p = partial + (((size_t)n * tpc + t) * NW + k) * MD_ROW;
+#pragma unroll
+    for (int q = 0; q < MD_ROW; ++q) tot[q] += p[q];
+  }
+#pragma unroll
+  for (int q = 0; q < MD_ROW; ++q) tot[q] = wave_sum_d(tot[q]);
+  const float hg = half[(size_t)(n / P) * NW + k];
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < MD_ROW; ++q) rows[(size_t)blockIdx.x * MD_ROW + q] = hg == hg ? tot[q] : (double)hg;
   }
 }
 
@@ -538,5 +672,86 @@ extern "C" int gsd_mesh_pose_score(const gsd_mesh_grid* grid, const gsd_mesh_vie
   hipLaunchKernelGGL(mesh_pose_rows, dim3((unsigned)N), dim3(64), 0, st, (const double*)partial, (int)(blocks / N), (const float*)table,
                      rows);
   GSD_LAUNCH_CHECK("gsd_mesh_pose_score rows");
+  return GSD_OK;
+}
+
+// doubles: the pose table (8 floats a row) | the half-widths (B x G floats, rounded up to whole doubles) | G partial rows per block
+extern "C" int64_t gsd_mesh_pose_score_widths_workspace(int B, int P, int G, int H, int W, int stride) {
+  const int64_t blocks = md_score_blocks(B, P, H, W, stride);
+  if (blocks < 0 || blocks > INT32_MAX || G < 1 || G > MD_WIDTHS || (int64_t)B * P * G > INT32_MAX) return 0;
+  return (int64_t)B * P * (MD_POSE / 2) + ((int64_t)B * G + 1) / 2 + blocks * G * MD_ROW;
+}
+
+extern "C" int gsd_mesh_pose_score_widths(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
+                                          const int32_t* cells, const int32_t* list, int64_t list_elems, const float* observed, int B,
+                                          const float* candidates, const float* widths, int P, int G, int H, int W, int stride,
+                                          float contact_depth, double* rows, double* workspace, int64_t workspace_elems, void* stream) {
+  if (md_check_grid(grid, "gsd_mesh_pose_score_widths")) return GSD_ERR_BAD_ARG;
+  GSD_REQUIRE(view && records && cells && list && observed && candidates && widths && rows && workspace, GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score_widths: null pointer");
+  GSD_REQUIRE(T >= 1 && T <= MD_MAX_T, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: %d triangles, 1..%d", T, MD_MAX_T);
+  GSD_REQUIRE(B >= 1 && P >= 1 && H >= 1 && W >= 1, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: bad dims B=%d P=%d H=%d W=%d", B, P,
+              H, W);
+  GSD_REQUIRE(G >= 1 && G <= MD_WIDTHS, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: %d widths per observation, 1..%d", G, MD_WIDTHS);
+  GSD_REQUIRE(stride >= 1, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: stride %d must be at least 1", stride);
+  GSD_REQUIRE(isfinite(contact_depth) && contact_depth >= 0.f, GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score_widths: contact_depth %g must be finite and >= 0", (double)contact_depth);
+  GSD_REQUIRE(list_elems >= 1 && list_elems <= INT32_MAX, GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score_widths: list of %lld entries, 1..2^31-1", (long long)list_elems);
+  GSD_REQUIRE(isfinite(view->mpp) && view->mpp > 0.f && isfinite(view->width_offset), GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score_widths: mm per pixel %g must be finite and positive, the width offset %g finite", (double)view->mpp,
+              (double)view->width_offset);
+  GSD_REQUIRE(view->reserved == 0, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: the reserved word must be 0");
+  GSD_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)rows & 7) == 0 && ((uintptr_t)workspace & 7) == 0, GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score_widths: records must be 16-byte aligned, rows and workspace 8-byte aligned");
+  const int64_t blocks = md_score_blocks(B, P, H, W, stride);
+  GSD_REQUIRE(blocks >= 0 && blocks <= INT32_MAX && (int64_t)B * P * G <= INT32_MAX, GSD_ERR_BAD_ARG,
+              "gsd_mesh_pose_score_widths: %lld blocks (B=%d x P=%d of %d x %d, stride %d) and %lld rows, at most 2^31-1 per launch",
+              (long long)blocks, B, P, H, W, stride, (long long)B * P * G);
+  const int64_t need = gsd_mesh_pose_score_widths_workspace(B, P, G, H, W, stride);
+  GSD_REQUIRE(workspace_elems >= need, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: workspace of %lld doubles, need %lld",
+              (long long)workspace_elems, (long long)need);
+  const int N = B * P;
+  const hipStream_t st = (hipStream_t)stream;
+  float* table = reinterpret_cast<float*>(workspace);
+  float* half = reinterpret_cast<float*>(workspace + (int64_t)N * (MD_POSE / 2));
+  double* partial = workspace + (int64_t)N * (MD_POSE / 2) + ((int64_t)B * G + 1) / 2;
+  // G > 1: the pose table's own width column is not read (per = N: every row takes widths[0]).  G = 1: widths is
+  // gsd_mesh_pose_score's B floats, and the call is that one's three launches
+  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, candidates, widths, N, G == 1 ? P : N,
+                     view->width_offset, table);
+  GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths pose table");
+  if (G > 1) {
+    hipLaunchKernelGGL(mesh_pose_half_widths, dim3((unsigned)ceil_div(B * G, 256)), dim3(256), 0, st, widths, B * G, view->width_offset,
+                       half);
+    GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths half-widths");
+  }
+  MdView V;
+  V.mpp = view->mpp, V.cx = grid->cx, V.cy = grid->cy;
+  V.swap_axes = view->swap_axes != 0, V.invert = view->invert_affine != 0, V.lr_flip = view->lr_flip != 0;
+  V.H = H, V.W = W, V.tiles_x = ceil_div(W, 16), V.tiles_y = ceil_div(H, 16), V.T = T, V.list_elems = list_elems;
+  MdLattice S;
+  S.stride = stride, S.off = stride / 2, S.rows = md_lattice_len(H, stride), S.cols = md_lattice_len(W, stride);
+  S.tiles_x = ceil_div(S.cols, 16), S.tiles_y = ceil_div(S.rows, 16), S.P = P, S.contact = contact_depth;
+  if (G == 1) {
+    if (blocks > 0) {
+      hipLaunchKernelGGL(mesh_pose_score, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), V, S, records, cells + 2, list,
+                         (const float*)table, observed, partial);
+      GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths");
+    }
+    hipLaunchKernelGGL(mesh_pose_rows, dim3((unsigned)N), dim3(64), 0, st, (const double*)partial, (int)(blocks / N),
+                       (const float*)table, rows);
+    GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths rows");
+    return GSD_OK;
+  }
+  if (blocks > 0) {      // a stride that leaves no lattice point: every row is five zeros
+    const auto kernel = G == 2 ? mesh_pose_score_widths<2> : mesh_pose_score_widths<4>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), V, S, G, records, cells + 2, list,
+                       (const float*)table, (const float*)half, observed, partial);
+    GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths");
+  }
+  hipLaunchKernelGGL(mesh_pose_rows_widths, dim3((unsigned)(N * G)), dim3(64), 0, st, (const double*)partial, (int)(blocks / N), G, P,
+                     (const float*)half, rows);
+  GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths rows");
   return GSD_OK;
 }

@@ -473,6 +473,78 @@ def score_poses(grid: MeshGrid, observed: torch.Tensor, candidates: torch.Tensor
     return out
 
 
+POSE_WIDTHS_MAX = L.GSD_POSE_WIDTHS_MAX      # widths per observation that one `score_poses_widths` call takes
+
+
+def score_poses_widths(grid: MeshGrid, observed: torch.Tensor, candidates: torch.Tensor, widths: torch.Tensor,
+                       image_height_mm: float = 12.0, grasp_width_offset: float = 0.0, LR_flip: bool = False,
+                       invert_affine: bool = False, stride: int = 1, contact_depth: float = 0.0, out: Optional[torch.Tensor] = None,
+                       validate: bool = True) -> torch.Tensor:
+    """`score_poses` for G grasp widths per observation at the price of one render per candidate: rows
+    (B, P, G, 5) float64 with rows[b, p, k] THE SAME BITS as score_poses(...)[b, p] at the width widths[b, k] -- `widths` is a
+    (B, G) float32 tensor on the device, 1 <= G <= POSE_WIDTHS_MAX.  The width enters a pixel's depth in its last step only,
+    d = -max(0, m - g/2), so one libgsd call (gsd_mesh_pose_score_widths) finds every lattice point's surface value m once and
+    reduces G rows from it.  Every other argument is `score_poses`'.
+
+    `validate=True` reads the smallest width + offset back once and raises MeshDepthError for a negative or non-finite one;
+    `validate=False` reads nothing, and such a (b, :, k) column is five NaN per row (+inf for `pose_cost`)."""
+    if not isinstance(grid, MeshGrid):
+        raise MeshDepthError(f"score_poses_widths: grid must be a MeshGrid, got {type(grid).__name__}")
+    for name, t, shape in (("observed", observed, "(B, 2, H, W)"), ("candidates", candidates, "(B, P, 3) or (P, 3)"),
+                           ("widths", widths, "(B, G)")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
+            raise MeshDepthError(f"score_poses_widths: {name} must be a float32 {shape} tensor on the GPU, got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')}")
+        if t.device != grid.device:
+            raise MeshDepthError(f"score_poses_widths: {name} is on {t.device}, the mesh on {grid.device}")
+    if observed.dim() != 4 or observed.shape[1] != 2 or min(observed.shape) < 1:
+        raise MeshDepthError(f"score_poses_widths: observed must be (B, 2, H, W) with B, H, W >= 1, got {tuple(observed.shape)}")
+    b, _, h, w = (int(d) for d in observed.shape)
+    if candidates.dim() == 2:
+        candidates = candidates.unsqueeze(0).expand(b, -1, -1)
+    if candidates.dim() != 3 or candidates.shape[0] != b or candidates.shape[2] != 3 or candidates.shape[1] < 1:
+        raise MeshDepthError(f"score_poses_widths: candidates must be ({b}, P, 3) or (P, 3) with P >= 1, got {tuple(candidates.shape)}")
+    p = int(candidates.shape[1])
+    if widths.dim() != 2 or widths.shape[0] != b or not 1 <= widths.shape[1] <= POSE_WIDTHS_MAX:
+        raise MeshDepthError(f"score_poses_widths: widths must be ({b}, G) with 1 <= G <= {POSE_WIDTHS_MAX}, got {tuple(widths.shape)}")
+    g = int(widths.shape[1])
+    observed, candidates, widths = observed.contiguous(), candidates.contiguous(), widths.contiguous()
+    mpp = float(image_height_mm) / h
+    if not (math.isfinite(mpp) and mpp > 0.0):
+        raise MeshDepthError(f"score_poses_widths: image_height_mm {image_height_mm!r} must be finite and positive")
+    offset = float(grasp_width_offset)
+    if not math.isfinite(offset):
+        raise MeshDepthError(f"score_poses_widths: grasp_width_offset must be finite, got {grasp_width_offset!r}")
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
+        raise MeshDepthError(f"score_poses_widths: stride must be an integer >= 1, got {stride!r}")
+    depth = float(contact_depth)
+    if not (math.isfinite(depth) and depth >= 0.0):
+        raise MeshDepthError(f"score_poses_widths: contact_depth must be finite and >= 0, got {contact_depth!r}")
+    if out is None:
+        out = torch.empty((b, p, g, POSE_ROW), device=grid.device, dtype=torch.float64)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != grid.device or not out.is_contiguous()
+          or tuple(out.shape) != (b, p, g, POSE_ROW)):
+        raise MeshDepthError(f"score_poses_widths: out must be a contiguous float64 ({b}, {p}, {g}, {POSE_ROW}) tensor on {grid.device}")
+    words = int(lib.gsd_mesh_pose_score_widths_workspace(b, p, g, h, w, int(stride)))
+    if words < 1:
+        raise MeshDepthError(f"score_poses_widths: {b} x {p} candidates x {g} widths of {h} x {w} at stride {stride} are more than "
+                             "one launch takes (2^31 - 1 blocks or rows): score them in parts")
+    if validate:
+        g_min = float((widths + offset).min())          # NaN propagates through min
+        if not (g_min >= 0.0) or not bool(torch.isfinite(widths).all()):
+            raise MeshDepthError(f"score_poses_widths: grasp width + offset must be finite and >= 0, the smallest is {g_min!r}")
+    view = L.gsd_mesh_view()
+    view.mpp, view.width_offset = mpp, offset
+    view.swap_axes, view.invert_affine, view.lr_flip, view.reserved = grid.swap_axes, int(bool(invert_affine)), int(bool(LR_flip)), 0
+    with torch.cuda.device(grid.device):
+        ws = torch.empty((words,), device=grid.device, dtype=torch.float64)
+        check(lib.gsd_mesh_pose_score_widths(C.byref(grid.grid), C.byref(view), grid.records.data_ptr(), grid.triangles,
+                                             grid.cells.data_ptr(), grid.list.data_ptr(), grid.list.numel(), observed.data_ptr(), b,
+                                             candidates.data_ptr(), widths.data_ptr(), p, g, h, w, int(stride), depth,
+                                             out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr()), "mesh_pose_score_widths")
+    return out
+
+
 _COSTS = ("mse", "l1", "iou")
 
 
@@ -543,12 +615,38 @@ def search_schedule(half_span: Sequence[float], counts: Sequence[int] = (7, 7, 9
     return np.stack(spans), np.stack(offsets)
 
 
+def width_schedule(width_half_span: float, width_count: int, levels: int = 4) -> Tuple[np.ndarray, np.ndarray]:
+    """`search_schedule` for the fourth axis of `estimate_pose`, the grasp width [mm], on the host in fp32: (half_spans
+    (levels + 1,), offsets (levels, n)).  Level l has the half-span half_spans[l] and the step half_spans[l + 1] =
+    2 * half_spans[l] / (n - 1); its width k lies offsets[l, k] = (k - (n - 1) / 2) * step from the centre, so the middle offset
+    is exactly 0.  n = `width_count` is odd and >= 3, `width_half_span` finite and > 0."""
+    n = width_count
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 3 or n % 2 == 0 or n > POSE_WIDTHS_MAX:
+        raise MeshDepthError(f"estimate_pose: width_count must be 1 or an odd integer in 3..{POSE_WIDTHS_MAX}, got {width_count!r}")
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1:
+        raise MeshDepthError(f"estimate_pose: levels must be an integer >= 1, got {levels!r}")
+    try:
+        half = np.float32(width_half_span)
+    except (TypeError, ValueError):
+        half = np.float32("nan")
+    if half.shape != () or not np.isfinite(half) or not half > 0:
+        raise MeshDepthError(f"estimate_pose: width_half_span must be a finite value > 0 [mm] for a width axis, got {width_half_span!r}")
+    spans, offsets = [half], []
+    for _ in range(int(levels)):
+        step = (np.float32(2.0) * spans[-1]) / np.float32(n - 1)
+        offsets.append((np.arange(n, dtype=np.float32) - np.float32((n - 1) // 2)) * step)
+        spans.append(step)
+    return np.asarray(spans, dtype=np.float32), np.stack(offsets).astype(np.float32)
+
+
 class PoseEstimate:
     """What `estimate_pose` found, all tensors on the device: `pose` (B, 3) fp32 = (t1 [m], t2 [m], theta [rad]), `cost` (B,)
-    fp64 and `row` (B, 5) fp64 of that pose at the last level's stride, `trace` (levels, B) fp64, the best cost of every level."""
+    fp64 and `row` (B, 5) fp64 of that pose at the last level's stride, `trace` (levels, B) fp64, the best cost of every level,
+    `width` (B,) fp32 [mm], the grasp width that `row` was scored at: the one passed in, or the width axis' winner."""
 
-    def __init__(self, pose: torch.Tensor, cost: torch.Tensor, row: torch.Tensor, trace: torch.Tensor) -> None:
-        self.pose, self.cost, self.row, self.trace = pose, cost, row, trace
+    def __init__(self, pose: torch.Tensor, cost: torch.Tensor, row: torch.Tensor, trace: torch.Tensor,
+                 width: Optional[torch.Tensor] = None) -> None:
+        self.pose, self.cost, self.row, self.trace, self.width = pose, cost, row, trace, width
 
     def __repr__(self) -> str:
         return f"PoseEstimate({self.pose.shape[0]} observations, {self.trace.shape[0]} levels)"
@@ -557,7 +655,8 @@ class PoseEstimate:
 def estimate_pose(grid: MeshGrid, observed: torch.Tensor, grasp_widths: torch.Tensor, init, half_span: Sequence[float],
                   counts: Sequence[int] = (7, 7, 9), levels: int = 4, strides: Optional[Sequence[int]] = None, cost="mse",
                   image_height_mm: float = 12.0, grasp_width_offset: float = 0.0, LR_flip: bool = False,
-                  invert_affine: bool = False, contact_depth: float = 0.0, validate: bool = True) -> PoseEstimate:
+                  invert_affine: bool = False, contact_depth: float = 0.0, validate: bool = True, width_half_span: float = 0.0,
+                  width_count: int = 1) -> PoseEstimate:
     """The planar pose (t1, t2, theta) of `grid`'s mesh in the hand from depth images `observed` (B, 2, H, W) -- a prediction of the
     net or a label -- and the grasp widths: a coarse-to-fine lattice search, render-and-compare through `score_poses`.
 
@@ -569,13 +668,30 @@ def estimate_pose(grid: MeshGrid, observed: torch.Tensor, grasp_widths: torch.Te
     +inf, which never beats a finite cost.  The next level is centred on the winner with half-span = this level's step.  Because
     a row does not depend on its batch, the best cost cannot rise from one level to the next at an equal stride.
 
+    An unknown grasp width: `width_count` = n_w odd and >= 3 with `width_half_span` > 0 [mm] adds the width
+    as a fourth axis.  `grasp_widths` is then the starting width; level l scores every pose candidate at the n_w widths
+    centre_w + (k - (n_w - 1) / 2) * step_w (`width_schedule`; one fp32 add, the middle width IS the centre) through
+    `score_poses_widths` -- one render per pose candidate, whatever n_w -- and the winner is the least cost over the flat index
+    pose_flat * n_w + k, under the same tie rule.  A lattice width whose g falls below 0 is a NaN row, hence +inf.  The default,
+    `width_count` = 1 (`width_half_span` is then ignored), is the fixed-width search above, call for call.  `PoseEstimate.width`
+    is the width of the winner.
+
     Everything runs on the device; nothing is read back (with `validate=True`, `score_poses`' one check of the widths is made
-    once, before the first level).  The view arguments are `score_poses`'."""
+    once, before the first level -- of the starting widths, with a width axis).  The view arguments are `score_poses`'."""
     spans, offsets = search_schedule(half_span, counts, levels)
     levels = int(levels)
     strides = (1,) * levels if strides is None else tuple(strides)
     if len(strides) != levels or any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) or s < 1 for s in strides):
         raise MeshDepthError(f"estimate_pose: strides must be {levels} integers >= 1, one per level, got {strides!r}")
+    try:
+        w_half = float(width_half_span)
+    except (TypeError, ValueError):
+        w_half = float("nan")
+    if not (math.isfinite(w_half) and w_half >= 0.0):
+        raise MeshDepthError(f"estimate_pose: width_half_span must be finite and >= 0 [mm], got {width_half_span!r}")
+    width_axis = not (isinstance(width_count, (int, np.integer)) and not isinstance(width_count, bool) and width_count == 1)
+    if width_axis:
+        _, w_offsets = width_schedule(width_half_span, width_count, levels)          # raises for an even count, 2, a zero span
     if not isinstance(grid, MeshGrid):
         raise MeshDepthError(f"estimate_pose: grid must be a MeshGrid, got {type(grid).__name__}")
     if not isinstance(observed, torch.Tensor) or observed.dim() != 4:
@@ -587,21 +703,41 @@ def estimate_pose(grid: MeshGrid, observed: torch.Tensor, grasp_widths: torch.Te
     if tuple(centre.shape) != (b, 3):
         raise MeshDepthError(f"estimate_pose: init must be ({b}, 3) or (3,), got {tuple(centre.shape)}")
     centre = centre.contiguous()
+    if width_axis:
+        if (not isinstance(grasp_widths, torch.Tensor) or grasp_widths.dtype != torch.float32 or grasp_widths.device != grid.device
+                or tuple(grasp_widths.shape) != (b,)):
+            raise MeshDepthError(f"estimate_pose: grasp_widths must be a float32 ({b},) tensor on {grid.device}")
+        if validate:
+            g_min = float((grasp_widths + float(grasp_width_offset)).min())          # NaN propagates through min
+            if not (g_min >= 0.0) or not bool(torch.isfinite(grasp_widths).all()):
+                raise MeshDepthError(f"estimate_pose: grasp width + offset must be finite and >= 0, the smallest is {g_min!r}")
     with torch.cuda.device(grid.device):
         offs = torch.from_numpy(offsets).to(grid.device)          # (levels, P, 3)
         trace = torch.empty((levels, b), device=grid.device, dtype=torch.float64)
         best_cost = best_row = None
+        if width_axis:
+            w_offs = torch.from_numpy(w_offsets).to(grid.device)          # (levels, n_w)
+            n_w = int(w_offs.shape[1])
+            centre_w = grasp_widths.contiguous()
         for lvl in range(levels):
             cand = (centre.unsqueeze(1) + offs[lvl].unsqueeze(0)).contiguous()          # one fp32 add: the middle one is the centre
-            rows = score_poses(grid, observed, cand, grasp_widths, image_height_mm, grasp_width_offset, LR_flip, invert_affine,
-                               strides[lvl], contact_depth, validate=validate and lvl == 0)
+            if width_axis:
+                cand_w = (centre_w.unsqueeze(1) + w_offs[lvl].unsqueeze(0)).contiguous()          # (B, n_w), the same rule
+                rows = score_poses_widths(grid, observed, cand, cand_w, image_height_mm, grasp_width_offset, LR_flip, invert_affine,
+                                          strides[lvl], contact_depth, validate=False).reshape(b, -1, POSE_ROW)
+            else:
+                rows = score_poses(grid, observed, cand, grasp_widths, image_height_mm, grasp_width_offset, LR_flip, invert_affine,
+                                   strides[lvl], contact_depth, validate=validate and lvl == 0)
             c = pose_cost(rows, cost, lattice_points((h, w), strides[lvl]))
             win = first_argmin(c)
-            centre = torch.gather(cand, 1, win.view(b, 1, 1).expand(b, 1, 3)).squeeze(1).contiguous()
             best_row = torch.gather(rows, 1, win.view(b, 1, 1).expand(b, 1, POSE_ROW)).squeeze(1)
             best_cost = torch.gather(c, 1, win.view(b, 1)).squeeze(1)
             trace[lvl] = best_cost
-    return PoseEstimate(centre, best_cost, best_row, trace)
+            if width_axis:
+                centre_w = torch.gather(cand_w, 1, (win % n_w).view(b, 1)).squeeze(1).contiguous()
+                win = torch.div(win, n_w, rounding_mode="floor")
+            centre = torch.gather(cand, 1, win.view(b, 1, 1).expand(b, 1, 3)).squeeze(1).contiguous()
+    return PoseEstimate(centre, best_cost, best_row, trace, centre_w if width_axis else grasp_widths)
 
 
 def pose_error(estimate, truth: torch.Tensor) -> torch.Tensor:

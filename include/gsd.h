@@ -542,6 +542,26 @@ int gsd_mesh_pose_score(const gsd_mesh_grid* grid, const gsd_mesh_view* view, co
                         const float* widths, int P, int H, int W, int stride, float contact_depth, double* rows, double* workspace,
                         int64_t workspace_elems, void* stream);
 
+/* ---- the same for G grasp widths per observation, one render per candidate ---- */
+/* For each of B observations, each of its P candidates and each of its G widths one row of GSD_POSE_ROW doubles:
+ *   rows[b][p][k] is, in all five entries, THE SAME BITS as the row gsd_mesh_pose_score gives for observation b, candidate p
+ *   and the width widths[b][k] -- the five NaN of a refused width (g = widths[b][k] + view.width_offset negative or not
+ *   finite) and the non-finite sums of a non-finite D included.  A row therefore does not depend on B, P, G or its position.
+ * The width enters a pixel's depth only in its last step, d = -max(0, m - g/2): the kernel finds the surface value m of a
+ * lattice point once (the map into the mesh frame, the cell, the walk over its triangles) and forms the G depths, errors and
+ * contact predicates from it, reduced in gsd_mesh_pose_score's order.  G widths cost one walk, not G.
+ * widths: B x G floats [mm]; rows: B x P x G x GSD_POSE_ROW doubles, 8-byte aligned; every other argument as for
+ * gsd_mesh_pose_score.  workspace: gsd_mesh_pose_score_widths_workspace(B, P, G, H, W, stride) doubles, 8-byte aligned (0 for
+ * arguments the call refuses).  Nothing is allocated, every launch is on `stream`, nothing synchronises, no float atomics.
+ * GSD_ERR_BAD_ARG before any launch: what gsd_mesh_pose_score refuses, G below 1 or above GSD_POSE_WIDTHS_MAX, 2^31 or more
+ * rows (B * P * G). */
+#define GSD_POSE_WIDTHS_MAX 32
+int64_t gsd_mesh_pose_score_widths_workspace(int B, int P, int G, int H, int W, int stride);   /* doubles */
+int gsd_mesh_pose_score_widths(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
+                               const int32_t* cells, const int32_t* list, int64_t list_elems, const float* observed, int B,
+                               const float* candidates, const float* widths, int P, int G, int H, int W, int stride,
+                               float contact_depth, double* rows, double* workspace, int64_t workspace_elems, void* stream);
+
 /* ---- optimiser (train_unet.py:306,375-376) -------------------------------------------------- */
 /* Fused torch.optim.Adam(lr, betas, eps, weight_decay: coupled L2) + torch_ema update over a flat
  * parameter arena. step is the 1-based Adam step; ema may be NULL; ema_decay already resolved
