@@ -36,6 +36,13 @@
 //   only md_surface is expensive.  A thread finds its point's surface value once and forms the G depths, errors and contact
 //   predicates from it; the G rows are reduced in the same order as the single one, so row (b, p, k) has the bits of
 //   gsd_mesh_pose_score at the width widths[b][k].
+//
+//   host layer: the render and the two score entry points share one validator (md_check: grid, view, T, list, alignment), one
+//   MdView and one MdLattice builder, and one thread -> point decode on the device (md_point).  Both score entry points check
+//   through md_check_score, carve their own workspace layout and hand it to one launcher, md_score: the pose table, for G > 1
+//   the half-widths, the score kernel (mesh_pose_score for G = 1, mesh_pose_score_widths<CH> otherwise) and ONE rows kernel,
+//   mesh_pose_rows, for every G.  gsd_mesh_pose_score_widths with G = 1 therefore makes gsd_mesh_pose_score's launches by
+//   construction: it is the same call of md_score on another workspace layout.
 #include "gsd_common.h"
 
 #include <math.h>
@@ -167,14 +174,15 @@ __global__ __launch_bounds__(256) void mesh_fill(const MdGrid G, const float* __
 }
 
 // row n of the pose table: cos, sin, 1000 t1, 1000 t2, g/2 (NaN when g is negative or not finite: the sample's images are NaN).
-// `per` consecutive poses share a width: 1 for the render, the P candidates of an observation for the pose score.
+// `per` consecutive poses share a width: 1 for the render, the P candidates of an observation for the pose score.  A score over
+// several widths keeps them in an array of its own (mesh_pose_half_widths) and passes no `widths`: the column is 0, nobody reads it.
 __global__ __launch_bounds__(256) void mesh_pose_table(const float* __restrict__ poses, const float* __restrict__ widths, int N, int per,
                                                        float width_offset, float* __restrict__ table) {
 #pragma clang fp contract(off)
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   const float t1 = poses[3 * (size_t)n], t2 = poses[3 * (size_t)n + 1], th = poses[3 * (size_t)n + 2];
-  const float g = widths[n / per] + width_offset;
+  const float g = widths != nullptr ? widths[n / per] + width_offset : 0.f;
   float* row = table + (size_t)n * MD_POSE;
   row[0] = (float)cos((double)th);
   row[1] = (float)sin((double)th);
@@ -273,21 +281,33 @@ __device__ __forceinline__ float md_pixel(const MdGrid& G, const MdView& V, cons
   return md_depth(md_surface(G, V, rec, start, list, row, r, c, right), row[4]);
 }
 
+// The work of a thread of the render and score launches: a block of 256 threads owns a 16 x 16 tile of points of one image,
+// blockIdx.x = (img * tiles_y + ty) * tiles_x + tx, a wave an 8 x 8 patch of it, a thread the point (i, j).
+struct MdPoint {
+  int img, n, ch;       // image n * 2 + channel: n the pose (the render) or observation * P + candidate (the score)
+  int wave, lane, i, j;
+};
+__device__ __forceinline__ MdPoint md_point(int tiles_x, int tiles_y) {
+  int b = blockIdx.x;
+  const int tx = b % tiles_x;
+  b /= tiles_x;
+  const int ty = b % tiles_y;
+  MdPoint p;
+  p.img = b / tiles_y, p.n = p.img >> 1, p.ch = p.img & 1;
+  p.wave = threadIdx.x >> 6, p.lane = threadIdx.x & 63;
+  p.i = ty * 16 + (p.wave >> 1) * 8 + (p.lane >> 3);
+  p.j = tx * 16 + (p.wave & 1) * 8 + (p.lane & 7);
+  return p;
+}
+
 __global__ __launch_bounds__(256) void mesh_render(const MdGrid G, const MdView V, const float* __restrict__ rec,
                                                    const int* __restrict__ start, const int* __restrict__ list,
                                                    const float* __restrict__ table, float* __restrict__ out) {
-  int b = blockIdx.x;
-  const int tx = b % V.tiles_x;
-  b /= V.tiles_x;
-  const int ty = b % V.tiles_y;
-  const int img = b / V.tiles_y;            // n * 2 + channel
-  const int n = img >> 1, ch = img & 1;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int r = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
-  const int c = tx * 16 + (wave & 1) * 8 + (lane & 7);
+  const MdPoint p = md_point(V.tiles_x, V.tiles_y);
+  const int r = p.i, c = p.j;
   if (r >= V.H || c >= V.W) return;
-  const bool right = (ch == 1) != (V.lr_flip != 0);
-  out[((size_t)img * V.H + r) * V.W + c] = md_pixel(G, V, rec, start, list, table + (size_t)n * MD_POSE, r, c, right);
+  const bool right = (p.ch == 1) != (V.lr_flip != 0);
+  out[((size_t)p.img * V.H + r) * V.W + c] = md_pixel(G, V, rec, start, list, table + (size_t)p.n * MD_POSE, r, c, right);
 }
 
 // ---- pose score: render and compare in registers, one row of five doubles per candidate --------------
@@ -308,19 +328,12 @@ __global__ __launch_bounds__(256) void mesh_pose_score(const MdGrid G, const MdV
                                                        const float* __restrict__ table, const float* __restrict__ observed,
                                                        double* __restrict__ partial) {
 #pragma clang fp contract(off)
-  int b = blockIdx.x;
-  const int tx = b % S.tiles_x;
-  b /= S.tiles_x;
-  const int ty = b % S.tiles_y;
-  const int img = b / S.tiles_y;            // (observation * P + candidate) * 2 + channel
-  const int n = img >> 1, ch = img & 1;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int i = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
-  const int j = tx * 16 + (wave & 1) * 8 + (lane & 7);
+  const MdPoint p = md_point(S.tiles_x, S.tiles_y);
+  const int n = p.n, ch = p.ch, wave = p.wave, lane = p.lane;
   double sq = 0.0, ab = 0.0;
   bool cr = false, cd = false;
-  if (i < S.rows && j < S.cols) {           // a point off the lattice adds zeros; every thread reaches the reduction
-    const int r = S.off + i * S.stride, c = S.off + j * S.stride;       // < H, < W: no overflow
+  if (p.i < S.rows && p.j < S.cols) {       // a point off the lattice adds zeros; every thread reaches the reduction
+    const int r = S.off + p.i * S.stride, c = S.off + p.j * S.stride;   // < H, < W: no overflow
     const bool right = (ch == 1) != (V.lr_flip != 0);
     const float R = md_pixel(G, V, rec, start, list, table + (size_t)n * MD_POSE, r, c, right);
     const float D = observed[(((size_t)(n / S.P) * 2 + ch) * V.H + r) * V.W + c];
@@ -344,31 +357,7 @@ __global__ __launch_bounds__(256) void mesh_pose_score(const MdGrid G, const MdV
   }
 }
 
-// One wave per candidate: lane l adds the partial rows l, l + 64, ... of the candidate's `tpc` tiles in ascending order, the 64
-// lane sums meet in the xor butterfly.  The order is a function of tpc alone.  A refused width (NaN in the pose table) gives
-// five NaN.
-__global__ __launch_bounds__(64) void mesh_pose_rows(const double* __restrict__ partial, int tpc, const float* __restrict__ table,
-                                                     double* __restrict__ rows) {
-#pragma clang fp contract(off)
-  const int n = blockIdx.x, lane = threadIdx.x;
-  double tot[MD_ROW];
-#pragma unroll
-  for (int q = 0; q < MD_ROW; ++q) tot[q] = 0.0;
-  for (int k = lane; k < tpc; k += 64) {
-    const double* p = partial + ((size_t)n * tpc + k) * MD_ROW;
-#pragma unroll
-    for (int q = 0; q < MD_ROW; ++q) tot[q] += p[q];
-  }
-#pragma unroll
-  for (int q = 0; q < MD_ROW; ++q) tot[q] = wave_sum_d(tot[q]);
-  const float hg = table[(size_t)n * MD_POSE + 4];
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < MD_ROW; ++q) rows[(size_t)n * MD_ROW + q] = hg == hg ? tot[q] : (double)hg;
-  }
-}
-
-// ---- pose score over many widths per render -------------------------------------------------------------
+// ---- G widths per render -----------------------------------------------------------------------------
 constexpr int MD_WIDTHS = GSD_POSE_WIDTHS_MAX;
 
 // half-width k of observation b, entry b * G + k: the expression of mesh_pose_table's row[4]
@@ -381,8 +370,8 @@ __global__ __launch_bounds__(256) void mesh_pose_half_widths(const float* __rest
   half[i] = (g >= 0.f && isfinite(g)) ? 0.5f * g : __builtin_nanf("");
 }
 
-// wave_sum_d for CH values at once (CH = 2, 4): the same tree -- lane l meets l ^ 32, then l ^ 16, ... -- but while more than one
-// value is left an exchange halves them: a lane keeps the half that its bit selects and sends the other, so both lanes add the
+// wave_sum_d for CH values at once (CH = 2, 4): the same tree -- lane l meets l ^ 32, then l ^ 16, ... -- but while more than
+// one value is left an exchange halves them: a lane keeps the half that its bit selects and sends the other, so both lanes add the
 // pair of terms that wave_sum_d adds (a + b and b + a are the same bits).  Afterwards v[0] of lane l is the wave's sum of value
 // l / (64 / CH), bit for bit what wave_sum_d gives, for fewer exchanges: CH = 4 costs 2 + 1 + 4 of them instead of 4 * 6.
 template <int CH>
@@ -412,33 +401,26 @@ __global__ __launch_bounds__(256) void mesh_pose_score_widths(const MdGrid G, co
                                                               const float* __restrict__ half, const float* __restrict__ observed,
                                                               double* __restrict__ partial) {
 #pragma clang fp contract(off)
-  int b = blockIdx.x;
-  const int tx = b % S.tiles_x;
-  b /= S.tiles_x;
-  const int ty = b % S.tiles_y;
-  const int img = b / S.tiles_y;            // (observation * P + candidate) * 2 + channel
-  const int n = img >> 1, ch = img & 1;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int i = ty * 16 + (wave >> 1) * 8 + (lane >> 3);
-  const int j = tx * 16 + (wave & 1) * 8 + (lane & 7);
-  const bool on = i < S.rows && j < S.cols;   // a point off the lattice adds zeros; every thread reaches the reductions
+  const MdPoint p = md_point(S.tiles_x, S.tiles_y);
+  const int n = p.n, ch = p.ch, wave = p.wave, lane = p.lane;
+  const float* row = table + (size_t)n * MD_POSE;
+  const bool on = p.i < S.rows && p.j < S.cols;   // a point off the lattice adds zeros; every thread reaches the reductions
   float m = 0.f, D = 0.f;
   if (on) {
-    const int r = S.off + i * S.stride, c = S.off + j * S.stride;       // < H, < W: no overflow
+    const int r = S.off + p.i * S.stride, c = S.off + p.j * S.stride;   // < H, < W: no overflow
     const bool right = (ch == 1) != (V.lr_flip != 0);
-    m = md_surface(G, V, rec, start, list, table + (size_t)n * MD_POSE, r, c, right);
+    m = md_surface(G, V, rec, start, list, row, r, c, right);
     D = observed[(((size_t)(n / S.P) * 2 + ch) * V.H + r) * V.W + c];
   }
   const bool cd = on && D < -S.contact && isfinite(D);     // a non-finite D is not contact
   const int n_d = __popcll(__ballot(cd));
-  const float* hw = half + (size_t)(n / S.P) * NW;
   __shared__ double red[4][MD_WIDTHS][MD_ROW];
   for (int k0 = 0; k0 < NW; k0 += CH) {
     double sq[CH], ab[CH];
     int n_i[CH], n_r[CH];
 #pragma unroll
     for (int u = 0; u < CH; ++u) {
-      const float R = md_depth(m, hw[min(k0 + u, NW - 1)]);
+      const float R = md_depth(m, half[(size_t)(n / S.P) * NW + min(k0 + u, NW - 1)]);
       const double e = (double)R - (double)D;
       sq[u] = on ? e * e : 0.0;
       ab[u] = on ? fabs(e) : 0.0;
@@ -461,9 +443,12 @@ __global__ __launch_bounds__(256) void mesh_pose_score_widths(const MdGrid G, co
   }
 }
 
-// mesh_pose_rows for one (candidate, width) per wave, block n * NW + k: the same lane order over that pair's partial rows.
-__global__ __launch_bounds__(64) void mesh_pose_rows_widths(const double* __restrict__ partial, int tpc, int NW, int P,
-                                                            const float* __restrict__ half, double* __restrict__ rows) {
+// One wave per (candidate n, width k), block n * NW + k: lane l adds the partial rows l, l + 64, ... of the candidate's `tpc` tiles
+// in ascending order, the 64 lane sums meet in the xor butterfly.  The order is a function of tpc alone.  A refused width gives
+// five NaN; its mark is the NaN half-width flag[(n / per) * step + k]: {table + 4, 1, MD_POSE} for the one width of a pose-table
+// row, {half, P, NW} for the array of several.
+__global__ __launch_bounds__(64) void mesh_pose_rows(const double* __restrict__ partial, int tpc, int NW, const float* __restrict__ flag,
+                                                     int per, int step, double* __restrict__ rows) {
 #pragma clang fp contract(off)
   const int n = blockIdx.x / NW, k = blockIdx.x - n * NW, lane = threadIdx.x;
   double tot[MD_ROW];
@@ -476,7 +461,7 @@ __global__ __launch_bounds__(64) void mesh_pose_rows_widths(const double* __rest
   }
 #pragma unroll
   for (int q = 0; q < MD_ROW; ++q) tot[q] = wave_sum_d(tot[q]);
-  const float hg = half[(size_t)(n / P) * NW + k];
+  const float hg = flag[(size_t)(n / per) * step + k];
   if (lane == 0) {
 #pragma unroll
     for (int q = 0; q < MD_ROW; ++q) rows[(size_t)blockIdx.x * MD_ROW + q] = hg == hg ? tot[q] : (double)hg;
@@ -488,10 +473,17 @@ int md_lattice_len(int len, int stride) {
   const int off = stride / 2;
   return off < len ? (len - 1 - off) / stride + 1 : 0;
 }
-// blocks of the score launch, or -1 when an argument is out of range
+MdLattice md_lattice(int H, int W, int stride, int P, float contact) {
+  MdLattice S;
+  S.stride = stride, S.off = stride / 2, S.rows = md_lattice_len(H, stride), S.cols = md_lattice_len(W, stride);
+  S.tiles_x = ceil_div(S.cols, 16), S.tiles_y = ceil_div(S.rows, 16), S.P = P, S.contact = contact;
+  return S;
+}
+// blocks of the score launch (the tiles that md_point decodes), or -1 when an argument is out of range
 int64_t md_score_blocks(int B, int P, int H, int W, int stride) {
   if (B < 1 || P < 1 || H < 1 || W < 1 || stride < 1 || (int64_t)B * P > INT32_MAX) return -1;
-  return (int64_t)ceil_div(md_lattice_len(W, stride), 16) * ceil_div(md_lattice_len(H, stride), 16) * 2 * ((int64_t)B * P);
+  const MdLattice S = md_lattice(H, W, stride, P, 0.f);
+  return (int64_t)S.tiles_x * S.tiles_y * 2 * ((int64_t)B * P);
 }
 
 int md_check_grid(const gsd_mesh_grid* g, const char* what) {
@@ -510,6 +502,99 @@ MdGrid md_grid(const gsd_mesh_grid* g) {
   return G;
 }
 int64_t md_cells(const gsd_mesh_grid* g) { return (int64_t)g->nx * g->ny; }
+
+// ---- the host layer of the three launching entry points; `what` is the one that was called and begins every message ----------
+struct MdMesh {         // a built mesh and the view of it, as the caller passed them
+  const gsd_mesh_grid* grid;
+  const gsd_mesh_view* view;
+  const float* records;
+  int T;
+  const int32_t* cells;
+  const int32_t* list;
+  int64_t list_elems;
+};
+int md_check(const MdMesh& M, const char* what) {
+  if (md_check_grid(M.grid, what)) return GSD_ERR_BAD_ARG;
+  GSD_REQUIRE(M.view && M.records && M.cells && M.list, GSD_ERR_BAD_ARG, "%s: null pointer", what);
+  GSD_REQUIRE(isfinite(M.view->mpp) && M.view->mpp > 0.f && isfinite(M.view->width_offset), GSD_ERR_BAD_ARG,
+              "%s: mm per pixel %g must be finite and positive, the width offset %g finite", what, (double)M.view->mpp,
+              (double)M.view->width_offset);
+  GSD_REQUIRE(M.view->reserved == 0, GSD_ERR_BAD_ARG, "%s: the reserved word must be 0", what);
+  GSD_REQUIRE(M.T >= 1 && M.T <= MD_MAX_T, GSD_ERR_BAD_ARG, "%s: %d triangles, 1..%d", what, M.T, MD_MAX_T);
+  GSD_REQUIRE(M.list_elems >= 1 && M.list_elems <= INT32_MAX, GSD_ERR_BAD_ARG, "%s: list of %lld entries, 1..2^31-1", what,
+              (long long)M.list_elems);
+  GSD_REQUIRE(((uintptr_t)M.records & 15) == 0, GSD_ERR_BAD_ARG, "%s: records must be 16-byte aligned", what);
+  return 0;
+}
+MdView md_view(const MdMesh& M, int H, int W) {
+  MdView V;
+  V.mpp = M.view->mpp, V.cx = M.grid->cx, V.cy = M.grid->cy;
+  V.swap_axes = M.view->swap_axes != 0, V.invert = M.view->invert_affine != 0, V.lr_flip = M.view->lr_flip != 0;
+  V.H = H, V.W = W, V.tiles_x = ceil_div(W, 16), V.tiles_y = ceil_div(H, 16), V.T = M.T, V.list_elems = M.list_elems;
+  return V;
+}
+
+struct MdScore {        // what is scored: G widths per observation, G = 1 for gsd_mesh_pose_score
+  const float* observed;
+  int B;
+  const float* candidates;
+  const float* widths;
+  int P, G, H, W, stride;
+  float contact;
+  double* rows;
+};
+// everything a score entry point refuses (all of it GSD_ERR_BAD_ARG); `need` is its own workspace formula
+int md_check_score(const MdMesh& M, const MdScore& Q, const double* workspace, int64_t workspace_elems, int64_t need, const char* what) {
+  if (md_check(M, what)) return GSD_ERR_BAD_ARG;
+  GSD_REQUIRE(Q.observed && Q.candidates && Q.widths && Q.rows && workspace, GSD_ERR_BAD_ARG, "%s: null pointer", what);
+  GSD_REQUIRE(Q.B >= 1 && Q.P >= 1 && Q.H >= 1 && Q.W >= 1, GSD_ERR_BAD_ARG, "%s: bad dims B=%d P=%d H=%d W=%d", what, Q.B, Q.P, Q.H,
+              Q.W);
+  GSD_REQUIRE(Q.G >= 1 && Q.G <= MD_WIDTHS, GSD_ERR_BAD_ARG, "%s: %d widths per observation, 1..%d", what, Q.G, MD_WIDTHS);
+  GSD_REQUIRE(Q.stride >= 1, GSD_ERR_BAD_ARG, "%s: stride %d must be at least 1", what, Q.stride);
+  GSD_REQUIRE(isfinite(Q.contact) && Q.contact >= 0.f, GSD_ERR_BAD_ARG, "%s: contact_depth %g must be finite and >= 0", what,
+              (double)Q.contact);
+  GSD_REQUIRE(((uintptr_t)Q.rows & 7) == 0 && ((uintptr_t)workspace & 7) == 0, GSD_ERR_BAD_ARG,
+              "%s: rows and workspace must be 8-byte aligned", what);
+  const int64_t blocks = md_score_blocks(Q.B, Q.P, Q.H, Q.W, Q.stride);
+  GSD_REQUIRE(blocks >= 0 && blocks <= INT32_MAX && (int64_t)Q.B * Q.P * Q.G <= INT32_MAX, GSD_ERR_BAD_ARG,
+              "%s: %lld blocks (B=%d x P=%d of %d x %d, stride %d) and %lld rows, at most 2^31-1 per launch", what, (long long)blocks, Q.B,
+              Q.P, Q.H, Q.W, Q.stride, (long long)Q.B * Q.P * Q.G);
+  GSD_REQUIRE(workspace_elems >= need, GSD_ERR_BAD_ARG, "%s: workspace of %lld doubles, need %lld", what, (long long)workspace_elems,
+              (long long)need);
+  return 0;
+}
+// The launches of both score entry points, on workspace that the caller has carved: the pose table, for G > 1 the half-widths,
+// the score kernel (one partial row per block and width) and the rows kernel.  G = 1 keeps its width in the pose table.
+int md_score(const MdMesh& M, const MdScore& Q, float* table, float* half, double* partial, hipStream_t st, const char* what) {
+  const int N = Q.B * Q.P, G = Q.G;
+  const int64_t blocks = md_score_blocks(Q.B, Q.P, Q.H, Q.W, Q.stride);
+  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, Q.candidates, G == 1 ? Q.widths : nullptr, N,
+                     Q.P, M.view->width_offset, table);
+  GSD_LAUNCH_CHECK(what);
+  if (G > 1) {
+    hipLaunchKernelGGL(mesh_pose_half_widths, dim3((unsigned)ceil_div(Q.B * G, 256)), dim3(256), 0, st, Q.widths, Q.B * G,
+                       M.view->width_offset, half);
+    GSD_LAUNCH_CHECK(what);
+  }
+  if (blocks > 0) {      // a stride that leaves no lattice point: every row is five zeros
+    const MdGrid grid = md_grid(M.grid);
+    const MdView V = md_view(M, Q.H, Q.W);
+    const MdLattice S = md_lattice(Q.H, Q.W, Q.stride, Q.P, Q.contact);
+    if (G == 1) {
+      hipLaunchKernelGGL(mesh_pose_score, dim3((unsigned)blocks), dim3(256), 0, st, grid, V, S, M.records, M.cells + 2, M.list,
+                         (const float*)table, Q.observed, partial);
+    } else {
+      const auto kernel = G == 2 ? mesh_pose_score_widths<2> : mesh_pose_score_widths<4>;
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, grid, V, S, G, M.records, M.cells + 2, M.list,
+                         (const float*)table, (const float*)half, Q.observed, partial);
+    }
+    GSD_LAUNCH_CHECK(what);
+  }
+  hipLaunchKernelGGL(mesh_pose_rows, dim3((unsigned)(N * G)), dim3(64), 0, st, (const double*)partial, (int)(blocks / N), G,
+                     G == 1 ? (const float*)table + 4 : (const float*)half, G == 1 ? 1 : Q.P, G == 1 ? MD_POSE : G, Q.rows);
+  GSD_LAUNCH_CHECK(what);
+  return GSD_OK;
+}
 
 }   // namespace
 
@@ -585,94 +670,44 @@ extern "C" int gsd_mesh_depth_render(const gsd_mesh_grid* grid, const gsd_mesh_v
                                      const int32_t* cells, const int32_t* list, int64_t list_elems, const float* poses,
                                      const float* widths, int N, int H, int W, float* out, float* workspace,
                                      int64_t workspace_elems, void* stream) {
-  if (md_check_grid(grid, "gsd_mesh_depth_render")) return GSD_ERR_BAD_ARG;
-  GSD_REQUIRE(view && records && cells && list && poses && widths && out && workspace, GSD_ERR_BAD_ARG,
-              "gsd_mesh_depth_render: null pointer");
-  GSD_REQUIRE(T >= 1 && T <= MD_MAX_T, GSD_ERR_BAD_ARG, "gsd_mesh_depth_render: %d triangles, 1..%d", T, MD_MAX_T);
-  GSD_REQUIRE(N >= 1 && H >= 1 && W >= 1, GSD_ERR_BAD_ARG, "gsd_mesh_depth_render: bad dims N=%d H=%d W=%d", N, H, W);
-  GSD_REQUIRE(list_elems >= 1 && list_elems <= INT32_MAX, GSD_ERR_BAD_ARG, "gsd_mesh_depth_render: list of %lld entries, 1..2^31-1",
-              (long long)list_elems);
-  GSD_REQUIRE(isfinite(view->mpp) && view->mpp > 0.f && isfinite(view->width_offset), GSD_ERR_BAD_ARG,
-              "gsd_mesh_depth_render: mm per pixel %g must be finite and positive, the width offset %g finite", (double)view->mpp,
-              (double)view->width_offset);
-  GSD_REQUIRE(view->reserved == 0, GSD_ERR_BAD_ARG, "gsd_mesh_depth_render: the reserved word must be 0");
-  GSD_REQUIRE(((uintptr_t)records & 15) == 0, GSD_ERR_BAD_ARG, "gsd_mesh_depth_render: records must be 16-byte aligned");
-  GSD_REQUIRE(workspace_elems >= (int64_t)N * MD_POSE, GSD_ERR_WORKSPACE, "gsd_mesh_depth_render: workspace of %lld floats, need %lld",
+  const char* what = "gsd_mesh_depth_render";
+  const MdMesh M{grid, view, records, T, cells, list, list_elems};
+  if (md_check(M, what)) return GSD_ERR_BAD_ARG;
+  GSD_REQUIRE(poses && widths && out && workspace, GSD_ERR_BAD_ARG, "%s: null pointer", what);
+  GSD_REQUIRE(N >= 1 && H >= 1 && W >= 1, GSD_ERR_BAD_ARG, "%s: bad dims N=%d H=%d W=%d", what, N, H, W);
+  GSD_REQUIRE(workspace_elems >= (int64_t)N * MD_POSE, GSD_ERR_WORKSPACE, "%s: workspace of %lld floats, need %lld", what,
               (long long)workspace_elems, (long long)N * MD_POSE);
-  const int tiles_x = ceil_div(W, 16), tiles_y = ceil_div(H, 16);
-  const int64_t blocks = (int64_t)tiles_x * tiles_y * 2 * N;
-  GSD_REQUIRE(blocks <= INT32_MAX, GSD_ERR_UNSUPPORTED, "gsd_mesh_depth_render: %lld blocks (N=%d of %d x %d), at most 2^31-1 per launch",
+  const MdView V = md_view(M, H, W);
+  const int64_t blocks = (int64_t)V.tiles_x * V.tiles_y * 2 * N;
+  GSD_REQUIRE(blocks <= INT32_MAX, GSD_ERR_UNSUPPORTED, "%s: %lld blocks (N=%d of %d x %d), at most 2^31-1 per launch", what,
               (long long)blocks, N, H, W);
   const hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, poses, widths, N, 1, view->width_offset,
                      workspace);
-  GSD_LAUNCH_CHECK("gsd_mesh_depth_render pose table");
-  MdView V;
-  V.mpp = view->mpp, V.cx = grid->cx, V.cy = grid->cy;
-  V.swap_axes = view->swap_axes != 0, V.invert = view->invert_affine != 0, V.lr_flip = view->lr_flip != 0;
-  V.H = H, V.W = W, V.tiles_x = tiles_x, V.tiles_y = tiles_y, V.T = T, V.list_elems = list_elems;
+  GSD_LAUNCH_CHECK(what);
   hipLaunchKernelGGL(mesh_render, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), V, records, cells + 2, list,
                      (const float*)workspace, out);
-  GSD_LAUNCH_CHECK("gsd_mesh_depth_render");
+  GSD_LAUNCH_CHECK(what);
   return GSD_OK;
 }
 
+// doubles: the pose table (8 floats a row) | one partial row per block
 extern "C" int64_t gsd_mesh_pose_score_workspace(int B, int P, int H, int W, int stride) {
   const int64_t blocks = md_score_blocks(B, P, H, W, stride);
   if (blocks < 0 || blocks > INT32_MAX) return 0;
-  return (int64_t)B * P * (MD_POSE / 2) + blocks * MD_ROW;   // the pose table (8 floats a row) | one partial row per block
+  return (int64_t)B * P * (MD_POSE / 2) + blocks * MD_ROW;
 }
 
 extern "C" int gsd_mesh_pose_score(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
                                    const int32_t* cells, const int32_t* list, int64_t list_elems, const float* observed, int B,
                                    const float* candidates, const float* widths, int P, int H, int W, int stride, float contact_depth,
                                    double* rows, double* workspace, int64_t workspace_elems, void* stream) {
-  if (md_check_grid(grid, "gsd_mesh_pose_score")) return GSD_ERR_BAD_ARG;
-  GSD_REQUIRE(view && records && cells && list && observed && candidates && widths && rows && workspace, GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score: null pointer");
-  GSD_REQUIRE(T >= 1 && T <= MD_MAX_T, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: %d triangles, 1..%d", T, MD_MAX_T);
-  GSD_REQUIRE(B >= 1 && P >= 1 && H >= 1 && W >= 1, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: bad dims B=%d P=%d H=%d W=%d", B, P, H, W);
-  GSD_REQUIRE(stride >= 1, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: stride %d must be at least 1", stride);
-  GSD_REQUIRE(isfinite(contact_depth) && contact_depth >= 0.f, GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score: contact_depth %g must be finite and >= 0", (double)contact_depth);
-  GSD_REQUIRE(list_elems >= 1 && list_elems <= INT32_MAX, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: list of %lld entries, 1..2^31-1",
-              (long long)list_elems);
-  GSD_REQUIRE(isfinite(view->mpp) && view->mpp > 0.f && isfinite(view->width_offset), GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score: mm per pixel %g must be finite and positive, the width offset %g finite", (double)view->mpp,
-              (double)view->width_offset);
-  GSD_REQUIRE(view->reserved == 0, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: the reserved word must be 0");
-  GSD_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)rows & 7) == 0 && ((uintptr_t)workspace & 7) == 0, GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score: records must be 16-byte aligned, rows and workspace 8-byte aligned");
-  const int64_t blocks = md_score_blocks(B, P, H, W, stride);
-  GSD_REQUIRE(blocks >= 0 && blocks <= INT32_MAX, GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score: %lld blocks (B=%d x P=%d of %d x %d, stride %d), at most 2^31-1 per launch", (long long)blocks, B, P, H,
-              W, stride);
-  const int64_t need = gsd_mesh_pose_score_workspace(B, P, H, W, stride);
-  GSD_REQUIRE(workspace_elems >= need, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score: workspace of %lld doubles, need %lld",
-              (long long)workspace_elems, (long long)need);
-  const int N = B * P;
-  const hipStream_t st = (hipStream_t)stream;
-  float* table = reinterpret_cast<float*>(workspace);
-  double* partial = workspace + (int64_t)N * (MD_POSE / 2);
-  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, candidates, widths, N, P, view->width_offset,
-                     table);
-  GSD_LAUNCH_CHECK("gsd_mesh_pose_score pose table");
-  MdView V;
-  V.mpp = view->mpp, V.cx = grid->cx, V.cy = grid->cy;
-  V.swap_axes = view->swap_axes != 0, V.invert = view->invert_affine != 0, V.lr_flip = view->lr_flip != 0;
-  V.H = H, V.W = W, V.tiles_x = ceil_div(W, 16), V.tiles_y = ceil_div(H, 16), V.T = T, V.list_elems = list_elems;
-  MdLattice S;
-  S.stride = stride, S.off = stride / 2, S.rows = md_lattice_len(H, stride), S.cols = md_lattice_len(W, stride);
-  S.tiles_x = ceil_div(S.cols, 16), S.tiles_y = ceil_div(S.rows, 16), S.P = P, S.contact = contact_depth;
-  if (blocks > 0) {      // a stride that leaves no lattice point: every row is five zeros
-    hipLaunchKernelGGL(mesh_pose_score, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), V, S, records, cells + 2, list,
-                       (const float*)table, observed, partial);
-    GSD_LAUNCH_CHECK("gsd_mesh_pose_score");
-  }
-  hipLaunchKernelGGL(mesh_pose_rows, dim3((unsigned)N), dim3(64), 0, st, (const double*)partial, (int)(blocks / N), (const float*)table,
-                     rows);
-  GSD_LAUNCH_CHECK("gsd_mesh_pose_score rows");
-  return GSD_OK;
+  const char* what = "gsd_mesh_pose_score";
+  const MdMesh M{grid, view, records, T, cells, list, list_elems};
+  const MdScore Q{observed, B, candidates, widths, P, 1, H, W, stride, contact_depth, rows};
+  if (md_check_score(M, Q, workspace, workspace_elems, gsd_mesh_pose_score_workspace(B, P, H, W, stride), what)) return GSD_ERR_BAD_ARG;
+  const int64_t table_words = (int64_t)B * P * (MD_POSE / 2);
+  return md_score(M, Q, reinterpret_cast<float*>(workspace), nullptr, workspace + table_words, (hipStream_t)stream, what);
 }
 
 // doubles: the pose table (8 floats a row) | the half-widths (B x G floats, rounded up to whole doubles) | G partial rows per block
@@ -682,76 +717,17 @@ extern "C" int64_t gsd_mesh_pose_score_widths_workspace(int B, int P, int G, int
   return (int64_t)B * P * (MD_POSE / 2) + ((int64_t)B * G + 1) / 2 + blocks * G * MD_ROW;
 }
 
+// G = 1 (widths is gsd_mesh_pose_score's B floats) makes that call's launches, on this layout
 extern "C" int gsd_mesh_pose_score_widths(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
                                           const int32_t* cells, const int32_t* list, int64_t list_elems, const float* observed, int B,
                                           const float* candidates, const float* widths, int P, int G, int H, int W, int stride,
                                           float contact_depth, double* rows, double* workspace, int64_t workspace_elems, void* stream) {
-  if (md_check_grid(grid, "gsd_mesh_pose_score_widths")) return GSD_ERR_BAD_ARG;
-  GSD_REQUIRE(view && records && cells && list && observed && candidates && widths && rows && workspace, GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score_widths: null pointer");
-  GSD_REQUIRE(T >= 1 && T <= MD_MAX_T, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: %d triangles, 1..%d", T, MD_MAX_T);
-  GSD_REQUIRE(B >= 1 && P >= 1 && H >= 1 && W >= 1, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: bad dims B=%d P=%d H=%d W=%d", B, P,
-              H, W);
-  GSD_REQUIRE(G >= 1 && G <= MD_WIDTHS, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: %d widths per observation, 1..%d", G, MD_WIDTHS);
-  GSD_REQUIRE(stride >= 1, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: stride %d must be at least 1", stride);
-  GSD_REQUIRE(isfinite(contact_depth) && contact_depth >= 0.f, GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score_widths: contact_depth %g must be finite and >= 0", (double)contact_depth);
-  GSD_REQUIRE(list_elems >= 1 && list_elems <= INT32_MAX, GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score_widths: list of %lld entries, 1..2^31-1", (long long)list_elems);
-  GSD_REQUIRE(isfinite(view->mpp) && view->mpp > 0.f && isfinite(view->width_offset), GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score_widths: mm per pixel %g must be finite and positive, the width offset %g finite", (double)view->mpp,
-              (double)view->width_offset);
-  GSD_REQUIRE(view->reserved == 0, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: the reserved word must be 0");
-  GSD_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)rows & 7) == 0 && ((uintptr_t)workspace & 7) == 0, GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score_widths: records must be 16-byte aligned, rows and workspace 8-byte aligned");
-  const int64_t blocks = md_score_blocks(B, P, H, W, stride);
-  GSD_REQUIRE(blocks >= 0 && blocks <= INT32_MAX && (int64_t)B * P * G <= INT32_MAX, GSD_ERR_BAD_ARG,
-              "gsd_mesh_pose_score_widths: %lld blocks (B=%d x P=%d of %d x %d, stride %d) and %lld rows, at most 2^31-1 per launch",
-              (long long)blocks, B, P, H, W, stride, (long long)B * P * G);
-  const int64_t need = gsd_mesh_pose_score_widths_workspace(B, P, G, H, W, stride);
-  GSD_REQUIRE(workspace_elems >= need, GSD_ERR_BAD_ARG, "gsd_mesh_pose_score_widths: workspace of %lld doubles, need %lld",
-              (long long)workspace_elems, (long long)need);
-  const int N = B * P;
-  const hipStream_t st = (hipStream_t)stream;
-  float* table = reinterpret_cast<float*>(workspace);
-  float* half = reinterpret_cast<float*>(workspace + (int64_t)N * (MD_POSE / 2));
-  double* partial = workspace + (int64_t)N * (MD_POSE / 2) + ((int64_t)B * G + 1) / 2;
-  // G > 1: the pose table's own width column is not read (per = N: every row takes widths[0]).  G = 1: widths is
-  // gsd_mesh_pose_score's B floats, and the call is that one's three launches
-  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, candidates, widths, N, G == 1 ? P : N,
-                     view->width_offset, table);
-  GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths pose table");
-  if (G > 1) {
-    hipLaunchKernelGGL(mesh_pose_half_widths, dim3((unsigned)ceil_div(B * G, 256)), dim3(256), 0, st, widths, B * G, view->width_offset,
-                       half);
-    GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths half-widths");
-  }
-  MdView V;
-  V.mpp = view->mpp, V.cx = grid->cx, V.cy = grid->cy;
-  V.swap_axes = view->swap_axes != 0, V.invert = view->invert_affine != 0, V.lr_flip = view->lr_flip != 0;
-  V.H = H, V.W = W, V.tiles_x = ceil_div(W, 16), V.tiles_y = ceil_div(H, 16), V.T = T, V.list_elems = list_elems;
-  MdLattice S;
-  S.stride = stride, S.off = stride / 2, S.rows = md_lattice_len(H, stride), S.cols = md_lattice_len(W, stride);
-  S.tiles_x = ceil_div(S.cols, 16), S.tiles_y = ceil_div(S.rows, 16), S.P = P, S.contact = contact_depth;
-  if (G == 1) {
-    if (blocks > 0) {
-      hipLaunchKernelGGL(mesh_pose_score, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), V, S, records, cells + 2, list,
-                         (const float*)table, observed, partial);
-      GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths");
-    }
-    hipLaunchKernelGGL(mesh_pose_rows, dim3((unsigned)N), dim3(64), 0, st, (const double*)partial, (int)(blocks / N),
-                       (const float*)table, rows);
-    GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths rows");
-    return GSD_OK;
-  }
-  if (blocks > 0) {      // a stride that leaves no lattice point: every row is five zeros
-    const auto kernel = G == 2 ? mesh_pose_score_widths<2> : mesh_pose_score_widths<4>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), V, S, G, records, cells + 2, list,
-                       (const float*)table, (const float*)half, observed, partial);
-    GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths");
-  }
-  hipLaunchKernelGGL(mesh_pose_rows_widths, dim3((unsigned)(N * G)), dim3(64), 0, st, (const double*)partial, (int)(blocks / N), G, P,
-                     (const float*)half, rows);
-  GSD_LAUNCH_CHECK("gsd_mesh_pose_score_widths rows");
-  return GSD_OK;
+  const char* what = "gsd_mesh_pose_score_widths";
+  const MdMesh M{grid, view, records, T, cells, list, list_elems};
+  const MdScore Q{observed, B, candidates, widths, P, G, H, W, stride, contact_depth, rows};
+  if (md_check_score(M, Q, workspace, workspace_elems, gsd_mesh_pose_score_widths_workspace(B, P, G, H, W, stride), what))
+    return GSD_ERR_BAD_ARG;
+  const int64_t table_words = (int64_t)B * P * (MD_POSE / 2), half_words = ((int64_t)B * G + 1) / 2;
+  return md_score(M, Q, reinterpret_cast<float*>(workspace), reinterpret_cast<float*>(workspace + table_words),
+                  workspace + table_words + half_words, (hipStream_t)stream, what);
 }

@@ -236,6 +236,41 @@ class MeshGrid:
                 f"{self.cell_mm:.4g} mm, {self.pairs} pairs)")
 
 
+def _check_tensors(what: str, grid, tensors, contiguous: bool = False) -> None:
+    """`grid` is a MeshGrid and every (name, tensor, shape as text) of `tensors` a float32 tensor on its device."""
+    if not isinstance(grid, MeshGrid):
+        raise MeshDepthError(f"{what}: grid must be a MeshGrid, got {type(grid).__name__}")
+    for name, t, shape in tensors:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or (contiguous and not t.is_contiguous()):
+            raise MeshDepthError(f"{what}: {name} must be a {'contiguous ' if contiguous else ''}float32 {shape} tensor on the GPU, got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')}")
+        if t.device != grid.device:
+            raise MeshDepthError(f"{what}: {name} is on {t.device}, the mesh on {grid.device}")
+
+
+def _check_widths(what: str, widths: torch.Tensor, offset: float) -> None:
+    """`validate=True`: the smallest width + offset is read back from the device, the call's only synchronisation."""
+    g_min = float((widths + offset).min())          # NaN propagates through min
+    if not (g_min >= 0.0) or not bool(torch.isfinite(widths).all()):
+        raise MeshDepthError(f"{what}: grasp width + offset must be finite and >= 0, the smallest is {g_min!r}")
+
+
+def _mesh_view(grid: MeshGrid, mpp: float, offset: float, LR_flip: bool, invert_affine: bool) -> "L.gsd_mesh_view":
+    view = L.gsd_mesh_view()
+    view.mpp, view.width_offset = mpp, offset
+    view.swap_axes, view.invert_affine, view.lr_flip, view.reserved = grid.swap_axes, int(bool(invert_affine)), int(bool(LR_flip)), 0
+    return view
+
+
+def _out_tensor(what: str, grid: MeshGrid, out: Optional[torch.Tensor], shape: Tuple[int, ...], dtype: torch.dtype) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, device=grid.device, dtype=dtype)
+    if (not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != grid.device or not out.is_contiguous()
+            or tuple(out.shape) != shape):
+        raise MeshDepthError(f"{what}: out must be a contiguous {str(dtype)[6:]} {shape} tensor on {grid.device}")
+    return out
+
+
 def render_depth(grid: MeshGrid, poses: torch.Tensor, grasp_widths: torch.Tensor, image_size: Sequence[int] = (320, 427),
                  image_height_mm: float = 12.0, grasp_width_offset: float = 0.0, LR_flip: bool = False,
                  invert_affine: bool = False, out: Optional[torch.Tensor] = None, validate: bool = True) -> torch.Tensor:
@@ -247,14 +282,7 @@ def render_depth(grid: MeshGrid, poses: torch.Tensor, grasp_widths: torch.Tensor
     from the device and a negative or non-finite one raises MeshDepthError (a ValueError) before anything of libgsd runs: this
     is the call's only synchronisation.  `validate=False` promises that the caller has checked (generate_depth_images_v1
     checks the whole file on the host): then nothing is synchronised, and a sample with a bad g comes out as NaN."""
-    if not isinstance(grid, MeshGrid):
-        raise MeshDepthError(f"render_depth: grid must be a MeshGrid, got {type(grid).__name__}")
-    for name, t, shape in (("poses", poses, "(N, 3)"), ("grasp_widths", grasp_widths, "(N,)")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-            raise MeshDepthError(f"render_depth: {name} must be a contiguous float32 {shape} tensor on the GPU, got "
-                                 f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')}")
-        if t.device != grid.device:
-            raise MeshDepthError(f"render_depth: {name} is on {t.device}, the mesh on {grid.device}")
+    _check_tensors("render_depth", grid, (("poses", poses, "(N, 3)"), ("grasp_widths", grasp_widths, "(N,)")), contiguous=True)
     if poses.dim() != 2 or poses.shape[1] != 3 or poses.shape[0] < 1:
         raise MeshDepthError(f"render_depth: poses must be (N, 3) with N >= 1, got {tuple(poses.shape)}")
     n = int(poses.shape[0])
@@ -267,18 +295,10 @@ def render_depth(grid: MeshGrid, poses: torch.Tensor, grasp_widths: torch.Tensor
     offset = float(grasp_width_offset)
     if not math.isfinite(offset):
         raise MeshDepthError(f"render_depth: grasp_width_offset must be finite, got {grasp_width_offset!r}")
-    if out is None:
-        out = torch.empty((n, 2, h, w), device=grid.device, dtype=torch.float32)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != grid.device or not out.is_contiguous()
-          or tuple(out.shape) != (n, 2, h, w)):
-        raise MeshDepthError(f"render_depth: out must be a contiguous float32 ({n}, 2, {h}, {w}) tensor on {grid.device}")
+    out = _out_tensor("render_depth", grid, out, (n, 2, h, w), torch.float32)
     if validate:
-        g_min = float((grasp_widths + offset).min())          # NaN propagates through min
-        if not (g_min >= 0.0) or not bool(torch.isfinite(grasp_widths).all()):
-            raise MeshDepthError(f"render_depth: grasp width + offset must be finite and >= 0, the smallest is {g_min!r}")
-    view = L.gsd_mesh_view()
-    view.mpp, view.width_offset = mpp, offset
-    view.swap_axes, view.invert_affine, view.lr_flip, view.reserved = grid.swap_axes, int(bool(invert_affine)), int(bool(LR_flip)), 0
+        _check_widths("render_depth", grasp_widths, offset)
+    view = _mesh_view(grid, mpp, offset, LR_flip, invert_affine)
     with torch.cuda.device(grid.device):
         ws = torch.empty((int(lib.gsd_mesh_depth_render_workspace(n)),), device=grid.device, dtype=torch.float32)
         check(lib.gsd_mesh_depth_render(C.byref(grid.grid), C.byref(view), grid.records.data_ptr(), grid.triangles,
@@ -398,6 +418,59 @@ def lattice_points(image_size: Sequence[int], stride: int = 1) -> int:
     return 2 * len(range(s // 2, h, s)) * len(range(s // 2, w, s))
 
 
+POSE_WIDTHS_MAX = L.GSD_POSE_WIDTHS_MAX      # widths per observation that one `score_poses_widths` call takes
+
+
+def _score(what: str, many: bool, grid, observed, candidates, widths, image_height_mm, grasp_width_offset, LR_flip, invert_affine,
+           stride, contact_depth, out, validate) -> torch.Tensor:
+    """`score_poses` (`widths` (B,), rows (B, P, 5), gsd_mesh_pose_score) and, with `many`, `score_poses_widths` (`widths` (B, G),
+    rows (B, P, G, 5), gsd_mesh_pose_score_widths): the same checks, view and call, `what` the public name for the messages."""
+    _check_tensors(what, grid, (("observed", observed, "(B, 2, H, W)"), ("candidates", candidates, "(B, P, 3) or (P, 3)"),
+                                ("widths" if many else "grasp_widths", widths, "(B, G)" if many else "(B,)")))
+    if observed.dim() != 4 or observed.shape[1] != 2 or min(observed.shape) < 1:
+        raise MeshDepthError(f"{what}: observed must be (B, 2, H, W) with B, H, W >= 1, got {tuple(observed.shape)}")
+    b, _, h, w = (int(d) for d in observed.shape)
+    if candidates.dim() == 2:
+        candidates = candidates.unsqueeze(0).expand(b, -1, -1)
+    if candidates.dim() != 3 or candidates.shape[0] != b or candidates.shape[2] != 3 or candidates.shape[1] < 1:
+        raise MeshDepthError(f"{what}: candidates must be ({b}, P, 3) or (P, 3) with P >= 1, got {tuple(candidates.shape)}")
+    p = int(candidates.shape[1])
+    if many:
+        if widths.dim() != 2 or widths.shape[0] != b or not 1 <= widths.shape[1] <= POSE_WIDTHS_MAX:
+            raise MeshDepthError(f"{what}: widths must be ({b}, G) with 1 <= G <= {POSE_WIDTHS_MAX}, got {tuple(widths.shape)}")
+    elif tuple(widths.shape) != (b,):
+        raise MeshDepthError(f"{what}: {b} observations but grasp_widths of shape {tuple(widths.shape)}")
+    g = tuple(int(d) for d in widths.shape[1:])          # (G,) or (): where G stands in the shapes and in the argument lists
+    observed, candidates, widths = observed.contiguous(), candidates.contiguous(), widths.contiguous()
+    mpp = float(image_height_mm) / h
+    if not (math.isfinite(mpp) and mpp > 0.0):
+        raise MeshDepthError(f"{what}: image_height_mm {image_height_mm!r} must be finite and positive")
+    offset = float(grasp_width_offset)
+    if not math.isfinite(offset):
+        raise MeshDepthError(f"{what}: grasp_width_offset must be finite, got {grasp_width_offset!r}")
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
+        raise MeshDepthError(f"{what}: stride must be an integer >= 1, got {stride!r}")
+    depth = float(contact_depth)
+    if not (math.isfinite(depth) and depth >= 0.0):
+        raise MeshDepthError(f"{what}: contact_depth must be finite and >= 0, got {contact_depth!r}")
+    out = _out_tensor(what, grid, out, (b, p) + g + (POSE_ROW,), torch.float64)
+    entry = "gsd_mesh_pose_score_widths" if many else "gsd_mesh_pose_score"          # from the module's `lib`, at every call
+    words = int(getattr(lib, entry + "_workspace")(b, p, *g, h, w, int(stride)))
+    if words < 1:
+        raise MeshDepthError(f"{what}: {b} x {p} candidates{f' x {g[0]} widths' if many else ''} of {h} x {w} at stride {stride} are "
+                             "more than one launch takes (2^31 - 1 blocks or rows): score them in parts")
+    if validate:
+        _check_widths(what, widths, offset)
+    view = _mesh_view(grid, mpp, offset, LR_flip, invert_affine)
+    with torch.cuda.device(grid.device):
+        ws = torch.empty((words,), device=grid.device, dtype=torch.float64)
+        check(getattr(lib, entry)(C.byref(grid.grid), C.byref(view), grid.records.data_ptr(), grid.triangles, grid.cells.data_ptr(),
+                                  grid.list.data_ptr(), grid.list.numel(), observed.data_ptr(), b, candidates.data_ptr(),
+                                  widths.data_ptr(), p, *g, h, w, int(stride), depth, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  L.stream_ptr()), entry[4:])
+    return out
+
+
 def score_poses(grid: MeshGrid, observed: torch.Tensor, candidates: torch.Tensor, grasp_widths: torch.Tensor,
                 image_height_mm: float = 12.0, grasp_width_offset: float = 0.0, LR_flip: bool = False, invert_affine: bool = False,
                 stride: int = 1, contact_depth: float = 0.0, out: Optional[torch.Tensor] = None, validate: bool = True) -> torch.Tensor:
@@ -417,63 +490,8 @@ def score_poses(grid: MeshGrid, observed: torch.Tensor, candidates: torch.Tensor
     `validate` is `render_depth`'s: by default the smallest grasp width + offset is read back (the call's only synchronisation)
     and a negative or non-finite one raises MeshDepthError; with `validate=False` nothing is synchronised and such an
     observation's rows are five NaN each."""
-    if not isinstance(grid, MeshGrid):
-        raise MeshDepthError(f"score_poses: grid must be a MeshGrid, got {type(grid).__name__}")
-    for name, t, shape in (("observed", observed, "(B, 2, H, W)"), ("candidates", candidates, "(B, P, 3) or (P, 3)"),
-                           ("grasp_widths", grasp_widths, "(B,)")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
-            raise MeshDepthError(f"score_poses: {name} must be a float32 {shape} tensor on the GPU, got "
-                                 f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')}")
-        if t.device != grid.device:
-            raise MeshDepthError(f"score_poses: {name} is on {t.device}, the mesh on {grid.device}")
-    if observed.dim() != 4 or observed.shape[1] != 2 or min(observed.shape) < 1:
-        raise MeshDepthError(f"score_poses: observed must be (B, 2, H, W) with B, H, W >= 1, got {tuple(observed.shape)}")
-    b, _, h, w = (int(d) for d in observed.shape)
-    if candidates.dim() == 2:
-        candidates = candidates.unsqueeze(0).expand(b, -1, -1)
-    if candidates.dim() != 3 or candidates.shape[0] != b or candidates.shape[2] != 3 or candidates.shape[1] < 1:
-        raise MeshDepthError(f"score_poses: candidates must be ({b}, P, 3) or (P, 3) with P >= 1, got {tuple(candidates.shape)}")
-    p = int(candidates.shape[1])
-    if tuple(grasp_widths.shape) != (b,):
-        raise MeshDepthError(f"score_poses: {b} observations but grasp_widths of shape {tuple(grasp_widths.shape)}")
-    observed, candidates, grasp_widths = observed.contiguous(), candidates.contiguous(), grasp_widths.contiguous()
-    mpp = float(image_height_mm) / h
-    if not (math.isfinite(mpp) and mpp > 0.0):
-        raise MeshDepthError(f"score_poses: image_height_mm {image_height_mm!r} must be finite and positive")
-    offset = float(grasp_width_offset)
-    if not math.isfinite(offset):
-        raise MeshDepthError(f"score_poses: grasp_width_offset must be finite, got {grasp_width_offset!r}")
-    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
-        raise MeshDepthError(f"score_poses: stride must be an integer >= 1, got {stride!r}")
-    depth = float(contact_depth)
-    if not (math.isfinite(depth) and depth >= 0.0):
-        raise MeshDepthError(f"score_poses: contact_depth must be finite and >= 0, got {contact_depth!r}")
-    if out is None:
-        out = torch.empty((b, p, POSE_ROW), device=grid.device, dtype=torch.float64)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != grid.device or not out.is_contiguous()
-          or tuple(out.shape) != (b, p, POSE_ROW)):
-        raise MeshDepthError(f"score_poses: out must be a contiguous float64 ({b}, {p}, {POSE_ROW}) tensor on {grid.device}")
-    words = int(lib.gsd_mesh_pose_score_workspace(b, p, h, w, int(stride)))
-    if words < 1:
-        raise MeshDepthError(f"score_poses: {b} x {p} candidates of {h} x {w} at stride {stride} are more than one launch takes "
-                             "(2^31 - 1 blocks): score them in parts")
-    if validate:
-        g_min = float((grasp_widths + offset).min())          # NaN propagates through min
-        if not (g_min >= 0.0) or not bool(torch.isfinite(grasp_widths).all()):
-            raise MeshDepthError(f"score_poses: grasp width + offset must be finite and >= 0, the smallest is {g_min!r}")
-    view = L.gsd_mesh_view()
-    view.mpp, view.width_offset = mpp, offset
-    view.swap_axes, view.invert_affine, view.lr_flip, view.reserved = grid.swap_axes, int(bool(invert_affine)), int(bool(LR_flip)), 0
-    with torch.cuda.device(grid.device):
-        ws = torch.empty((words,), device=grid.device, dtype=torch.float64)
-        check(lib.gsd_mesh_pose_score(C.byref(grid.grid), C.byref(view), grid.records.data_ptr(), grid.triangles,
-                                      grid.cells.data_ptr(), grid.list.data_ptr(), grid.list.numel(), observed.data_ptr(), b,
-                                      candidates.data_ptr(), grasp_widths.data_ptr(), p, h, w, int(stride), depth, out.data_ptr(),
-                                      ws.data_ptr(), ws.numel(), L.stream_ptr()), "mesh_pose_score")
-    return out
-
-
-POSE_WIDTHS_MAX = L.GSD_POSE_WIDTHS_MAX      # widths per observation that one `score_poses_widths` call takes
+    return _score("score_poses", False, grid, observed, candidates, grasp_widths, image_height_mm, grasp_width_offset, LR_flip,
+                  invert_affine, stride, contact_depth, out, validate)
 
 
 def score_poses_widths(grid: MeshGrid, observed: torch.Tensor, candidates: torch.Tensor, widths: torch.Tensor,
@@ -488,61 +506,8 @@ def score_poses_widths(grid: MeshGrid, observed: torch.Tensor, candidates: torch
 
     `validate=True` reads the smallest width + offset back once and raises MeshDepthError for a negative or non-finite one;
     `validate=False` reads nothing, and such a (b, :, k) column is five NaN per row (+inf for `pose_cost`)."""
-    if not isinstance(grid, MeshGrid):
-        raise MeshDepthError(f"score_poses_widths: grid must be a MeshGrid, got {type(grid).__name__}")
-    for name, t, shape in (("observed", observed, "(B, 2, H, W)"), ("candidates", candidates, "(B, P, 3) or (P, 3)"),
-                           ("widths", widths, "(B, G)")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
-            raise MeshDepthError(f"score_poses_widths: {name} must be a float32 {shape} tensor on the GPU, got "
-                                 f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')}")
-        if t.device != grid.device:
-            raise MeshDepthError(f"score_poses_widths: {name} is on {t.device}, the mesh on {grid.device}")
-    if observed.dim() != 4 or observed.shape[1] != 2 or min(observed.shape) < 1:
-        raise MeshDepthError(f"score_poses_widths: observed must be (B, 2, H, W) with B, H, W >= 1, got {tuple(observed.shape)}")
-    b, _, h, w = (int(d) for d in observed.shape)
-    if candidates.dim() == 2:
-        candidates = candidates.unsqueeze(0).expand(b, -1, -1)
-    if candidates.dim() != 3 or candidates.shape[0] != b or candidates.shape[2] != 3 or candidates.shape[1] < 1:
-        raise MeshDepthError(f"score_poses_widths: candidates must be ({b}, P, 3) or (P, 3) with P >= 1, got {tuple(candidates.shape)}")
-    p = int(candidates.shape[1])
-    if widths.dim() != 2 or widths.shape[0] != b or not 1 <= widths.shape[1] <= POSE_WIDTHS_MAX:
-        raise MeshDepthError(f"score_poses_widths: widths must be ({b}, G) with 1 <= G <= {POSE_WIDTHS_MAX}, got {tuple(widths.shape)}")
-    g = int(widths.shape[1])
-    observed, candidates, widths = observed.contiguous(), candidates.contiguous(), widths.contiguous()
-    mpp = float(image_height_mm) / h
-    if not (math.isfinite(mpp) and mpp > 0.0):
-        raise MeshDepthError(f"score_poses_widths: image_height_mm {image_height_mm!r} must be finite and positive")
-    offset = float(grasp_width_offset)
-    if not math.isfinite(offset):
-        raise MeshDepthError(f"score_poses_widths: grasp_width_offset must be finite, got {grasp_width_offset!r}")
-    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
-        raise MeshDepthError(f"score_poses_widths: stride must be an integer >= 1, got {stride!r}")
-    depth = float(contact_depth)
-    if not (math.isfinite(depth) and depth >= 0.0):
-        raise MeshDepthError(f"score_poses_widths: contact_depth must be finite and >= 0, got {contact_depth!r}")
-    if out is None:
-        out = torch.empty((b, p, g, POSE_ROW), device=grid.device, dtype=torch.float64)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != grid.device or not out.is_contiguous()
-          or tuple(out.shape) != (b, p, g, POSE_ROW)):
-        raise MeshDepthError(f"score_poses_widths: out must be a contiguous float64 ({b}, {p}, {g}, {POSE_ROW}) tensor on {grid.device}")
-    words = int(lib.gsd_mesh_pose_score_widths_workspace(b, p, g, h, w, int(stride)))
-    if words < 1:
-        raise MeshDepthError(f"score_poses_widths: {b} x {p} candidates x {g} widths of {h} x {w} at stride {stride} are more than "
-                             "one launch takes (2^31 - 1 blocks or rows): score them in parts")
-    if validate:
-        g_min = float((widths + offset).min())          # NaN propagates through min
-        if not (g_min >= 0.0) or not bool(torch.isfinite(widths).all()):
-            raise MeshDepthError(f"score_poses_widths: grasp width + offset must be finite and >= 0, the smallest is {g_min!r}")
-    view = L.gsd_mesh_view()
-    view.mpp, view.width_offset = mpp, offset
-    view.swap_axes, view.invert_affine, view.lr_flip, view.reserved = grid.swap_axes, int(bool(invert_affine)), int(bool(LR_flip)), 0
-    with torch.cuda.device(grid.device):
-        ws = torch.empty((words,), device=grid.device, dtype=torch.float64)
-        check(lib.gsd_mesh_pose_score_widths(C.byref(grid.grid), C.byref(view), grid.records.data_ptr(), grid.triangles,
-                                             grid.cells.data_ptr(), grid.list.data_ptr(), grid.list.numel(), observed.data_ptr(), b,
-                                             candidates.data_ptr(), widths.data_ptr(), p, g, h, w, int(stride), depth,
-                                             out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr()), "mesh_pose_score_widths")
-    return out
+    return _score("score_poses_widths", True, grid, observed, candidates, widths, image_height_mm, grasp_width_offset, LR_flip,
+                  invert_affine, stride, contact_depth, out, validate)
 
 
 _COSTS = ("mse", "l1", "iou")
@@ -586,6 +551,19 @@ def first_argmin(cost: torch.Tensor) -> torch.Tensor:
     return torch.where(cost == best, index, torch.full_like(index, cost.shape[1])).min(dim=1).values.clamp_(max=cost.shape[1] - 1)
 
 
+def _axis_schedule(half: np.float32, n: int, levels: int) -> Tuple[np.ndarray, np.ndarray]:
+    """One axis of a search lattice in fp32: (half_spans (levels + 1,), offsets (levels, n)), step = half_spans[l + 1] =
+    2 * half_spans[l] / (n - 1), offsets[l, i] = (i - (n - 1) / 2) * step."""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1:
+        raise MeshDepthError(f"estimate_pose: levels must be an integer >= 1, got {levels!r}")
+    spans, offsets = [np.float32(half)], []
+    for _ in range(int(levels)):
+        step = (np.float32(2.0) * spans[-1]) / np.float32(n - 1)
+        offsets.append((np.arange(n, dtype=np.float32) - np.float32((n - 1) // 2)) * step)
+        spans.append(step)
+    return np.asarray(spans, dtype=np.float32), np.stack(offsets)
+
+
 def search_schedule(half_span: Sequence[float], counts: Sequence[int] = (7, 7, 9), levels: int = 4) -> Tuple[np.ndarray, np.ndarray]:
     """The lattices of `estimate_pose`, on the host in fp32: (half_spans (levels + 1, 3), offsets (levels, P, 3)).
     Level l has the half-span half_spans[l] and the step half_spans[l + 1] = 2 * half_spans[l] / (n - 1) per axis; its candidate
@@ -597,22 +575,15 @@ def search_schedule(half_span: Sequence[float], counts: Sequence[int] = (7, 7, 9
         counts = ()
     if len(counts) != 3 or any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 3 or n % 2 == 0 for n in counts):
         raise MeshDepthError(f"estimate_pose: counts must be three odd integers >= 3, got {counts!r}")
-    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1:
-        raise MeshDepthError(f"estimate_pose: levels must be an integer >= 1, got {levels!r}")
     if isinstance(half_span, torch.Tensor):
         half_span = half_span.detach().cpu().numpy()
     half = np.asarray(half_span, dtype=np.float32)
     if half.shape != (3,) or not np.isfinite(half).all() or (half < 0).any():
         raise MeshDepthError(f"estimate_pose: half_span must be three finite values >= 0 (t1 [m], t2 [m], theta [rad]), got {half_span!r}")
-    div = np.asarray([n - 1 for n in counts], dtype=np.float32)
-    spans, offsets = [half], []
-    for _ in range(int(levels)):
-        step = (np.float32(2.0) * spans[-1]) / div
-        axes = [(np.arange(n, dtype=np.float32) - np.float32((n - 1) // 2)) * step[a] for a, n in enumerate(counts)]
-        mesh = np.meshgrid(*axes, indexing="ij")
-        offsets.append(np.stack([m.reshape(-1) for m in mesh], axis=1).astype(np.float32))
-        spans.append(step)
-    return np.stack(spans), np.stack(offsets)
+    axes = [_axis_schedule(half[a], n, levels) for a, n in enumerate(counts)]
+    offsets = [np.stack([m.reshape(-1) for m in np.meshgrid(*(offs[lvl] for _, offs in axes), indexing="ij")], axis=1)
+               for lvl in range(int(levels))]
+    return np.stack([spans for spans, _ in axes], axis=1), np.stack(offsets)
 
 
 def width_schedule(width_half_span: float, width_count: int, levels: int = 4) -> Tuple[np.ndarray, np.ndarray]:
@@ -623,20 +594,13 @@ def width_schedule(width_half_span: float, width_count: int, levels: int = 4) ->
     n = width_count
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 3 or n % 2 == 0 or n > POSE_WIDTHS_MAX:
         raise MeshDepthError(f"estimate_pose: width_count must be 1 or an odd integer in 3..{POSE_WIDTHS_MAX}, got {width_count!r}")
-    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1:
-        raise MeshDepthError(f"estimate_pose: levels must be an integer >= 1, got {levels!r}")
     try:
         half = np.float32(width_half_span)
     except (TypeError, ValueError):
         half = np.float32("nan")
     if half.shape != () or not np.isfinite(half) or not half > 0:
         raise MeshDepthError(f"estimate_pose: width_half_span must be a finite value > 0 [mm] for a width axis, got {width_half_span!r}")
-    spans, offsets = [half], []
-    for _ in range(int(levels)):
-        step = (np.float32(2.0) * spans[-1]) / np.float32(n - 1)
-        offsets.append((np.arange(n, dtype=np.float32) - np.float32((n - 1) // 2)) * step)
-        spans.append(step)
-    return np.asarray(spans, dtype=np.float32), np.stack(offsets).astype(np.float32)
+    return _axis_schedule(half, n, levels)
 
 
 class PoseEstimate:
@@ -708,9 +672,7 @@ def estimate_pose(grid: MeshGrid, observed: torch.Tensor, grasp_widths: torch.Te
                 or tuple(grasp_widths.shape) != (b,)):
             raise MeshDepthError(f"estimate_pose: grasp_widths must be a float32 ({b},) tensor on {grid.device}")
         if validate:
-            g_min = float((grasp_widths + float(grasp_width_offset)).min())          # NaN propagates through min
-            if not (g_min >= 0.0) or not bool(torch.isfinite(grasp_widths).all()):
-                raise MeshDepthError(f"estimate_pose: grasp width + offset must be finite and >= 0, the smallest is {g_min!r}")
+            _check_widths("estimate_pose", grasp_widths, float(grasp_width_offset))
     with torch.cuda.device(grid.device):
         offs = torch.from_numpy(offsets).to(grid.device)          # (levels, P, 3)
         trace = torch.empty((levels, b), device=grid.device, dtype=torch.float64)

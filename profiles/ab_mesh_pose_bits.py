@@ -1,13 +1,14 @@
-"""A/B of bit-identity between two builds of libgsd.so over render_depth and score_poses (md_pixel was split
-into md_surface and md_depth, and the two launches that call it must not change by a bit): seeded inputs, the sha256 of every
-output compared between the two libraries.  The cases: the three test meshes at 24 x 31, 40 x 53 and 80 x 106 with both channel
+"""A/B of bit-identity between two builds of libgsd.so over render_depth, score_poses and score_poses_widths (DESIGN.md section 18:
+whatever is done to the kernels behind them, no output may change by a bit): seeded inputs, the sha256 of every output compared
+between the two libraries.  The cases: the three test meshes at 24 x 31, 40 x 53 and 80 x 106 with both channel
 orders and pose senses, widths that include 0, one at which nothing touches, a refused one (validate=False: NaN), score_poses at
-strides 1, 2 and 3 with two contact depths on noisy observations with a NaN and a -inf pixel, and the subdivision-6 icosphere
-at 320 x 427.
+strides 1, 2 and 3 with two contact depths on noisy observations with a NaN and a -inf pixel, score_poses_widths on the same
+observations, strides and contact depths at G = 1, 2, 3, 5 and 32 with a refused width in one column, and the subdivision-6
+icosphere at 320 x 427.
 
 usage (GPU box, repo root): python profiles/ab_mesh_pose_bits.py LIB_A LIB_B [--tree-a DIR] [--out profiles/mesh_pose_width_outputs_equal.txt]
 --tree-a: the checkout whose gelslim_depth_amd package and tests/ helpers drive LIB_A (the parent commit's: its library lacks
-the symbols that this tree's binding declares, and render_depth and score_poses are the same text in both).
+the symbols that this tree's binding declares; it has to have the three functions, with these arguments).
 Each library runs in a fresh child process of its own (GSD_LIB_PATH) under its own time limit; the second starts only if the
 first succeeded.  Writes one line per case ("equal" / "DIFFER") and exits non-zero unless all are equal."""
 import hashlib
@@ -28,7 +29,7 @@ def child(out_path):
     import torch
     import mesh_depth_ref as R
     import mesh_pose_ref as P
-    from gelslim_depth_amd.mesh_depth import MeshGrid, render_depth, score_poses
+    from gelslim_depth_amd.mesh_depth import MeshGrid, render_depth, score_poses, score_poses_widths
     lines = []
 
     def emit(case, t):
@@ -54,6 +55,17 @@ def child(out_path):
                         rows = score_poses(grid, seen.contiguous(), cand.contiguous(), w2, 12.0, 0.1, flip, invert, stride, contact,
                                            validate=False)
                         emit(f"score_poses {name} {size[0]}x{size[1]} P={p} widths {w2.tolist()} stride {stride} contact {contact} "
+                             f"flip={flip} invert={invert}", rows)
+                for g_count in (1, 2, 3, 5, 32):          # the same observations; one refused column (G = 1: one refused observation)
+                    wg = widths[3:5, None] + torch.linspace(-0.6, 0.4, g_count, device="cuda")[None, :]
+                    if g_count > 1:
+                        wg[:, g_count // 2] = -1.0
+                    else:
+                        wg[1, 0] = -1.0
+                    for stride, contact in ((1, 0.0), (2, 0.05), (3, 0.0)):
+                        rows = score_poses_widths(grid, seen.contiguous(), cand.contiguous(), wg.contiguous(), 12.0, 0.1, flip, invert,
+                                                  stride, contact, validate=False)
+                        emit(f"score_poses_widths {name} {size[0]}x{size[1]} P={p} G={g_count} stride {stride} contact {contact} "
                              f"flip={flip} invert={invert}", rows)
 
     for name in ("lprism", "sphere4", "ellipsoid"):

@@ -87,7 +87,8 @@ def test_the_twin_recovers_the_width_of_a_smooth_asymmetric_object():
 
 def test_width_kernels_use_no_scratch():
     """The loop over the widths of mesh_pose_score_widths keeps its per-width values in registers (groups of at most four, fully
-    unrolled): no private array, no scratch, in every instantiation, and none in the rows kernel (device-only compile, ~5 s)."""
+    unrolled): no private array, no scratch, in every instantiation, none in mesh_pose_score, and none in the one rows kernel that
+    serves them all (device-only compile, ~5 s)."""
     import re
     import shutil
     import subprocess
@@ -101,8 +102,9 @@ def test_width_kernels_use_no_scratch():
     scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
     lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)]
     assert len(names) == len(scratch) == len(lds)
-    score = {n: (s, m) for n, s, m in zip(names, scratch, lds) if "mesh_pose_score_widths" in n}
-    rows = {n: (s, m) for n, s, m in zip(names, scratch, lds) if "mesh_pose_rows_widths" in n}
-    assert len(score) >= 1 and len(rows) == 1, r.stderr[-2000:]
-    assert all(v == (0, 4 * 32 * 5 * 8) for v in score.values()), score          # 5 KiB: four waves' partials of 32 widths
+    score = {n: (s, m) for n, s, m in zip(names, scratch, lds) if "mesh_pose_score" in n}
+    rows = {n: (s, m) for n, s, m in zip(names, scratch, lds) if "mesh_pose_rows" in n}
+    assert len(score) == 3 and len(rows) == 1, r.stderr[-2000:]          # one width, CH = 2, CH = 4; one rows kernel for every G
+    # four waves' partials: of 32 widths (5 KiB) in the kernel for several, of the one width in mesh_pose_score
+    assert all(v == (0, 4 * 32 * 5 * 8 if "widths" in n else 4 * 5 * 8) for n, v in score.items()), score
     assert all(v == (0, 0) for v in rows.values()), rows
