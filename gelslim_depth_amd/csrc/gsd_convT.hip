@@ -1,42 +1,43 @@
 // gsd_convT.hip -- ConvTranspose2d(k=2, s=2) forward and its data gradient as flat implicit GEMMs on
-// v_mfma_f32_16x16x4_f32 (gfx950).  "Flat": the GEMM column is a run of BN consecutive pixels of one
-// image plane (no halo), because a 2x2 stride-2 transposed convolution has no spatial overlap.
+// v_mfma_f32_16x16x4_f32 (gfx950).  "Flat": the GEMM column is a run of consecutive pixels (no halo), because a 2x2
+// stride-2 transposed convolution has no spatial overlap.
 //
 //   D[m][pixel] = sum_k  Wt[k][m] * B[k][pixel]
 //
-//   FWD    k = ci, m = co*4+kh*2+kw, B = x[ci][pixel]; pixel-shuffle + bias epilogue
-//          (replaces aten::conv_transpose2d at /root/reference/gelslim_depth/models/unet.py:36,41).
-//   DGRAD  k = co*4+kh*2+kw, m = ci, B = dy[co][2h+kh][2w+kw] (space-to-depth staging)
-//          (the dX half of aten::convolution_backward for the same operator).
+//   forward  k = ci, m = co*4+kh*2+kw, B = relu(bn(x))[ci][pixel]; pixel-shuffle + bias epilogue
+//            (replaces aten::conv_transpose2d at unet.py:36,41 of the reference).
+//   dX       k = co*4+kh*2+kw, m = ci, B = dy[co][2h+kh][2w+kw] (space-to-depth)
+//            (the dX half of aten::convolution_backward for the same operator).
 //
-// Pixels sit on the MFMA column (lane&15), so the NCHW store of one accumulator register is 16
-// consecutive floats per lane group.  FWD applies the producer's deferred BatchNorm scale/shift +
-// ReLU on the way into LDS, so relu(bn(x)) never exists in HBM.
-//
-// Block = 256 threads = 4 waves, wave tile 64 (m) x 64 (pixels) = 4x4 MFMA tiles (64 accumulator
-// VGPRs); block tile 64x256 (WM=1,WN=4) for M<=64, 128x128 (WM=2,WN=2) otherwise.  K is walked in
-// chunks of 16 k-rows (4 k-steps); the next chunk's global loads are issued before the current
-// chunk's MFMAs (register prefetch) and written to LDS after them.  The 3x3 convolutions, which
-// dominate the step, live in gsd_conv3x3.hip / gsd_wgrad.hip; these two operators are ~4% of it.
+// Both run on the LDS-DMA template of the conv3x3 kernels: block tile 128 (m) x 128 pixels of the whole batch's flattened pixel
+// grid, K in chunks of 32 k-rows, both operand tiles by global_load_lds into a double-buffered LDS image, two blocks per CU
+// (convT_fwd_dma_kernel, weight layout mode 6; convT_dgrad_dma_kernel, mode 7, plain or fused with the backward of the
+// relu(bn(raw)) that produced the ConvT's input).  The dX kernel reads pixel PAIRS of dy: an odd-width dy without two readable
+// floats behind it (gsd_src.slack) -- and any dX under the tuning switch GSD_CONVT_DG_DMA=0 -- takes the register-staged dX
+// kernel below instead (convT_dgrad_staged_kernel, weight layout mode 3).  Which of the two a call runs is decided on the host,
+// once: gsd_convT_host.h holds the rule, the operand checks and the plans of all three kernels.
+// The 3x3 convolutions, which dominate the step, live in gsd_conv3x3*.hip / gsd_wgrad*.hip; these two operators are ~4% of it.
 // The weight and bias gradients of this operator: gsd_convT_wgrad.hip.
-#include "gsd_common.h"
+#include "gsd_convT_host.h"
 
 namespace {
 
-enum : int { CT_FWD = 1, CT_DGRAD = 2 };
-
-struct ConvTParams {
-  SrcD src;
-  DstD dst;
-  const float* wt;    // [K][Mpad] (gsd_weight_layout modes 2/3)
-  const float* bias;  // FWD only, may be null
+// Register-staged dX.  Block = 256 threads = 4 waves, wave tile 64 (m) x 64 (pixels) = 4x4 MFMA tiles (64 accumulator VGPRs);
+// block tile 64x256 (WM=1,WN=4) for Cin<=64, 128x128 (WM=2,WN=2) otherwise, a column = a run of BN consecutive pixels of one
+// image plane.  Pixels sit on the MFMA column (lane&15), so the NCHW store of one accumulator register is 16 consecutive floats
+// per lane group.  K is walked in chunks of 16 k-rows (4 output channels, 4 k-steps); the next chunk's global loads are issued
+// before the current chunk's MFMAs (register prefetch) and written to LDS after them.
+struct ConvTDgStagedParams {
+  SrcD src;           // dy (Cout, 2H, 2W), plain
+  DstD dst;           // dx (Cin, H, W)
+  const float* wt;    // [K][Mpad] (gsd_weight_layout mode 3)
   int K, M, Mpad, nchunks, mblocks;
-  int N, H, W;        // the LOW-resolution plane (convT input / dgrad output)
+  int N, H, W;        // the LOW-resolution plane
   int tiles_flat;
 };
 
-template <int MODE, int WM, int WN>
-__global__ __launch_bounds__(256) void convT_kernel(const ConvTParams P) {
+template <int WM, int WN>
+__global__ __launch_bounds__(256) void convT_dgrad_staged_kernel(const ConvTDgStagedParams P) {
   constexpr int MT = 4, NT = 4;
   constexpr int BM = WM * 64, BN = WN * 64;
   constexpr int KSTEPS = 4;
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(256) void convT_kernel(const ConvTParams P) {
   constexpr int PS = BN + 16;
   constexpr int W4 = WROWS * BM / 4;
   constexpr int NW4 = (W4 + 255) / 256;
-  constexpr int NXE = MODE == CT_FWD ? (16 * BN / 256) : (8 * BN / 256);
+  constexpr int NXE = 8 * BN / 256;
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Wl = smem;
@@ -75,11 +76,8 @@ __global__ __launch_bounds__(256) void convT_kernel(const ConvTParams P) {
   const int fq = tid % BN;
   const int frow0 = tid / BN;  // 0 when BN==256, 0/1 when BN==128
   const bool f_ok = (p0 + fq) < HW;
-  int fh = 0, fw = 0;
-  if constexpr (MODE == CT_DGRAD) {
-    fh = (p0 + fq) / P.W;
-    fw = (p0 + fq) - fh * P.W;
-  }
+  const int fh = (p0 + fq) / P.W;
+  const int fw = (p0 + fq) - fh * P.W;
   int wv_off[NW4], wl_off[NW4];
 #pragma unroll
   for (int i = 0; i < NW4; ++i) {
@@ -90,9 +88,7 @@ __global__ __launch_bounds__(256) void convT_kernel(const ConvTParams P) {
     wl_off[i] = r * WS + c4 * 4;
   }
 
-  float xr[NXE];
-  float xr2[MODE == CT_DGRAD ? NXE : 1];  // DGRAD loads float2 (kw = 0,1)
-  unsigned xvalid = 0;
+  float xr[NXE], xr2[NXE];  // a load is the float2 (kw = 0, 1) of a pixel
   f32x4 wr[NW4];
 
   auto prefetch = [&](int chunk) {
@@ -103,60 +99,32 @@ __global__ __launch_bounds__(256) void convT_kernel(const ConvTParams P) {
       if (wv_off[i] >= 0) v = *reinterpret_cast<const f32x4*>(wbase + wv_off[i]);
       wr[i] = v;
     }
-    xvalid = 0;
-    if constexpr (MODE == CT_FWD) {
 #pragma unroll
-      for (int i = 0; i < NXE; ++i) {
-        const int c = chunk * 16 + frow0 + i * (256 / BN);
-        const bool ok = f_ok && c < P.K;
-        float v = 0.f;
-        if (ok) v = P.src.p[(long long)n * P.src.ns + (long long)c * P.src.cs + p0 + fq];
-        xr[i] = v;
-        xvalid |= ok ? (1u << i) : 0u;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NXE; ++i) {
-        const int row = frow0 + i * (256 / BN);  // 0..7 : (co_i, kh)
-        const int co = chunk * 4 + (row >> 1);
-        const int kh = row & 1;
-        const bool ok = f_ok && co < P.src.C;
-        float2 v = make_float2(0.f, 0.f);
-        if (ok)
-          v = *reinterpret_cast<const float2*>(P.src.p + (long long)n * P.src.ns + (long long)co * P.src.cs +
-                                               (long long)(2 * fh + kh) * P.src.W + 2 * fw);
-        xr[i] = v.x;
-        xr2[i] = v.y;
-      }
+    for (int i = 0; i < NXE; ++i) {
+      const int row = frow0 + i * (256 / BN);  // 0..7 : (co_i, kh)
+      const int co = chunk * 4 + (row >> 1);
+      const int kh = row & 1;
+      const bool ok = f_ok && co < P.src.C;
+      float2 v = make_float2(0.f, 0.f);
+      if (ok)
+        v = *reinterpret_cast<const float2*>(P.src.p + (long long)n * P.src.ns + (long long)co * P.src.cs +
+                                             (long long)(2 * fh + kh) * P.src.W + 2 * fw);
+      xr[i] = v.x;
+      xr2[i] = v.y;
     }
   };
 
-  auto stage = [&](int chunk) {
+  auto stage = [&]() {
 #pragma unroll
     for (int i = 0; i < NW4; ++i) {
       if (tid + i * 256 < W4) *reinterpret_cast<f32x4*>(&Wl[wl_off[i]]) = wr[i];
     }
-    if constexpr (MODE == CT_FWD) {
 #pragma unroll
-      for (int i = 0; i < NXE; ++i) {
-        const int ch = frow0 + i * (256 / BN);
-        const int c = chunk * 16 + ch;
-        float sc = 1.f, sh = 0.f;
-        if (P.src.scale != nullptr && c < P.K) {
-          sc = P.src.scale[c];
-          sh = P.src.shift[c];
-        }
-        const bool ok = (xvalid >> i) & 1u;
-        Xl[ch * PS + fq] = ok ? apply_affine(xr[i], sc, sh, P.src.relu) : 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NXE; ++i) {
-        const int row = frow0 + i * (256 / BN);
-        const int k = (row >> 1) * 4 + (row & 1) * 2;
-        Xl[k * PS + fq] = xr[i];
-        Xl[(k + 1) * PS + fq] = xr2[i];
-      }
+    for (int i = 0; i < NXE; ++i) {
+      const int row = frow0 + i * (256 / BN);
+      const int k = (row >> 1) * 4 + (row & 1) * 2;
+      Xl[k * PS + fq] = xr[i];
+      Xl[(k + 1) * PS + fq] = xr2[i];
     }
   };
 
@@ -170,7 +138,7 @@ __global__ __launch_bounds__(256) void convT_kernel(const ConvTParams P) {
   prefetch(0);
   for (int chunk = 0; chunk < P.nchunks; ++chunk) {
     __syncthreads();  // everyone finished reading the previous chunk's LDS image
-    stage(chunk);
+    stage();
     __syncthreads();
     if (chunk + 1 < P.nchunks) prefetch(chunk + 1);
 #pragma unroll
@@ -189,43 +157,22 @@ __global__ __launch_bounds__(256) void convT_kernel(const ConvTParams P) {
 
   // ---- epilogue -------------------------------------------------------------------------------
   const DstD& D = P.dst;
-  if constexpr (MODE == CT_FWD) {
-    // one accumulator quad = the 2x2 output patch of (co, pixel): two float2 stores
 #pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      const int co = (m0 + wm * 64 + m * 16 + j * 4) >> 2;
-      if (co < D.C) {
-        const float bz = P.bias != nullptr ? P.bias[co] : 0.f;
+  for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          if (opix[t] >= 0) {
-            const int p = p0 + opix[t];
-            const int h = p / P.W, w = p - h * P.W;
-            float* o = D.p + (long long)n * D.ns + (long long)co * D.cs + (long long)(2 * h) * D.W + 2 * w;
-            *reinterpret_cast<float2*>(o) = make_float2(acc[m][t][0] + bz, acc[m][t][1] + bz);
-            *reinterpret_cast<float2*>(o + D.W) = make_float2(acc[m][t][2] + bz, acc[m][t][3] + bz);
-          }
-        }
+    for (int reg = 0; reg < 4; ++reg) {
+      const int ci = m0 + wm * 64 + m * 16 + j * 4 + reg;
+      if (ci < D.C) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+          if (opix[t] >= 0) D.p[(long long)n * D.ns + (long long)ci * D.cs + p0 + opix[t]] = acc[m][t][reg];
       }
     }
-  } else {
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int ci = m0 + wm * 64 + m * 16 + j * 4 + reg;
-        if (ci < D.C) {
-#pragma unroll
-          for (int t = 0; t < NT; ++t)
-            if (opix[t] >= 0) D.p[(long long)n * D.ns + (long long)ci * D.cs + p0 + opix[t]] = acc[m][t][reg];
-        }
-      }
-  }
 }
 
 // -------------------------------------------------------------------------------------------------------------------------
-// FWD on the LDS-DMA template of the conv3x3 kernels (the register-staged form above ran at 48 % of the fp32 MFMA peak and
-// stays for DGRAD): block tile 128 (m = co*4+kh*2+kw) x 128 pixels, K walked in chunks of 32 input channels, both operand
+// Forward on the LDS-DMA template of the conv3x3 kernels (a register-staged form like the one above ran at 48 % of the fp32
+// MFMA peak): block tile 128 (m = co*4+kh*2+kw) x 128 pixels, K walked in chunks of 32 input channels, both operand
 // tiles straight from L2/HBM into a double-buffered LDS image by global_load_lds -- weights as 16 one-KiB pieces of a
 // [chunk][32][128] image whose columns are permuted so that a lane's four A operands are one ds_read_b128
 // (gsd_weight_layout mode 6), activations as rows of 128 consecutive pixels of a channel plane (16-byte pieces when the
@@ -633,78 +580,69 @@ __global__ __launch_bounds__(256, 2) void convT_dgrad_dma_kernel(const ConvTDgPa
   }
 }
 
-template <int MODE, int WM, int WN>
-int launch(const ConvTParams& P, int grid, size_t lds, hipStream_t st, const char* what) {
-  hipLaunchKernelGGL((convT_kernel<MODE, WM, WN>), dim3(grid), dim3(256), lds, st, P);
-  GSD_LAUNCH_CHECK(what);
-  return GSD_OK;
-}
-
-// common tail of both entry points: tile choice, grid, launch
-template <int MODE>
-int run(ConvTParams& P, hipStream_t st, const char* what) {
-  const bool wide = P.M <= 64;
-  const int BM = wide ? 64 : 128, BN = wide ? 256 : 128;
-  P.Mpad = round_up(P.M, 64);
-  P.mblocks = ceil_div(P.M, BM);
-  P.tiles_flat = ceil_div(P.H * P.W, BN);
-  const long grid = (long)P.N * P.tiles_flat * P.mblocks;
-  GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "%s: grid too large", what);
-  const size_t lds = (size_t)(16 * (BM + 16) + 16 * (BN + 16)) * sizeof(float);  // <= 24 KB, no attribute needed
-  if (wide) return launch<MODE, 1, 4>(P, (int)grid, lds, st, what);
-  return launch<MODE, 2, 2>(P, (int)grid, lds, st, what);
+// The one launcher of the dX entry points `name`: wt is the caller's mode-`wt_mode` image (7: the LDS-DMA kernel, plain or -- with
+// bw and partials -- fused; 3: the register-staged kernel).  Validates, plans, launches.
+int convT_dgrad_launch(const char* name, int wt_mode, const gsd_src* src, const float* wt, int Cin, int Cout, const gsd_dst* dst,
+                       const ConvTBw& bw, float* partials, int N, int H, int W, hipStream_t st) {
+  const bool dma = wt_mode == 7, fused = bw.raw != nullptr;
+  GSD_REQUIRE(src && dst && wt, GSD_ERR_BAD_ARG, "%s: null argument", name);
+  if (int e = convT_check_sizes(name, Cin, Cout, N, H, W)) return e;
+  // (the plain entry was handed the wrong image: a bad argument; the fused one has no other kernel to offer)
+  GSD_REQUIRE(!dma || convT_dgrad_dma_admits(src, Cin, Cout, N, H, W), fused ? GSD_ERR_UNSUPPORTED : GSD_ERR_BAD_ARG,
+              "%s: a mode-7 weight image needs the LDS-DMA kernel, which these arguments do not admit (an odd W needs src->slack >= 2: "
+              "W = %d, slack %d; N * n_stride must stay below 2^40; gsd_convT2x2_dgrad_bnrelu_partial_rows == 0); build the image with "
+              "the mode gsd_convT2x2_dgrad_layout returns",
+              name, W, src->slack);
+  if (int e = convT_check_dgrad_operands(name, *src, *dst, Cin, Cout, H, W)) return e;
+  ConvTLaunch L;
+  if (!dma) {
+    ConvTDgStagedParams P;
+    P.src = to_srcd(*src);
+    P.dst = to_dstd(*dst);
+    P.wt = wt;
+    if (int e = convT_plan_dgrad_staged(name, P, Cin, Cout, N, H, W, &L)) return e;
+    if (L.wide) return gsd_launch<convT_dgrad_staged_kernel<1, 4>>(name, dim3(L.grid), dim3(256), L.lds, st, P);
+    return gsd_launch<convT_dgrad_staged_kernel<2, 2>>(name, dim3(L.grid), dim3(256), L.lds, st, P);
+  }
+  GSD_REQUIRE(((uintptr_t)wt & 15) == 0, GSD_ERR_BAD_ARG, "%s: the weight image must be 16-byte aligned", name);
+  ConvTDgParams Q;
+  Q.src = to_srcd(*src);
+  Q.dst = to_dstd(*dst);
+  Q.wt = wt;
+  Q.bw_raw = bw.raw; Q.bw_scale = bw.scale; Q.bw_shift = bw.shift; Q.bw_mean = bw.mean; Q.bw_invstd = bw.invstd;
+  Q.partials = partials;
+  if (int e = convT_plan_dgrad(name, Q, Cin, Cout, N, H, W, fused, &L)) return e;
+  if (fused) return gsd_launch<convT_dgrad_dma_kernel<true>>(name, dim3(L.grid), dim3(256), L.lds, st, Q);
+  return gsd_launch<convT_dgrad_dma_kernel<false>>(name, dim3(L.grid), dim3(256), L.lds, st, Q);
 }
 
 }  // namespace
 
 extern "C" int gsd_convT2x2(const gsd_src* src, const float* wt, const float* bias, int Cin, int Cout,
                             const gsd_dst* dst, int N, int H, int W, void* stream) {
-  GSD_REQUIRE(src && dst && wt, GSD_ERR_BAD_ARG, "gsd_convT2x2: null argument");
-  GSD_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, GSD_ERR_BAD_ARG, "gsd_convT2x2: bad sizes");
-  if (int e = gsd_check_src(*src, "gsd_convT2x2 src")) return e;
-  // (the epilogue addresses output rows through w_stride: a pitched destination -- the up-sampled half of a decoder level's
-  //  concat buffer -- is written in place; only the 8-byte stores ask for an even pitch)
-  if (int e = gsd_check_dst(*dst, "gsd_convT2x2 dst", true)) return e;
-  GSD_REQUIRE((dst->w_stride & 1) == 0, GSD_ERR_UNSUPPORTED, "gsd_convT2x2: dst needs an even row pitch (got %d)", dst->w_stride);
-  GSD_REQUIRE(src->C == Cin && src->H == H && src->W == W && src->off_h == 0 && src->off_w == 0, GSD_ERR_BAD_ARG,
-              "gsd_convT2x2: src must be the full (Cin,H,W) tensor");
-  GSD_REQUIRE(dst->C == Cout && dst->H == 2 * H && dst->W == 2 * W && dst->off_h == 0 && dst->off_w == 0,
-              GSD_ERR_BAD_ARG, "gsd_convT2x2: dst must be (Cout,2H,2W)");
-  GSD_REQUIRE(((uintptr_t)dst->ptr & 7) == 0 && (dst->c_stride & 1) == 0 && (dst->n_stride & 1) == 0,
-              GSD_ERR_UNSUPPORTED, "gsd_convT2x2: dst must be 8-byte aligned with even strides");
-  GSD_REQUIRE(((uintptr_t)wt & 15) == 0, GSD_ERR_BAD_ARG, "gsd_convT2x2: the weight image must be 16-byte aligned");
+  const char* const name = "gsd_convT2x2";
+  GSD_REQUIRE(src && dst && wt, GSD_ERR_BAD_ARG, "%s: null argument", name);
+  if (int e = convT_check_sizes(name, Cin, Cout, N, H, W)) return e;
+  if (int e = convT_check_fwd_operands(name, *src, *dst, Cin, Cout, H, W)) return e;
+  GSD_REQUIRE(((uintptr_t)wt & 15) == 0, GSD_ERR_BAD_ARG, "%s: the weight image must be 16-byte aligned", name);
   ConvTFwdParams P;
   P.src = to_srcd(*src);
   P.dst = to_dstd(*dst);
   P.wt = wt;
   P.bias = bias;
-  P.K = Cin;
-  P.Kpad = round_up(Cin, 32);
-  P.M = Cout * 4;
-  P.nchunks = P.Kpad / 32;
-  P.mblocks = ceil_div(P.M, 128);
-  P.N = N; P.H = H; P.W = W;
-  P.tiles_flat = (int)ceil_div64((int64_t)N * H * W, 128);   // pixel tiles over the whole batch
-  const long grid = (long)P.tiles_flat * P.mblocks;
-  GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_convT2x2: grid too large");
-  const size_t lds = (size_t)(2 * (32 * 128 + 32 * 128) + 2 * P.Kpad) * sizeof(float);   // 64 KiB + coefficients: two blocks per CU
-  GSD_REQUIRE(lds <= 80 * 1024, GSD_ERR_UNSUPPORTED, "gsd_convT2x2: Cin %d too large for the coefficient table", Cin);
+  ConvTLaunch L;
+  if (int e = convT_plan_fwd(name, P, Cin, Cout, N, H, W, &L)) return e;
   // 16-byte activation pieces: channel planes start 16-byte aligned and hold a multiple of 4 pixels
   const bool x4 = gsd_env_int("GSD_CONVT_X4", 1) != 0 && ((uintptr_t)src->ptr & 15) == 0 && src->c_stride % 4 == 0 &&
                   src->n_stride % 4 == 0 && (H * W) % 4 == 0;
-  if (x4) return gsd_launch<convT_fwd_dma_kernel<true>>("gsd_convT2x2", dim3((int)grid), dim3(256), lds, (hipStream_t)stream, P);
-  return gsd_launch<convT_fwd_dma_kernel<false>>("gsd_convT2x2", dim3((int)grid), dim3(256), lds, (hipStream_t)stream, P);
+  if (x4) return gsd_launch<convT_fwd_dma_kernel<true>>(name, dim3(L.grid), dim3(256), L.lds, (hipStream_t)stream, P);
+  return gsd_launch<convT_fwd_dma_kernel<false>>(name, dim3(L.grid), dim3(256), L.lds, (hipStream_t)stream, P);
 }
 
-// Which gsd_weight_layout mode gsd_convT2x2_dgrad expects for these arguments: 7 (the LDS-DMA kernel) unless an odd-width
-// plane comes without the two readable floats behind the tensor that its virtual last column reads (gsd_src.slack), or the
-// tuning switch GSD_CONVT_DG_DMA=0 asks for the register-staged kernel: then 3.
+// Which gsd_weight_layout mode gsd_convT2x2_dgrad expects for these arguments: 7 (the LDS-DMA kernel) unless the arguments do not
+// admit it or the tuning switch GSD_CONVT_DG_DMA=0 asks for the register-staged kernel: then 3.
 extern "C" int gsd_convT2x2_dgrad_layout(const gsd_src* src, int Cin, int Cout, int N, int H, int W) {
-  if (src == nullptr || Cin <= 0 || Cout <= 0 || N <= 0 || H <= 0 || W <= 0) return 3;
-  if (gsd_env_int("GSD_CONVT_DG_DMA", 1) == 0) return 3;
-  if ((W & 1) && src->slack < 2) return 3;
-  if ((int64_t)N * src->n_stride >= (1LL << 40)) return 3;
-  return 7;
+  return convT_dgrad_dma_admits(src, Cin, Cout, N, H, W) && gsd_env_int("GSD_CONVT_DG_DMA", 1) != 0 ? 7 : 3;
 }
 
 extern "C" int gsd_convT2x2_dgrad(const gsd_src* src, const float* wt, int Cin, int Cout, const gsd_dst* dst, int N,
@@ -717,55 +655,8 @@ extern "C" int gsd_convT2x2_dgrad(const gsd_src* src, const float* wt, int Cin, 
 // by an environment switch or a different `slack` at launch time -- a mode the arguments do not admit is refused.
 extern "C" int gsd_convT2x2_dgrad_as(int wt_mode, const gsd_src* src, const float* wt, int Cin, int Cout, const gsd_dst* dst, int N,
                                      int H, int W, void* stream) {
-  GSD_REQUIRE(src && dst && wt, GSD_ERR_BAD_ARG, "gsd_convT2x2_dgrad: null argument");
   GSD_REQUIRE(wt_mode == 3 || wt_mode == 7, GSD_ERR_BAD_ARG, "gsd_convT2x2_dgrad: weight layout mode %d is neither 3 nor 7", wt_mode);
-  if (wt_mode == 7)
-    GSD_REQUIRE(!((W & 1) && src->slack < 2) && (int64_t)N * src->n_stride < (1LL << 40), GSD_ERR_BAD_ARG,
-                "gsd_convT2x2_dgrad: a mode-7 weight image needs the LDS-DMA kernel, which these arguments do not admit "
-                "(odd W = %d needs src->slack >= 2, got %d); build the image with the mode gsd_convT2x2_dgrad_layout returns",
-                W, src->slack);
-  GSD_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, GSD_ERR_BAD_ARG, "gsd_convT2x2_dgrad: bad sizes");
-  if (int e = gsd_check_src(*src, "gsd_convT2x2_dgrad src")) return e;
-  if (int e = gsd_check_dst(*dst, "gsd_convT2x2_dgrad dst")) return e;
-  GSD_REQUIRE(src->C == Cout && src->H == 2 * H && src->W == 2 * W && src->scale == nullptr && src->relu == 0 &&
-                  src->off_h == 0 && src->off_w == 0,
-              GSD_ERR_BAD_ARG, "gsd_convT2x2_dgrad: src must be the plain (Cout,2H,2W) gradient");
-  GSD_REQUIRE(((uintptr_t)src->ptr & 7) == 0 && (src->c_stride & 1) == 0 && (src->n_stride & 1) == 0,
-              GSD_ERR_UNSUPPORTED, "gsd_convT2x2_dgrad: src must be 8-byte aligned with even strides");
-  GSD_REQUIRE(dst->C == Cin && dst->H == H && dst->W == W && dst->off_h == 0 && dst->off_w == 0, GSD_ERR_BAD_ARG,
-              "gsd_convT2x2_dgrad: dst must be (Cin,H,W)");
-  if (wt_mode == 7) {
-    GSD_REQUIRE(((uintptr_t)wt & 15) == 0, GSD_ERR_BAD_ARG, "gsd_convT2x2_dgrad: the weight image must be 16-byte aligned");
-    ConvTDgParams Q;
-    Q.src = to_srcd(*src);
-    Q.dst = to_dstd(*dst);
-    Q.wt = wt;
-    Q.K = Cout * 4;
-    Q.Kpad = round_up(Cout, 8) * 4;
-    Q.M = Cin;
-    Q.nchunks = Q.Kpad / 32;
-    Q.mblocks = ceil_div(Cin, 128);
-    Q.N = N; Q.H = H; Q.W = W;
-    Q.Wv = round_up(W, 2);
-    Q.tiles_flat = (int)ceil_div64((int64_t)N * H * Q.Wv, 128);   // pixel tiles over the whole batch's virtual grid
-    const long grid = (long)Q.tiles_flat * Q.mblocks;
-    GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_convT2x2_dgrad: grid too large");
-    const size_t lds = (size_t)(2 * (32 * 128 + 16 * 256)) * sizeof(float);   // 64 KiB: two blocks per CU
-    Q.bw_raw = Q.bw_scale = Q.bw_shift = Q.bw_mean = Q.bw_invstd = nullptr;
-    Q.partials = nullptr;
-    Q.Mpad = 0;
-    return gsd_launch<convT_dgrad_dma_kernel<false>>("gsd_convT2x2_dgrad", dim3((int)grid), dim3(256), lds, (hipStream_t)stream, Q);
-  }
-  ConvTParams P;
-  P.src = to_srcd(*src);
-  P.dst = to_dstd(*dst);
-  P.wt = wt;
-  P.bias = nullptr;
-  P.K = Cout * 4;
-  P.M = Cin;
-  P.nchunks = ceil_div(Cout, 4);
-  P.N = N; P.H = H; P.W = W;
-  return run<CT_DGRAD>(P, (hipStream_t)stream, "gsd_convT2x2_dgrad");
+  return convT_dgrad_launch("gsd_convT2x2_dgrad", wt_mode, src, wt, Cin, Cout, dst, ConvTBw{}, nullptr, N, H, W, (hipStream_t)stream);
 }
 
 // dX of the transposed convolution fused with the backward of the relu(bn(raw)) that produced its INPUT (the ConvT reads the
@@ -773,51 +664,16 @@ extern "C" int gsd_convT2x2_dgrad_as(int wt_mode, const gsd_src* src, const floa
 // partials (sum dz, sum dz*xhat) per channel in rows of 2*Mpad floats, Mpad = round_up(Cin, 64) -- as gsd_conv3x3_dgrad_bnrelu,
 // so the separate gsd_bn_bwd_reduce pass over that unit (one read of g and raw, one write of g) disappears.  The LDS-DMA kernel
 // only (weight layout mode 7); gsd_convT2x2_dgrad_bnrelu_partial_rows: 0 when the arguments do not admit it.
-static bool ct_dma_admits(const gsd_src* src, int Cin, int Cout, int N, int H, int W) {
-  if (src == nullptr || Cin <= 0 || Cout <= 0 || N <= 0 || H <= 0 || W <= 0) return false;
-  return !((W & 1) && src->slack < 2) && (int64_t)N * src->n_stride < (1LL << 40);
-}
-
 extern "C" int gsd_convT2x2_dgrad_bnrelu_partial_rows(const gsd_src* src, int Cin, int Cout, int N, int H, int W) {
-  if (!ct_dma_admits(src, Cin, Cout, N, H, W)) return 0;
-  return (int)ceil_div64((int64_t)N * H * round_up(W, 2), 128) * 2;
+  return convT_dgrad_dma_admits(src, Cin, Cout, N, H, W) ? 2 * convT_dgrad_tiles(N, H, W) : 0;
 }
 
 extern "C" int gsd_convT2x2_dgrad_bnrelu(const gsd_src* src, const float* wt, int Cin, int Cout, const gsd_dst* dst, const float* raw,
                                          const float* scale, const float* shift, const float* mean, const float* invstd,
                                          float* partials, int N, int H, int W, void* stream) {
-  GSD_REQUIRE(src && dst && wt && raw && scale && shift && mean && invstd && partials, GSD_ERR_BAD_ARG,
-              "gsd_convT2x2_dgrad_bnrelu: null argument");
-  GSD_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, GSD_ERR_BAD_ARG, "gsd_convT2x2_dgrad_bnrelu: bad sizes");
-  GSD_REQUIRE(ct_dma_admits(src, Cin, Cout, N, H, W), GSD_ERR_UNSUPPORTED,
-              "gsd_convT2x2_dgrad_bnrelu: the arguments do not admit the LDS-DMA kernel (gsd_convT2x2_dgrad_bnrelu_partial_rows == 0)");
-  if (int e = gsd_check_src(*src, "gsd_convT2x2_dgrad_bnrelu src")) return e;
-  if (int e = gsd_check_dst(*dst, "gsd_convT2x2_dgrad_bnrelu dst")) return e;
-  GSD_REQUIRE(src->C == Cout && src->H == 2 * H && src->W == 2 * W && src->scale == nullptr && src->relu == 0 && src->off_h == 0 &&
-                  src->off_w == 0,
-              GSD_ERR_BAD_ARG, "gsd_convT2x2_dgrad_bnrelu: src must be the plain (Cout,2H,2W) gradient");
-  GSD_REQUIRE(((uintptr_t)src->ptr & 7) == 0 && (src->c_stride & 1) == 0 && (src->n_stride & 1) == 0, GSD_ERR_UNSUPPORTED,
-              "gsd_convT2x2_dgrad_bnrelu: src must be 8-byte aligned with even strides");
-  GSD_REQUIRE(dst->C == Cin && dst->H == H && dst->W == W && dst->off_h == 0 && dst->off_w == 0, GSD_ERR_BAD_ARG,
-              "gsd_convT2x2_dgrad_bnrelu: dst must be the full (Cin,H,W) gradient buffer (raw shares its strides)");
-  GSD_REQUIRE(((uintptr_t)wt & 15) == 0, GSD_ERR_BAD_ARG, "gsd_convT2x2_dgrad_bnrelu: the weight image must be 16-byte aligned");
-  ConvTDgParams Q;
-  Q.src = to_srcd(*src);
-  Q.dst = to_dstd(*dst);
-  Q.wt = wt;
-  Q.K = Cout * 4;
-  Q.Kpad = round_up(Cout, 8) * 4;
-  Q.M = Cin;
-  Q.nchunks = Q.Kpad / 32;
-  Q.mblocks = ceil_div(Cin, 128);
-  Q.N = N; Q.H = H; Q.W = W;
-  Q.Wv = round_up(W, 2);
-  Q.tiles_flat = (int)ceil_div64((int64_t)N * H * Q.Wv, 128);
-  Q.bw_raw = raw; Q.bw_scale = scale; Q.bw_shift = shift; Q.bw_mean = mean; Q.bw_invstd = invstd;
-  Q.partials = partials;
-  Q.Mpad = round_up(Cin, 64);
-  const long grid = (long)Q.tiles_flat * Q.mblocks;
-  GSD_REQUIRE(grid < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_convT2x2_dgrad_bnrelu: grid too large");
-  const size_t lds = (size_t)(2 * (32 * 128 + 16 * 256)) * sizeof(float);
-  return gsd_launch<convT_dgrad_dma_kernel<true>>("gsd_convT2x2_dgrad_bnrelu", dim3((int)grid), dim3(256), lds, (hipStream_t)stream, Q);
+  const char* const name = "gsd_convT2x2_dgrad_bnrelu";
+  GSD_REQUIRE(src && dst && wt && raw && scale && shift && mean && invstd && partials, GSD_ERR_BAD_ARG, "%s: null argument", name);
+  ConvTBw bw;
+  bw.raw = raw; bw.scale = scale; bw.shift = shift; bw.mean = mean; bw.invstd = invstd;
+  return convT_dgrad_launch(name, 7, src, wt, Cin, Cout, dst, bw, partials, N, H, W, (hipStream_t)stream);
 }

@@ -1,12 +1,13 @@
 // gsd_convT_wgrad.hip -- dW and db of ConvTranspose2d(k2,s2) as an implicit GEMM over pixels on v_mfma_f32_16x16x4_f32 (gfx950),
 // and gsd_sum_planes (the per-channel sums behind every bias gradient).
 //
-//   dW[ci][co][kh][kw] = sum_{n,h,w} x[n,ci,h,w] * dy[n,co,2h+kh,2w+kw]      (/root/reference/gelslim_depth/models/unet.py:36)
+//   dW[ci][co][kh][kw] = sum_{n,h,w} x[n,ci,h,w] * dy[n,co,2h+kh,2w+kw]      (unet.py:36 of the reference)
 //
 // GEMM view: D[m][col] = sum_pixels A[m][pixel] * B[pixel][col] with the pixel index on the MFMA k dimension (4 consecutive
 // pixels per instruction).  A = space-to-depth rows (co,kh,kw) of dy, B = x with the deferred BatchNorm+ReLU recomputed on
 // load.  Wave tile 64 x 64.  The reduction over pixels is split across blocks (split-K); every block writes a partial slab and
 // convT_wgrad_reduce_kernel sums the slabs in a fixed order => bitwise reproducible.
+#include "gsd_convT_host.h"
 #include "gsd_wgrad_host.h"
 
 // Register-staged form: flat 64-pixel stages, operand tiles through registers (A = space-to-depth dy rows (co,kh,kw),
@@ -112,21 +113,20 @@ __global__ __launch_bounds__(256) void convT_wgrad_kernel(const WgradParams P) {
 // flat pixel -> (h, w) map live in the per-lane source address), one LDS image per block and two blocks per CU, so one
 // block's DMA issue + flight is covered by the other's MFMAs.  The deferred BatchNorm+ReLU of x is applied after the
 // ds_read (a lane owns four fixed input channels).  Measured against the register-staged kernel: see DESIGN.md.
-// BX (XM >= 1): the activation operand as aligned 16-byte pieces -- 64 consecutive pixels of a channel plane are 256 contiguous bytes
-// (H * W % 4 == 0, 16-byte aligned strides): an instruction fills four channel rows, 8 instead of 32 instructions per wave and
-// stage.  The rows are then contiguous in LDS (pitch 64), so piece q of row r is stored at slot q ^ (r & 15) (swizzle on the
+// X4: both operands as aligned 16-byte pieces instead of dword gathers (BX and AX below name the two halves of the switch).
+// BX, the activation operand: 64 consecutive pixels of a channel plane are 256 contiguous bytes (H * W % 4 == 0, 16-byte
+// aligned strides): an instruction fills four channel rows, 8 instead of 32 instructions per wave and stage.  The rows are then contiguous in LDS (pitch 64), so piece q of row r is stored at slot q ^ (r & 15) (swizzle on the
 // DMA's source piece and on the read) to keep the 16 rows of a read off one bank.
 __device__ __attribute__((aligned(16))) const float gsd_zero16_wg[4] = {0.f, 0.f, 0.f, 0.f};
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-// AX (XM == 2): the gradient operand as 16-byte pieces too.  Rows m = (co, kh, kw = 0 / 1) read the same stretch of dy row
-// 2h + kh interleaved, so an LDS row holds a (co, kh) PAIR of m rows: 128 floats = 64 pixels x (kw 0, kw 1), a piece = two
+// AX, the gradient operand: rows m = (co, kh, kw = 0 / 1) read the same stretch of dy row 2h + kh interleaved, so an LDS row holds a (co, kh) PAIR of m rows: 128 floats = 64 pixels x (kw 0, kw 1), a piece = two
 // pixels; an instruction fills two such rows (four m rows): 8 instead of 32 instructions per wave and stage.  Slot q of row R
 // holds source piece q ^ (R & 7) (eight rows a read touches -> eight bank groups).  A pixel pair that straddles the end of an
 // image row (odd W only) gets its second pixel's two floats from a plain load issued beside the fills and written over the
-// piece by the same lane once its fills have landed.  Instantiated: XM = 0 (both operands as dword gathers) and XM = 2.
-template <int XM>
+// piece by the same lane once its fills have landed.
+template <bool X4>
 __global__ __launch_bounds__(256, 2) void convT_wgrad_dma_kernel(const WgradParams P) {
-  constexpr bool BX = XM >= 1, AX = XM == 2;
+  constexpr bool BX = X4, AX = X4;
   constexpr int MT = 4, NTB = 4, BMw = 128, BNw = 128, DS = 66, DSB = BX ? 64 : DS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Al = smem;
@@ -391,24 +391,21 @@ extern "C" int64_t gsd_convT2x2_wgrad_workspace(int N, int H, int W, int Cin, in
 
 extern "C" int gsd_convT2x2_wgrad(const gsd_src* x, const gsd_src* dy, int Cin, int Cout, float* dw, float* dbias,
                                   float* workspace, int64_t workspace_elems, int N, int H, int W, void* stream) {
-  GSD_REQUIRE(x && dy && dw && workspace, GSD_ERR_BAD_ARG, "gsd_convT2x2_wgrad: null argument");
-  GSD_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, GSD_ERR_BAD_ARG, "gsd_convT2x2_wgrad: bad sizes");
+  const char* const what = "gsd_convT2x2_wgrad";
+  GSD_REQUIRE(x && dy && dw && workspace, GSD_ERR_BAD_ARG, "%s: null argument", what);
+  if (int e = convT_check_sizes(what, Cin, Cout, N, H, W)) return e;
   GSD_REQUIRE(x->ptr != nullptr && x->C == Cin && x->H == H && x->W == W && x->off_h == 0 && x->off_w == 0,
-              GSD_ERR_BAD_ARG, "gsd_convT2x2_wgrad: x must be the full (Cin,H,W) tensor");
-  GSD_REQUIRE((x->scale == nullptr) == (x->shift == nullptr), GSD_ERR_BAD_ARG,
-              "gsd_convT2x2_wgrad: scale/shift must come together");
+              GSD_ERR_BAD_ARG, "%s: x must be the full (Cin,H,W) tensor", what);
+  GSD_REQUIRE((x->scale == nullptr) == (x->shift == nullptr), GSD_ERR_BAD_ARG, "%s: scale/shift must come together", what);
   if (int e = wgrad_check_plain(*dy, "gsd_convT2x2_wgrad dy")) return e;
   if (int e = gsd_require_rows_contiguous(*dy, "gsd_convT2x2_wgrad dy")) return e;
   if (int e = gsd_require_rows_contiguous(*x, "gsd_convT2x2_wgrad x")) return e;
-  GSD_REQUIRE(dy->C == Cout && dy->H == 2 * H && dy->W == 2 * W, GSD_ERR_BAD_ARG,
-              "gsd_convT2x2_wgrad: dy must be (Cout,2H,2W)");
-  GSD_REQUIRE(((uintptr_t)dy->ptr & 7) == 0 && (dy->c_stride & 1) == 0 && (dy->n_stride & 1) == 0, GSD_ERR_UNSUPPORTED,
-              "gsd_convT2x2_wgrad: dy must be 8-byte aligned with even strides");
+  if (int e = convT_check_dy(what, "dy", *dy, Cout, H, W)) return e;
   const int M = Cout * 4;
   const ConvTWgPlan pl = plan_convT_wgrad(N, H, W, M, Cin);
   const int64_t need = pl.slab_elems + (int64_t)Cout * 64;
-  GSD_REQUIRE(workspace_elems >= need, GSD_ERR_WORKSPACE, "gsd_convT2x2_wgrad: workspace %lld < %lld elements",
-              (long long)workspace_elems, (long long)need);
+  GSD_REQUIRE(workspace_elems >= need, GSD_ERR_WORKSPACE, "%s: workspace %lld < %lld elements", what, (long long)workspace_elems,
+              (long long)need);
   WgradParams P{};   // (a1 and the conv3x3 stage geometry stay 0)
   wgrad_fill_common(P, x, 1, dy, Cin, M, workspace, N, H, W, pl.splits, pl.mblocks, pl.nblocks);
   P.Cact = Cin;
@@ -419,12 +416,11 @@ extern "C" int gsd_convT2x2_wgrad(const gsd_src* x, const gsd_src* dy, int Cin, 
   // both operands as aligned 16-byte pieces when 64 consecutive pixels of an activation plane are 256 aligned bytes (the gradient
   // rows then move as 16-byte pieces of dy rows: 8-byte aligned pixel pairs, dy is 8-byte aligned with even strides)
   const bool aligned = (H * W) % 4 == 0 && ((uintptr_t)x->ptr & 15) == 0 && x->c_stride % 4 == 0 && x->n_stride % 4 == 0;
-  const char* const what = "gsd_convT2x2_wgrad";
   const hipStream_t st = (hipStream_t)stream;
   // (wide: M = 4*Cout <= 64, never the case for this network; the register-staged kernel keeps it working)
   if (int e = pl.wide   ? gsd_launch<convT_wgrad_kernel<1, 4>>(what, dim3(grid), dim3(256), lds, st, P)
-              : aligned ? gsd_launch<convT_wgrad_dma_kernel<2>>(what, dim3(grid), dim3(256), lds, st, P)
-                        : gsd_launch<convT_wgrad_dma_kernel<0>>(what, dim3(grid), dim3(256), lds, st, P))
+              : aligned ? gsd_launch<convT_wgrad_dma_kernel<true>>(what, dim3(grid), dim3(256), lds, st, P)
+                        : gsd_launch<convT_wgrad_dma_kernel<false>>(what, dim3(grid), dim3(256), lds, st, P))
     return e;
   launch_convT_wgrad_reduce(workspace, dw, pl.splits, M, Cin, st);
   GSD_LAUNCH_CHECK("gsd_convT2x2_wgrad reduce");

@@ -6,7 +6,8 @@
 //   one K-chunk of one m-block is ONE contiguous LDS image (36 x BM floats).  Inside every group of 64 columns
 //   (one wave's output channels) the order is permuted: storage slot l*4+m holds column m*16+l, so the four
 //   MFMA A operands of a lane (its 4 m-tiles) are one aligned float4 in LDS.
-// modes 2/3 (convT): plain [k row][Mpad].
+// mode 2: retired (the register-staged ConvT forward kernel's image; the ConvT forward layout is mode 6).
+// mode 3 (convT dgrad, register-staged kernel): plain [k row][Mpad].
 // mode 6 (convT forward, LDS-DMA kernel): like modes 0/1 with BM = 128 and k rows padded to 32: [mblock][k row][128],
 //   one K-chunk of 32 input channels of one m-block is one contiguous 16 KiB LDS image, columns permuted as above.
 // mode 7 (convT dgrad, LDS-DMA kernel): the same image shape with k = co*4+kh*2+kw (8 output channels per chunk), m = ci.
@@ -14,7 +15,6 @@ static void layout_dims(int mode, int Co, int Ci, int* rows, int* M, int* BM, in
   switch (mode) {
     case 0: *rows = round_up(Ci, 4) * 9; *M = Co; break;        // k = ci*9+t        m = co
     case 1: *rows = round_up(Co, 4) * 9; *M = Ci; break;        // k = co*9+t (flip) m = ci
-    case 2: *rows = round_up(Ci, 16); *M = Co * 4; break;       // k = ci            m = co*4+khkw
     case 3: *rows = round_up(Co, 4) * 4; *M = Ci; break;        // k = co*4+khkw     m = ci
     case 4: *rows = round_up(Ci, 4) * 18; *M = Co; break;       // k = ci*18+r*6+f   m = co   (Winograd F(4,3) rows)
     case 5: *rows = round_up(Co, 4) * 18; *M = Ci; break;       // k = co*18+r*6+f (flip) m = ci
@@ -42,7 +42,7 @@ static void layout_dims(int mode, int Co, int Ci, int* rows, int* M, int* BM, in
   }
 }
 extern "C" int64_t gsd_weight_layout_size(int mode, int Co, int Ci) {
-  if (mode < 0 || mode > 9 || Co <= 0 || Ci <= 0) return 0;
+  if (mode < 0 || mode > 9 || mode == 2 || Co <= 0 || Ci <= 0) return 0;
   int rows, M, BM, pitch, mblocks;
   layout_dims(mode, Co, Ci, &rows, &M, &BM, &pitch, &mblocks);
   return (int64_t)mblocks * rows * pitch;
@@ -88,9 +88,7 @@ __global__ void weight_layout_kernel(int mode, const float* __restrict__ w, int 
             default: v = g2; break;
           }
         }
-      } else if (mode == 2) {
-        if (k < Ci) v = w[(size_t)k * M + m];  // (Ci, Co*4) is already [k][m]
-      } else {
+      } else {   // mode 3
         const int co = k >> 2;
         if (co < Co) v = w[(size_t)m * (Co * 4) + k];
       }
@@ -180,6 +178,7 @@ __global__ __launch_bounds__(256) void weight_layout_w2d_kernel(int mode, const 
 }
 extern "C" int gsd_weight_layout(int mode, const float* w, int Co, int Ci, float* wt, void* stream) {
   GSD_REQUIRE(w && wt && mode >= 0 && mode <= 9 && Co > 0 && Ci > 0, GSD_ERR_BAD_ARG, "gsd_weight_layout: bad argument");
+  GSD_REQUIRE(mode != 2, GSD_ERR_BAD_ARG, "gsd_weight_layout: mode 2 is retired; the ConvT forward layout is mode 6");
   int rows, M, BM, pitch, mblocks;
   layout_dims(mode, Co, Ci, &rows, &M, &BM, &pitch, &mblocks);
   if (mode == 8 || mode == 9) {

@@ -107,8 +107,9 @@ int gsd_selftest_mfma(const float* a, const float* b, float* out, void* stream);
 /* ---- weight re-layouts (cheap, once per optimiser step) ----------------------------------- */
 /* mode 0: conv3x3 forward   W[Co][Ci][3][3]  -> k = ci*9+t,           m = co
  * mode 1: conv3x3 dgrad     W[Co][Ci][3][3]  -> k = co*9+(8-t) flipped, m = ci
- * mode 2: convT   forward   W[Ci][Co][2][2]  -> k = ci,               m = co*4+kh*2+kw
- * mode 3: convT   dgrad     W[Ci][Co][2][2]  -> k = co*4+kh*2+kw,     m = ci
+ * mode 2: retired (the image of a ConvT forward kernel that no longer exists; the ConvT forward layout is mode 6):
+ *         gsd_weight_layout_size returns 0 for it and gsd_weight_layout GSD_ERR_BAD_ARG
+ * mode 3: convT   dgrad,   register-staged kernel: W[Ci][Co][2][2]  -> k = co*4+kh*2+kw,     m = ci
  * mode 4: conv3x3 forward, Winograd F(4,3) rows: k = ci*18+r*6+f, m = co   (see gsd_conv3x3_w43)
  * mode 5: conv3x3 dgrad,   Winograd F(4,3) rows: k = co*18+r*6+f (flipped kernel), m = ci
  * mode 6: convT   forward, LDS-DMA kernel: k = ci (rows padded to 32), m = co*4+kh*2+kw in 128-column blocks
@@ -117,7 +118,7 @@ int gsd_selftest_mfma(const float* a, const float* b, float* out, void* stream);
  * mode 9: conv3x3 dgrad,   Winograd F(2x4,3x3): k = co*24+fr*6+fc (flipped kernel), m = ci
  * Modes 0/1 are tiled for the LDS-DMA kernel: [m-block][k row][BM] with BM = 64 (M <= 64) or 128, columns
  * permuted inside each 64-group (slot l*4+t = column t*16+l), so one K-chunk of one m-block is a contiguous LDS
- * image whose A operands are aligned float4s; modes 2/3 are [k row][M rounded up to 64].
+ * image whose A operands are aligned float4s; mode 3 is [k row][M rounded up to 64].
  * k rows are zero-padded to whole K-chunks. gsd_weight_layout_size returns the element count; the buffer
  * must be 16-byte aligned. */
 int64_t gsd_weight_layout_size(int mode, int Co, int Ci);
@@ -209,7 +210,10 @@ int gsd_conv3x3_w2d_dgrad_bnrelu_ws(const gsd_src* src, const float* wt, int Cin
                                     int N, int H, int W, void* stream);
 
 /* ConvTranspose2d(k=2,s=2)+bias. Replaces aten::convolution(transposed) at unet.py:36,41.
- * src is the (h,w) input (deferred BN allowed), dst the (2h,2w) output. weights: mode 6. */
+ * src is the (h,w) input (deferred BN allowed), dst the (2h,2w) output (a row pitch is allowed, an even one). weights: mode 6.
+ * The forward and dX run on LDS-DMA kernels; dX falls back to a register-staged kernel (weights: mode 3) for an odd-width
+ * gradient without slack and under GSD_CONVT_DG_DMA=0.  Every entry point below validates its operands the same way: dy is
+ * the plain (Cout,2H,2W) gradient, 8-byte aligned with even strides. */
 int gsd_convT2x2(const gsd_src* src, const float* wt, const float* bias, int Cin, int Cout,
                  const gsd_dst* dst, int N, int H, int W, void* stream);
 /* dX of the above: src = gradient w.r.t. the (2h,2w) output (plain), dst (h,w).  weights: the gsd_weight_layout mode that

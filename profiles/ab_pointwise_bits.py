@@ -56,7 +56,7 @@ def child(out_path):
     # ---- gsd_weight_layout.hip: every mode at Co = 8, Ci = 5, and the batch entry with three jobs
     Co, Ci = 8, 5
     w = randn(Co * Ci * 9)          # (Co,Ci,3,3) of the conv modes; the ConvT modes read its first Ci*Co*4 floats
-    for mode in range(10):
+    for mode in (m for m in range(10) if m != 2):      # mode 2 is retired
         wt = nan(lib.gsd_weight_layout_size(mode, Co, Ci))
         check(lib.gsd_weight_layout(mode, w.data_ptr(), Co, Ci, wt.data_ptr(), st), f"weight_layout {mode}")
         emit(f"weight_layout mode{mode}", wt)
