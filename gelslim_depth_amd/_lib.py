@@ -84,6 +84,13 @@ class gsd_mesh_view(C.Structure):
 GSD_MESH_RECORD_FLOATS = 12   # floats per triangle record of gsd_mesh_depth_count
 GSD_POSE_ROW = 5              # doubles per row of gsd_mesh_pose_score: sum_sq, sum_abs, inter, n_rendered, n_observed
 GSD_POSE_WIDTHS_MAX = 32      # widths per observation of gsd_mesh_pose_score_widths
+GSD_POSE_NORMAL_ROW = 16      # doubles per row of gsd_mesh_pose_normal: sum e^2, #active, J^T e (4), upper triangle of J^T J (10)
+
+
+class gsd_pose_lm(C.Structure):
+    """The constants of gsd_mesh_pose_lm_update (include/gsd.h): damping factors and bounds, step clip, free parameters."""
+    _fields_ = [("down", C.c_double), ("up", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double),
+                ("max_step", C.c_double * 4), ("free_mask", C.c_int32), ("first", C.c_int32)]
 
 
 class gsd_augment_draw(C.Structure):
@@ -206,6 +213,12 @@ SIGNATURES = {
     "gsd_mesh_pose_score_widths_workspace": (_L, [_I, _I, _I, _I, _I, _I]),
     "gsd_mesh_pose_score_widths": (_I, [C.POINTER(gsd_mesh_grid), C.POINTER(gsd_mesh_view), _P, _I, _P, _P, _L, _P, _I, _P, _P, _I, _I,
                                         _I, _I, _I, _F, _P, _P, _L, _P]),
+    "gsd_mesh_pose_normal_workspace": (_L, [_I, _I, _I, _I, _I]),
+    "gsd_mesh_pose_normal": (_I, [C.POINTER(gsd_mesh_grid), C.POINTER(gsd_mesh_view), _P, _I, _P, _P, _L, _P, _I, _P, _P, _I, _I, _I,
+                                  _I, _P, _P, _L, _P]),
+    "gsd_mesh_depth_render_jacobian": (_I, [C.POINTER(gsd_mesh_grid), C.POINTER(gsd_mesh_view), _P, _I, _P, _P, _L, _P, _P, _I, _I,
+                                            _I, _P, _P, _L, _P]),
+    "gsd_mesh_pose_lm_update": (_I, [C.POINTER(gsd_pose_lm), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gsd_guard_snapshot": (_I, [_P, _P, _L, _P]),
     "gsd_guard_restore": (_I, [_GUARD, _P, _P, _L, _P]),
     "gsd_adam_ema": (_I, [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _GUARD, _P]),

@@ -37,6 +37,13 @@
 //   predicates from it; the G rows are reduced in the same order as the single one, so row (b, p, k) has the bits of
 //   gsd_mesh_pose_score at the width widths[b][k].
 //
+//   refinement past the lattice (gsd_mesh_pose_normal, gsd_mesh_depth_render_jacobian, gsd_mesh_pose_lm_update, DESIGN.md section
+//   19): the walk can also say WHICH triangle gave m (md_walk<true>; the lowest id among equal values), and from that triangle's
+//   slope and the derivatives of the pixel -> mesh map a thread forms dR/d(t1, t2, theta, g) in fp64.  mesh_pose_normal sums e^2,
+//   J^T e and J^T J per candidate in mesh_pose_score's shape and order (entry 0 is that kernel's sum_sq to the bit),
+//   mesh_render_jacobian writes the per-pixel derivatives out, mesh_pose_lm_update does a damped Gauss-Newton step's bookkeeping
+//   for a batch of problems without a host read.
+//
 //   host layer: the render and the two score entry points share one validator (md_check: grid, view, T, list, alignment), one
 //   MdView and one MdLattice builder, and one thread -> point decode on the device (md_point).  Both score entry points check
 //   through md_check_score, carve their own workspace layout and hand it to one launcher, md_score: the pose table, for G > 1
@@ -219,11 +226,21 @@ struct MdView {
   long long list_elems;
 };
 
+// What the winner-tracking walk (md_walk<true>) keeps beside m: the triangle that gave it, -1 where none covers the point --
+// among equal values THE LOWEST ID, because the order inside a cell's list changes from build to build and the ids do not --
+// and the point in the transformed frame, the floats that the derivatives of x and y are made of.
+struct MdWin {
+  int id;
+  float pa, pb;
+};
+
 // The surface under pixel (r, c) of one finger under the pose-table row `row`: m = the max of sg * q over the triangles that
 // cover the pixel, -inf where none does.  Everything expensive (the pixel -> mesh map, the cell lookup, the walk) is here and
-// depends on the pose alone; the width enters in md_depth.
-__device__ __forceinline__ float md_surface(const MdGrid& G, const MdView& V, const float* __restrict__ rec, const int* __restrict__ start,
-                                            const int* __restrict__ list, const float* __restrict__ row, int r, int c, bool right) {
+// depends on the pose alone; the width enters in md_depth.  WIN also fills *win; m is the same bits either way.
+template <bool WIN>
+__device__ __forceinline__ float md_walk(const MdGrid& G, const MdView& V, const float* __restrict__ rec, const int* __restrict__ start,
+                                         const int* __restrict__ list, const float* __restrict__ row, int r, int c, bool right,
+                                         MdWin* win) {
 #pragma clang fp contract(off)
   const float cs = row[0], sn = row[1], t1 = row[2], t2 = row[3];
   // pixel -> transformed in-plane point: u along the unaligned axis (mirrored for the left finger), v along the aligned one
@@ -242,6 +259,7 @@ __device__ __forceinline__ float md_surface(const MdGrid& G, const MdView& V, co
   }
   const float sg = right ? 1.f : -1.f;
   float m = -INFINITY;                       // max of sg * q over the covering triangles
+  int best = -1;
   const float fx = (x - G.x0) * G.inv_cell, fy = (y - G.y0) * G.inv_cell;
   // a point more than a cell outside the grid is outside every triangle's bounding box (a NaN fails the test as well)
   if (fx >= -1.f && fx <= (float)G.nx + 1.f && fy >= -1.f && fy <= (float)G.ny + 1.f) {
@@ -258,10 +276,22 @@ __device__ __forceinline__ float md_surface(const MdGrid& G, const MdView& V, co
 #pragma unroll
       for (int k = 0; k < MD_WALK; ++k) tri[k] = md_load(rec, min(max(id[k], 0), V.T - 1));
 #pragma unroll
-      for (int k = 0; k < MD_WALK; ++k) m = fmaxf(m, md_cover(tri[k], x, y, sg));
+      for (int k = 0; k < MD_WALK; ++k) {
+        const float q = md_cover(tri[k], x, y, sg);
+        if constexpr (WIN) {     // a repeated position changes nothing: its id is not below itself
+          const int t = min(max(id[k], 0), V.T - 1);
+          if (q > m || (q == m && q > -INFINITY && t < best)) best = t;
+        }
+        m = fmaxf(m, q);
+      }
     }
   }
+  if constexpr (WIN) win->id = best, win->pa = pa, win->pb = pb;
   return m;
+}
+__device__ __forceinline__ float md_surface(const MdGrid& G, const MdView& V, const float* __restrict__ rec, const int* __restrict__ start,
+                                            const int* __restrict__ list, const float* __restrict__ row, int r, int c, bool right) {
+  return md_walk<false>(G, V, rec, start, list, row, r, c, right, nullptr);
 }
 
 // The depth of a surface value m (md_surface) at the half-width hg:
@@ -447,25 +477,232 @@ __global__ __launch_bounds__(256) void mesh_pose_score_widths(const MdGrid G, co
 // in ascending order, the 64 lane sums meet in the xor butterfly.  The order is a function of tpc alone.  A refused width gives
 // five NaN; its mark is the NaN half-width flag[(n / per) * step + k]: {table + 4, 1, MD_POSE} for the one width of a pose-table
 // row, {half, P, NW} for the array of several.
-__global__ __launch_bounds__(64) void mesh_pose_rows(const double* __restrict__ partial, int tpc, int NW, const float* __restrict__ flag,
-                                                     int per, int step, double* __restrict__ rows) {
+// ROW is the row's length: MD_ROW here, MD_NROW for the normal rows of section 19 (mesh_pose_normal_sum), which add in this order.
+template <int ROW>
+__device__ __forceinline__ void md_sum_rows(const double* __restrict__ partial, int tpc, int NW, const float* __restrict__ flag, int per,
+                                            int step, double* __restrict__ rows) {
 #pragma clang fp contract(off)
   const int n = blockIdx.x / NW, k = blockIdx.x - n * NW, lane = threadIdx.x;
-  double tot[MD_ROW];
+  double tot[ROW];
 #pragma unroll
-  for (int q = 0; q < MD_ROW; ++q) tot[q] = 0.0;
+  for (int q = 0; q < ROW; ++q) tot[q] = 0.0;
   for (int t = lane; t < tpc; t += 64) {
-    const double* p = partial + (((size_t)n * tpc + t) * NW + k) * MD_ROW;
+    const double* p = partial + (((size_t)n * tpc + t) * NW + k) * ROW;
 #pragma unroll
-    for (int q = 0; q < MD_ROW; ++q) tot[q] += p[q];
+    for (int q = 0; q < ROW; ++q) tot[q] += p[q];
   }
 #pragma unroll
-  for (int q = 0; q < MD_ROW; ++q) tot[q] = wave_sum_d(tot[q]);
+  for (int q = 0; q < ROW; ++q) tot[q] = wave_sum_d(tot[q]);
   const float hg = flag[(size_t)(n / per) * step + k];
   if (lane == 0) {
 #pragma unroll
-    for (int q = 0; q < MD_ROW; ++q) rows[(size_t)blockIdx.x * MD_ROW + q] = hg == hg ? tot[q] : (double)hg;
+    for (int q = 0; q < ROW; ++q) rows[(size_t)blockIdx.x * ROW + q] = hg == hg ? tot[q] : (double)hg;
   }
+}
+__global__ __launch_bounds__(64) void mesh_pose_rows(const double* __restrict__ partial, int tpc, int NW, const float* __restrict__ flag,
+                                                     int per, int step, double* __restrict__ rows) {
+  md_sum_rows<MD_ROW>(partial, tpc, NW, flag, per, step, rows);
+}
+
+// ---- refinement past the lattice: normal-equation rows, the Jacobian image, the damped step -----------
+constexpr int MD_NROW = GSD_POSE_NORMAL_ROW;   // sum e^2, #active, sum J_k e (a1, a2, theta, g), sum J_j J_k (j <= k, row-major)
+
+// dR/d(a1, a2, theta) of a point whose walk ended on `w` and whose depth is R, a1 = 1000 t1 and a2 = 1000 t2 in mm: 0 unless the
+// point is active (R < 0, which needs a winner).  In fp64 from floats alone: the winner's record, reloaded once -- its slope
+// (qx, qy), the clamp of q to the triangle's range ignored -- and cs, sn, pa, pb, da, db as md_walk formed them.
+__device__ __forceinline__ void md_jacobian(const MdView& V, const float* __restrict__ rec, const float* __restrict__ row, const MdWin& w,
+                                            bool right, float R, double (&J)[3]) {
+#pragma clang fp contract(off)
+  J[0] = J[1] = J[2] = 0.0;
+  if (!(R < 0.f) || w.id < 0) return;
+  const MdTri t = md_load(rec, w.id);
+  const double a = (double)t.q1 - (double)t.q0, b = (double)t.q2 - (double)t.q0, inv = (double)t.inv;
+  const double qx = (a * ((double)t.y2 - (double)t.y0) - b * ((double)t.y1 - (double)t.y0)) * inv;
+  const double qy = (b * ((double)t.x1 - (double)t.x0) - a * ((double)t.x2 - (double)t.x0)) * inv;
+  const double cs = row[0], sn = row[1], pa = w.pa, pb = w.pb;
+  const double da = (double)(w.pa - row[2]), db = (double)(w.pb - row[3]);   // the fp32 differences of md_walk
+  const double sg = right ? 1.0 : -1.0;
+  double xk[3], yk[3];
+  if (V.invert) {
+    xk[0] = 1.0, xk[1] = 0.0, xk[2] = -sn * pa - cs * pb;
+    yk[0] = 0.0, yk[1] = 1.0, yk[2] = cs * pa - sn * pb;
+  } else {
+    xk[0] = -cs, xk[1] = -sn, xk[2] = -sn * da + cs * db;
+    yk[0] = sn, yk[1] = -cs, yk[2] = -sn * db - cs * da;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) J[k] = -sg * (qx * xk[k] + qy * yk[k]);
+}
+
+// mesh_pose_score's block, wave and thread shape; a thread adds its point's e^2, J_k e and J_j J_k (J_g = 0.5 where the point is
+// active).  The 15 sums go through md_wave_sums<4> in four groups (slot 1 of the 16 is the count, a ballot), the four waves meet
+// as (w0 + w1) + (w2 + w3) through LDS and the block stores partial row blockIdx.x: entry 0 takes mesh_pose_score's path to the bit.
+__global__ __launch_bounds__(256) void mesh_pose_normal(const MdGrid G, const MdView V, const MdLattice S, const float* __restrict__ rec,
+                                                        const int* __restrict__ start, const int* __restrict__ list,
+                                                        const float* __restrict__ table, const float* __restrict__ observed,
+                                                        double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  const MdPoint p = md_point(S.tiles_x, S.tiles_y);
+  const int n = p.n, ch = p.ch, wave = p.wave, lane = p.lane;
+  double e = 0.0, J[4] = {0.0, 0.0, 0.0, 0.0};
+  bool active = false;
+  if (p.i < S.rows && p.j < S.cols) {       // a point off the lattice adds zeros; every thread reaches the reduction
+    const int r = S.off + p.i * S.stride, c = S.off + p.j * S.stride;   // < H, < W: no overflow
+    const bool right = (ch == 1) != (V.lr_flip != 0);
+    const float* row = table + (size_t)n * MD_POSE;
+    MdWin w;
+    const float R = md_depth(md_walk<true>(G, V, rec, start, list, row, r, c, right, &w), row[4]);
+    const float D = observed[(((size_t)(n / S.P) * 2 + ch) * V.H + r) * V.W + c];
+    e = (double)R - (double)D;
+    active = R < 0.f;
+    double J3[3];
+    md_jacobian(V, rec, row, w, right, R, J3);
+    J[0] = J3[0], J[1] = J3[1], J[2] = J3[2], J[3] = active ? 0.5 : 0.0;
+  }
+  double v[4][4];                           // slot 4 g + u is row entry 4 g + u
+  v[0][0] = e * e, v[0][1] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[(2 + k) >> 2][(2 + k) & 3] = J[k] * e;
+  {
+    int s = 6;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int k = j; k < 4; ++k, ++s) v[s >> 2][s & 3] = J[j] * J[k];
+  }
+  const int n_active = __popcll(__ballot(active));
+  __shared__ double red[4][MD_NROW];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    md_wave_sums<4>(v[g], lane);
+    if ((lane & 15) == 0) {
+      const int slot = 4 * g + (lane >> 4);
+      red[wave][slot] = slot == 1 ? (double)n_active : v[g][0];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < MD_NROW) {
+    const int q = threadIdx.x;
+    partial[(size_t)blockIdx.x * MD_NROW + q] = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
+  }
+}
+
+// mesh_pose_rows for rows of MD_NROW: one wave per candidate, 16 NaN for a refused width (the NaN half-width of its table row)
+__global__ __launch_bounds__(64) void mesh_pose_normal_sum(const double* __restrict__ partial, int tpc, const float* __restrict__ table,
+                                                           double* __restrict__ rows) {
+  md_sum_rows<MD_NROW>(partial, tpc, 1, table + 4, 1, MD_POSE, rows);
+}
+
+// mesh_render's launch; writes J_a1, J_a2, J_theta of every pixel as doubles, (N, 2, 3, H, W): what mesh_pose_normal sums, to look at
+__global__ __launch_bounds__(256) void mesh_render_jacobian(const MdGrid G, const MdView V, const float* __restrict__ rec,
+                                                            const int* __restrict__ start, const int* __restrict__ list,
+                                                            const float* __restrict__ table, double* __restrict__ out) {
+  const MdPoint p = md_point(V.tiles_x, V.tiles_y);
+  const int r = p.i, c = p.j;
+  if (r >= V.H || c >= V.W) return;
+  const bool right = (p.ch == 1) != (V.lr_flip != 0);
+  const float* row = table + (size_t)p.n * MD_POSE;
+  MdWin w;
+  const float R = md_depth(md_walk<true>(G, V, rec, start, list, row, r, c, right, &w), row[4]);
+  double J[3];
+  md_jacobian(V, rec, row, w, right, R, J);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[(((size_t)p.img * 3 + k) * V.H + r) * V.W + c] = J[k];
+}
+
+struct MdLm {           // gsd_pose_lm by value
+  double down, up, lambda_min, lambda_max, max_step[4];
+  int free_mask, first;
+};
+
+// One thread per problem, fp64 (the definition is include/gsd.h's).  The system is always 4 x 4: a parameter that is not free has
+// the identity's row and column and a zero right-hand side, so its step is exactly 0, the others' factorisation meets only exact
+// zeros from it, and every index is a constant -- the matrix lives in registers.
+__global__ __launch_bounds__(64) void mesh_pose_lm_update(const MdLm lm, int B, float* __restrict__ pose, float* __restrict__ width,
+                                                          double* __restrict__ lambda, double* __restrict__ row,
+                                                          float* __restrict__ trial_pose, float* __restrict__ trial_width,
+                                                          const double* __restrict__ trial_row, double* __restrict__ trace,
+                                                          int* __restrict__ accepted, double* __restrict__ last_step) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= B) return;
+  double cur[MD_NROW];
+#pragma unroll
+  for (int q = 0; q < MD_NROW; ++q) cur[q] = row[(size_t)i * MD_NROW + q];
+  float t1 = pose[3 * (size_t)i], t2 = pose[3 * (size_t)i + 1], th = pose[3 * (size_t)i + 2], g = width[i];
+  double lam = lambda[i];
+  int count = lm.first ? 0 : accepted[i];
+  const double trial_sq = trial_row[(size_t)i * MD_NROW];
+  const bool take = lm.first || trial_sq < cur[0];      // strict, and a NaN never wins
+  if (take) {
+#pragma unroll
+    for (int q = 0; q < MD_NROW; ++q) cur[q] = trial_row[(size_t)i * MD_NROW + q];
+    t1 = trial_pose[3 * (size_t)i], t2 = trial_pose[3 * (size_t)i + 1], th = trial_pose[3 * (size_t)i + 2], g = trial_width[i];
+  }
+  if (!lm.first) {
+    lam = take ? fmax(lam * lm.down, lm.lambda_min) : fmin(lam * lm.up, lm.lambda_max);
+    count += take ? 1 : 0;
+  }
+  // (A + lam diag(A)) d = -b by Cholesky, in the order a1, a2, theta, g
+  double M[4][4], rhs[4], Lc[4][4], z[4], d[4];
+  {
+    int s = 6;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int k = j; k < 4; ++k, ++s) {
+        const bool both = ((lm.free_mask >> j) & 1) && ((lm.free_mask >> k) & 1);
+        const double a = j == k ? cur[s] + lam * cur[s] : cur[s];
+        M[j][k] = M[k][j] = both ? a : (j == k ? 1.0 : 0.0);
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) rhs[j] = ((lm.free_mask >> j) & 1) ? -cur[2 + j] : 0.0;
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    double piv = M[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) piv = piv - Lc[j][k] * Lc[j][k];
+    ok = ok && piv > 0.0 && isfinite(piv);
+    Lc[j][j] = sqrt(piv);
+#pragma unroll
+    for (int r = j + 1; r < 4; ++r) {
+      double s = M[r][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) s = s - Lc[r][k] * Lc[j][k];
+      Lc[r][j] = s / Lc[j][j];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double s = rhs[r];
+#pragma unroll
+    for (int k = 0; k < r; ++k) s = s - Lc[r][k] * z[k];
+    z[r] = s / Lc[r][r];
+  }
+#pragma unroll
+  for (int r = 3; r >= 0; --r) {
+    double s = z[r];
+#pragma unroll
+    for (int k = r + 1; k < 4; ++k) s = s - Lc[k][r] * d[k];
+    d[r] = s / Lc[r][r];
+  }
+  ok = ok && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]) && isfinite(d[3]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) d[k] = ok ? fmin(fmax(d[k], -lm.max_step[k]), lm.max_step[k]) : 0.0;
+  if (take) {
+#pragma unroll
+    for (int q = 0; q < MD_NROW; ++q) row[(size_t)i * MD_NROW + q] = cur[q];
+    pose[3 * (size_t)i] = t1, pose[3 * (size_t)i + 1] = t2, pose[3 * (size_t)i + 2] = th, width[i] = g;
+  }
+  lambda[i] = lam, accepted[i] = count, trace[i] = cur[0];
+  trial_pose[3 * (size_t)i] = (float)((double)t1 + d[0] / 1000.0);
+  trial_pose[3 * (size_t)i + 1] = (float)((double)t2 + d[1] / 1000.0);
+  trial_pose[3 * (size_t)i + 2] = (float)((double)th + d[2]);
+  trial_width[i] = (float)((double)g + d[3]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) last_step[4 * (size_t)i + k] = fabs(d[k]);
 }
 
 // lattice points along an axis of `len` pixels
@@ -666,12 +903,11 @@ extern "C" int gsd_mesh_depth_fill(const gsd_mesh_grid* grid, const float* recor
 
 extern "C" int64_t gsd_mesh_depth_render_workspace(int N) { return N > 0 ? (int64_t)N * MD_POSE : 0; }
 
-extern "C" int gsd_mesh_depth_render(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
-                                     const int32_t* cells, const int32_t* list, int64_t list_elems, const float* poses,
-                                     const float* widths, int N, int H, int W, float* out, float* workspace,
-                                     int64_t workspace_elems, void* stream) {
-  const char* what = "gsd_mesh_depth_render";
-  const MdMesh M{grid, view, records, T, cells, list, list_elems};
+namespace {
+// gsd_mesh_depth_render and gsd_mesh_depth_render_jacobian: the same checks, pose table and grid of blocks; `kernel` writes `out`
+template <typename Out, typename Kernel>
+int md_render(Kernel kernel, const char* what, const MdMesh& M, const float* poses, const float* widths, int N, int H, int W, Out* out,
+              float* workspace, int64_t workspace_elems, void* stream) {
   if (md_check(M, what)) return GSD_ERR_BAD_ARG;
   GSD_REQUIRE(poses && widths && out && workspace, GSD_ERR_BAD_ARG, "%s: null pointer", what);
   GSD_REQUIRE(N >= 1 && H >= 1 && W >= 1, GSD_ERR_BAD_ARG, "%s: bad dims N=%d H=%d W=%d", what, N, H, W);
@@ -682,13 +918,32 @@ extern "C" int gsd_mesh_depth_render(const gsd_mesh_grid* grid, const gsd_mesh_v
   GSD_REQUIRE(blocks <= INT32_MAX, GSD_ERR_UNSUPPORTED, "%s: %lld blocks (N=%d of %d x %d), at most 2^31-1 per launch", what,
               (long long)blocks, N, H, W);
   const hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, poses, widths, N, 1, view->width_offset,
+  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, poses, widths, N, 1, M.view->width_offset,
                      workspace);
   GSD_LAUNCH_CHECK(what);
-  hipLaunchKernelGGL(mesh_render, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), V, records, cells + 2, list,
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(M.grid), V, M.records, M.cells + 2, M.list,
                      (const float*)workspace, out);
   GSD_LAUNCH_CHECK(what);
   return GSD_OK;
+}
+}   // namespace
+
+extern "C" int gsd_mesh_depth_render(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
+                                     const int32_t* cells, const int32_t* list, int64_t list_elems, const float* poses,
+                                     const float* widths, int N, int H, int W, float* out, float* workspace,
+                                     int64_t workspace_elems, void* stream) {
+  return md_render(mesh_render, "gsd_mesh_depth_render", MdMesh{grid, view, records, T, cells, list, list_elems}, poses, widths, N, H, W,
+                   out, workspace, workspace_elems, stream);
+}
+
+extern "C" int gsd_mesh_depth_render_jacobian(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
+                                              const int32_t* cells, const int32_t* list, int64_t list_elems, const float* poses,
+                                              const float* widths, int N, int H, int W, double* out, float* workspace,
+                                              int64_t workspace_elems, void* stream) {
+  const char* what = "gsd_mesh_depth_render_jacobian";
+  GSD_REQUIRE(((uintptr_t)out & 7) == 0, GSD_ERR_BAD_ARG, "%s: out must be 8-byte aligned", what);
+  return md_render(mesh_render_jacobian, what, MdMesh{grid, view, records, T, cells, list, list_elems}, poses, widths, N, H, W, out,
+                   workspace, workspace_elems, stream);
 }
 
 // doubles: the pose table (8 floats a row) | one partial row per block
@@ -730,4 +985,67 @@ extern "C" int gsd_mesh_pose_score_widths(const gsd_mesh_grid* grid, const gsd_m
   const int64_t table_words = (int64_t)B * P * (MD_POSE / 2), half_words = ((int64_t)B * G + 1) / 2;
   return md_score(M, Q, reinterpret_cast<float*>(workspace), reinterpret_cast<float*>(workspace + table_words),
                   workspace + table_words + half_words, (hipStream_t)stream, what);
+}
+
+// doubles: the pose table (8 floats a row) | one partial row of MD_NROW per block
+extern "C" int64_t gsd_mesh_pose_normal_workspace(int B, int P, int H, int W, int stride) {
+  const int64_t blocks = md_score_blocks(B, P, H, W, stride);
+  if (blocks < 0 || blocks > INT32_MAX) return 0;
+  return (int64_t)B * P * (MD_POSE / 2) + blocks * MD_NROW;
+}
+
+// md_score's launches with the normal kernels: the pose table with one width per candidate (per = 1), one partial row per block,
+// one wave per candidate
+extern "C" int gsd_mesh_pose_normal(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
+                                    const int32_t* cells, const int32_t* list, int64_t list_elems, const float* observed, int B,
+                                    const float* candidates, const float* widths, int P, int H, int W, int stride, double* rows,
+                                    double* workspace, int64_t workspace_elems, void* stream) {
+  const char* what = "gsd_mesh_pose_normal";
+  const MdMesh M{grid, view, records, T, cells, list, list_elems};
+  const MdScore Q{observed, B, candidates, widths, P, 1, H, W, stride, 0.f, rows};
+  if (md_check_score(M, Q, workspace, workspace_elems, gsd_mesh_pose_normal_workspace(B, P, H, W, stride), what)) return GSD_ERR_BAD_ARG;
+  const int N = B * P;
+  const int64_t blocks = md_score_blocks(B, P, H, W, stride);
+  float* table = reinterpret_cast<float*>(workspace);
+  double* partial = workspace + (int64_t)N * (MD_POSE / 2);
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mesh_pose_table, dim3((unsigned)ceil_div(N, 256)), dim3(256), 0, st, candidates, widths, N, 1, view->width_offset,
+                     table);
+  GSD_LAUNCH_CHECK(what);
+  if (blocks > 0) {      // a stride that leaves no lattice point: every row is 16 zeros
+    hipLaunchKernelGGL(mesh_pose_normal, dim3((unsigned)blocks), dim3(256), 0, st, md_grid(grid), md_view(M, H, W),
+                       md_lattice(H, W, stride, P, 0.f), records, cells + 2, list, (const float*)table, observed, partial);
+    GSD_LAUNCH_CHECK(what);
+  }
+  hipLaunchKernelGGL(mesh_pose_normal_sum, dim3((unsigned)N), dim3(64), 0, st, (const double*)partial, (int)(blocks / N),
+                     (const float*)table, rows);
+  GSD_LAUNCH_CHECK(what);
+  return GSD_OK;
+}
+
+extern "C" int gsd_mesh_pose_lm_update(const gsd_pose_lm* lm, int B, float* pose, float* width, double* lambda, double* row,
+                                       float* trial_pose, float* trial_width, const double* trial_row, double* trace,
+                                       int32_t* accepted, double* last_step, void* stream) {
+  const char* what = "gsd_mesh_pose_lm_update";
+  GSD_REQUIRE(lm && pose && width && lambda && row && trial_pose && trial_width && trial_row && trace && accepted && last_step,
+              GSD_ERR_BAD_ARG, "%s: null pointer", what);
+  GSD_REQUIRE(B >= 1, GSD_ERR_BAD_ARG, "%s: %d problems, at least 1", what, B);
+  GSD_REQUIRE((lm->free_mask & 7) == 7 && (lm->free_mask & ~15) == 0, GSD_ERR_BAD_ARG,
+              "%s: free_mask %d: bits 0..2 (the pose) must be set, bit 3 (the width) may be, no other", what, lm->free_mask);
+  GSD_REQUIRE(lm->down > 0.0 && lm->down <= 1.0 && lm->up >= 1.0 && isfinite(lm->up) && lm->lambda_min >= 0.0 &&
+                  lm->lambda_max >= lm->lambda_min && isfinite(lm->lambda_max),
+              GSD_ERR_BAD_ARG, "%s: need 0 < down <= 1 <= up and 0 <= lambda_min <= lambda_max, all finite", what);
+  for (int k = 0; k < 4; ++k)
+    GSD_REQUIRE(lm->max_step[k] >= 0.0 && isfinite(lm->max_step[k]), GSD_ERR_BAD_ARG, "%s: max_step[%d] = %g must be finite and >= 0",
+                what, k, lm->max_step[k]);
+  GSD_REQUIRE((((uintptr_t)lambda | (uintptr_t)row | (uintptr_t)trial_row | (uintptr_t)trace | (uintptr_t)last_step) & 7) == 0,
+              GSD_ERR_BAD_ARG, "%s: the fp64 arrays must be 8-byte aligned", what);
+  MdLm p;
+  p.down = lm->down, p.up = lm->up, p.lambda_min = lm->lambda_min, p.lambda_max = lm->lambda_max;
+  for (int k = 0; k < 4; ++k) p.max_step[k] = lm->max_step[k];
+  p.free_mask = lm->free_mask, p.first = lm->first != 0;
+  hipLaunchKernelGGL(mesh_pose_lm_update, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, (hipStream_t)stream, p, B, pose, width, lambda,
+                     row, trial_pose, trial_width, trial_row, trace, accepted, last_step);
+  GSD_LAUNCH_CHECK(what);
+  return GSD_OK;
 }

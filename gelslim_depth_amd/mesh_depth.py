@@ -282,30 +282,49 @@ def render_depth(grid: MeshGrid, poses: torch.Tensor, grasp_widths: torch.Tensor
     from the device and a negative or non-finite one raises MeshDepthError (a ValueError) before anything of libgsd runs: this
     is the call's only synchronisation.  `validate=False` promises that the caller has checked (generate_depth_images_v1
     checks the whole file on the host): then nothing is synchronised, and a sample with a bad g comes out as NaN."""
-    _check_tensors("render_depth", grid, (("poses", poses, "(N, 3)"), ("grasp_widths", grasp_widths, "(N,)")), contiguous=True)
+    return _render("render_depth", False, grid, poses, grasp_widths, image_size, image_height_mm, grasp_width_offset, LR_flip, invert_affine,
+                   out, validate)
+
+
+def _render(what: str, jacobian: bool, grid, poses, grasp_widths, image_size, image_height_mm, grasp_width_offset, LR_flip, invert_affine,
+            out, validate) -> torch.Tensor:
+    """`render_depth` ((N, 2, H, W) fp32, gsd_mesh_depth_render) and, with `jacobian`, `render_depth_jacobian` ((N, 2, 3, H, W)
+    fp64, gsd_mesh_depth_render_jacobian): the same checks, view, workspace and call."""
+    _check_tensors(what, grid, (("poses", poses, "(N, 3)"), ("grasp_widths", grasp_widths, "(N,)")), contiguous=True)
     if poses.dim() != 2 or poses.shape[1] != 3 or poses.shape[0] < 1:
-        raise MeshDepthError(f"render_depth: poses must be (N, 3) with N >= 1, got {tuple(poses.shape)}")
+        raise MeshDepthError(f"{what}: poses must be (N, 3) with N >= 1, got {tuple(poses.shape)}")
     n = int(poses.shape[0])
     if tuple(grasp_widths.shape) != (n,):
-        raise MeshDepthError(f"render_depth: {n} poses but grasp_widths of shape {tuple(grasp_widths.shape)}")
+        raise MeshDepthError(f"{what}: {n} poses but grasp_widths of shape {tuple(grasp_widths.shape)}")
     h, w = (int(d) for d in image_size)
     mpp = float(image_height_mm) / h if h > 0 else float("nan")
     if h < 1 or w < 1 or not (math.isfinite(mpp) and mpp > 0.0):
-        raise MeshDepthError(f"render_depth: image_size {tuple(image_size)} and image_height_mm {image_height_mm!r} must be positive")
+        raise MeshDepthError(f"{what}: image_size {tuple(image_size)} and image_height_mm {image_height_mm!r} must be positive")
     offset = float(grasp_width_offset)
     if not math.isfinite(offset):
-        raise MeshDepthError(f"render_depth: grasp_width_offset must be finite, got {grasp_width_offset!r}")
-    out = _out_tensor("render_depth", grid, out, (n, 2, h, w), torch.float32)
+        raise MeshDepthError(f"{what}: grasp_width_offset must be finite, got {grasp_width_offset!r}")
+    out = _out_tensor(what, grid, out, (n, 2, 3, h, w) if jacobian else (n, 2, h, w), torch.float64 if jacobian else torch.float32)
     if validate:
-        _check_widths("render_depth", grasp_widths, offset)
+        _check_widths(what, grasp_widths, offset)
     view = _mesh_view(grid, mpp, offset, LR_flip, invert_affine)
+    entry = "gsd_mesh_depth_render_jacobian" if jacobian else "gsd_mesh_depth_render"
     with torch.cuda.device(grid.device):
         ws = torch.empty((int(lib.gsd_mesh_depth_render_workspace(n)),), device=grid.device, dtype=torch.float32)
-        check(lib.gsd_mesh_depth_render(C.byref(grid.grid), C.byref(view), grid.records.data_ptr(), grid.triangles,
-                                        grid.cells.data_ptr(), grid.list.data_ptr(), grid.list.numel(), poses.data_ptr(),
-                                        grasp_widths.data_ptr(), n, h, w, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        L.stream_ptr()), "mesh_depth_render")
+        check(getattr(lib, entry)(C.byref(grid.grid), C.byref(view), grid.records.data_ptr(), grid.triangles,
+                                  grid.cells.data_ptr(), grid.list.data_ptr(), grid.list.numel(), poses.data_ptr(),
+                                  grasp_widths.data_ptr(), n, h, w, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  L.stream_ptr()), entry[4:])
     return out
+
+
+def render_depth_jacobian(grid: MeshGrid, poses: torch.Tensor, grasp_widths: torch.Tensor, image_size: Sequence[int] = (320, 427),
+                          image_height_mm: float = 12.0, grasp_width_offset: float = 0.0, LR_flip: bool = False,
+                          invert_affine: bool = False, out: Optional[torch.Tensor] = None, validate: bool = True) -> torch.Tensor:
+    """(N, 2, 3, H, W) float64: the derivatives of every pixel of `render_depth`'s images with respect to a1 = 1000 t1 [mm],
+    a2 = 1000 t2 [mm] and theta [rad] -- the terms that `pose_normal_rows` sums, written out for
+    inspection.  0 where the pixel's depth is 0.  The arguments are `render_depth`'s."""
+    return _render("render_depth_jacobian", True, grid, poses, grasp_widths, image_size, image_height_mm, grasp_width_offset, LR_flip,
+                   invert_affine, out, validate)
 
 
 # ---- the reference's class ------------------------------------------------------------------------------------------
@@ -419,14 +438,17 @@ def lattice_points(image_size: Sequence[int], stride: int = 1) -> int:
 
 
 POSE_WIDTHS_MAX = L.GSD_POSE_WIDTHS_MAX      # widths per observation that one `score_poses_widths` call takes
+NORMAL_ROW = L.GSD_POSE_NORMAL_ROW      # columns of a normal row: sum e^2, #active, J^T e (a1, a2, theta, g), upper triangle of J^T J
 
 
 def _score(what: str, many: bool, grid, observed, candidates, widths, image_height_mm, grasp_width_offset, LR_flip, invert_affine,
-           stride, contact_depth, out, validate) -> torch.Tensor:
-    """`score_poses` (`widths` (B,), rows (B, P, 5), gsd_mesh_pose_score) and, with `many`, `score_poses_widths` (`widths` (B, G),
-    rows (B, P, G, 5), gsd_mesh_pose_score_widths): the same checks, view and call, `what` the public name for the messages."""
+           stride, contact_depth, out, validate, normal: bool = False) -> torch.Tensor:
+    """`score_poses` (`widths` (B,), rows (B, P, 5), gsd_mesh_pose_score), with `many` `score_poses_widths` (`widths` (B, G),
+    rows (B, P, G, 5), gsd_mesh_pose_score_widths) and with `normal` `pose_normal_rows` (`widths` (B,) or (B, P), rows (B, P, 16),
+    gsd_mesh_pose_normal): the same checks, view and call, `what` the public name for the messages."""
     _check_tensors(what, grid, (("observed", observed, "(B, 2, H, W)"), ("candidates", candidates, "(B, P, 3) or (P, 3)"),
-                                ("widths" if many else "grasp_widths", widths, "(B, G)" if many else "(B,)")))
+                                ("widths" if many or normal else "grasp_widths", widths,
+                                 "(B, G)" if many else "(B,) or (B, P)" if normal else "(B,)")))
     if observed.dim() != 4 or observed.shape[1] != 2 or min(observed.shape) < 1:
         raise MeshDepthError(f"{what}: observed must be (B, 2, H, W) with B, H, W >= 1, got {tuple(observed.shape)}")
     b, _, h, w = (int(d) for d in observed.shape)
@@ -438,9 +460,13 @@ def _score(what: str, many: bool, grid, observed, candidates, widths, image_heig
     if many:
         if widths.dim() != 2 or widths.shape[0] != b or not 1 <= widths.shape[1] <= POSE_WIDTHS_MAX:
             raise MeshDepthError(f"{what}: widths must be ({b}, G) with 1 <= G <= {POSE_WIDTHS_MAX}, got {tuple(widths.shape)}")
+    elif normal:
+        if tuple(widths.shape) not in ((b,), (b, p)):
+            raise MeshDepthError(f"{what}: widths must be ({b},) or ({b}, {p}), one per observation or per candidate, got {tuple(widths.shape)}")
+        widths = widths.reshape(b, -1).expand(b, p)
     elif tuple(widths.shape) != (b,):
         raise MeshDepthError(f"{what}: {b} observations but grasp_widths of shape {tuple(widths.shape)}")
-    g = tuple(int(d) for d in widths.shape[1:])          # (G,) or (): where G stands in the shapes and in the argument lists
+    g = tuple(int(d) for d in widths.shape[1:]) if not normal else ()          # (G,) or (): where G stands in the shapes and in the argument lists
     observed, candidates, widths = observed.contiguous(), candidates.contiguous(), widths.contiguous()
     mpp = float(image_height_mm) / h
     if not (math.isfinite(mpp) and mpp > 0.0):
@@ -453,8 +479,9 @@ def _score(what: str, many: bool, grid, observed, candidates, widths, image_heig
     depth = float(contact_depth)
     if not (math.isfinite(depth) and depth >= 0.0):
         raise MeshDepthError(f"{what}: contact_depth must be finite and >= 0, got {contact_depth!r}")
-    out = _out_tensor(what, grid, out, (b, p) + g + (POSE_ROW,), torch.float64)
-    entry = "gsd_mesh_pose_score_widths" if many else "gsd_mesh_pose_score"          # from the module's `lib`, at every call
+    out = _out_tensor(what, grid, out, (b, p) + g + (NORMAL_ROW if normal else POSE_ROW,), torch.float64)
+    entry = "gsd_mesh_pose_score_widths" if many else "gsd_mesh_pose_normal" if normal else "gsd_mesh_pose_score"          # from the module's `lib`, at every call
+    tail = () if normal else (depth,)          # the normal rows take no contact depth
     words = int(getattr(lib, entry + "_workspace")(b, p, *g, h, w, int(stride)))
     if words < 1:
         raise MeshDepthError(f"{what}: {b} x {p} candidates{f' x {g[0]} widths' if many else ''} of {h} x {w} at stride {stride} are "
@@ -466,7 +493,7 @@ def _score(what: str, many: bool, grid, observed, candidates, widths, image_heig
         ws = torch.empty((words,), device=grid.device, dtype=torch.float64)
         check(getattr(lib, entry)(C.byref(grid.grid), C.byref(view), grid.records.data_ptr(), grid.triangles, grid.cells.data_ptr(),
                                   grid.list.data_ptr(), grid.list.numel(), observed.data_ptr(), b, candidates.data_ptr(),
-                                  widths.data_ptr(), p, *g, h, w, int(stride), depth, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  widths.data_ptr(), p, *g, h, w, int(stride), *tail, out.data_ptr(), ws.data_ptr(), ws.numel(),
                                   L.stream_ptr()), entry[4:])
     return out
 
@@ -508,6 +535,115 @@ def score_poses_widths(grid: MeshGrid, observed: torch.Tensor, candidates: torch
     `validate=False` reads nothing, and such a (b, :, k) column is five NaN per row (+inf for `pose_cost`)."""
     return _score("score_poses_widths", True, grid, observed, candidates, widths, image_height_mm, grasp_width_offset, LR_flip,
                   invert_affine, stride, contact_depth, out, validate)
+
+
+def pose_normal_rows(grid: MeshGrid, observed: torch.Tensor, candidates: torch.Tensor, widths: torch.Tensor,
+                     image_height_mm: float = 12.0, grasp_width_offset: float = 0.0, LR_flip: bool = False, invert_affine: bool = False,
+                     stride: int = 1, out: Optional[torch.Tensor] = None, validate: bool = True) -> torch.Tensor:
+    """Normal-equation rows (B, P, 16) float64 of the squared error that `score_poses` sums: per candidate
+
+        [0] sum e^2   [1] #active   [2..5] sum J_k e   [6..15] sum J_j J_k, j <= k, row-major   (k over a1, a2, theta, g)
+
+    with J the derivatives of the rendered depth with respect to a1 = 1000 t1 [mm], a2 = 1000 t2 [mm], theta [rad] and the grasp
+    width g [mm] -- of the triangle that gives the pixel its depth; 0 where the depth is 0 --, over `score_poses`' lattice, in one
+    libgsd call (gsd_mesh_pose_normal) at about the price of a score: the walk over the triangles is the same.  Entry 0 is
+    `score_poses`' sum_sq of that candidate, width and stride BIT FOR BIT, entry 1 its n_rendered at contact_depth 0.
+
+    `widths` is (B,) as `score_poses`' or (B, P), one per candidate; the other arguments and `validate` are `score_poses`'.  With
+    `validate=False` a candidate whose width + offset is negative or not finite gets 16 NaN."""
+    return _score("pose_normal_rows", False, grid, observed, candidates, widths, image_height_mm, grasp_width_offset, LR_flip,
+                  invert_affine, stride, 0.0, out, validate, normal=True)
+
+
+class PoseRefinement:
+    """What `refine_pose` found, all tensors on the device: `pose` (B, 3) fp32, `width` (B,) fp32 [mm], `cost` (B,) fp64 = sum e^2 /
+    lattice points, `normal_row` (B, 16) fp64 of that pose, `trace` (iterations + 1, B) fp64, the accepted cost after every
+    evaluation (entry 0: the start's), `accepted` (B,) int32, the trials that lowered the cost, `last_step` (B, 4) fp64, |step|
+    of the last solve (mm, mm, rad, mm)."""
+
+    def __init__(self, pose, width, cost, normal_row, trace, accepted, last_step) -> None:
+        self.pose, self.width, self.cost, self.normal_row = pose, width, cost, normal_row
+        self.trace, self.accepted, self.last_step = trace, accepted, last_step
+
+    def __repr__(self) -> str:
+        return f"PoseRefinement({self.pose.shape[0]} observations, {self.trace.shape[0] - 1} iterations)"
+
+
+_LAMBDA_MIN, _LAMBDA_MAX = 1e-12, 1e12      # bounds of the damping in refine_pose
+
+
+def refine_pose(grid: MeshGrid, observed: torch.Tensor, grasp_widths: torch.Tensor, init, iterations: int = 10, fit_width: bool = False,
+                stride: int = 1, damping: float = 1e-3, damping_up: float = 10.0, damping_down: float = 0.1,
+                max_step: Sequence[float] = (0.5, 0.5, 0.1, 0.5), cost="mse", image_height_mm: float = 12.0,
+                grasp_width_offset: float = 0.0, LR_flip: bool = False, invert_affine: bool = False, validate: bool = True) -> PoseRefinement:
+    """Continuous refinement of in-hand poses by Levenberg-Marquardt on `score_poses`' mean squared error:
+    the step that `estimate_pose`'s lattice cannot make.  `init` is (B, 3) -- or (B, S, 3) for S starts per observation, each
+    refined on its own, the lowest final sum e^2 winning under `first_argmin`'s rule.  Every iteration is one `pose_normal_rows`
+    evaluation of the trial and one gsd_mesh_pose_lm_update: the trial is accepted iff its sum e^2 is STRICTLY below the current
+    one (the damping is then multiplied by `damping_down`, otherwise by `damping_up`), and the next trial solves
+    (J^T J + damping diag(J^T J)) step = -J^T e, clipped per component to `max_step` (mm, mm, rad, mm).  So `trace` never rises.
+
+    With `fit_width` the grasp width is a fourth free parameter, started at `grasp_widths`; a trial whose width + offset falls
+    below 0 is a NaN row and is rejected.  Without it the width is returned as passed, bit for bit.  Only the 'mse' is
+    differentiable here: `cost` 'l1' and 'iou' are refused.  Nothing is read back from the device (with `validate`, the widths
+    are checked once, before the first evaluation).  The view arguments are `score_poses`'."""
+    if cost != "mse":
+        raise MeshDepthError(f"refine_pose: only cost='mse' can be refined ('l1' and 'iou' are not differentiable), got {cost!r}")
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+        raise MeshDepthError(f"refine_pose: iterations must be an integer >= 0, got {iterations!r}")
+    try:
+        steps = tuple(float(v) for v in max_step)
+        damp = tuple(float(v) for v in (damping, damping_up, damping_down))
+    except (TypeError, ValueError):
+        steps, damp = (), (float("nan"),) * 3
+    if len(steps) != 4 or not all(math.isfinite(v) and v >= 0.0 for v in steps):
+        raise MeshDepthError(f"refine_pose: max_step must be four finite values >= 0 (mm, mm, rad, mm), got {max_step!r}")
+    if not (all(math.isfinite(v) for v in damp) and _LAMBDA_MIN <= damp[0] <= _LAMBDA_MAX and damp[1] >= 1.0 and 0.0 < damp[2] <= 1.0):
+        raise MeshDepthError(f"refine_pose: need {_LAMBDA_MIN} <= damping <= {_LAMBDA_MAX}, damping_up >= 1 and 0 < damping_down <= 1, got "
+                             f"{damping!r}, {damping_up!r}, {damping_down!r}")
+    if not isinstance(grid, MeshGrid):
+        raise MeshDepthError(f"refine_pose: grid must be a MeshGrid, got {type(grid).__name__}")
+    if not isinstance(observed, torch.Tensor) or observed.dim() != 4:
+        raise MeshDepthError("refine_pose: observed must be a (B, 2, H, W) tensor")
+    b, _, h, w = (int(d) for d in observed.shape)
+    start = torch.as_tensor(init, dtype=torch.float32).to(grid.device)
+    if start.dim() == 2:
+        start = start.unsqueeze(1)
+    if start.dim() != 3 or start.shape[0] != b or start.shape[1] < 1 or start.shape[2] != 3:
+        raise MeshDepthError(f"refine_pose: init must be ({b}, 3) or ({b}, S, 3), got {tuple(start.shape)}")
+    s = int(start.shape[1])
+    if (not isinstance(grasp_widths, torch.Tensor) or grasp_widths.dtype != torch.float32 or grasp_widths.device != grid.device
+            or tuple(grasp_widths.shape) != (b,)):
+        raise MeshDepthError(f"refine_pose: grasp_widths must be a float32 ({b},) tensor on {grid.device}")
+    lm = L.gsd_pose_lm()
+    lm.down, lm.up, lm.lambda_min, lm.lambda_max = damp[2], damp[1], _LAMBDA_MIN, _LAMBDA_MAX
+    lm.max_step[:] = steps
+    lm.free_mask = 15 if fit_width else 7
+    n = b * s
+    with torch.cuda.device(grid.device):
+        dev = grid.device
+        trial_pose = start.contiguous().clone()          # (B, S, 3): what the next evaluation scores, rewritten by every update
+        trial_width = grasp_widths.unsqueeze(1).expand(b, s).contiguous()
+        pose, width = torch.empty_like(trial_pose), torch.empty_like(trial_width)
+        lam = torch.full((n,), damp[0], device=dev, dtype=torch.float64)
+        row = torch.empty((b, s, NORMAL_ROW), device=dev, dtype=torch.float64)
+        trial_row = torch.empty_like(row)
+        trace = torch.empty((int(iterations) + 1, b, s), device=dev, dtype=torch.float64)
+        accepted = torch.empty((b, s), device=dev, dtype=torch.int32)
+        last_step = torch.empty((b, s, 4), device=dev, dtype=torch.float64)
+        for it in range(int(iterations) + 1):
+            pose_normal_rows(grid, observed, trial_pose, trial_width, image_height_mm, grasp_width_offset, LR_flip, invert_affine, stride,
+                             out=trial_row, validate=validate and it == 0)
+            lm.first = int(it == 0)
+            check(lib.gsd_mesh_pose_lm_update(C.byref(lm), n, pose.data_ptr(), width.data_ptr(), lam.data_ptr(), row.data_ptr(),
+                                              trial_pose.data_ptr(), trial_width.data_ptr(), trial_row.data_ptr(), trace[it].data_ptr(),
+                                              accepted.data_ptr(), last_step.data_ptr(), L.stream_ptr()), "mesh_pose_lm_update")
+        sq = row[..., 0]
+        win = first_argmin(torch.where(torch.isnan(sq), torch.full_like(sq, float("inf")), sq))          # (B,): the best start
+        pick = lambda t: torch.gather(t, 1, win.view(b, 1, *([1] * (t.dim() - 2))).expand(b, 1, *t.shape[2:])).squeeze(1)
+        points = float(lattice_points((h, w), stride))
+        best_trace = torch.gather(trace, 2, win.view(1, b, 1).expand(trace.shape[0], b, 1)).squeeze(2)
+        return PoseRefinement(pick(pose), pick(width), pick(sq) / points, pick(row), best_trace / points, pick(accepted), pick(last_step))
 
 
 _COSTS = ("mse", "l1", "iou")
@@ -606,11 +742,17 @@ def width_schedule(width_half_span: float, width_count: int, levels: int = 4) ->
 class PoseEstimate:
     """What `estimate_pose` found, all tensors on the device: `pose` (B, 3) fp32 = (t1 [m], t2 [m], theta [rad]), `cost` (B,)
     fp64 and `row` (B, 5) fp64 of that pose at the last level's stride, `trace` (levels, B) fp64, the best cost of every level,
-    `width` (B,) fp32 [mm], the grasp width that `row` was scored at: the one passed in, or the width axis' winner."""
+    `width` (B,) fp32 [mm], the grasp width that `row` was scored at: the one passed in, or the width axis' winner.
+    `lattice_pose` (B, 3) and `lattice_cost` (B,) are the last level's winner and its cost: `pose` and `cost` themselves unless
+    `refine_iterations` > 0 moved them past the lattice; `refinement` is then the `PoseRefinement`, otherwise None."""
 
     def __init__(self, pose: torch.Tensor, cost: torch.Tensor, row: torch.Tensor, trace: torch.Tensor,
-                 width: Optional[torch.Tensor] = None) -> None:
+                 width: Optional[torch.Tensor] = None, lattice_pose: Optional[torch.Tensor] = None,
+                 lattice_cost: Optional[torch.Tensor] = None, refinement: Optional[PoseRefinement] = None) -> None:
         self.pose, self.cost, self.row, self.trace, self.width = pose, cost, row, trace, width
+        self.lattice_pose = pose if lattice_pose is None else lattice_pose
+        self.lattice_cost = cost if lattice_cost is None else lattice_cost
+        self.refinement = refinement
 
     def __repr__(self) -> str:
         return f"PoseEstimate({self.pose.shape[0]} observations, {self.trace.shape[0]} levels)"
@@ -620,7 +762,7 @@ def estimate_pose(grid: MeshGrid, observed: torch.Tensor, grasp_widths: torch.Te
                   counts: Sequence[int] = (7, 7, 9), levels: int = 4, strides: Optional[Sequence[int]] = None, cost="mse",
                   image_height_mm: float = 12.0, grasp_width_offset: float = 0.0, LR_flip: bool = False,
                   invert_affine: bool = False, contact_depth: float = 0.0, validate: bool = True, width_half_span: float = 0.0,
-                  width_count: int = 1) -> PoseEstimate:
+                  width_count: int = 1, refine_iterations: int = 0) -> PoseEstimate:
     """The planar pose (t1, t2, theta) of `grid`'s mesh in the hand from depth images `observed` (B, 2, H, W) -- a prediction of the
     net or a label -- and the grasp widths: a coarse-to-fine lattice search, render-and-compare through `score_poses`.
 
@@ -640,8 +782,16 @@ def estimate_pose(grid: MeshGrid, observed: torch.Tensor, grasp_widths: torch.Te
     `width_count` = 1 (`width_half_span` is then ignored), is the fixed-width search above, call for call.  `PoseEstimate.width`
     is the width of the winner.
 
+    `refine_iterations` = K > 0 runs `refine_pose` for K iterations from the last level's winner, at the
+    last level's stride, the width free iff there is a width axis.  `pose`, `width` and `cost` are then the refined ones, `row` is
+    one `score_poses` call at the refined pose, and `lattice_pose` / `lattice_cost` keep the winner.  The refinement minimises
+    the 'mse' whatever `cost` is: it accepts a step only if sum e^2 -- `score_poses`' sum_sq bit for bit -- falls, so for
+    cost='mse' `cost` <= `lattice_cost` holds exactly; for another `cost` it need not.  The default 0 is the search alone.
+
     Everything runs on the device; nothing is read back (with `validate=True`, `score_poses`' one check of the widths is made
     once, before the first level -- of the starting widths, with a width axis).  The view arguments are `score_poses`'."""
+    if isinstance(refine_iterations, bool) or not isinstance(refine_iterations, (int, np.integer)) or refine_iterations < 0:
+        raise MeshDepthError(f"estimate_pose: refine_iterations must be an integer >= 0, got {refine_iterations!r}")
     spans, offsets = search_schedule(half_span, counts, levels)
     levels = int(levels)
     strides = (1,) * levels if strides is None else tuple(strides)
@@ -699,7 +849,15 @@ def estimate_pose(grid: MeshGrid, observed: torch.Tensor, grasp_widths: torch.Te
                 centre_w = torch.gather(cand_w, 1, (win % n_w).view(b, 1)).squeeze(1).contiguous()
                 win = torch.div(win, n_w, rounding_mode="floor")
             centre = torch.gather(cand, 1, win.view(b, 1, 1).expand(b, 1, 3)).squeeze(1).contiguous()
-    return PoseEstimate(centre, best_cost, best_row, trace, centre_w if width_axis else grasp_widths)
+        width = centre_w if width_axis else grasp_widths
+        if refine_iterations == 0:
+            return PoseEstimate(centre, best_cost, best_row, trace, width)
+        fine = refine_pose(grid, observed, width, centre, int(refine_iterations), width_axis, strides[-1], image_height_mm=image_height_mm,
+                           grasp_width_offset=grasp_width_offset, LR_flip=LR_flip, invert_affine=invert_affine, validate=False)
+        row = score_poses(grid, observed, fine.pose.unsqueeze(1), fine.width, image_height_mm, grasp_width_offset, LR_flip, invert_affine,
+                          strides[-1], contact_depth, validate=False).squeeze(1)
+        return PoseEstimate(fine.pose, pose_cost(row, cost, lattice_points((h, w), strides[-1])), row, trace, fine.width, centre,
+                            best_cost, fine)
 
 
 def pose_error(estimate, truth: torch.Tensor) -> torch.Tensor:

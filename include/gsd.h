@@ -566,6 +566,66 @@ int gsd_mesh_pose_score_widths(const gsd_mesh_grid* grid, const gsd_mesh_view* v
                                const float* candidates, const float* widths, int P, int G, int H, int W, int stride,
                                float contact_depth, double* rows, double* workspace, int64_t workspace_elems, void* stream);
 
+/* ---- refinement past the lattice: normal-equation rows and a damped Gauss-Newton step ---- */
+/* For one lattice point of one (observation, candidate, channel), in section 16's notation:
+ *   winner: among the triangles that cover the point, the one with the largest sg * q, THE LOWEST TRIANGLE ID among equal
+ *     values (the order of a cell's list changes from build to build, the ids do not).  m is that largest value and
+ *     R = -max(0, m - g/2): the bits of gsd_mesh_depth_render.  No covering triangle: no winner, R = 0.
+ *   slope, in fp64 from the winner's record floats (sorted vertices, inv), a = q1 - q0, b = q2 - q0:
+ *     qx = (a (y2 - y0) - b (y1 - y0)) inv,   qy = (b (x1 - x0) - a (x2 - x0)) inv;   the clamp of q to the triangle's range is ignored.
+ *   point derivatives, in fp64 from the floats of the pixel -> mesh map (cs, sn, pa, pb, da = pa - t1, db = pb - t2), for the
+ *     parameters a1 = 1000 t1 [mm], a2 = 1000 t2 [mm], theta [rad]:
+ *       invert_affine = 0:  x_a1 = -cs, x_a2 = -sn, y_a1 = sn, y_a2 = -cs, x_th = -sn da + cs db, y_th = -sn db - cs da
+ *       invert_affine = 1:  x_a1 = 1,   x_a2 = 0,   y_a1 = 0,  y_a2 = 1,   x_th = -sn pa - cs pb, y_th = cs pa - sn pb
+ *   Jacobian: a point is active when R < 0.  There J_k = -sg (qx x_k + qy y_k) for k = a1, a2, theta and J_g = dR/dg = 0.5
+ *     (g the width in mm); at an inactive point all four are 0.
+ * gsd_mesh_pose_normal: one row of GSD_POSE_NORMAL_ROW doubles per candidate, summed over both channels and gsd_mesh_pose_score's
+ * pixel lattice, e = (double)R - (double)D:
+ *   [0] sum e^2   [1] #active   [2..5] sum J_k e (a1, a2, theta, g)   [6..15] sum J_j J_k, j <= k, row-major upper triangle
+ * Entry 0 is gsd_mesh_pose_score's sum_sq of that candidate, width and stride BIT FOR BIT (the same tiles, tree and order), entry
+ * 1 its n_rendered at contact_depth = 0.  widths: B x P floats, ONE PER CANDIDATE (g = widths[b][p] + view.width_offset); a
+ * negative or non-finite g gives 16 NaN, a non-finite D on the lattice non-finite sums.  A row depends on its own observation,
+ * candidate, width, stride and image alone and repeats bitwise: no float atomics, nothing added in memory.
+ * workspace: gsd_mesh_pose_normal_workspace doubles, 8-byte aligned (0 for arguments the call refuses).  Every other argument,
+ * and what is refused with GSD_ERR_BAD_ARG before any launch, as for gsd_mesh_pose_score.  Nothing is allocated or synchronised. */
+#define GSD_POSE_NORMAL_ROW 16
+int64_t gsd_mesh_pose_normal_workspace(int B, int P, int H, int W, int stride);   /* doubles */
+int gsd_mesh_pose_normal(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T, const int32_t* cells,
+                         const int32_t* list, int64_t list_elems, const float* observed, int B, const float* candidates,
+                         const float* widths, int P, int H, int W, int stride, double* rows, double* workspace,
+                         int64_t workspace_elems, void* stream);
+/* gsd_mesh_depth_render's arguments and workspace; out: N x 2 x 3 x H x W DOUBLES, 8-byte aligned: J_a1, J_a2, J_theta of every
+ * pixel of every channel, the terms gsd_mesh_pose_normal sums, for inspection. */
+int gsd_mesh_depth_render_jacobian(const gsd_mesh_grid* grid, const gsd_mesh_view* view, const float* records, int T,
+                                   const int32_t* cells, const int32_t* list, int64_t list_elems, const float* poses,
+                                   const float* widths, int N, int H, int W, double* out, float* workspace, int64_t workspace_elems,
+                                   void* stream);
+/* One Levenberg-Marquardt bookkeeping step for B independent problems, on the device in fp64, one thread each; nothing is read
+ * back.  Per problem the state is pose (3 floats: t1 [m], t2 [m], theta [rad]), width (float, mm), lambda (double), row (its
+ * GSD_POSE_NORMAL_ROW doubles), accepted (int32); the trial is trial_pose, trial_width and trial_row, its normal row.
+ *   1. accept iff trial_row[0] < row[0] (strict; a NaN never wins): the state and row become the trial's, ++accepted and
+ *      lambda = max(lambda * down, lambda_min); otherwise lambda = min(lambda * up, lambda_max).
+ *      With `first` != 0 the trial is taken as the state unconditionally, accepted = 0 and lambda is left as it is.
+ *   2. solve (A + lambda diag(A)) d = -b, A = row[6..15], b = row[2..5], on the free parameters (bit k of free_mask, order a1,
+ *      a2, theta, g; bits 0..2 must be set, bit 3 frees the width) by a Cholesky factorisation in that fixed order.  A pivot
+ *      that is <= 0 or not finite, or a solution that is not finite, gives d = 0.  d is clipped per component to max_step
+ *      (mm, mm, rad, mm).
+ *   3. trial_pose = (float)((double)t + d_a / 1000) for the translations, (float)((double)theta + d_theta); trial_width =
+ *      (float)((double)g + d_g): the next trial.  trace[i] = row[0] of the state (the accepted cost, one double per problem),
+ *      last_step[4 i + k] = |d_k|.
+ * GSD_ERR_BAD_ARG before the launch: a null pointer, B < 1, a free_mask without bits 0..2 or with a bit above 3, a factor outside
+ * 0 < down <= 1 <= up, lambda bounds that are negative, unordered or not finite, a max_step that is negative or not finite. */
+typedef struct gsd_pose_lm {
+  double down, up;                /* factors of lambda after an accepted / a rejected trial */
+  double lambda_min, lambda_max;
+  double max_step[4];             /* mm, mm, rad, mm */
+  int32_t free_mask;              /* bit k: parameter k (a1, a2, theta, g) is free */
+  int32_t first;                  /* != 0: the trial initialises the state */
+} gsd_pose_lm;
+int gsd_mesh_pose_lm_update(const gsd_pose_lm* lm, int B, float* pose, float* width, double* lambda, double* row, float* trial_pose,
+                            float* trial_width, const double* trial_row, double* trace, int32_t* accepted, double* last_step,
+                            void* stream);
+
 /* ---- optimiser (train_unet.py:306,375-376) -------------------------------------------------- */
 /* Fused torch.optim.Adam(lr, betas, eps, weight_decay: coupled L2) + torch_ema update over a flat
  * parameter arena. step is the 1-based Adam step; ema may be NULL; ema_decay already resolved
