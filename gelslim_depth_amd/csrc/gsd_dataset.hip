@@ -4,7 +4,9 @@
 //   gsd_ingest_images    finger split (strided channel view) + difference image + F.interpolate(mode='area')
 //                        /root/reference/gelslim_depth/datasets/general_dataset.py:61-83, image_utils.py:6-15
 //   gsd_channel_stats    per-channel min / max / mean / unbiased std over the whole dataset
-//                        general_dataset.py:199-220
+//                        general_dataset.py:199-220.  As tensor.min() / .max() / .mean() / .std() there, one NaN element makes
+//                        all four statistics of its channel NaN (min and max keep a NaN: nan_min / nan_max); an infinity gives
+//                        an infinite min or max and mean and a NaN std; a single element has std NaN
 //   gsd_gather_affine    batch assembly: rows picked by a (shuffled) index vector, normalised on the way
 //                        general_dataset.py:222-236 (__getitem__ + normalize_sample), normalization_utils.py:4-35,67-99
 //
@@ -18,6 +20,10 @@
 namespace {
 
 constexpr int SG = 64;  // row groups of the stats reduction
+
+// min / max that keep a NaN, as torch's reductions do (fminf / fmaxf and fmin / fmax return the other operand)
+template <typename T> __device__ __forceinline__ T nan_min(T a, T b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
+template <typename T> __device__ __forceinline__ T nan_max(T a, T b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
 
 template <typename T>
 __global__ __launch_bounds__(256) void ingest_kernel(const T* __restrict__ in, const T* __restrict__ base, int C, int H, int W,
@@ -56,14 +62,14 @@ __global__ __launch_bounds__(256) void stats_stage1(const float* __restrict__ x,
     const float v = x[((size_t)n * C + c) * HW + p];
     s += (double)v;
     s2 += (double)v * (double)v;
-    mn = fminf(mn, v);
-    mx = fmaxf(mx, v);
+    mn = nan_min(mn, v);
+    mx = nan_max(mx, v);
   }
   for (int o = 32; o > 0; o >>= 1) {
     s += __shfl_xor(s, o, 64);
     s2 += __shfl_xor(s2, o, 64);
-    mn = fminf(mn, __shfl_xor(mn, o, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    mn = nan_min(mn, __shfl_xor(mn, o, 64));
+    mx = nan_max(mx, __shfl_xor(mx, o, 64));
   }
   __shared__ double red[4][4];
   if ((threadIdx.x & 63) == 0) {
@@ -77,11 +83,11 @@ __global__ __launch_bounds__(256) void stats_stage1(const float* __restrict__ x,
     double* o = ws + ((size_t)c * SG + g) * 4;
     o[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
     o[1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-    o[2] = fmin(fmin(red[0][2], red[1][2]), fmin(red[2][2], red[3][2]));
-    o[3] = fmax(fmax(red[0][3], red[1][3]), fmax(red[2][3], red[3][3]));
+    o[2] = nan_min(nan_min(red[0][2], red[1][2]), nan_min(red[2][2], red[3][2]));
+    o[3] = nan_max(nan_max(red[0][3], red[1][3]), nan_max(red[2][3], red[3][3]));
   }
 }
-// stage 2: one thread per channel; out[c] = {min, max, mean, std (unbiased, torch.std default)}
+// stage 2: one thread per channel; out[c] = {min, max, mean, std (unbiased, torch.std default)}; a NaN stays in all four
 __global__ void stats_stage2(const double* __restrict__ ws, int C, double count, double* __restrict__ out) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
@@ -90,8 +96,8 @@ __global__ void stats_stage2(const double* __restrict__ ws, int C, double count,
     const double* p = ws + ((size_t)c * SG + g) * 4;
     s += p[0];
     s2 += p[1];
-    mn = fmin(mn, p[2]);
-    mx = fmax(mx, p[3]);
+    mn = nan_min(mn, p[2]);
+    mx = nan_max(mx, p[3]);
   }
   const double mean = s / count;
   double var = count > 1.0 ? (s2 - s * mean) / (count - 1.0) : __builtin_nan("");

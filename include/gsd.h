@@ -706,7 +706,9 @@ int gsd_ingest_images_interp(int mode, const void* in, const void* base, int dty
 int gsd_gaussian_blur(const float* in, int64_t planes, int H, int W, const float* kernel2d, int K, float* out, void* stream);
 /* Per-channel {min, max, mean, unbiased std} over x (N,C,HW) -> out[4*C] doubles
  * (calculate_image_normalization_params / calculate_depth_normalization_params, general_dataset.py:199-220).
- * workspace: gsd_channel_stats_workspace(C) doubles. Deterministic (fixed reduction order). */
+ * workspace: gsd_channel_stats_workspace(C) doubles. Deterministic (fixed reduction order).
+ * Non-finite input answers as torch's tensor.min() / .max() / .mean() / .std() do: a NaN element makes all four statistics of
+ * its channel NaN; an infinity gives an infinite mean and a NaN std; N * HW == 1 gives a NaN std. */
 int64_t gsd_channel_stats_workspace(int C);
 int gsd_channel_stats(const float* x, int64_t N, int C, int64_t HW, double* out, double* workspace, void* stream);
 /* Batch assembly (__getitem__ + normalize_sample, general_dataset.py:222-236, behind DataLoader's shuffle):

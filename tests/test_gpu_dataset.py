@@ -1,5 +1,6 @@
 """GPU parity for SURVEY 8(f) N4: the device-resident dataset path (gelslim_depth_amd/dataset.py, gsd_dataset.hip)
-against the golden fixture made with the reference's normalisers and against oracle/dataset_ref.py."""
+against the golden fixture made with the reference's normalisers and against oracle/dataset_ref.py.
+The per-element fp64 checks of these kernels (derived bounds, NaN-filled outputs, sentinels) are tests/test_gpu_data_path_fp64.py."""
 import numpy as np
 import pytest
 import torch

@@ -1,5 +1,6 @@
 """GPU parity for the SURVEY 8(f) 'next' rows: N1 inference pre/post-processing, N2 EMA-weights evaluation without
-parameter copies, N3 checkpoint written by the fused step."""
+parameter copies, N3 checkpoint written by the fused step.
+The per-element fp64 check of gsd_area_resize_affine (derived bound, every shape) is tests/test_gpu_data_path_fp64.py."""
 import types
 
 import numpy as np
