@@ -189,6 +189,7 @@ class UNetEngine(EngineBase):
         key = (n, h, w, str(dev), self._env_key())
         if self._shape == key and (not train or self.units[0].g is not None):
             return
+        self.buffers_made += 1     # past the early return: pooled, partials and the workspaces below are re-made every time
         if self._shape != key:
             for u in self.units:
                 u.raw = u.g = None

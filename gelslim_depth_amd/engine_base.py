@@ -79,6 +79,9 @@ class EngineBase:
             self.dec.append((Unit(p, 0, 1, cin, cout, i - 1), Unit(p, 3, 4, cout, cout, i - 1)))
         self.units: List[ConvUnit] = [u for pair in self.enc for u in pair] + [u for pair in self.dec for u in pair]
         self._shape = None
+        # times the engine's _ensure has (re)made its buffers: whatever holds raw pointers into them (graph.GraphedInference)
+        # is stale once this moves
+        self.buffers_made = 0
         self.sync_fn: Optional[Callable[[torch.Tensor], None]] = None   # SyncBN hook: all-reduce fp64 sums in place
         self.world = 1
         self.block_done_cb: Optional[Callable[[str], None]] = None   # data-parallel hook: a block's grads are final

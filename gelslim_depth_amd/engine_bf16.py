@@ -78,6 +78,7 @@ class UNetEngineBF16(EngineBase):
             return
         if self._shape is not None and self._shape[:5] == key[:5] and not train:
             return                      # eval after train at the same shape: everything needed exists
+        self.buffers_made += 1          # past the early returns: the concat buffers, partials and the rest are re-made below
         self._shape = key
         hs, ws = self._set_pyramid(h, w)
         bf = dict(device=dev, dtype=torch.bfloat16)

@@ -4,7 +4,18 @@ The engine's schedule is static for a fixed input shape: every buffer it touches
 kernel argument is a device pointer or a shape, nothing synchronises with the host.  So one eager warm-up (which also sets
 the kernels' LDS attributes) followed by a capture on a side stream gives a graph whose replay re-reads the CURRENT
 parameter values (the per-launch weight re-layout is part of the graph), i.e. it stays valid across optimiser steps and
-`load_state_dict` as long as the parameter storages are not replaced.
+`load_state_dict` as long as the parameter storages are not replaced AND the engine keeps its buffers: the graph holds raw
+pointers into them.  The engine re-makes them (`_ensure` past its early return, counted in `engine.buffers_made`) on
+
+  * a forward at any other batch size or image size, or after one of the engine's sizing switches changed;
+  * the first forward with a backward behind it (train mode; fp32 also an eval-mode forward of an input that requires
+    grad) at the captured shape when an eval-mode forward had made the buffers: the backward's buffers are added and the
+    shared scratch (partial rows, pooled tensors, workspaces; bf16: everything) is re-made with them.
+
+Further train steps at the captured shape, eval forwards at the captured shape and loads keep them.  So
+build the GraphedInference AFTER the first train step at its shape, and validate at the training batch size (or on a model
+of its own).  A replay after the buffers were re-made would read and write memory the allocator has handed to someone else;
+`__call__` refuses it instead.
 
 Not in the reference (eager torch); SURVEY.md section 8(d) config 1 / DESIGN.md "next" item.  Training is not captured:
 its Adam step count and EMA decay are host scalars that change every step.
@@ -41,6 +52,8 @@ class GraphedInference:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph), torch.no_grad():
             eng.forward(self.x, model._tensor_map(), train=False, out=self.y)
+        self._engine = eng
+        self._buffers_made = eng.buffers_made      # the graph's pointers are into the buffers of this making
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         if x.shape != self.x.shape:
@@ -49,6 +62,10 @@ class GraphedInference:
         if now != self._params:
             raise L.GsdError("a parameter or buffer storage was replaced since capture (e.g. a TrainStep moved the parameters "
                              "into its arena): build a new GraphedInference")
+        eng = self.model._engine
+        if eng is not self._engine or eng.buffers_made != self._buffers_made:
+            raise L.GsdError("the engine re-made its buffers since capture (a forward at another shape, or the first train-mode "
+                             "forward at this one: the graph's pointers are stale): build a new GraphedInference")
         self.x.copy_(x)
         self.graph.replay()
         return self.y
