@@ -93,6 +93,17 @@ class gsd_pose_lm(C.Structure):
                 ("max_step", C.c_double * 4), ("free_mask", C.c_int32), ("first", C.c_int32)]
 
 
+class gsd_depth_points_view(C.Structure):
+    """How gsd_depth_points_* turn pixels into points (include/gsd.h): pixel pitch, width offset, contact depth, axes, frame."""
+    _fields_ = [("mpp", C.c_double), ("width_offset", C.c_double), ("contact_depth", C.c_double), ("mid", C.c_double),
+                ("perp_ind", C.c_int32), ("swap_axes", C.c_int32), ("multiplier", C.c_int32), ("invert_affine", C.c_int32),
+                ("lr_flip", C.c_int32), ("frame", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+GSD_DEPTH_POINTS_BLOCK = 1024        # lattice points per block of gsd_depth_points_count / _write
+GSD_DEPTH_POINTS_SCAN_PASS = 4096    # block counts per pass of their scan
+
+
 class gsd_augment_draw(C.Structure):
     """What gsd_gather_augment draws for one dataset row (gsd_augment_sample)."""
     _fields_ = [("hflip", C.c_int32), ("vflip", C.c_int32), ("dy", C.c_int32), ("dx", C.c_int32),
@@ -219,6 +230,9 @@ SIGNATURES = {
     "gsd_mesh_depth_render_jacobian": (_I, [C.POINTER(gsd_mesh_grid), C.POINTER(gsd_mesh_view), _P, _I, _P, _P, _L, _P, _P, _I, _I,
                                             _I, _P, _P, _L, _P]),
     "gsd_mesh_pose_lm_update": (_I, [C.POINTER(gsd_pose_lm), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gsd_depth_points_workspace": (_L, [_I, _I, _I, _I]),
+    "gsd_depth_points_count": (_I, [C.POINTER(gsd_depth_points_view), _P, _P, _I, _I, _I, _I, _P, _P, _L, _P]),
+    "gsd_depth_points_write": (_I, [C.POINTER(gsd_depth_points_view), _P, _P, _P, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _L, _P]),
     "gsd_guard_snapshot": (_I, [_P, _P, _L, _P]),
     "gsd_guard_restore": (_I, [_GUARD, _P, _P, _L, _P]),
     "gsd_adam_ema": (_I, [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _GUARD, _P]),

@@ -626,6 +626,67 @@ int gsd_mesh_pose_lm_update(const gsd_pose_lm* lm, int B, float* pose, float* wi
                             float* trial_width, const double* trial_row, double* trace, int32_t* accepted, double* last_step,
                             void* stream);
 
+/* ---- contact point clouds and normals from depth images ---- */
+/* The inverse of section 16's pixel -> mesh map: every contact pixel of a batch of depth images becomes a 3-D point with a unit
+ * normal, in the sensor, the grasp or the object frame, by a stream compaction whose order is part of the contract.
+ *   lattice: r = stride/2 + i*stride < H, k = stride/2 + j*stride < W (gsd_mesh_pose_score's).  A lattice pixel is a point iff
+ *     its depth d < -contact_depth, compared in fp32 (a NaN is not a point).  Points are ordered by image, then channel as stored,
+ *     then r, then k, all ascending.
+ *   sensor frame (0): (x, y, z) = (mpp (r - H/2), mpp (k - W/2), d), normal n = (d_x, d_y, -1) / |.|.  d_x (along r) and d_y (along k)
+ *     are differences between the IMMEDIATE neighbours in the full image, whatever the stride; a neighbour is usable iff it is
+ *     inside the image and itself below -contact_depth: both usable (d+ - d-) / (2 mpp), one usable the one-sided difference
+ *     over mpp, none 0.
+ *   grasp frame (1): s = +1 for the right finger, -1 for the left (channel 1 is the right one, channel 0 with view.lr_flip);
+ *     (u, v, q) = (s x, y, s (g/2 - d)), g = widths[b] + view.width_offset; n = (s d_x, d_y, s) / |.|.
+ *   object frame (2): the mesh file's coordinates times pc_scale.  (ta, tb) = (u, v), or (v, u) with view.swap_axes;
+ *     (a, b) = M^-1 (ta, tb) with M = [[cos th, -sin th, 1000 t1], [sin th, cos th, 1000 t2]], M itself with view.invert_affine;
+ *     a goes to the lower in-plane axis, b to the higher one, q / multiplier + mid to axis perp_ind.  The normal's in-plane pair
+ *     goes through the linear part of the same map, its third component is divided by multiplier.
+ *   Everything after the fp32 loads is fp64 (contraction off), rounded to fp32 once at the store.
+ *   An image whose g is negative or not finite has no points in frames 1 and 2 (frame 0 reads no widths).
+ * depth: B x 2 x H x W floats in mm, channels as gsd_mesh_depth_render writes them.  widths: B floats, required for frames 1 and
+ * 2; poses: B x 3 floats (t1 [m], t2 [m], theta [rad]), required for frame 2.
+ * workspace: gsd_depth_points_workspace(B, H, W, stride) int32 words, 8-byte aligned; 0 for arguments the calls refuse (a
+ *   dimension below 1, 2 B H W >= 2^31, 2^31 or more blocks).  Words 0..1 hold the call's total as one int64 once
+ *   gsd_depth_points_count has run; the write needs the workspace as the count of the same depth, view, widths and dims left it.
+ * gsd_depth_points_count: counts (B x 2 int32) receives the true number of points of every (image, channel), the workspace the
+ *   total and the offsets.  Blocks of 1024 lattice points of one (image, channel) count by wave ballots, one block scans the
+ *   block counts in as many passes as it takes.
+ * gsd_depth_points_write: recomputes the predicate and writes points (rows x 3 floats), normals (rows x 3 floats, may be NULL)
+ *   and pixel (rows int32, ((b*2 + ch)*H + r)*W + k, may be NULL).  `rows` is what the three outputs hold; no row at or beyond it
+ *   is written.
+ *     packed, capacity = 0: point number i of the call goes to row i; the caller sized the outputs from the total.
+ *     padded, capacity = M > 0: image b's points, both channels in order, go to rows b*M .. b*M + min(n_b, M) - 1, later points
+ *       are dropped, and the rows from min(n_b, M) to M - 1 are written as NaN (pixel: -1); rows must be at least B*M.
+ *       `counts` keeps the true numbers, so an overflow stays visible.
+ * Nothing is allocated, every launch is on `stream`, nothing synchronises; no float atomics and no atomics for placement, so a
+ * repeated call gives the same bits and an image's points do not depend on its batch.
+ * GSD_ERR_BAD_ARG before any launch: a null pointer that is required, bad dims, a view with a non-zero reserved word, a frame
+ * outside 0..2, mpp not finite and positive, width_offset or mid not finite, contact_depth negative or not finite, perp_ind
+ * outside 0..2, multiplier not +-1, a flag that is not 0 or 1, capacity or rows negative, rows below B*capacity or above
+ * 2^31 - 1, a misaligned workspace.  GSD_ERR_WORKSPACE: a workspace that is too small. */
+typedef struct gsd_depth_points_view {
+  double mpp;            /* mm per pixel: image_height_mm / H                                              */
+  double width_offset;   /* added to every grasp width, mm                                                 */
+  double contact_depth;  /* c >= 0, mm: a pixel is a point iff d < -(float)c                               */
+  double mid;            /* what the perpendicular object coordinate is relative to (MeshGrid.mid), mm     */
+  int32_t perp_ind;      /* the object axis perpendicular to the image plane, 0..2                         */
+  int32_t swap_axes;     /* 0: the unaligned axis is the lower-numbered in-plane axis, 1: the aligned one is */
+  int32_t multiplier;    /* +1 or -1: the right finger looks along multiplier * axis perp_ind              */
+  int32_t invert_affine; /* the poses are those of the grasp frame in the mesh frame                       */
+  int32_t lr_flip;       /* channel order (right, left)                                                    */
+  int32_t frame;         /* 0 sensor, 1 grasp, 2 object                                                    */
+  int32_t reserved[2];   /* 0 */
+} gsd_depth_points_view;
+#define GSD_DEPTH_POINTS_BLOCK 1024      /* lattice points per block of the count and write launches */
+#define GSD_DEPTH_POINTS_SCAN_PASS 4096  /* block counts per pass of the scan                          */
+int64_t gsd_depth_points_workspace(int B, int H, int W, int stride);            /* int32 words */
+int gsd_depth_points_count(const gsd_depth_points_view* view, const float* depth, const float* widths, int B, int H, int W, int stride,
+                           int32_t* counts, int32_t* workspace, int64_t workspace_elems, void* stream);
+int gsd_depth_points_write(const gsd_depth_points_view* view, const float* depth, const float* widths, const float* poses, int B, int H,
+                           int W, int stride, int capacity, int64_t rows, float* points, float* normals, int32_t* pixel,
+                           int32_t* workspace, int64_t workspace_elems, void* stream);
+
 /* ---- optimiser (train_unet.py:306,375-376) -------------------------------------------------- */
 /* Fused torch.optim.Adam(lr, betas, eps, weight_decay: coupled L2) + torch_ema update over a flat
  * parameter arena. step is the 1-based Adam step; ema may be NULL; ema_decay already resolved
