@@ -68,21 +68,30 @@ def render(name, cases, size, plane="+y+z", flip=False, invert=False, cell=None,
     return render_depth(grid_of(name, plane, cell), poses, widths, size, SIZES[size], 0.0, flip, invert, **kw)
 
 
-def check(name, cases, size, plane="+y+z", flip=False, invert=False):
-    got = render(name, cases, size, plane, flip, invert).cpu().numpy().astype(np.float64)
-    assert got.shape == (len(cases), 2, size[0], size[1]) and np.isfinite(got).all()
+def hold(got, intervals, flip, slack, what):
+    """The rule, for any mesh: image k of `got` (B, 2, H, W) lies in [lo - slack, hi + slack] of intervals[k], every pixel, and is
+    finite and <= 0.  Returns (worst excess over [lo, hi], contact pixels)."""
+    assert got.shape[0] == len(intervals) and np.isfinite(got).all()
     worst, contact = -np.inf, 0
-    for k, (pose, g) in enumerate(cases):
-        lo, hi = interval(name, plane, tuple(pose), g, size, invert)
+    for k, (lo, hi) in enumerate(intervals):
+        assert got[k].shape == lo.shape == hi.shape
         if flip:
             lo, hi = lo[::-1], hi[::-1]
         over = np.maximum(got[k] - hi, lo - got[k])
         worst = max(worst, float(over.max()))
         contact += int((got[k] < 0).sum())
         assert np.all(got[k] <= 0)
-    print(f"{name} {size} {plane} flip={flip} invert={invert}: {len(cases)} poses, {contact} contact pixels, "
-          f"worst excess over [lo, hi] {worst:.3e} mm")
-    assert worst <= SLACK_MM, (name, size, plane, flip, invert, worst)
+    print(f"{what} flip={flip}: {len(intervals)} poses, {contact} contact pixels, worst excess over [lo, hi] {worst:.3e} mm "
+          f"(slack {slack:.0e})")
+    assert worst <= slack, (what, flip, worst)
+    return worst, contact
+
+
+def check(name, cases, size, plane="+y+z", flip=False, invert=False):
+    got = render(name, cases, size, plane, flip, invert).cpu().numpy().astype(np.float64)
+    assert got.shape == (len(cases), 2, size[0], size[1])
+    intervals = [interval(name, plane, tuple(pose), g, size, invert) for pose, g in cases]
+    _, contact = hold(got, intervals, flip, SLACK_MM, f"{name} {size} {plane} invert={invert}")
     return got, contact
 
 
