@@ -1199,9 +1199,9 @@ static int w2d_impl(const gsd_src* src, int nsrc, const float* wt, int Cin, int 
   P.d_WCp = w2d_div_of(P.WCp);
   const size_t lds = (size_t)(2 * (W2D_WTILE + 4 * P.PS) + 2 * 4 * P.nchunks + 4 * W2D_BM + 3 * 128 * NWP) * sizeof(float);
   if (gsd_env_set("GSD_W2D_TRACE"))
-    fprintf(stderr, "w2d M%d K%d %dx%d N%d nsrc %d ndst %d plain %d x4 %d u4 %d | ptr&15 %d ws %d cs%%4 %d ns%%4 %d NI %d tile %dx%d slabs %d\n", Cout, Cin, H, W, N,
+    fprintf(stderr, "w2d M%d K%d %dx%d N%d nsrc %d ndst %d plain %d x4 %d u4 %d | ptr&15 %d ws %d cs%%4 %d ns%%4 %d NI %d tile %dx%d slabs %d dfast %d\n", Cout, Cin, H, W, N,
             nsrc, ndst, (int)plain, (int)x4, (int)u4, (int)((uintptr_t)src[0].ptr & 15), src[0].w_stride, (int)(src[0].c_stride % 4),
-            (int)(src[0].n_stride % 4), P.NI, pl.TH, pl.TW, S);
+            (int)(src[0].n_stride % 4), P.NI, pl.TH, pl.TW, S, P.dfast);
   if (S > 1) {
     if (x4) return launch_w2d<true, 1, true>(P, (int)grid, lds, (hipStream_t)stream);
     if (u4) return plain ? launch_w2d<true, 2, true>(P, (int)grid, lds, (hipStream_t)stream) : launch_w2d<false, 2, true>(P, (int)grid, lds, (hipStream_t)stream);

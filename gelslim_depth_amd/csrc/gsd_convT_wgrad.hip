@@ -406,6 +406,10 @@ extern "C" int gsd_convT2x2_wgrad(const gsd_src* x, const gsd_src* dy, int Cin, 
   const int64_t need = pl.slab_elems + (int64_t)Cout * 64;
   GSD_REQUIRE(workspace_elems >= need, GSD_ERR_WORKSPACE, "%s: workspace %lld < %lld elements", what, (long long)workspace_elems,
               (long long)need);
+  // (the plane sums of the bias gradient walk dy as one dense array; refused before anything is launched, so that dW is not
+  // written by a call that fails)
+  GSD_REQUIRE(dbias == nullptr || (dy->c_stride == (int64_t)4 * H * W && dy->n_stride == (int64_t)Cout * 4 * H * W), GSD_ERR_UNSUPPORTED,
+              "gsd_convT2x2_wgrad: bias gradient needs a contiguous dy");
   WgradParams P{};   // (a1 and the conv3x3 stage geometry stay 0)
   wgrad_fill_common(P, x, 1, dy, Cin, M, workspace, N, H, W, pl.splits, pl.mblocks, pl.nblocks);
   P.Cact = Cin;
@@ -425,8 +429,6 @@ extern "C" int gsd_convT2x2_wgrad(const gsd_src* x, const gsd_src* dy, int Cin, 
   launch_convT_wgrad_reduce(workspace, dw, pl.splits, M, Cin, st);
   GSD_LAUNCH_CHECK("gsd_convT2x2_wgrad reduce");
   if (dbias != nullptr) {
-    GSD_REQUIRE(dy->c_stride == (int64_t)4 * H * W && dy->n_stride == (int64_t)Cout * 4 * H * W, GSD_ERR_UNSUPPORTED,
-                "gsd_convT2x2_wgrad: bias gradient needs a contiguous dy");
     float* ws2 = workspace + pl.slab_elems;
     hipLaunchKernelGGL(sum_planes_stage1, dim3(Cout, 64), dim3(256), 0, (hipStream_t)stream, dy->ptr, N, Cout,
                        (long long)4 * H * W, ws2);

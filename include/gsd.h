@@ -97,6 +97,27 @@ typedef struct {
   int64_t c_stride;
 } gsd_dst;
 
+/* Addressing.  n_stride and c_stride are 64-bit and every kernel forms n * n_stride + c * c_stride in 64 bits: images and planes may
+ * lie any distance apart (tests/test_gpu_far_strides_fp64.py runs every strided entry point with bases past 2^31 bytes, 2^32
+ * bytes, 2^31 and 2^32 elements).  INSIDE a plane, and in a few forms inside a block's group of planes, offsets are 32-bit; where
+ * an operand does not fit, the call is refused before anything is launched (GSD_ERR_UNSUPPORTED unless stated) or another
+ * kernel of the same entry point takes it -- each limit is stated at its entry point below and crossed on the host in
+ * tests/test_addressing_limits_cpu.py:
+ *   conv3x3 (all forms)      H, W < 32768; a source plane H * w_stride < 2^31 floats ("plane too large")
+ *   gsd_conv3x3_w2d          also a destination plane < 2^31 floats, and a source plane H * w_stride + 4 < 2^30 floats (its fills
+ *                            address a plane by an unsigned 32-bit BYTE offset); a destination whose 12 * c_stride * 4 + plane
+ *                            bytes reach 2^32 takes the 64-bit store path (same results)
+ *   gsd_conv3x3_w43          a FOLDED plan (images folded into tile rows: gsd_conv3x3_w43_partial_rows counts one image) needs
+ *                            N * n_stride < 2^31 floats for every source and destination ("batch too large for row folding");
+ *                            the call is refused, never run unfolded: the caller sized its partial rows for the folded plan
+ *   gsd_conv3x3_wgrad        the 2-D form needs 64 * c_stride * 4 < 2^31 bytes for dy and every segment, else the row form runs;
+ *                            the row form moves activations as 16-byte pieces only while BN * c_stride < 2^31 floats
+ *   grid.y / grid.z kernels  N, C <= 65535: gsd_maxpool2[_pitched], gsd_bnrelu_pitched, gsd_bn_bwd_reduce, gsd_bn_bwd_apply,
+ *                            gsd_conv1x1_out (N), gsd_conv1x1_out_wgrad, gsd_gather_affine (B, C), gsd_gather_augment (B, Ci + Cd;
+ *                            H * W < 2^30), gsd_ingest_images[_interp], gsd_[area_]resize_affine, gsd_conv3x3_dgrad_bn (Cout)
+ *   gsd_conv1x1_out          dense planes (c_stride == H * W; GSD_ERR_BAD_ARG), any n_stride
+ *   gsd_convT2x2_wgrad       any strides for dW; the bias gradient needs a dense dy (see there) */
+
 /* ---- library ------------------------------------------------------------------------------ */
 const char* gsd_version(void);
 const char* gsd_last_error(void);
@@ -155,7 +176,11 @@ int gsd_conv3x3_dgrad_bnrelu(const gsd_src* src, const float* wt, int Cin, int C
  * same fp32 storage and accumulation; weights from gsd_weight_layout modes 4 (forward) / 5 (dX):
  * [m-block of 64][k row = ci*18 + r*6 + f][64], U = G g per kernel row r).  gsd_conv3x3_algo says which form the
  * library prefers for a shape (0 direct, 1 Winograd: tile padding can eat the gain on small images); the caller
- * lays the weights out for the form it calls.  Partial-row layout as gsd_conv3x3, its own row count. */
+ * lays the weights out for the form it calls.  Partial-row layout as gsd_conv3x3, its own row count.
+ * A plan that folds images into tile rows (small H * W, N > 1; GSD_W43_FOLD=0 switches folding off) carries n * n_stride in
+ * 32-bit lane offsets: with N * n_stride >= 2^31 floats for any source or destination the call returns GSD_ERR_UNSUPPORTED
+ * ("batch too large for row folding") and launches nothing.  It does not fall back to the unfolded plan: gsd_conv3x3_w43_partial_rows
+ * depends on the shape alone and told the caller the folded row count. */
 int gsd_conv3x3_algo(int N, int H, int W, int Cin, int Cout);
 int gsd_conv3x3_w43_partial_rows(int N, int H, int W, int Cout);
 int64_t gsd_conv3x3_w43_mfma_count(int N, int H, int W, int Cin, int Cout);
@@ -188,7 +213,9 @@ int gsd_conv3x3_w43_dgrad_bnrelu_ws(const gsd_src* src, const float* wt, int Cin
  * K slabs (the _ws entries, as gsd_conv3x3_w43_ws): with scratch lent by the caller a launch whose tile grid leaves most of the
  * chip idle is cut along the input channels, the slabs summed in a fixed order by a second kernel that also runs the epilogue
  * (run-to-run bitwise; not bit-equal to the unsplit launch).  gsd_conv3x3_w2d_workspace: the floats such a launch wants (0: it runs
- * unsplit); any capacity is safe -- the launcher shrinks the slab count to what fits. */
+ * unsplit); any capacity is safe -- the launcher shrinks the slab count to what fits.
+ * Planes: every source plane H * w_stride + 4 < 2^30 floats and every destination plane < 2^31 floats, else GSD_ERR_UNSUPPORTED;
+ * planes and images may lie any distance apart. */
 int gsd_conv3x3_w2d_supported(int Cin, int C0);
 int gsd_conv3x3_prefers_w2d(int N, int H, int W, int Cin, int Cout, int train);   /* 1: run this Winograd launch in the 2-D form */
 double gsd_conv3x3_w2d_estimate_us(int N, int H, int W, int Cin, int Cout);          /* the planner's run-time models */
@@ -285,7 +312,9 @@ int gsd_conv3x3_dgrad_bn(const float* dz, const float* raw, const float* scale, 
                          const float* invstd, const float* c1, const float* c2, const float* w,
                          int Cin, int Cout, float* dx, int N, int H, int W, void* stream);
 /* dW and db of ConvTranspose2d(k2,s2): x (h,w) with deferred BN, dy (2h,2w) plain;
- * dW in the reference's (Ci,Co,2,2) layout. */
+ * dW in the reference's (Ci,Co,2,2) layout.  x and dy may have any n_stride / c_stride (64-bit; 8-byte aligned, even, for dy) as
+ * long as dbias == NULL: the bias gradient sums dy as ONE dense (N,Cout,2H,2W) array, and a call that asks for it with a
+ * dy that is not dense is refused (GSD_ERR_UNSUPPORTED, "bias gradient needs a contiguous dy") before anything is launched. */
 int64_t gsd_convT2x2_wgrad_workspace(int N, int H, int W, int Cin, int Cout);
 int gsd_convT2x2_wgrad(const gsd_src* x, const gsd_src* dy, int Cin, int Cout,
                        float* dw, float* dbias, float* workspace, int64_t workspace_elems,

@@ -33,6 +33,10 @@ statistics rows sum the whole raw output whether a destination crops it or not (
 second (cropped) destination's sums are the ConvT bias gradient: the direct dX cases pass no partials, as the engine does.
 
 GSD_FP64_REPORT_TILES=<path>: write the worst ratio per family and per case there as JSON.
+
+The bodies of the tests are functions (conv_case, fused_case, wgrad_case, wgrad_bn_case, convT_case) and the allocators (source,
+Out, Scratch) take a placement: tests/test_gpu_far_strides_fp64.py runs the same launches and checks with every strided operand
+carved from an arena in which images and planes lie gigabytes apart (tests/far_layouts.py).
 """
 import ctypes as C
 import json
@@ -44,6 +48,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import far_layouts as FL
 import fp64_ref as R
 import tile_cases as T
 from conftest import rel_l1
@@ -114,14 +119,19 @@ def vec(t):
 
 
 # ------------------------------------------------------------------------------------------------------------------ buffers
-def source(g, shape, pitch=None, front=GUARD, positive=False):
+def source(g, shape, pitch=None, front=GUARD, positive=False, place=None):
     """A random (n, c, h, w) source tensor with row pitch `pitch` (pad columns 0) between NaN floats: `front` in front (8: the
     tensor starts 16-byte aligned, 5: 4 bytes off) and GUARD behind.  Whatever a kernel reads outside the tensor and its pad
-    columns and lets into a result shows as a NaN."""
+    columns and lets into a result shows as a NaN.
+    place: a far_layouts.Placement -- the tensor is carved from its arena instead (the same values, the same alignment class,
+    the layout's strides; the arena's fill is the NaN around it)."""
     n, c, h, w = shape
     p = pitch or w
-    flat = torch.full((front + n * c * h * p + GUARD,), NAN, device="cuda")
-    body = flat[front:front + n * c * h * p].view(n, c, h, p)
+    if place is not None:
+        body = place.view(n, c, h, p, misalign=front % 4)
+    else:
+        flat = torch.full((front + n * c * h * p + GUARD,), NAN, device="cuda")
+        body = flat[front:front + n * c * h * p].view(n, c, h, p)
     body.zero_()
     t = body[..., :w]
     t.copy_(torch.rand(shape, generator=g, device="cuda") if positive else torch.randn(shape, generator=g, device="cuda"))
@@ -132,12 +142,19 @@ class Out:
     """An (n, ct, h, w) destination with row pitch `pitch` inside a buffer of sentinels; the launch owns columns < w of channels
     [c_off, c_off + c_len), NaN-filled before the launch.  check(): everything else still holds the sentinel."""
 
-    def __init__(self, shape, pitch=None, c_off=0, c_len=None, fill=NAN):
+    def __init__(self, shape, pitch=None, c_off=0, c_len=None, fill=NAN, place=None):
         n, ct, h, w = shape
         p = pitch or w
+        self.c_off, self.c_len = c_off, ct - c_off if c_len is None else c_len
+        self.place, self.w = place, w
+        if place is not None:       # carved from a far_layouts arena: its fill pattern is the sentinel
+            self.full = place.view(n, ct, h, p)[..., :w]
+            self.rec = place.recs[-1]
+            self.t = self.full[:, c_off:c_off + self.c_len]
+            self.t.fill_(fill)
+            return
         self.flat = torch.full((GUARD + n * ct * h * p + GUARD,), SENT, device="cuda")
         self.full = self.flat[GUARD:GUARD + n * ct * h * p].view(n, ct, h, p)[..., :w]
-        self.c_off, self.c_len = c_off, ct - c_off if c_len is None else c_len
         self.t = self.full[:, c_off:c_off + self.c_len]
         self.t.fill_(fill)
         self.owned = torch.zeros_like(self.flat, dtype=torch.bool)
@@ -147,6 +164,11 @@ class Out:
         return gsd.make_dst(self.full, c_off=self.c_off, c_len=self.c_len, off=off)
 
     def check(self, what):
+        if self.place is not None:  # pad columns and neighbouring channels here; everything else by the arena's scan
+            bad = self.place.int_view(self.rec) != FL.FILL_I32
+            bad[:, self.c_off:self.c_off + self.c_len, :, :self.w] = False
+            assert not bool(bad.any()), f"{what}: {int(bad.sum())} words of the destination's pad columns / other channels were written"
+            return
         bad = (self.flat != SENT) & ~self.owned
         assert not bool(bad.any()), f"{what}: {int(bad.sum())} floats outside the destination were written, first at flat index " \
                                     f"{int(bad.nonzero()[0, 0])} of {self.flat.numel()} (guard {GUARD})"
@@ -155,15 +177,24 @@ class Out:
 class Scratch:
     """`need` floats the launch may use (filled with `fill`) and 64 sentinels behind them."""
 
-    def __init__(self, need, fill=0.0):
+    def __init__(self, need, fill=0.0, place=None):
         self.need = int(need)
-        self.flat = torch.full((max(self.need, 1) + 64,), SENT, device="cuda")
+        self.place = place
+        if place is not None:
+            self.flat = place.view(1, 1, 1, max(self.need, 1) + 64).view(-1)
+            self.rec = place.recs[-1]
+        else:
+            self.flat = torch.full((max(self.need, 1) + 64,), SENT, device="cuda")
         self.flat[:self.need] = fill
 
     def ptr(self):
         return self.flat.data_ptr()
 
     def check(self, what):
+        if self.place is not None:
+            behind = self.place.int_view(self.rec).view(-1)[self.need:]
+            assert bool((behind == FL.FILL_I32).all()), f"{what}: written behind its {self.need} floats"
+            return
         assert bool((self.flat[self.need:] == SENT).all()), f"{what}: written behind its {self.need} floats"
 
 
@@ -171,22 +202,16 @@ class Scratch:
 MODES = {"direct": (0, 1), "w43": (4, 5), "w2d": (8, 9)}
 
 
-def second_segment(form, h, w):
-    """(off_h, off_w, H, W) of the second source segment: smaller than the grid, as F.pad of an up-sampled tensor leaves it."""
-    if form == "two11":
-        oh, ow = (1 if h >= 3 else 0), (1 if w >= 3 else 0)
-        return oh, ow, h - oh - (1 if h >= 4 else 0), w - ow - (1 if w >= 4 else 0)
-    ow = 4 if w >= 6 else 0
-    return 0, ow, (h - 1 if h > 1 else h), (w - ow - 1 if w - ow > 1 else w - ow)
+second_segment = T.second_segment
 
 
 class ConvOperands:
     """Sources of a forward case in its operand form (tile_cases.py), the fp64 activation they stand for, and the dX operands
     that mirror them: dy in the same alignment class, one destination per source segment with the segment's offsets."""
 
-    def __init__(self, gsd, c, g):
+    def __init__(self, gsd, c, g, place=None):
         n, h, w, c0, c1 = c.n, c.h, c.w, c.c0, c.c1
-        self.c, self.gsd = c, gsd
+        self.c, self.gsd, self.place = c, gsd, place
         form = c.form
         self.bn = form in ("slack_bn", "two04")
         self.sc = uniform(g, 0.5, 1.5, c0) if self.bn else None
@@ -194,14 +219,14 @@ class ConvOperands:
         self.aligned = form in ("x4", "slice")
         self.slack = 0 if form in ("x4", "slice", "dword") else gsd.SLACK
         ct, self.c_off = (c0 + 5, 3) if form == "slice" else (c0, 0)
-        self.raw0 = source(g, (n, ct, h, w), pitch=_r4(w) if self.aligned else None, front=5 if form == "dword" else GUARD)
+        self.raw0 = source(g, (n, ct, h, w), pitch=_r4(w) if self.aligned else None, front=5 if form == "dword" else GUARD, place=place)
         self.segs = [gsd.make_src(self.raw0, self.sc, self.sh, relu=self.bn, c_off=self.c_off, c_len=c0, slack=self.slack)]
         r0 = self.raw0[:, self.c_off:self.c_off + c0]
         a = R.deferred_act(r0, self.sc, self.sh) if self.bn else r0.double()
         self.geom = [(0, 0, h, w)]
         if c1:
             oh, ow, uh, uw = second_segment(form, h, w)
-            self.up = source(g, (n, c1, uh, uw))
+            self.up = source(g, (n, c1, uh, uw), place=place)
             self.segs.append(gsd.make_src(self.up, off=(oh, ow), slack=self.slack))
             a = torch.cat([a, F.pad(self.up.double(), [ow, w - uw - ow, oh, h - uh - oh])], 1)
             self.geom.append((oh, ow, uh, uw))
@@ -210,7 +235,8 @@ class ConvOperands:
 
     def dy(self, g, co):
         c = self.c
-        t = source(g, (c.n, co, c.h, c.w), pitch=_r4(c.w) if self.aligned else None, front=5 if c.form == "dword" else GUARD)
+        t = source(g, (c.n, co, c.h, c.w), pitch=_r4(c.w) if self.aligned else None, front=5 if c.form == "dword" else GUARD,
+                   place=self.place)
         return t, self.gsd.make_src(t, slack=self.slack)
 
     def dx_outs(self):
@@ -218,7 +244,8 @@ class ConvOperands:
         outs = []
         for (oh, ow, uh, uw), ch in zip(self.geom, (c.c0, c.c1)):
             pitch = _r4(uw) if self.aligned else uw + 1
-            outs.append(Out((c.n, ch + 5, uh, uw), pitch, 3, ch) if c.form == "slice" else Out((c.n, ch, uh, uw), pitch))
+            outs.append(Out((c.n, ch + 5, uh, uw), pitch, 3, ch, place=self.place) if c.form == "slice"
+                        else Out((c.n, ch, uh, uw), pitch, place=self.place))
         return outs
 
 
@@ -252,7 +279,7 @@ def expected_halo_form(fam, plan, segs, plain):
     return int(x4), int(fast)
 
 
-def launch_conv(gsd, fam, srcs, nsrc, wl, cin, cout, dsts, part, n, h, w, split):
+def launch_conv(gsd, fam, srcs, nsrc, wl, cin, cout, dsts, part, n, h, w, split, place=None):
     """One forward / dX launch: the K-slab entry point with the scratch the library asks for when the case forces a split.
     Returns the scratch (or None)."""
     L, st = gsd.lib, gsd.stream_ptr()
@@ -266,7 +293,7 @@ def launch_conv(gsd, fam, srcs, nsrc, wl, cin, cout, dsts, part, n, h, w, split)
         return None
     need = getattr(L, f"gsd_conv3x3_{fam}_workspace")(n, h, w, cin, cout)
     assert need > 0, "a forced slab count applies wherever the shape admits it"
-    ws = Scratch(need, NAN)
+    ws = Scratch(need, NAN, place=place)
     gsd.check(getattr(L, f"gsd_conv3x3_{fam}_ws")(srcs, nsrc, wl.data_ptr(), cin, cout, darr, len(dsts), part, ws.ptr(), need,
                                                    n, h, w, st), f"gsd_conv3x3_{fam}_ws")
     return ws
@@ -288,7 +315,15 @@ ALL_CONV = T.CONV_CASES + T.SPLIT_CASES
 
 @pytest.mark.parametrize("case", ALL_CONV, ids=[T.case_id(c) for c in ALL_CONV])
 def test_conv3x3_forward_and_dx_tile_form(gsd, monkeypatch, capfd, case):
+    conv_case(gsd, monkeypatch, capfd, case)
+
+
+def conv_case(gsd, monkeypatch, capfd, case, place=None, ns="tiles"):
+    """One forward + statistics and one dX launch of `case`, every check of this module on them.  place: carve every strided
+    operand, the partials and the K-slab scratch from a far_layouts arena; ns: the prefix of the keys in fp64_ref.RATIOS.
+    Returns what the launches stored (compact copies) and the launch line, for a caller that compares two placements."""
     c = case
+    res = {}
     fam, n, h, w, co = c.fam, c.n, c.h, c.w, c.co
     ci = c.c0 + c.c1
     for k, v in T.env_of(c).items():
@@ -299,7 +334,7 @@ def test_conv3x3_forward_and_dx_tile_form(gsd, monkeypatch, capfd, case):
     tag = T.case_id(c)
     tau = TAUS[fam]
     assert tau <= R.ceiling(max(ci, co))
-    op = ConvOperands(gsd, c, g)
+    op = ConvOperands(gsd, c, g, place)
     wd = randn(g, co, ci, 3, 3, scale=1.0 / (9 * ci) ** 0.5)
     w64 = wd.double()
     plan = T.conv_plan(fam, n, h, w, co, T.env_of(c))
@@ -311,14 +346,16 @@ def test_conv3x3_forward_and_dx_tile_form(gsd, monkeypatch, capfd, case):
     # ---- forward + statistics
     rows = rows_fn(n, h, w, co)
     assert rows == T.conv_partial_rows(fam, n, h, w, co, T.env_of(c))
-    y = Out((n, co + 5, h, w), _r4(w), 3, co) if c.form == "slice" else Out((n, co, h, w), _r4(w) if op.aligned else w + 1)
-    part = Scratch(rows * 2 * _r64(co))
+    y = Out((n, co + 5, h, w), _r4(w), 3, co, place=place) if c.form == "slice" \
+        else Out((n, co, h, w), _r4(w) if op.aligned else w + 1, place=place)
+    part = Scratch(rows * 2 * _r64(co), place=place)
     capfd.readouterr()
     ws = launch_conv(gsd, fam, op.src, len(op.segs), layout(gsd, MODES[fam][0], wd, co, ci), ci, co, [y.dst(gsd)], part.ptr(),
-                     n, h, w, split)
+                     n, h, w, split, place)
     torch.cuda.synchronize()
     if fam != "direct":
         line, _ = trace_line(capfd, fam)
+        res["line"] = line
         assert field(line, "tile") == f"{plan.TH}x{plan.TW}", line
         assert int(field(line, "plain")) == int(not op.bn), line
         assert int(field(line, "slabs")) == (int(dict(c.env)[f"GSD_{fam.upper()}_SPLIT"]) if split else 1), line
@@ -328,12 +365,13 @@ def test_conv3x3_forward_and_dx_tile_form(gsd, monkeypatch, capfd, case):
         if fam == "w43":
             assert int(field(line, "fold")) == plan.fold, line
     ref, cond = R.conv3x3_fwd(op.act, w64)
-    R.check_bound(y.t, ref, cond, tau, f"{tag} forward", image=n - 1, key=f"tiles:{fam}:{tag}")
+    R.check_bound(y.t, ref, cond, tau, f"{tag} forward", image=n - 1, key=f"{ns}:{fam}:{tag}")
+    res["y"], res["part"] = y.t.clone(), part.flat[:part.need].clone()
     y.check(f"{tag} forward")
     part.check(f"{tag} forward partials")
     if ws is not None:
         ws.check(f"{tag} forward K-slab scratch")
-    check_stats(gsd, part, rows, co, [(0, y.t)], [(0, cond)], f"{tag} forward", f"tiles:stats:{tag}")
+    check_stats(gsd, part, rows, co, [(0, y.t)], [(0, cond)], f"{tag} forward", f"{ns}:stats:{tag}")
     forward_mutation_rejected(op.act[-1:], w64, y.t[n - 1:n], ref[-1:], cond[-1:], tau, f"{tag} forward")
 
     # ---- dX: dy in the same alignment class, one (cropped) destination per source segment
@@ -347,26 +385,31 @@ def test_conv3x3_forward_and_dx_tile_form(gsd, monkeypatch, capfd, case):
     rows_d = rows_fn(n, h, w, ci)
     # statistics of the two (cropped) destinations, as the engine takes the ConvT bias gradient from them -- of the Winograd forms
     # only: the direct form sums the whole raw output, cropped or not (include/gsd.h), and the engine never asks it
-    part_d = Scratch(rows_d * 2 * _r64(ci)) if len(outs) == 2 and fam != "direct" else None
+    part_d = Scratch(rows_d * 2 * _r64(ci), place=place) if len(outs) == 2 and fam != "direct" else None
     dsts = [o.dst(gsd, off=(oh, ow)) for o, (oh, ow, _, _) in zip(outs, op.geom)]
     ws = launch_conv(gsd, fam, gsd.src_array([sdy]), 1, layout(gsd, MODES[fam][1], wd, kd, ci), kd, ci, dsts,
-                     part_d.ptr() if part_d else None, n, h, w, split)
+                     part_d.ptr() if part_d else None, n, h, w, split, place)
     torch.cuda.synchronize()
+    if fam != "direct":
+        res["line_dx"] = trace_line(capfd, fam)[0]
     ref, cond = R.conv3x3_dx(dy.double(), w64)
     stored, conds, lo = [], [], 0
     for o, (oh, ow, uh, uw) in zip(outs, op.geom):
         ch = o.t.shape[1]
         r_, c_ = ref[:, lo:lo + ch, oh:oh + uh, ow:ow + uw], cond[:, lo:lo + ch, oh:oh + uh, ow:ow + uw]
-        R.check_bound(o.t, r_, c_, tau, f"{tag} dX segment at ({oh},{ow})", image=n - 1, key=f"tiles:{fam}:{tag}")
+        R.check_bound(o.t, r_, c_, tau, f"{tag} dX segment at ({oh},{ow})", image=n - 1, key=f"{ns}:{fam}:{tag}")
+        res[f"dx{len(stored)}"] = o.t.clone()
         o.check(f"{tag} dX segment at ({oh},{ow})")
         stored.append((lo, o.t))
         conds.append((lo, c_))
         lo += ch
     if part_d is not None:
         part_d.check(f"{tag} dX partials")
-        check_stats(gsd, part_d, rows_d, ci, stored, conds, f"{tag} dX", f"tiles:stats:{tag}")
+        check_stats(gsd, part_d, rows_d, ci, stored, conds, f"{tag} dX", f"{ns}:stats:{tag}")
+        res["part_d"] = part_d.flat[:part_d.need].clone()
     if ws is not None:
         ws.check(f"{tag} dX K-slab scratch")
+    return res
 
 
 @pytest.mark.parametrize("c0,c1", [(5, 0), (6, 5), (8, 6)])
@@ -394,6 +437,12 @@ def test_w2d_refuses_channel_counts_off_a_multiple_of_4(gsd, c0, c1):
 def test_fused_dx_epilogue_tile_form(gsd, monkeypatch, case):
     """gsd_conv3x3[_w43|_w2d]_dgrad_bnrelu[_ws]: dz = dX * [fmaf(raw, scale, shift) > 0] against the exact mask, and both sums
     (sum dz, sum dz * xhat) of the values stored."""
+    fused_case(gsd, monkeypatch, case)
+
+
+def fused_case(gsd, monkeypatch, case, place=None, ns="tiles"):
+    """The launch and checks of test_fused_dx_epilogue_tile_form; place / ns / the return value as conv_case (raw shares dz's
+    strides, so it shares its placement)."""
     c = case
     fam, n, h, w, co, ci = c.fam, c.n, c.h, c.w, c.co, c.ci
     for k, v in T.env_of(c).items():
@@ -404,15 +453,15 @@ def test_fused_dx_epilogue_tile_form(gsd, monkeypatch, case):
     tag = f"fused-{fam}-{n}x{h}x{w}-k{co}-m{ci}" + ("-split" if split else "")
     tau = TAUS[fam]
     pitched = fam != "direct"          # the direct form takes row-contiguous sources only
-    dy = source(g, (n, co, h, w), pitch=_r4(w) if pitched else None)
-    raw = source(g, (n, ci, h, w))
+    dy = source(g, (n, co, h, w), pitch=_r4(w) if pitched else None, place=place)
+    raw = source(g, (n, ci, h, w), place=place)
     sc, sh = uniform(g, 0.5, 1.5, ci), randn(g, ci, scale=0.3)
     mean, invstd = randn(g, ci, scale=0.3), uniform(g, 0.5, 2.0, ci)
     wd = randn(g, co, ci, 3, 3, scale=1.0 / (9 * co) ** 0.5)
     rows_fn = {"direct": L.gsd_conv3x3_partial_rows, "w43": L.gsd_conv3x3_w43_partial_rows, "w2d": L.gsd_conv3x3_w2d_partial_rows}[fam]
     rows = rows_fn(n, h, w, ci)
-    part = Scratch(rows * 2 * _r64(ci))
-    dz = Out((n, ci, h, w))
+    part = Scratch(rows * 2 * _r64(ci), place=place)
+    dz = Out((n, ci, h, w), place=place)
     s, d = gsd.make_src(dy), dz.dst(gsd)
     wl = layout(gsd, MODES[fam][1], wd, co, ci)
     name = "gsd_conv3x3_dgrad_bnrelu" if fam == "direct" else f"gsd_conv3x3_{fam}_dgrad_bnrelu"
@@ -422,7 +471,7 @@ def test_fused_dx_epilogue_tile_form(gsd, monkeypatch, case):
     if split:
         need = getattr(L, f"gsd_conv3x3_{fam}_workspace")(n, h, w, co, ci)
         assert need > 0
-        ws = Scratch(need, NAN)
+        ws = Scratch(need, NAN, place=place)
         gsd.check(getattr(L, name + "_ws")(*args, ws.ptr(), need, n, h, w, st), name + "_ws")
     else:
         gsd.check(getattr(L, name)(*args, n, h, w, st), name)
@@ -430,7 +479,8 @@ def test_fused_dx_epilogue_tile_form(gsd, monkeypatch, case):
     ref, cond = R.conv3x3_dx(dy.double(), wd.double())
     m = R.bnrelu_mask(raw, sc, sh)
     ref, cond = ref * m, cond * m
-    R.check_bound(dz.t, ref, cond, tau, f"{tag} dz", image=n - 1, key=f"tiles:{fam}:{tag}")
+    R.check_bound(dz.t, ref, cond, tau, f"{tag} dz", image=n - 1, key=f"{ns}:{fam}:{tag}")
+    res = {"dz": dz.t.clone(), "part": part.flat[:part.need].clone()}
     assert bool((dz.t[~m] == 0).all()), "dz is exactly 0 where the mask is off"
     dz.check(f"{tag} dz")
     part.check(f"{tag} partials")
@@ -439,9 +489,9 @@ def test_fused_dx_epilogue_tile_form(gsd, monkeypatch, case):
     q1, q2 = sums(gsd, part.flat, rows, _r64(ci), ci)
     xhat = (raw.double() - vec(mean)) * vec(invstd)
     z64 = dz.t.double()
-    R.check_sums(q1, z64.sum((0, 2, 3)), cond.sum((0, 2, 3)), R.TAU_STATS, f"{tag} sum dz", key=f"tiles:stats:{tag}")
+    R.check_sums(q1, z64.sum((0, 2, 3)), cond.sum((0, 2, 3)), R.TAU_STATS, f"{tag} sum dz", key=f"{ns}:stats:{tag}")
     R.check_sums(q2, (z64 * xhat).sum((0, 2, 3)), (cond * xhat.abs()).sum((0, 2, 3)), R.TAU_STATS, f"{tag} sum dz*xhat",
-                 key=f"tiles:stats:{tag}")
+                 key=f"{ns}:stats:{tag}")
     # one product removed from the corner pixel of the last image (where the mask lets it through)
     if bool(m[n - 1, 0, h - 1, w - 1]):
         win = F.pad(dy[n - 1:n].double(), [1, 1, 1, 1])[0, :, h - 1:h + 2, w - 1:w + 2]
@@ -450,6 +500,7 @@ def test_fused_dx_epilogue_tile_form(gsd, monkeypatch, case):
         got = dz.t[n - 1:n].double().clone()
         got[0, 0, h - 1, w - 1] -= p
         rejects(got.float(), ref[-1:], cond[-1:], tau, f"{tag}: largest product removed")
+    return res
 
 
 # --------------------------------------------------------------------------------------------------------------------- dW
@@ -460,7 +511,15 @@ def _wg_id(c):
 
 @pytest.mark.parametrize("case", T.WG_CASES, ids=[_wg_id(c) for c in T.WG_CASES])
 def test_conv3x3_wgrad_stage_shapes(gsd, monkeypatch, capfd, case):
+    wgrad_case(gsd, monkeypatch, capfd, case)
+
+
+def wgrad_case(gsd, monkeypatch, capfd, case, place=None, ns="tiles", form=None):
+    """The launch and checks of test_conv3x3_wgrad_stage_shapes; place / ns / the return value as conv_case (dW itself and the
+    workspace are dense and stay outside the arena).  form: the form the library must report under this placement when it is
+    not the case's own (a documented fall-back)."""
     c = case
+    form = c.form if form is None else form
     n, h, w, c0, c1, co = c.n, c.h, c.w, c.c0, c.c1, c.co
     ci = c0 + c1
     for k, v in T.env_of(c).items():
@@ -469,18 +528,18 @@ def test_conv3x3_wgrad_stage_shapes(gsd, monkeypatch, capfd, case):
     g = gen(n, h, w, ci, co, c.form, c.slack)
     tag = _wg_id(c)
     sc, sh = (uniform(g, 0.5, 1.5, c0), randn(g, c0, scale=0.3)) if c.bn else (None, None)
-    raw0 = source(g, (n, c0, h, w))
+    raw0 = source(g, (n, c0, h, w), place=place)
     segs = [gsd.make_src(raw0, sc, sh, relu=c.bn, slack=c.slack)]
     act = R.deferred_act(raw0, sc, sh) if c.bn else raw0.double()
     if c1:
         oh, ow, uh, uw = second_segment("two11", h, w)
-        up = source(g, (n, c1, uh, uw))
+        up = source(g, (n, c1, uh, uw), place=place)
         segs.append(gsd.make_src(up, off=(oh, ow), slack=c.slack))
         act = torch.cat([act, F.pad(up.double(), [ow, w - uw - ow, oh, h - uh - oh])], 1)
-    dy = source(g, (n, co, h, w), pitch=_r4(w) if c.pitched else None)
+    dy = source(g, (n, co, h, w), pitch=_r4(w) if c.pitched else None, place=place)
     sdy = gsd.make_src(dy)
     src = gsd.src_array(segs)
-    assert L.gsd_conv3x3_wgrad_form(src, len(segs), C.byref(sdy), ci, co, n, h, w) == c.form
+    assert L.gsd_conv3x3_wgrad_form(src, len(segs), C.byref(sdy), ci, co, n, h, w) == form
     need = L.gsd_conv3x3_wgrad_workspace(n, h, w, ci, co)
     assert need == T.wgrad_workspace(n, h, w, ci, co, T.env_of(c))
     ws = Scratch(need, NAN)
@@ -488,7 +547,9 @@ def test_conv3x3_wgrad_stage_shapes(gsd, monkeypatch, capfd, case):
     capfd.readouterr()
     gsd.check(L.gsd_conv3x3_wgrad(src, len(segs), C.byref(sdy), ci, co, dw.t.data_ptr(), ws.ptr(), need, n, h, w, st), "gsd_conv3x3_wgrad")
     torch.cuda.synchronize()
-    if c.form == 1:
+    if form == 0:                    # the direct-tap form prints no launch line
+        line = "direct"
+    elif form == 1:
         p = T.plan_wg43(n, h, w, co, ci, T.env_of(c))
         line, _ = trace_line(capfd, "wg43")
         assert field(line, "tile") == f"{p.TH}x{p.TW}" and int(field(line, "BM")) == p.BM and int(field(line, "BN")) == p.BN, line
@@ -502,23 +563,30 @@ def test_conv3x3_wgrad_stage_shapes(gsd, monkeypatch, capfd, case):
         p = T.plan_wg2d(n, h, w, co, ci, T.env_of(c))
         line, _ = trace_line(capfd, "wg2d")
         assert field(line, "kstep") == f"{p.KY}x{p.KX}" and int(field(line, "BM")) == p.BM and int(field(line, "BN")) == p.BN, line
-    assert int(field(line, "plain")) == int(not c.bn), line
+    assert form == 0 or int(field(line, "plain")) == int(not c.bn), line
     ref, cond = R.conv3x3_dw(act, dy.double())
-    R.check_bound(dw.t, ref, cond, R.TAU_DW, f"{tag} dW", key=f"tiles:dw:{tag}", weights=True)
+    R.check_bound(dw.t, ref, cond, R.TAU_DW, f"{tag} dW", key=f"{ns}:dw:{tag}", weights=True)
     dw.check(f"{tag} dW")
     ws.check(f"{tag} dW workspace")
     dw_mutation_rejected(act[n - 1:n], dy[n - 1:n].double(), dw.t, ref, cond, R.TAU_DW, f"{tag} dW")
+    return {"dw": dw.t.clone(), "line": line}
 
 
 @pytest.mark.parametrize("n,h,w", T.WGRAD_BN_SHAPES, ids=[f"{n}x{h}x{w}" for n, h, w in T.WGRAD_BN_SHAPES])
 def test_first_layer_wgrad_bn_small_shapes(gsd, n, h, w):
     """gsd_conv3x3_wgrad_bn (3 -> 64): forms d_raw = scale * (dz - c1 - (raw - mean) * invstd * c2) itself."""
+    wgrad_bn_case(gsd, n, h, w)
+
+
+def wgrad_bn_case(gsd, n, h, w, place=None, ns="tiles"):
+    """The launch and checks of test_first_layer_wgrad_bn_small_shapes; place: the input image `a`, the entry point's only strided
+    operand (dz and raw are dense by contract)."""
     L, st = gsd.lib, gsd.stream_ptr()
     ci, co = 3, 64
     g = gen(n, h, w, 3)
     tag = f"wgrad_bn-{n}x{h}x{w}"
     assert L.gsd_conv3x3_wgrad_bn_supported(n, h, w, ci, co) == 1
-    x = source(g, (n, ci, h, w), positive=True)
+    x = source(g, (n, ci, h, w), positive=True, place=place)
     y, dz = source(g, (n, co, h, w)), source(g, (n, co, h, w))
     sc, mu = uniform(g, 0.5, 1.5, co), randn(g, co, scale=0.3)
     istd, k1, k2 = uniform(g, 0.5, 2.0, co), randn(g, co, scale=0.1), randn(g, co, scale=0.1)
@@ -533,10 +601,11 @@ def test_first_layer_wgrad_bn_small_shapes(gsd, n, h, w):
     d = vec(sc) * (dz.double() - vec(k1) - t)
     da = vec(sc) * (dz.double().abs() + vec(k1).abs() + t.abs())
     ref, cond = R.conv3x3_dw(x.double(), d, da)
-    R.check_bound(dw.t, ref, cond, R.TAU_DW, f"{tag} dW", key=f"tiles:dw:{tag}", weights=True)
+    R.check_bound(dw.t, ref, cond, R.TAU_DW, f"{tag} dW", key=f"{ns}:dw:{tag}", weights=True)
     dw.check(f"{tag} dW")
     ws.check(f"{tag} workspace")
     dw_mutation_rejected(x[n - 1:n].double(), d[n - 1:n], dw.t, ref, cond, R.TAU_DW, f"{tag} dW")
+    return {"dw": dw.t.clone()}
 
 
 # ------------------------------------------------------------------------------------------------------------------ ConvT
@@ -545,30 +614,38 @@ def test_convT_small_shapes(gsd, n, h, w, ci, co):
     """gsd_convT2x2 (H*W on and off a multiple of 4: with and without 16-byte pieces; 1 and 2 m-blocks), gsd_convT2x2_dgrad_as in
     weight layout mode 7 (odd W with the 2 floats of slack it asks for) and mode 3 (block <1,4> for Cin <= 64, <2,2> above),
     gsd_convT2x2_dgrad_bnrelu and gsd_convT2x2_wgrad."""
+    convT_case(gsd, n, h, w, ci, co)
+
+
+def convT_case(gsd, n, h, w, ci, co, place=None, ns="tiles"):
+    """The launches and checks of test_convT_small_shapes; place / ns / the return value as conv_case (dW, db and the workspace are
+    dense and stay outside the arena)."""
     L, st = gsd.lib, gsd.stream_ptr()
     g = gen(n, h, w, ci, co)
     tag = f"convT-{n}x{h}x{w}-k{ci}-m{co}"
-    key = f"tiles:convT:{tag}"
+    key = f"{ns}:convT:{tag}"
+    res = {}
     bn = ci != 36          # two cases from a deferred BatchNorm + ReLU source, two from a plain one
-    raw = source(g, (n, ci, h, w))
+    raw = source(g, (n, ci, h, w), place=place)
     sc, sh = (uniform(g, 0.5, 1.5, ci), randn(g, ci, scale=0.3)) if bn else (None, None)
     x64 = R.deferred_act(raw, sc, sh) if bn else raw.double()
     wd, bd = randn(g, ci, co, 2, 2, scale=1.0 / ci ** 0.5), randn(g, co)
     w64 = wd.double()
     s = gsd.make_src(raw, sc, sh, relu=bn)
-    y = Out((n, co, 2 * h, 2 * w))
+    y = Out((n, co, 2 * h, 2 * w), place=place)
     d = y.dst(gsd)
     gsd.check(L.gsd_convT2x2(C.byref(s), layout(gsd, 6, wd, co, ci).data_ptr(), bd.data_ptr(), ci, co, C.byref(d), n, h, w, st))
     torch.cuda.synchronize()
     ref, cond = R.convT_fwd(x64, w64, bd.double())
     R.check_bound(y.t, ref, cond, R.TAU_CONVT, f"{tag} forward", image=n - 1, key=key)
+    res["y"] = y.t.clone()
     y.check(f"{tag} forward")
     prods = w64[:, 0, 1, 1] * x64[n - 1, :, h - 1, w - 1]        # one product removed from the last pixel of the last image
     got = y.t[n - 1:n].double().clone()
     got[0, 0, 2 * h - 1, 2 * w - 1] -= prods[int(prods.abs().argmax())]
     rejects(got.float(), ref[-1:], cond[-1:], R.TAU_CONVT, f"{tag} forward: largest product removed")
 
-    dy = source(g, (n, co, 2 * h, 2 * w))
+    dy = source(g, (n, co, 2 * h, 2 * w), place=place)
     slack = 2 if w % 2 else 0
     sdy = gsd.make_src(dy, slack=slack)
     assert L.gsd_convT2x2_dgrad_layout(C.byref(sdy), ci, co, n, h, w) == 7
@@ -576,20 +653,21 @@ def test_convT_small_shapes(gsd, n, h, w, ci, co):
     assert L.gsd_convT2x2_dgrad_layout(C.byref(bare), ci, co, n, h, w) == (3 if w % 2 else 7)
     ref, cond = R.convT_dx(dy.double(), w64)
     for mode, sd in ((7, sdy), (3, bare)):
-        dx = Out((n, ci, h, w))
+        dx = Out((n, ci, h, w), place=place)
         dd = dx.dst(gsd)
         gsd.check(L.gsd_convT2x2_dgrad_as(mode, C.byref(sd), layout(gsd, mode, wd, co, ci).data_ptr(), ci, co, C.byref(dd), n, h, w, st),
                   f"dgrad mode {mode}")
         torch.cuda.synchronize()
         R.check_bound(dx.t, ref, cond, R.TAU_CONVT, f"{tag} dX (mode {mode})", image=n - 1, key=key)
+        res[f"dx{mode}"] = dx.t.clone()
         dx.check(f"{tag} dX (mode {mode})")
 
     rows = L.gsd_convT2x2_dgrad_bnrelu_partial_rows(C.byref(sdy), ci, co, n, h, w)
     assert rows == -(-n * h * (w + w % 2) // 128) * 2
     rs, rh = uniform(g, 0.5, 1.5, ci), randn(g, ci, scale=0.3)
     mean, invstd = randn(g, ci, scale=0.3), uniform(g, 0.5, 2.0, ci)
-    part = Scratch(rows * 2 * _r64(ci))
-    dz = Out((n, ci, h, w))
+    part = Scratch(rows * 2 * _r64(ci), place=place)
+    dz = Out((n, ci, h, w), place=place)
     dd = dz.dst(gsd)
     gsd.check(L.gsd_convT2x2_dgrad_bnrelu(C.byref(sdy), layout(gsd, 7, wd, co, ci).data_ptr(), ci, co, C.byref(dd), raw.data_ptr(),
                                           rs.data_ptr(), rh.data_ptr(), mean.data_ptr(), invstd.data_ptr(), part.ptr(), n, h, w, st))
@@ -597,23 +675,37 @@ def test_convT_small_shapes(gsd, n, h, w, ci, co):
     m = R.bnrelu_mask(raw, rs, rh)
     rm, cm = ref * m, cond * m
     R.check_bound(dz.t, rm, cm, R.TAU_CONVT, f"{tag} dX fused", image=n - 1, key=key)
+    res["dz"], res["part"] = dz.t.clone(), part.flat[:part.need].clone()
     dz.check(f"{tag} dX fused")
     part.check(f"{tag} dX fused partials")
     q1, q2 = sums(gsd, part.flat, rows, _r64(ci), ci)
     xhat = (raw.double() - vec(mean)) * vec(invstd)
     z64 = dz.t.double()
-    R.check_sums(q1, z64.sum((0, 2, 3)), cm.sum((0, 2, 3)), R.TAU_STATS, f"{tag} fused dX sum dz", key=f"tiles:stats:{tag}")
+    R.check_sums(q1, z64.sum((0, 2, 3)), cm.sum((0, 2, 3)), R.TAU_STATS, f"{tag} fused dX sum dz", key=f"{ns}:stats:{tag}")
     R.check_sums(q2, (z64 * xhat).sum((0, 2, 3)), (cm * xhat.abs()).sum((0, 2, 3)), R.TAU_STATS, f"{tag} fused dX sum dz*xhat",
-                 key=f"tiles:stats:{tag}")
+                 key=f"{ns}:stats:{tag}")
 
     need = L.gsd_convT2x2_wgrad_workspace(n, h, w, ci, co)
     ws = Scratch(need, NAN)
     dw, db = Out((ci, co, 2, 2)), Out((1, 1, 1, co))
-    gsd.check(L.gsd_convT2x2_wgrad(C.byref(s), C.byref(bare), ci, co, dw.t.data_ptr(), db.t.data_ptr(), ws.ptr(), need, n, h, w, st))
+    if place is not None:
+        # the bias gradient sums dy as one dense array: a strided dy is refused before anything is launched; dW alone takes it
+        rc = L.gsd_convT2x2_wgrad(C.byref(s), C.byref(bare), ci, co, dw.t.data_ptr(), db.t.data_ptr(), ws.ptr(), need, n, h, w, st)
+        torch.cuda.synchronize()
+        assert rc == gsd.GSD_ERR_UNSUPPORTED and b"bias gradient needs a contiguous dy" in L.gsd_last_error()
+        assert bool(torch.isnan(dw.t).all()) and bool(torch.isnan(db.t).all()) and bool(torch.isnan(ws.flat[:need]).all()), \
+            "a refused launch writes nothing"
+        gsd.check(L.gsd_convT2x2_wgrad(C.byref(s), C.byref(bare), ci, co, dw.t.data_ptr(), None, ws.ptr(), need, n, h, w, st))
+        db.t.copy_(dy.sum((0, 2, 3)).view(1, 1, 1, co))      # (torch's sum: not what is under test here)
+    else:
+        gsd.check(L.gsd_convT2x2_wgrad(C.byref(s), C.byref(bare), ci, co, dw.t.data_ptr(), db.t.data_ptr(), ws.ptr(), need, n, h, w, st))
     torch.cuda.synchronize()
     rw, cw, rb, cb = R.convT_dw(x64, dy.double())
     R.check_bound(dw.t, rw, cw, R.TAU_CONVT, f"{tag} dW", key=key, weights=True)
     R.check_bound(db.t.view(co), rb, cb, R.TAU_CONVT, f"{tag} db", key=key, weights=True)
+    res["dw"] = dw.t.clone()
+    if place is None:
+        res["db"] = db.t.clone()
     dw.check(f"{tag} dW")
     db.check(f"{tag} db")
     ws.check(f"{tag} dW workspace")
@@ -621,6 +713,7 @@ def test_convT_small_shapes(gsd, n, h, w, ci, co):
     got = dw.t.double().clone()
     got[:, :, 0, 0] -= rows_
     rejects(got.float(), rw, cw, R.TAU_CONVT, f"{tag} dW: one image row removed", weights=True)
+    return res
 
 
 # ------------------------------------------------------------------------------------------------------ the metric's blind spot

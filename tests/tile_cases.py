@@ -380,5 +380,14 @@ WGRAD_BN_SHAPES = [(2, 9, 37), (1, 5, 16), (3, 7, 50)]
 CONVT_CASES = [(2, 4, 5, 8, 32), (3, 5, 53, 36, 40), (2, 7, 9, 264, 32), (1, 3, 2, 36, 40)]
 
 
+def second_segment(form, h, w):
+    """(off_h, off_w, H, W) of the second source segment: smaller than the grid, as F.pad of an up-sampled tensor leaves it."""
+    if form == "two11":
+        oh, ow = (1 if h >= 3 else 0), (1 if w >= 3 else 0)
+        return oh, ow, h - oh - (1 if h >= 4 else 0), w - ow - (1 if w >= 4 else 0)
+    ow = 4 if w >= 6 else 0
+    return 0, ow, (h - 1 if h > 1 else h), (w - ow - 1 if w - ow > 1 else w - ow)
+
+
 def env_of(case) -> dict:
     return {k: str(v) for k, v in case.env}
