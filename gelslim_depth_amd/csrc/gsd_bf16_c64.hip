@@ -1,4 +1,5 @@
 // gsd_bf16_c64.hip -- conv3x3 64 -> 64 channels at full resolution with the weights RESIDENT in LDS (bf16 path).
+// Host side over gsd_bf16_host.h (the tile grid, the fused-BatchNorm-backward operands).
 //
 // The 64-channel 3x3 convolutions of the first level (unet.py:14 for `inc` and `up.3.conv`: K = M = 64 at 320 x 427, forward and
 // dX: four of a step's 34 conv3x3 launches) are where the DMA-filled kernel (gsd_bf16_conv.hip) is weakest -- 0.285 of the matrix
@@ -23,7 +24,7 @@
 // Same products in the same order through the same MFMA as gsd_bf16_conv3x3: outputs bit-identical.
 // LDS images as in gsd_bf16_inc.hip: activations [chunk][halo pixel q = r*66 + c][64 B], piece p at slot p ^ (2*((c>>2)&1))
 // (bank-conflict free for every tap shift); weights [tap][64 rows][128 B], piece p of row i at slot p ^ (i & 6).
-#include "gsd_bf16_common.h"
+#include "gsd_bf16_host.h"
 
 #include <type_traits>
 
@@ -315,23 +316,11 @@ __global__ __launch_bounds__(512) void conv64_bf16_kernel(const C64P P) {
   }
 }
 
-int c64_cu_count() {
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-    v = 256;
-  return v;
-}
-
-long c64_tiles(int N, int H, int W, int th) { return (long)N * ceil_div(H, th) * ceil_div(W, C_TW); }
-
+// one persistent block per CU, one partial row each
 template <int EP, int TH>
 int c64_launch(C64P& P, size_t lds, void* stream, const char* what) {
-  const long nt = c64_tiles(P.N, P.H, P.W, TH);
-  GSD_REQUIRE(nt < 2147483647L, GSD_ERR_UNSUPPORTED, "%s: too many tiles", what);
-  P.tiles_y = ceil_div(P.H, TH); P.tiles_x = ceil_div(P.W, C_TW);
-  P.ntiles = (int)nt;
-  const int cus = c64_cu_count();
-  const int grid = (int)(nt < cus ? nt : cus);
+  int grid;
+  if (int e = bf16_plan_tiles(what, P, TH, C_TW, gsd_cu_count(), &grid)) return e;
   return gsd_launch<conv64_bf16_kernel<EP, TH>>(what, dim3(grid), dim3(512), lds, (hipStream_t)stream, P);
 }
 
@@ -347,7 +336,6 @@ int c64_common(C64P& P, const gsd_nhwc* in, const void* wt, const gsd_nhwc* out,
   GSD_REQUIRE((long long)in->H * in->W * in->pitch < (1LL << 30), GSD_ERR_UNSUPPORTED, "gsd_bf16_conv3x3_c64: one input image exceeds 2 GiB");
   P.img_bytes = (unsigned)((long long)in->H * in->W * in->pitch * 2);
   P.out = (u16*)out->ptr; P.out_pitch = out->pitch; P.partials = partials;
-  P.bw_y = nullptr; P.bw_pitch = 0; P.bw_scale = P.bw_shift = P.bw_mean = P.bw_invstd = nullptr;
   P.N = in->N; P.H = in->H; P.W = in->W; P.Mpad = round_up(C_M, 128);
   return GSD_OK;
 }
@@ -358,23 +346,19 @@ extern "C" int gsd_bf16_conv3x3_c64_supported(int K, int M) { return (K == C_M &
 
 extern "C" int gsd_bf16_conv3x3_c64_partial_rows(int N, int H, int W) {
   if (N <= 0 || H <= 0 || W <= 0) return 0;
-  const long nt = c64_tiles(N, H, W, 8);
-  const int cus = c64_cu_count();
-  return (int)(nt < cus ? nt : cus);
+  Bf16Tiles t;
+  bf16_tile_grid(N, H, W, 8, C_TW, gsd_cu_count(), &t);
+  return t.grid;
 }
 
 extern "C" int gsd_bf16_conv3x3_c64(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, float* partials,
                                     const gsd_bf16_bnbwd* bw, void* stream) {
   C64P P;
   if (int e = c64_common(P, in, wt, out, partials, "gsd_bf16_conv3x3_c64")) return e;
+  if (bw != nullptr)
+    if (int e = bf16_check_bnbwd("gsd_bf16_conv3x3_c64", bw, partials, out->N, out->H, out->W, C_M)) return e;
+  bf16_fill_bnbwd(P, bw);
   if (bw == nullptr) return c64_launch<EP_STATS, 8>(P, C64Geo<8>::LDS_PLAIN, stream, "gsd_bf16_conv3x3_c64");
-  if (int e = gsd_check_nhwc(bw->y, "gsd_bf16_conv3x3_c64 bw.y")) return e;
-  GSD_REQUIRE(bw->scale && bw->shift && bw->mean && bw->invstd && partials, GSD_ERR_BAD_ARG,
-              "gsd_bf16_conv3x3_c64: fused BatchNorm backward needs coefficients and partials");
-  GSD_REQUIRE(bw->y->N == out->N && bw->y->H == out->H && bw->y->W == out->W && bw->y->C == C_M && (bw->y->pitch & 3) == 0,
-              GSD_ERR_BAD_ARG, "gsd_bf16_conv3x3_c64: bw.y must have out's geometry");
-  P.bw_y = (const u16*)bw->y->ptr; P.bw_pitch = bw->y->pitch;
-  P.bw_scale = bw->scale; P.bw_shift = bw->shift; P.bw_mean = bw->mean; P.bw_invstd = bw->invstd;
   return c64_launch<EP_BNBWD, 8>(P, C64Geo<8>::LDS_PLAIN, stream, "gsd_bf16_conv3x3_c64");
 }
 

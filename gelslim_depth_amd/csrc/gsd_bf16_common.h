@@ -1,4 +1,5 @@
-// gsd_bf16_common.h -- shared pieces of the bf16 mixed-precision path (BASELINE.json configs[4]).
+// gsd_bf16_common.h -- shared device-side pieces of the bf16 mixed-precision path (BASELINE.json configs[4]) and its NHWC tensor
+// descriptor; the host side of the convolution units is gsd_bf16_host.h.
 //
 // Layout: activations NHWC bf16 ("pixel-major": the C channels of one pixel are contiguous, `pitch` elements from one
 // pixel to the next, so a tensor may be a channel slice of a wider buffer -- that is how torch.cat([skip, up]) exists
@@ -119,11 +120,3 @@ static inline int gsd_check_nhwc(const gsd_nhwc* t, const char* what) {
               what);
   return 0;
 }
-
-// gsd_bf16_ctgemm.hip: the large-tile kernel behind gsd_bf16_conv_dense for the transposed convolutions' forward and dX
-bool gsd_ctgemm_shape(int N, int H, int W, int K, int M, int ntaps, int stride, int scatter_cs);
-bool gsd_ctgemm_operands(const gsd_nhwc* in, const gsd_nhwc* out, const gsd_bf16_bnbwd* bw, int ntaps, const int* ty, const int* tx, int H,
-                         int W);
-int gsd_ctgemm_partial_rows(int N, int H, int W, int M);
-int gsd_ctgemm_launch(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, int K, int M, int ntaps, const int* ty, const int* tx, int H,
-                      int W, int scatter_cs, int oy, int ox, const float* bias, float* partials, const gsd_bf16_bnbwd* bw, void* stream);

@@ -1,4 +1,5 @@
 // gsd_bf16_conv.hip -- forward-type convolutions of the bf16 path as implicit GEMM on v_mfma_f32_16x16x32_bf16.
+// Host side over gsd_bf16_host.h (grids, XCD flag, tile picker, fused-BatchNorm-backward operands).
 //
 //   out[pixel][m] = sum_taps sum_k  in[pixel moved by the tap][k] * Wt[tap][m][k]          (fp32 accumulation)
 //
@@ -23,7 +24,7 @@
 // Block = 4 waves; wave tile 64 (m) x 128 (pixels) = 4 x 8 MFMA tiles = 128 accumulator registers; block tile
 // 128 x 256 (WM=2, WN=2) or 64 x 512 (WM=1, WN=4): L2->LDS traffic per FLOP falls with the PIXEL extent of the tile
 // (weights are re-read per pixel tile), which is why the tile is wide in pixels.
-#include "gsd_bf16_common.h"
+#include "gsd_bf16_host.h"
 
 #include <type_traits>
 
@@ -525,53 +526,55 @@ Plan make_plan(int H, int W, int M) {
   p.wide = M <= 64;
   p.BM = p.wide ? 64 : 128;
   p.NPX = p.wide ? 512 : 256;
-  long best = -1;
-  const int force_tw = gsd_env_int("GSD_BF16_TW", 0);   // tuning: force the tile width (16, 32 or 64)
-  for (int tw = 16; tw <= 64; tw *= 2) {
-    if (force_tw && tw != force_tw) continue;
-    const int th = p.NPX / tw;
-    const long cost = (long)ceil_div(H, th) * ceil_div(W, tw);   // tiles; ties -> wider rows (longer DMA row segments)
-    if (best < 0 || cost <= best) {
-      best = cost;
-      p.TW = tw;
-      p.TH = th;
-    }
-  }
-  p.tiles_y = ceil_div(H, p.TH);
-  p.tiles_x = ceil_div(W, p.TW);
+  // ties -> wider rows (longer DMA row segments); GSD_BF16_TW (tuning) forces the tile width (16, 32 or 64)
+  bf16_pick_tile(p, H, W, p.NPX, 16, 64, true, gsd_env_int("GSD_BF16_TW", 0));
   p.Mpad = round_up(M, 128);
   p.mblocks = ceil_div(M, p.BM);
-  p.HC = p.TW + 2;
-  p.HP = (p.TH + 2) * (p.TW + 2);
   return p;
 }
 
-int cu_count() {
-  static int n = 0;   // benign race: every thread computes the same value
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    n = v;
-  }
-  return n;
-}
-
-// items = (pixel tile, m-block) pairs; one persistent block per CU (the LDS image allows one), a multiple of mblocks
-long launch_grid(long items, int mblocks) {
-  long grid = cu_count() / mblocks * mblocks;
-  if (grid < mblocks) grid = mblocks;
-  return grid > items ? items : grid;
-}
+// work items of a batch of N images: (pixel tile, m-block) pairs
+long plan_items(int N, const Plan& p) { return (long)N * p.tiles_y * p.tiles_x * p.mblocks; }
 
 template <int MODE, int WM, int WN, int BUF = 0>
 int launch(GConvP& P, long items, size_t lds, hipStream_t st, const char* what) {
   GSD_REQUIRE(items > 0 && items < 2147483647L, GSD_ERR_UNSUPPORTED, "%s: %ld work items out of range", what, items);
   P.nitems = (int)items;
-  const long grid = launch_grid(items, P.mblocks);
-  P.xcd = (gsd_env_int("GSD_BF16_XCD", 1) != 0 && grid % 8 == 0 && (grid / 8) % P.mblocks == 0) ? 1 : 0;
+  const long grid = bf16_mblock_grid(items, P.mblocks);
+  P.xcd = bf16_xcd_order(grid, P.mblocks);
   GSD_REQUIRE(grid > 0 && grid < 2147483647L, GSD_ERR_UNSUPPORTED, "%s: grid %ld out of range", what, grid);
   return gsd_launch<gconv_bf16_kernel<MODE, WM, WN, BUF>>(what, dim3((unsigned)grid), dim3(256), lds, st, P);
+}
+
+// K, M and the output pitch of the entry point `name`: whole 32-channel k-chunks of in, whole 16-row MFMA tiles, 8-byte stores
+int check_channels(const char* name, const gsd_nhwc* in, const gsd_nhwc* out, int K, int M) {
+  GSD_REQUIRE(K > 0 && K % 32 == 0 && in->C == K, GSD_ERR_UNSUPPORTED, "%s: K=%d must be a multiple of 32 and in->C", name, K);
+  GSD_REQUIRE(M > 0 && M % 16 == 0, GSD_ERR_UNSUPPORTED, "%s: M=%d must be a multiple of 16", name, M);
+  GSD_REQUIRE((out->pitch & 3) == 0, GSD_ERR_UNSUPPORTED, "%s: out pitch must be a multiple of 4", name);
+  return 0;
+}
+
+// The kernel arguments of a GEMM over the (N, H, W) pixel grid with the plan's tile: operands, taps and epilogue operands (bw:
+// already checked).  Left at 0 for the caller: MODE 0 its halo (HC, HP) and the BUF decision, MODE 1 the scatter and the bias.
+GConvP make_params(const Plan& pl, const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, int K, int M, int H, int W, int ntaps,
+                   int stride, const int* ty, const int* tx, float* partials, const gsd_bf16_bnbwd* bw, const float* ep_scale,
+                   const float* ep_shift) {
+  GConvP P;
+  P.in = (const u16*)in->ptr; P.in_pitch = in->pitch; P.Hin = in->H; P.Win = in->W;
+  P.wt = (const u16*)wt;
+  P.out = (u16*)out->ptr; P.out_pitch = out->pitch; P.Hob = out->H; P.Wob = out->W;
+  P.N = in->N; P.H = H; P.W = W;
+  P.K = K; P.M = M; P.Mpad = pl.Mpad; P.mblocks = pl.mblocks;
+  P.ntaps = ntaps; P.stride = stride;
+  for (int t = 0; t < 9; ++t) { P.ty[t] = t < ntaps ? ty[t] : 0; P.tx[t] = t < ntaps ? tx[t] : 0; }
+  P.TH = pl.TH; P.TW = pl.TW; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x; P.HC = 0; P.HP = 0;
+  P.buf = 0; P.img_bytes = P.wt_bytes = 0;
+  P.Cs = 0; P.oy = P.ox = 0;
+  P.bias = nullptr;
+  P.partials = partials;
+  P.ep_scale = ep_scale; P.ep_shift = ep_shift;
+  bf16_fill_bnbwd(P, bw);
+  return P;
 }
 
 }  // namespace
@@ -581,7 +584,7 @@ extern "C" int gsd_bf16_conv_mpad(int M) { return M > 0 ? round_up(M, 128) : 0; 
 extern "C" int gsd_bf16_conv_partial_rows(int N, int H, int W, int M) {
   if (N <= 0 || H <= 0 || W <= 0 || M <= 0) return 0;
   const Plan p = make_plan(H, W, M);
-  return (int)(launch_grid((long)N * p.tiles_y * p.tiles_x * p.mblocks, p.mblocks) / p.mblocks) * (p.wide ? 4 : 2);
+  return (int)(bf16_mblock_grid(plan_items(N, p), p.mblocks) / p.mblocks) * (p.wide ? 4 : 2);
 }
 
 static int conv3x3_impl(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, int K, int M, float* partials,
@@ -589,43 +592,21 @@ static int conv3x3_impl(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out,
   if (int e = gsd_check_nhwc(in, "gsd_bf16_conv3x3 in")) return e;
   if (int e = gsd_check_nhwc(out, "gsd_bf16_conv3x3 out")) return e;
   GSD_REQUIRE(wt != nullptr, GSD_ERR_BAD_ARG, "gsd_bf16_conv3x3: null weights");
-  GSD_REQUIRE(K > 0 && K % 32 == 0 && in->C == K, GSD_ERR_UNSUPPORTED, "gsd_bf16_conv3x3: K=%d must be a multiple of 32 and in->C",
-              K);
-  GSD_REQUIRE(M > 0 && M % 16 == 0 && out->C == M, GSD_ERR_UNSUPPORTED, "gsd_bf16_conv3x3: M=%d must be a multiple of 16 and out->C",
-              M);
+  if (int e = check_channels("gsd_bf16_conv3x3", in, out, K, M)) return e;
+  GSD_REQUIRE(out->C == M, GSD_ERR_UNSUPPORTED, "gsd_bf16_conv3x3: out->C=%d must be M=%d", out->C, M);
   GSD_REQUIRE(in->N == out->N && in->H == out->H && in->W == out->W, GSD_ERR_BAD_ARG, "gsd_bf16_conv3x3: in/out extents differ");
-  GSD_REQUIRE((out->pitch & 3) == 0, GSD_ERR_UNSUPPORTED, "gsd_bf16_conv3x3: out pitch must be a multiple of 4");
+  if (bw != nullptr)
+    if (int e = bf16_check_bnbwd("gsd_bf16_conv3x3", bw, partials, out->N, out->H, out->W, M)) return e;
   const Plan pl = make_plan(in->H, in->W, M);
-  GConvP P;
-  P.in = (const u16*)in->ptr; P.in_pitch = in->pitch; P.Hin = in->H; P.Win = in->W;
-  P.wt = (const u16*)wt;
-  P.out = (u16*)out->ptr; P.out_pitch = out->pitch; P.Hob = out->H; P.Wob = out->W;
-  P.N = in->N; P.H = in->H; P.W = in->W;
-  P.K = K; P.M = M; P.Mpad = pl.Mpad; P.mblocks = pl.mblocks;
-  P.ntaps = 9; P.stride = 1;
-  for (int t = 0; t < 9; ++t) { P.ty[t] = t / 3 - 1; P.tx[t] = t % 3 - 1; }
-  P.TH = pl.TH; P.TW = pl.TW; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x; P.HC = pl.HC; P.HP = pl.HP;
-  P.Cs = 0; P.oy = P.ox = 0;
-  {
-    const long long ib = (long long)in->H * in->W * in->pitch * 2, wb = (long long)9 * pl.Mpad * K * 2;
-    P.buf = (ib < (1LL << 31) && wb < (1LL << 31) && gsd_env_int("GSD_BF16_CONV_BUF", 1) != 0) ? 1 : 0;
-    P.img_bytes = (unsigned)ib;
-    P.wt_bytes = (unsigned)wb;
-  }
-  P.bias = nullptr;
-  P.partials = partials;
-  P.ep_scale = ep_scale; P.ep_shift = ep_shift;
-  P.bw_y = nullptr; P.bw_pitch = 0; P.bw_scale = P.bw_shift = P.bw_mean = P.bw_invstd = nullptr;
-  if (bw != nullptr) {
-    if (int e = gsd_check_nhwc(bw->y, "gsd_bf16_conv3x3 bw.y")) return e;
-    GSD_REQUIRE(bw->scale && bw->shift && bw->mean && bw->invstd && partials, GSD_ERR_BAD_ARG,
-                "gsd_bf16_conv3x3: fused BatchNorm backward needs coefficients and partials");
-    GSD_REQUIRE(bw->y->N == out->N && bw->y->H == out->H && bw->y->W == out->W && bw->y->C == M && (bw->y->pitch & 3) == 0,
-                GSD_ERR_BAD_ARG, "gsd_bf16_conv3x3: bw.y must have out's geometry");
-    P.bw_y = (const u16*)bw->y->ptr; P.bw_pitch = bw->y->pitch;
-    P.bw_scale = bw->scale; P.bw_shift = bw->shift; P.bw_mean = bw->mean; P.bw_invstd = bw->invstd;
-  }
-  const long grid = (long)P.N * pl.tiles_y * pl.tiles_x * pl.mblocks;
+  int ty[9], tx[9];
+  for (int t = 0; t < 9; ++t) { ty[t] = t / 3 - 1; tx[t] = t % 3 - 1; }
+  GConvP P = make_params(pl, in, wt, out, K, M, in->H, in->W, 9, 1, ty, tx, partials, bw, ep_scale, ep_shift);
+  P.HC = pl.HC; P.HP = pl.HP;
+  const long long ib = (long long)in->H * in->W * in->pitch * 2, wb = (long long)9 * pl.Mpad * K * 2;
+  P.buf = (ib < (1LL << 31) && wb < (1LL << 31) && gsd_env_int("GSD_BF16_CONV_BUF", 1) != 0) ? 1 : 0;
+  P.img_bytes = (unsigned)ib;
+  P.wt_bytes = (unsigned)wb;
+  const long grid = plan_items(P.N, pl);
   const size_t lds = (size_t)2 * 3 * pl.BM * 64 + (size_t)2 * (pl.wide ? 16 : 10) * 4096 + (size_t)(4 * pl.BM + 512) * sizeof(float);
   if (P.buf) {
     if (pl.wide) return launch<0, 1, 4, 1>(P, grid, lds, (hipStream_t)stream, "gsd_bf16_conv3x3");
@@ -641,12 +622,9 @@ static int conv_dense_impl(const gsd_nhwc* in, const void* wt, const gsd_nhwc* o
   if (int e = gsd_check_nhwc(in, "gsd_bf16_conv_dense in")) return e;
   if (int e = gsd_check_nhwc(out, "gsd_bf16_conv_dense out")) return e;
   GSD_REQUIRE(wt != nullptr && ty != nullptr && tx != nullptr, GSD_ERR_BAD_ARG, "gsd_bf16_conv_dense: null argument");
-  GSD_REQUIRE(K > 0 && K % 32 == 0 && in->C == K, GSD_ERR_UNSUPPORTED, "gsd_bf16_conv_dense: K=%d must be a multiple of 32 and in->C",
-              K);
-  GSD_REQUIRE(M > 0 && M % 16 == 0, GSD_ERR_UNSUPPORTED, "gsd_bf16_conv_dense: M=%d must be a multiple of 16", M);
+  if (int e = check_channels("gsd_bf16_conv_dense", in, out, K, M)) return e;
   GSD_REQUIRE(ntaps >= 1 && ntaps <= 9 && (stride == 1 || stride == 2), GSD_ERR_BAD_ARG, "gsd_bf16_conv_dense: bad taps/stride");
   GSD_REQUIRE(H > 0 && W > 0 && H < 65536 && W < 4096 && in->N == out->N, GSD_ERR_BAD_ARG, "gsd_bf16_conv_dense: bad grid");
-  GSD_REQUIRE((out->pitch & 3) == 0, GSD_ERR_UNSUPPORTED, "gsd_bf16_conv_dense: out pitch must be a multiple of 4");
   if (scatter_cs > 0) {
     GSD_REQUIRE(M == 4 * scatter_cs && scatter_cs % 16 == 0 && out->C == scatter_cs, GSD_ERR_BAD_ARG,
                 "gsd_bf16_conv_dense: scatter needs M == 4*Cs, Cs %% 16 == 0, out->C == Cs");
@@ -658,12 +636,9 @@ static int conv_dense_impl(const gsd_nhwc* in, const void* wt, const gsd_nhwc* o
     GSD_REQUIRE(out->C == M && H <= out->H && W <= out->W, GSD_ERR_BAD_ARG, "gsd_bf16_conv_dense: out must hold (H,W,M)");
   }
   if (bw != nullptr) {
-    if (int e = gsd_check_nhwc(bw->y, "gsd_bf16_conv_dense bw.y")) return e;
-    GSD_REQUIRE(scatter_cs == 0 && bias == nullptr && bw->scale && bw->shift && bw->mean && bw->invstd && partials, GSD_ERR_BAD_ARG,
-                "gsd_bf16_conv_dense: fused BatchNorm backward needs plain output, coefficients and partials");
-    GSD_REQUIRE(bw->y->N == out->N && bw->y->H == out->H && bw->y->W == out->W && out->H == H && out->W == W && bw->y->C == M &&
-                    (bw->y->pitch & 3) == 0,
-                GSD_ERR_BAD_ARG, "gsd_bf16_conv_dense: bw.y must have out's geometry (and out the GEMM's pixel grid)");
+    if (int e = bf16_check_bnbwd("gsd_bf16_conv_dense", bw, partials, out->N, out->H, out->W, M)) return e;
+    GSD_REQUIRE(scatter_cs == 0 && bias == nullptr && out->H == H && out->W == W, GSD_ERR_BAD_ARG,
+                "gsd_bf16_conv_dense: fused BatchNorm backward needs plain output (no scatter, no bias) on the GEMM's pixel grid");
   }
   if (ep_scale == nullptr && (partials == nullptr) == (bw == nullptr) && gsd_ctgemm_shape(in->N, H, W, K, M, ntaps, stride, scatter_cs)) {
     // the transposed convolutions' forward and dX: the large-tile kernel (gsd_bf16_ctgemm.hip)
@@ -673,26 +648,10 @@ static int conv_dense_impl(const gsd_nhwc* in, const void* wt, const gsd_nhwc* o
                 "gsd_bf16_conv_dense: taps that leave the buffer with fused statistics (gsd_bf16_conv_dense_partial_rows counted the large-tile kernel's rows)");
   }
   const Plan pl = make_plan(H, W, M);
-  GConvP P;
-  P.in = (const u16*)in->ptr; P.in_pitch = in->pitch; P.Hin = in->H; P.Win = in->W;
-  P.wt = (const u16*)wt;
-  P.out = (u16*)out->ptr; P.out_pitch = out->pitch; P.Hob = out->H; P.Wob = out->W;
-  P.N = in->N; P.H = H; P.W = W;
-  P.K = K; P.M = M; P.Mpad = pl.Mpad; P.mblocks = pl.mblocks;
-  P.ntaps = ntaps; P.stride = stride;
-  for (int t = 0; t < 9; ++t) { P.ty[t] = t < ntaps ? ty[t] : 0; P.tx[t] = t < ntaps ? tx[t] : 0; }
-  P.TH = pl.TH; P.TW = pl.TW; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x; P.HC = 0; P.HP = 0;
+  GConvP P = make_params(pl, in, wt, out, K, M, H, W, ntaps, stride, ty, tx, partials, bw, ep_scale, ep_shift);
   P.Cs = scatter_cs; P.oy = oy; P.ox = ox;
-  P.buf = 0; P.img_bytes = P.wt_bytes = 0;
   P.bias = bias;
-  P.partials = partials;
-  P.ep_scale = ep_scale; P.ep_shift = ep_shift;
-  P.bw_y = nullptr; P.bw_pitch = 0; P.bw_scale = P.bw_shift = P.bw_mean = P.bw_invstd = nullptr;
-  if (bw != nullptr) {
-    P.bw_y = (const u16*)bw->y->ptr; P.bw_pitch = bw->y->pitch;
-    P.bw_scale = bw->scale; P.bw_shift = bw->shift; P.bw_mean = bw->mean; P.bw_invstd = bw->invstd;
-  }
-  const long grid = (long)P.N * pl.tiles_y * pl.tiles_x * pl.mblocks;
+  const long grid = plan_items(P.N, pl);
   const int nsub = pl.wide ? 1 : 2;   // k-steps per barrier (kernel: NSUB)
   GSD_REQUIRE(K % (32 * nsub) == 0, GSD_ERR_UNSUPPORTED, "gsd_bf16_conv_dense: K=%d must be a multiple of 64 when M > 64", K);
   const size_t lds = (size_t)2 * nsub * pl.BM * 64 + (size_t)2 * nsub * pl.NPX * 96 + (size_t)(4 * pl.BM + 512) * sizeof(float);

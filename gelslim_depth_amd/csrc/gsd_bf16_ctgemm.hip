@@ -1,4 +1,5 @@
 // gsd_bf16_ctgemm.hip -- the two GEMM-shaped halves of ConvTranspose2d(k=2, s=2) (unet.py:36,41) on a large-tile kernel.
+// Host side over gsd_bf16_host.h (the m-block-aligned grid, the XCD flag, the fused-BatchNorm-backward fields).
 //
 //   forward   out[n, 2h+kh+oy, 2w+kw+ox, co] = bias[co] + sum_ci x[n,h,w,ci] * Wt[(kh,kw,co)][ci]      (K = Cin,   M = 4 Cout)
 //   dX        dx[n,h,w,ci] = sum_{kh,kw,co} g[n, 2h+kh+oy, 2w+kw+ox, co] * Wd[(kh,kw)][ci][co]          (K = 4 Cout, M = Cin)
@@ -13,7 +14,7 @@
 // of 256 consecutive pixels of the flattened (n,h,w) grid (no 2-D tile padding; the scatter / gather decodes (n,h,w) with
 // one reciprocal multiply per item).  Persistent blocks, XCD-aware order, next item's first fill under the epilogue.
 // Same accumulation order as gconv_bf16_kernel<1,..> (taps, then 32-channel chunks): outputs are bit-identical to it.
-#include "gsd_bf16_common.h"
+#include "gsd_bf16_host.h"
 
 #include <type_traits>
 
@@ -360,17 +361,6 @@ __global__ __launch_bounds__(512) void ctgemm_bf16_kernel(const CtP P) {
   }
 }
 
-int cu_count_ct() {
-  static int n = 0;   // benign race: every thread computes the same value
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    n = v;
-  }
-  return n;
-}
-
 struct CtPlan {
   bool ok;
   int BM, NPX, WN, mblocks, ntile, grid;
@@ -388,11 +378,8 @@ CtPlan ct_plan(long long Ppix, int M, bool dx) {
   p.NPX = 256;
   p.mblocks = M / p.BM;
   p.ntile = (int)((Ppix + p.NPX - 1) / p.NPX);
-  long grid = cu_count_ct() / p.mblocks * p.mblocks;
-  if (grid < p.mblocks) return p;
-  const long items = (long)p.ntile * p.mblocks;
-  if (grid > items) grid = items;
-  p.grid = (int)grid;
+  if (gsd_cu_count() < p.mblocks) return p;   // (the general kernel runs more m-blocks than CUs; this one does not)
+  p.grid = (int)bf16_mblock_grid((long)p.ntile * p.mblocks, p.mblocks);
   p.ok = true;
   return p;
 }
@@ -446,17 +433,12 @@ int gsd_ctgemm_launch(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, i
   P.N = in->N; P.H = H; P.W = W; P.P = in->N * H * W;
   P.rW = 1.0f / (float)W; P.rHW = 1.0f / (float)(H * W);
   P.M = M; P.mblocks = pl.mblocks; P.ntile = pl.ntile;
-  P.xcd = (gsd_env_int("GSD_BF16_XCD", 1) != 0 && pl.grid % 8 == 0 && (pl.grid / 8) % pl.mblocks == 0) ? 1 : 0;
+  P.xcd = bf16_xcd_order(pl.grid, pl.mblocks);
   P.Cs = scatter_cs; P.oy = ntaps == 4 ? ty[0] : oy; P.ox = ntaps == 4 ? tx[0] : ox;
   P.bias = bias; P.partials = partials;
-  P.bw_y = nullptr; P.bw_pitch = 0; P.bw_scale = P.bw_shift = P.bw_mean = P.bw_invstd = nullptr;
+  bf16_fill_bnbwd(P, bw);
   P.out_bytes = (unsigned)(((long long)(P.P - 1) * out->pitch + M) * 2);
-  P.y_bytes = 0;
-  if (bw != nullptr) {
-    P.bw_y = (const u16*)bw->y->ptr; P.bw_pitch = bw->y->pitch;
-    P.y_bytes = (unsigned)(((long long)(P.P - 1) * bw->y->pitch + M) * 2);
-    P.bw_scale = bw->scale; P.bw_shift = bw->shift; P.bw_mean = bw->mean; P.bw_invstd = bw->invstd;
-  }
+  P.y_bytes = bw != nullptr ? (unsigned)(((long long)(P.P - 1) * bw->y->pitch + M) * 2) : 0;
   hipStream_t st = (hipStream_t)stream;
   if (ntaps == 1) return launch_ct<0, 4, 2, 8>(P, pl.grid, st);
   if (pl.BM == 256) return launch_ct<1, 4, 2, 8>(P, pl.grid, st);

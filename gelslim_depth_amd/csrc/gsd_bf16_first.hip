@@ -1,4 +1,5 @@
 // gsd_bf16_first.hip -- the first layer of the bf16 path WITHOUT the im2col tensor.
+// Host side over gsd_bf16_host.h (the tile grids that the queries and launches share).
 //
 // `inc`'s first convolution (unet.py:11, 3 -> 64 @320x427) has K = 27: as an implicit GEMM it is one MFMA k-step
 // (v_mfma_f32_16x16x32_bf16, K padded to 32) per output tile -- 15 GFLOP per batch of 32 against 560 MB of output: it is bound
@@ -14,7 +15,7 @@
 //
 // Same products as the im2col path (same bf16 operands in the same k order through the same MFMA): the forward is
 // bit-identical to gsd_bf16_im2col3x3 + gsd_bf16_conv_dense, dW agrees to the rounding of another summation order.
-#include "gsd_bf16_common.h"
+#include "gsd_bf16_host.h"
 
 namespace {
 
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(256, FM == FM_BWD ? 2 : 3) void conv_first_bf16_ker
   }
 }
 
-int first_grid(int ntiles) { return ntiles < 2048 ? ntiles : 2048; }   // 8 small blocks per CU; one partial row each
+constexpr int F_GRID_CAP = 2048;   // 8 small blocks per CU; one partial row each
 
 // ---- dW of the first layer --------------------------------------------------------------------------------------------
 // D[co][k] = sum over pixels of d_raw[pixel][co] * patch[pixel][k], k = c*9 + t: the reduction runs over PIXELS, so both MFMA
@@ -445,7 +446,17 @@ __global__ __launch_bounds__(256) void wgrad_first_bf16_reduce(const float* __re
   dw[i] = (s0 + s1) + (s2 + s3);
 }
 
-int wg_first_grid(int ntiles) { return ntiles < 768 ? ntiles : 768; }   // 3 blocks per CU (LDS), one slab each
+constexpr int WG_GRID_CAP = 768;   // 3 blocks per CU (LDS), one slab each
+
+template <int MT>
+void first_launch_mt(int fm, int grid, hipStream_t st, const FirstP& P) {
+  switch (fm) {
+    case FM_STORE: hipLaunchKernelGGL((conv_first_bf16_kernel<MT, FM_STORE>), dim3(grid), dim3(256), 0, st, P); break;
+    case FM_EVAL: hipLaunchKernelGGL((conv_first_bf16_kernel<MT, FM_EVAL>), dim3(grid), dim3(256), 0, st, P); break;
+    case FM_STATS: hipLaunchKernelGGL((conv_first_bf16_kernel<MT, FM_STATS>), dim3(grid), dim3(256), 0, st, P); break;
+    default: hipLaunchKernelGGL((conv_first_bf16_kernel<MT, FM_BWD>), dim3(grid), dim3(256), 0, st, P); break;
+  }
+}
 
 }  // namespace
 
@@ -453,35 +464,15 @@ extern "C" int gsd_bf16_conv3x3_first_supported(int C, int M) { return (C >= 1 &
 
 extern "C" int gsd_bf16_conv3x3_first_partial_rows(int N, int H, int W, int M) {
   if (N <= 0 || H <= 0 || W <= 0 || M <= 0) return 0;
-  const long nt = (long)N * ceil_div(H, F_TH) * ceil_div(W, F_TW);
-  return nt < 2147483647L ? first_grid((int)nt) : 0;
+  Bf16Tiles t;
+  return bf16_tile_grid(N, H, W, F_TH, F_TW, F_GRID_CAP, &t) ? t.grid : 0;
 }
 
 static int first_launch(FirstP& P, int fm, void* stream, const char* what) {
-  P.tiles_y = ceil_div(P.H, F_TH); P.tiles_x = ceil_div(P.W, F_TW);
-  const long nt = (long)P.N * P.tiles_y * P.tiles_x;
-  GSD_REQUIRE(nt < 2147483647L, GSD_ERR_UNSUPPORTED, "%s: too many tiles", what);
-  P.ntiles = (int)nt;
-  const int grid = first_grid(P.ntiles);
-  const dim3 gd(grid), bd(256);
-  hipStream_t st = (hipStream_t)stream;
-#define GSD_FIRST_CASE(MT_, FM_) hipLaunchKernelGGL((conv_first_bf16_kernel<MT_, FM_>), gd, bd, 0, st, P)
-  if (P.M == 64) {
-    switch (fm) {
-      case FM_STORE: GSD_FIRST_CASE(4, FM_STORE); break;
-      case FM_EVAL: GSD_FIRST_CASE(4, FM_EVAL); break;
-      case FM_STATS: GSD_FIRST_CASE(4, FM_STATS); break;
-      default: GSD_FIRST_CASE(4, FM_BWD); break;
-    }
-  } else {
-    switch (fm) {
-      case FM_STORE: GSD_FIRST_CASE(2, FM_STORE); break;
-      case FM_EVAL: GSD_FIRST_CASE(2, FM_EVAL); break;
-      case FM_STATS: GSD_FIRST_CASE(2, FM_STATS); break;
-      default: GSD_FIRST_CASE(2, FM_BWD); break;
-    }
-  }
-#undef GSD_FIRST_CASE
+  int grid;
+  if (int e = bf16_plan_tiles(what, P, F_TH, F_TW, F_GRID_CAP, &grid)) return e;
+  if (P.M == 64) first_launch_mt<4>(fm, grid, (hipStream_t)stream, P);
+  else first_launch_mt<2>(fm, grid, (hipStream_t)stream, P);
   GSD_LAUNCH_CHECK(what);
   return GSD_OK;
 }
@@ -531,8 +522,9 @@ extern "C" int gsd_bf16_first_bn_bwd_reduce(const float* x, int N, int C, int H,
 
 extern "C" int64_t gsd_bf16_wgrad_first_workspace(int N, int H, int W, int M) {
   if (N <= 0 || H <= 0 || W <= 0 || M <= 0) return 0;
-  const long nt = (long)N * ceil_div(H, F_TH) * ceil_div(W, F_TW);
-  return (int64_t)wg_first_grid(nt < 2147483647L ? (int)nt : 2147483647) * M * 32;
+  Bf16Tiles t;
+  bf16_tile_grid(N, H, W, F_TH, F_TW, WG_GRID_CAP, &t);
+  return (int64_t)t.grid * M * 32;
 }
 
 static int wgrad_first_impl(const float* x, int N, int C, int H, int W, const gsd_nhwc* dz, const gsd_nhwc* y, const void* wt0,
@@ -561,11 +553,8 @@ static int wgrad_first_impl(const float* x, int N, int C, int H, int W, const gs
   P.shift = shift; P.wt0 = (const u16*)wt0;
   P.slabs = workspace;
   P.N = N; P.C = C; P.H = H; P.W = W; P.M = M;
-  P.tiles_y = ceil_div(H, F_TH); P.tiles_x = ceil_div(W, F_TW);
-  const long nt = (long)N * P.tiles_y * P.tiles_x;
-  GSD_REQUIRE(nt < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_bf16_wgrad_first: too many tiles");
-  P.ntiles = (int)nt;
-  const int grid = wg_first_grid(P.ntiles);
+  int grid;
+  if (int e = bf16_plan_tiles("gsd_bf16_wgrad_first", P, F_TH, F_TW, WG_GRID_CAP, &grid)) return e;
   GSD_REQUIRE(workspace_elems >= (int64_t)grid * M * 32, GSD_ERR_WORKSPACE, "gsd_bf16_wgrad_first: workspace too small");
   if (recompute) {
     if (M == 64) hipLaunchKernelGGL((wgrad_first_bf16_kernel<4, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, P);

@@ -1,5 +1,6 @@
 // gsd_bf16_inc.hip -- the north star's named block: the `inc` double convolution (unet.py:7-20 for `inc`, :67; 3 -> 64 -> 64 at
 // full resolution) in TRAIN mode without the raw output of its first convolution ever existing in HBM.
+// Host side over gsd_bf16_host.h (the tile grid that query and launch share).
 //
 // Unfused (gsd_bf16_first.hip + gsd_bf16_conv.hip + two BatchNorm-apply passes) the block moves 2.55x its algorithmic bytes:
 // the first convolution writes its raw output y0 (one MFMA k-step of arithmetic under 560 MB at batch 32), a pass reads it
@@ -39,7 +40,7 @@
 // DMA-filled kernel spends (the swizzle depends on the column only, so kernel rows and channel chunks are address immediates).
 // Weights: [tap][64 rows][128 B], piece p of row i at slot p ^ (i & 6); rows permuted as in gsd_bf16_conv.hip so that a lane
 // ends up with channels g*8 .. g*8+7 and 32 + g*8 .. of its pixel (16-byte stores).
-#include "gsd_bf16_common.h"
+#include "gsd_bf16_host.h"
 
 #include <type_traits>
 
@@ -380,24 +381,15 @@ __global__ __launch_bounds__(512) void inc_fused_bf16_kernel(const IncP P) {
 
 constexpr int INC_TH = 8;
 
-int inc_cu_count() {
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-    v = 256;
-  return v;
-}
-
-long inc_tiles(int N, int H, int W) { return (long)N * ceil_div(H, INC_TH) * ceil_div(W, I_TW); }
-
 }  // namespace
 
 extern "C" int gsd_bf16_inc_supported(int C, int M) { return (C >= 1 && 9 * C <= 32 && M == I_M) ? 1 : 0; }
 
 extern "C" int gsd_bf16_inc_conv_partial_rows(int N, int H, int W) {
   if (N <= 0 || H <= 0 || W <= 0) return 0;
-  const long nt = inc_tiles(N, H, W);
-  const int cus = inc_cu_count();
-  return (int)(nt < cus ? nt : cus);
+  Bf16Tiles t;   // one persistent block per CU, one partial row each
+  bf16_tile_grid(N, H, W, INC_TH, I_TW, gsd_cu_count(), &t);
+  return t.grid;
 }
 
 extern "C" int gsd_bf16_inc_conv(const float* x, int N, int C, int H, int W, const void* wt0, const float* scale0, const float* shift0,
@@ -418,10 +410,7 @@ extern "C" int gsd_bf16_inc_conv(const float* x, int N, int C, int H, int W, con
   P.a0 = (u16*)a0->ptr; P.a0_pitch = a0->pitch; P.y1 = (u16*)y1->ptr; P.y1_pitch = y1->pitch;
   P.partials = partials;
   P.N = N; P.C = C; P.H = H; P.W = W; P.Mpad = round_up(I_M, 128);
-  P.tiles_y = ceil_div(H, INC_TH); P.tiles_x = ceil_div(W, I_TW);
-  const long nt = inc_tiles(N, H, W);
-  GSD_REQUIRE(nt < 2147483647L, GSD_ERR_UNSUPPORTED, "gsd_bf16_inc_conv: too many tiles");
-  P.ntiles = (int)nt;
-  const int grid = gsd_bf16_inc_conv_partial_rows(N, H, W);
+  int grid;
+  if (int e = bf16_plan_tiles("gsd_bf16_inc_conv", P, INC_TH, I_TW, gsd_cu_count(), &grid)) return e;
   return gsd_launch<inc_fused_bf16_kernel<INC_TH>>("gsd_bf16_inc_conv", dim3(grid), dim3(512), IncGeo<INC_TH>::LDS, (hipStream_t)stream, P);
 }

@@ -1,4 +1,5 @@
 // gsd_bf16_wgrad.hip -- weight gradients of the bf16 path on v_mfma_f32_16x16x32_bf16, reduction over PIXELS.
+// Host side over gsd_bf16_host.h (the tile picker, the XCD knob).
 //
 //   D[t][m][n] = sum over pixels p of  A[p][m] * B[stride*p + tap_t][n]            (fp32 accumulation, fp32 result)
 //
@@ -18,7 +19,7 @@
 // Wave tile: 64 m x 16 n x T taps (36 accumulator tiles for 3x3); block = 4 waves: 128 m x 32 n, or 64 m x 64 n when
 // M <= 64.  One LDS image per block, two blocks per CU (the other block's MFMAs cover this block's DMA), split-K over
 // pixel tiles with fp32 slabs summed in a fixed order by gwgrad_reduce_kernel => bitwise reproducible.
-#include "gsd_bf16_common.h"
+#include "gsd_bf16_host.h"
 
 #include <cstdlib>
 
@@ -510,20 +511,7 @@ WPlan make_wplan(bool halo, int T, int N, int H, int W, int M, int Ncols) {
   p.BM = p.wide ? 64 : 128;
   p.BNC = p.wide ? 64 : 32;
   p.NPIX = halo ? 128 : 64;
-  long best = -1;
-  for (int tw = 32; tw <= 64; tw *= 2) {
-    const int th = p.NPIX / tw;
-    const long cost = (long)ceil_div(H, th) * ceil_div(W, tw);
-    if (best < 0 || cost < best) {
-      best = cost;
-      p.TW = tw;
-      p.TH = th;
-    }
-  }
-  p.tiles_y = ceil_div(H, p.TH);
-  p.tiles_x = ceil_div(W, p.TW);
-  p.HC = p.TW + 2;
-  p.HP = (p.TH + 2) * (p.TW + 2);
+  bf16_pick_tile(p, H, W, p.NPIX, 32, 64, false, 0);   // ties -> the narrower tile
   p.mblocks = ceil_div(M, p.BM);
   p.nblocks = ceil_div(Ncols, p.BNC);
   p.stages_total = N * p.tiles_y * p.tiles_x;
@@ -544,10 +532,6 @@ int launch_w(const GWgradP& P, int grid, size_t lds, hipStream_t st, const char*
   return gsd_launch<gwgrad_bf16_kernel<HALO, TT, WM, WN>>(what, dim3(grid), dim3(256), lds, st, P);
 }
 
-}  // namespace
-
-namespace {
-
 struct BigPlan {
   bool ok;
   int BM, mblocks, nblocks, stages_total, splits;
@@ -565,9 +549,7 @@ BigPlan make_bigplan(int ntaps, int N, int H, int W, int M, int Ncols) {
   p.mblocks = M / p.BM;
   p.nblocks = Ncols / 64;
   p.stages_total = (int)((P + 63) / 64);
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  int splits = cus / (p.mblocks * p.nblocks);   // one block per CU (its two LDS images fill the CU)
+  int splits = gsd_cu_count() / (p.mblocks * p.nblocks);   // one block per CU (its two LDS images fill the CU)
   if (splits < 1) splits = 1;
   if (splits > p.stages_total) splits = p.stages_total;
   p.splits = splits;
@@ -581,6 +563,14 @@ int launch_big(const GWBigP& P, int grid, hipStream_t st) {
   constexpr int BM = WM * 64;
   constexpr size_t img = ((size_t)(64 * (BM * 2 + 32) + 1023) / 1024 + (size_t)(4 * 64 * (64 * 2 + 32) + 1023) / 1024) * 1024;
   return gsd_launch<gwgrad_big_bf16_kernel<WM, WN>>("gsd_bf16_wgrad (large tile)", dim3(grid), dim3(512), 2 * img + 512, st, P);
+}
+
+// the tail of either form: the status `rc` of its launch, then its slabs summed into dw
+int reduce_slabs(int rc, const float* slabs, float* dw, int splits, int T, int M, int Ncols, int ncols_out, hipStream_t st) {
+  if (rc) return rc;
+  launch_reduce(slabs, dw, splits, T, M, Ncols, ncols_out, st);
+  GSD_LAUNCH_CHECK("gsd_bf16_wgrad reduce");
+  return GSD_OK;
 }
 
 }  // namespace
@@ -608,6 +598,7 @@ extern "C" int gsd_bf16_wgrad(const gsd_nhwc* a, const gsd_nhwc* b, int ntaps, i
       GSD_REQUIRE(ty[t] == t / 3 - 1 && tx[t] == t % 3 - 1, GSD_ERR_UNSUPPORTED, "gsd_bf16_wgrad: 9 taps must be the 3x3 p1 stencil");
   }
   const int M = a->C, Ncols = b->C;
+  hipStream_t st = (hipStream_t)stream;
   const BigPlan bp = make_bigplan(ntaps, a->N, a->H, a->W, M, Ncols);
   if (bp.ok && stride == 2 && (long long)a->N * a->H * a->W * a->pitch < 2147483647LL && (long long)b->N * b->H * b->W * b->pitch < 2147483647LL) {
     bool inside = true;   // the large-tile form gathers without a zero line: every tap of every pixel must be in b's buffer
@@ -624,13 +615,10 @@ extern "C" int gsd_bf16_wgrad(const gsd_nhwc* a, const gsd_nhwc* b, int ntaps, i
       Q.M = M; Q.Ncols = Ncols;
       for (int t = 0; t < 4; ++t) { Q.ty[t] = ty[t]; Q.tx[t] = tx[t]; }
       Q.stages_total = bp.stages_total; Q.splits = bp.splits; Q.mblocks = bp.mblocks; Q.nblocks = bp.nblocks;
-      Q.xcd = gsd_env_int("GSD_BF16_XCD", 1) != 0 ? 1 : 0;
+      Q.xcd = bf16_xcd_knob() ? 1 : 0;
       const int grid = bp.splits * bp.mblocks * bp.nblocks;
-      const int rc = bp.BM == 256 ? launch_big<4, 2>(Q, grid, (hipStream_t)stream) : launch_big<2, 4>(Q, grid, (hipStream_t)stream);
-      if (rc) return rc;
-      launch_reduce(workspace, dw, bp.splits, 4, M, Ncols, ncols_out, (hipStream_t)stream);
-      GSD_LAUNCH_CHECK("gsd_bf16_wgrad reduce");
-      return GSD_OK;
+      const int rc = bp.BM == 256 ? launch_big<4, 2>(Q, grid, st) : launch_big<2, 4>(Q, grid, st);
+      return reduce_slabs(rc, workspace, dw, bp.splits, 4, M, Ncols, ncols_out, st);
     }
   }
   const WPlan pl = make_wplan(halo, ntaps, a->N, a->H, a->W, M, Ncols);
@@ -647,19 +635,15 @@ extern "C" int gsd_bf16_wgrad(const gsd_nhwc* a, const gsd_nhwc* b, int ntaps, i
   P.TH = pl.TH; P.TW = pl.TW; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x; P.HC = pl.HC; P.HP = pl.HP;
   P.NPIX = pl.NPIX; P.KS = pl.NPIX / 32;
   P.stages_total = pl.stages_total; P.splits = pl.splits; P.mblocks = pl.mblocks; P.nblocks = pl.nblocks;
-  P.xcd = gsd_env_int("GSD_BF16_XCD", 1) != 0 ? 1 : 0;
+  P.xcd = bf16_xcd_knob() ? 1 : 0;
   GSD_REQUIRE((long long)a->H * a->W * a->pitch < (1LL << 30) && (long long)b->H * b->W * b->pitch < (1LL << 30), GSD_ERR_UNSUPPORTED,
               "gsd_bf16_wgrad: one image of an operand exceeds 2 GiB");
   P.a_img_bytes = (unsigned)((long long)a->H * a->W * a->pitch * 2);
   P.b_img_bytes = (unsigned)((long long)b->H * b->W * b->pitch * 2);
   const int grid = pl.splits * pl.mblocks * pl.nblocks;
   int rc;
-  hipStream_t st = (hipStream_t)stream;
   if (halo) rc = pl.wide ? launch_w<1, 9, 1, 4>(P, grid, pl.lds, st, "gsd_bf16_wgrad") : launch_w<1, 9, 2, 2>(P, grid, pl.lds, st, "gsd_bf16_wgrad");
   else if (ntaps == 4) rc = pl.wide ? launch_w<0, 4, 1, 4>(P, grid, pl.lds, st, "gsd_bf16_wgrad") : launch_w<0, 4, 2, 2>(P, grid, pl.lds, st, "gsd_bf16_wgrad");
   else rc = pl.wide ? launch_w<0, 1, 1, 4>(P, grid, pl.lds, st, "gsd_bf16_wgrad") : launch_w<0, 1, 2, 2>(P, grid, pl.lds, st, "gsd_bf16_wgrad");
-  if (rc) return rc;
-  launch_reduce(workspace, dw, pl.splits, ntaps, M, Ncols, ncols_out, (hipStream_t)stream);
-  GSD_LAUNCH_CHECK("gsd_bf16_wgrad reduce");
-  return GSD_OK;
+  return reduce_slabs(rc, workspace, dw, pl.splits, ntaps, M, Ncols, ncols_out, st);
 }

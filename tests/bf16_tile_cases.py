@@ -5,8 +5,10 @@ tests/test_gpu_bf16_tile_forms_fp64.py), not collected; it imports neither torch
 The restatements follow the host code line by line, force knobs included (read from `env`; default: the process environment, as
 the library reads it on every call); `cus` is the CU count the planners size their grids by (256: what the library assumes
 without a device, and what the MI355X reports):
-  gsd_bf16_conv.hip    make_plan, launch_grid, the XCD rule of launch<>, gsd_bf16_conv_partial_rows, the BUF rule of conv3x3_impl,
-                       gsd_bf16_conv_dense_partial_rows            (GSD_BF16_TW, GSD_BF16_XCD, GSD_BF16_CONV_BUF)
+  gsd_bf16_host.h      bf16_pick_tile (the loop of make_plan and of make_wplan, with either tie rule), bf16_mblock_grid (launch_grid
+                       here, and the grid of ct_plan), bf16_xcd_order (xcd_on here)                               (GSD_BF16_XCD)
+  gsd_bf16_conv.hip    make_plan, gsd_bf16_conv_partial_rows, the BUF rule of conv3x3_impl, gsd_bf16_conv_dense_partial_rows
+                                                                    (GSD_BF16_TW, GSD_BF16_CONV_BUF)
   gsd_bf16_ctgemm.hip  ct_plan, gsd_ctgemm_shape, gsd_ctgemm_operands, gsd_ctgemm_partial_rows      (GSD_BF16_CTGEMM, GSD_BF16_CT_BM)
   gsd_bf16_wgrad.hip   make_wplan, make_bigplan, gsd_bf16_wgrad_workspace and the dispatch of gsd_bf16_wgrad
                                                                     (GSD_BF16_WGRAD_BLOCKS, GSD_BF16_WGRAD_BIG)
