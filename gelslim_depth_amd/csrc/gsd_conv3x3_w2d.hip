@@ -34,6 +34,11 @@
 // bool that crosses a block boundary through a vector register).  The kernel lives at 256 registers: state the loop does not need
 // waits in LDS or packed in one register, and tests/test_w2d_isa.py holds every instantiation to zero scratch and the loop to its
 // vector-instruction count (profiles/r07_w2d_isa_counts.txt).
+// WHERE the loop's vector work sits counts for more than how much there is: every MFMA-to-MFMA gap that carries a vector
+// instruction or a fill costs cycles of its own, in both waves of a SIMD one after the other.  A chunk has three such gaps under
+// its MFMAs (weight fills; a halo fill; a halo fill + the second frequency row's transform) and the barrier's; the plain forms keep their LDS
+// addresses of both images in registers, so the loop's vector instructions are the transforms' arithmetic and nothing else;
+// the accumulators are zeroed by LDS reads (tests/test_w2d_gaps.py, profiles/w2d_gaps_isa_counts.txt).
 #include "gsd_conv3x3_host.h"
 
 #include <cstdio>
@@ -49,6 +54,8 @@ typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) f32x4v g_f32x4v;
 typedef __attribute__((address_space(1))) float g_float;
 typedef __attribute__((address_space(1))) char g_char;
+typedef __attribute__((address_space(3))) f32x4 l_f32x4;   // ... and LDS views
+typedef __attribute__((address_space(3))) float l_float;
 __device__ __forceinline__ g_f32x4v* w2d_g4(g_char* base, unsigned off) { return (g_f32x4v*)(base + off); }
 __device__ __forceinline__ g_float* w2d_g1(g_char* base, unsigned off) { return (g_float*)(base + off); }
 
@@ -623,11 +630,7 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
   const int rowA = (2 * fh) * P.WCp, rowB = (2 - fh) * P.WCp, rowC = (1 + 2 * fh) * P.WCp;   // (arithmetic in fh: they stay scalar)
   const f32x2v sg2 = {fh ? -1.f : 1.f, fh ? -1.f : 1.f};
 
-  f32x4 acc[4][12];   // [m-tile][frequency 6 r + fc of the wave's rows r = 0, 1]
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int f = 0; f < 12; ++f) acc[m][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[4][12];   // [m-tile][frequency 6 r + fc of the wave's rows r = 0, 1]; zeroed below, behind the first fills
 
   // A operands: MFMA group g = 0..11 of a chunk is frequency pair g / 2 of the wave (weight-image pair 6 fh + g / 2) for two m-tiles
   // of the pair's two frequencies -- one ds_read_b128 (16 lanes read 256 contiguous bytes), four MFMAs.  acc[0..1] are the m-tiles the
@@ -643,8 +646,46 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
     for (int ch = 0; ch < 4; ++ch) halo_slot(ch, smem + WTILE);
   }
 
-  // the chunk loop, unrolled by two: the LDS image a chunk reads (`cur`) is then a constant of each copy, and the image offsets
-  // fold into the instructions' immediate fields instead of costing an address addition per base register and chunk
+  // The accumulators start at zero without a vector instruction: 192 v_mov contend with the MFMAs of the CU's other block like
+  // any vector work, LDS reads do not.  The wave writes 16 bytes of zeros where nothing else lands before the first chunk's
+  // barrier -- the weight half of image 1, which the first chunk's group 0 starts to fill -- and reads them back 48 times (the
+  // LDS instructions of a wave execute in order; every lane reads the same address: a broadcast; the barrier's release fence has
+  // the reads complete before any wave goes on to fill the image).  A zero C operand in a peeled first chunk would need a third
+  // copy of the loop body.
+  {
+    l_f32x4* zp = (l_f32x4*)(smem + BUF + wave8 * 4);   // (an LDS pointer by type: 32 bits, and no base to add per read)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {   // (four dword stores of one zero register: a 16-byte store wants four)
+      asm volatile("" : "+v"(zp));
+      ((l_float*)zp)[e] = 0.f;
+    }
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int f = 0; f < 12; ++f) {
+        asm volatile("" : "+v"(zp));   // (an address hipcc cannot see through: 48 reads, not one read and 188 copies)
+        acc[m][f] = *zp;
+      }
+  }
+
+  // PLAIN: the lane's LDS byte addresses in both images -- window rows A, B, C, the A operands it keeps and those it gives -- wait
+  // in ten registers (the plain forms have them to spare, the activated ones do not): the loop adds no address, every read is a
+  // register plus an immediate
+  const l_float* l_adr[2][5] = {};   // (LDS pointers by type: 32 bits each)
+  if constexpr (PLAIN) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      l_adr[b][0] = (const l_float*)(smem + b * BUF + rowA + baddr);
+      l_adr[b][1] = (const l_float*)(smem + b * BUF + rowB + baddr);
+      l_adr[b][2] = (const l_float*)(smem + b * BUF + rowC + baddr);
+      l_adr[b][3] = (const l_float*)(smem + b * BUF + a_keep);
+      l_adr[b][4] = (const l_float*)(smem + b * BUF + a_give + a_keep);
+#pragma unroll
+      for (int k = 0; k < 5; ++k) asm volatile("" : "+v"(l_adr[b][k]));
+    }
+  }
+
+  // the chunk loop, unrolled by two: the LDS image a chunk reads (`cur`) is a constant of each copy
   auto run_chunk = [&](const int chunk, auto cur_c) {
     constexpr int cur = decltype(cur_c)::value;
     if constexpr (U4) {
@@ -675,26 +716,33 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       sc = sAff[kc], sh = sAff[Kpad + kc];
       lo = chunk < c_sw ? lo0 : lo1;   // (a chunk lies inside one segment and Cin is a multiple of 4: a scalar select)
     }
-    int more = (chunk + 1 - c_hi) >> 31;   // chunk + 1 < c_hi, as an integer made scalar by hand: hipcc carries the bool through a vector register to branch on it, twice
-    more = __builtin_amdgcn_readfirstlane(more);
-    // the image's offset as an opaque scalar: the LDS bases of the two images are then one set of registers plus an addition each,
-    // not two sets held through the loop (registers the accumulators need)
-    int ioff = cur * BUF, ioA = cur * BUF + rowA, ioB = cur * BUF + rowB, ioC = cur * BUF + rowC, ioG = cur * BUF + a_give;
-    __asm__ volatile("" : "+s"(ioff), "+s"(ioA), "+s"(ioB), "+s"(ioC), "+s"(ioG));
-    const float* Wc = smem + ioff;
-    const float* Wg = smem + ioG;
-    auto load_row = [&](const int io, float (&r)[6]) {
-      const float* Wr = smem + io;
-      const f32x4 ra = *reinterpret_cast<const f32x4*>(&Wr[baddr]);
-      const f32x2v rb = *reinterpret_cast<const f32x2v*>(&Wr[baddr + 4]);
+    // chunks behind this one, as a scalar the compiler cannot see through: a comparison it recognises (chunk + 1 < c_hi is the
+    // loop's own) travels as a bool through a vector register (v_cndmask + v_readfirstlane per chunk)
+    int more = c_hi - 1 - chunk;
+    asm volatile("" : "+s"(more));
+    const float *pA, *pB, *pC, *Wc, *Wg;   // the lane's three window rows and its two A-operand streams in image `cur`
+    if constexpr (PLAIN) {
+      pA = (const float*)l_adr[cur][0], pB = (const float*)l_adr[cur][1], pC = (const float*)l_adr[cur][2];
+      Wc = (const float*)l_adr[cur][3], Wg = (const float*)l_adr[cur][4];
+    } else {
+      // the image's offset as an opaque scalar: the LDS bases of the two images are then one set of registers plus an addition each,
+      // not two sets held through the loop (registers the activated forms do not have)
+      int ioff = cur * BUF, ioA = cur * BUF + rowA, ioB = cur * BUF + rowB, ioC = cur * BUF + rowC, ioG = cur * BUF + a_give;
+      __asm__ volatile("" : "+s"(ioff), "+s"(ioA), "+s"(ioB), "+s"(ioC), "+s"(ioG));
+      pA = smem + ioA + baddr, pB = smem + ioB + baddr, pC = smem + ioC + baddr;
+      Wc = smem + ioff + a_keep, Wg = smem + ioG + a_keep;
+    }
+    auto load_row = [&](const float* Wr, float (&r)[6]) {
+      const f32x4 ra = *reinterpret_cast<const f32x4*>(Wr);
+      const f32x2v rb = *reinterpret_cast<const f32x2v*>(Wr + 4);
       r[0] = ra[0], r[1] = ra[1], r[2] = ra[2], r[3] = ra[3], r[4] = rb[0], r[5] = rb[1];
     };
     float dA[6], dB[6], dC[6];
-    load_row(ioA, dA);
-    load_row(ioB, dB);
-    load_row(ioC, dC);
+    load_row(pA, dA);
+    load_row(pB, dB);
+    load_row(pC, dC);
     f32x4 av[2];   // read one group (four MFMAs) ahead
-    av[0] = *reinterpret_cast<const f32x4*>(&Wc[a_keep]);
+    av[0] = *reinterpret_cast<const f32x4*>(Wc);
     auto affine = [&](float (&r)[6]) {
       if constexpr (!PLAIN) {
         const f32x2v sc2 = {sc, sc}, sh2 = {sh, sh};
@@ -750,46 +798,44 @@ __global__ __launch_bounds__(128 * NWP, 2) void conv3x3_w2d_kernel(const W2DPara
       rt_c(tA, v[0]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    // the chunk's 48 MFMAs in 12 groups of four (one A read each, issued a group ahead).  Row 2 fh + 1 is transformed in small
-    // pieces inside the first row's groups -- an MFMA holds the SIMD's vector issue for 8 of its 32 cycles and every gap that carries
-    // vector work costs cycles of its own (profiles/r05_mfma_f32_issue_ubench.txt), so the pieces are few and short; the second
-    // row's groups carry no vector work.  The next chunk's fills ride in the first three groups.
+    // the chunk's 48 MFMAs in 12 groups of four (one A read each, issued a group ahead).  What an MFMA stream pays for is the
+    // number of MFMA-to-MFMA gaps that carry vector work, far more than the instructions in them, and the SIMD's two waves pay it
+    // one after the other (profiles/r05_mfma_f32_issue_ubench.txt).  So everything the vector pipe and the DMA have to do under
+    // the MFMAs sits in THREE gaps, behind the four MFMAs of groups 0, 1 and 2: the next chunk's weight fills, one halo unit, and
+    // the other halo unit with the whole transform of row 2 fh + 1 (ten packed instructions; due before group 6).  The other nine
+    // groups are MFMAs, LDS reads and scalar work.  (Both halo units in group 1's gap with the transform -- two gaps -- measured
+    // 0.8 % slower over the 17 plain layer shapes at batch 32: profiles/w2d_gaps_layers_b32.txt.)
 #pragma unroll
     for (int g = 0; g < 12; ++g) {
       const int r = g / 6, fe = (g >> 1) * 2 - 6 * r, mt = 2 * (g & 1);
-      if (g + 1 < 12) av[(g + 1) & 1] = *reinterpret_cast<const f32x4*>(&((g + 1) & 1 ? Wg : Wc)[a_keep + ((g + 1) >> 1) * 128]);
+      if (g + 1 < 12) av[(g + 1) & 1] = *reinterpret_cast<const f32x4*>(&((g + 1) & 1 ? Wg : Wc)[((g + 1) >> 1) * 128]);
       const f32x4& ap = av[g & 1];
       acc[mt][6 * r + fe] = mfma16(ap[0], v[r][fe], acc[mt][6 * r + fe]);
       acc[mt + 1][6 * r + fe] = mfma16(ap[1], v[r][fe], acc[mt + 1][6 * r + fe]);
       acc[mt][6 * r + fe + 1] = mfma16(ap[2], v[r][fe + 1], acc[mt][6 * r + fe + 1]);
       acc[mt + 1][6 * r + fe + 1] = mfma16(ap[3], v[r][fe + 1], acc[mt + 1][6 * r + fe + 1]);
-      // the second row's transform: tB (plain sources), then the three stages
-      const int piece = PLAIN ? g + 1 : g + 2;
-      if (piece == 1) col_b();
-      if (piece == 2) rt_a(tB, acB, beB);
-      if (piece == 3) rt_b(acB, beB, v[1]);
-      if (piece == 4) rt_c(tB, v[1]);
-      int more_g = more;   // (opaque per group: one scalar compare each instead of a lane mask carried from group to group)
-      asm volatile("" : "+s"(more_g));
-      if (g < 3 && more_g != 0) {
-        float* Wn = smem + (cur ^ 1) * BUF;
-        if (g == 0) {
-          begin_fill(chunk + 1, cur ^ 1);
-          weight_fill(chunk + 1, Wn);
-        } else {
-          if constexpr (PC) {
+      if (g < 3) {
+        __builtin_amdgcn_sched_barrier(0);   // the group's MFMAs and its A read first, the gap's work behind them in one piece
+        int more_g = more;   // (opaque per group: one scalar compare each instead of a lane mask carried from group to group)
+        asm volatile("" : "+s"(more_g));
+        if (more_g > 0) {
+          float* Wn = smem + (cur ^ 1) * BUF;
+          if (g == 0) {
+            begin_fill(chunk + 1, cur ^ 1);
+            weight_fill(chunk + 1, Wn);
+          } else if constexpr (PC) {
             halo_unit(g - 1, Wn + WTILE);
           } else {
             halo_slot(2 * g - 2, Wn + WTILE);
             halo_slot(2 * g - 1, Wn + WTILE);
           }
         }
-      }
-      if (g < 6) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // an MFMA
-          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // at most one vector instruction of the piece
+        // the second row's transform, whole: tB (plain sources), then the three stages
+        if (g == 2) {
+          if constexpr (PLAIN) col_b();
+          rt_a(tB, acB, beB);
+          rt_b(acB, beB, v[1]);
+          rt_c(tB, v[1]);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
