@@ -29,6 +29,7 @@ import torch
 from . import _lib as L
 from ._lib import lib, check
 from .engine_base import BN_EPS, ConvUnit, EngineBase, UpUnit
+from .engine_plan import PARTIAL_ROWS, WEIGHT_MODES, WORKSPACE, StepPlan, UnitPlan, UpPlan, choose_algo, plan_step
 
 
 def _r64(c: int) -> int:
@@ -40,71 +41,66 @@ def _r4(w: int) -> int:
 
 
 class _ConvForm:
-    """Entry points and weight-layout modes of one of the three conv3x3 forms: 0 direct taps, 1 Winograd F(4,3) along rows,
-    2 two-dimensional Winograd F(2x4,3x3)."""
+    """One of the three conv3x3 forms -- 0 direct taps, 1 Winograd F(4,3) along rows, 2 two-dimensional Winograd F(2x4,3x3): its
+    launches, without and with the engine's K-slab scratch (the direct form never splits K), and the library's queries about it.
+    Which form a launch takes, and with how many rows and slabs, is the plan's matter (engine_plan.ConvLaunch)."""
+    _CONV = ((lib.gsd_conv3x3, None), (lib.gsd_conv3x3_w43, lib.gsd_conv3x3_w43_ws), (lib.gsd_conv3x3_w2d, lib.gsd_conv3x3_w2d_ws))
+    _DGRAD_BNRELU = ((lib.gsd_conv3x3_dgrad_bnrelu, None), (lib.gsd_conv3x3_w43_dgrad_bnrelu, lib.gsd_conv3x3_w43_dgrad_bnrelu_ws),
+                     (lib.gsd_conv3x3_w2d_dgrad_bnrelu, lib.gsd_conv3x3_w2d_dgrad_bnrelu_ws))
 
     def __init__(self, algo: int):
         self.algo = algo
-        self.conv = (lib.gsd_conv3x3, lib.gsd_conv3x3_w43, lib.gsd_conv3x3_w2d)[algo]
-        self.dgrad_bnrelu = (lib.gsd_conv3x3_dgrad_bnrelu, lib.gsd_conv3x3_w43_dgrad_bnrelu, lib.gsd_conv3x3_w2d_dgrad_bnrelu)[algo]
-        self.partial_rows = (lib.gsd_conv3x3_partial_rows, lib.gsd_conv3x3_w43_partial_rows, lib.gsd_conv3x3_w2d_partial_rows)[algo]
-        self.mode_f, self.mode_d = ((0, 1), (4, 5), (8, 9))[algo]
-        # K-slab scratch the form would like for a shape (the two Winograd forms; 0: the shape runs unsplit)
-        self.workspace = (lambda *a: 0, lib.gsd_conv3x3_w43_workspace, lib.gsd_conv3x3_w2d_workspace)[algo]
+        self.mode_f, self.mode_d = WEIGHT_MODES[algo]
+        self.partial_rows, self.workspace = PARTIAL_ROWS[algo], WORKSPACE[algo]
 
     @staticmethod
     def choose(n: int, h: int, w: int, cin: int, c0: int, cout: int, train: bool) -> "_ConvForm":
-        """The library's preference for a launch shape (include/gsd.h: gsd_conv3x3_algo, gsd_conv3x3_prefers_w2d).  c0: channels
-        of the first source segment.  Eval mode gets the forms whose bits do not depend on the batch (no row folding, no K slabs)."""
-        if not train:
-            # decided from N-independent quantities only: the one-image plan says direct or Winograd; Winograd means the 2-D form (no
-            # row folding, no K slabs: image i of a batch gets the bits the image alone gets); where the 2-D form does not serve
-            # the channel counts the direct form does (its tiles never span images either) -- never the row form, which folds rows
-            # across images
-            algo = lib.gsd_conv3x3_algo(1, h, w, cin, cout)
-            if algo == 1:
-                algo = 2 if lib.gsd_conv3x3_w2d_supported(cin, c0) else 0
-            return _ConvForm(algo)
-        algo = lib.gsd_conv3x3_algo(n, h, w, cin, cout)
-        if algo == 1 and lib.gsd_conv3x3_w2d_supported(cin, c0) and lib.gsd_conv3x3_prefers_w2d(n, h, w, cin, cout, int(train)):
-            algo = 2
-        return _ConvForm(algo)
+        return _FORMS[choose_algo(n, h, w, cin, c0, cout, train)]
 
     def run(self, ws, src, nsrc, wt, cin, cout, dst, ndst, part, n, h, w, st):
         """conv3x3 forward / dX; `ws`: the engine's K-slab scratch (train mode) or None."""
-        if self.algo >= 1 and ws is not None:
-            fn = lib.gsd_conv3x3_w43_ws if self.algo == 1 else lib.gsd_conv3x3_w2d_ws
-            return fn(src, nsrc, wt, cin, cout, dst, ndst, part, ws.data_ptr(), ws.numel(), n, h, w, st)
-        return self.conv(src, nsrc, wt, cin, cout, dst, ndst, part, n, h, w, st)
+        plain, with_ws = self._CONV[self.algo]
+        if with_ws is not None and ws is not None:
+            return with_ws(src, nsrc, wt, cin, cout, dst, ndst, part, ws.data_ptr(), ws.numel(), n, h, w, st)
+        return plain(src, nsrc, wt, cin, cout, dst, ndst, part, n, h, w, st)
 
     def run_bnrelu(self, ws, src, wt, cin, cout, dst, raw, scale, shift, mean, invstd, part, n, h, w, st):
-        if self.algo >= 1 and ws is not None:
-            fn = lib.gsd_conv3x3_w43_dgrad_bnrelu_ws if self.algo == 1 else lib.gsd_conv3x3_w2d_dgrad_bnrelu_ws
-            return fn(src, wt, cin, cout, dst, raw, scale, shift, mean, invstd, part, ws.data_ptr(), ws.numel(), n, h, w, st)
-        return self.dgrad_bnrelu(src, wt, cin, cout, dst, raw, scale, shift, mean, invstd, part, n, h, w, st)
+        plain, with_ws = self._DGRAD_BNRELU[self.algo]
+        if with_ws is not None and ws is not None:
+            return with_ws(src, wt, cin, cout, dst, raw, scale, shift, mean, invstd, part, ws.data_ptr(), ws.numel(), n, h, w, st)
+        return plain(src, wt, cin, cout, dst, raw, scale, shift, mean, invstd, part, n, h, w, st)
+
+
+_FORMS = tuple(_ConvForm(algo) for algo in range(3))
+
+
+def _of_plan(name: str) -> property:
+    """A read-only view of one field of the owner's plan under the name the decision had as an attribute: nothing is copied."""
+    return property(lambda self: getattr(self.plan, name))
 
 
 class _Unit(ConvUnit):
     def __init__(self, prefix: str, conv_idx: int, bn_idx: int, cin: int, cout: int, level: int):
         super().__init__(prefix, conv_idx, bn_idx, cin, cout, level)
-        self.c0 = cin              # channels of the first source segment (the decoder's first convs: the skip tensor's)
+        self.plan: Optional[UnitPlan] = None   # every decision about this unit's launches at the current shape (engine_plan)
         self.raw = None
         self.dsrc = None  # d_raw as the dW / dX kernels read it: g itself, or the pitched scratch buffer (engine.gp)
-        self.pitched = False   # gsd_bn_bwd_apply writes d_raw out of place into the pitched buffer
-        self.fused_dw = False  # first layer: no dX, so dW forms d_raw itself (gsd_conv3x3_wgrad_bn) and the apply pass is skipped
         self.srcs = None  # gsd_src array kept for wgrad
-        self.act_once = False  # train-mode forward: relu(bn(.)) of the input is written once, pitched, and read as a plain source
-        self.form_f = self.form_d = None   # _ConvForm of the forward / dX launch for the current shape
-        self.forms_f = None                # ... of the forward launch in eval (False) and train (True) mode
+
+    pitched, fused_dw, act_once = _of_plan("pitched"), _of_plan("fused_dw"), _of_plan("act_once")
+    # the form of the train-mode forward launch and of the dX launch (None: the first layer)
+    form_f = property(lambda self: _FORMS[self.plan.fwd[True].algo])
+    form_d = property(lambda self: None if self.plan.dgrad is None else _FORMS[self.plan.dgrad.algo])
 
 
 class _Up(UpUnit):
     def __init__(self, j: int, cin: int, level_in: int):
         super().__init__(j, cin, level_in)
-        self.mode_d = 3            # gsd_weight_layout mode of wt_d (gsd_convT2x2_dgrad_layout)
-        self.bn_rows = 0           # > 0: the dX launch also does pass 1 of the BatchNorm backward of the unit below (partial rows)
+        self.plan: Optional[UpPlan] = None
         self.out = self.dout = None
         self.cat = None            # the level's concat buffer when `out` is a view of it (GSD_ACT_ONCE)
+
+    mode_d, bn_rows = _of_plan("mode_d"), _of_plan("bn_rows")
 
 
 class UNetEngine(EngineBase):
@@ -112,8 +108,7 @@ class UNetEngine(EngineBase):
 
     def __init__(self, n_channels: int, n_classes: int, layer_dimensions: Sequence[int]):
         super().__init__(n_channels, n_classes, layer_dimensions)
-        for j, (u0, _) in enumerate(self.dec):
-            u0.c0 = self.dims[self.L - 1 - j]      # cat[skip, up]: the skip tensor comes first
+        self.plan: Optional[StepPlan] = None   # what a step launches at the current shape; units and ups hold their part of it
         self._saved = False        # the last forward kept what a backward needs (train mode, or eval mode with keep=True)
         self._saved_eval = False   # ... and ran in eval mode: BatchNorm normalised with the running statistics
         # partial-row count up to which BatchNorm's column sums and finalize run as ONE launch (gsd_bn_[bwd_]reduce_finalize)
@@ -125,83 +120,45 @@ class UNetEngine(EngineBase):
         # bench hooks.  kernel_log (EngineBase): every conv3x3 forward / dX launch appends the row _log_end builds
         self.wgrad_log: Optional[list] = None      # conv3x3 dW launches (+ slab reducer), same rows as kernel_log
 
+    # per decoder / per level (index 0 unused), as lists: views of the plan
+    cat_on = property(lambda self: [up.plan.cat_on for up in self.ups])
+    pooled_pitched = property(lambda self: list(self.plan.pooled_pitched))
+
     # ------------------------------------------------------------------ buffers
-    # Library switches that change launch plans (tile shapes, partial-row counts, slab counts, the form a launch takes): partials,
-    # conv_ws and the weight-gradient workspaces are sized from them, so they are part of the shape key -- a switch flipped
-    # between two steps (a test's monkeypatch, a sweep in one process) re-sizes the buffers instead of overrunning them
+    # Library switches that change the plan (the form a launch takes, tile shapes, partial-row and slab counts, weight-image modes,
+    # which tensors go pitched): they are part of the shape key, so a switch flipped between two steps (a test's monkeypatch, a
+    # sweep in one process) re-plans and re-sizes the buffers instead of running a stale plan.  tests/test_engine_plan_cpu.py
+    # holds the list complete: every library switch that moves a plan must be named here
     _SIZING_ENV = ("GSD_W2D_TW", "GSD_W2D_TW8_PCT", "GSD_W43_TW", "GSD_W43_FOLD", "GSD_CONV_W2D", "GSD_CONV_ALGO", "GSD_W43_SPLIT",
                    "GSD_WGRAD_ALGO", "GSD_WGRAD_W2D", "GSD_WG2D_KX", "GSD_WG2D_BLOCKS", "GSD_WGRAD_BLOCKS", "GSD_WG43_TW",
-                   "GSD_ACT_ONCE", "GSD_ACT_ONCE_FORCE", "GSD_W2D_X4")
-
-    @staticmethod
-    def _desc(c: int, h: int, w: int, pitch: int, deferred: bool = False, n: int = 1) -> L.gsd_src:
-        """A gsd_src for the library's host-side queries (they read no device memory): a (c, h, w) segment with rows of `pitch`."""
-        s = L.gsd_src()
-        s.ptr = 256
-        s.scale = s.shift = 256 if deferred else None
-        s.C, s.H, s.W, s.relu, s.w_stride, s.slack = c, h, w, int(deferred), pitch, L.SLACK
-        s.c_stride = h * pitch
-        s.n_stride = c * h * pitch
-        return s
-
-    def _dw_form(self, u: "_Unit", n: int, lh: int, lw: int, segs) -> int:
-        arr = L.src_array(segs)
-        # (d_raw is pitched under the condition _ensure states for u.pitched, which it sets for train-mode forwards only)
-        pitched = bool(lib.gsd_conv3x3_wgrad_takes_pitched_dy(n, lh, lw, u.cin, u.cout)) and (not u.need_dgrad or u.form_d.algo >= 1)
-        dy = self._desc(u.cout, lh, lw, _r4(lw) if pitched else lw)
-        return lib.gsd_conv3x3_wgrad_form(arr, len(segs), C.byref(dy), u.cin, u.cout, n, lh, lw)
-
-    def _plan_act_once(self, n: int) -> None:
-        """Which tensors a train-mode forward writes activated and pitched (GSD_ACT_ONCE, default 1; 0: the deferred schedule).
-        Decided from the shape alone, whatever the mode of the forward that sizes the buffers: they serve both modes."""
-        on = os.environ.get("GSD_ACT_ONCE", "1") != "0"
-        hs, ws = self.hs, self.ws
-        self.pooled_pitched = [False] * (self.L + 1)
-        self.cat_on = [False] * self.L
-        for u in self.units:
-            u.act_once = False
-        if not on:
-            return
-        w2d = lambda u: all(f.algo == 2 for f in u.forms_f.values())   # the eval-mode forward reads the same buffers
-        for lvl, (u0, u1) in enumerate(self.enc):
-            lh, lw = hs[lvl], ws[lvl]
-            if lvl >= 1 and w2d(u0) and lib.gsd_act_once_pays(n, lh, lw, u0.cin, u0.cin, u0.cout, 0, 0, 2) and \
-                    lib.gsd_conv3x3_wgrad_takes_pitched_act(n, lh, lw, u0.cin, u0.cout) and \
-                    self._dw_form(u0, n, lh, lw, [self._desc(u0.cin, lh, lw, lw)]) == \
-                    self._dw_form(u0, n, lh, lw, [self._desc(u0.cin, lh, lw, _r4(lw))]):
-                self.pooled_pitched[lvl] = True
-        for pair in self.enc + self.dec:
-            u0, u1 = pair
-            lh, lw = hs[u1.level], ws[u1.level]
-            u1.act_once = u1.forms_f[True].algo == 2 and bool(lib.gsd_act_once_pays(n, lh, lw, u1.cin, u1.cin, u1.cout, 0, 0, 0))
-        for j, (u0, _) in enumerate(self.dec):
-            lvl = self.L - 1 - j
-            lh, lw = hs[lvl], ws[lvl]
-            cs, cu = u0.c0, u0.cin - u0.c0
-            p = _r4(lw)
-            two = [self._desc(cs, lh, lw, lw, deferred=True), self._desc(cu, 2 * hs[lvl + 1], 2 * ws[lvl + 1], 2 * ws[lvl + 1])]
-            self.cat_on[j] = self._pad_off(lvl) == (0, 0) and w2d(u0) and \
-                bool(lib.gsd_act_once_pays(n, lh, lw, cs, u0.cin, u0.cout, 0, 0, 1)) and \
-                bool(lib.gsd_conv3x3_wgrad_takes_pitched_act(n, lh, lw, u0.cin, u0.cout)) and \
-                self._dw_form(u0, n, lh, lw, two) == self._dw_form(u0, n, lh, lw, [self._desc(u0.cin, lh, lw, p)])
+                   "GSD_ACT_ONCE", "GSD_ACT_ONCE_FORCE", "GSD_W2D_X4", "GSD_W2D_SPLIT", "GSD_CONVT_DG_DMA", "GSD_WGRAD_FIRST")
 
     def _ensure(self, n: int, h: int, w: int, dev: torch.device, train: bool) -> None:
         key = (n, h, w, str(dev), self._env_key())
         if self._shape == key and (not train or self.units[0].g is not None):
             return
-        self.buffers_made += 1     # past the early return: pooled, partials and the workspaces below are re-made every time
+        self.buffers_made += 1     # past the early return: pooled, partials and the workspaces are re-made every time
         if self._shape != key:
             for u in self.units:
                 u.raw = u.g = None
             for up in self.ups:
                 up.out = up.dout = up.cat = None
+            self.plan = plan_step(self.n_channels, self.n_classes, self.dims, n, h, w)
+            for u, p in zip(self.units + self.ups, self.plan.units + self.plan.ups):
+                u.plan = p
         self._shape = key
-        hs, ws = self._set_pyramid(h, w)
+        self._set_pyramid(h, w)
+        self._allocate(dev, train)
+
+    def _allocate(self, dev: torch.device, train: bool) -> None:
+        """self.plan's sizes and flags as tensors and streams; train: also what a backward needs."""
+        plan, size = self.plan, self.plan.sizes[train]
+        n, hs, ws = plan.n, plan.hs, plan.ws
         f32 = dict(device=dev, dtype=torch.float32)
-        max_part = 1
-        max_ws = 1
-        max_gp = 0
-        max_slab = 0
+
+        def fit(t: Optional[torch.Tensor], numel: int) -> torch.Tensor:
+            return t if t is not None and t.numel() == numel and t.device == dev else torch.empty((numel,), **f32)
+
         for u in self.units:
             lh, lw = hs[u.level], ws[u.level]
             if u.raw is None:
@@ -209,50 +166,15 @@ class UNetEngine(EngineBase):
             if train and u.g is None:
                 u.g = torch.empty((n, u.cout, lh, lw), **f32)
             self._alloc_bn(u, dev)
-            # direct taps, Winograd F(4,3) rows or two-dimensional Winograd, per layer shape, per direction and per mode: an
-            # eval-mode forward takes the forms whose bits do not depend on the batch size (_ConvForm.choose)
-            u.forms_f = {t: _ConvForm.choose(n, lh, lw, u.cin, u.c0, u.cout, t) for t in (False, True)}
-            u.form_f = u.forms_f[train]
-            u.form_d = _ConvForm.choose(n, lh, lw, u.cout, u.cout, u.cin, True) if u.need_dgrad else None
-            need = max(lib.gsd_weight_layout_size(f.mode_f, u.cout, u.cin) for f in u.forms_f.values())
-            if u.wt_f is None or u.wt_f.numel() != need or u.wt_f.device != dev:
-                u.wt_f = torch.empty((need,), **f32)
-            if not u.need_dgrad and train:
-                # the first layer's dX runs only for an input gradient; where gsd_conv3x3_dgrad_bn does not take over (u.fused_dw
-                # off) it is the direct form on the materialised d_raw (_input_dgrad)
-                need = lib.gsd_weight_layout_size(1, u.cout, u.cin)
-                if u.wt_d is None or u.wt_d.numel() != need or u.wt_d.device != dev:
-                    u.wt_d = torch.empty((need,), **f32)
-            if u.need_dgrad:
-                need = lib.gsd_weight_layout_size(u.form_d.mode_d, u.cout, u.cin)
-                if u.wt_d is None or u.wt_d.numel() != need or u.wt_d.device != dev:
-                    u.wt_d = torch.empty((need,), **f32)
-                max_part = max(max_part, u.form_d.partial_rows(n, lh, lw, u.cin) * 2 * _r64(u.cin))
-            rows = max(f.partial_rows(n, lh, lw, u.cout) for f in u.forms_f.values())
-            max_part = max(max_part, rows * 2 * _r64(u.cout))
-            if train:
-                # K slabs (gsd_conv3x3_w43_ws) for the launches that would leave most of the chip idle: train mode only --
-                # an eval-mode forward keeps the one summation order whatever the batch (image i of a batch == the image alone)
-                max_slab = max(max_slab, u.form_f.workspace(n, lh, lw, u.cin, u.cout),
-                               u.form_d.workspace(n, lh, lw, u.cout, u.cin) if u.need_dgrad else 0)
-                max_part = max(max_part, lib.gsd_bn_bwd_partial_rows(n, u.cout, lh, lw) * 3 * u.cout)
-                max_ws = max(max_ws, lib.gsd_conv3x3_wgrad_workspace(n, lh, lw, u.cin, u.cout))
-                # d_raw goes to a row-pitched scratch buffer (16-byte aligned rows) when both of its readers -- dW and dX
-                # of this unit -- are the Winograd kernels, which then move it as aligned 16-byte LDS-DMA pieces
-                u.pitched = bool(lib.gsd_conv3x3_wgrad_takes_pitched_dy(n, lh, lw, u.cin, u.cout)) and \
-                    (not u.need_dgrad or u.form_d.algo >= 1)
-                if u.pitched:
-                    max_gp = max(max_gp, n * u.cout * lh * _r4(lw))
-                u.fused_dw = (not u.need_dgrad) and bool(lib.gsd_conv3x3_wgrad_bn_supported(n, lh, lw, u.cin, u.cout))
-                if u.fused_dw:
-                    max_ws = max(max_ws, lib.gsd_conv3x3_wgrad_bn_workspace(n, lh, lw, u.cin, u.cout))
-        self._plan_act_once(n)
-        # relu(bn(raw)) of a unit's input, pitched: ONE recycled scratch (the forward conv is its only reader; dW stays deferred)
-        max_act = max([n * u.cin * hs[u.level] * _r4(ws[u.level]) for u in self.units if u.act_once] + [0])
-        self.act_buf = torch.empty((max_act,), **f32) if (train and max_act) else None
+            u.wt_f = fit(u.wt_f, u.plan.wt_f_size)
+            # the first layer's dX runs only for an input gradient; where gsd_conv3x3_dgrad_bn does not take over (fused_dw off) it
+            # is the direct form on the materialised d_raw (_input_dgrad)
+            if u.need_dgrad or train:
+                u.wt_d = fit(u.wt_d, u.plan.wt_d_size)
+        self.act_buf = torch.empty((size.act_buf,), **f32) if size.act_buf else None
         for up in self.ups:
             li = up.level_in
-            if up.out is None and self.cat_on[up.j]:
+            if up.out is None and up.plan.cat_on:
                 # the level's concat buffer, zero-filled ONCE: nothing ever writes its pad columns or, where 2w = W - 1, the last
                 # column of the up-sampled half -- the zero padding the plain aligned conv3x3 and dW launches read there
                 up.cat = L.pitched_slack_zeros((n, 2 * up.cout, hs[li - 1], ws[li - 1]), dev)
@@ -261,22 +183,10 @@ class UNetEngine(EngineBase):
                 up.out = L.slack_empty((n, up.cout, 2 * hs[li], 2 * ws[li]), dev)
             if train and up.dout is None:
                 up.dout = L.slack_empty((n, up.cout, 2 * hs[li], 2 * ws[li]), dev)   # ConvT dX reads pixel PAIRS: 2 floats past odd rows
-            if up.wt_f is None or up.wt_f.device != dev:
-                up.wt_f = torch.empty((lib.gsd_weight_layout_size(6, up.cout, up.cin),), **f32)
+            up.wt_f = fit(up.wt_f, up.plan.wt_f_size)
             if train:
-                up.mode_d = lib.gsd_convT2x2_dgrad_layout(C.byref(L.make_src(up.dout, slack=L.SLACK)), up.cin, up.cout, n, hs[li], ws[li])
-                need = lib.gsd_weight_layout_size(up.mode_d, up.cout, up.cin)
-                if up.wt_d is None or up.wt_d.numel() != need or up.wt_d.device != dev:
-                    up.wt_d = torch.empty((need,), **f32)
-                # the LDS-DMA dX kernel can leave dz of the unit below and its per-channel sums (gsd_convT2x2_dgrad_bnrelu)
-                up.bn_rows = 0
-                if up.mode_d == 7:
-                    up.bn_rows = lib.gsd_convT2x2_dgrad_bnrelu_partial_rows(C.byref(L.make_src(up.dout, slack=L.SLACK)), up.cin,
-                                                                            up.cout, n, hs[li], ws[li])
-                    max_part = max(max_part, up.bn_rows * 2 * _r64(up.cin))
-            if train:
-                max_ws = max(max_ws, lib.gsd_convT2x2_wgrad_workspace(n, hs[li], ws[li], up.cin, up.cout))
-        self.pooled = [None] + [(L.pitched_slack_zeros if self.pooled_pitched[l] else L.slack_empty)((n, self.dims[l - 1], hs[l], ws[l]), dev)
+                up.wt_d = fit(up.wt_d, up.plan.wt_d_size)
+        self.pooled = [None] + [(L.pitched_slack_zeros if plan.pooled_pitched[l] else L.slack_empty)((n, self.dims[l - 1], hs[l], ws[l]), dev)
                                 for l in range(1, self.L + 1)]
         self.dpooled = [None] + ([torch.empty((n, self.dims[l - 1], hs[l], ws[l]), **f32)
                                  for l in range(1, self.L + 1)] if train else [None] * self.L)
@@ -284,20 +194,16 @@ class UNetEngine(EngineBase):
         # still read its buffer while the BatchNorm backward of the next unit writes the other)
         side = train and self.side_dw
         self.side = torch.cuda.Stream(device=dev) if side else None   # (a high-priority side stream measured the same)
-        self.gps = [torch.empty((max_gp,), **f32) for _ in range(2 if side else 1)] if (train and max_gp) else None
+        self.gps = [torch.empty((size.gp,), **f32) for _ in range(2 if side else 1)] if size.gp else None
         self.gp_turn = 0
         self.gp_free: List[Optional[torch.cuda.Event]] = [None, None]   # recorded on the side stream behind a buffer's last reader
-        self.partials = torch.empty((max_part,), **f32)
-        self.conv_ws = torch.empty((max_slab,), **f32) if (train and max_slab) else None
-        # fp64 column sums of a dX launch's statistics (ConvT bias gradients): gsd_bn_reduce_partials wants (1 + 64) x 2 C doubles
-        self.db_sums = torch.empty((65 * 2 * max(u.cin for u in self.units),), device=dev, dtype=torch.float64) if train else None
-        self.wgrad_ws = torch.empty((max(max_ws, 64 * max(1, self.n_classes)),), **f32) if train else None
-        self.wgrad_ws_side = torch.empty((max(max_ws, 64),), **f32) if side else None
-        self.outw_partials = self.outw_sums = None
-        if train and self.n_classes > 1:    # dW of the output conv for K > 1 (gsd_conv1x1_out_wgrad)
-            kc = self.n_classes * self.dims[0]
-            self.outw_partials = torch.empty((lib.gsd_conv1x1_out_wgrad_rows(n, hs[0], ws[0]) * kc,), **f32)
-            self.outw_sums = torch.empty((65 * kc,), device=dev, dtype=torch.float64)
+        self.partials = torch.empty((size.partials,), **f32)
+        self.conv_ws = torch.empty((size.conv_ws,), **f32) if size.conv_ws else None
+        self.db_sums = torch.empty((size.db_sums,), device=dev, dtype=torch.float64) if train else None
+        self.wgrad_ws = torch.empty((size.wgrad_ws,), **f32) if train else None
+        self.wgrad_ws_side = torch.empty((size.wgrad_ws_side,), **f32) if side else None
+        self.outw_partials = torch.empty((size.outw_partials,), **f32) if size.outw_partials else None
+        self.outw_sums = torch.empty((size.outw_sums,), device=dev, dtype=torch.float64) if size.outw_sums else None
 
     # ------------------------------------------------------------------ helpers
     @staticmethod
@@ -319,14 +225,14 @@ class UNetEngine(EngineBase):
 
     def _run_unit(self, u: _Unit, srcs: List[L.gsd_src], P: Dict[str, torch.Tensor], train: bool, st: int,
                   keep: bool = False, prev: Optional[_Unit] = None) -> None:
-        """prev: the unit whose deferred output `srcs` describes.  Where the plan says so (u.act_once, train mode) it is written
+        """prev: the unit whose deferred output `srcs` describes.  Where the plan says so (act_once, train mode) it is written
         activated into the scratch buffer first and the conv reads that as a plain source; dW keeps the deferred one (u.srcs)."""
         n = u.raw.shape[0]
         lh, lw = self.hs[u.level], self.ws[u.level]
-        u.form_f = u.forms_f[train]
+        form = u.plan.fwd[train]
         u.srcs = L.src_array(srcs)
         arr = u.srcs
-        if train and prev is not None and u.act_once:
+        if train and prev is not None and u.plan.act_once:
             p = _r4(lw)
             act = self.act_buf[:n * u.cin * lh * p].view(n, u.cin, lh, p)[..., :lw]
             self._activate(prev, act, st)
@@ -335,11 +241,11 @@ class UNetEngine(EngineBase):
         dst = L.dst_array([L.make_dst(u.raw)])
         part = self.partials.data_ptr() if train else None
         ev = self._log_begin()
-        check(u.form_f.run(self.conv_ws if train else None, arr, len(srcs), u.wt_f.data_ptr(), u.cin, u.cout, dst, 1, part,
-                           n, lh, lw, st), "conv3x3")
-        self._log_end(ev, u.cout, u.cin, n, lh, lw, u.form_f.algo)
+        check(_FORMS[form.algo].run(self.conv_ws if train else None, arr, len(srcs), u.wt_f.data_ptr(), u.cin, u.cout, dst, 1, part,
+                                    n, lh, lw, st), "conv3x3")
+        self._log_end(ev, u.cout, u.cin, n, lh, lw, form.algo)
         if train:
-            rows = u.form_f.partial_rows(n, lh, lw, u.cout)
+            rows = form.partial_rows
             self._bn_stats(u, rows, _r64(u.cout), float(n * lh * lw), P, st,
                            one_launch=self.sync_fn is None and rows <= self.one_launch_rows)
         elif keep:   # a backward follows: also the running statistics as mean / invstd (same scale / shift bits)
@@ -388,7 +294,7 @@ class UNetEngine(EngineBase):
         self._saved = train or keep
         self._saved_eval = keep
         # every forward-mode weight layout of the pass: the 2-D Winograd images in one launch
-        self._layouts([(u.forms_f[train].mode_f, P[u.wname], u.cout, u.cin, u.wt_f) for u in self.units] +
+        self._layouts([(u.plan.fwd[train].weight_mode, P[u.wname], u.cout, u.cin, u.wt_f) for u in self.units] +
                       [(6, P[up.wname], up.cout, up.cin, up.wt_f) for up in self.ups], st)
         region = self._log_begin() if self.region_log is not None else None
         for lvl in range(self.L + 1):
@@ -401,9 +307,10 @@ class UNetEngine(EngineBase):
                 prev = self.enc[lvl - 1][1]
                 s = self._act_src(prev)
                 # train mode with a concat buffer at the level above: the pool also leaves the skip tensor activated in its channels
-                cat = self.ups[self.L - lvl].cat if train and self.cat_on[self.L - lvl] else None
+                above = self.ups[self.L - lvl]
+                cat = above.cat if train and above.plan.cat_on else None
                 skip_t = None if cat is None else cat[:, :prev.cout]
-                if self.pooled_pitched[lvl]:
+                if self.plan.pooled_pitched[lvl]:
                     dp = L.make_dst(self.pooled[lvl])
                     da = None if skip_t is None else C.byref(L.make_dst(skip_t))
                     check(lib.gsd_maxpool2_pitched(C.byref(s), C.byref(dp), da, n, st), "maxpool2_pitched")
@@ -427,7 +334,7 @@ class UNetEngine(EngineBase):
                                    self.hs[lvl + 1], self.ws[lvl + 1], st), "convT2x2")
             skip = self.enc[lvl][1]
             u0, u1 = self.dec[j]
-            if train and self.cat_on[j]:     # [activated skip | up]: one plain pitched source, for the conv and for its dW
+            if train and up.plan.cat_on:     # [activated skip | up]: one plain pitched source, for the conv and for its dW
                 self._run_unit(u0, [L.make_src(up.cat, slack=L.SLACK)], P, train, st, keep)
             else:
                 self._run_unit(u0, [self._act_src(skip), L.make_src(up.out, off=self._pad_off(lvl), slack=L.SLACK)], P, train, st,
@@ -443,12 +350,13 @@ class UNetEngine(EngineBase):
         return out
 
     # ------------------------------------------------------------------ backward
-    def _bn_bwd_tail(self, u: _Unit, P, G, st: int, dwout: Optional[torch.Tensor] = None, fused: bool = False) -> None:
+    def _bn_bwd_tail(self, u: _Unit, P, G, st: int, dwout: Optional[torch.Tensor] = None) -> None:
         """u.g holds dz and self.partials its per-block sums: finish BN backward, then dW.
-        fused: the partials come from gsd_conv3x3_dgrad_bnrelu (conv layout) instead of gsd_bn_bwd_reduce."""
+        u.plan.bn_bwd_fused: the partials come from a dX epilogue (conv layout) instead of gsd_bn_bwd_reduce."""
         n = u.raw.shape[0]
         lh, lw = self.hs[u.level], self.ws[u.level]
-        rows = u.fused_rows if fused else lib.gsd_bn_bwd_partial_rows(n, u.cout, lh, lw)   # fused: of the dX launch (_dgrad_fused)
+        fused = u.plan.bn_bwd_fused
+        rows = u.fused_rows if fused else u.plan.bn_bwd_rows   # fused: of the dX launch that wrote them
         # the one-launch form takes the output conv's dW row only from stand-alone rows
         self._bn_bwd_sums(u, rows, _r64(u.cout) if fused else 0, float(n * lh * lw), G, dwout, st,
                           one_launch=self.sync_fn is None and rows <= self.one_launch_rows and (dwout is None or not fused))
@@ -457,14 +365,14 @@ class UNetEngine(EngineBase):
             # c1 = c2 = 0 (dgamma = sum dz * xhat and dbeta = sum dz above hold as they are, xhat from the running statistics)
             u.c1.zero_()
             u.c2.zero_()
-        if u.fused_dw:
+        if u.plan.fused_dw:
             self._on_side(lambda sst, ws: check(
                 lib.gsd_conv3x3_wgrad_bn(u.srcs, u.g.data_ptr(), u.raw.data_ptr(), u.scale.data_ptr(), u.mean.data_ptr(),
                                          u.invstd.data_ptr(), u.c1.data_ptr(), u.c2.data_ptr(), u.cin, u.cout,
                                          G[u.wname].data_ptr(), ws.data_ptr(), ws.numel(), n, lh, lw, sst), "conv3x3_wgrad_bn"))
             return
         turn = None
-        if u.pitched:
+        if u.plan.pitched:
             p = _r4(lw)
             turn = self.gp_turn = (self.gp_turn + 1) % len(self.gps)
             if self.gp_free[turn] is not None:     # the dW launch that read this buffer two units ago
@@ -484,7 +392,7 @@ class UNetEngine(EngineBase):
                                   n, lh, lw, sst), "conv3x3_wgrad"))
         if ev0 is not None and not on_side:
             ev1 = self._event()
-            form = lib.gsd_conv3x3_wgrad_form(u.srcs, len(u.srcs), C.byref(dy), u.cin, u.cout, n, lh, lw)
+            form = u.plan.dw_form
             name = ("wgrad3x3_kernel", "wgrad3x3_w43_kernel", "wgrad3x3_w2d_kernel")[form]
             flops = 2.0 * u.cout * u.cin * 9 * n * lh * lw
             executed = 2048.0 * lib.gsd_conv3x3_wgrad_mfma_count(form, n, lh, lw, u.cin, u.cout) if form else flops
@@ -515,8 +423,8 @@ class UNetEngine(EngineBase):
         ev = self._log_begin()
         check(u.form_d.run(self.conv_ws, s, 1, u.wt_d.data_ptr(), u.cout, u.cin, L.dst_array(dsts), len(dsts),
                            self.partials.data_ptr() if stats else None, n, lh, lw, st), "conv3x3 dgrad")
-        self._log_end(ev, u.cin, u.cout, n, lh, lw, u.form_d.algo)
-        return u.form_d.partial_rows(n, lh, lw, u.cin) if stats else 0
+        self._log_end(ev, u.cin, u.cout, n, lh, lw, u.plan.dgrad.algo)
+        return u.plan.dgrad.partial_rows if stats else 0
 
     def _dgrad_fused(self, u: _Unit, prev: _Unit, P, st: int) -> None:
         """dX of unit u straight into prev.g as dz of prev's relu(bn(.)) (+ partial sums): u's input is prev's output."""
@@ -524,21 +432,21 @@ class UNetEngine(EngineBase):
         lh, lw = self.hs[u.level], self.ws[u.level]
         s = L.make_src(u.dsrc)
         d = L.make_dst(prev.g)
-        prev.fused_rows = u.form_d.partial_rows(n, lh, lw, u.cin)
+        prev.fused_rows = u.plan.dgrad.partial_rows
         ev = self._log_begin()
         check(u.form_d.run_bnrelu(self.conv_ws, C.byref(s), u.wt_d.data_ptr(), u.cout, u.cin, C.byref(d), prev.raw.data_ptr(),
                                   prev.scale.data_ptr(), prev.shift.data_ptr(), prev.mean.data_ptr(),
                                   prev.invstd.data_ptr(), self.partials.data_ptr(), n, lh, lw, st),
               "conv3x3_dgrad_bnrelu")
-        self._log_end(ev, u.cin, u.cout, n, lh, lw, u.form_d.algo)
+        self._log_end(ev, u.cin, u.cout, n, lh, lw, u.plan.dgrad.algo)
 
     def _input_dgrad(self, u: _Unit, P, dx: torch.Tensor, st: int) -> None:
         """dX of the first conv (the gradient w.r.t. the network's input) into dx, after u's BatchNorm backward is final.
-        u.fused_dw: d_raw was never stored, gsd_conv3x3_dgrad_bn forms it from dz and raw.  Otherwise gsd_bn_bwd_apply has left it
+        fused_dw: d_raw was never stored, gsd_conv3x3_dgrad_bn forms it from dz and raw.  Otherwise gsd_bn_bwd_apply has left it
         in u.dsrc and the general direct-form dX runs on it."""
         n = u.raw.shape[0]
         lh, lw = self.hs[u.level], self.ws[u.level]
-        if u.fused_dw:
+        if u.plan.fused_dw:
             check(lib.gsd_conv3x3_dgrad_bn(u.g.data_ptr(), u.raw.data_ptr(), u.scale.data_ptr(), u.mean.data_ptr(),
                                            u.invstd.data_ptr(), u.c1.data_ptr(), u.c2.data_ptr(), P[u.wname].data_ptr(), u.cin,
                                            u.cout, dx.data_ptr(), n, lh, lw, st), "conv3x3_dgrad_bn")
@@ -576,15 +484,15 @@ class UNetEngine(EngineBase):
             if dx.shape != x.shape or dx.dtype != torch.float32 or not dx.is_contiguous() or dx.device != x.device:
                 raise L.GsdError(f"backward(dx=...): expected a contiguous float32 {tuple(x.shape)} tensor on {x.device}")
             u = self.enc[0][0]
-            if u.fused_dw and not lib.gsd_conv3x3_dgrad_bn_supported(x.shape[0], x.shape[2], x.shape[3], u.cin, u.cout):
+            if u.plan.fused_dw and not self.input_grad_supported(x.shape[0], x.shape[2], x.shape[3]):
                 raise NotImplementedError(f"gelslim_depth_amd.UNet: no kernel computes the input gradient at input shape "
                                           f"{tuple(x.shape)} with {u.cout} first-layer channels")
         dout = dout.contiguous()
         st = L.stream_ptr()
         n = dout.shape[0]
         # the dX-mode weight layouts (the weights have not changed since the forward)
-        self._layouts([(u.form_d.mode_d, P[u.wname], u.cout, u.cin, u.wt_d) for u in self.units if u.need_dgrad] +
-                      [(up.mode_d, P[up.wname], up.cout, up.cin, up.wt_d) for up in self.ups], st)
+        self._layouts([(u.plan.dgrad.weight_mode, P[u.wname], u.cout, u.cin, u.wt_d) for u in self.units if u.need_dgrad] +
+                      [(up.plan.mode_d, P[up.wname], up.cout, up.cin, up.wt_d) for up in self.ups], st)
         last = self._last_unit()
         self._reduce(2, last, st, dout=dout, wout=P["outc.conv.weight"])
         check(lib.gsd_sum_planes(dout.data_ptr(), n, self.n_classes, dout.shape[2] * dout.shape[3],
@@ -603,14 +511,14 @@ class UNetEngine(EngineBase):
             up = self.ups[j]
             lvl = self.L - 1 - j
             # dz of u1 came from the output conv (j = L-1) or from the ConvT dX of the level above -- with its sums when fused
-            self._bn_bwd_tail(u1, P, G, st, dwout, fused=j < self.L - 1 and self.ups[j + 1].bn_rows > 0)
+            self._bn_bwd_tail(u1, P, G, st, dwout)
             dwout = None
             self._dgrad_fused(u1, u0, P, st)
-            self._bn_bwd_tail(u0, P, G, st, fused=True)
+            self._bn_bwd_tail(u0, P, G, st)
             skip = self.enc[lvl][1]
             # the ConvT bias gradient is the per-channel sum of up.dout: the Winograd dX launch that writes up.dout leaves it
             # as statistics of its second (cropped) destination -- no second pass over up.dout
-            db_fused = u0.form_d.algo >= 1
+            db_fused = u0.plan.dgrad.algo >= 1
             rows = self._dgrad(u0, P, [L.make_dst(skip.g), L.make_dst(up.dout, off=self._pad_off(lvl))], st, stats=db_fused)
             if db_fused:
                 check(lib.gsd_partials_channel_sums(self.partials.data_ptr(), rows, _r64(u0.cin), u0.cin, skip.cout, up.cout,
@@ -624,14 +532,14 @@ class UNetEngine(EngineBase):
                                        None if db_fused else G[up.bname].data_ptr(), ws.data_ptr(), ws.numel(), n, hi, wi, sst),
                 "convT2x2_wgrad"))
             d = L.make_dst(prev.g)
-            if up.bn_rows:
+            if up.plan.bn_rows:
                 check(lib.gsd_convT2x2_dgrad_bnrelu(C.byref(dys), up.wt_d.data_ptr(), up.cin, up.cout, C.byref(d), prev.raw.data_ptr(),
                                                     prev.scale.data_ptr(), prev.shift.data_ptr(), prev.mean.data_ptr(),
                                                     prev.invstd.data_ptr(), self.partials.data_ptr(), n, hi, wi, st),
                       "convT2x2_dgrad_bnrelu")
-                prev.fused_rows = up.bn_rows
+                prev.fused_rows = up.plan.bn_rows
             else:
-                check(lib.gsd_convT2x2_dgrad_as(up.mode_d, C.byref(dys), up.wt_d.data_ptr(), up.cin, up.cout, C.byref(d), n, hi, wi, st),
+                check(lib.gsd_convT2x2_dgrad_as(up.plan.mode_d, C.byref(dys), up.wt_d.data_ptr(), up.cin, up.cout, C.byref(d), n, hi, wi, st),
                       "convT2x2_dgrad")
                 self._reduce(0, prev, st)
             self._announce(f"dec{j}")      # up.{j}.* (and outc with the last decoder) are final
@@ -640,10 +548,10 @@ class UNetEngine(EngineBase):
             if lvl < self.L:
                 self._reduce(1, u1, st, dpool=self.dpooled[lvl + 1])
             # the bottom unit's dz came from the first ConvT dX -- with its sums when that launch was the fused one
-            self._bn_bwd_tail(u1, P, G, st, dwout, fused=lvl == self.L and self.L > 0 and self.ups[0].bn_rows > 0)
+            self._bn_bwd_tail(u1, P, G, st, dwout)
             dwout = None
             self._dgrad_fused(u1, u0, P, st)
-            self._bn_bwd_tail(u0, P, G, st, fused=True)
+            self._bn_bwd_tail(u0, P, G, st)
             if lvl == 0 and dx is not None:
                 self._input_dgrad(u0, P, dx, st)   # c1 / c2 are final; the first layer's dW runs beside it on the side stream
             self._announce(f"enc{lvl}")

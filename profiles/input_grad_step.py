@@ -24,4 +24,4 @@ for i in range(steps + 1):
     loss.backward()
 torch.cuda.synchronize()
 u = m._engine.enc[0][0]
-print(f"batch {B}: {steps + 1} steps, first layer fused dW/dX {u.fused_dw}, |x.grad| sum {x.grad.abs().sum().item():.6e}")
+print(f"batch {B}: {steps + 1} steps, first layer fused dW/dX {u.plan.fused_dw}, |x.grad| sum {x.grad.abs().sum().item():.6e}")

@@ -297,7 +297,7 @@ def assert_pads_zero(eng):
         if up.dout is not None:
             slacked.append(up.dout)
     for l in range(1, eng.L + 1):
-        if eng.pooled_pitched[l]:
+        if eng.plan.pooled_pitched[l]:
             zero(full_pitch(eng.pooled[l])[..., eng.pooled[l].shape[3]:], f"pooled[{l}] pad columns")
     for t in slacked:
         for part in slack_of(t, _lib.SLACK):

@@ -257,7 +257,7 @@ def _two_steps(env):
         losses = [float(step(xd, td)), float(step(xd, td))]
         torch.cuda.synchronize()
         e = m._engine
-        plan = (sum(u.act_once for u in e.units), sum(e.cat_on), sum(e.pooled_pitched))
+        plan = (sum(u.plan.act_once for u in e.units), sum(up.plan.cat_on for up in e.ups), sum(e.plan.pooled_pitched))
         cats = [(up.cat, 2 * e.hs[up.level_in], 2 * e.ws[up.level_in]) for up in e.ups if up.cat is not None]
         res = dict(loss=losses, out=step._out.clone(), g=step.g_flat.clone(), p=step.p_flat.clone(),
                    bn=None if step.bn_flat is None else step.bn_flat.clone(),

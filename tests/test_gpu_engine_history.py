@@ -110,7 +110,7 @@ def test_train_step_results_do_not_depend_on_what_ran_before(monkeypatch, precis
     assert precision == "bf16" or (eng.one_launch_rows == 0) == ("GSD_BN_ONE_LAUNCH_ROWS" in env)
     assert S.assert_pads_zero(eng) > 0
     if env == FORCED:
-        assert any(eng.cat_on) and any(eng.pooled_pitched), "the forced plan: concat buffers and pitched pooled tensors"
+        assert any(up.plan.cat_on for up in eng.ups) and any(eng.plan.pooled_pitched), "the forced plan: concat buffers and pitched pooled tensors"
 
 
 # --------------------------------------------------------------------------------------------------------- autograd sequence

@@ -72,9 +72,9 @@ def engine_flags(eng):
         c64 = any(eng._use_c64(u.cin, u.cout) for u in eng.units if not u.first)
         return {"first_direct": {eng.first_direct}, "fused_inc": {eng.fused_inc}, "apply_pool": {eng.apply_pool}, "c64": {c64},
                 "fused_out": {eng.fused_out}, "side_dw": {eng.side_dw}}
-    return {"act_once": {bool(u.act_once) for u in eng.units}, "cat_on": {bool(v) for v in eng.cat_on},
-            "pooled_pitched": {bool(v) for v in eng.pooled_pitched[1:]}, "pitched": {bool(u.pitched) for u in eng.units},
-            "fused_dw": {bool(u.fused_dw) for u in eng.units}, "conv_ws": {eng.conv_ws is not None}, "side": {eng.side is not None},
+    return {"act_once": {u.plan.act_once for u in eng.units}, "cat_on": {up.plan.cat_on for up in eng.ups},
+            "pooled_pitched": set(eng.plan.pooled_pitched[1:]), "pitched": {u.plan.pitched for u in eng.units},
+            "fused_dw": {u.plan.fused_dw for u in eng.units}, "conv_ws": {eng.conv_ws is not None}, "side": {eng.side is not None},
             "bn_one_launch": {eng.one_launch_rows > 0}}      # (no layer of these cases has more than a few hundred partial rows)
 
 
@@ -145,7 +145,7 @@ def test_an_unzeroed_concat_buffer_is_rejected(monkeypatch):
     for pattern in S.PATTERNS:
         with S.poison(monkeypatch, pattern):
             res[pattern], eng = S.train_steps(case)
-        assert sum(eng.cat_on) == 2 and sum(eng.pooled_pitched) == 2
+        assert sum(up.plan.cat_on for up in eng.ups) == 2 and sum(eng.plan.pooled_pitched) == 2
     with pytest.raises(AssertionError, match="differ in their bits"):      # finite, and wrong
         S.same_results(res[S.ZERO], res[S.BIG], "unzeroed concat buffers: zero against big")
     with pytest.raises(AssertionError):       # (different bits or non-finite, as far as an fmaxf on the way swallows the NaN)

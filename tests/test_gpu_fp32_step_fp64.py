@@ -148,7 +148,7 @@ def act_in(r, u, i, j):
 def holds_dz(u):
     """u.g still holds dz: the apply pass wrote d_raw out of place into the pitched buffer (since reused), or the first layer's
     dW formed d_raw itself.  Otherwise u.g holds d_raw in place."""
-    return u.pitched or u.fused_dw
+    return u.plan.pitched or u.plan.fused_dw
 
 
 def d_raw_of(u, i, j):
@@ -159,22 +159,7 @@ def d_raw_of(u, i, j):
 
 
 def dx_tau(u):
-    return R.TAU_WINO if u.form_d.algo else R.TAU_DIRECT
-
-
-def bwd_fused(e, u):
-    """Whether _bn_bwd_tail runs with fused=True for u (its dz and sums came from a dX epilogue), as UNetEngine.backward does."""
-    for lvl, (u0, u1) in enumerate(e.enc):
-        if u is u0:
-            return True
-        if u is u1:
-            return lvl == e.L and e.L > 0 and e.ups[0].bn_rows > 0
-    for j, (u0, u1) in enumerate(e.dec):
-        if u is u0:
-            return True
-        if u is u1:
-            return j < e.L - 1 and e.ups[j + 1].bn_rows > 0
-    raise AssertionError
+    return R.TAU_WINO if u.plan.dgrad.algo else R.TAU_DIRECT
 
 
 # ----------------------------------------------------------------------------------------------------------- schedule
@@ -185,33 +170,34 @@ def test_schedule(run):
     assert e.side is not None and e.side_dw, "weight gradients run on the side stream"
     assert e.gps is not None and len(e.gps) == 2, "two pitched d_raw buffers, taken in turn"
     assert e.one_launch_rows == 4096 and e.sync_fn is None
-    assert e.enc[0][0].fused_dw, "the first layer's dW forms d_raw itself"
-    pitched = [run.name[id(u)] for u in e.units if u.pitched]
+    assert e.enc[0][0].plan.fused_dw, "the first layer's dW forms d_raw itself"
+    pitched = [run.name[id(u)] for u in e.units if u.plan.pitched]
     assert pitched, "at least one unit writes d_raw to the pitched buffer"
     forms, fwd, bwd, slabs = {}, {}, {}, []
     for u in e.units:
         lh, lw = e.hs[u.level], e.ws[u.level]
         nm = run.name[id(u)]
-        rows = u.form_f.partial_rows(n, lh, lw, u.cout)
+        rows = u.plan.fwd[True].partial_rows
         fwd[nm] = "one" if rows <= e.one_launch_rows else "three"
-        fused = bwd_fused(e, u)
-        rows_b = u.fused_rows if fused else L.lib.gsd_bn_bwd_partial_rows(n, u.cout, lh, lw)
+        fused = u.plan.bn_bwd_fused     # (tests/test_engine_plan_cpu.py states the rule)
+        rows_b = u.fused_rows if fused else u.plan.bn_bwd_rows
         bwd[nm] = ("one" if rows_b <= e.one_launch_rows else "three") + (" (dX epilogue)" if fused else "")
-        if u.form_f.workspace(n, lh, lw, u.cin, u.cout) or (u.need_dgrad and u.form_d.workspace(n, lh, lw, u.cout, u.cin)):
+        if u.plan.fwd[True].workspace or (u.need_dgrad and u.plan.dgrad.workspace):
             slabs.append(nm)
-        if not u.fused_dw:
+        if not u.plan.fused_dw:
             dy = L.make_src(u.dsrc)
-            forms[nm] = ("direct", "w43", "w2d")[L.lib.gsd_conv3x3_wgrad_form(u.srcs, len(u.srcs), C.byref(dy), u.cin, u.cout, n,
-                                                                             lh, lw)]
-    SCHED[f"N{n}"] = {"pitched": pitched, "fused_dw": [run.name[id(u)] for u in e.units if u.fused_dw], "dw_form": forms,
+            form = L.lib.gsd_conv3x3_wgrad_form(u.srcs, len(u.srcs), C.byref(dy), u.cin, u.cout, n, lh, lw)
+            assert form == u.plan.dw_form, f"{nm}: the plan's dW form against the library's with the real operands"
+            forms[nm] = ("direct", "w43", "w2d")[form]
+    SCHED[f"N{n}"] = {"pitched": pitched, "fused_dw": [run.name[id(u)] for u in e.units if u.plan.fused_dw], "dw_form": forms,
                       "bn_forward": fwd, "bn_backward": bwd, "k_slabs": slabs,
-                      "convT_dx_fused_bn": [up.bn_rows > 0 for up in e.ups],
-                      "convT_db_from_dx_stats": [e.dec[j][0].form_d.algo >= 1 for j in range(e.L)]}
+                      "convT_dx_fused_bn": [up.plan.bn_rows > 0 for up in e.ups],
+                      "convT_db_from_dx_stats": [e.dec[j][0].plan.dgrad.algo >= 1 for j in range(e.L)]}
     assert "w2d" in forms.values(), "the 2-D Winograd dW runs somewhere"
     seen_f = {v for s in SCHED.values() for v in s["bn_forward"].values()}
     seen_b = {v.split()[0] for s in SCHED.values() for v in s["bn_backward"].values()}
     assert seen_f == {"one", "three"} and seen_b == {"one", "three"}, (seen_f, seen_b)
-    assert any(up.bn_rows > 0 for up in e.ups), "the fused ConvT dX + BatchNorm pass 1 runs"
+    assert any(up.plan.bn_rows > 0 for up in e.ups), "the fused ConvT dX + BatchNorm pass 1 runs"
 
 
 # ----------------------------------------------------------------------------------------------------------- forward
@@ -220,7 +206,7 @@ def test_forward_and_batchnorm(run):
     for u in e.units:
         lh, lw = e.hs[u.level], e.ws[u.level]
         nm = run.name[id(u)]
-        tau = R.TAU_WINO if u.form_f.algo else R.TAU_DIRECT
+        tau = R.TAU_WINO if u.plan.fwd[True].algo else R.TAU_DIRECT
         w64 = P[u.wname].double()
         acc = [torch.zeros(u.cout, dtype=torch.float64, device="cuda") for _ in range(4)]
         for i, j in chunks(n, max(u.cin, u.cout) * lh * lw):
@@ -383,7 +369,7 @@ def test_backward_chain(run):
             R.check_bound(e.dpooled[lvl][i:j], ref, cond, dx_tau(u0), f"{tag} dpooled[{lvl}]", n0=i, key=f"{tag}-dx")
             del d, da, ref, cond
     for jj, up in enumerate(e.ups):
-        if e.dec[jj][0].form_d.algo >= 1:     # the bias gradient from the statistics of the dX launch that wrote up.dout
+        if e.dec[jj][0].plan.dgrad.algo >= 1:     # the bias gradient from the statistics of the dX launch that wrote up.dout
             R.check_sums(G[up.bname], dbacc[jj][0], dbacc[jj][1], R.TAU_STATS, f"{tag} up{jj}.up db (dX statistics)",
                          key=f"{tag}-stats")
 
@@ -427,7 +413,7 @@ def test_parameter_gradients(run):
             ref += r_
             cond += c_
             del d, da, r_, c_
-        R.check_bound(G[u.wname], ref, cond, R.TAU_DW, f"{tag} {nm} dW{' (fused first layer)' if u.fused_dw else ''}",
+        R.check_bound(G[u.wname], ref, cond, R.TAU_DW, f"{tag} {nm} dW{' (fused first layer)' if u.plan.fused_dw else ''}",
                       key=f"{tag}-dw", weights=True)
     for jj, up in enumerate(e.ups):
         prev = e.dec[jj - 1][1] if jj > 0 else e.enc[e.L][1]
@@ -439,7 +425,7 @@ def test_parameter_gradients(run):
             acc = [a + b for a, b in zip(acc, p_)]
             del p_
         R.check_bound(G[up.wname], acc[0], acc[1], R.TAU_CONVT, f"{tag} up{jj}.up dW", key=f"{tag}-convT", weights=True)
-        if e.dec[jj][0].form_d.algo == 0:     # else from the dX statistics (test_backward_chain)
+        if e.dec[jj][0].plan.dgrad.algo == 0:     # else from the dX statistics (test_backward_chain)
             R.check_bound(G[up.bname], acc[2], acc[3], R.TAU_CONVT, f"{tag} up{jj}.up db", key=f"{tag}-convT", weights=True)
     last = e.dec[-1][1]
     dout = run.step._dout.double()

@@ -70,7 +70,7 @@ def test_config2_batch32_train_step_is_deterministic_and_forms_agree(monkeypatch
         m = make_model(st).train()
         step = TrainStep(m)
         loss = float(step(x, t))
-        forms = {u.form_f.algo for u in m._engine.units[1:]} | {u.form_d.algo for u in m._engine.units[1:]}
+        forms = {u.plan.fwd[True].algo for u in m._engine.units[1:]} | {u.plan.dgrad.algo for u in m._engine.units[1:]}
         if algo == "0":
             assert forms == {0}, forms
         elif w2d == "0":

@@ -298,11 +298,11 @@ def test_full_size_teacher_forced(case, monkeypatch):
     _, gx, _ = step(m, x, t, True)
     u = m._engine.enc[0][0]
     w = m.inc.double_conv[0].weight.detach()
-    assert u.fused_dw == case.startswith("fused")
+    assert u.plan.fused_dw == case.startswith("fused")
     worst = 0.0
     for i in range(0, n, 8):
         j = min(n, i + 8)
-        if u.fused_dw:   # from the engine's own dz (u.g: the apply pass was skipped) and BatchNorm coefficients
+        if u.plan.fused_dw:   # from the engine's own dz (u.g: the apply pass was skipped) and BatchNorm coefficients
             d, form = draw_ref(u.g[i:j], u.raw[i:j], u.scale, u.mean, u.invstd, u.c1, u.c2)
             ref, _ = R.conv3x3_dx(d, w.double())
             cond, _ = R.conv3x3_dx(form, w.double().abs())

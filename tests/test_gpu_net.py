@@ -313,10 +313,10 @@ def test_winograd_and_direct_forms_agree(monkeypatch):
         m.train()
         out = m(x=xd)
         mse_loss(out, td).backward()
-        forms = [u.form_f.algo for u in m._engine.units]
+        forms = [u.plan.fwd[True].algo for u in m._engine.units]
         if algo == "2":
             assert forms[0] == 1 and all(f == 2 for f in forms[1:]), forms
-            assert all(u.form_d.algo == 2 for u in m._engine.units[1:]), "dX launches too"
+            assert all(u.plan.dgrad.algo == 2 for u in m._engine.units[1:]), "dX launches too"
         else:
             assert all(f == int(algo) for f in forms), forms     # forcing a form includes the 3-channel first layer
         res[algo] = (out.detach().cpu().numpy(), {k: p.grad.detach().cpu().numpy() for k, p in m.named_parameters()})
@@ -420,7 +420,7 @@ def test_backward_teacher_forced_unit_by_unit(dims, h, w):
         assert np.allclose(invstd, 1.0 / np.sqrt(r64.var(axis=(0, 2, 3)) + 1e-5), rtol=1e-5), u.gname
         xhat = (r64 - mean[None, :, None, None]) * invstd[None, :, None, None]
         g = npy(u.g).astype(np.float64)
-        if u.pitched or u.fused_dw:
+        if u.plan.pitched or u.plan.fused_dw:
             # u.g still holds dz (the apply pass wrote d_raw out of place / the first layer's dW formed it on the fly)
             cnt = g.shape[0] * g.shape[2] * g.shape[3]
             dbeta, dgamma = g.sum(axis=(0, 2, 3)), (g * xhat).sum(axis=(0, 2, 3))
@@ -441,19 +441,19 @@ def test_backward_teacher_forced_unit_by_unit(dims, h, w):
         return np.where(act(u) > 0, da, 0).astype(np.float32)
 
     def dz_of(u):
-        assert u.pitched or u.fused_dw, "this check reads dz from u.g"
+        assert u.plan.pitched or u.plan.fused_dw, "this check reads dz from u.g"
         return npy(u.g)
 
     last = eng.dec[-1][1] if L_ > 0 else eng.enc[0][1]
     dout = 2.0 * (npy(out).astype(np.float64) - tgt) / out.numel()
     wout = st["outc.conv.weight"].reshape(1, -1, 1, 1).astype(np.float64)
-    if last.pitched:
+    if last.plan.pitched:
         close(dz_of(last), masked(last, dout * wout), 1e-5, "output conv dX + ReLU mask")
     close(G["outc.conv.bias"], dout.sum(axis=(0, 2, 3)), 1e-5, "outc bias grad")
     close(G["outc.conv.weight"].reshape(-1), (dout * act(last).astype(np.float64)).sum(axis=(0, 2, 3)), 1e-5, "outc weight grad")
     for pair in list(eng.enc) + list(eng.dec):      # second unit -> first unit of a DoubleConv
         u0, u1 = pair
-        if u0.pitched or u0.fused_dw:
+        if u0.plan.pitched or u0.plan.fused_dw:
             close(dz_of(u0), masked(u0, dx_of[id(u1)]), 1e-5, f"{u1.wname} dX into {u0.gname}")
     for lvl in range(1, L_ + 1):                     # first encoder unit of a level -> the pooled gradient
         close(npy(eng.dpooled[lvl]), dx_of[id(eng.enc[lvl][0])], 1e-5, f"dX into pooled[{lvl}]")
@@ -469,10 +469,10 @@ def test_backward_teacher_forced_unit_by_unit(dims, h, w):
         dxu, dwu, dbu = on.convT_bwd(act(prev), st[up.wname], npy(up.dout))
         close(G[up.wname], dwu, 5e-5, f"{up.wname} grad")
         close(G[up.bname], dbu, 1e-5, f"{up.bname} grad")
-        if prev.pitched:
+        if prev.plan.pitched:
             close(dz_of(prev), masked(prev, dxu), 1e-5, f"{up.wname} dX into {prev.gname}")
         # the skip unit's gradient: its slice of the decoder conv's dX + the max-pool routing of the level below
-        if skip.pitched:
+        if skip.plan.pitched:
             _, idx = on.maxpool2_fwd(act(skip))
             dpool = on.maxpool2_bwd(npy(eng.dpooled[lvl + 1]), idx, act(skip).shape)
             close(dz_of(skip), masked(skip, dcat[:, :skip.cout] + dpool), 1e-5, f"skip + pool gradient into {skip.gname}")
