@@ -640,12 +640,14 @@ static int conv_dense_impl(const gsd_nhwc* in, const void* wt, const gsd_nhwc* o
     GSD_REQUIRE(scatter_cs == 0 && bias == nullptr && out->H == H && out->W == W, GSD_ERR_BAD_ARG,
                 "gsd_bf16_conv_dense: fused BatchNorm backward needs plain output (no scatter, no bias) on the GEMM's pixel grid");
   }
-  if (ep_scale == nullptr && (partials == nullptr) == (bw == nullptr) && gsd_ctgemm_shape(in->N, H, W, K, M, ntaps, stride, scatter_cs)) {
-    // the transposed convolutions' forward and dX: the large-tile kernel (gsd_bf16_ctgemm.hip)
-    if (gsd_ctgemm_operands(in, out, bw, ntaps, ty, tx, H, W))
+  if (ep_scale == nullptr && gsd_ctgemm_shape(in->N, H, W, K, M, ntaps, stride, scatter_cs)) {
+    // the transposed convolutions' forward and dX: the large-tile kernel (gsd_bf16_ctgemm.hip), plain or with the fused statistics
+    if ((partials == nullptr) == (bw == nullptr) && gsd_ctgemm_operands(in, out, bw, ntaps, ty, tx, H, W))
       return gsd_ctgemm_launch(in, wt, out, K, M, ntaps, ty, tx, H, W, scatter_cs, oy, ox, bias, partials, bw, stream);
+    // whatever else asks for statistics at such a shape -- operands too large for 32-bit byte offsets, taps that leave the buffer,
+    // statistics without bw -- would get the general kernel's rows in a buffer sized for the large-tile kernel's
     GSD_REQUIRE(partials == nullptr, GSD_ERR_UNSUPPORTED,
-                "gsd_bf16_conv_dense: taps that leave the buffer with fused statistics (gsd_bf16_conv_dense_partial_rows counted the large-tile kernel's rows)");
+                "gsd_bf16_conv_dense: statistics at a large-tile shape that the large-tile kernel cannot serve (operands past 32-bit byte offsets, taps that leave the buffer, or no bw; gsd_bf16_conv_dense_partial_rows counted the large-tile kernel's rows)");
   }
   const Plan pl = make_plan(H, W, M);
   GConvP P = make_params(pl, in, wt, out, K, M, H, W, ntaps, stride, ty, tx, partials, bw, ep_scale, ep_shift);
@@ -662,6 +664,16 @@ static int conv_dense_impl(const gsd_nhwc* in, const void* wt, const gsd_nhwc* o
 extern "C" int gsd_bf16_conv_dense_partial_rows(int N, int H, int W, int K, int M, int ntaps, int stride) {
   if (gsd_ctgemm_shape(N, H, W, K, M, ntaps, stride, 0)) return gsd_ctgemm_partial_rows(N, H, W, M);
   return gsd_bf16_conv_partial_rows(N, H, W, M);
+}
+
+// What conv_dense_impl does with a plain-output launch that carries statistics (partials; y: bw->y or null), asked from extents and
+// pitches alone: 0 it is served; else the large-tile kernel's rows were counted and it cannot run (gsd_ctgemm_misfit's code, 5: no bw).
+extern "C" int gsd_bf16_conv_dense_fused_misfit(const gsd_nhwc* in, const gsd_nhwc* out, const gsd_nhwc* y, int K, int M, int ntaps, int stride,
+                                                const int* ty, const int* tx, int H, int W) {
+  if (in == nullptr || out == nullptr || ty == nullptr || tx == nullptr || ntaps < 1 || ntaps > 9) return 0;
+  if (!gsd_ctgemm_shape(in->N, H, W, K, M, ntaps, stride, 0)) return 0;
+  if (y == nullptr) return 5;   // statistics without bw: the large-tile kernel has no such form
+  return gsd_ctgemm_misfit(in, out, y, ntaps, ty, tx, H, W);
 }
 
 extern "C" int gsd_bf16_conv3x3(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, int K, int M, float* partials,

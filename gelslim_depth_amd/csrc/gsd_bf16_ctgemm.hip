@@ -409,18 +409,25 @@ int gsd_ctgemm_partial_rows(int N, int H, int W, int M) {
 }
 
 // the operand conditions of a shape gsd_ctgemm_shape accepted: 32-bit element offsets, the four taps are the 2 x 2 block at (oy, ox)
-// and stay inside the buffer (the kernel has no zero line), and the dX output buffer has exactly the GEMM's pixel grid
-bool gsd_ctgemm_operands(const gsd_nhwc* in, const gsd_nhwc* out, const gsd_bf16_bnbwd* bw, int ntaps, const int* ty, const int* tx, int H,
-                         int W) {
+// and stay inside the buffer (the kernel has no zero line), and the dX output buffer has exactly the GEMM's pixel grid.
+// gsd_ctgemm_misfit names the condition that fails: 0 none, 1 / 2 / 3 `in` / `out` / `y` too large for 32-bit byte offsets, 4 the taps
+// or the extents.  Reads extents and pitches only, never a pointer's target (gsd_bf16_conv_dense_fused_misfit asks without tensors).
+int gsd_ctgemm_misfit(const gsd_nhwc* in, const gsd_nhwc* out, const gsd_nhwc* y, int ntaps, const int* ty, const int* tx, int H, int W) {
   // 32-bit BYTE offsets per pixel, also for the (up to 512) pixel slots past the last item's end: (pixels + 512) * pitch * 2 < 2^32
   auto fits = [](const gsd_nhwc* t) { return ((long long)t->N * t->H * t->W + 512) * t->pitch < 2147483647LL; };
-  if (!fits(in) || !fits(out)) return false;
-  if (bw != nullptr && !fits(bw->y)) return false;
-  if (ntaps == 1) return ty[0] == 0 && tx[0] == 0 && in->H == H && in->W == W;
-  if (out->H != H || out->W != W) return false;   // the dX epilogue addresses out by the flattened pixel index: out is the pixel grid
+  if (!fits(in)) return 1;
+  if (!fits(out)) return 2;
+  if (y != nullptr && !fits(y)) return 3;
+  if (ntaps == 1) return ty[0] == 0 && tx[0] == 0 && in->H == H && in->W == W ? 0 : 4;
+  if (out->H != H || out->W != W) return 4;   // the dX epilogue addresses out by the flattened pixel index: out is the pixel grid
   const int oy = ty[0], ox = tx[0];
-  if (oy < 0 || ox < 0 || ty[1] != oy || tx[1] != ox + 1 || ty[2] != oy + 1 || tx[2] != ox || ty[3] != oy + 1 || tx[3] != ox + 1) return false;
-  return 2 * (H - 1) + oy + 1 < in->H && 2 * (W - 1) + ox + 1 < in->W;
+  if (oy < 0 || ox < 0 || ty[1] != oy || tx[1] != ox + 1 || ty[2] != oy + 1 || tx[2] != ox || ty[3] != oy + 1 || tx[3] != ox + 1) return 4;
+  return 2 * (H - 1) + oy + 1 < in->H && 2 * (W - 1) + ox + 1 < in->W ? 0 : 4;
+}
+
+bool gsd_ctgemm_operands(const gsd_nhwc* in, const gsd_nhwc* out, const gsd_bf16_bnbwd* bw, int ntaps, const int* ty, const int* tx, int H,
+                         int W) {
+  return gsd_ctgemm_misfit(in, out, bw != nullptr ? bw->y : nullptr, ntaps, ty, tx, H, W) == 0;
 }
 
 int gsd_ctgemm_launch(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, int K, int M, int ntaps, const int* ty, const int* tx, int H,

@@ -11,6 +11,7 @@
 bool gsd_ctgemm_shape(int N, int H, int W, int K, int M, int ntaps, int stride, int scatter_cs);
 bool gsd_ctgemm_operands(const gsd_nhwc* in, const gsd_nhwc* out, const gsd_bf16_bnbwd* bw, int ntaps, const int* ty, const int* tx, int H,
                          int W);
+int gsd_ctgemm_misfit(const gsd_nhwc* in, const gsd_nhwc* out, const gsd_nhwc* y, int ntaps, const int* ty, const int* tx, int H, int W);
 int gsd_ctgemm_partial_rows(int N, int H, int W, int M);
 int gsd_ctgemm_launch(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, int K, int M, int ntaps, const int* ty, const int* tx, int H,
                       int W, int scatter_cs, int oy, int ox, const float* bias, float* partials, const gsd_bf16_bnbwd* bw, void* stream);

@@ -72,12 +72,60 @@ class UNetEngineBF16(EngineBase):
     # in one process) re-sizes the buffers instead of overrunning them
     _SIZING_ENV = ("GSD_BF16_BN_BLOCKS", "GSD_BF16_CTGEMM", "GSD_BF16_CT_BM", "GSD_BF16_TW", "GSD_BF16_XCD")
 
+    # ------------------------------------------------------------------ pre-flight
+    _OPERANDS = {1: "in (the gradient slice of the concat buffer)", 2: "out (the gradient of the unit below)",
+                 3: "bw.y (the raw output of the unit below)"}
+
+    def _train_misfit(self, n: int, h: int, w: int):
+        """The first transposed convolution whose dX launch with fused BatchNorm statistics the library would refuse at batch n
+        (gsd_bf16_conv_dense_fused_misfit over the extents and pitches _ensure would allocate), as (up, level, code, pixels, pitch),
+        or None.  No tensor, no device."""
+        hs, ws = [h], [w]
+        for _ in range(self.L):
+            hs.append(hs[-1] // 2)
+            ws.append(ws[-1] // 2)
+
+        def nhwc(h_, w_, c, pitch):
+            t = L.gsd_nhwc()
+            t.ptr, t.pitch, t.N, t.H, t.W, t.C = 16, pitch, n, h_, w_, c     # (the query reads no pointer)
+            return t
+        for j, up in enumerate(self.ups):
+            lvl = self.L - 1 - j
+            hi, wi = hs[lvl + 1], ws[lvl + 1]
+            oy, ox = (hs[lvl] - 2 * hi) // 2, (ws[lvl] - 2 * wi) // 2
+            ops = (nhwc(hs[lvl], ws[lvl], up.cout, self.dims[lvl] + up.cout), nhwc(hi, wi, up.cin, up.cin), nhwc(hi, wi, up.cin, up.cin))
+            code = lib.gsd_bf16_conv_dense_fused_misfit(C.byref(ops[0]), C.byref(ops[1]), C.byref(ops[2]), up.cout, up.cin, 4, 2,
+                                                        L.int_array([oy, oy, oy + 1, oy + 1]), L.int_array([ox, ox + 1, ox, ox + 1]), hi, wi)
+            if code:
+                t = ops[min(code, 3) - 1]
+                return up, lvl, code, t.H * t.W, t.pitch
+        return None
+
+    def preflight(self, n: int, h: int, w: int) -> None:
+        """Refuse a train-capable (n, h, w) the backward could not finish, before anything is launched or allocated: the last
+        ConvT dX of a step carries the BatchNorm-backward statistics on the large-tile kernel, whose 32-bit byte offsets hold
+        (N*H*W + 512) * pitch < 2^31 - 1 elements per operand -- batch 123 at 320x427 with the default dims does not fit, and
+        the library would say so only inside backward(), after the forward had updated every running statistic."""
+        bad = self._train_misfit(n, h, w)
+        if bad is None:
+            return
+        up, lvl, code, pixels, pitch = bad
+        lo = n - 1                      # (a scan, not a bisection: past 2^24 pixels a level leaves the large tile and is served again)
+        while lo > 0 and self._train_misfit(lo, h, w) is not None:
+            lo -= 1
+        what = self._OPERANDS.get(code, "the taps of the gradient slice")
+        raise L.GsdError(f"bf16 train step at batch {n}, {h}x{w}: the dX of {up.wname} (level {lvl}) carries fused BatchNorm statistics "
+                         f"and its operand {what}, {n} x {pixels} pixels at pitch {pitch}, exceeds the large-tile kernel's limit "
+                         f"(N*H*W + 512) * pitch < 2^31 - 1 elements; the largest batch that fits is {lo}")
+
     def _ensure(self, n: int, h: int, w: int, dev: torch.device, train: bool) -> None:
         key = (n, h, w, str(dev), self._env_key(), train)
         if self._shape == key:
             return
         if self._shape is not None and self._shape[:5] == key[:5] and not train:
             return                      # eval after train at the same shape: everything needed exists
+        if train:
+            self.preflight(n, h, w)     # raises before a buffer, a launch or the shape key has changed
         self.buffers_made += 1          # past the early returns: the concat buffers, partials and the rest are re-made below
         self._shape = key
         hs, ws = self._set_pyramid(h, w)

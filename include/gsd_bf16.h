@@ -17,7 +17,14 @@ extern "C" {
 #endif
 
 /* A bf16 NHWC tensor, possibly a channel slice of a wider buffer: element (n,h,w,c) lives at
- * ptr + (((n*H + h)*W + w) * pitch + c).  ptr 16-byte aligned, pitch a multiple of 8. */
+ * ptr + (((n*H + h)*W + w) * pitch + c).  ptr 16-byte aligned, pitch a multiple of 8.
+ *
+ * Addressing limits.  Every entry point checks its gsd_nhwc operands before anything is launched:
+ *   GSD_ERR_BAD_ARG      null tensor, a dimension <= 0, pitch < C
+ *   GSD_ERR_UNSUPPORTED  "base must be 16-byte aligned and pitch a multiple of 8 elements"
+ *   GSD_ERR_UNSUPPORTED  "one image exceeds 2^31 elements": H*W*pitch >= 2^31 - 1 (offsets inside an image are 32-bit)
+ * The whole tensor N*H*W*pitch may be of any size: image bases and pixel * pitch are formed in 64 bits.  What an entry point
+ * asks beyond that is stated with it below; all of it is refused before the first launch, with nothing written. */
 typedef struct {
   void* ptr;
   int64_t pitch;   /* elements from one pixel to the next (>= C) */
@@ -43,7 +50,10 @@ int gsd_bf16_conv_mpad(int M);
  *   out[n,h,w,m] = sum_{t,k} in[n,h+t/3-1,w+t%3-1,k] * wt[t][m][k];  wt: [9][mpad(M)][K] bf16, K % 32 == 0, M % 16 == 0.
  * partials (or NULL): BatchNorm partial sums of the STORED (rounded) values, one row of 2*mpad(M) floats per (persistent
  * block, wave): gsd_bf16_conv_partial_rows rows (a few hundred, it depends on the device's CU count), to be reduced
- * with gsd_bn_reduce_partials(partials, rows, mpad(M), M, ...) from gsd.h. */
+ * with gsd_bn_reduce_partials(partials, rows, mpad(M), M, ...) from gsd.h.
+ * Limits: fewer than 2^31 work items (GSD_ERR_UNSUPPORTED "work items out of range").  While one input image and the weight
+ * image stay below 2^31 BYTES the halo fills go through buffer descriptors; an input image of 2^30 elements or more (up to
+ * the 2^31 of gsd_nhwc) is filled through per-lane 64-bit addresses instead -- the same values, another fill path. */
 int gsd_bf16_conv_partial_rows(int N, int H, int W, int M);
 int gsd_bf16_conv3x3(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, int K, int M, float* partials,
                      const gsd_bf16_bnbwd* bw, void* stream);
@@ -70,8 +80,19 @@ int gsd_bf16_conv_dense(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out,
 /* BatchNorm partial rows a gsd_bf16_conv_dense launch of this shape writes (plain output, scatter_cs == 0): the transposed
  * convolutions' shapes (4 taps at stride 2, K % 64 == 0, M == 128 or M % 256 == 0) run on a large-tile kernel with its own
  * row count (csrc/gsd_bf16_ctgemm.hip; GSD_BF16_CTGEMM=0 keeps them on the general kernel), everything else writes
- * gsd_bf16_conv_partial_rows(N, H, W, M) rows. */
+ * gsd_bf16_conv_partial_rows(N, H, W, M) rows.
+ * Limits of gsd_bf16_conv_dense: H < 65536 and W < 4096 (GSD_ERR_BAD_ARG "bad grid"), fewer than 2^31 work items.  The
+ * large-tile kernel addresses each operand by 32-bit byte offsets from its base: it serves a launch only while
+ * (N*H*W + 512) * pitch < 2^31 - 1 elements holds for in, out and bw->y (extents and pitch of each operand's own buffer) and
+ * the four taps stay inside in.  Otherwise a launch WITHOUT statistics runs on the general kernel (same values); one WITH
+ * statistics at such a shape is refused, GSD_ERR_UNSUPPORTED "... (gsd_bf16_conv_dense_partial_rows counted the large-tile
+ * kernel's rows)", because the caller sized `partials` for the other kernel -- so too statistics without bw, which the
+ * large-tile kernel does not form.  gsd_bf16_conv_dense_fused_misfit answers that in advance from extents and pitches alone
+ * (the ptr fields are not read; y: bw->y or NULL): 0 the launch with statistics is served, 1 / 2 / 3 in / out / y is too
+ * large, 4 the taps or extents keep it off the large tile, 5 no bw. */
 int gsd_bf16_conv_dense_partial_rows(int N, int H, int W, int K, int M, int ntaps, int stride);
+int gsd_bf16_conv_dense_fused_misfit(const gsd_nhwc* in, const gsd_nhwc* out, const gsd_nhwc* y, int K, int M, int ntaps,
+                                     int stride, const int* ty, const int* tx, int H, int W);
 
 /* ---- weight images (fp32 master -> bf16 GEMM layout [T][mpad(M)][round_up(K,32)], zero padded) ---------------------
  * mode 0 conv3x3 forward  from (Cout,Cin,3,3):  [t][co][ci]
@@ -82,7 +103,8 @@ int gsd_bf16_conv_dense_partial_rows(int N, int H, int W, int K, int M, int ntap
 int64_t gsd_bf16_weight_image_size(int mode, int Cout, int Cin);
 int gsd_bf16_weight_image(int mode, const float* w, int Cout, int Cin, void* out, void* stream);
 /* n images in one launch per 32 jobs (a train step wants 43: as separate launches between the convolutions they are pure
- * latency); same values as gsd_bf16_weight_image job by job.  `jobs` is a host array. */
+ * latency); same values as gsd_bf16_weight_image job by job.  `jobs` is a host array.
+ * Limit: mpad(M) * round_up(K,32) of one image below 2^31 - 1 (GSD_ERR_UNSUPPORTED "image %d too large"). */
 typedef struct gsd_bf16_wimg_job {
   const float* w;   /* fp32 master weights */
   void* out;        /* gsd_bf16_weight_image_size(mode, Cout, Cin) bf16 elements */
@@ -146,7 +168,10 @@ int gsd_bf16_wgrad_first_recompute(const float* x, int N, int C, int H, int W, c
  * kernel that loads its 72 KiB of weights once per CU and fills the whole 64-channel halo of a pixel tile by one LDS-DMA fill
  * under the previous tile's epilogue: no operand fill and no barrier inside the K loop.  Same products in the same order as
  * gsd_bf16_conv3x3 (outputs bit-identical); `wt`, `partials` (gsd_bf16_conv3x3_c64_partial_rows rows of 2*gsd_bf16_conv_mpad(64)
- * floats, one per block; NULL: a plain convolution) and `bw` as there. */
+ * floats, one per block; NULL: a plain convolution) and `bw` as there.
+ * Limits: one input image below 2^30 elements (its fills use 32-bit byte offsets; GSD_ERR_UNSUPPORTED "one input image exceeds
+ * 2 GiB" -- gsd_bf16_conv3x3 serves such an image), fewer than 2^31 tiles ("too many tiles"; so too gsd_bf16_conv3x3_first,
+ * gsd_bf16_inc_conv, gsd_bf16_first_bn_bwd_reduce and gsd_bf16_wgrad_first). */
 int gsd_bf16_conv3x3_c64_supported(int K, int M);
 int gsd_bf16_conv3x3_c64_partial_rows(int N, int H, int W);
 int gsd_bf16_conv3x3_c64(const gsd_nhwc* in, const void* wt, const gsd_nhwc* out, float* partials, const gsd_bf16_bnbwd* bw,
@@ -224,7 +249,11 @@ int gsd_bf16_convT_bias_grad(const float* partials, int rows, int ld, int col0, 
  * first layer:              a = dy, b = im2col'd input, 1 tap, ncols_out = 9*Cin -> dw == dW (Cout,Cin,3,3)
  * ConvTranspose2d (unet.py:36): a = x, b = gradient of its (padded) output slice, taps (kh+oy, kw+ox) at stride 2
  *                                                                               -> dw == dW (Cin,Cout,2,2)
- * workspace: gsd_bf16_wgrad_workspace(ntaps, N, H, W, a->C, b->C) floats (split-K slabs, summed in a fixed order). */
+ * workspace: gsd_bf16_wgrad_workspace(ntaps, N, H, W, a->C, b->C) floats (split-K slabs, summed in a fixed order).
+ * Limits: a->H < 32768 and a->W < 4096 (GSD_ERR_UNSUPPORTED "extent too large").  The large-tile form (4 taps at stride 2,
+ * M % 128 == 0, Ncols % 64 == 0, every tap inside b) runs only while N*H*W*pitch < 2^31 - 1 elements for a and for b (32-bit
+ * element offsets from the base); past that the general kernel computes the same dW in another summation order.  The general
+ * kernel needs one image of a and of b below 2^30 elements (GSD_ERR_UNSUPPORTED "one image of an operand exceeds 2 GiB"). */
 int64_t gsd_bf16_wgrad_workspace(int ntaps, int N, int H, int W, int M, int Ncols);
 int gsd_bf16_wgrad(const gsd_nhwc* a, const gsd_nhwc* b, int ntaps, int stride, const int* ty, const int* tx, float* dw,
                    int ncols_out, float* workspace, int64_t workspace_elems, void* stream);

@@ -43,6 +43,25 @@ def test_struct_layout_matches_header():
     assert ctypes.sizeof(_lib.gsd_bf16_wimg_job) == 8 + 8 + 4 * 4 and _lib.gsd_bf16_wimg_job.mode.offset == 16
 
 
+def test_bf16_conv_dense_fused_misfit_is_a_host_query_over_extents_and_pitches():
+    """gsd_bf16_conv_dense_fused_misfit(in, out, y, K, M, ntaps, stride, ty, tx, H, W): no pointer of the three gsd_nhwc is read (they
+    are NULL here), the codes are the header's, and anything that is no large-tile shape is served whatever its size."""
+    from gelslim_depth_amd import _lib
+
+    def t(n, h, w, c, pitch):
+        d = _lib.gsd_nhwc()
+        d.ptr, d.pitch, d.N, d.H, d.W, d.C = None, pitch, n, h, w, c
+        return d
+    ty, tx = _lib.int_array([0, 0, 1, 1]), _lib.int_array([1, 2, 1, 2])
+    q = _lib.lib.gsd_bf16_conv_dense_fused_misfit
+    ask = lambda n, pin=128, pout=128, py=128, h=160, w=213, y=True: q(ctypes.byref(t(n, 320, 427, 64, pin)), ctypes.byref(t(n, h, w, 128, pout)),      # noqa: E731
+                                                                        ctypes.byref(t(n, h, w, 128, py)) if y else None, 64, 128, 4, 2, ty, tx, h, w)
+    assert (ask(122), ask(123), ask(16, pout=1 << 20), ask(16, py=1 << 20), ask(16, y=False)) == (0, 1, 2, 3, 5)
+    assert ask(16, h=161) == 4                      # the last taps leave the 320-row gradient buffer
+    assert ask(500) == 0                            # 2^24 pixels or more: no large-tile shape, the general kernel's rows are counted
+    assert q(ctypes.byref(t(123, 320, 427, 64, 128)), ctypes.byref(t(123, 160, 213, 128, 128)), None, 64, 128, 1, 1, ty, tx, 160, 213) == 0
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(REPO, "gelslim_depth_amd")
     for root, _, files in os.walk(pkg):
