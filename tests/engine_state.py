@@ -171,8 +171,17 @@ def rich_step_kwargs():
                 max_grad_norm=0.05, lr_schedule=LRSchedule(warmup_steps=2, decay="cosine", total_steps=8), nan_policy="skip")
 
 
-def train_steps(case, k=2, rich=False, hook=None):
-    """k TrainStep steps on one batch.  hook(model, step, i): called in front of step i (the mutation tests)."""
+def on_device(results):
+    """{name: tensor} -> on-device clones taken on the current stream, as an optimiser or a caller would read the results: nothing
+    here waits for the device, so a result that another stream has not finished is cloned as it stands."""
+    return {k: None if v is None else v.detach().clone() for k, v in results.items()}
+
+
+def train_steps(case, k=2, rich=False, hook=None, consume=False):
+    """k TrainStep steps on one batch.  hook(model, step, i): called in front of step i (the mutation tests).
+    consume: nothing synchronises with the device until every result has been cloned on the current stream right behind the
+    last step (the per-step loss and clip tensors right behind their step); the host snapshots are made of those clones.  The
+    plain form's device-wide synchronise in front of its snapshots would hide a join that is missing at the end of backward."""
     import torch
     from gelslim_depth_amd.train import TrainStep
     with environ(case.env):
@@ -180,16 +189,28 @@ def train_steps(case, k=2, rich=False, hook=None):
         step = TrainStep(m, **(rich_step_kwargs() if rich else {}))
         x, t = make_batch(case.n, case.h, case.w, n_classes=case.n_classes)
         res = {}
+        keep = on_device if consume else (lambda d: {k_: snap(v) for k_, v in d.items()})
         for i in range(k):
             if hook is not None:
                 hook(m, step, i)
             loss = step(x, t)
-            res[f"loss.{i}"] = snap(loss)
+            per_step = {f"loss.{i}": loss}
             if step.last_grad_norm is not None:
-                res[f"grad_norm.{i}"] = snap(step.last_grad_norm)
-                res[f"clip_coef.{i}"] = snap(step.last_clip_coef)
+                per_step[f"grad_norm.{i}"] = step.last_grad_norm
+                per_step[f"clip_coef.{i}"] = step.last_clip_coef
             if step.last_loss_terms is not None:
-                res[f"loss_terms.{i}"] = snap(step.last_loss_terms)
+                per_step[f"loss_terms.{i}"] = step.last_loss_terms
+            res.update(keep(per_step))
+        if consume:
+            arenas = {"out": step._out, "g_flat": step.g_flat, "p_flat": step.p_flat, "m_flat": step.m_flat, "v_flat": step.v_flat}
+            if step.ema_flat is not None:
+                arenas["ema_flat"] = step.ema_flat
+            arenas.update({"buf." + k_: b for k_, b in m.named_buffers()})
+            res.update(on_device(arenas))
+            torch.cuda.synchronize()
+            res = {k_: snap(v) for k_, v in res.items()}
+            res["skipped_steps"] = step.skipped_steps()
+            return res, m._engine
         torch.cuda.synchronize()
         res["out"] = snap(step._out)
         res["g_flat"] = snap(step.g_flat)
@@ -197,8 +218,10 @@ def train_steps(case, k=2, rich=False, hook=None):
         return res, m._engine
 
 
-def autograd_step(case):
-    """model(x) in train mode and backward through torch's autograd, with the input's gradient where the engine has one (fp32)."""
+def autograd_step(case, consume=False):
+    """model(x) in train mode and backward through torch's autograd, with the input's gradient where the engine has one (fp32).
+    consume: as in train_steps -- out, every p.grad, x.grad and the BatchNorm buffers are cloned on the current stream right behind
+    backward(), in front of the first synchronise."""
     import torch
     with environ(case.env):
         m = make_model(case.precision, case.dims, case.n_classes)
@@ -206,6 +229,15 @@ def autograd_step(case):
         x.requires_grad_(case.precision == "fp32")
         out = m(x)
         (out * t).sum().backward()
+        if consume:
+            res = {"out": out}
+            res.update({"grad." + k: p.grad for k, p in m.named_parameters()})
+            if x.grad is not None:
+                res["x.grad"] = x.grad
+            res.update({"buf." + k: b for k, b in m.named_buffers()})
+            res = on_device(res)
+            torch.cuda.synchronize()
+            return {k: snap(v) for k, v in res.items()}, m._engine
         torch.cuda.synchronize()
         res = {"out": snap(out)}
         res.update({"grad." + k: snap(p.grad) for k, p in m.named_parameters()})
@@ -240,6 +272,10 @@ def graphed_forward(case):
         return {"out": out}, m._engine
 
 
+# the workloads of test_gpu_stream_order.py: three steps, so that a buffer left in use by one step meets the next one
+CONSUMING = {"train_steps": lambda case, hook=None: train_steps(case, k=3, hook=hook, consume=True),
+             "train_steps_rich": lambda case, hook=None: train_steps(case, k=3, rich=True, hook=hook, consume=True),
+             "autograd_step": lambda case, hook=None: autograd_step(case, consume=True)}
 WORKLOADS = {"train_steps": train_steps, "train_steps_rich": lambda case: train_steps(case, rich=True),
              "autograd_step": autograd_step, "eval_forward": eval_forward, "graphed_forward": graphed_forward}
 

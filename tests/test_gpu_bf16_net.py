@@ -253,7 +253,8 @@ def _bf16_step_state(dims, monkeypatch, env, steps=2, n=3, h=37, w=53, cin=3):
 def test_bf16_side_stream_weight_gradients_change_nothing(dims, monkeypatch):
     """GSD_BF16_SIDE_DW (default on) moves the weight-gradient launches to a side stream; every kernel is deterministic, so a
     missing stream dependency is the only way the two schedules can differ: gradients, parameters and BatchNorm buffers after
-    two steps must be bit-equal."""
+    two steps must be bit-equal.  Both schedules run undisturbed here, so a missing dependency shows only when the GPU happens to
+    run the streams in an unlucky order; test_gpu_stream_order.py makes one stream late on purpose and holds the enforced order."""
     e0, l0, g0, p0, b0 = _bf16_step_state(dims, monkeypatch, {"GSD_BF16_SIDE_DW": "0"})
     e1, l1, g1, p1, b1 = _bf16_step_state(dims, monkeypatch, {"GSD_BF16_SIDE_DW": "1"})
     assert not e0.side_dw and e1.side_dw

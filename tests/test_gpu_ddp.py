@@ -121,33 +121,51 @@ def test_two_rank_bf16_syncbn_matches_single_process_global_batch(tmp_path):
             assert rel_l1(res[0]["buf/" + k], v.cpu().numpy()) < 1e-3, k
 
 
-@pytest.mark.parametrize("precision", ["fp32", "bf16"])
-def test_one_rank_rccl_step_is_bit_equal(tmp_path, precision):
+@pytest.mark.parametrize("precision,policy", [("fp32", None), ("bf16", None), ("fp32", "side_late"), ("bf16", "side_late")],
+                         ids=["fp32", "bf16", "fp32-side_late", "bf16-side_late"])
+def test_one_rank_rccl_step_is_bit_equal(tmp_path, precision, policy):
     """The RCCL path on hardware (the GPU box has one card, so one rank): backend "nccl", collectives forced on.  Three
-    steps with bucketed async all-reduce + SyncBN + guard exchange == three steps without a process group, bit for bit."""
+    steps with bucketed async all-reduce + SyncBN + guard exchange == three steps without a process group, bit for bit.
+    side_late: the worker's steps run under stream_delays.delays -- at every fork the weight gradients and the buckets' all-reduces
+    start late by twice a step of the run without a process group, which is then the one-stream schedule, unperturbed
+    (test_gpu_stream_order.py has the rule and the proof that such a delay is long enough)."""
     import socket
     import torch
+    import engine_state
+    import stream_delays
     from gelslim_depth_amd.models.unet import UNet
     from gelslim_depth_amd.train import TrainStep
+    dims = [16, 32, 64] if precision == "fp32" else [32, 64, 128]
+    st = synth.make_state(3, 1, dims, 5, "conditioned")
+    x, t = synth.make_batch(3, 37, 53, 6)
+    marks, losses = [], []
+    with engine_state.environ({} if policy is None else {"GSD_SIDE_DW": "0", "GSD_BF16_SIDE_DW": "0"}):
+        m = UNet(n_channels=3, n_classes=1, layer_dimensions=dims, precision=precision)
+        m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in st.items()}, strict=True)
+        m = m.to("cuda").train()
+        step = TrainStep(m)
+        xd, td = torch.from_numpy(x).cuda(), torch.from_numpy(t).cuda()
+        for _ in range(3):
+            marks.append(torch.cuda.current_stream().record_event(torch.cuda.Event(enable_timing=True)))
+            losses.append(float(step(xd, td).item()))
+    assert (m._engine.side is None) == (policy is not None)
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(REPO, "tests", "nccl_worker.py"), str(tmp_path), precision, str(port)]
+    if policy is not None:
+        cmd += [policy, repr(stream_delays.delay_for(marks[1].elapsed_time(marks[2])))]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     res = dict(np.load(os.path.join(tmp_path, "nccl.npz")))
     assert int(res["world"]) == 1 and str(res["backend"]) == "nccl" and int(res["skipped"]) == 0
-    dims = [16, 32, 64] if precision == "fp32" else [32, 64, 128]
-    st = synth.make_state(3, 1, dims, 5, "conditioned")
-    x, t = synth.make_batch(3, 37, 53, 6)
-    m = UNet(n_channels=3, n_classes=1, layer_dimensions=dims, precision=precision)
-    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in st.items()}, strict=True)
-    m = m.to("cuda").train()
-    step = TrainStep(m)
-    xd, td = torch.from_numpy(x).cuda(), torch.from_numpy(t).cuda()
-    losses = [float(step(xd, td).item()) for _ in range(3)]
+    if policy is None:
+        assert list(res["delayed"]) == [0, 0]
+    else:       # per step: one fork onto the side stream for every weight-gradient launch, one onto the hand-off stream per bucket
+        assert res["delayed"][0] >= 3 and res["delayed"][1] == 3 * (2 * len(dims) - 1), res["delayed"]
+        assert bool(res["apart"]), "the worker found no streams on hardware queues of their own: its delays made nothing late"
     assert np.array_equal(np.array(losses), res["losses"])
     assert np.array_equal(step.g_flat.cpu().numpy(), res["g"])
     assert np.array_equal(step.p_flat.cpu().numpy(), res["p"])

@@ -331,7 +331,9 @@ def test_winograd_and_direct_forms_agree(monkeypatch):
 def test_side_stream_weight_gradients_are_bit_identical(monkeypatch, dims, n, h, w):
     """The weight-gradient launches run on a side stream next to the dX chain (engine_base.py: _on_side; two d_raw scratch buffers used
     in turn).  Same kernels on the same operands: every gradient must equal the single-stream schedule's bit for bit, over several
-    steps (a missing dependency between the streams shows up as a difference here)."""
+    steps.  Both schedules run undisturbed here: a missing dependency between the streams shows only if the GPU happens to run them
+    in an unlucky order, which at these shapes it rarely does.  test_gpu_stream_order.py makes one stream late on purpose and holds
+    the enforced order."""
     from gelslim_depth_amd.train import mse_loss
     st = synth.make_state(3, 1, dims, 5, "conditioned")
     x, tgt = synth.make_batch(n, h, w, 6)
