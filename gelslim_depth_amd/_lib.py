@@ -159,6 +159,11 @@ SIGNATURES = {
     "gsd_conv3x3_w43_estimate_us": (C.c_double, [_I, _I, _I, _I, _I, _I]),
     "gsd_conv3x3_w2d_partial_rows": (_I, [_I, _I, _I, _I]),
     "gsd_conv3x3_w2d_mfma_count": (C.c_int64, [_I, _I, _I, _I, _I]),
+    "gsd_conv3x3_w2d_source_class": (_I, [_SRC, _I]),
+    "gsd_conv3x3_w2d_strips_scratch": (_L, [_I, _I, _I, _I, _I]),
+    "gsd_conv3x3_w2d_mfma_count_class": (C.c_int64, [_I, _I, _I, _I, _I, _I, _I]),
+    "gsd_conv3x3_w2d_strips_plan": (_I, [_I, _I, _I, _I, _I, _IP]),
+    "gsd_conv3x3_w2d_strips_tile": (_I, [_I, _I, _I, _I, _IP]),
     "gsd_conv3x3_w2d": (_I, [_SRC, _I, _P, _I, _I, _DST, _I, _P, _I, _I, _I, _P]),
     "gsd_conv3x3_w2d_dgrad_bnrelu": (_I, [_SRC, _P, _I, _I, _DST, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "gsd_conv3x3_w2d_estimate_slabs_us": (C.c_double, [_I, _I, _I, _I, _I]),

@@ -74,16 +74,12 @@ static inline void conv3_fill_common(Params& P, const gsd_src* src, int nsrc, co
 // plane stride PS, both in floats: the sum over the block's `groups` groups of 16 tiles of the LDS cycles per read pair.  Lane ->
 // tile as in the kernels: tile q = 16 group + (lane & 15) sits TWq to a tile row, tile rows are row_step window rows apart (1: the
 // row form, 2: the two-dimensional form), channel plane lane >> 4; `off` shifts every address (the read offset of the 16-byte fills).
-static inline int conv3_halo_read_cycles(int groups, int row_step, int TWq, int LP, int PS, int off) {
+// (conv3_read_cycles: the same count for one wave whose lanes read at the given float addresses -- any lane -> tile map)
+static inline int conv3_read_cycles(const int (&addr)[64]) {
   static const int g128[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
                                   {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
   int total = 0;
-  for (int grp = 0; grp < groups; ++grp) {
-    int addr[64];
-    for (int lane = 0; lane < 64; ++lane) {
-      const int q = grp * 16 + (lane & 15);
-      addr[lane] = (lane >> 4) * PS + row_step * (q / TWq) * LP + 4 * (q % TWq) + off;
-    }
+  {
     for (int half = 0; half < 2; ++half) {
       for (int g = 0; g < 2; ++g) {   // ds_read_b128: 16-lane groups, 16 slots of 16 B
         int worst = 0;
@@ -114,6 +110,18 @@ static inline int conv3_halo_read_cycles(int groups, int row_step, int TWq, int 
       }
       total += worst;
     }
+  }
+  return total;
+}
+static inline int conv3_halo_read_cycles(int groups, int row_step, int TWq, int LP, int PS, int off) {
+  int total = 0;
+  for (int grp = 0; grp < groups; ++grp) {
+    int addr[64];
+    for (int lane = 0; lane < 64; ++lane) {
+      const int q = grp * 16 + (lane & 15);
+      addr[lane] = (lane >> 4) * PS + row_step * (q / TWq) * LP + 4 * (q % TWq) + off;
+    }
+    total += conv3_read_cycles(addr);
   }
   return total;
 }

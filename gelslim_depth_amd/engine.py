@@ -150,6 +150,16 @@ class UNetEngine(EngineBase):
         self._set_pyramid(h, w)
         self._allocate(dev, train)
 
+    @staticmethod
+    def _strips_scratch(u: "_Unit", n: int, lh: int, lw: int) -> int:
+        """Floats of conv_ws the train-mode forward and dX launches of unit u want for the strip list's statistics (0: rectangles)."""
+        need = 0
+        if u.plan.fwd[True].algo == 2:
+            need = lib.gsd_conv3x3_w2d_strips_scratch(n, lh, lw, u.cin, u.cout)
+        if u.plan.dgrad is not None and u.plan.dgrad.algo == 2:
+            need = max(need, lib.gsd_conv3x3_w2d_strips_scratch(n, lh, lw, u.cout, u.cin))
+        return int(need)
+
     def _allocate(self, dev: torch.device, train: bool) -> None:
         """self.plan's sizes and flags as tensors and streams; train: also what a backward needs."""
         plan, size = self.plan, self.plan.sizes[train]
@@ -198,7 +208,9 @@ class UNetEngine(EngineBase):
         self.gp_turn = 0
         self.gp_free: List[Optional[torch.cuda.Event]] = [None, None]   # recorded on the side stream behind a buffer's last reader
         self.partials = torch.empty((size.partials,), **f32)
-        self.conv_ws = torch.empty((size.conv_ws,), **f32) if size.conv_ws else None
+        # K-slab scratch; an unsplit deep-level launch on the strip list leaves its per-tile statistics there (never both at once)
+        conv_ws = max([size.conv_ws] + ([self._strips_scratch(u, n, hs[u.level], ws[u.level]) for u in self.units] if train else []))
+        self.conv_ws = torch.empty((conv_ws,), **f32) if conv_ws else None
         self.db_sums = torch.empty((size.db_sums,), device=dev, dtype=torch.float64) if train else None
         self.wgrad_ws = torch.empty((size.wgrad_ws,), **f32) if train else None
         self.wgrad_ws_side = torch.empty((size.wgrad_ws_side,), **f32) if side else None
@@ -243,7 +255,7 @@ class UNetEngine(EngineBase):
         ev = self._log_begin()
         check(_FORMS[form.algo].run(self.conv_ws if train else None, arr, len(srcs), u.wt_f.data_ptr(), u.cin, u.cout, dst, 1, part,
                                     n, lh, lw, st), "conv3x3")
-        self._log_end(ev, u.cout, u.cin, n, lh, lw, form.algo)
+        self._log_end(ev, u.cout, u.cin, n, lh, lw, form.algo, arr, len(srcs), train)
         if train:
             rows = form.partial_rows
             self._bn_stats(u, rows, _r64(u.cout), float(n * lh * lw), P, st,
@@ -263,15 +275,18 @@ class UNetEngine(EngineBase):
             return None
         return self._event()
 
-    def _log_end(self, ev, m: int, k_ch: int, n: int, lh: int, lw: int, algo: int = 0) -> None:
-        """(kernel, ALGORITHMIC flops of the convolution = 2*9*M*K*pixels, events, shape, flops the MFMAs executed)."""
+    def _log_end(self, ev, m: int, k_ch: int, n: int, lh: int, lw: int, algo: int = 0, src=None, nsrc: int = 0,
+                 with_ws: bool = True) -> None:
+        """(kernel, ALGORITHMIC flops of the convolution = 2*9*M*K*pixels, events, shape, flops the MFMAs executed).
+        src, nsrc: the launch's sources -- their class decides whether a two-dimensional Winograd launch ran the strip list."""
         if ev is None or self.kernel_log is None:
             return
         e = self._event()
         flops = 2.0 * m * k_ch * 9 * n * lh * lw
         if algo == 2:
             variant = "conv3x3_w2d_kernel"
-            executed = 2048.0 * lib.gsd_conv3x3_w2d_mfma_count(n, lh, lw, k_ch, m)
+            cls = lib.gsd_conv3x3_w2d_source_class(src, nsrc) if src is not None else 0
+            executed = 2048.0 * lib.gsd_conv3x3_w2d_mfma_count_class(n, lh, lw, k_ch, m, cls, int(with_ws and self.conv_ws is not None))
         elif algo:
             variant = "conv3x3_w43_kernel"
             executed = 2048.0 * lib.gsd_conv3x3_w43_mfma_count(n, lh, lw, k_ch, m)   # one v_mfma_f32_16x16x4_f32 = 2048 flops
@@ -423,7 +438,7 @@ class UNetEngine(EngineBase):
         ev = self._log_begin()
         check(u.form_d.run(self.conv_ws, s, 1, u.wt_d.data_ptr(), u.cout, u.cin, L.dst_array(dsts), len(dsts),
                            self.partials.data_ptr() if stats else None, n, lh, lw, st), "conv3x3 dgrad")
-        self._log_end(ev, u.cin, u.cout, n, lh, lw, u.plan.dgrad.algo)
+        self._log_end(ev, u.cin, u.cout, n, lh, lw, u.plan.dgrad.algo, s, 1)
         return u.plan.dgrad.partial_rows if stats else 0
 
     def _dgrad_fused(self, u: _Unit, prev: _Unit, P, st: int) -> None:
@@ -438,7 +453,7 @@ class UNetEngine(EngineBase):
                                   prev.scale.data_ptr(), prev.shift.data_ptr(), prev.mean.data_ptr(),
                                   prev.invstd.data_ptr(), self.partials.data_ptr(), n, lh, lw, st),
               "conv3x3_dgrad_bnrelu")
-        self._log_end(ev, u.cin, u.cout, n, lh, lw, u.plan.dgrad.algo)
+        self._log_end(ev, u.cin, u.cout, n, lh, lw, u.plan.dgrad.algo, C.byref(s), 1)
 
     def _input_dgrad(self, u: _Unit, P, dx: torch.Tensor, st: int) -> None:
         """dX of the first conv (the gradient w.r.t. the network's input) into dx, after u's BatchNorm backward is final.

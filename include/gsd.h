@@ -222,6 +222,18 @@ double gsd_conv3x3_w2d_estimate_us(int N, int H, int W, int Cin, int Cout);     
 double gsd_conv3x3_w43_estimate_us(int N, int H, int W, int Cin, int Cout, int slabs);
 int gsd_conv3x3_w2d_partial_rows(int N, int H, int W, int Cout);
 int64_t gsd_conv3x3_w2d_mfma_count(int N, int H, int W, int Cin, int Cout);
+/* The deep levels' unsplit launches of source class 1 -- one plain source, rows 16-byte aligned on a pitch of a multiple of 4
+ * floats: every dX launch, the "activate once" forwards -- run a band-major flat list of the Winograd tiles instead of a grid of
+ * rectangles per image where that takes fewer blocks (gsd_conv3x3_w2d_strips.hip; GSD_W2D_STRIPS = 0 never, 1 wherever the list is
+ * admitted, unset: where the run-time model has the shorter list finish sooner): same outputs and the same partial rows bit for bit (a launch
+ * with partial rows leaves per-tile sums in the workspace of the _ws entries -- gsd_conv3x3_w2d_strips_scratch floats -- and a second
+ * kernel adds them in the rectangles' rows and order; without that much workspace it keeps the rectangles).
+ * _mfma_count_class: the MFMAs such a launch issues; _strips_plan / _strips_tile: the listing itself, for tests (out: 7 / 5 ints). */
+int gsd_conv3x3_w2d_source_class(const gsd_src* src, int nsrc);
+int64_t gsd_conv3x3_w2d_strips_scratch(int N, int H, int W, int Cin, int Cout);
+int64_t gsd_conv3x3_w2d_mfma_count_class(int N, int H, int W, int Cin, int Cout, int source_class, int with_workspace);
+int gsd_conv3x3_w2d_strips_plan(int N, int H, int W, int Cin, int Cout, int* out);
+int gsd_conv3x3_w2d_strips_tile(int N, int H, int W, int t, int* out);
 int gsd_conv3x3_w2d(const gsd_src* src, int nsrc, const float* wt, int Cin, int Cout,
                     const gsd_dst* dst, int ndst, float* partials, int N, int H, int W, void* stream);
 int gsd_conv3x3_w2d_dgrad_bnrelu(const gsd_src* src, const float* wt, int Cin, int Cout, const gsd_dst* dst,
