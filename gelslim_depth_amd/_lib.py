@@ -104,6 +104,15 @@ GSD_DEPTH_POINTS_BLOCK = 1024        # lattice points per block of gsd_depth_poi
 GSD_DEPTH_POINTS_SCAN_PASS = 4096    # block counts per pass of their scan
 
 
+class gsd_contact_patches_view(C.Structure):
+    """What gsd_contact_patches_* call contact and a patch (include/gsd.h): contact depth, connectivity, smallest kept area."""
+    _fields_ = [("contact_depth", C.c_double), ("connectivity", C.c_int32), ("min_area", C.c_int32)]
+
+
+GSD_CONTACT_PATCHES_SEG = 64         # columns of a row that one wave of gsd_contact_patches_label takes
+GSD_CONTACT_PATCHES_COLS = 12        # int64 columns per row of gsd_contact_patches_stats
+
+
 class gsd_augment_draw(C.Structure):
     """What gsd_gather_augment draws for one dataset row (gsd_augment_sample)."""
     _fields_ = [("hflip", C.c_int32), ("vflip", C.c_int32), ("dy", C.c_int32), ("dx", C.c_int32),
@@ -238,6 +247,10 @@ SIGNATURES = {
     "gsd_depth_points_workspace": (_L, [_I, _I, _I, _I]),
     "gsd_depth_points_count": (_I, [C.POINTER(gsd_depth_points_view), _P, _P, _I, _I, _I, _I, _P, _P, _L, _P]),
     "gsd_depth_points_write": (_I, [C.POINTER(gsd_depth_points_view), _P, _P, _P, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _L, _P]),
+    "gsd_contact_patches_workspace": (_L, [_I, _I, _I]),
+    "gsd_contact_patches_label": (_I, [C.POINTER(gsd_contact_patches_view), _P, _I, _I, _I, _P, _P, _P, _L, _P]),
+    "gsd_contact_patches_stats": (_I, [C.POINTER(gsd_contact_patches_view), _P, _P, _I, _I, _I, _I, _P, _P]),
+    "gsd_contact_patches_filter": (_I, [C.POINTER(gsd_contact_patches_view), _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "gsd_guard_snapshot": (_I, [_P, _P, _L, _P]),
     "gsd_guard_restore": (_I, [_GUARD, _P, _P, _L, _P]),
     "gsd_adam_ema": (_I, [_P, _P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _F, _F, _GUARD, _P]),

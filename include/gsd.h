@@ -728,6 +728,46 @@ int gsd_depth_points_write(const gsd_depth_points_view* view, const float* depth
                            int W, int stride, int capacity, int64_t rows, float* points, float* normals, int32_t* pixel,
                            int32_t* workspace, int64_t workspace_elems, void* stream);
 
+/* ---- connected contact patches of depth images ---- */
+/* Connected-component labelling of the contact mask of a batch of depth images, integer statistics per patch, and a filter that
+ * removes the patches that are not kept.  Everything is an integer or a bit copy: one result whatever the schedule.
+ *   contact: d < -(float)contact_depth, compared in fp32 (gsd_depth_points' rule): a NaN is not contact, -inf is, -c itself is not.
+ *   patch: a maximal 4- or 8-connected set of contact pixels of one (image, channel) plane; planes never connect.
+ *   numbering: patches of fewer than min_area pixels are dropped, the rest are numbered 1, 2, ... per plane in raster order of each
+ *     patch's first pixel (the smallest r W + k): scipy.ndimage.label's order.
+ * depth: B x 2 x H x W floats in mm.  2 B H W must be below 2^31.
+ * gsd_contact_patches_workspace(B, H, W): int32 words the label call needs (one per pixel and one per 1024 pixels of a plane), 0
+ *   for dims the calls refuse.  What the workspace holds before the call does not matter.
+ * gsd_contact_patches_label: labels (B x 2 x H x W int32) receives 0 for background and dropped patches, else the patch number
+ *   (numbers above any K included); counts (B x 2 int32) the true number of kept patches per plane.  A union-find over the row
+ *   runs of 64-column segments, the parents in `labels` itself; every loop that follows parents is limited to H W steps.
+ * gsd_contact_patches_stats: stats (B x 2 x K x 12 int64), row j of a plane for patch number j + 1; rows without a patch are
+ *   all zero (the call clears the table first).  Columns: 0 area; 1..4 r_min, r_max, k_min, k_max; 5..9 sum r, sum k, sum r^2,
+ *   sum k^2, sum r k; 10 sum dq, dq = (int64) rint((double) max(d, -1024.0f) * 2^20), half to even; 11 the minimum over the patch
+ *   of (ord(d) << 32) | (r W + k), ord(d) = ~u if the sign bit of the fp32 bits u is set, else u | 0x80000000: the deepest pixel,
+ *   among equals the first in raster order.  Patches numbered above K have no row.  Integer atomics only.
+ * gsd_contact_patches_filter: out = depth bit for bit, except +0.0 where a pixel is contact and its patch is not kept.  A patch
+ *   is kept when its label is non-zero and, with a keep table (B x 2 x (K + 1) uint8, entry 0 unused), its number is at most K
+ *   with a non-zero entry; keep = NULL keeps every numbered patch.  The view supplies contact_depth: a dropped patch has label 0
+ *   like the background, so the predicate is evaluated again.  out may be depth itself.
+ * Nothing is allocated, every launch is on `stream`, nothing synchronises.  GSD_ERR_BAD_ARG before any launch: a null pointer
+ * that is required, bad dims, contact_depth negative or not finite, connectivity other than 4 or 8, min_area below 1, K below 1
+ * or a table of 2^31 entries or more.  GSD_ERR_WORKSPACE: a workspace that is too small. */
+typedef struct gsd_contact_patches_view {
+  double contact_depth;  /* c >= 0, mm: a pixel is contact iff d < -(float)c */
+  int32_t connectivity;  /* 4 or 8                                            */
+  int32_t min_area;      /* >= 1: patches with fewer pixels are dropped       */
+} gsd_contact_patches_view;
+#define GSD_CONTACT_PATCHES_SEG 64   /* columns of a row that one wave labels: runs are cut at multiples of it */
+#define GSD_CONTACT_PATCHES_COLS 12  /* int64 columns per row of the statistics                                */
+int64_t gsd_contact_patches_workspace(int B, int H, int W);                     /* int32 words */
+int gsd_contact_patches_label(const gsd_contact_patches_view* view, const float* depth, int B, int H, int W, int32_t* labels,
+                              int32_t* counts, int32_t* workspace, int64_t workspace_elems, void* stream);
+int gsd_contact_patches_stats(const gsd_contact_patches_view* view, const float* depth, const int32_t* labels, int B, int H, int W, int K,
+                              int64_t* stats, void* stream);
+int gsd_contact_patches_filter(const gsd_contact_patches_view* view, const float* depth, const int32_t* labels, const uint8_t* keep, int B,
+                               int H, int W, int K, float* out, void* stream);
+
 /* ---- optimiser (train_unet.py:306,375-376) -------------------------------------------------- */
 /* Fused torch.optim.Adam(lr, betas, eps, weight_decay: coupled L2) + torch_ema update over a flat
  * parameter arena. step is the 1-based Adam step; ema may be NULL; ema_decay already resolved
