@@ -113,6 +113,22 @@ GSD_CONTACT_PATCHES_SEG = 64         # columns of a row that one wave of gsd_con
 GSD_CONTACT_PATCHES_COLS = 12        # int64 columns per row of gsd_contact_patches_stats
 
 
+class gsd_mesh_volume(C.Structure):
+    """The cubic cell grid of one mesh for closest-point queries (include/gsd.h, gsd_mesh_volume_*): box, cell, cells per axis."""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("z0", C.c_double), ("x1", C.c_double), ("y1", C.c_double), ("z1", C.c_double),
+                ("cell", C.c_double), ("inv_cell", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class gsd_icp_lm(C.Structure):
+    """The constants of gsd_mesh_icp_lm_update (include/gsd.h): damping factors and bounds, step clip (mm x 3, rad x 3)."""
+    _fields_ = [("down", C.c_double), ("up", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double),
+                ("max_step", C.c_double * 6), ("first", C.c_int32), ("reserved", C.c_int32)]
+
+
+GSD_ICP_ROW = 30              # doubles per row of gsd_mesh_icp_rows: cost, #active, sum w r^2, J^T r (6), upper triangle of J^T J (21)
+
+
 class gsd_augment_draw(C.Structure):
     """What gsd_gather_augment draws for one dataset row (gsd_augment_sample)."""
     _fields_ = [("hflip", C.c_int32), ("vflip", C.c_int32), ("dy", C.c_int32), ("dx", C.c_int32),
@@ -244,6 +260,14 @@ SIGNATURES = {
     "gsd_mesh_depth_render_jacobian": (_I, [C.POINTER(gsd_mesh_grid), C.POINTER(gsd_mesh_view), _P, _I, _P, _P, _L, _P, _P, _I, _I,
                                             _I, _P, _P, _L, _P]),
     "gsd_mesh_pose_lm_update": (_I, [C.POINTER(gsd_pose_lm), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gsd_mesh_volume_plan": (_I, [C.POINTER(C.c_double), _D, C.POINTER(gsd_mesh_volume)]),
+    "gsd_mesh_volume_workspace": (_L, [C.POINTER(gsd_mesh_volume)]),
+    "gsd_mesh_volume_count": (_I, [C.POINTER(gsd_mesh_volume), _P, _I, _P, _L, _P]),
+    "gsd_mesh_volume_fill": (_I, [C.POINTER(gsd_mesh_volume), _P, _I, _P, _L, _P, _L, _P]),
+    "gsd_mesh_closest_points": (_I, [C.POINTER(gsd_mesh_volume), _P, _I, _P, _P, _L, _P, _L, _D, _P, _P, _P, _P, _P]),
+    "gsd_mesh_icp_rows_workspace": (_L, [_I, _I]),
+    "gsd_mesh_icp_rows": (_I, [C.POINTER(gsd_mesh_volume), _P, _I, _P, _P, _L, _P, _P, _I, _P, _I, _D, _I, _P, _P, _L, _P]),
+    "gsd_mesh_icp_lm_update": (_I, [C.POINTER(gsd_icp_lm), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gsd_depth_points_workspace": (_L, [_I, _I, _I, _I]),
     "gsd_depth_points_count": (_I, [C.POINTER(gsd_depth_points_view), _P, _P, _I, _I, _I, _I, _P, _P, _L, _P]),
     "gsd_depth_points_write": (_I, [C.POINTER(gsd_depth_points_view), _P, _P, _P, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _L, _P]),

@@ -768,6 +768,83 @@ int gsd_contact_patches_stats(const gsd_contact_patches_view* view, const float*
 int gsd_contact_patches_filter(const gsd_contact_patches_view* view, const float* depth, const int32_t* labels, const uint8_t* keep, int B,
                                int H, int W, int K, float* out, void* stream);
 
+/* ---- closest points on a mesh and rigid registration of point clouds ---- */
+/* Exact nearest surface points of a triangle mesh, the normal-equation rows of a point-to-plane or point-to-point fit over SE(3),
+ * and the Levenberg-Marquardt bookkeeping of that fit.  Frame: gsd_depth_points' object frame (the mesh file's coordinates times
+ * pc_scale, mm).
+ *   tri: T x 9 floats on the device, per triangle the vertices a, b, c (x, y, z).  A triangle whose cross product (b - a) x (c - a),
+ *     formed in fp64 from two rounded products and one subtraction per component, is exactly (0, 0, 0) is SKIPPED: no cell lists it.
+ *   volume: cubic cells over the mesh's bounding box (gsd_mesh_volume_plan, host only).  cells: gsd_mesh_volume_workspace int32
+ *     words, 8-byte aligned: words 0..1 the pair total as one int64, then nx*ny*nz + 1 list starts, then nx*ny*nz fill cursors
+ *     (cell (ix, iy, iz) has the index (iz*ny + iy)*nx + ix).  list: triangle ids grouped by cell, at least the pair total.  A
+ *     triangle is listed in every cell its axis-aligned box touches (the index range is widened, rounding can only add a cell).
+ *     plan -> count -> (one host read of the pair total) -> fill, as for gsd_mesh_depth_*.
+ *   closest point of p on a triangle: the region method on
+ *       d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp, d5 = ab.cp, d6 = ac.cp   (u.v = (ux vx + uy vy) + uz vz, ap = p - a, ...)
+ *       vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, e1 = d4 - d3, e2 = d5 - d6,
+ *     the first of: d1 <= 0 and d2 <= 0: a | d3 >= 0 and d4 <= d3: b | vc <= 0, d1 >= 0, d3 <= 0: a + (d1 / (d1 - d3)) ab |
+ *       d6 >= 0 and d5 <= d6: c | vb <= 0, d2 >= 0, d6 <= 0: a + (d2 / (d2 - d6)) ac | va <= 0, e1 >= 0, e2 >= 0: b + (e1 / (e1 + e2)) (c - b) |
+ *       else (a + (vb / s) ab) + (vc / s) ac with s = (va + vb) + vc;
+ *     d^2 = ((px - x)^2 + (py - y)^2) + (pz - z)^2.  All of it in fp64 from the fp32 loads on, no contraction.
+ *   winner of p: the triangle with the smallest d^2, THE LOWEST TRIANGLE ID among bit-equal ones; with max_distance D (+inf:
+ *     unlimited) it needs d^2 <= D*D.  The result depends on p and the mesh alone: not on the cells, N or p's place.
+ * gsd_mesh_closest_points: points N x 3 floats; triangle (N int32), closest (N x 3 floats, (float)x), distance (N floats,
+ *   (float)sqrt(d^2)), sq_distance (N doubles, 8-byte aligned).  No winner, or a non-finite coordinate: -1, NaN, +inf, +inf.
+ * gsd_mesh_icp_rows: for each of S transforms (12 doubles, a row-major 3 x 4 [R | t]) one row of GSD_ICP_ROW doubles over the N
+ *   points p' = R p + t, p'_x = ((R00 px + R01 py) + R02 pz) + t0, kept in fp64; weights (N floats >= 0) may be NULL (1).  A point is
+ *   active iff it has a winner within D; one with a non-finite p' adds nothing.
+ *     [0] sum_active w d^2 + D^2 sum_inactive w (the second term only for a finite D)   [1] #active   [2] sum_active w r^2
+ *     [3..8] sum w J^T r   [9..29] sum w J^T J, upper triangle, row-major; parameters: the left twist (v, omega), dp' = v + omega x p'.
+ *     kind 0, point to plane: n = cross / |cross| of the winner, r = n.(p' - x), J = [n, p' x n];
+ *     kind 1, point to point: r = p' - x, J = [I, -[p']x].
+ *   Blocks of 256 points are summed by a fixed tree, a second launch adds a start's blocks in ascending order: no float atomics, a
+ *   row repeats bitwise and does not depend on S or its place.  workspace: gsd_mesh_icp_rows_workspace(N, S) doubles (0 for
+ *   arguments the call refuses).
+ * gsd_mesh_icp_lm_update: gsd_mesh_pose_lm_update for S starts on six parameters.  State: transforms (S x 12), lambda, row (S x
+ *   GSD_ICP_ROW), accepted; trial: trial_transforms, trial_row.
+ *   1. accept iff trial_row[0] < row[0] (strict; a NaN never wins), lambda = max(lambda * down, lambda_min), else lambda =
+ *      min(lambda * up, lambda_max); `first` != 0 takes the trial unconditionally, accepted = 0, lambda untouched.
+ *   2. (A + lambda diag A) xi = -b, A = row[9..29], b = row[3..8], by Cholesky in the order v1 v2 v3 w1 w2 w3; a pivot <= 0 or not
+ *      finite, or a non-finite solution, gives xi = 0; xi is clipped per component to max_step (mm x 3, rad x 3).
+ *   3. trial_transforms = exp(xi) T of the state: E = I + A K + B K^2, u = (I + B K + C K^2) v, K = [omega]x, th = |omega|,
+ *      A = sin th / th, B = (1 - cos th) / th^2, C = (th - sin th) / th^3, below th = 1e-8 their series 1 - th^2/6, 1/2 - th^2/24,
+ *      1/6 - th^2/120; R' = E R, t' = E t + u.  trace[i] = row[0] of the state, last_step[6 i + k] = |xi_k|.
+ * Nothing is allocated, every launch is on `stream`, nothing synchronises.  GSD_ERR_BAD_ARG before any launch: a null pointer
+ * (weights excepted), N, S or T below 1, a max_distance that is negative or NaN, a kind other than 0 or 1, a volume outside 1..1024
+ * cells per axis or 2^24 in all or with a non-finite field, a non-zero reserved word, misaligned fp64 arrays or cells, what
+ * gsd_mesh_pose_lm_update refuses of its constants.  GSD_ERR_WORKSPACE: a workspace that is too small. */
+typedef struct gsd_mesh_volume {
+  double x0, y0, z0;     /* grid origin, mm                                                             */
+  double x1, y1, z1;     /* x0 + nx * cell, ...: the box that holds every vertex, queries are clamped into it */
+  double cell, inv_cell; /* side of a cubic cell in mm, and its reciprocal                              */
+  int32_t nx, ny, nz;    /* cells per axis, 1..1024, at most 2^24 in all                                */
+  int32_t reserved;      /* 0 */
+} gsd_mesh_volume;
+typedef struct gsd_icp_lm {
+  double down, up;                /* factors of lambda after an accepted / a rejected trial */
+  double lambda_min, lambda_max;
+  double max_step[6];             /* mm, mm, mm, rad, rad, rad */
+  int32_t first;                  /* != 0: the trial initialises the state */
+  int32_t reserved;               /* 0 */
+} gsd_icp_lm;
+#define GSD_ICP_ROW 30
+/* Host only: the grid over bbox = {xmin, ymin, zmin, xmax, ymax, zmax} (mm) with cells of cell_mm, enlarged where an axis would
+ * need more than 1024 cells or the grid more than 2^24. */
+int gsd_mesh_volume_plan(const double* bbox, double cell_mm, gsd_mesh_volume* volume);
+int64_t gsd_mesh_volume_workspace(const gsd_mesh_volume* volume);            /* int32 words of `cells` */
+int gsd_mesh_volume_count(const gsd_mesh_volume* volume, const float* tri, int T, int32_t* cells, int64_t cells_elems, void* stream);
+int gsd_mesh_volume_fill(const gsd_mesh_volume* volume, const float* tri, int T, int32_t* cells, int64_t cells_elems, int32_t* list,
+                         int64_t list_elems, void* stream);
+int gsd_mesh_closest_points(const gsd_mesh_volume* volume, const float* tri, int T, const int32_t* cells, const int32_t* list,
+                            int64_t list_elems, const float* points, int64_t N, double max_distance, int32_t* triangle, float* closest,
+                            float* distance, double* sq_distance, void* stream);
+int64_t gsd_mesh_icp_rows_workspace(int N, int S);                           /* doubles */
+int gsd_mesh_icp_rows(const gsd_mesh_volume* volume, const float* tri, int T, const int32_t* cells, const int32_t* list,
+                      int64_t list_elems, const float* points, const float* weights, int N, const double* transforms, int S,
+                      double max_distance, int kind, double* rows, double* workspace, int64_t workspace_elems, void* stream);
+int gsd_mesh_icp_lm_update(const gsd_icp_lm* lm, int S, double* transforms, double* lambda, double* row, double* trial_transforms,
+                           const double* trial_row, double* trace, int32_t* accepted, double* last_step, void* stream);
+
 /* ---- optimiser (train_unet.py:306,375-376) -------------------------------------------------- */
 /* Fused torch.optim.Adam(lr, betas, eps, weight_decay: coupled L2) + torch_ema update over a flat
  * parameter arena. step is the 1-based Adam step; ema may be NULL; ema_decay already resolved
