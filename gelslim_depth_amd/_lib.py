@@ -129,6 +129,22 @@ class gsd_icp_lm(C.Structure):
 GSD_ICP_ROW = 30              # doubles per row of gsd_mesh_icp_rows: cost, #active, sum w r^2, J^T r (6), upper triangle of J^T J (21)
 
 
+class gsd_touch_volume(C.Structure):
+    """The voxel lattice of gsd_touch_* (include/gsd.h): position of voxel (0, 0, 0), spacing, truncation, voxels per axis."""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("z0", C.c_double), ("voxel", C.c_double), ("truncation", C.c_double),
+                ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("reserved", C.c_int32)]
+
+
+class gsd_touch_view(C.Structure):
+    """How gsd_touch_integrate reads a touch (include/gsd.h): image height, width offset, contact depth, carve weight, flags."""
+    _fields_ = [("image_height_mm", C.c_double), ("width_offset", C.c_double), ("contact_depth", C.c_double), ("carve_weight", C.c_double),
+                ("lr_flip", C.c_int32), ("cull", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+GSD_TOUCH_EXTRACT_BLOCK = 256         # cells per block of gsd_touch_extract_count / _write
+GSD_TOUCH_EXTRACT_SCAN_PASS = 4096    # block totals per pass of their scan
+
+
 class gsd_augment_draw(C.Structure):
     """What gsd_gather_augment draws for one dataset row (gsd_augment_sample)."""
     _fields_ = [("hflip", C.c_int32), ("vflip", C.c_int32), ("dy", C.c_int32), ("dx", C.c_int32),
@@ -268,6 +284,10 @@ SIGNATURES = {
     "gsd_mesh_icp_rows_workspace": (_L, [_I, _I]),
     "gsd_mesh_icp_rows": (_I, [C.POINTER(gsd_mesh_volume), _P, _I, _P, _P, _L, _P, _P, _I, _P, _I, _D, _I, _P, _P, _L, _P]),
     "gsd_mesh_icp_lm_update": (_I, [C.POINTER(gsd_icp_lm), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gsd_touch_integrate": (_I, [C.POINTER(gsd_touch_volume), C.POINTER(gsd_touch_view), _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "gsd_touch_extract_workspace": (_L, [C.POINTER(gsd_touch_volume)]),
+    "gsd_touch_extract_count": (_I, [C.POINTER(gsd_touch_volume), _P, _P, _D, _P, _P, _L, _P]),
+    "gsd_touch_extract_write": (_I, [C.POINTER(gsd_touch_volume), _P, _P, _D, _L, _L, _P, _P, _P, _L, _P]),
     "gsd_depth_points_workspace": (_L, [_I, _I, _I, _I]),
     "gsd_depth_points_count": (_I, [C.POINTER(gsd_depth_points_view), _P, _P, _I, _I, _I, _I, _P, _P, _L, _P]),
     "gsd_depth_points_write": (_I, [C.POINTER(gsd_depth_points_view), _P, _P, _P, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _L, _P]),

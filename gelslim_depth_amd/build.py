@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
-SOURCES = ["gsd_conv3x3.hip", "gsd_conv3x3_w43.hip", "gsd_conv3x3_w2d.hip", "gsd_conv3x3_w2d_strips.hip", "gsd_convT.hip", "gsd_convT_wgrad.hip", "gsd_wgrad.hip", "gsd_wgrad_w43.hip", "gsd_wgrad_w2d.hip", "gsd_wgrad_first.hip", "gsd_dgrad_first.hip", "gsd_api.hip", "gsd_weight_layout.hip", "gsd_bn.hip", "gsd_head.hip", "gsd_optim.hip", "gsd_depth_loss.hip", "gsd_depth_metrics.hip", "gsd_mesh_depth.hip", "gsd_mesh_closest.hip", "gsd_depth_points.hip", "gsd_contact_patches.hip", "gsd_dataset.hip", "gsd_augment.hip", "gsd_resize.hip", "gsd_bf16_conv.hip", "gsd_bf16_layout.hip", "gsd_bf16_bn.hip", "gsd_bf16_head.hip", "gsd_bf16_sums.hip", "gsd_bf16_wgrad.hip", "gsd_bf16_first.hip", "gsd_bf16_inc.hip", "gsd_bf16_c64.hip", "gsd_bf16_ctgemm.hip"]
+SOURCES = ["gsd_conv3x3.hip", "gsd_conv3x3_w43.hip", "gsd_conv3x3_w2d.hip", "gsd_conv3x3_w2d_strips.hip", "gsd_convT.hip", "gsd_convT_wgrad.hip", "gsd_wgrad.hip", "gsd_wgrad_w43.hip", "gsd_wgrad_w2d.hip", "gsd_wgrad_first.hip", "gsd_dgrad_first.hip", "gsd_api.hip", "gsd_weight_layout.hip", "gsd_bn.hip", "gsd_head.hip", "gsd_optim.hip", "gsd_depth_loss.hip", "gsd_depth_metrics.hip", "gsd_mesh_depth.hip", "gsd_mesh_closest.hip", "gsd_touch_fusion.hip", "gsd_depth_points.hip", "gsd_contact_patches.hip", "gsd_dataset.hip", "gsd_augment.hip", "gsd_resize.hip", "gsd_bf16_conv.hip", "gsd_bf16_layout.hip", "gsd_bf16_bn.hip", "gsd_bf16_head.hip", "gsd_bf16_sums.hip", "gsd_bf16_wgrad.hip", "gsd_bf16_first.hip", "gsd_bf16_inc.hip", "gsd_bf16_c64.hip", "gsd_bf16_ctgemm.hip"]
 OUT = os.path.join(CSRC, "libgsd.so")
 STAMP = OUT + ".stamp"      # sha256 of everything the .so was built from (git-ignored, travels with the .so)
 OBJ = os.path.join(CSRC, "obj")

@@ -845,6 +845,75 @@ int gsd_mesh_icp_rows(const gsd_mesh_volume* volume, const float* tri, int T, co
 int gsd_mesh_icp_lm_update(const gsd_icp_lm* lm, int S, double* transforms, double* lambda, double* row, double* trial_transforms,
                            const double* trial_row, double* trace, int32_t* accepted, double* last_step, void* stream);
 
+/* ---- touches fused into a surface: TSDF volume and marching tetrahedra ---- */
+/* Many depth images of one object, each with a rigid map object -> grasp frame, are fused into a truncated signed distance volume,
+ * and the volume's zero level is extracted as triangles.  Both are gathers in a fixed order without float atomics: a numpy twin
+ * holds them bit for bit.  Frame: gsd_depth_points' object frame, mm.
+ *   volume: nx x ny x nz voxels, voxel (ix, iy, iz) at origin + voxel * (ix, iy, iz) (fp64, one product and one sum per component),
+ *     linear index (iz*ny + iy)*nx + ix.  State: acc = sum w * sample and weight = sum w, nz x ny x nx floats each.
+ *   touch k: depth image k (2 x H x W floats, channels as gsd_mesh_depth_render writes them), widths[k], transforms + 12 k (row-major
+ *     3 x 4 [A | t], gsd_mesh_icp_rows' layout; rows give u (unaligned), v (aligned), q (perpendicular, right finger at q > 0); A may
+ *     be improper and is not checked), weights[k] (weights may be NULL: 1).
+ *   one sample (voxel p, touch k, channel ch), fp64 without contraction after the fp32 loads:
+ *     s = +1 for the right finger (channel 1, channel 0 with view.lr_flip), -1 for the left
+ *     u = ((A00 px + A01 py) + A02 pz) + t0, likewise v, q;   g = (double)widths[k] + view.width_offset; a negative or non-finite g
+ *     makes the touch contribute nothing;   mpp = image_height_mm / H, inv_mpp = 1 / mpp (host)
+ *     rf = (s u) inv_mpp + H/2, kf = v inv_mpp + W/2, r0 = floor(rf), k0 = floor(kf)
+ *     usable: 0 <= r0 <= H - 2 and 0 <= k0 <= W - 2 (compared in fp64) and the pixels d00, d01, d10, d11 (row offset, column offset)
+ *       all finite;   a = rf - r0, b = kf - k0, top = d00 + b (d01 - d00), bot = d10 + b (d11 - d10), dbar = top + a (bot - top)
+ *     phi = (s q - g/2) + dbar;   contact: all four pixels d < -(float)contact_depth (fp32)
+ *     update in fp32, products and sums rounded separately, w = weights[k]:
+ *       contact and phi >= -truncation:      acc += w * (float)min(phi * inv_truncation, 1), weight += w
+ *       usable, not contact and phi > 0:     acc += wc, weight += wc, wc = w * (float)carve_weight
+ *   Per voxel the updates run in touch order, channel 0 before channel 1, onto the stored state: K touches in one call equal any
+ *   split of them into consecutive calls, bit for bit.
+ * gsd_touch_integrate: one thread per voxel, a block of 256 owns a brick of 16 x 4 x 4 voxels and walks the K touches; state is read
+ *   once and stored once.  With view.cull != 0 a block skips a touch whose image rectangle, grown by one pixel, cannot hold any voxel
+ *   of the brick's box: a bound, so it never changes a bit.  2 K H W must be below 2^31.
+ * field: f = (double)acc / (double)weight; a voxel is observed iff weight > (float)min_weight, inside iff f < 0.
+ * surface: a cell (ix, iy, iz), ix < nx - 1, ..., is valid iff its eight corners are observed; it is split into the six Kuhn
+ *   tetrahedra around the diagonal (0,0,0)-(1,1,1) (axis permutations in lexicographic order) and each is triangulated by the table
+ *   of section 24, normals out of the object.  A vertex on the edge between the voxels lo < hi (linear index):
+ *   t = f_lo / (f_lo - f_hi), p = p_lo + (p_hi - p_lo) t per component in fp64, rounded to fp32 at the store: every cell that shares
+ *   the edge stores the same bits.  Order: cell index (iz*(ny-1) + iy)*(nx-1) + ix, tetrahedron 0..5, the table's order.
+ * gsd_touch_extract_workspace: int32 words of the workspace (8-byte aligned), 0 for a volume the calls refuse.
+ * gsd_touch_extract_count: blocks of 256 cells count their triangles, one block scans the block totals (4096 per pass, with a
+ *   carry); the total is left as one int64 at the head of the workspace and in *total (device).
+ * gsd_touch_extract_write: needs the workspace as the count of the same volume, state and min_weight left it; writes triangles
+ *   (rows x 9 floats: a, b, c) and cell (rows int32, may be NULL).  No row at or beyond `rows` is written.
+ *     packed, capacity = 0: triangle i goes to row i.
+ *     padded, capacity = M > 0: the first min(total, M) triangles, then NaN (cell: -1) up to row M - 1; rows must be at least M.
+ * Nothing is allocated, every launch is on `stream`, nothing synchronises.  GSD_ERR_BAD_ARG before any launch: a null pointer
+ * (weights and cell excepted), K < 1, H or W < 2, 2 K H W >= 2^31, an axis outside 2..1024, voxel or truncation not finite and
+ * positive, a non-finite origin, image height or width offset, a negative or non-finite contact_depth, carve_weight or min_weight, a
+ * non-zero reserved word, a negative capacity or rows, rows below capacity or above 2^31 - 1, a misaligned workspace, total or
+ * transforms.  GSD_ERR_WORKSPACE: a workspace that is too small. */
+typedef struct gsd_touch_volume {
+  double x0, y0, z0;      /* position of voxel (0, 0, 0), mm                  */
+  double voxel;           /* spacing h, mm                                    */
+  double truncation;      /* tau, mm                                          */
+  int32_t nx, ny, nz;     /* voxels per axis, 2..1024                         */
+  int32_t reserved;       /* 0 */
+} gsd_touch_volume;
+typedef struct gsd_touch_view {
+  double image_height_mm; /* the H rows of an image span this many mm         */
+  double width_offset;    /* added to every grasp width, mm                   */
+  double contact_depth;   /* c >= 0, mm: a pixel is contact iff d < -(float)c */
+  double carve_weight;    /* weight of a free-space sample relative to w      */
+  int32_t lr_flip;        /* channel order (right, left)                      */
+  int32_t cull;           /* != 0: blocks skip touches that cannot reach them */
+  int32_t reserved[2];    /* 0 */
+} gsd_touch_view;
+#define GSD_TOUCH_EXTRACT_BLOCK 256    /* cells per block of the count and write launches */
+#define GSD_TOUCH_EXTRACT_SCAN_PASS 4096 /* block totals per pass of the scan             */
+int gsd_touch_integrate(const gsd_touch_volume* volume, const gsd_touch_view* view, const float* depth, const float* widths,
+                        const double* transforms, const float* weights, int K, int H, int W, float* acc, float* weight, void* stream);
+int64_t gsd_touch_extract_workspace(const gsd_touch_volume* volume);            /* int32 words */
+int gsd_touch_extract_count(const gsd_touch_volume* volume, const float* acc, const float* weight, double min_weight, int64_t* total,
+                            int32_t* workspace, int64_t workspace_elems, void* stream);
+int gsd_touch_extract_write(const gsd_touch_volume* volume, const float* acc, const float* weight, double min_weight, int64_t capacity,
+                            int64_t rows, float* triangles, int32_t* cell, int32_t* workspace, int64_t workspace_elems, void* stream);
+
 /* ---- optimiser (train_unet.py:306,375-376) -------------------------------------------------- */
 /* Fused torch.optim.Adam(lr, betas, eps, weight_decay: coupled L2) + torch_ema update over a flat
  * parameter arena. step is the 1-based Adam step; ema may be NULL; ema_decay already resolved
