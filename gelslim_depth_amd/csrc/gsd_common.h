@@ -5,18 +5,11 @@
 #include <stdlib.h>
 #include <atomic>
 #include "gsd.h"
+#include "gsd_block_prims.h"
+#include "gsd_error.h"      // the host-side error plumbing: gsd_set_error, GSD_REQUIRE
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// ---- host-side error plumbing (thread-local message, defined in gsd_api.hip) ---------------
-void gsd_set_error(const char* fmt, ...);
-#define GSD_REQUIRE(cond, code, ...)                 \
-  do {                                               \
-    if (!(cond)) {                                   \
-      gsd_set_error(__VA_ARGS__);                    \
-      return (code);                                 \
-    }                                                \
-  } while (0)
 #define GSD_LAUNCH_CHECK(what)                                                       \
   do {                                                                               \
     hipError_t e_ = hipGetLastError();                                               \
@@ -116,14 +109,8 @@ __device__ __forceinline__ float reduce16_to_lane15(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, true));
   return v;
 }
-__device__ __forceinline__ double wave_sum_d(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+__device__ __forceinline__ double wave_sum_d(double v) { return gsd_wave_sum(v); }
+__device__ __forceinline__ float wave_sum_f(float v) { return gsd_wave_sum(v); }
 
 // pitched_ok: the kernel addresses rows through w_stride; otherwise the operand must be row-contiguous (w_stride == W)
 static inline int gsd_check_src(const gsd_src& s, const char* what, bool pitched_ok = false) {

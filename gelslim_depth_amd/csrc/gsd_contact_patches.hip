@@ -198,76 +198,35 @@ __global__ __launch_bounds__(CP_THREADS) void patches_count(const CpView V, cons
   int n = 0;
 #pragma unroll
   for (int j = 0; j < CP_ROUNDS; ++j) n += __popcll(__ballot(is[j]));
-  if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    n = 0;
-#pragma unroll
-    for (int w = 0; w < CP_WAVES; ++w) n += wave_n[w];
-    block_count[blockIdx.x] = n;
-  }
+  n = gsd_block_count<CP_THREADS>(n, wave_n);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = n;
 }
 
 // One block per plane: the plane's block counts -> exclusive offsets in place, CP_THREADS counts per pass with a carry; the
 // total is the plane's count of kept patches.
 __global__ __launch_bounds__(CP_THREADS) void patches_scan(int nblk, int* block_off, int* __restrict__ counts) {
-  __shared__ int wave_sum[CP_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int* off = block_off + (size_t)blockIdx.x * nblk;
-  int carry = 0;      // below 2^31: there are fewer pixels than that
-  for (int base = 0; base < nblk; base += CP_THREADS) {
-    const int i = base + tid;
-    const int v = i < nblk ? off[i] : 0;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wave_sum[wave] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < CP_WAVES; ++w) {
-      const int x = wave_sum[w];
-      before += w < wave ? x : 0;
-      all += x;
-    }
-    if (i < nblk) off[i] = carry + before + inc - v;
-    carry += all;
-    __syncthreads();      // wave_sum is reused
-  }
-  if (tid == 0) counts[blockIdx.x] = carry;
+  const int carry = gsd_block_exclusive_scan<int, CP_THREADS, 1>(      // below 2^31: there are fewer pixels than that
+      nblk, [&](int i) { return off[i]; }, [&](int i, int run) { off[i] = run; });
+  if (threadIdx.x == 0) counts[blockIdx.x] = carry;
 }
 
 // area[root] becomes the patch's number, 0 for a root that is dropped
 __global__ __launch_bounds__(CP_THREADS) void patches_number(const CpView V, const int* __restrict__ parent, int* __restrict__ area,
                                                            const int* __restrict__ block_off) {
   __shared__ int slot_n[CP_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   bool is[CP_ROUNDS];
-  int g[CP_ROUNDS];
+  int g[CP_ROUNDS], rank[CP_ROUNDS];
   unsigned long long mask[CP_ROUNDS];
 #pragma unroll
   for (int j = 0; j < CP_ROUNDS; ++j) g[j] = cp_root(V, parent, area, j, &is[j]);
 #pragma unroll
-  for (int j = 0; j < CP_ROUNDS; ++j) {
-    mask[j] = __ballot(is[j]);
-    if (lane == 0) slot_n[j * CP_WAVES + wave] = __popcll(mask[j]);
-  }
-  __syncthreads();
+  for (int j = 0; j < CP_ROUNDS; ++j) mask[j] = __ballot(is[j]);
+  gsd_block_rank<CP_THREADS, CP_ROUNDS>(mask, slot_n, rank);
   const int base = block_off[blockIdx.x];
-  int n[CP_SLOTS];
 #pragma unroll
-  for (int v = 0; v < CP_SLOTS; ++v) n[v] = slot_n[v];
-#pragma unroll
-  for (int j = 0; j < CP_ROUNDS; ++j) {
-    int before = 0;
-#pragma unroll
-    for (int v = 0; v < CP_SLOTS; ++v) before += v < j * CP_WAVES + wave ? n[v] : 0;
-    const int number = base + before + __popcll(mask[j] & ((1ull << lane) - 1ull)) + 1;
-    if (g[j] >= 0) area[g[j]] = is[j] ? number : 0;
-  }
+  for (int j = 0; j < CP_ROUNDS; ++j)
+    if (g[j] >= 0) area[g[j]] = is[j] ? base + rank[j] + 1 : 0;
 }
 
 __global__ __launch_bounds__(CP_THREADS) void patches_relabel(long long pixels, int* __restrict__ labels, const int* __restrict__ number) {
@@ -278,19 +237,6 @@ __global__ __launch_bounds__(CP_THREADS) void patches_relabel(long long pixels, 
 }
 
 // ---- statistics ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long cp_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned long long cp_wave_min(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long t = __shfl_xor(v, o, 64);
-    v = t < v ? t : v;
-  }
-  return v;
-}
 // the order-preserving map of the fp32 bits to uint32
 __device__ __forceinline__ unsigned cp_ord(float d) {
   const unsigned u = __float_as_uint(d);
@@ -361,8 +307,8 @@ __global__ __launch_bounds__(CP_THREADS) void patches_stats(const CpView V, cons
       const int which = __shfl(lab[j], __ffsll((long long)rem) - 1, 64);
       const bool mine = active && lab[j] == which;
       const unsigned long long mm = __ballot(mine);
-      const long long sum_k = cp_wave_sum(mine ? k : 0ll), sum_kk = cp_wave_sum(mine ? k * k : 0ll), sum_dq = cp_wave_sum(mine ? dq : 0ll);
-      const unsigned long long peak = cp_wave_min(mine ? key : ~0ull);
+      const long long sum_k = gsd_wave_sum(mine ? k : 0ll), sum_kk = gsd_wave_sum(mine ? k * k : 0ll), sum_dq = gsd_wave_sum(mine ? dq : 0ll);
+      const unsigned long long peak = gsd_wave_min(mine ? key : ~0ull);
       const long long n = __popcll(mm), base = seg * CP_SEG;
       const long long k_min = base + __ffsll((long long)mm) - 1, k_max = base + 63 - __clzll((long long)mm);
       if (which != A.label) {

@@ -45,13 +45,6 @@ __device__ __forceinline__ float dm_max(float v, float m) { return v > m ? v : m
 __device__ __forceinline__ float dm_e_at(const char* po, const char* pt, long long off) {
   return *reinterpret_cast<const float*>(po + off) - *reinterpret_cast<const float*>(pt + off);
 }
-__device__ __forceinline__ double wave_max_d(double v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double u = __shfl_xor(v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
-}
 
 __global__ __launch_bounds__(256) void depth_metrics_stage1(const DmParams P, const float* __restrict__ o,
                                                             const float* __restrict__ t, double* __restrict__ ws) {
@@ -105,7 +98,7 @@ __global__ __launch_bounds__(256) void depth_metrics_stage1(const DmParams P, co
                                 (double)m_t, (double)m_p, s_slope, (double)n_bad};
 #pragma unroll
   for (int q = 0; q < DM_USED; ++q) {
-    const double v = dm_is_max(q) ? wave_max_d(vals[q]) : wave_sum_d(vals[q]);
+    const double v = dm_is_max(q) ? gsd_wave_max(vals[q]) : wave_sum_d(vals[q]);
     if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = v;
   }
   __syncthreads();
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(64) void depth_metrics_stage2(const double* __restr
 #pragma unroll
   for (int q = 0; q < DM_USED; ++q) tot[q] = b < bpi ? row[q] : 0.0;   // sums and counts add 0; the maxima are never negative
 #pragma unroll
-  for (int q = 0; q < DM_USED; ++q) tot[q] = dm_is_max(q) ? wave_max_d(tot[q]) : wave_sum_d(tot[q]);
+  for (int q = 0; q < DM_USED; ++q) tot[q] = dm_is_max(q) ? gsd_wave_max(tot[q]) : wave_sum_d(tot[q]);
   if (threadIdx.x == 0) {
     double* out = table + (size_t)n * DM_COLS;
 #pragma unroll

@@ -88,59 +88,20 @@ __global__ __launch_bounds__(DP_THREADS) void depth_points_count(const DpView V,
   int n = 0;
 #pragma unroll
   for (int j = 0; j < DP_ROUNDS; ++j) n += __popcll(__ballot(is[j]));
-  if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    n = 0;
-#pragma unroll
-    for (int w = 0; w < DP_THREADS / 64; ++w) n += wave_n[w];
-    block_count[blockIdx.x] = n;
-  }
+  n = gsd_block_count<DP_THREADS>(n, wave_n);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = n;
 }
 
 // One block: block counts -> exclusive offsets in place, pass by pass with a carry; then the total and the count of every
 // (image, channel), to the caller's `counts` and to the workspace copy that the write reads.
 __global__ __launch_bounds__(DP_SCAN_THREADS) void depth_points_scan(int nblocks, int nblk, int images, int* block_off, int* __restrict__ counts,
                                                               int* __restrict__ counts_ws, long long* __restrict__ total) {
-  __shared__ int wave_sum[DP_SCAN_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  long long carry = 0;
-  for (int base = 0; base < nblocks; base += DP_SCAN_PASS) {
-    const int i0 = base + tid * DP_SCAN_PER;      // nblocks < 2^31 - DP_SCAN_PASS: refused on the host otherwise
-    const int v0 = i0 < nblocks ? block_off[i0] : 0;
-    const int v1 = i0 + 1 < nblocks ? block_off[i0 + 1] : 0;
-    const int v2 = i0 + 2 < nblocks ? block_off[i0 + 2] : 0;
-    const int v3 = i0 + 3 < nblocks ? block_off[i0 + 3] : 0;
-    const int s = v0 + v1 + v2 + v3;
-    int inc = s;                                   // inclusive scan over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wave_sum[wave] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < DP_SCAN_THREADS / 64; ++w) {
-      const int x = wave_sum[w];
-      before += w < wave ? x : 0;
-      all += x;
-    }
-    int run = (int)carry + before + inc - s;       // the total stays below 2^31: there are fewer lattice points than that
-    if (i0 < nblocks) block_off[i0] = run;
-    run += v0;
-    if (i0 + 1 < nblocks) block_off[i0 + 1] = run;
-    run += v1;
-    if (i0 + 2 < nblocks) block_off[i0 + 2] = run;
-    run += v2;
-    if (i0 + 3 < nblocks) block_off[i0 + 3] = run;
-    carry += all;
-    __syncthreads();                               // wave_sum is reused; the offsets are visible to the block
-  }
+  const int tid = threadIdx.x;
+  const int carry = gsd_block_exclusive_scan<int, DP_SCAN_THREADS, DP_SCAN_PER>(      // below 2^31: there are fewer lattice points than that
+      nblocks, [&](int i) { return block_off[i]; }, [&](int i, int run) { block_off[i] = run; });
   if (tid == 0) *total = carry;
   for (int img = tid; img < images; img += DP_SCAN_THREADS) {
-    const int n = (img + 1 < images ? block_off[(size_t)(img + 1) * nblk] : (int)carry) - block_off[(size_t)img * nblk];
+    const int n = (img + 1 < images ? block_off[(size_t)(img + 1) * nblk] : carry) - block_off[(size_t)img * nblk];
     counts[img] = n;
     counts_ws[img] = n;
   }
@@ -237,29 +198,20 @@ __global__ __launch_bounds__(DP_THREADS) void depth_points_write(const DpView V,
                                                                  int capacity, long long rows, float* __restrict__ points,
                                                                  float* __restrict__ normals, int* __restrict__ pixel) {
   __shared__ int slot_n[DP_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   DpPoint P[DP_ROUNDS];
   unsigned long long mask[DP_ROUNDS];
+  int rank[DP_ROUNDS];      // the points in front of this one in its block, in point order
 #pragma unroll
   for (int j = 0; j < DP_ROUNDS; ++j) P[j] = dp_point(V, depth, widths, j);
 #pragma unroll
-  for (int j = 0; j < DP_ROUNDS; ++j) {
-    mask[j] = __ballot(P[j].is);
-    if (lane == 0) slot_n[j * (DP_THREADS / 64) + wave] = __popcll(mask[j]);
-  }
-  __syncthreads();
+  for (int j = 0; j < DP_ROUNDS; ++j) mask[j] = __ballot(P[j].is);
+  gsd_block_rank<DP_THREADS, DP_ROUNDS>(mask, slot_n, rank);
   const int b = blockIdx.x / (2 * V.nblk);
   const long long first = capacity > 0 ? block_off[(size_t)(2 * b) * V.nblk] : 0;      // the image's first point
   const long long base = block_off[blockIdx.x];      // the row of the block's first point
-  int n[DP_SLOTS];
-#pragma unroll
-  for (int v = 0; v < DP_SLOTS; ++v) n[v] = slot_n[v];
 #pragma unroll
   for (int j = 0; j < DP_ROUNDS; ++j) {
-    int before = 0;      // the points of the slots in front of this wave's slot of round j, in point order
-#pragma unroll
-    for (int v = 0; v < DP_SLOTS; ++v) before += v < j * (DP_THREADS / 64) + wave ? n[v] : 0;
-    long long row = base + before + __popcll(mask[j] & ((1ull << lane) - 1ull));
+    long long row = base + rank[j];
     bool keep = P[j].is;
     if (capacity > 0) {
       keep = keep && row - first < capacity;

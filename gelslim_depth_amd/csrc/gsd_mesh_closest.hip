@@ -1,17 +1,19 @@
 // Closest points on a triangle mesh and the normal-equation rows of a rigid registration (include/gsd.h).
 //
-//   mesh_volume_count / mesh_volume_fill   a 3-D grid of cubic cells over the mesh: count, scan (gsd_mesh_depth's order), fill.
+//   mesh_volume_count / mesh_volume_fill   a 3-D grid of cubic cells over the mesh: count, scan, fill (gsd_cell_lists.h).
 //     A triangle is listed in every cell its axis-aligned box touches, widened by MC_CELL_EPS of a cell on either side so that
 //     rounding in the index can only add a cell.  A triangle whose fp64 cross product is exactly (0, 0, 0) is listed nowhere.
 //   mesh_closest          one lane per point: the lane walks shells of cells of growing Chebyshev radius around the cell of q, the
 //     point clamped into the grid's box, and stops once its best d^2 is strictly below a lower bound of every unseen triangle's.
 //   mesh_icp_rows         the same walk on p' = R p + t (kept in fp64) and the 30 sums of one start over one block of 256 points:
 //     a butterfly per wave, (w0 + w1) + (w2 + w3) through LDS; mesh_icp_rows_sum adds a start's blocks in ascending order.
-//   mesh_icp_lm_update    gsd_mesh_pose_lm_update on six parameters: one thread per start, Cholesky in a fixed order, exp(xi) T.
+//   mesh_icp_lm_update    one thread per start: the shared LM step (gsd_lm_step.h) on six parameters, then exp(xi) T.
 //
 // The distance arithmetic (mc_triangle) is the definition: fp64 from the fp32 loads on, contraction off, + - * / and comparisons
 // only, so that a numpy twin repeats it bit for bit.  No per-lane array is indexed with a run-time value.
 #include "gsd_common.h"
+#include "gsd_cell_lists.h"
+#include "gsd_lm_step.h"
 
 #include <math.h>
 
@@ -88,34 +90,10 @@ __global__ __launch_bounds__(256) void mesh_volume_count(const McVol G, const fl
       for (int ix = lo[0]; ix <= hi[0]; ++ix) atomicAdd(count + ((size_t)iz * G.ny + iy) * G.nx + ix, 1);
 }
 
-// one block: exclusive scan of the cell counts in place, a copy as the fill's cursors, the total as an int64 (gsd_mesh_depth's scan)
-__global__ __launch_bounds__(1024) void mesh_volume_scan(int ncells, int* __restrict__ start, int* __restrict__ cursor,
-                                                         long long* __restrict__ total) {
-  __shared__ long long part[1024];
-  const int tid = threadIdx.x;
-  const int per = (ncells + 1023) / 1024;
-  const int lo = min(tid * per, ncells), hi = min(lo + per, ncells);
-  long long s = 0;
-  for (int c = lo; c < hi; ++c) s += start[c];
-  part[tid] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const long long add = tid >= o ? part[tid - o] : 0;
-    __syncthreads();
-    part[tid] += add;
-    __syncthreads();
-  }
-  long long run = part[tid] - s;
-  for (int c = lo; c < hi; ++c) {
-    const int n = start[c];
-    start[c] = (int)run;
-    cursor[c] = (int)run;
-    run += n;
-  }
-  if (tid == 1023) {
-    start[ncells] = (int)part[1023];
-    *total = part[1023];
-  }
+// one block: start becomes the exclusive sums of the cell counts, cursor a copy, *total the int64 total (gsd_cell_lists.h)
+__global__ __launch_bounds__(GSD_CELL_SCAN_THREADS) void mesh_volume_scan(int ncells, int* __restrict__ start, int* __restrict__ cursor,
+                                                                          long long* __restrict__ total) {
+  gsd_cell_scan(ncells, start, cursor, total);
 }
 
 // one thread per triangle: its id into every cell of the range the count pass walked
@@ -372,60 +350,15 @@ __global__ __launch_bounds__(64) void mesh_icp_lm_update(const McLm lm, int S, d
   for (int q = 0; q < 12; ++q) T[q] = transforms[(size_t)i * 12 + q];
   double lam = lambda[i];
   int count = lm.first ? 0 : accepted[i];
-  const bool take = lm.first || trial_row[(size_t)i * MC_ROW] < cur[0];      // strict, and a NaN never wins
+  const bool take = gsd_lm_accept(lm, trial_row[(size_t)i * MC_ROW], cur[0], lam, count);
   if (take) {
 #pragma unroll
     for (int q = 0; q < MC_ROW; ++q) cur[q] = trial_row[(size_t)i * MC_ROW + q];
 #pragma unroll
     for (int q = 0; q < 12; ++q) T[q] = trial_transforms[(size_t)i * 12 + q];
   }
-  if (!lm.first) {
-    lam = take ? fmax(lam * lm.down, lm.lambda_min) : fmin(lam * lm.up, lm.lambda_max);
-    count += take ? 1 : 0;
-  }
-  // (A + lam diag(A)) d = -b by Cholesky, in the order v1, v2, v3, w1, w2, w3
-  double M[6][6], Lc[6][6], z[6], d[6];
-  {
-    int q = 9;
-#pragma unroll
-    for (int j = 0; j < 6; ++j)
-#pragma unroll
-      for (int k = j; k < 6; ++k, ++q) M[j][k] = M[k][j] = j == k ? cur[q] + lam * cur[q] : cur[q];
-  }
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double piv = M[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) piv = piv - Lc[j][k] * Lc[j][k];
-    ok = ok && piv > 0.0 && isfinite(piv);
-    Lc[j][j] = sqrt(piv);
-#pragma unroll
-    for (int r = j + 1; r < 6; ++r) {
-      double s = M[r][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s = s - Lc[r][k] * Lc[j][k];
-      Lc[r][j] = s / Lc[j][j];
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    double s = -cur[3 + r];
-#pragma unroll
-    for (int k = 0; k < r; ++k) s = s - Lc[r][k] * z[k];
-    z[r] = s / Lc[r][r];
-  }
-#pragma unroll
-  for (int r = 5; r >= 0; --r) {
-    double s = z[r];
-#pragma unroll
-    for (int k = r + 1; k < 6; ++k) s = s - Lc[k][r] * d[k];
-    d[r] = s / Lc[r][r];
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) ok = ok && isfinite(d[k]);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) d[k] = ok ? fmin(fmax(d[k], -lm.max_step[k]), lm.max_step[k]) : 0.0;
+  double d[6];      // the step in the order v1, v2, v3, w1, w2, w3
+  gsd_lm_solve<6>(cur + 9, cur + 3, lam, 0x3fu, lm.max_step, d);
   // exp(xi): E = I + A K + B K^2, u = (I + B K + C K^2) v, K = [w]x, K^2 = w w^T - th2 I
   const double wx = d[3], wy = d[4], wz = d[5];
   const double th2 = (wx * wx + wy * wy) + wz * wz, th = sqrt(th2);
@@ -540,43 +473,26 @@ extern "C" int64_t gsd_mesh_volume_workspace(const gsd_mesh_volume* volume) {
   if (volume == nullptr || volume->nx < 1 || volume->ny < 1 || volume->nz < 1 || volume->nx > MC_MAX_AXIS || volume->ny > MC_MAX_AXIS ||
       volume->nz > MC_MAX_AXIS || mc_cells(volume) > MC_MAX_CELLS)
     return 0;
-  return 2 + (mc_cells(volume) + 1) + mc_cells(volume);   // int64 total | starts (cells + 1) | cursors (cells)
+  return gsd_cell_words(mc_cells(volume));
 }
 
 extern "C" int gsd_mesh_volume_count(const gsd_mesh_volume* volume, const float* tri, int T, int32_t* cells, int64_t cells_elems,
                                      void* stream) {
   const char* what = "gsd_mesh_volume_count";
   if (mc_check_volume(volume, what)) return GSD_ERR_BAD_ARG;
-  GSD_REQUIRE(tri && cells, GSD_ERR_BAD_ARG, "%s: null pointer", what);
-  GSD_REQUIRE(T >= 1 && T <= MC_MAX_T, GSD_ERR_BAD_ARG, "%s: %d triangles, 1..%d", what, T, MC_MAX_T);
-  GSD_REQUIRE(((uintptr_t)cells & 7) == 0, GSD_ERR_BAD_ARG, "%s: cells must be 8-byte aligned", what);
-  const int64_t need = gsd_mesh_volume_workspace(volume);
-  GSD_REQUIRE(cells_elems >= need, GSD_ERR_WORKSPACE, "%s: cells of %lld words, need %lld", what, (long long)cells_elems, (long long)need);
   const hipStream_t st = (hipStream_t)stream;
-  const int64_t nc = mc_cells(volume);
-  int* start = cells + 2;
-  if (hipError_t e = hipMemsetAsync(cells, 0, sizeof(int32_t) * (size_t)need, st); e != hipSuccess) {
-    gsd_set_error("%s: hipMemsetAsync: %s", what, hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  hipLaunchKernelGGL(mesh_volume_count, dim3((unsigned)ceil_div(T, 256)), dim3(256), 0, st, mc_vol(volume), tri, T, start);
-  GSD_LAUNCH_CHECK(what);
-  hipLaunchKernelGGL(mesh_volume_scan, dim3(1), dim3(1024), 0, st, (int)nc, start, start + nc + 1, reinterpret_cast<long long*>(cells));
-  GSD_LAUNCH_CHECK(what);
-  return GSD_OK;
+  const auto count = [&](int* start) {
+    hipLaunchKernelGGL(mesh_volume_count, dim3((unsigned)ceil_div(T, 256)), dim3(256), 0, st, mc_vol(volume), tri, T, start);
+  };
+  return gsd_cell_count(GsdCellCall{what, tri, T, MC_MAX_T, mc_cells(volume), cells, cells_elems, nullptr, 0}, count, mesh_volume_scan, st);
 }
 
 extern "C" int gsd_mesh_volume_fill(const gsd_mesh_volume* volume, const float* tri, int T, int32_t* cells, int64_t cells_elems,
                                     int32_t* list, int64_t list_elems, void* stream) {
   const char* what = "gsd_mesh_volume_fill";
-  if (mc_check_mesh(McMesh{volume, tri, T, cells, list, list_elems}, what)) return GSD_ERR_BAD_ARG;
-  const int64_t need = gsd_mesh_volume_workspace(volume);
-  GSD_REQUIRE(cells_elems >= need, GSD_ERR_WORKSPACE, "%s: cells of %lld words, need %lld", what, (long long)cells_elems, (long long)need);
-  const int64_t nc = mc_cells(volume);
-  hipLaunchKernelGGL(mesh_volume_fill, dim3((unsigned)ceil_div(T, 256)), dim3(256), 0, (hipStream_t)stream, mc_vol(volume), tri, T,
-                     cells + 2 + nc + 1, list, (long long)list_elems);
-  GSD_LAUNCH_CHECK(what);
-  return GSD_OK;
+  if (mc_check_volume(volume, what)) return GSD_ERR_BAD_ARG;
+  return gsd_cell_fill(GsdCellCall{what, tri, T, MC_MAX_T, mc_cells(volume), cells, cells_elems, list, list_elems}, mesh_volume_fill,
+                       mc_vol(volume), (hipStream_t)stream);
 }
 
 extern "C" int gsd_mesh_closest_points(const gsd_mesh_volume* volume, const float* tri, int T, const int32_t* cells, const int32_t* list,

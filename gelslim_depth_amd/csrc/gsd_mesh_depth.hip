@@ -51,6 +51,8 @@
 //   mesh_pose_rows, for every G.  gsd_mesh_pose_score_widths with G = 1 therefore makes gsd_mesh_pose_score's launches by
 //   construction: it is the same call of md_score on another workspace layout.
 #include "gsd_common.h"
+#include "gsd_cell_lists.h"      // the count / scan / fill sequence of the cell lists
+#include "gsd_lm_step.h"         // the LM accept rule and solve of mesh_pose_lm_update
 
 #include <math.h>
 
@@ -133,35 +135,10 @@ __global__ __launch_bounds__(256) void mesh_records_count(const MdGrid G, const 
     for (int ix = ix0; ix <= ix1; ++ix) atomicAdd(count + (size_t)iy * G.nx + ix, 1);
 }
 
-// one block: exclusive scan of the cell counts, in place (start[c], start[ncells] = total), a copy as the fill's cursors,
-// and the total as an int64 (the int32 starts wrap beyond 2^31 - 1 pairs; the caller reads the total before it fills)
-__global__ __launch_bounds__(1024) void mesh_scan(int ncells, int* __restrict__ start, int* __restrict__ cursor,
-                                                  long long* __restrict__ total) {
-  __shared__ long long part[1024];
-  const int tid = threadIdx.x;
-  const int per = (ncells + 1023) / 1024;
-  const int lo = min(tid * per, ncells), hi = min(lo + per, ncells);
-  long long s = 0;
-  for (int c = lo; c < hi; ++c) s += start[c];
-  part[tid] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const long long add = tid >= o ? part[tid - o] : 0;
-    __syncthreads();
-    part[tid] += add;
-    __syncthreads();
-  }
-  long long run = part[tid] - s;   // exclusive prefix of this thread's run
-  for (int c = lo; c < hi; ++c) {
-    const int n = start[c];
-    start[c] = (int)run;
-    cursor[c] = (int)run;
-    run += n;
-  }
-  if (tid == 1023) {
-    start[ncells] = (int)part[1023];
-    *total = part[1023];
-  }
+// one block: start becomes the exclusive sums of the cell counts, cursor a copy, *total the int64 total (gsd_cell_lists.h)
+__global__ __launch_bounds__(GSD_CELL_SCAN_THREADS) void mesh_scan(int ncells, int* __restrict__ start, int* __restrict__ cursor,
+                                                                   long long* __restrict__ total) {
+  gsd_cell_scan(ncells, start, cursor, total);
 }
 
 // one thread per triangle: its id into every cell of the same range the count pass walked
@@ -632,65 +609,14 @@ __global__ __launch_bounds__(64) void mesh_pose_lm_update(const MdLm lm, int B, 
   float t1 = pose[3 * (size_t)i], t2 = pose[3 * (size_t)i + 1], th = pose[3 * (size_t)i + 2], g = width[i];
   double lam = lambda[i];
   int count = lm.first ? 0 : accepted[i];
-  const double trial_sq = trial_row[(size_t)i * MD_NROW];
-  const bool take = lm.first || trial_sq < cur[0];      // strict, and a NaN never wins
+  const bool take = gsd_lm_accept(lm, trial_row[(size_t)i * MD_NROW], cur[0], lam, count);
   if (take) {
 #pragma unroll
     for (int q = 0; q < MD_NROW; ++q) cur[q] = trial_row[(size_t)i * MD_NROW + q];
     t1 = trial_pose[3 * (size_t)i], t2 = trial_pose[3 * (size_t)i + 1], th = trial_pose[3 * (size_t)i + 2], g = trial_width[i];
   }
-  if (!lm.first) {
-    lam = take ? fmax(lam * lm.down, lm.lambda_min) : fmin(lam * lm.up, lm.lambda_max);
-    count += take ? 1 : 0;
-  }
-  // (A + lam diag(A)) d = -b by Cholesky, in the order a1, a2, theta, g
-  double M[4][4], rhs[4], Lc[4][4], z[4], d[4];
-  {
-    int s = 6;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int k = j; k < 4; ++k, ++s) {
-        const bool both = ((lm.free_mask >> j) & 1) && ((lm.free_mask >> k) & 1);
-        const double a = j == k ? cur[s] + lam * cur[s] : cur[s];
-        M[j][k] = M[k][j] = both ? a : (j == k ? 1.0 : 0.0);
-      }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) rhs[j] = ((lm.free_mask >> j) & 1) ? -cur[2 + j] : 0.0;
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    double piv = M[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) piv = piv - Lc[j][k] * Lc[j][k];
-    ok = ok && piv > 0.0 && isfinite(piv);
-    Lc[j][j] = sqrt(piv);
-#pragma unroll
-    for (int r = j + 1; r < 4; ++r) {
-      double s = M[r][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s = s - Lc[r][k] * Lc[j][k];
-      Lc[r][j] = s / Lc[j][j];
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    double s = rhs[r];
-#pragma unroll
-    for (int k = 0; k < r; ++k) s = s - Lc[r][k] * z[k];
-    z[r] = s / Lc[r][r];
-  }
-#pragma unroll
-  for (int r = 3; r >= 0; --r) {
-    double s = z[r];
-#pragma unroll
-    for (int k = r + 1; k < 4; ++k) s = s - Lc[k][r] * d[k];
-    d[r] = s / Lc[r][r];
-  }
-  ok = ok && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]) && isfinite(d[3]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) d[k] = ok ? fmin(fmax(d[k], -lm.max_step[k]), lm.max_step[k]) : 0.0;
+  double d[4];      // the step in the order a1, a2, theta, g
+  gsd_lm_solve<4>(cur + 6, cur + 2, lam, (unsigned)lm.free_mask, lm.max_step, d);
   if (take) {
 #pragma unroll
     for (int q = 0; q < MD_NROW; ++q) row[(size_t)i * MD_NROW + q] = cur[q];
@@ -858,47 +784,29 @@ extern "C" int gsd_mesh_depth_plan(const double* bbox, double cell_mm, gsd_mesh_
 
 extern "C" int64_t gsd_mesh_depth_workspace(const gsd_mesh_grid* grid) {
   if (grid == nullptr || grid->nx < 1 || grid->ny < 1 || grid->nx > MD_MAX_N || grid->ny > MD_MAX_N) return 0;
-  return 2 + (md_cells(grid) + 1) + md_cells(grid);   // int64 total | starts (cells + 1) | cursors (cells)
+  return gsd_cell_words(md_cells(grid));
 }
 
 extern "C" int gsd_mesh_depth_count(const gsd_mesh_grid* grid, const float* tri, int T, float* records, int32_t* cells,
                                     int64_t cells_elems, void* stream) {
-  if (md_check_grid(grid, "gsd_mesh_depth_count")) return GSD_ERR_BAD_ARG;
-  GSD_REQUIRE(tri && records && cells, GSD_ERR_BAD_ARG, "gsd_mesh_depth_count: null pointer");
-  GSD_REQUIRE(T >= 1 && T <= MD_MAX_T, GSD_ERR_BAD_ARG, "gsd_mesh_depth_count: %d triangles, 1..%d", T, MD_MAX_T);
-  GSD_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)cells & 7) == 0, GSD_ERR_BAD_ARG,
-              "gsd_mesh_depth_count: records must be 16-byte aligned, cells 8-byte aligned");
-  GSD_REQUIRE(cells_elems >= gsd_mesh_depth_workspace(grid), GSD_ERR_WORKSPACE, "gsd_mesh_depth_count: cells of %lld words, need %lld",
-              (long long)cells_elems, (long long)gsd_mesh_depth_workspace(grid));
+  const char* what = "gsd_mesh_depth_count";
+  if (md_check_grid(grid, what)) return GSD_ERR_BAD_ARG;
+  GSD_REQUIRE(records != nullptr, GSD_ERR_BAD_ARG, "%s: null pointer", what);
+  GSD_REQUIRE(((uintptr_t)records & 15) == 0, GSD_ERR_BAD_ARG, "%s: records must be 16-byte aligned", what);
   const hipStream_t st = (hipStream_t)stream;
-  const int64_t nc = md_cells(grid);
-  int* start = cells + 2;
-  if (hipError_t e = hipMemsetAsync(cells, 0, sizeof(int32_t) * (size_t)gsd_mesh_depth_workspace(grid), st); e != hipSuccess) {
-    gsd_set_error("gsd_mesh_depth_count: hipMemsetAsync: %s", hipGetErrorString(e));
-    return GSD_ERR_HIP;
-  }
-  hipLaunchKernelGGL(mesh_records_count, dim3((unsigned)ceil_div(T, 256)), dim3(256), 0, st, md_grid(grid), tri, T, records, start);
-  GSD_LAUNCH_CHECK("gsd_mesh_depth_count records");
-  hipLaunchKernelGGL(mesh_scan, dim3(1), dim3(1024), 0, st, (int)nc, start, start + nc + 1, reinterpret_cast<long long*>(cells));
-  GSD_LAUNCH_CHECK("gsd_mesh_depth_count scan");
-  return GSD_OK;
+  const auto count = [&](int* start) {
+    hipLaunchKernelGGL(mesh_records_count, dim3((unsigned)ceil_div(T, 256)), dim3(256), 0, st, md_grid(grid), tri, T, records, start);
+  };
+  return gsd_cell_count(GsdCellCall{what, tri, T, MD_MAX_T, md_cells(grid), cells, cells_elems, nullptr, 0}, count, mesh_scan, st);
 }
 
 extern "C" int gsd_mesh_depth_fill(const gsd_mesh_grid* grid, const float* records, int T, int32_t* cells, int64_t cells_elems,
                                    int32_t* list, int64_t list_elems, void* stream) {
-  if (md_check_grid(grid, "gsd_mesh_depth_fill")) return GSD_ERR_BAD_ARG;
-  GSD_REQUIRE(records && cells && list, GSD_ERR_BAD_ARG, "gsd_mesh_depth_fill: null pointer");
-  GSD_REQUIRE(T >= 1 && T <= MD_MAX_T, GSD_ERR_BAD_ARG, "gsd_mesh_depth_fill: %d triangles, 1..%d", T, MD_MAX_T);
-  GSD_REQUIRE(((uintptr_t)records & 15) == 0, GSD_ERR_BAD_ARG, "gsd_mesh_depth_fill: records must be 16-byte aligned");
-  GSD_REQUIRE(cells_elems >= gsd_mesh_depth_workspace(grid), GSD_ERR_WORKSPACE, "gsd_mesh_depth_fill: cells of %lld words, need %lld",
-              (long long)cells_elems, (long long)gsd_mesh_depth_workspace(grid));
-  GSD_REQUIRE(list_elems >= 1 && list_elems <= INT32_MAX, GSD_ERR_BAD_ARG, "gsd_mesh_depth_fill: list of %lld entries, 1..2^31-1",
-              (long long)list_elems);
-  const int64_t nc = md_cells(grid);
-  hipLaunchKernelGGL(mesh_fill, dim3((unsigned)ceil_div(T, 256)), dim3(256), 0, (hipStream_t)stream, md_grid(grid), records, T,
-                     cells + 2 + nc + 1, list, (long long)list_elems);
-  GSD_LAUNCH_CHECK("gsd_mesh_depth_fill");
-  return GSD_OK;
+  const char* what = "gsd_mesh_depth_fill";
+  if (md_check_grid(grid, what)) return GSD_ERR_BAD_ARG;
+  GSD_REQUIRE(((uintptr_t)records & 15) == 0, GSD_ERR_BAD_ARG, "%s: records must be 16-byte aligned", what);
+  return gsd_cell_fill(GsdCellCall{what, records, T, MD_MAX_T, md_cells(grid), cells, cells_elems, list, list_elems}, mesh_fill,
+                       md_grid(grid), (hipStream_t)stream);
 }
 
 extern "C" int64_t gsd_mesh_depth_render_workspace(int N) { return N > 0 ? (int64_t)N * MD_POSE : 0; }

@@ -214,60 +214,17 @@ __global__ __launch_bounds__(TE_BLOCK) void touch_extract_count(const TeView V, 
                                                                 long long* __restrict__ block_count) {
   __shared__ int wave_n[TE_BLOCK / 64];
   const int cell = (int)blockIdx.x * TE_BLOCK + (int)threadIdx.x;      // below 2^30 + 256
-  int n = te_count(te_cell(V, acc, weight, cell).corners);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-  if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    n = 0;
-#pragma unroll
-    for (int w = 0; w < TE_BLOCK / 64; ++w) n += wave_n[w];
-    block_count[blockIdx.x] = n;
-  }
+  const int n = gsd_block_count<TE_BLOCK>(gsd_wave_sum(te_count(te_cell(V, acc, weight, cell).corners)), wave_n);
+  if (threadIdx.x == 0) block_count[blockIdx.x] = n;
 }
 
-// One block: block totals -> exclusive offsets in place, pass by pass with a carry (gsd_depth_points' scan on int64); then the total,
+// One block: block totals -> exclusive offsets in place, pass by pass with a carry; then the total,
 // to the head of the workspace and to the caller's scalar.
 __global__ __launch_bounds__(TE_SCAN_THREADS) void touch_extract_scan(int nblocks, long long* block_off, long long* __restrict__ total_ws,
                                                                       long long* __restrict__ total) {
-  __shared__ long long wave_sum[TE_SCAN_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  long long carry = 0;
-  for (int base = 0; base < nblocks; base += TE_SCAN_PASS) {
-    const int i0 = base + tid * TE_SCAN_PER;      // nblocks is below 2^22
-    long long v[TE_SCAN_PER];
-    long long s = 0;
-#pragma unroll
-    for (int j = 0; j < TE_SCAN_PER; ++j) {
-      v[j] = i0 + j < nblocks ? block_off[i0 + j] : 0;
-      s += v[j];
-    }
-    long long inc = s;                              // inclusive scan over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wave_sum[wave] = inc;
-    __syncthreads();
-    long long before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < TE_SCAN_THREADS / 64; ++w) {
-      const long long x = wave_sum[w];
-      before += w < wave ? x : 0;
-      all += x;
-    }
-    long long run = carry + before + inc - s;
-#pragma unroll
-    for (int j = 0; j < TE_SCAN_PER; ++j) {
-      if (i0 + j < nblocks) block_off[i0 + j] = run;
-      run += v[j];
-    }
-    carry += all;
-    __syncthreads();                               // wave_sum is reused
-  }
-  if (tid == 0) *total_ws = carry, *total = carry;
+  const long long carry = gsd_block_exclusive_scan<long long, TE_SCAN_THREADS, TE_SCAN_PER>(
+      nblocks, [&](int i) { return block_off[i]; }, [&](int i, long long run) { block_off[i] = run; });      // nblocks is below 2^22
+  if (threadIdx.x == 0) *total_ws = carry, *total = carry;
 }
 
 // vertex on the edge between the cube corners lo < hi of cell C: section 24's arithmetic, fp64, one rounding at the store
@@ -292,21 +249,11 @@ __global__ __launch_bounds__(TE_BLOCK) void touch_extract_write(const TeView V, 
                                                                 long long capacity, long long rows, int nblocks, float* __restrict__ triangles,
                                                                 int* __restrict__ cell_out) {
   __shared__ int wave_n[TE_BLOCK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int cell = (int)blockIdx.x * TE_BLOCK + (int)threadIdx.x;
   const TeCell C = te_cell(V, acc, weight, cell);
   const int n = te_count(C.corners);
-  int inc = n;                                     // inclusive scan over the wave
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wave_n[wave] = inc;
-  __syncthreads();
-  int before = 0;
-#pragma unroll
-  for (int w = 0; w < TE_BLOCK / 64; ++w) before += w < wave ? wave_n[w] : 0;
+  const int inc = gsd_wave_inclusive_scan(n);
+  const int before = gsd_block_waves_before<TE_BLOCK>(inc, wave_n);
   const long long limit = capacity > 0 && capacity < rows ? capacity : rows;      // rows a triangle may go to
   long long row = block_off[blockIdx.x] + before + (inc - n);
   if (n > 0) {

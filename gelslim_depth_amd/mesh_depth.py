@@ -156,6 +156,23 @@ def default_cell_mm(a: np.ndarray, b: np.ndarray, target: float = 8.0) -> float:
     return max(math.sqrt(target * area / a.shape[0]) - s, 0.5 * s, ext / 512.0)
 
 
+def _build_cell_lists(owner: str, entry: str, device, words: int, count, fill):
+    """The workspace-to-list tail of MeshGrid and MeshVolume: allocate the `words` int32 of cells, count(cells, words, stream),
+    read the int64 total of (cell, triangle) pairs back (the one host read of a mesh), allocate the list and
+    fill(cells, words, list, entries, stream).  Returns (cells, pairs, list); with no pair (every triangle is skipped) the list is
+    one zero and nothing is filled."""
+    cells = torch.empty((words,), device=device, dtype=torch.int32)
+    check(count(cells.data_ptr(), words, L.stream_ptr()), f"{entry}_count")
+    pairs = int(cells[:2].view(torch.int64).item())
+    if pairs >= 1 << 31:
+        raise MeshDepthError(f"{owner}: {pairs} (cell, triangle) pairs, at most 2^31 - 1: use larger cells")
+    if pairs == 0:
+        return cells, pairs, torch.zeros((1,), device=device, dtype=torch.int32)
+    lst = torch.empty((pairs,), device=device, dtype=torch.int32)
+    check(fill(cells.data_ptr(), words, lst.data_ptr(), lst.numel(), L.stream_ptr()), f"{entry}_fill")
+    return cells, pairs, lst
+
+
 class MeshGrid:
     """A mesh prepared for `render_depth`: the per-triangle records and the per-cell triangle lists on the device, built once.
 
@@ -211,19 +228,11 @@ class MeshGrid:
         with torch.cuda.device(self.device):
             self._tri = torch.from_numpy(tri.reshape(-1, 9)).to(self.device)
             self.records = torch.empty((self.triangles, L.GSD_MESH_RECORD_FLOATS), device=self.device, dtype=torch.float32)
-            words = int(lib.gsd_mesh_depth_workspace(C.byref(self.grid)))
-            self.cells = torch.empty((words,), device=self.device, dtype=torch.int32)
-            check(lib.gsd_mesh_depth_count(C.byref(self.grid), self._tri.data_ptr(), self.triangles, self.records.data_ptr(),
-                                           self.cells.data_ptr(), words, L.stream_ptr()), "mesh_depth_count")
-            self.pairs = int(self.cells[:2].view(torch.int64).item())         # the one host read of a mesh
-            if self.pairs >= 1 << 31:
-                raise MeshDepthError(f"MeshGrid: {self.pairs} (cell, triangle) pairs, at most 2^31 - 1: use larger cells")
-            self.list = torch.empty((max(self.pairs, 1),), device=self.device, dtype=torch.int32)
-            if self.pairs == 0:
-                self.list.zero_()         # every triangle is degenerate in this plane: all lists are empty
-            else:
-                check(lib.gsd_mesh_depth_fill(C.byref(self.grid), self.records.data_ptr(), self.triangles, self.cells.data_ptr(),
-                                              words, self.list.data_ptr(), self.list.numel(), L.stream_ptr()), "mesh_depth_fill")
+            grid, rec, n = C.byref(self.grid), self.records.data_ptr(), self.triangles
+            self.cells, self.pairs, self.list = _build_cell_lists(
+                "MeshGrid", "mesh_depth", self.device, int(lib.gsd_mesh_depth_workspace(grid)),
+                lambda *ws: lib.gsd_mesh_depth_count(grid, self._tri.data_ptr(), n, rec, *ws),
+                lambda *ws: lib.gsd_mesh_depth_fill(grid, rec, n, *ws))
             del self._tri
 
     @property

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib as L
 from ._lib import check, lib
-from .mesh_depth import MeshDepthError, _need_cuda, first_argmin
+from .mesh_depth import MeshDepthError, _build_cell_lists, _need_cuda, first_argmin
 
 ICP_ROW = L.GSD_ICP_ROW      # columns of a row of `icp_rows`
 _KINDS = {"plane": 0, "point": 1}
@@ -92,19 +92,10 @@ class MeshVolume:
         self.cell_mm = float(self.volume.cell)
         with torch.cuda.device(self.device):
             self.tri = torch.from_numpy(tri.reshape(-1, 9)).to(self.device)
-            words = int(lib.gsd_mesh_volume_workspace(C.byref(self.volume)))
-            self.cells = torch.empty((words,), device=self.device, dtype=torch.int32)
-            check(lib.gsd_mesh_volume_count(C.byref(self.volume), self.tri.data_ptr(), self.triangles, self.cells.data_ptr(), words,
-                                            L.stream_ptr()), "mesh_volume_count")
-            self.pairs = int(self.cells[:2].view(torch.int64).item())         # the one host read of a mesh
-            if self.pairs >= 1 << 31:
-                raise MeshDepthError(f"MeshVolume: {self.pairs} (cell, triangle) pairs, at most 2^31 - 1: use larger cells")
-            self.list = torch.empty((max(self.pairs, 1),), device=self.device, dtype=torch.int32)
-            if self.pairs == 0:
-                self.list.zero_()         # every triangle is skipped: all lists are empty
-            else:
-                check(lib.gsd_mesh_volume_fill(C.byref(self.volume), self.tri.data_ptr(), self.triangles, self.cells.data_ptr(), words,
-                                               self.list.data_ptr(), self.list.numel(), L.stream_ptr()), "mesh_volume_fill")
+            geometry = (C.byref(self.volume), self.tri.data_ptr(), self.triangles)
+            self.cells, self.pairs, self.list = _build_cell_lists(
+                "MeshVolume", "mesh_volume", self.device, int(lib.gsd_mesh_volume_workspace(C.byref(self.volume))),
+                lambda *ws: lib.gsd_mesh_volume_count(*geometry, *ws), lambda *ws: lib.gsd_mesh_volume_fill(*geometry, *ws))
 
     @property
     def shape(self):

@@ -20,6 +20,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
 
 DEV = "cuda:0"
@@ -79,8 +80,10 @@ def cdist_floor(verts, pts, pairs=1 << 27):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(HERE, "closest_points_times.txt"))
+    ap.add_argument("--no-compositions", action="store_true", help="skip the torch compositions (region, cdist) and the large clouds")
     args = ap.parse_args()
     import mesh_depth_ref as R
+    from cell_list_phases import build_phases
     from gelslim_depth_amd.mesh_depth import read_stl
     from gelslim_depth_amd.mesh_register import MeshVolume, closest_points, icp_rows, register_cloud
     meshes = {"marble": (read_stl(os.path.join(os.path.dirname(HERE), "tests", "golden", "meshes", "marble.stl")), 1000.0),
@@ -91,9 +94,15 @@ def main():
     for name, (tri, scale) in meshes.items():
         rng = np.random.Generator(np.random.PCG64(1))
         vol = MeshVolume(tri, scale, DEV)
+        for mult in (1.0, 0.5):      # the default cells and a grid twice as fine
+            v = MeshVolume(tri, scale, DEV, vol.cell_mm * mult)
+            count_ms, fill_ms = build_phases(lambda: MeshVolume(tri, scale, DEV, vol.cell_mm * mult), "gsd_mesh_volume")
+            lines.append(f"{name:18s} cell lists, cells x {mult:g} ({v.volume.nx * v.volume.ny * v.volume.nz} cells, {v.pairs} pairs): "
+                         f"count + scan {count_ms:.4f} ms, fill {fill_ms:.4f} ms")
+            print(lines[-1], flush=True)
         tri64 = (vol.tri.view(-1, 3, 3)).double()
         verts = torch.unique(vol.tri.view(-1, 3), dim=0)
-        for n in (10 ** 4, 2600000):
+        for n in (10 ** 4,) if args.no_compositions else (10 ** 4, 2600000):
             cloud = R.sample_surface(np.float64(tri) * scale, n, seed=3) + rng.normal(0.0, 0.05, (n, 3))
             for order in ("shuffled", "sorted"):
                 if order == "sorted":
@@ -104,13 +113,13 @@ def main():
                 eye = torch.eye(4, dtype=torch.float64, device=DEV)
                 t_rows = timed(lambda: icp_rows(vol, pts, eye))
                 t_region = float("nan")
-                if n <= 10 ** 4:
+                if n <= 10 ** 4 and not args.no_compositions:
                     ids, d2 = region_torch(tri64, pts)
                     worst = float(((d2 - out.sq_distance).abs() / out.sq_distance.clamp_min(1e-300)).max())
                     lines.append(f"  region method against closest_points, {n} points: {int((d2 != out.sq_distance).sum())} d^2 differ in bits, "
                                  f"largest relative gap {worst:.2e}, {int((ids != out.triangle).sum())} ids differ (torch.min keeps no id rule)")
                     t_region = timed(lambda: region_torch(tri64, pts), warm=1, runs=3 if tri.shape[0] > 10000 else 10)
-                t_cdist = timed(lambda: cdist_floor(verts, pts), warm=1, runs=3 if n > 10 ** 4 else 10)
+                t_cdist = float("nan") if args.no_compositions else timed(lambda: cdist_floor(verts, pts), warm=1, runs=3 if n > 10 ** 4 else 10)
                 g = vol.volume
                 lines.append(f"{name:18s} {f'{g.nx}x{g.ny}x{g.nz}':>14s} {vol.pairs:9d} {n:9d} {order:>8s} {t_closest:9.3f} {t_rows:9.3f} "
                              f"{t_region:9.3f} {t_cdist:9.3f} {n / t_closest / 1e3:10.2f}")

@@ -14,6 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import mesh_depth_ref as R  # noqa: E402
+from cell_list_phases import build_phases  # noqa: E402
 
 from gelslim_depth_amd.mesh_depth import MeshGrid, render_depth  # noqa: E402
 
@@ -57,6 +58,11 @@ def median(fn):
 
 dev_ms, host_ms = median(lambda: MeshGrid(tri, 1.0, "+y+z", "cuda"))
 grid = MeshGrid(tri, 1.0, "+y+z", "cuda")
+for mult in (1.0, min([float(c) for c in a.cells.split(",") if c] + [0.5])):      # the default cells and the finest grid of --cells
+    g = MeshGrid(tri, 1.0, "+y+z", "cuda", cell_mm=grid.cell_mm * mult)
+    count_ms, fill_ms = build_phases(lambda: MeshGrid(tri, 1.0, "+y+z", "cuda", cell_mm=grid.cell_mm * mult), "gsd_mesh_depth", a.warmup, a.reps)
+    print(f"cell lists, cells x {mult:g} ({g.grid.nx * g.grid.ny} cells, {g.pairs} pairs): records + count + scan {count_ms:.4f} ms, fill "
+          f"{fill_ms:.4f} ms (device events; median of {a.reps} after {a.warmup})")
 print(f"{grid!r}")
 print(f"MeshGrid build, {tri.shape[0]} triangles: {host_ms:.2f} ms on the host clock (numpy preparation, upload, count, the one "
       f"read, fill), {dev_ms:.2f} ms between device events; median of {a.reps} after {a.warmup}")

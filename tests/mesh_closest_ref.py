@@ -160,6 +160,20 @@ def icp_row(tri32, points32, T, D=None, kind="plane", weights=None, pc_scale=1.0
     return (np.array([math.fsum(t[:, q]) for q in range(ROW)]), np.array([math.fsum(np.abs(t[:, q])) for q in range(ROW)]))
 
 
+# ---- the cells of MeshVolume ------------------------------------------------------------------------------------------------
+CELL_EPS = 1e-6      # of a cell: how far a triangle's index range is widened on either side
+
+
+def volume_cell_ranges(tri32, origin, inv_cell, dims, pc_scale=1.0):
+    """mc_cell_range in numpy, fp64: (T, 3) lowest and highest (ix, iy, iz) of every triangle's widened box."""
+    v = vertices(tri32, pc_scale)
+
+    def cell(x, eps):
+        f = np.floor((x - np.asarray(origin, float)) * float(inv_cell) + eps)
+        return np.clip(f, 0, np.asarray(dims) - 1).astype(np.int64)
+    return cell(v.min(axis=1), -CELL_EPS), cell(v.max(axis=1), CELL_EPS)
+
+
 # ---- the damped step --------------------------------------------------------------------------------------------------------
 def lm_solve(row, lam, max_step):
     """(A + lam diag A) xi = -b by Cholesky in the order v1 v2 v3 w1 w2 w3; a bad pivot or a non-finite solution gives 0."""

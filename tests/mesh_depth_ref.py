@@ -308,3 +308,59 @@ def erode(mask, k):
         for dx in range(2 * k + 1):
             out &= pad[dy:dy + h, dx:dx + w]
     return out
+
+
+# ---- the per-cell triangle lists of MeshGrid and MeshVolume -------------------------------------------------------------
+CELL_LIST_SKIPPED = 12      # the index of the degenerate triangle of cell_list_mesh
+
+
+def cell_list_mesh(cells):
+    """The twelve-triangle box, one degenerate triangle inside it (two coincident corners, index CELL_LIST_SKIPPED) and three
+    tilted triangles of different sizes inside it, which cover different parts of any grid so that the counts differ from cell to
+    cell whichever axis one looks along.  Cells of 1 mm give exactly cells[k] of them along axis k: the planners take
+    ceil((extent + 0.002) / 1), and the extent is cells[k] - 0.5."""
+    size = np.array([float(n) - 0.5 for n in cells])
+    inside = np.array([[0.125, 0.0, 0.0], [0.125, 0.0, 0.0], [-0.125, 0.125, 0.0625]])
+    tilted = 0.5 * size * np.array([[[-0.9, -0.9, -0.9], [0.1, -0.5, 0.3], [-0.3, 0.6, -0.2]],
+                                    [[0.2, 0.1, -0.7], [0.95, 0.3, 0.8], [0.5, 0.9, 0.1]],
+                                    [[-0.1, -0.2, 0.1], [0.05, -0.1, 0.3], [-0.05, 0.1, 0.15]]])
+    return _f32(np.concatenate((box(tuple(size)).astype(float), inside[None], tilted)))
+
+
+def grid_cell_ranges(records, x0, y0, inv_cell, nx, ny):
+    """md_cell_range in numpy, fp32 throughout: (T, 2) lowest and highest (ix, iy) of every record's vertex box -- the x are sorted
+    in a record, the y are not."""
+    rec = np.asarray(records, np.float32)
+
+    def cell(v, g0, n):
+        f = np.floor((v - np.float32(g0)) * np.float32(inv_cell))
+        return np.clip(f, 0, n - 1).astype(np.int64)
+    ys = rec[:, [1, 3, 5]]
+    return (np.stack((cell(rec[:, 0], x0, nx), cell(ys.min(axis=1), y0, ny)), axis=1),
+            np.stack((cell(rec[:, 4], x0, nx), cell(ys.max(axis=1), y0, ny)), axis=1))
+
+
+def check_cell_lists(cells, entries, pairs, dims, triangles, listed, lo, hi):
+    """What a built cell list must satisfy.  cells: the int32 workspace (total as int64 | start[ncells + 1] | cursor[ncells]) after
+    the fill; entries: the list; dims: cells per axis, x first (the x index runs fastest); listed: the ids that the one-cell build
+    lists; lo, hi: (T, len(dims)) inclusive index ranges by the numpy rule."""
+    ncells = int(np.prod(dims))
+    total = int(cells[:2].view(np.int64)[0])
+    start, cursor = cells[2:2 + ncells + 1].astype(np.int64), cells[2 + ncells + 1:2 + 2 * ncells + 1].astype(np.int64)
+    assert cells.size == 2 + 2 * ncells + 1
+    assert start[0] == 0 and (np.diff(start) >= 0).all()
+    assert start[ncells] == total == pairs == entries.size
+    assert np.array_equal(cursor, start[1:])
+    assert entries.min() >= 0 and entries.max() < triangles and not (entries == CELL_LIST_SKIPPED).any()
+    cell_of = np.repeat(np.arange(ncells), np.diff(start))
+    got = np.stack((cell_of, entries.astype(np.int64)), axis=1)
+    got = got[np.lexsort((got[:, 1], got[:, 0]))]
+    assert np.unique(got, axis=0).shape == got.shape, "an id twice in one cell"
+    want = []
+    for t in listed:
+        axes = np.meshgrid(*[np.arange(lo[t, k], hi[t, k] + 1) for k in range(len(dims))][::-1], indexing="ij")      # slowest first
+        index = np.zeros_like(axes[0])
+        for k, a in zip(range(len(dims) - 1, -1, -1), axes):
+            index = index * dims[k] + a
+        want += [(int(c), int(t)) for c in index.ravel()]
+    assert np.array_equal(got, np.array(sorted(want), np.int64).reshape(-1, 2))

@@ -292,3 +292,76 @@ def test_icp_rows_against_the_twin(n):
                     if D is not None and n >= 1023:
                         assert 0 < want[1] < n - 1          # the limit bites, and the NaN row is in no count
     print(f"n = {n}: worst |row - twin| / bound = {worst:.3g}")
+
+
+# ---- the cell lists -----------------------------------------------------------------------------------------------------------
+# cells per axis at 1 mm: one cell, then the counts around the multiples 4096 and 8192 of the scan's pass of 2048 counts: one short
+# of two passes, exactly two, one count in a third pass, two counts in a fifth (8193 = 3 * 2731 needs an axis of 2731 cells, more
+# than the 1024 allowed: 8194 is the nearest count above 8192)
+@pytest.mark.parametrize("dims, ncells", (((1, 1, 1), 1), ((15, 13, 21), 4095), ((16, 16, 16), 4096), ((17, 241, 1), 4097),
+                                          ((17, 241, 2), 8194)))
+def test_cell_lists_across_the_scan_pass_boundary(dims, ncells):
+    from gelslim_depth_amd.mesh_register import MeshVolume
+    tri = R.cell_list_mesh(dims)
+    one = MeshVolume(tri, 1.0, DEV, 1000.0)
+    assert one.shape == (1, 1, 1) and one.skipped == 1
+    listed = np.sort(one.list.cpu().numpy())
+    assert np.array_equal(listed, np.delete(np.arange(len(tri)), R.CELL_LIST_SKIPPED)) and len(tri) == 16
+    vol = MeshVolume(tri, 1.0, DEV, 1.0)
+    assert vol.shape == dims[::-1] and int(np.prod(dims)) == ncells
+    g = vol.volume
+    lo, hi = M.volume_cell_ranges(tri, (g.x0, g.y0, g.z0), g.inv_cell, dims)
+    R.check_cell_lists(vol.cells.cpu().numpy(), vol.list.cpu().numpy(), vol.pairs, dims, len(tri), listed, lo, hi)
+
+
+# ---- the damped step's edge rows ------------------------------------------------------------------------------------------------
+def icp_spd_row(rng, b_scale=1.0):
+    Jm = rng.normal(0, 1, (40, 6)) * np.array([1.0, 0.7, 1.3, 3.0, 2.0, 2.5])
+    e = rng.normal(0, 0.1, 40)
+    A, b = Jm.T @ Jm, (Jm.T @ e) * b_scale
+    return np.concatenate(([e @ e, 40.0, e @ e], b, [A[j, k] for j, k in M.PAIRS])), A
+
+
+def test_lm_update_edge_rows_equal_the_twin_bit_for_bit():
+    """Three starts in one call: (0) an accepted trial whose matrix is singular in one parameter -- the gate gives the step 0 and
+    the next trial is the state; (1) a NaN trial cost -- not accepted, the step comes from the old row, unclipped in translation;
+    (2) an accepted trial whose right-hand side is so large that the clip binds in every component.  The rotation's clip of
+    1e-9 rad keeps |omega| below 1e-8, so exp(xi) takes its series branch and no sine or cosine stands between the device and
+    M.lm_update: every output is compared bit for bit."""
+    from gelslim_depth_amd import _lib as L
+    rng = np.random.Generator(np.random.PCG64(31))
+    max_step = (1e-3, 1e-3, 1e-3, 1e-9, 1e-9, 1e-9)
+    cur = np.stack([icp_spd_row(rng, s)[0] for s in (1.0, 1e-3, 1.0)])
+    trial = np.stack([icp_spd_row(rng, s)[0] for s in (1.0, 1.0, 1e6)])
+    trial[0, 0], trial[1, 0], trial[2, 0] = 0.5 * cur[0, 0], np.nan, 0.5 * cur[2, 0]
+    for q, (j, k) in enumerate(M.PAIRS):
+        if 4 in (j, k):
+            trial[0, 9 + q] = 0.0                     # w2 drops out of start 0's trial matrix
+    trial[0, 3 + 4] = 0.0
+    T0 = np.stack([np.asarray(t, float) for t in TRANSFORMS])
+    T1 = T0[[1, 2, 0]].copy()
+    lam0 = np.array([1e-3, 0.25, 5e-12])
+    free = M.lm_solve(cur[1], lam0[1] * 10.0, (np.inf,) * 6)
+    assert (np.abs(free[:3]) < 1e-3).all() and free[:3].all()
+    free = M.lm_solve(trial[2], 1e-12, (np.inf,) * 6)
+    assert (np.abs(free) > np.asarray(max_step)).all()
+    lm = L.gsd_icp_lm()
+    lm.down, lm.up, lm.lambda_min, lm.lambda_max, lm.first = 0.1, 10.0, 1e-12, 1e12, 0
+    lm.max_step[:] = max_step
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    state, lam, row, t_state, t_row = dev(T0), dev(lam0), dev(cur), dev(T1), dev(trial)
+    trace = torch.zeros(3, dtype=torch.float64, device=DEV)
+    accepted = torch.full((3,), 5, dtype=torch.int32, device=DEV)
+    last = torch.zeros((3, 6), dtype=torch.float64, device=DEV)
+    assert L.lib.gsd_mesh_icp_lm_update(C.byref(lm), 3, state.data_ptr(), lam.data_ptr(), row.data_ptr(), t_state.data_ptr(), t_row.data_ptr(),
+                                        trace.data_ptr(), accepted.data_ptr(), last.data_ptr(), L.stream_ptr()) == L.GSD_OK
+    same = lambda got, want: np.array_equal(got.cpu().numpy().reshape(-1).view(np.int64), np.asarray(want, np.float64).reshape(-1).view(np.int64))
+    for i in range(3):
+        s, nxt, step = M.lm_update({"T": T0[i], "lam": float(lam0[i]), "row": cur[i], "accepted": 5}, T1[i], trial[i], max_step=max_step)
+        assert s["accepted"] == int(accepted[i]) == (5 if i == 1 else 6), i
+        assert same(state[i], s["T"]) and same(lam[i], s["lam"]) and same(row[i], s["row"]) and same(trace[i], s["row"][0]), i
+        assert same(last[i], step) and same(t_state[i], nxt), (i, last[i].cpu().numpy(), step)
+        if i == 0:
+            assert not step.any() and same(t_state[i], T1[i])
+        if i == 2:
+            assert np.array_equal(step, max_step)

@@ -256,3 +256,26 @@ def test_refusals_raise_the_package_error_and_write_nothing():
     # validate=False never reads the widths back: the refused sample is NaN, the others are rendered
     got = render_depth(grid, poses, widths, (24, 31), 12.0, validate=False)
     assert bool(torch.isnan(got[2]).all()) and bool(torch.isfinite(got[:2]).all()) and got[:2].min() < 0
+
+
+# ---- the cell lists -----------------------------------------------------------------------------------------------------------
+# cells per axis at 1 mm: one cell, then the counts around the multiples 4096 and 8192 of the scan's pass of 2048 counts: one short
+# of two passes, exactly two, one count in a third pass, two counts in a fifth (8193 = 3 * 2731 needs an axis of 2731 cells, more
+# than the 2048 allowed: 8194 is the nearest count above 8192)
+@pytest.mark.parametrize("nx, ny, ncells", ((1, 1, 1), (63, 65, 4095), (64, 64, 4096), (17, 241, 4097), (34, 241, 8194)))
+def test_cell_lists_across_the_scan_pass_boundary(nx, ny, ncells, monkeypatch):
+    from gelslim_depth_amd.mesh_depth import MeshGrid
+    monkeypatch.delenv("GSD_MESH_CELL_MM", raising=False)
+    tri = R.cell_list_mesh((4, nx, ny))          # "+y+z": x is the perpendicular axis, the grid's x runs along y, its y along z
+    one = MeshGrid(tri, 1.0, "+y+z", "cuda:0", cell_mm=1000.0)
+    assert one.shape == (1, 1)
+    listed = np.sort(one.list.cpu().numpy())
+    # the two faces seen face-on and the three tilted triangles; the eight walls seen edge-on and the degenerate one are skipped
+    assert np.array_equal(listed, np.nonzero(one.records[:, 9].cpu().numpy() != 0)[0]) and listed.tolist() == [0, 1, 2, 3, 13, 14, 15]
+    grid = MeshGrid(tri, 1.0, "+y+z", "cuda:0", cell_mm=1.0)
+    assert grid.shape == (ny, nx) and nx * ny == ncells
+    g = grid.grid
+    lo, hi = R.grid_cell_ranges(grid.records.cpu().numpy(), g.x0, g.y0, g.inv_cell, nx, ny)
+    cells = grid.cells.cpu().numpy()
+    R.check_cell_lists(cells, grid.list.cpu().numpy(), grid.pairs, (nx, ny), len(tri), listed, lo, hi)
+    assert ncells == 1 or len(np.unique(np.diff(cells[2:2 + ncells + 1]))) >= 3      # the counts differ from cell to cell

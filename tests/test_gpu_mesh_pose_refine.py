@@ -394,3 +394,57 @@ def test_estimate_pose_refines_its_winner():
     wide = md().estimate_pose(grid, observed, torch.tensor([PW.start_width(case)], device=DEV), P.case_start(case), case["half_span"], (5, 5, 7), 2,
                               None, "mse", case["height_mm"], width_half_span=PW.WIDTH_HALF_SPAN, width_count=PW.WIDTH_COUNT, refine_iterations=6)
     assert bool((wide.cost <= wide.lattice_cost).all()) and wide.refinement.last_step.shape == (1, 4)          # the width axis frees the width
+
+
+def test_lm_update_edge_rows_equal_the_twin_bit_for_bit():
+    """Three problems in one call, every parameter free: (0) an accepted trial whose matrix is singular in theta -- the gate gives
+    the step 0 and the next trial is the state; (1) a NaN trial cost -- not accepted, the step comes from the old row, unclipped;
+    (2) an accepted trial whose right-hand side is so large that the clip binds in every component.  The kernel's arithmetic is
+    + - * / and sqrt in lm_update_ref's order: every output is compared bit for bit."""
+    from gelslim_depth_amd import _lib as L
+    rng = np.random.Generator(np.random.PCG64(33))
+    max_step = (0.5, 0.5, 0.1, 0.5)
+    cur = np.stack([spd_row(rng)[0] for _ in range(3)])
+    trial = np.stack([spd_row(rng)[0] for _ in range(3)])
+    cur[1, 2:6] *= 1e-2
+    trial[2, 2:6] *= 1e6
+    trial[0, 0], trial[1, 0], trial[2, 0] = 0.5 * cur[0, 0], np.nan, 0.5 * cur[2, 0]
+    for q, (j, k) in enumerate(PR.PAIRS):
+        if 2 in (j, k):
+            trial[0, 6 + q] = 0.0
+    trial[0, 2 + 2] = 0.0
+    lam0 = np.array([1e-3, 0.25, 5e-12])
+    free, _ = PR.lm_solve(cur[1], lam0[1] * 10.0, 15, (np.inf,) * 4)
+    assert (np.abs(free) < np.asarray(max_step)).all() and free.all()
+    free, _ = PR.lm_solve(trial[2], 1e-12, 15, (np.inf,) * 4)
+    assert (np.abs(free) > np.asarray(max_step)).all()
+    pose0 = (rng.uniform(-1, 1, (3, 3)) * np.array([1e-3, 1e-3, 1.0])).astype(np.float32)
+    pose1 = (pose0 + rng.uniform(-1, 1, (3, 3)).astype(np.float32) * np.float32(1e-4)).astype(np.float32)
+    width0 = rng.uniform(4, 6, 3).astype(np.float32)
+    width1 = (width0 + np.float32(0.01)).astype(np.float32)
+    lm = L.gsd_pose_lm()
+    lm.down, lm.up, lm.lambda_min, lm.lambda_max, lm.free_mask, lm.first = 0.1, 10.0, 1e-12, 1e12, 15, 0
+    lm.max_step[:] = max_step
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    pose, width, lam, row = dev(pose0), dev(width0), dev(lam0), dev(cur)
+    t_pose, t_width, t_row = dev(pose1), dev(width1), dev(trial)
+    trace = torch.zeros(3, dtype=torch.float64, device=DEV)
+    accepted = torch.full((3,), 5, dtype=torch.int32, device=DEV)
+    last = torch.zeros((3, 4), dtype=torch.float64, device=DEV)
+    assert L.lib.gsd_mesh_pose_lm_update(C.byref(lm), 3, pose.data_ptr(), width.data_ptr(), lam.data_ptr(), row.data_ptr(), t_pose.data_ptr(),
+                                         t_width.data_ptr(), t_row.data_ptr(), trace.data_ptr(), accepted.data_ptr(), last.data_ptr(),
+                                         L.stream_ptr()) == L.GSD_OK
+    host = lambda t: t.cpu().numpy()
+    same = lambda t, want: same_bits(t.cpu().reshape(-1), torch.from_numpy(np.asarray(want, np.float64).reshape(-1)))
+    for i in range(3):
+        st = {"pose": pose0[i].copy(), "width": width0[i], "lam": float(lam0[i]), "row": cur[i].copy(), "accepted": 5}
+        nxt, nxt_width, dl, took = PR.lm_update_ref(st, pose1[i], width1[i], trial[i], 15, max_step=max_step)
+        assert took == (i != 1) and int(accepted[i]) == st["accepted"] == (5 if i == 1 else 6), i
+        assert np.array_equal(host(pose[i]), st["pose"]) and host(width[i]) == st["width"] and host(lam[i]) == st["lam"], i
+        assert same(row[i], st["row"]) and same(trace[i], st["row"][0]), i
+        assert same(last[i], np.abs(dl)), (i, host(last[i]), dl)
+        assert np.array_equal(host(t_pose[i]), nxt) and host(t_width[i]) == nxt_width, i
+        if i == 0:
+            assert not dl.any() and np.array_equal(nxt, st["pose"]) and nxt_width == st["width"]
+        if i == 2:
+            assert np.array_equal(np.abs(dl), max_step)

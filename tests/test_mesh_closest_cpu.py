@@ -218,3 +218,27 @@ def test_the_twin_registration_converges_on_the_gpu_cases():
         if D is not None:      # the limit is what recovers the motion: without it the outliers drag the fit five times as far off
             free = M.register(tri, cloud, None, 20, None, kind)
             assert M.corner_gap(free["matrix"] @ M.T0, np.eye(4), tri) > 3 * want_err and err < 0.05
+
+
+def test_registration_kernels_use_no_scratch():
+    """The 6 x 6 system of mesh_icp_lm_update (gsd_lm_solve<6>) is indexed by constants only and the 30 sums of mesh_icp_rows_sum
+    stay in registers: neither kernel has scratch or LDS (device-only compile, a few seconds)."""
+    import re
+    import shutil
+    import subprocess
+    from gelslim_depth_amd import build as b
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+        pytest.skip("no hipcc on this machine")
+    r = subprocess.run([hipcc] + b.CFLAGS + [f"-I{b.INCLUDE}", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
+                        os.path.join(b.CSRC, "gsd_mesh_closest.hip"), "-o", os.devnull], capture_output=True, text=True, check=True)
+    names = re.findall(r"Function Name: (\S+)", r.stderr)
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
+    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)]
+    assert len(names) == len(scratch) == len(lds)
+    got = {}
+    for key in ("mesh_icp_lm_update", "mesh_icp_rows_sum", "mesh_volume_scan"):
+        hits = [(s, m) for n, s, m in zip(names, scratch, lds) if re.search(rf"\d{key}E", n)]
+        assert len(hits) == 1, (key, names)
+        got[key] = hits[0]
+    assert got == {"mesh_icp_lm_update": (0, 0), "mesh_icp_rows_sum": (0, 0), "mesh_volume_scan": (0, 16 * 8)}, got
